@@ -14,6 +14,12 @@ One step = detector.run_batch(images): backbone + DCN + heads + fused sigmoid / 
 top-K decode over one device-resident batch -- the same entry point in warm-up and in the
 timed loop.  Images shard over ranks (weak scaling, no collective in the loop); rank 0
 broadcasts the flat weight buffer once at start-up over RCCL.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times --steps steps and prints the headline.  --full adds every
+other figure and check (box calibration, per-class rooflines from events inside the timed loop,
+precision check, fp32 and untracked legs, clock under load, batch 1, configs[2..4], CPU baseline,
+cross-rank agreement).  --dump-outputs DIR writes the last timed step's detections; inputs and
+weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -220,7 +226,15 @@ def parse(argv=None):
     p.add_argument("--no-secondary", action="store_true",
                    help="skip the short runs of BASELINE configs[2..4] behind the headline loop")
     p.add_argument("--secondary-steps", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beyond the headline: box calibration, per-class "
+                        "rooflines, precision check, fp32 / untracked legs, batch 1, BASELINE configs[2..4], "
+                        "CPU baseline, cross-rank agreement")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the detections of the last timed step to DIR/detections.npy (float32)")
     a = p.parse_args(argv)
+    if a.per_op and not a.full:
+        p.error("--per-op needs --full")
     cfg = CONFIGS[a.config]
     for k, v in cfg.items():
         if getattr(a, k) is None:
@@ -658,7 +672,7 @@ def main():
     # here would mean the calibration is broken -- never time a run that is not range-clean
     assert det.range_ok(images), "f32s range check failed during warm-up"
     agreement = None
-    if dist is not None:
+    if dist is not None and a.full:
         # every rank calibrated its f32s exponents on ITS OWN images: one shared batch through all
         # replicas must still give the same detections (scores within 1e-4) behind the broadcast
         shared = synth.images(B, a.res, a.res, seed=99).to(dev)
@@ -669,15 +683,16 @@ def main():
         agreement = cross_rank_agreement([g.cpu() for g in gathered])
         assert agreement["ok"], "replicas disagree on a shared batch: %r" % (agreement,)
         assert det.range_ok(shared), "f32s range check failed on the shared batch"
-    calib = box_calibration(dev) if (rank == 0 and not stub) else None
+    calib = box_calibration(dev) if (a.full and rank == 0 and not stub) else None
     if dist is not None:
         dist.barrier()
     sync()
 
     plan = det.model.plan_for(B, a.res, a.res, dev)
-    # HIP events on the launch stream, inside the timed region.  A marker after every launch
+    # --full: HIP events on the launch stream, inside the timed region.  A marker after every launch
     # costs ~7 us of bubble each, so by default events sit only where the kernel class changes
-    # (the per-class sums stay exact); --per-op records one after every launch.
+    # (the per-class sums stay exact); --per-op records one after every launch.  A plain run
+    # records none.
     metas = plan.b.meta
     nops = len(metas)
     if a.per_op:
@@ -689,7 +704,7 @@ def main():
     probes = []
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        probe = {"event_after": bset}
+        probe = {"event_after": bset} if a.full else None
         dets = det.run_batch(images, probe=probe)    # same entry point as the warm-up
         probes.append(probe)
     # inside the timed region: the (synchronising) look at the f32s range words of all K steps
@@ -714,8 +729,15 @@ def main():
 
     if not range_clean:
         raise SystemExit("bench.py: an f32s forward clamped a value inside the timed region")
+    if a.dump_outputs:
+        # what the caller of the timed path receives from its last step: (B, K, 6) ctdet / (B, K, 40)
+        # multi_pose detections of this rank's batch (seeded images and weights: identical inputs per run)
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        name = "detections.npy" if rank == 0 else "detections_rank%d.npy" % rank
+        np.save(os.path.join(a.dump_outputs, name), dets.detach().float().cpu().numpy())
     clock = None
-    if rank == 0 and not stub:
+    if a.full and rank == 0 and not stub:
         # the shader clock WHILE the step runs: one spinning lane on a side stream counts core cycles
         # (s_memtime) against the constant 100 MHz clock for about two steps, with untimed steps of the
         # same loop on the launch stream around it -- and the same probe on the resting part.  What power
@@ -766,7 +788,7 @@ def main():
                  "what": "s_memtime cycles of one spinning lane over two steps (side stream, steps running "
                          "on the launch stream) / over 30 us after 0.5 s of rest, against the constant 100 MHz clock"}
     fp32_leg = None
-    if rank == 0 and not a.fp16 and not a.fp32_mfma and not a.no_fp32_leg and not stub:
+    if a.full and rank == 0 and not a.fp16 and not a.fp32_mfma and not a.no_fp32_leg and not stub:
         # the same step on the plain fp32 matrix instruction (v_mfma_f32_32x32x2_f32), a few
         # steps, so that the headline is never ambiguous about what the f32s arithmetic buys
         det.model.fp32_mfma(True)
@@ -783,7 +805,7 @@ def main():
                     "ms_per_step": leg_dt / n_leg * 1e3, "dtype": "f32"}
         det.model.fp32_mfma(None)
     track_leg = None
-    if rank == 0 and not a.fp16 and not a.fp32_mfma and not a.no_fp32_leg and not stub:
+    if a.full and rank == 0 and not a.fp16 and not a.fp32_mfma and not a.no_fp32_leg and not stub:
         # the same step with the range words compiled out of the plan (NULL range pointers: no
         # running maxima, no per-wave atomics, no fold launch) against the tracked plan, back to
         # back in this process: what "nothing saturates silently" costs on this box
@@ -806,74 +828,8 @@ def main():
                      "note": "untracked plans clamp silently: measurement only"}
     if rank == 0:
         plan = det.model.plan_for(B, a.res, a.res, dev)     # (the legs above rebuilt the plans)
-        # ---- per-kernel-class time from the HIP events recorded inside the timed region
-        kinds = {}
-        for pr in probes:
-            evs = pr["net_events"]
-            for si, (first, last) in enumerate(zip(seg_first, bounds)):
-                ms = evs[si].elapsed_time(evs[si + 1])
-                k = kinds.setdefault(metas[first]["kind"], {"ms": 0.0, "flops": 0, "bytes": 0, "launches": 0})
-                k["ms"] += ms
-                for m in metas[first:last + 1]:
-                    k["flops"] += m["flops"]; k["bytes"] += m["bytes"]; k["launches"] += 1
-        if a.per_op:
-            for i, m in enumerate(plan.b.meta):
-                ms = sum(pr["net_events"][i].elapsed_time(pr["net_events"][i + 1]) for pr in probes) / a.steps
-                kind, act = plan.b.trace[i]
-                if act is None:
-                    continue
-                print("op %2d %-7s out(B,H,W,C)=(%d,%d,%d,%d) %8.3f ms  %7.2f TF/s  %7.1f GB/s" % (
-                    i, kind, act.B, act.H, act.W, act.C, ms, m["flops"] / ms / 1e9 if ms else 0,
-                    m["bytes"] / ms / 1e6 if ms else 0), file=sys.stderr)
-        dec_ms = sum(pr["dec_events"][0].elapsed_time(pr["dec_events"][1]) for pr in probes)
-        Ho = a.res // 4
-        if a.task == "ctdet":   # hm + wh + reg read once, (K,6) written
-            dec_bytes = B * (opt.num_classes * Ho * Ho * 4 + 2 * 2 * Ho * Ho * 4 + opt.K * 6 * 4)
-        else:                   # hm 1 + wh 2 + hps 34 + reg 2 + hm_hp 17 + hp_offset 2, (K,40)
-            dec_bytes = B * ((1 + 2 + 34 + 2 + 17 + 2) * Ho * Ho * 4 + opt.K * 40 * 4)
-        kinds["decode"] = {"ms": dec_ms, "flops": 0, "bytes": dec_bytes * a.steps,
-                           "launches": DECODE_LAUNCHES["ctdet_large" if a.task == "ctdet" and Ho > 128
-                                                       else a.task] * a.steps}
-        dom = max(kinds, key=lambda k: kinds[k]["ms"])
         standard = (a.res == 512 and not a.tune and not a.fp32_mfma and
                     all(getattr(a, k) == v for k, v in CONFIGS[a.config].items()))
-        pmc, pmc_file = pmc_traffic("cfg%d" % a.config) if standard else ({}, None)
-        pmc_stale = pmc.pop("_stale", None)
-
-        def traffic(k):
-            # measured HBM bytes per launch of this kernel class (committed PMC profile of the
-            # same command), or null when no profile covers this configuration
-            if k not in pmc:
-                return None
-            byts, launches = pmc[k]
-            return byts / max(launches, 1)
-
-        def roof(k, bound):
-            s = kinds[k]
-            sec = s["ms"] * 1e-3
-            if bound == "mfma":
-                ach = s["flops"] / sec / 1e12 if sec > 0 else 0.0
-                peak = F16_MFMA_PEAK_TF if a.fp16 else (F32_MFMA_PEAK_TF if a.fp32_mfma else F32S_MFMA_PEAK_TF)
-                unit = "TFLOP/s"
-            else:
-                ach = s["bytes"] / sec / 1e9 if sec > 0 else 0.0
-                peak, unit = HBM_PEAK_GBS, "GB/s"
-            tr, alg = traffic(k), s["bytes"] / max(s["launches"], 1)
-            note = None
-            if tr is not None and tr < alg:
-                note = ("measured HBM bytes below the algorithmic count: " + (
-                    "the algorithmic figure charges every decode input map as read once (SURVEY 8d), "
-                    "but only the heat-maps are streamed -- wh / reg / hps / hp_offset are gathered at the "
-                    "K selected cells (a few 32-byte sectors each)" if k == "decode" else
-                    "consecutive launches hand small tensors and the weights over through L2 / the 256 MB "
-                    "Infinity Cache (written, not yet evicted, read again), so fewer bytes reach HBM than a "
-                    "per-launch count of inputs + outputs assumes"))
-            return {"kernel": k, "bound": bound, "achieved": ach, "peak": peak, "unit": unit,
-                    "frac": ach / peak, "traffic": tr, "traffic_note": note,
-                    "algorithmic_bytes_per_launch": s["bytes"] / max(s["launches"], 1),
-                    "avg_launch_ms": s["ms"] / max(s["launches"], 1),
-                    "launches_per_step": s["launches"] // a.steps}
-
         total_imgs = B * a.steps * world
         if a.fp16:
             compute_dtype = "f16"
@@ -899,73 +855,143 @@ def main():
             "rank_devices": rank_devices,
             "backend": ("%s (RCCL over xGMI)" % backend if backend == "nccl" else backend) if dist is not None else None,
             "weight_broadcast_bytes": bcast_bytes, "weight_broadcast_ms": bcast_ms,
-            "per_rank_img_s": per_rank_rate, "cross_rank_agreement": agreement,
-            "box_calibration": calib,
-            "headline_over_calibration": None if not calib else {
-                "img_s_per_mfma_TFLOPs": total_imgs / dt / world / calib["mfma_f16_TFLOPs"],
-                "img_s_per_copy_TBs": total_imgs / dt / world / calib["copy_TBs"]},
-            "range_tracking_off_leg": track_leg,
-            "clock_under_load": clock,
-            "roofline": roof(dom, "mfma" if kinds[dom]["flops"] > 0 else "hbm"),
-            "roofline_dcn_mfma": roof("dcn", "mfma") if "dcn" in kinds else None,
-            "roofline_dcn_hbm": roof("dcn", "hbm") if "dcn" in kinds else None,
-            "roofline_decode_hbm": roof("decode", "hbm"),
-            "dominant_launch": None if stub else dominant_launch(
-                det, images, plan, 5,
-                F16_MFMA_PEAK_TF if a.fp16 else (F32_MFMA_PEAK_TF if a.fp32_mfma else F32S_MFMA_PEAK_TF),
-                a.config),
-            "pmc_profile": pmc_file,
-            "pmc_profile_head": None if pmc_file is None else (pmc_stale[0] if pmc_stale else kernel_tree_sha()),
-            "kernel_tree_head": kernel_tree_sha(),
-            "pmc_profile_stale": bool(pmc_stale),
-            "traffic_source": None if pmc_file is None else
-            ("REFUSED: profiles/%s was taken on kernel sources %s, this run is %s -- traffic is null until the "
-             "PMC passes are re-taken (tools/profile_round.sh)" % (pmc_file, pmc_stale[0], pmc_stale[1])) if pmc_stale else
-            "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, committed as profiles/%s "
-            "(counters cannot be read from inside the run)" % pmc_file,
-            "precision_check": precision_check(dev) if not (a.fp16 or stub) else None,
-            "fp32_mfma_leg": fp32_leg,
+            "per_rank_img_s": per_rank_rate,
             "f32s_range": None if (a.fp16 or a.fp32_mfma) else {
                 "clean": bool(range_clean),
                 "calibrations": det.model.__dict__.get("_calibrations", 0),
                 "policy": "per-tensor power-of-two exponents from one fp32 calibration pass; every "
                           "split site max-es |value| into range words, read inside the timed region"},
-            "time_share": {k: round(v["ms"] / (dt * 1e3), 4) for k, v in kinds.items()},
         }
-        if world == 1 and standard and a.config == 1 and not a.no_secondary and not stub:
-            # the reference's own operating point -- ONE image per step (src/test.py:60-62, MODEL_ZOO: 7 ms on a
-            # TITAN Xp for this network) -- on the headline's detector: det.run_batch on a batch of one, the same
-            # entry point, no markers inside the loop
-            try:
-                one = synth.images(1, a.res, a.res, seed=7).to(dev)
-                for _ in range(10):
-                    det.run_batch(one)
-                torch.cuda.synchronize()
-                assert det.range_ok(one), "f32s range check failed at batch 1"
-                n1 = 100
-                t1 = time.perf_counter()
-                for _ in range(n1):
-                    det.run_batch(one)
-                ok1 = det.range_ok()
-                torch.cuda.synchronize()
-                b1 = (time.perf_counter() - t1) / n1 * 1e3
-                res["batch_1"] = {"b1_ms_per_step": b1, "img_s": 1e3 / b1, "steps": n1, "range_clean": bool(ok1),
-                                  "what": "network + decode for ONE 512x512 image per step (device-resident input), "
-                                          "launches per step %d" % (len(det.model.plan_for(1, a.res, a.res, dev).b.ops) + 1)}
-            except Exception as e:
-                res["batch_1"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-            # BASELINE configs[2..4], a few steps each, behind the headline loop (never inside it)
-            sec = {}
-            for cid in (2, 3, 4):
+        if a.full:
+            # ---- per-kernel-class time from the HIP events recorded inside the timed region
+            kinds = {}
+            for pr in probes:
+                evs = pr["net_events"]
+                for si, (first, last) in enumerate(zip(seg_first, bounds)):
+                    ms = evs[si].elapsed_time(evs[si + 1])
+                    k = kinds.setdefault(metas[first]["kind"], {"ms": 0.0, "flops": 0, "bytes": 0, "launches": 0})
+                    k["ms"] += ms
+                    for m in metas[first:last + 1]:
+                        k["flops"] += m["flops"]; k["bytes"] += m["bytes"]; k["launches"] += 1
+            if a.per_op:
+                for i, m in enumerate(plan.b.meta):
+                    ms = sum(pr["net_events"][i].elapsed_time(pr["net_events"][i + 1]) for pr in probes) / a.steps
+                    kind, act = plan.b.trace[i]
+                    if act is None:
+                        continue
+                    print("op %2d %-7s out(B,H,W,C)=(%d,%d,%d,%d) %8.3f ms  %7.2f TF/s  %7.1f GB/s" % (
+                        i, kind, act.B, act.H, act.W, act.C, ms, m["flops"] / ms / 1e9 if ms else 0,
+                        m["bytes"] / ms / 1e6 if ms else 0), file=sys.stderr)
+            dec_ms = sum(pr["dec_events"][0].elapsed_time(pr["dec_events"][1]) for pr in probes)
+            Ho = a.res // 4
+            if a.task == "ctdet":   # hm + wh + reg read once, (K,6) written
+                dec_bytes = B * (opt.num_classes * Ho * Ho * 4 + 2 * 2 * Ho * Ho * 4 + opt.K * 6 * 4)
+            else:                   # hm 1 + wh 2 + hps 34 + reg 2 + hm_hp 17 + hp_offset 2, (K,40)
+                dec_bytes = B * ((1 + 2 + 34 + 2 + 17 + 2) * Ho * Ho * 4 + opt.K * 40 * 4)
+            kinds["decode"] = {"ms": dec_ms, "flops": 0, "bytes": dec_bytes * a.steps,
+                               "launches": DECODE_LAUNCHES["ctdet_large" if a.task == "ctdet" and Ho > 128
+                                                           else a.task] * a.steps}
+            dom = max(kinds, key=lambda k: kinds[k]["ms"])
+            pmc, pmc_file = pmc_traffic("cfg%d" % a.config) if standard else ({}, None)
+            pmc_stale = pmc.pop("_stale", None)
+
+            def traffic(k):
+                # measured HBM bytes per launch of this kernel class (committed PMC profile of the
+                # same command), or null when no profile covers this configuration
+                if k not in pmc:
+                    return None
+                byts, launches = pmc[k]
+                return byts / max(launches, 1)
+
+            def roof(k, bound):
+                s = kinds[k]
+                sec = s["ms"] * 1e-3
+                if bound == "mfma":
+                    ach = s["flops"] / sec / 1e12 if sec > 0 else 0.0
+                    peak = F16_MFMA_PEAK_TF if a.fp16 else (F32_MFMA_PEAK_TF if a.fp32_mfma else F32S_MFMA_PEAK_TF)
+                    unit = "TFLOP/s"
+                else:
+                    ach = s["bytes"] / sec / 1e9 if sec > 0 else 0.0
+                    peak, unit = HBM_PEAK_GBS, "GB/s"
+                tr, alg = traffic(k), s["bytes"] / max(s["launches"], 1)
+                note = None
+                if tr is not None and tr < alg:
+                    note = ("measured HBM bytes below the algorithmic count: " + (
+                        "the algorithmic figure charges every decode input map as read once (SURVEY 8d), "
+                        "but only the heat-maps are streamed -- wh / reg / hps / hp_offset are gathered at the "
+                        "K selected cells (a few 32-byte sectors each)" if k == "decode" else
+                        "consecutive launches hand small tensors and the weights over through L2 / the 256 MB "
+                        "Infinity Cache (written, not yet evicted, read again), so fewer bytes reach HBM than a "
+                        "per-launch count of inputs + outputs assumes"))
+                return {"kernel": k, "bound": bound, "achieved": ach, "peak": peak, "unit": unit,
+                        "frac": ach / peak, "traffic": tr, "traffic_note": note,
+                        "algorithmic_bytes_per_launch": s["bytes"] / max(s["launches"], 1),
+                        "avg_launch_ms": s["ms"] / max(s["launches"], 1),
+                        "launches_per_step": s["launches"] // a.steps}
+
+            res.update({
+                "cross_rank_agreement": agreement,
+                "box_calibration": calib,
+                "headline_over_calibration": None if not calib else {
+                    "img_s_per_mfma_TFLOPs": total_imgs / dt / world / calib["mfma_f16_TFLOPs"],
+                    "img_s_per_copy_TBs": total_imgs / dt / world / calib["copy_TBs"]},
+                "range_tracking_off_leg": track_leg,
+                "clock_under_load": clock,
+                "roofline": roof(dom, "mfma" if kinds[dom]["flops"] > 0 else "hbm"),
+                "roofline_dcn_mfma": roof("dcn", "mfma") if "dcn" in kinds else None,
+                "roofline_dcn_hbm": roof("dcn", "hbm") if "dcn" in kinds else None,
+                "roofline_decode_hbm": roof("decode", "hbm"),
+                "dominant_launch": None if stub else dominant_launch(
+                    det, images, plan, 5,
+                    F16_MFMA_PEAK_TF if a.fp16 else (F32_MFMA_PEAK_TF if a.fp32_mfma else F32S_MFMA_PEAK_TF),
+                    a.config),
+                "pmc_profile": pmc_file,
+                "pmc_profile_head": None if pmc_file is None else (pmc_stale[0] if pmc_stale else kernel_tree_sha()),
+                "kernel_tree_head": kernel_tree_sha(),
+                "pmc_profile_stale": bool(pmc_stale),
+                "traffic_source": None if pmc_file is None else
+                ("REFUSED: profiles/%s was taken on kernel sources %s, this run is %s -- traffic is null until the "
+                 "PMC passes are re-taken (tools/profile_round.sh)" % (pmc_file, pmc_stale[0], pmc_stale[1])) if pmc_stale else
+                "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, committed as profiles/%s "
+                "(counters cannot be read from inside the run)" % pmc_file,
+                "precision_check": precision_check(dev) if not (a.fp16 or stub) else None,
+                "fp32_mfma_leg": fp32_leg,
+                "time_share": {k: round(v["ms"] / (dt * 1e3), 4) for k, v in kinds.items()},
+            })
+            if world == 1 and standard and a.config == 1 and not a.no_secondary and not stub:
+                # the reference's own operating point -- ONE image per step (src/test.py:60-62, MODEL_ZOO: 7 ms on a
+                # TITAN Xp for this network) -- on the headline's detector: det.run_batch on a batch of one, the same
+                # entry point, no markers inside the loop
                 try:
-                    sec["configs[%d]" % cid] = secondary_config(cid, a.res, a.secondary_steps, dev)
-                except Exception as e:      # a secondary leg must never cost the headline line
-                    sec["configs[%d]" % cid] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-            res["secondary_configs"] = sec
-        if world == 1 and not a.no_cpu_baseline and not stub:
-            sd = {k: v.detach().cpu() for k, v in det.model.state_dict().items()}
-            res["cpu_baseline"] = cpu_baseline(a.task, a.arch, sd, list(opt.heads), a.res,
-                                               a.cpu_seconds)
+                    one = synth.images(1, a.res, a.res, seed=7).to(dev)
+                    for _ in range(10):
+                        det.run_batch(one)
+                    torch.cuda.synchronize()
+                    assert det.range_ok(one), "f32s range check failed at batch 1"
+                    n1 = 100
+                    t1 = time.perf_counter()
+                    for _ in range(n1):
+                        det.run_batch(one)
+                    ok1 = det.range_ok()
+                    torch.cuda.synchronize()
+                    b1 = (time.perf_counter() - t1) / n1 * 1e3
+                    res["batch_1"] = {"b1_ms_per_step": b1, "img_s": 1e3 / b1, "steps": n1, "range_clean": bool(ok1),
+                                      "what": "network + decode for ONE 512x512 image per step (device-resident input), "
+                                              "launches per step %d" % (len(det.model.plan_for(1, a.res, a.res, dev).b.ops) + 1)}
+                except Exception as e:
+                    res["batch_1"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+                # BASELINE configs[2..4], a few steps each, behind the headline loop (never inside it)
+                sec = {}
+                for cid in (2, 3, 4):
+                    try:
+                        sec["configs[%d]" % cid] = secondary_config(cid, a.res, a.secondary_steps, dev)
+                    except Exception as e:      # a secondary leg must never cost the headline line
+                        sec["configs[%d]" % cid] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+                res["secondary_configs"] = sec
+            if world == 1 and not a.no_cpu_baseline and not stub:
+                sd = {k: v.detach().cpu() for k, v in det.model.state_dict().items()}
+                res["cpu_baseline"] = cpu_baseline(a.task, a.arch, sd, list(opt.heads), a.res,
+                                                   a.cpu_seconds)
         print(json.dumps(res))
         sys.stdout.flush()
     if dist is not None:

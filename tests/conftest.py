@@ -40,7 +40,9 @@ def decode_golden():
 
 @pytest.fixture(scope="session")
 def net_golden():
-    z = np.load(os.path.join(GOLDEN, "net_golden.npz"))
+    z = {}
+    for name in ("net_golden.npz", "net_golden_2.npz"):     # split: each file below 1 MiB
+        z.update(np.load(os.path.join(GOLDEN, name)))
     with open(os.path.join(GOLDEN, "net_golden.json")) as f:
         meta = json.load(f)
     return z, meta

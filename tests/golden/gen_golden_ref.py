@@ -2,7 +2,8 @@
 (DCNv2/src/cuda/dcn_v2_im2col_cuda.cu, host build) and soft-NMS (external/nms.pyx, cython) --
 so the pin survives where /root/reference (and hence `make -C oracle _ref`) is not available.
 
-    python tests/golden/gen_golden_ref.py        # needs oracle/_ref built -> ref_golden.npz
+    python tests/golden/gen_golden_ref.py            # needs oracle/_ref built -> ref_golden.npz
+    python tests/golden/gen_golden_ref.py --digests  # -> ref_digests.json (tests/test_oracle_ref.py)
 
 Inputs are regenerated from seeds by the tests (dcn_inputs / nms_inputs below); only outputs are
 stored: the full forward output and every COL_STRIDE-th column entry of sample 0.
@@ -72,6 +73,14 @@ def nms_inputs(ncol, seed, n=80):
 def main():
     from oracle import ref
     assert ref.build(), "oracle/_ref could not be built (needs /root/reference)"
+    if "--digests" in sys.argv[1:]:
+        # tests/test_oracle_ref.py in recording mode: every case's live reference output -> its SHA-256
+        import subprocess
+        subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider",
+                               os.path.join(ROOT, "tests", "test_oracle_ref.py")],
+                              cwd=ROOT, env=dict(os.environ, CN_RECORD_REF_DIGESTS="1"))
+        print("wrote", os.path.join(os.path.dirname(OUT), "ref_digests.json"))
+        return
     out = {}
     for name, c in DCN_CASES.items():
         x, off, mask, w, b, kw = dcn_inputs(c)

@@ -1,6 +1,8 @@
 """Dataset descriptors (centernet_amd/datasets.py, CPU only): what test.py reads off ``dataset_factory
 [opt.dataset]`` -- against the attributes of the reference's own dataset classes (imported from where they
-lie when /root/reference is present; the values are also spelled out here) and the result-writer goldens."""
+lie when the reference tree is present, and always as recorded from them in tests/golden/datasets_golden.json by
+tests/golden/gen_golden_datasets.py; the values are also spelled out here) and the result-writer goldens."""
+import ast
 import importlib.util
 import json
 import os
@@ -15,6 +17,9 @@ from centernet_amd.opts import opts
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference/src/lib/datasets/dataset"
+DATASETS_GOLDEN = os.path.join(HERE, "golden", "datasets_golden.json")
+REF_CLASSES = [("coco", "coco.py", "COCO"), ("coco_hp", "coco_hp.py", "COCOHP"),
+               ("pascal", "pascal.py", "PascalVOC"), ("kitti", "kitti.py", "KITTI")]
 
 
 def _gen():
@@ -37,10 +42,9 @@ def test_factory_and_the_values_the_detectors_use():
     assert D.KITTI.class_name[1:] == ["Pedestrian", "Car", "Cyclist"] and D.PascalVOC.class_name[15] == "person"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
-@pytest.mark.parametrize("name,file,cls", [("coco", "coco.py", "COCO"), ("coco_hp", "coco_hp.py", "COCOHP"),
-                                           ("pascal", "pascal.py", "PascalVOC"), ("kitti", "kitti.py", "KITTI")])
-def test_class_attributes_equal_the_reference(name, file, cls):
+def reference_attrs(name, file, cls):
+    """The attributes the detectors read off the reference's dataset class ``cls`` (imported from REF), and
+    the class-name list its constructor assigns (read from its source)."""
     stub = types.ModuleType("pycocotools")
     stub.coco = types.ModuleType("pycocotools.coco")
     stub.cocoeval = types.ModuleType("pycocotools.cocoeval")
@@ -59,18 +63,39 @@ def test_class_attributes_equal_the_reference(name, file, cls):
                 sys.modules.pop(k, None)
             else:
                 sys.modules[k] = v
-    ref, mine = getattr(mod, cls), D.dataset_factory[name]
-    for attr in ("num_classes", "default_resolution"):
-        assert getattr(ref, attr) == getattr(mine, attr), attr
+    ref = getattr(mod, cls)
+    out = {"num_classes": ref.num_classes, "default_resolution": list(ref.default_resolution)}
     for attr in ("mean", "std"):
-        a, b = getattr(ref, attr), getattr(mine, attr)
+        a = getattr(ref, attr)
+        out[attr] = {"dtype": str(a.dtype), "shape": list(a.shape), "values": a.reshape(-1).tolist()}
+    if name == "coco_hp":
+        out["flip_idx"], out["num_joints"] = [list(p) for p in ref.flip_idx], ref.num_joints
+    # instance attributes of the reference (class names) from its constructor's source
+    with open(os.path.join(REF, file)) as f:
+        tree = ast.parse(f.read())
+    out["class_name"] = [ast.literal_eval(n.value) for n in ast.walk(tree) if isinstance(n, ast.Assign)
+                         and any(ast.unparse(t) == "self.class_name" for t in n.targets)]
+    return out
+
+
+@pytest.mark.parametrize("name,file,cls", REF_CLASSES)
+def test_class_attributes_equal_the_reference(name, file, cls):
+    with open(DATASETS_GOLDEN) as f:
+        ref = json.load(f)[name]
+    if os.path.isdir(REF):
+        assert reference_attrs(name, file, cls) == ref
+    mine = D.dataset_factory[name]
+    assert ref["num_classes"] == mine.num_classes
+    assert ref["default_resolution"] == list(mine.default_resolution)
+    for attr in ("mean", "std"):
+        b = getattr(mine, attr)
+        a = np.array(ref[attr]["values"], dtype=ref[attr]["dtype"]).reshape(ref[attr]["shape"])
         assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), attr
     if name == "coco_hp":
-        assert ref.flip_idx == mine.flip_idx and ref.num_joints == mine.num_joints
-    # instance attributes of the reference (class names, id maps) by reading its constructor's source
-    src = open(os.path.join(REF, file)).read()
+        assert ref["flip_idx"] == [list(p) for p in mine.flip_idx] and ref["num_joints"] == mine.num_joints
+    names = [c for lst in ref["class_name"] for c in lst]
     for cname in ([] if name == "coco_hp" else mine.class_name[1:]):      # (coco_hp.py names no classes: one, the person)
-        assert ("'%s'" % cname) in src or ('"%s"' % cname) in src, cname
+        assert cname in names, cname
 
 
 @pytest.mark.parametrize("task,dataset", [("ctdet", "coco"), ("ctdet", "pascal"), ("multi_pose", "coco_hp"),

@@ -26,7 +26,7 @@ def _bench(args, env_extra=None, timeout=900):
                     reason="needs two visible GPUs (RCCL, backend 'nccl')")
 def test_two_ranks_over_rccl():
     p, lines = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--no-secondary", "--no-cpu-baseline",
-                       "--no-fp32-leg"])
+                       "--no-fp32-leg", "--full"])
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1
     r = lines[0]

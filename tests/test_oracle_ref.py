@@ -8,10 +8,15 @@ against our restatements, bit for bit.
   * soft-NMS: external/nms.pyx:77-275 (cython) vs oracle/post_oracle.soft_nms and the product's
     cn_soft_nms_f32: kept count and the whole in-place array.
 
-Skipped when oracle/_ref was never built (needs /root/reference at build time); the committed
-fixtures tests/golden/ref_golden.npz (made from these libraries) keep the pin alive in that case
-(test_ref_fixtures_* below and tests/test_gpu_dcn.py).
+Where oracle/_ref was never built (it needs the reference tree at build time) every case is checked
+against the SHA-256 of the reference's output bits, recorded from these libraries in
+tests/golden/ref_digests.json (`python tests/golden/gen_golden_ref.py --digests`); where it is built,
+against the live output as well.  The committed fixtures tests/golden/ref_golden.npz pin the same
+libraries with stored outputs (test_ref_fixtures_* below and tests/test_gpu_dcn.py).
 """
+import atexit
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -20,7 +25,12 @@ import pytest
 from oracle import cref, post_oracle, ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-needs_ref = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built")
+DIGESTS = os.path.join(GOLDEN, "ref_digests.json")
+# set by `gen_golden_ref.py --digests`: record the live reference's digests instead of checking them
+_RECORD = os.environ.get("CN_RECORD_REF_DIGESTS") == "1"
+_recorded_now = {}
+if _RECORD:
+    atexit.register(lambda: json.dump(_recorded_now, open(DIGESTS, "w"), indent=1, sort_keys=True))
 
 # (Cin, H, W) of every distinct DCN layer input in resdcn_18 (resnet_dcn.py:149-153,221) and
 # dla_34 (pose_dla_dcn.py:360-413,437-443)
@@ -43,18 +53,40 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-@needs_ref
+def _digest(keep, arr):
+    h = hashlib.sha256()
+    if keep is not None:
+        h.update(np.asarray(keep, np.int64).tobytes())
+    h.update(_bits(arr).tobytes())
+    return h.hexdigest()
+
+
+def _same_as_reference(case, got, live, keep=None):
+    """``got`` (float32 array; ``keep``: kept indices, for soft-NMS) against the reference's output
+    of the same case, bit for bit: ``live()`` -> (keep, array) from oracle/_ref when it is built, and
+    always the SHA-256 recorded from it in tests/golden/ref_digests.json."""
+    if ref.available():
+        keep_r, want = live()
+        assert keep_r == keep, case
+        assert np.array_equal(_bits(want), _bits(got)), case
+        if _RECORD:
+            _recorded_now[case] = _digest(keep_r, want)
+            return
+    with open(DIGESTS) as f:
+        recorded = json.load(f)[case]
+    assert _digest(keep, got) == recorded, case
+
+
 @pytest.mark.parametrize("Cin,H,W", LAYERS)
 @pytest.mark.parametrize("stress", [False, True])
 def test_im2col_columns_bit_identical_on_layer_list(Cin, H, W, stress):
     x, off, mask = _inputs(Cin, H, W, seed=Cin + H + int(stress), stress=stress)
-    a = ref.dcn_v2_im2col(x, off, mask)
     b = cref.dcn_v2_im2col(x, off, mask)
-    assert np.array_equal(_bits(a), _bits(b))
-    assert np.abs(a).max() > 0
+    _same_as_reference("im2col_layer_%dx%dx%d_stress%d" % (Cin, H, W, stress), b,
+                       lambda: (None, ref.dcn_v2_im2col(x, off, mask)))
+    assert np.abs(b).max() > 0
 
 
-@needs_ref
 @pytest.mark.parametrize("cfg", [
     dict(Cin=64, H=24, W=20, dg=2),                         # DCNv2/test.py:169-179 example family
     dict(Cin=12, H=15, W=17, dg=3),
@@ -68,15 +100,14 @@ def test_im2col_columns_bit_identical_on_layer_list(Cin, H, W, stress):
 ])
 @pytest.mark.parametrize("stress", [False, True])
 def test_im2col_general_domain(cfg, stress):
+    case = "im2col_general_%s_stress%d" % ("_".join("%s%d" % kv for kv in sorted(cfg.items())), stress)
     cfg = dict(cfg)
     Cin, H, W = cfg.pop("Cin"), cfg.pop("H"), cfg.pop("W")
     x, off, mask = _inputs(Cin, H, W, seed=7, stress=stress, **cfg)
-    a = ref.dcn_v2_im2col(x, off, mask, **cfg)
     b = cref.dcn_v2_im2col(x, off, mask, **cfg)
-    assert np.array_equal(_bits(a), _bits(b))
+    _same_as_reference(case, b, lambda: (None, ref.dcn_v2_im2col(x, off, mask, **cfg)))
 
 
-@needs_ref
 def test_im2col_window_edges_and_exact_integers():
     """Offsets landing exactly on -1, 0, H-1, H and on half-integers (the window rule,
     dcn_v2_im2col_cuda.cu:165, and the per-corner rule, :30-41)."""
@@ -86,10 +117,10 @@ def test_im2col_window_edges_and_exact_integers():
     vals = np.array([-7, -2, -1.5, -1, -0.5, 0, 0.5, 1, H - 1, H - 0.5, H, W, W + 0.5], np.float32)
     off = rs.choice(vals, size=(18, H, W)).astype(np.float32)
     mask = np.ones((9, H, W), np.float32)
-    assert np.array_equal(_bits(ref.dcn_v2_im2col(x, off, mask)), _bits(cref.dcn_v2_im2col(x, off, mask)))
+    _same_as_reference("im2col_window_edges", cref.dcn_v2_im2col(x, off, mask),
+                       lambda: (None, ref.dcn_v2_im2col(x, off, mask)))
 
 
-@needs_ref
 @pytest.mark.parametrize("dg,stride", [(1, 1), (2, 1), (1, 2)])
 def test_forward_bit_identical(dg, stride):
     rs = np.random.RandomState(11 + dg)
@@ -100,21 +131,22 @@ def test_forward_bit_identical(dg, stride):
     mask = rs.uniform(0, 1, (B, dg * 9, Ho, Wo)).astype(np.float32)
     w = (rs.standard_normal((Cout, Cin, 3, 3)) * 0.1).astype(np.float32)
     b = rs.standard_normal(Cout).astype(np.float32)
-    ya = ref.dcn_v2_forward(x, off, mask, w, b, stride=stride, dg=dg)
     yb = cref.dcn_v2_forward(x, off, mask, w, b, stride=stride, dg=dg)
-    assert np.array_equal(_bits(ya), _bits(yb))
+    _same_as_reference("forward_dg%d_stride%d" % (dg, stride), yb,
+                       lambda: (None, ref.dcn_v2_forward(x, off, mask, w, b, stride=stride, dg=dg)))
 
 
-@needs_ref
 def test_reference_kat_on_reference_kernel():
-    """DCNv2/test.py:32-65 (zero offsets, mask 0.5, identity centre tap => 2*y == x) run on the
-    reference's own kernel."""
+    """DCNv2/test.py:32-65 (zero offsets, mask 0.5, identity centre tap => 2*y == x) on the
+    reference's own kernel (its recorded output where oracle/_ref is not built)."""
     N, inC, inH, inW = 2, 2, 4, 4
     x = np.random.RandomState(0).standard_normal((N, inC, inH, inW)).astype(np.float32)
     w = np.zeros((inC, inC, 3, 3), np.float32)
     w[np.arange(inC), np.arange(inC), 1, 1] = 1.0
-    y = ref.dcn_v2_forward(x, np.zeros((N, 18, inH, inW), np.float32),
-                           np.full((N, 9, inH, inW), 0.5, np.float32), w, np.zeros(inC, np.float32))
+    args = (x, np.zeros((N, 18, inH, inW), np.float32), np.full((N, 9, inH, inW), 0.5, np.float32), w,
+            np.zeros(inC, np.float32))
+    y = cref.dcn_v2_forward(*args)
+    _same_as_reference("kat", y, lambda: (None, ref.dcn_v2_forward(*args)))
     assert np.abs(2 * y - x).max() < 1e-10
 
 
@@ -132,7 +164,11 @@ def _nms_case(n, ncol, seed, crowded=True):
     return boxes
 
 
-@needs_ref
+def _ref_nms(fn, boxes, **kw):
+    r = boxes.copy()
+    return list(fn(r, **kw)), r
+
+
 @pytest.mark.parametrize("method", [0, 1, 2])
 @pytest.mark.parametrize("ncol", [5, 39])
 @pytest.mark.parametrize("seed", [0, 1, 2, 3, 4])
@@ -142,30 +178,29 @@ def test_soft_nms_restatement_and_product_match_reference_cython(method, ncol, s
     from centernet_amd.soft_nms import soft_nms, soft_nms_39
     base = _nms_case(80, ncol, seed * 13 + method)
     kw = dict(Nt=0.5, method=method, threshold=0.05 if seed else 0.001)
-    r = base.copy()
-    keep_r = (ref.soft_nms if ncol == 5 else ref.soft_nms_39)(r, **kw)
     o = base.copy()
-    keep_o = post_oracle.soft_nms(o, **kw)
+    keep_o = list(post_oracle.soft_nms(o, **kw))
     p = base.copy()
-    keep_p = (soft_nms if ncol == 5 else soft_nms_39)(p, **kw)
-    assert keep_r == keep_o == keep_p
+    keep_p = list((soft_nms if ncol == 5 else soft_nms_39)(p, **kw))
+    assert keep_o == keep_p
+    _same_as_reference("soft_nms_m%d_c%d_s%d" % (method, ncol, seed), o,
+                       lambda: _ref_nms(ref.soft_nms if ncol == 5 else ref.soft_nms_39, base, **kw), keep=keep_o)
     if seed or method == 0:
-        assert len(keep_r) < 80          # rows were discarded: the swap bookkeeping ran
-    assert np.array_equal(_bits(r), _bits(o))
-    assert np.array_equal(_bits(r), _bits(p))
+        assert len(keep_o) < 80          # rows were discarded: the swap bookkeeping ran
+    assert np.array_equal(_bits(o), _bits(p))
 
 
-@needs_ref
 def test_soft_nms_edge_cases_match_reference_cython():
     from centernet_amd.soft_nms import soft_nms
-    for boxes in (np.zeros((0, 5), np.float32),
-                  np.array([[0, 0, 9, 9, 0.9]], np.float32),
-                  np.array([[0, 0, 9, 9, 0.9], [0, 0, 9, 9, 0.8], [100, 100, 109, 109, 0.7]], np.float32),
-                  np.array([[5, 5, 1, 1, 0.5], [0, 0, 9, 9, 0.5], [0, 0, 9, 9, 0.5]], np.float32)):
+    for i, boxes in enumerate((np.zeros((0, 5), np.float32),
+                               np.array([[0, 0, 9, 9, 0.9]], np.float32),
+                               np.array([[0, 0, 9, 9, 0.9], [0, 0, 9, 9, 0.8], [100, 100, 109, 109, 0.7]], np.float32),
+                               np.array([[5, 5, 1, 1, 0.5], [0, 0, 9, 9, 0.5], [0, 0, 9, 9, 0.5]], np.float32))):
         for method in (0, 1, 2):
-            r, p = boxes.copy(), boxes.copy()
-            assert ref.soft_nms(r, Nt=0.5, method=method) == soft_nms(p, Nt=0.5, method=method)
-            assert np.array_equal(_bits(r), _bits(p))
+            p = boxes.copy()
+            keep_p = list(soft_nms(p, Nt=0.5, method=method))
+            _same_as_reference("soft_nms_edge%d_m%d" % (i, method), p,
+                               lambda: _ref_nms(ref.soft_nms, boxes, Nt=0.5, method=method), keep=keep_p)
 
 
 # ---- committed fixtures made from oracle/_ref (tests/golden/gen_golden_ref.py) ---------------

@@ -149,7 +149,7 @@ def test_bench_rank_logic_end_to_end_two_ranks_gloo():
     detector replaced by bench._StubDetector (BENCH_STUB=1; gloo instead of RCCL).  What an 8-GPU
     lease runs differs only in the backend string and the detector."""
     p, lines = _run_bench_stub(["--gpus", "2", "--steps", "6", "--warmup", "2", "--batch", "4",
-                                "--res", "64"])
+                                "--res", "64", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, "exactly one JSON line, from rank 0"
     r = lines[0]
@@ -170,6 +170,27 @@ def test_bench_rank_logic_end_to_end_two_ranks_gloo():
     assert [d["rank"] for d in r["rank_devices"]] == [0, 1]
     assert len({d["uuid"] for d in r["rank_devices"]}) == 2
     assert r["rccl_ranks_seen"] is None      # gloo here; an RCCL run reports the world it really formed
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the headline fields and none of the
+    --full figures, and --dump-outputs writes the last timed step's result as float32 .npy."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p, lines = _run_bench_stub(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--res", "64",
+                                "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(lines) == 1
+    r = lines[0]
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["higher_is_better"] is True
+    assert r["metric"].startswith("images/sec whole-node") and r["unit"] == "img/s" and r["dtype"] == "f32s"
+    assert abs(r["value"] - 2 * 3 / (r["ms_per_step"] * 3e-3)) <= 1e-6 * r["value"]
+    for k in ("roofline", "time_share", "box_calibration", "cross_rank_agreement", "cpu_baseline"):
+        assert k not in r, k
+    d = np.load(out / "detections.npy")
+    assert d.dtype == np.float32 and d.shape == (64, 64)
+    p, _ = _run_bench_stub(["--gpus", "1", "--steps", "1", "--per-op"])
+    assert p.returncode != 0 and "--per-op needs --full" in p.stderr
 
 
 def test_bench_refuses_two_ranks_on_one_device():

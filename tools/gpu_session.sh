@@ -12,14 +12,14 @@ if [ "$3" != "nosuite" ]; then
 fi
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 if [ "$3" == "suiteonly" ]; then
-  timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; cut -c1-400 $O/bench_default.json
+  timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cut -c1-400 $O/bench_default.json
   exit 0
 fi
 bash tools/profile_round.sh $RND $TAG 1 > $O/prof1.log 2>&1; tail -12 $O/prof1.log | cut -c1-200
 bash tools/profile_round.sh $RND $TAG 2 > $O/prof2.log 2>&1; tail -12 $O/prof2.log | cut -c1-200
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; cut -c1-400 $O/bench_default.json
-python bench.py --config 3 --steps 40 --warmup 5 --no-cpu-baseline > $O/bench_cfg3.json 2> $O/bench_cfg3.err; cut -c1-200 $O/bench_cfg3.json
-python bench.py --config 4 --steps 40 --warmup 5 --no-cpu-baseline > $O/bench_cfg4.json 2> $O/bench_cfg4.err; cut -c1-200 $O/bench_cfg4.json
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cut -c1-400 $O/bench_default.json
+python bench.py --config 3 --steps 40 --warmup 5 --full --no-cpu-baseline > $O/bench_cfg3.json 2> $O/bench_cfg3.err; cut -c1-200 $O/bench_cfg3.json
+python bench.py --config 4 --steps 40 --warmup 5 --full --no-cpu-baseline > $O/bench_cfg4.json 2> $O/bench_cfg4.err; cut -c1-200 $O/bench_cfg4.json
 timeout 300 python tools/bench_e2e.py > $O/e2e.txt 2>&1; tail -6 $O/e2e.txt
 bash tools/pmc_step.sh 1 > $O/pmc_step1.log 2>&1; tail -3 $O/pmc_step1.log | cut -c1-160
 for h in iid net floor; do HEAT=$h timeout 100 python tools/bench_decode.py 2>&1 | grep -v amdgpu.ids; done > $O/decode_forms.txt; grep "default product" $O/decode_forms.txt
