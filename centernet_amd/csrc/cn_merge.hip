@@ -1,0 +1,286 @@
+// cn_merge.hip -- the ctdet scale merge on the device (CtdetDetector.merge_outputs, detectors/ctdet.py:54-74;
+// reference ctdet.py:58-73), bit for bit.  Input: the device tail's output of every test scale
+// (cn_ctdet_post_process_f32 into slice s of rows (S, B, K, 5) / bounds (S, B, nc + 1)).  Output in the
+// tail's own format, so the host slices it as it slices a single scale.
+//
+// One workgroup of four waves per image; the image's rows (<= CN_MERGE_MAX_ROWS) live in LDS.
+//   1. per class, the rows of all scales in scale order (the np.concatenate of merge_outputs);
+//   2. when S > 1 or apply_nms: Gaussian soft-NMS (sigma 0.5, threshold 0.001) of every class segment,
+//      one wave per segment, with the arithmetic of cn_soft_nms_f32 (cn_misc.hip) term by term.  The whole
+//      in-place array is kept: the reference ignores the kept count, rows past N stay with stale scores;
+//   3. when the image has more rows than max_per_image: thresh = the max_per_image-th largest score
+//      (duplicates counted: np.partition(scores, len - max_per_image)), keep score >= thresh in array order.
+//
+// The greedy step of soft-NMS, for one segment and step i (rows [i, N) still live):
+//   argmax  -- a wave reduction; equal scores go to the lowest position (the reference's strict `<`);
+//   decay   -- every live row p > i is examined exactly once per step, at its own position or, after a
+//              discard moved it there, at the discarded row's position; its box does not change on the
+//              way, so its new score ns[p] = weight(p) * score(p) and whether it is discarded are computed
+//              for all rows at once, lane-parallel;
+//   walk    -- what stays order dependent is WHERE rows end up: a discarded row takes columns 0..4 of row
+//              N - 1 (which has not been examined yet and so still holds its old score), N shrinks and the
+//              moved row is examined at the same position next.  The wave jumps from discard to discard
+//              with ballots; orig[] records which row now sits where, and the decayed scores are written
+//              afterwards, at the positions their rows occupy.  tests/test_tta_host.py holds this form
+//              equal to cn_soft_nms_f32 on seeded arrays before any GPU run.
+#include "cn_common.h"
+
+namespace {
+constexpr int MG_THREADS = 256;
+constexpr int MG_WAVES = MG_THREADS / CN_WAVE;
+constexpr int MG_ROWS = CN_MERGE_MAX_ROWS;
+constexpr int MG_CLASSES = CN_MERGE_MAX_CLASSES;
+constexpr float MG_SIGMA = 0.5f, MG_THRESHOLD = 0.001f;
+
+struct MergeLds {
+    float box[4][MG_ROWS];   // x1, y1, x2, y2 of the merged rows (class segments back to back)
+    float sc[MG_ROWS];       // score
+    float ns[MG_ROWS];       // soft-NMS: decayed score of the row that started the step at p; select: prefix
+    int16_t orig[MG_ROWS];   // soft-NMS: start-of-step position of the row now at p
+    uint8_t disc[MG_ROWS];   // soft-NMS: the row that started the step at p is discarded
+    int seg[MG_CLASSES + 1]; // class c = [seg[c], seg[c + 1])
+    int red[MG_WAVES];
+};
+
+// LDS written by one lane is read by the others of the same wave next: order the wave's own accesses
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ int block_sum(int v, int *red)
+{
+    for (int o = CN_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const int w = threadIdx.x / CN_WAVE;
+    __syncthreads();                      // red[] of the previous call has been read
+    if ((threadIdx.x & (CN_WAVE - 1)) == 0) red[w] = v;
+    __syncthreads();
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < MG_WAVES; ++k) s += red[k];
+    return s;
+}
+
+// float -> unsigned key of the same order
+__device__ __forceinline__ uint32_t order_key(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(uint32_t k)
+{
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// float division through double: a / b for float a, b rounds to the same float either way (53 >= 2 * 24 + 2
+// bits), so the result is the IEEE quotient the host computes whatever the device division flags are
+__device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
+
+// Soft-NMS of one class segment [o, o + n) by one wave (see the head of the file).
+__device__ void soft_nms_segment(MergeLds &L, int o, int n, int lane)
+{
+#pragma clang fp contract(off)
+    float *x1 = L.box[0] + o, *y1 = L.box[1] + o, *x2 = L.box[2] + o, *y2 = L.box[3] + o;
+    float *sc = L.sc + o, *ns = L.ns + o;
+    int16_t *orig = L.orig + o;
+    uint8_t *disc = L.disc + o;
+    int N = n;
+    for (int i = 0; i < n && i < N; ++i) {
+        // argmax over [i, N): the first maximum wins
+        float best = 0.f;
+        int bpos = 0x7fffffff;
+        for (int p = i + lane; p < N; p += CN_WAVE) {
+            const float s = sc[p];
+            if (bpos == 0x7fffffff || s > best) { best = s; bpos = p; }
+        }
+        for (int off = CN_WAVE / 2; off > 0; off >>= 1) {
+            const float s2 = __shfl_xor(best, off);
+            const int p2 = __shfl_xor(bpos, off);
+            if (p2 != 0x7fffffff && (bpos == 0x7fffffff || s2 > best || (s2 == best && p2 < bpos))) {
+                best = s2;
+                bpos = p2;
+            }
+        }
+        if (lane == 0 && bpos != i) {
+            float t;
+            t = x1[i]; x1[i] = x1[bpos]; x1[bpos] = t;
+            t = y1[i]; y1[i] = y1[bpos]; y1[bpos] = t;
+            t = x2[i]; x2[i] = x2[bpos]; x2[bpos] = t;
+            t = y2[i]; y2[i] = y2[bpos]; y2[bpos] = t;
+            t = sc[i]; sc[i] = sc[bpos]; sc[bpos] = t;
+        }
+        wave_sync();
+        const float tx1 = x1[i], ty1 = y1[i], tx2 = x2[i], ty2 = y2[i];
+        // decay: every live row, as cn_soft_nms_f32 computes it
+        for (int p = i + 1 + lane; p < N; p += CN_WAVE) {
+            const float bx1 = x1[p], by1 = y1[p], bx2 = x2[p], by2 = y2[p];
+            float s = sc[p];
+            bool d = false;
+            const float area = (float)(((double)(bx2 - bx1) + 1.0) * ((double)(by2 - by1) + 1.0));
+            const float iw = (float)((double)(fminf(tx2, bx2) - fmaxf(tx1, bx1)) + 1.0);
+            if (iw > 0) {
+                const float ih = (float)((double)(fminf(ty2, by2) - fmaxf(ty1, by1)) + 1.0);
+                if (ih > 0) {
+                    const float ua = (float)((((double)(tx2 - tx1) + 1.0) * ((double)(ty2 - ty1) + 1.0) +
+                                              (double)area) - (double)(iw * ih));
+                    const float ov = div_rn(iw * ih, ua);
+                    const float weight = (float)exp((double)div_rn(-(ov * ov), MG_SIGMA));
+                    s = weight * s;
+                    d = s < MG_THRESHOLD;
+                }
+            }
+            ns[p] = s;
+            disc[p] = d ? 1 : 0;
+            orig[p] = (int16_t)p;
+        }
+        wave_sync();
+        // walk: from discard to discard
+        int pos = i + 1;
+        while (pos < N) {
+            int p = -1;
+            for (int base = pos; base < N; base += CN_WAVE) {
+                const int q = base + lane;
+                const unsigned long long m = __ballot(q < N && disc[q]);
+                if (m) {
+                    p = base + __builtin_ctzll(m);
+                    break;
+                }
+            }
+            if (p < 0) break;
+            // the row at p (a row that has not moved) is discarded; so is every row moved onto p after it
+            // that is itself discarded
+            for (;;) {
+                if (p == N - 1) {        // the last live row: it takes its own columns, N shrinks past it
+                    if (lane == 0) sc[p] = ns[orig[p]];
+                    N = p;
+                    break;
+                }
+                const int last = N - 1;  // has not moved: orig[last] == last, old score
+                if (lane == 0) {
+                    x1[p] = x1[last]; y1[p] = y1[last]; x2[p] = x2[last]; y2[p] = y2[last]; sc[p] = sc[last];
+                    orig[p] = (int16_t)last;
+                }
+                N = last;
+                if (!disc[last]) break;
+            }
+            wave_sync();
+            pos = p + 1;
+        }
+        // the decayed scores, where their rows now are
+        for (int q = i + 1 + lane; q < N; q += CN_WAVE) sc[q] = ns[orig[q]];
+        wave_sync();
+    }
+}
+
+__global__ __launch_bounds__(MG_THREADS) void ctdet_merge_kernel(const float *__restrict__ rows,
+                                                                 const int32_t *__restrict__ bounds, int S, int B,
+                                                                 int K, int nc, int do_nms, int max_per_image,
+                                                                 float *__restrict__ out_rows,
+                                                                 int32_t *__restrict__ out_bounds)
+{
+    __shared__ MergeLds L;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & (CN_WAVE - 1), w = t / CN_WAVE;
+    const size_t bstride = (size_t)nc + 1;
+    // 1. merged class segments: class c starts behind every row of classes < c of every scale
+    for (int c = t; c <= nc; c += MG_THREADS) {
+        int n = 0;
+        for (int s = 0; s < S; ++s) n += bounds[((size_t)s * B + b) * bstride + c];
+        L.seg[c] = n;
+    }
+    __syncthreads();
+    const int total = min(L.seg[nc], S * K);
+    for (int e = t; e < S * K; e += MG_THREADS) {
+        const int s = e / K, r = e - s * K;
+        const int32_t *bd = bounds + ((size_t)s * B + b) * bstride;
+        if (r >= bd[nc]) continue;
+        int lo = 0, hi = nc;             // class of row r: the last c with bd[c] <= r
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (bd[mid] <= r) lo = mid; else hi = mid;
+        }
+        int dst = L.seg[lo] + (r - bd[lo]);
+        for (int s2 = 0; s2 < s; ++s2) {
+            const int32_t *b2 = bounds + ((size_t)s2 * B + b) * bstride;
+            dst += b2[lo + 1] - b2[lo];
+        }
+        if (dst < 0 || dst >= total) continue;
+        const float *src = rows + (((size_t)s * B + b) * K + r) * 5;
+        L.box[0][dst] = src[0];
+        L.box[1][dst] = src[1];
+        L.box[2][dst] = src[2];
+        L.box[3][dst] = src[3];
+        L.sc[dst] = src[4];
+    }
+    __syncthreads();
+    // 2. soft-NMS, one class segment per wave at a time
+    if (do_nms) {
+        for (int c = w; c < nc; c += MG_WAVES) {
+            const int o = L.seg[c], e = min(L.seg[c + 1], total);
+            if (e - o > 1) soft_nms_segment(L, o, e - o, lane);
+        }
+        __syncthreads();
+    }
+    // 3. top max_per_image by threshold: the largest key T with #{key >= T} >= max_per_image, bit by bit
+    const int per = (total + MG_THREADS - 1) / MG_THREADS, r0 = min(t * per, total), r1 = min(r0 + per, total);
+    bool cut = total > max_per_image;
+    float thresh = 0.f;
+    if (cut) {
+        uint32_t T = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = T | (1u << bit);
+            int n = 0;
+            for (int r = r0; r < r1; ++r) n += order_key(L.sc[r]) >= cand ? 1 : 0;
+            if (block_sum(n, L.red) >= max_per_image) T = cand;
+        }
+        thresh = key_value(T);
+    }
+    // order-preserving compaction: exclusive prefix of the kept flags (chunk per thread, then a scan)
+    int n = 0;
+    for (int r = r0; r < r1; ++r) n += (!cut || L.sc[r] >= thresh) ? 1 : 0;
+    int incl = n;
+    for (int o = 1; o < CN_WAVE; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    __syncthreads();
+    if (lane == CN_WAVE - 1) L.red[w] = incl;
+    __syncthreads();
+    int run = incl - n;
+    for (int k = 0; k < w; ++k) run += L.red[k];
+    int kept = 0;
+    for (int k = 0; k < MG_WAVES; ++k) kept += L.red[k];
+    int *prefix = reinterpret_cast<int *>(L.ns);
+    float *ob = out_rows + (size_t)b * S * K * 5;
+    for (int r = r0; r < r1; ++r) {
+        prefix[r] = run;
+        if (!cut || L.sc[r] >= thresh) {
+            float *d = ob + (size_t)run * 5;
+            d[0] = L.box[0][r];
+            d[1] = L.box[1][r];
+            d[2] = L.box[2][r];
+            d[3] = L.box[3][r];
+            d[4] = L.sc[r];
+            ++run;
+        }
+    }
+    __syncthreads();
+    for (int c = t; c <= nc; c += MG_THREADS) {
+        const int sg = min(L.seg[c], total);
+        out_bounds[(size_t)b * bstride + c] = sg < total ? prefix[sg] : kept;
+    }
+}
+}  // namespace
+
+extern "C" int cn_ctdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int K, int num_classes,
+                                  int apply_nms, int max_per_image, float *out_rows, int32_t *out_bounds,
+                                  void *stream)
+{
+    if (!rows || !bounds || !out_rows || !out_bounds) return CN_ERR_NULL;
+    if (S <= 0 || B <= 0 || K <= 0 || num_classes <= 0 || max_per_image <= 0) return CN_ERR_SHAPE;
+    if ((long long)S * K > CN_MERGE_MAX_ROWS || num_classes > CN_MERGE_MAX_CLASSES) return CN_ERR_SHAPE;
+    hipLaunchKernelGGL(ctdet_merge_kernel, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, rows, bounds, S, B,
+                       K, num_classes, (S > 1 || apply_nms) ? 1 : 0, max_per_image, out_rows, out_bounds);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}

@@ -233,7 +233,7 @@ inline int blocks_for(size_t total, int per_block, int cap)
 
 }  // namespace
 
-extern "C" int cn_version(void) { return 300; }  // 0.3.0: f32s range control (cn_f32s_ctl)
+extern "C" int cn_version(void) { return 310; }  // 0.3.1: batched flip average, ctdet scale merge
 
 extern "C" const char *cn_arch(void) { return "gfx950"; }
 
@@ -771,46 +771,63 @@ extern "C" int cn_soft_nms_f32(float *boxes, int n, int stride, float sigma, flo
 }
 
 // ---- flip-test averaging (detectors/ctdet.py:34-37, multi_pose.py:44-55, models/utils.py:28-50): image 1
-// of the pair is the mirrored frame; out[c, y, x] = (f(x0[c, y, x]) + sign[c] * f(x1[src[c], y, W-1-x])) / 2
+// of a pair is the mirrored frame; out[c, y, x] = (f(x0[c, y, x]) + sign[c] * f(x1[src[c], y, W-1-x])) / 2
 // with f = the logistic when asked (then written back in place: the reference's sigmoid_()), src = the
-// left / right joint permutation, sign = -1 for the x components of joint offsets
+// left / right joint permutation, sign = -1 for the x components of joint offsets.  P pairs side by side
+// ((2P, C, H, W), as the batched pre-process with flip_concat lays them out) -> (P, C, H, W); mode 1 copies
+// image 0 of each pair (the offsets the reference takes from the un-mirrored frame only, reg[0:1]).
 namespace {
-__global__ void flip_average_kernel(float *__restrict__ x, float *__restrict__ out, int C, int H, int W,
+__global__ void flip_average_kernel(float *__restrict__ x, float *__restrict__ out, int P, int C, int H, int W,
                                     const int32_t *__restrict__ src, const float *__restrict__ sign,
-                                    int apply_sigmoid)
+                                    int apply_sigmoid, int mode)
 {
     const size_t total = (size_t)C * H * W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * blockDim.x) {
+    const size_t all = total * (size_t)P;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < all;
+         g += (size_t)gridDim.x * blockDim.x) {
+        const size_t p = g / total, i = g - p * total;
+        float *xp = x + 2 * p * total;
+        if (mode == 1) {
+            out[g] = xp[i];
+            continue;
+        }
         const int xx = (int)(i % W);
         size_t r = i / W;
         const int y = (int)(r % H);
         const int c = (int)(r / H);
         const int cs = src ? src[c] : c;
         const size_t j = total + ((size_t)cs * H + y) * W + (W - 1 - xx);
-        float a = x[i], b = x[j];
+        float a = xp[i], b = xp[j];
         if (apply_sigmoid) {
             a = sigmoidf_ref(a);      // the decode kernels' definition (cn_common.h)
             b = sigmoidf_ref(b);
-            x[i] = a;
-            x[j] = b;
+            xp[i] = a;
+            xp[j] = b;
         }
         if (sign) b = b * sign[c];
-        out[i] = (a + b) / 2.0f;
+        out[g] = (a + b) / 2.0f;
     }
 }
 }  // namespace
 
+extern "C" int cn_flip_average_f32_batch(float *x_pairs, float *out, int P, int C, int H, int W,
+                                         const int32_t *chan_src, const float *chan_sign, int apply_sigmoid,
+                                         int mode, void *stream)
+{
+    if (!x_pairs || !out) return CN_ERR_NULL;
+    if (P <= 0 || C <= 0 || H <= 0 || W <= 0 || (mode != 0 && mode != 1)) return CN_ERR_SHAPE;
+    const size_t all = (size_t)P * C * H * W;
+    hipLaunchKernelGGL(flip_average_kernel, dim3(blocks_for(all, 256, 65535)), dim3(256), 0,
+                       (hipStream_t)stream, x_pairs, out, P, C, H, W, chan_src, chan_sign, apply_sigmoid ? 1 : 0,
+                       mode);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 extern "C" int cn_flip_average_f32(float *x_pair, float *out, int C, int H, int W, const int32_t *chan_src,
                                    const float *chan_sign, int apply_sigmoid, void *stream)
 {
-    if (!x_pair || !out) return CN_ERR_NULL;
-    if (C <= 0 || H <= 0 || W <= 0) return CN_ERR_SHAPE;
-    const size_t total = (size_t)C * H * W;
-    hipLaunchKernelGGL(flip_average_kernel, dim3(blocks_for(total, 256, 65535)), dim3(256), 0,
-                       (hipStream_t)stream, x_pair, out, C, H, W, chan_src, chan_sign, apply_sigmoid ? 1 : 0);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    return cn_flip_average_f32_batch(x_pair, out, 1, C, H, W, chan_src, chan_sign, apply_sigmoid, 0, stream);
 }
 
 // ---- box calibration (bench.py "box_calibration"): what THIS box's matrix pipe and HBM deliver

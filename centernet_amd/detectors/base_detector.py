@@ -48,45 +48,58 @@ class _PhaseClock(object):
 
 class _FramePipe(object):
     """Persistent resources of ``run_frames`` / ``run_frames_stream`` for one batch geometry
-    (B frames of (H, W, 3) uint8 at one test scale): ``depth`` sets of a pinned uint8 staging
+    (B frames of (H, W, 3) uint8, the detector's test scales and flip setting): per test scale the
+    input geometry and meta, the resize buffer and the network batch ((B or 2B, 3, h, w): with
+    flip-test every frame is followed by its mirror image); ``depth`` sets of a pinned uint8 staging
     buffer, its device copy and pinned result buffers, one copy stream, a few staging threads.
 
     Per batch: the frames are copied into the pinned buffer by the staging threads (numpy releases
     the GIL), go to the device as ONE asynchronous uint8 copy on the copy stream, and everything
-    else -- the batched device pre-process, network + decode (``run_batch``), the device tail
-    (``cn_ctdet_post_process_f32``: inverse affine + class grouping) and the copies of the rows /
-    class bounds / f32s range digest into pinned memory -- is enqueued on the launch stream
-    without a single host synchronisation.  The host waits for batch i - depth + 1 only when it
-    collects it, i.e. while later batches are on the device."""
+    else -- per test scale the batched device pre-process, network + flip average + decode
+    (``_run_scale``) and the device tail (``cn_ctdet_post_process_f32``: inverse affine + class
+    grouping, into the scale's slice), then the scale merge (``cn_ctdet_merge_f32``: soft-NMS and
+    the top-100 cut, when there are several scales or --nms) and the copies of the rows / class
+    bounds / f32s range digests into pinned memory -- is enqueued on the launch stream without a
+    single host synchronisation.  The host waits for batch i - depth + 1 only when it collects it,
+    i.e. while later batches are on the device."""
 
-    def __init__(self, det, B, H, W, scale, depth):
+    def __init__(self, det, B, H, W, scales, flip, depth):
         import concurrent.futures
+        import types
         opt, dev = det.opt, det.opt.device
-        self.det, self.B, self.H, self.W, self.scale, self.depth = det, B, H, W, scale, depth
-        self.g = det.input_geometry(H, W, scale)
-        g = self.g
-        self.resize = (g.scaled_h, g.scaled_w) != (g.src_h, g.src_w)
-        self.meta = det._meta(g)
-        to_input = get_affine_transform(g.center, g.extent, 0, [g.inp_w, g.inp_h])
-        self.dst_to_src = (ctypes.c_double * 6)(*invert_affine(to_input).reshape(-1))
+        self.det, self.B, self.H, self.W, self.depth = det, B, H, W, depth
+        self.scales, self.flip = tuple(scales), bool(flip)
+        # merge_outputs does more than pass one scale through: soft-NMS, and a cut of S * K rows
+        self.merge = len(self.scales) > 1 or bool(getattr(opt, "nms", False))
+        self.levels = []
+        for scale in self.scales:
+            g = det.input_geometry(H, W, scale)
+            to_input = get_affine_transform(g.center, g.extent, 0, [g.inp_w, g.inp_h])
+            resize = (g.scaled_h, g.scaled_w) != (g.src_h, g.src_w)
+            self.levels.append(types.SimpleNamespace(
+                scale=scale, g=g, resize=resize, meta=det._meta(g),
+                dst_to_src=(ctypes.c_double * 6)(*invert_affine(to_input).reshape(-1)),
+                scaled=torch.empty((B, g.scaled_h, g.scaled_w, 3), dtype=torch.uint8, device=dev) if resize else None,
+                batch=torch.empty((B * (2 if self.flip else 1), 3, g.inp_h, g.inp_w), device=dev,
+                                  dtype=torch.float32)))
+        first = self.levels[0]        # (the single-scale pipe's own names)
+        self.scale, self.g, self.meta, self.batch = first.scale, first.g, first.meta, first.batch
         self.mean = (ctypes.c_float * 3)(*[float(v) for v in det.mean.reshape(-1)])
         self.std = (ctypes.c_float * 3)(*[float(v) for v in det.std.reshape(-1)])
         self.pinned_in = [torch.empty((B, H, W, 3), dtype=torch.uint8).pin_memory() for _ in range(depth)]
         self.np_in = [t.numpy() for t in self.pinned_in]
         self.dev_in = [torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(depth)]
-        self.scaled = torch.empty((B, g.scaled_h, g.scaled_w, 3), dtype=torch.uint8, device=dev) \
-            if self.resize else None
-        self.batch = torch.empty((B, 3, g.inp_h, g.inp_w), device=dev, dtype=torch.float32)
         self.copy_stream = torch.cuda.Stream()
         self.ev_h2d = [torch.cuda.Event() for _ in range(depth)]
         self.ev_pre = [torch.cuda.Event() for _ in range(depth)]
         self.ev_done = [torch.cuda.Event() for _ in range(depth)]
         self.used = [False] * depth
-        self.digest_host = [torch.zeros(2, dtype=torch.int32).pin_memory() for _ in range(depth)]
-        self.has_digest = [False] * depth
+        # one range digest per test scale: every scale's plan is looked at
+        self.digest_host = [torch.zeros((len(self.scales), 2), dtype=torch.int32).pin_memory() for _ in range(depth)]
+        self.has_digest = [[False] * len(self.scales) for _ in range(depth)]
         self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=min(4, B))
         self.tail = det._device_tail_alloc(self) if det._device_tail_alloc is not None else None
-        self.dets_host = None if self.tail is not None else [None] * depth
+        self.dets_host = None if self.tail is not None else [[None] * len(self.scales) for _ in range(depth)]
 
     def _stage(self, slot, frames):
         dst = self.np_in[slot]
@@ -99,7 +112,7 @@ class _FramePipe(object):
         list(self.pool.map(copy, range(0, n, step)))
 
     def submit(self, i, frames):
-        det, lib, g, B = self.det, native.lib(), self.g, self.B
+        det, lib, B = self.det, native.lib(), self.B
         slot = i % self.depth
         if self.used[slot]:
             self.ev_h2d[slot].synchronize()      # the pinned buffer's previous upload has left it
@@ -113,30 +126,34 @@ class _FramePipe(object):
         self.used[slot] = True
         cur.wait_event(self.ev_h2d[slot])
         stream = native.stream_ptr()
-        src = self.dev_in[slot]
-        if self.resize:
-            for j in range(B):
-                native.check(lib.cn_resize_bilinear_u8(native.ptr(src[j]), g.src_h, g.src_w, g.src_w * 3,
-                                                       g.scaled_h, g.scaled_w, native.ptr(self.scaled[j]), stream),
-                             "cn_resize_bilinear_u8")
-            src = self.scaled
-        native.check(lib.cn_warp_normalize_u8_f32_batch(
-            native.ptr(src), B, g.scaled_h * g.scaled_w * 3, g.scaled_h, g.scaled_w, g.scaled_w * 3,
-            self.dst_to_src, g.inp_h, g.inp_w, self.mean, self.std, 0, native.ptr(self.batch), stream),
-            "cn_warp_normalize_u8_f32_batch")
-        self.ev_pre[slot].record()
-        dets = det.run_batch(self.batch)
-        plan = det.model.plan_for(B, g.inp_h, g.inp_w, self.batch.device)
-        rs = getattr(plan.b, "range_sum", None) if plan.b.range is not None else None
-        self.has_digest[slot] = rs is not None
-        if rs is not None:
-            self.digest_host[slot].copy_(rs, non_blocking=True)
+        for li, lv in enumerate(self.levels):
+            g, src = lv.g, self.dev_in[slot]
+            if lv.resize:
+                for j in range(B):
+                    native.check(lib.cn_resize_bilinear_u8(native.ptr(src[j]), g.src_h, g.src_w, g.src_w * 3,
+                                                           g.scaled_h, g.scaled_w, native.ptr(lv.scaled[j]), stream),
+                                 "cn_resize_bilinear_u8")
+                src = lv.scaled
+            native.check(lib.cn_warp_normalize_u8_f32_batch(
+                native.ptr(src), B, g.scaled_h * g.scaled_w * 3, g.scaled_h, g.scaled_w, g.scaled_w * 3,
+                lv.dst_to_src, g.inp_h, g.inp_w, self.mean, self.std, int(self.flip), native.ptr(lv.batch), stream),
+                "cn_warp_normalize_u8_f32_batch")
+            if li == len(self.levels) - 1:
+                self.ev_pre[slot].record()
+            dets = det._run_scale(lv.batch, self.flip)
+            plan = det.model.plan_for(lv.batch.shape[0], g.inp_h, g.inp_w, lv.batch.device)
+            rs = getattr(plan.b, "range_sum", None) if plan.b.range is not None else None
+            self.has_digest[slot][li] = rs is not None
+            if rs is not None:
+                self.digest_host[slot][li].copy_(rs, non_blocking=True)
+            if self.tail is not None:
+                det._device_tail_run(self, slot, li, dets)
+            else:
+                dh = self.dets_host[slot]
+                dh[li] = torch.empty(dets.shape, dtype=dets.dtype).pin_memory() if dh[li] is None else dh[li]
+                dh[li].copy_(dets, non_blocking=True)
         if self.tail is not None:
-            det._device_tail_run(self, slot, dets)
-        else:
-            self.dets_host[slot] = torch.empty(dets.shape, dtype=dets.dtype).pin_memory() \
-                if self.dets_host[slot] is None else self.dets_host[slot]
-            self.dets_host[slot].copy_(dets, non_blocking=True)
+            det._device_tail_finish(self, slot)
         self.ev_done[slot].record()
 
     def collect(self, i, frames):
@@ -145,17 +162,21 @@ class _FramePipe(object):
         det = self.det
         slot = i % self.depth
         self.ev_done[slot].synchronize()
-        det.__dict__["_unchecked"] = 0       # (the batch's range digest is looked at right here)
-        if self.has_digest[slot] and (int(self.digest_host[slot][0]) & 0xffffffff) > F16_MAX_BITS:
+        det.__dict__["_unchecked"] = 0       # (the batch's range digests are looked at right here)
+        digest = self.digest_host[slot].tolist()
+        if any(has and (int(d[0]) & 0xffffffff) > F16_MAX_BITS for has, d in zip(self.has_digest[slot], digest)):
             # an f32s value was clamped somewhere up to this batch: results invalid.  Drain the
             # device, let the module re-calibrate, and run this batch again synchronously.
             torch.cuda.synchronize()
             det.range_ok(None)
-            return det._run_frames_sync(frames, self.scale)
-        metas = [self.meta] * len(frames)
+            return det._run_frames_sync(frames, self.scales)
+        n = len(frames)
         if self.tail is not None:
-            return det._device_tail_results(self, slot, len(frames))
-        return det.results_batch(self.dets_host[slot].numpy()[:len(frames)], metas, self.scale)
+            return det._device_tail_results(self, slot, n)
+        if not self.merge:
+            return det.results_batch(self.dets_host[slot][0].numpy()[:n], [self.meta] * n, self.scale)
+        return det._results_merged([(d.numpy()[:n], [lv.meta] * n, lv.scale)
+                                    for d, lv in zip(self.dets_host[slot], self.levels)])
 
 
 class BaseDetector(object):
@@ -303,50 +324,70 @@ class BaseDetector(object):
     # device tail of the frame pipeline: task classes that have one set the three hooks
     _device_tail_alloc = None
 
-    def _run_frames_sync(self, frames, scale):
-        """One batch, synchronously, frame by frame through ``pre_process_device`` (the comparison
-        path of the pipeline, and its re-run path after an f32s re-calibration)."""
+    def _run_scale(self, images, flip):
+        """Task hook of the frame pipeline: network + (with ``flip``: the batched flip average of the
+        (2B, 3, H, W) frame / mirror pairs) + decode of one test scale -> raw (B, K, .) detections in
+        output-grid units, asynchronously (as ``run_batch``)."""
+        raise NotImplementedError
+
+    def _results_merged(self, per_scale):
+        """Host tail of a merging frame pipeline: ``per_scale`` = [(host raw detections (n, K, .),
+        metas, scale)] in test-scale order -> per image ``merge_outputs([post_process(...) per
+        scale])``, what ``run(frame)['results']`` returns."""
+        posts = [self._post_batch(d, metas, scale) for d, metas, scale in per_scale]
+        return [self.merge_outputs([p[i] for p in posts]) for i in range(len(posts[0]))]
+
+    def _post_batch(self, dets, metas, scale):
+        """``post_process`` of every image of a host batch of raw detections (task specific)."""
+        raise NotImplementedError
+
+    def _run_frames_sync(self, frames, scales):
+        """One batch, synchronously, frame by frame through ``pre_process_device`` at every test scale
+        (the comparison path of the pipeline, and its re-run path after an f32s re-calibration)."""
         uploaded = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.opt.device)
-        g = self.input_geometry(uploaded.shape[1], uploaded.shape[2], scale)
-        batch = torch.empty((len(frames), 3, g.inp_h, g.inp_w), device=self.opt.device,
-                            dtype=torch.float32)
-        metas = [self.pre_process_device(frame, scale, out=batch[i:i + 1])[1]
-                 for i, frame in enumerate(uploaded)]
-        dets = self.run_batch(batch).detach().cpu().numpy()
-        if not self.range_ok(batch):    # a clamped f32s value: re-calibrated on this batch, run again
-            dets = self.run_batch(batch).detach().cpu().numpy()
-            if not self.range_ok(batch):
-                raise native.NativeError("f32s forward clamps values after re-calibration")
-        return self.results_batch(dets, metas, scale)
+        flip = bool(self.opt.flip_test)
+        k = 2 if flip else 1
+        per_scale = []
+        for scale in scales:
+            g = self.input_geometry(uploaded.shape[1], uploaded.shape[2], scale)
+            batch = torch.empty((k * len(frames), 3, g.inp_h, g.inp_w), device=self.opt.device,
+                                dtype=torch.float32)
+            metas = [self.pre_process_device(frame, scale, out=batch[k * i:k * i + k])[1]
+                     for i, frame in enumerate(uploaded)]
+            dets = self._run_scale(batch, flip).detach().cpu().numpy()
+            if not self.range_ok(batch):    # a clamped f32s value: re-calibrated on this batch, run again
+                dets = self._run_scale(batch, flip).detach().cpu().numpy()
+                if not self.range_ok(batch):
+                    raise native.NativeError("f32s forward clamps values after re-calibration")
+            per_scale.append((dets, metas, scale))
+        if len(per_scale) == 1 and not getattr(self.opt, "nms", False):
+            return self.results_batch(*per_scale[0])
+        return self._results_merged(per_scale)
 
     def _pipe_for(self, frames, depth):
-        if len(self.scales) != 1 or self.opt.flip_test:
-            raise ValueError("run_frames is single-scale, no flip")
-        if getattr(self.opt, "nms", False):
-            # merge_outputs applies soft-NMS under --nms (detectors/ctdet.py:63-64); the batched tail
-            # does not: refuse rather than return something else than run(frame)['results']
-            raise ValueError("run_frames does not apply --nms (soft-NMS): use run(frame)")
         shapes = {tuple(f.shape) for f in frames}
         if len(shapes) != 1:
             raise ValueError("run_frames needs frames of one size")
         (H, W, C), = shapes
         if C != 3 or any(f.dtype != np.uint8 for f in frames):
             raise ValueError("run_frames needs (H, W, 3) uint8 BGR frames")
-        key = (len(frames), H, W, self.scales[0], depth)
+        flip = bool(self.opt.flip_test)
+        key = (len(frames), H, W, tuple(self.scales), flip, bool(getattr(self.opt, "nms", False)), depth)
         pipes = self.__dict__.setdefault("_pipes", {})
         if key not in pipes:
             if len(pipes) >= 4:
                 pipes.pop(next(iter(pipes))).pool.shutdown(wait=False)
-            pipes[key] = _FramePipe(self, len(frames), H, W, self.scales[0], depth)
+            pipes[key] = _FramePipe(self, len(frames), H, W, self.scales, flip, depth)
         return pipes[key]
 
     def run_frames(self, frames):
         """A list of (H, W, 3) uint8 BGR frames of one size -> list of per-image results, what
-        ``run(frame)['results']`` returns for each (single scale, no flip).  The reference's
-        test loop is batch_size = 1 (test.py:60-62); here the frames are uploaded as ONE uint8
-        copy, pre-processed on the device in one launch straight into one batch tensor, the whole
-        batch goes through the network + decode once (``run_batch``) and, for ctdet, through the
-        device tail (inverse affine + class grouping); the host slices the result."""
+        ``run(frame)['results']`` returns for each (every test scale, flip-test and --nms as set).
+        The reference's test loop is batch_size = 1 (test.py:60-62); here the frames are uploaded as
+        ONE uint8 copy, pre-processed on the device in one launch per test scale straight into one
+        batch tensor (with flip-test: frame, mirror, frame, mirror, ...), each scale's batch goes
+        through the network + flip average + decode once and, for ctdet, through the device tail
+        (inverse affine + class grouping) and the device scale merge; the host slices the result."""
         pipe = self._pipe_for(frames, 1)
         pipe.submit(0, frames)
         return pipe.collect(0, frames)

@@ -8,7 +8,7 @@ import torch
 
 from ..decode import ctdet_decode
 from ..post_process import ctdet_results_batch
-from ..utils import flip_average
+from ..utils import flip_average, flip_average_batch
 from .base_detector import BaseDetector
 
 
@@ -101,32 +101,73 @@ class CtdetDetector(BaseDetector):
             probe['dec_events'] = (e0, e1)
             return dets
 
+    def _run_scale(self, images, flip):
+        """One test scale of the frame pipeline: ``run_batch``, or with ``flip`` the (2B, 3, H, W)
+        frame / mirror pairs -> network -> batched flip average (``hm`` after the sigmoid, ``reg`` of
+        the un-mirrored frame, as ``process``) -> decode: (B, K, 6), asynchronous."""
+        if not flip:
+            return self.run_batch(images)
+        self._note_unchecked_forward()
+        with torch.no_grad():
+            out = self.model(images, borrow=True)[-1]
+            hm = flip_average_batch(out['hm'], sigmoid=True)
+            wh = flip_average_batch(out['wh'])
+            reg = flip_average_batch(out['reg'], first=True) if self.opt.reg_offset else None
+            return self._decode(hm, wh, reg, False)
+
     # ---- device tail of the frame pipeline (base_detector._FramePipe)
     def _device_tail_alloc(self, pipe):
-        """Buffers of cn_ctdet_post_process_f32 for one pipe, or None when the host tail has to
-        serve it (more detections than the kernel takes or than max_per_image keeps)."""
+        """Buffers of cn_ctdet_post_process_f32 (one slice per test scale) and of cn_ctdet_merge_f32
+        for one pipe, or None when the host tail has to serve it (more detections than the kernels
+        take or than max_per_image keeps)."""
+        from .. import native
         from ..image import get_affine_transform
-        K, nc, B, dev = self.opt.K, self.opt.num_classes, pipe.B, self.opt.device
+        K, nc, B, dev, S = self.opt.K, self.opt.num_classes, pipe.B, self.opt.device, len(pipe.scales)
         if K > 128 or K > self.max_per_image:
             return None
-        m = pipe.meta
-        to_source = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
-        t = {'to_source': torch.from_numpy(np.ascontiguousarray(to_source, np.float64).reshape(-1)).to(dev),
-             'rows': torch.empty((B, K, 5), device=dev, dtype=torch.float32),
-             'bounds': torch.empty((B, nc + 1), device=dev, dtype=torch.int32),
-             'rows_host': [torch.empty((B, K, 5), dtype=torch.float32).pin_memory() for _ in range(pipe.depth)],
+        if pipe.merge and (S * K > native.MERGE_MAX_ROWS or nc > native.MERGE_MAX_CLASSES):
+            return None
+        to_source = []
+        for lv in pipe.levels:
+            m = lv.meta
+            t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+            to_source.append(torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev))
+        R = S * K if pipe.merge else K
+        t = {'to_source': to_source,
+             'rows': torch.empty((S, B, K, 5), device=dev, dtype=torch.float32),
+             'bounds': torch.empty((S, B, nc + 1), device=dev, dtype=torch.int32),
+             'rows_host': [torch.empty((B, R, 5), dtype=torch.float32).pin_memory() for _ in range(pipe.depth)],
              'bounds_host': [torch.empty((B, nc + 1), dtype=torch.int32).pin_memory() for _ in range(pipe.depth)]}
+        if pipe.merge:
+            t['merged_rows'] = torch.empty((B, R, 5), device=dev, dtype=torch.float32)
+            t['merged_bounds'] = torch.empty((B, nc + 1), device=dev, dtype=torch.int32)
         return t
 
-    def _device_tail_run(self, pipe, slot, dets):
+    def _device_tail_run(self, pipe, slot, level, dets):
+        """Test scale ``level``: raw detections -> source pixels / scale, grouped by class, into slice
+        ``level`` of the tail's rows / bounds."""
         from .. import native
         t, K, nc = pipe.tail, self.opt.K, self.opt.num_classes
         dets = dets.contiguous()
         native.check(native.lib().cn_ctdet_post_process_f32(
-            native.ptr(dets), pipe.B, K, nc, native.ptr(t['to_source']), 0, float(pipe.scale),
-            native.ptr(t['rows']), native.ptr(t['bounds']), native.stream_ptr()), "cn_ctdet_post_process_f32")
-        t['rows_host'][slot].copy_(t['rows'], non_blocking=True)
-        t['bounds_host'][slot].copy_(t['bounds'], non_blocking=True)
+            native.ptr(dets), pipe.B, K, nc, native.ptr(t['to_source'][level]), 0, float(pipe.levels[level].scale),
+            native.ptr(t['rows'][level]), native.ptr(t['bounds'][level]), native.stream_ptr()),
+            "cn_ctdet_post_process_f32")
+
+    def _device_tail_finish(self, pipe, slot):
+        """After the last test scale: the scale merge (merge_outputs on the device) when there is
+        one to do, then the copies into the slot's pinned buffers."""
+        from .. import native
+        t = pipe.tail
+        rows, bounds = t['rows'][0], t['bounds'][0]
+        if pipe.merge:
+            rows, bounds = t['merged_rows'], t['merged_bounds']
+            native.check(native.lib().cn_ctdet_merge_f32(
+                native.ptr(t['rows']), native.ptr(t['bounds']), len(pipe.scales), pipe.B, self.opt.K,
+                self.opt.num_classes, int(bool(self.opt.nms)), self.max_per_image, native.ptr(rows),
+                native.ptr(bounds), native.stream_ptr()), "cn_ctdet_merge_f32")
+        t['rows_host'][slot].copy_(rows, non_blocking=True)
+        t['bounds_host'][slot].copy_(bounds, non_blocking=True)
 
     def _device_tail_results(self, pipe, slot, n):
         """Per image ``{class: (n, 5) float32}`` -- the rows are already in source pixels and grouped
@@ -143,3 +184,7 @@ class CtdetDetector(BaseDetector):
     def results_batch(self, dets, metas, scale):
         """Host tail of ``run_frames``: (B, K, 6) host array -> per-image ``{class: (n, 5)}``."""
         return ctdet_results_batch(dets, metas, self.opt.num_classes, scale, self.max_per_image)
+
+    def _post_batch(self, dets, metas, scale):
+        """``post_process`` of every image of a (B, K, 6) host array (no cut: merge_outputs makes it)."""
+        return ctdet_results_batch(dets, metas, self.opt.num_classes, scale, max_per_image=dets.shape[1])

@@ -8,7 +8,7 @@ import torch
 
 from ..decode import multi_pose_decode
 from ..post_process import multi_pose_post_process
-from ..utils import flip_average
+from ..utils import flip_average, flip_average_batch
 from .base_detector import BaseDetector
 
 ROW = 39  # [x1, y1, x2, y2, score, 17 x (x, y)]
@@ -83,10 +83,26 @@ class MultiPoseDetector(BaseDetector):
                 probe['dec_events'] = (e0, e1)
             return dets
 
-    def results_batch(self, dets, metas, scale):
-        """Host tail of ``run_frames``: (B, K, 40) host array -> per image ``{1: [[x1, y1, x2,
-        y2, score, 17 x (x, y)], ...]}``, i.e. merge_outputs([post_process(...)]) for one scale
-        without NMS (multi_pose.py:62-81)."""
+    def _run_scale(self, images, flip):
+        """One test scale of the frame pipeline: ``run_batch``, or with ``flip`` the (2B, 3, H, W)
+        frame / mirror pairs -> network -> batched flip average (sigmoids in the flip kernel, joints
+        exchanged, offsets of the un-mirrored frame, as ``process``) -> decode: (B, K, 40)."""
+        if not flip:
+            return self.run_batch(images)
+        self._note_unchecked_forward()
+        opt = self.opt
+        with torch.no_grad():
+            o = self.model(images, borrow=True)[-1]
+            hm = flip_average_batch(o['hm'], sigmoid=True)
+            wh = flip_average_batch(o['wh'])
+            hps = flip_average_batch(o['hps'], self.flip_idx, offsets=True)
+            hm_hp = flip_average_batch(o['hm_hp'], self.flip_idx, sigmoid=not opt.mse_loss) if opt.hm_hp else None
+            reg = flip_average_batch(o['reg'], first=True) if opt.reg_offset else None
+            hp_offset = flip_average_batch(o['hp_offset'], first=True) if opt.reg_hp_offset else None
+            return multi_pose_decode(hm, wh, hps, reg=reg, hm_hp=hm_hp, hp_offset=hp_offset, K=opt.K)
+
+    def _post_batch(self, dets, metas, scale):
+        """``post_process`` of every image of a (B, K, 40) host array: per image ``{1: (K, 39)}``."""
         per = multi_pose_post_process(dets.copy(), [m['c'] for m in metas], [m['s'] for m in metas],
                                       metas[0]['out_height'], metas[0]['out_width'])
         out = []
@@ -94,8 +110,14 @@ class MultiPoseDetector(BaseDetector):
             rows = np.array(d[1], dtype=np.float32).reshape(-1, ROW)
             rows[:, :4] /= scale
             rows[:, 5:] /= scale
-            out.append({1: rows.tolist()})
+            out.append({1: rows})
         return out
+
+    def results_batch(self, dets, metas, scale):
+        """Host tail of ``run_frames``: (B, K, 40) host array -> per image ``{1: [[x1, y1, x2,
+        y2, score, 17 x (x, y)], ...]}``, i.e. merge_outputs([post_process(...)]) for one scale
+        without NMS (multi_pose.py:62-81)."""
+        return [{1: d[1].tolist()} for d in self._post_batch(dets, metas, scale)]
 
     def post_process(self, dets, meta, scale=1):
         """Output-grid units -> image coordinates of the unscaled frame (multi_pose.py:62-72)."""

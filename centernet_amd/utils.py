@@ -45,4 +45,28 @@ def flip_average(pair, flip_idx=None, offsets=False, sigmoid=False):
     return out
 
 
+def flip_average_batch(pairs, flip_idx=None, offsets=False, sigmoid=False, first=False):
+    """``flip_average`` for P pairs at once: ``pairs`` (2P, C, H, W) fp32 on the device, laid out [f0, f0
+    mirrored, f1, f1 mirrored, ...] (the batched pre-process with flip_concat) -> (P, C, H, W), pair p
+    bit-identical to ``flip_average(pairs[2p:2p + 2], ...)``.  ``first``: image 0 of every pair instead
+    (``reg[0:1]`` of the reference), one launch like the average."""
+    if pairs.dim() != 4 or pairs.shape[0] % 2 or pairs.dtype != torch.float32 or not pairs.is_cuda \
+            or not pairs.is_contiguous():
+        raise ValueError("flip_average_batch needs a contiguous (2P, C, H, W) fp32 HIP tensor")
+    N, C, H, W = pairs.shape
+    src = sign = None
+    if not first:
+        key = (C, None if flip_idx is None else tuple(map(tuple, flip_idx)), bool(offsets), str(pairs.device))
+        tabs = _TABLES.get(key)
+        if tabs is None:
+            tabs = _TABLES[key] = _tables(C, flip_idx, offsets, pairs.device)
+        src, sign = tabs
+    out = torch.empty((N // 2, C, H, W), device=pairs.device, dtype=torch.float32)
+    native.check(native.lib().cn_flip_average_f32_batch(native.ptr(pairs), native.ptr(out), N // 2, C, H, W,
+                                                        native.ptr(src), native.ptr(sign), int(bool(sigmoid)),
+                                                        1 if first else 0, native.stream_ptr()),
+                 "cn_flip_average_f32_batch")
+    return out
+
+
 _TABLES = {}

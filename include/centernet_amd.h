@@ -262,6 +262,13 @@ int cn_range_fold_digest(uint32_t *cur, uint32_t *hi, uint32_t *lo, uint32_t *su
  * chan_src must then be a permutation. */
 int cn_flip_average_f32(float *x_pair, float *out, int C, int H, int W, const int32_t *chan_src,
                         const float *chan_sign, int apply_sigmoid, void *stream);
+/* The same for P pairs at once (flip-test of a batch).  x_pairs (2P, C, H, W) = [f0, f0 mirrored, f1, f1
+ * mirrored, ...], the layout of cn_warp_normalize_u8_f32_batch(..., flip_concat = 1); out (P, C, H, W).
+ * mode 0: the average above, pair p bit-identical to cn_flip_average_f32 on that pair (which is the
+ * P = 1 call of this one); mode 1: out[p] = image 0 of pair p (reg / hp_offset, which the reference takes
+ * from the un-mirrored frame only), chan_src, chan_sign and apply_sigmoid unused. */
+int cn_flip_average_f32_batch(float *x_pairs, float *out, int P, int C, int H, int W, const int32_t *chan_src,
+                              const float *chan_sign, int apply_sigmoid, int mode, void *stream);
 /* Box calibration (bench.py `box_calibration`; measurement aid, not on the product path; no
  * reference counterpart).  cn_calib_mfma_f16: a register-only v_mfma_f32_32x32x16_f16 loop on
  * every SIMD (1024 workgroups x 4 waves, `iters` x 16 instructions per wave); returns the FLOPs
@@ -501,6 +508,18 @@ int cn_warp_normalize_u8_f32_batch(const uint8_t *images_hwc, int N, size_t imag
  * Bit-identical to the reference's float64 affine + float32 rounding. */
 int cn_ctdet_post_process_f32(const float *dets, int B, int K, int num_classes, const double *to_source_2x3,
                               int per_image, float scale, float *rows, int32_t *bounds, void *stream);
+/* The ctdet scale merge (CtdetDetector.merge_outputs, detectors/ctdet.py:58-73) on the device, bit for bit.
+ * rows (S, B, K, 5) / bounds (S, B, num_classes + 1): cn_ctdet_post_process_f32's output of test scale s in
+ * slice s.  Per image: per class the rows of all scales in scale order; when S > 1 or apply_nms, Gaussian
+ * soft-NMS of every class (sigma 0.5, threshold 0.001, the arithmetic of cn_soft_nms_f32, the whole in-place
+ * array kept as the reference keeps it); then, when the image has more than max_per_image rows, the rows
+ * whose score is >= the max_per_image-th largest score (ties kept), in order.  out_rows (B, S*K, 5) /
+ * out_bounds (B, num_classes + 1): the tail's format.  Row cap: S*K <= CN_MERGE_MAX_ROWS and num_classes
+ * <= CN_MERGE_MAX_CLASSES, CN_ERR_SHAPE above (one workgroup holds an image's rows in LDS). */
+#define CN_MERGE_MAX_ROWS 2048
+#define CN_MERGE_MAX_CLASSES 1024
+int cn_ctdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int K, int num_classes,
+                       int apply_nms, int max_per_image, float *out_rows, int32_t *out_bounds, void *stream);
 int cn_resize_bilinear_u8(const uint8_t *image_hwc, int H, int W, int pitch_bytes, int out_h,
                           int out_w, uint8_t *out_hwc, void *stream);
 
