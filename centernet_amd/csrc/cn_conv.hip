@@ -26,7 +26,8 @@
 // conflicts, and one b128 read feeds four consecutive MFMAs because K is
 // consumed in the order {k, k+4}: lane half h holds k = 4h..4h+3 of each 8-group
 // for both operands (any fixed K permutation is a valid dot-product order).
-#include "cn_common.h"
+#include "cn_internal.h"
+#include "cn_tuning.h"
 #include <type_traits>
 
 // f32s implicit GEMM: register sets of the tile prefetch.  2 = tiles requested two chunks ahead:
@@ -758,24 +759,6 @@ constexpr size_t igemm_lds_bytes()
            (AMODE == A_STEM ? (size_t)STEM_KMAX * 8 : 0);
 }
 
-int g_tune_setprio = 1; // cn_set_tuning key 8: s_setprio(1) around the MFMA clusters (+0.9 % measured)
-int g_tune_dbgskip = 0; // cn_set_tuning key 9 (ablation only): bit0 skip A staging, bit1 skip B staging
-int g_tune_swz = 0;   // cn_set_tuning key 7: XCD-aware tile order, 0 = deformable kernel only (default), 1 = all, 2 = none
-int g_tune_nbuf = 0;  // 0 = per-shape default, 1 / 2 = force (cn_set_tuning key 1)
-int g_tune_narrow = 0; // cn_set_tuning key 2: 0 = default, 1 = never prefer 64-wide tiles
-int g_tune_bm = 0;       // cn_set_tuning key 4: 0 = default, 64 / 128 = force the dense pixel tile
-int g_tune_nosplit = 0;  // cn_set_tuning key 5: 1 = never split K
-int g_tune_stem_persist = 1; // cn_set_tuning key 12: persistent, prefetching stem kernel (cn_stem.hip)
-int g_tune_dcn_split = 0;   // cn_set_tuning key 13: 0 = auto, 1 = never, 3 / 9 = force tap split of the deformable kernel
-int g_tune_bm256 = 0;       // cn_set_tuning key 14: 1 = 256-pixel tiles for 64-wide layers in the halo kernel (no gain, measured)
-int g_tune_waves8 = 1;      // cn_set_tuning key 15: 8-wave workgroups for the 128-wide halo tiles
-int g_tune_occ4 = 0;        // cn_set_tuning key 19: 4-workgroups-per-CU form of the 64-wide halo tiles: 0 = by rounds rule, 1 = always, 2 = never
-int g_tune_dcn_form = 0;   // cn_set_tuning key 23: f32s deformable kernel, 0 = by shape and grid (team form per key 36, else the register-sampling window form, else the gather form), 1 = global-gather form always, 2 = register-sampling form (cn_dcn2.hip) for every shape it takes, 4 / 5 = team form (cn_dcn3.hip) in T / N mode for every shape it takes, 6 / 7 = wide form (cn_dcn4.hip; 7: four blocks per workgroup) for every shape it takes
-int g_tune_stem16s = 1;     // cn_set_tuning key 27: f32s form of the stride-1 16-channel stem (DLA base_layer); 0 = fp32 kernel
-int g_tune_dcn_tile2d = 1; // cn_set_tuning key 22: deformable kernel, 1 = 8-wide pixel blocks as tiles (default), 0 = row segments
-int g_tune_nohalo = 0;   // cn_set_tuning key 10: 1 = generic implicit GEMM for 3x3/s1 instead of cn_conv3x3.hip
-int g_tune_nostem = 0;   // cn_set_tuning key 6: 1 = generic implicit-GEMM stem instead of cn_stem.hip
-
 template <typename T, int BM, int BN, int WM, int WN, int AMODE, bool OUT_NCHW, int NBUF>
 int launch_igemm_n(const IgemmArgs &a, hipStream_t st)
 {
@@ -787,9 +770,9 @@ int launch_igemm_n(const IgemmArgs &a, hipStream_t st)
     // ~36x; with round-robin tile -> XCD placement only 31 % of those hit the 4 MB L2, measured
     // TCC_HIT/TCC_MISS; contiguous tile ranges per XCD: +5-10 %, tools/bench_dcn.py SWZ=1);
     // cn_set_tuning key 7: 0 = default, 1 = also the dense kernels, 2 = nowhere
-    b.xcd_swizzle = (grid.x >= 16 && g_tune_swz != 2 && (AMODE == A_DCN || AMODE == A_DCN_PAD || g_tune_swz == 1)) ? 1 : 0;
-    b.setprio = g_tune_setprio;
-    b.dbgskip = g_tune_dbgskip;
+    b.xcd_swizzle = (grid.x >= 16 && cn_knobs.swz != 2 && (AMODE == A_DCN || AMODE == A_DCN_PAD || cn_knobs.swz == 1)) ? 1 : 0;
+    b.setprio = cn_knobs.setprio;
+    b.dbgskip = cn_knobs.dbgskip;
     hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, AMODE, OUT_NCHW, NBUF>), grid, dim3(NT),
                        lds, st, b);
     CN_CHECK_LAUNCH();
@@ -811,7 +794,7 @@ template <int BM, int BN, int WM, int WN, int AMODE, bool OUT_NCHW>
 int launch_igemm_s(const IgemmArgs &a, hipStream_t st)
 {
     static_assert(AMODE != A_STEM, "the stem stays on the fp32 kernel");
-    if (!OUT_NCHW && a.stride == 1 && g_tune_nbuf != 2)
+    if (!OUT_NCHW && a.stride == 1 && cn_knobs.nbuf != 2)
         return launch_igemm_n<cn_f32s, BM, BN, WM, WN, AMODE, OUT_NCHW, 1>(a, st);
     return launch_igemm_n<cn_f32s, BM, BN, WM, WN, AMODE, OUT_NCHW, 2>(a, st);
 }
@@ -821,7 +804,7 @@ int launch_igemm(const IgemmArgs &a, hipStream_t st)
 {
     // measured on MI355X (tools/bench_kernels.py, profiles/): single-buffered LDS (more
     // workgroups per CU) wins for stride-1 layers, double-buffered for strided gathers
-    int nbuf = g_tune_nbuf ? g_tune_nbuf : (a.stride == 1 ? 1 : 2);
+    int nbuf = cn_knobs.nbuf ? cn_knobs.nbuf : (a.stride == 1 ? 1 : 2);
     if (AMODE == A_STEM || OUT_NCHW) nbuf = 2;  // only the NHWC dense / DCN kernels carry both forms
     if (nbuf == 1) {
         if constexpr (AMODE != A_STEM && !OUT_NCHW)
@@ -913,68 +896,6 @@ __global__ void pack_stem_weight_kernel(const float *__restrict__ w, T *__restri
 }
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-}  // namespace
-int cn_stem_conv_f32(const float *x, const float *w_packed, const float *scale, const float *shift,
-                     float *y, int B, int H, int W, int Ho, int Wo, int Cout, int KH, int KW,
-                     int stride, int pad, int relu, int out_pitch, int KP, int persistent,
-                     const cn_f32s_ctl *ctl, hipStream_t st);
-int cn_stem_pool_rows(int B, int Ho, int Wo, int Cout, int KH, int KW, int stride, int KP);
-int cn_stem_pool_f32s(const float *x, const float *w_packed, const float *scale, const float *shift,
-                      float *y, int B, int H, int W, int Ho, int Wo, int Cout, int KH, int KW,
-                      int stride, int pad, int relu, int out_pitch, int KP, int y_f32s, const cn_f32s_ctl *ctl,
-                      hipStream_t st);
-int cn_dcn_window_f32s(const float *x, const void *w_packed, const float *bias, const float *om,
-                       int om_pitch, const float *scale, const float *shift, void *y, int out_pitch,
-                       int out_plain, int B, int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
-                       float x_mul, uint32_t *range, int min_wgs, int dbg, float *partial,
-                       size_t partial_bytes, int *ksplit_out, hipStream_t st);
-bool cn_offconv_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int ksplit);
-int cn_offconv_f32s(const float *x, const void *w_packed, const float *scale, const float *shift, float *y,
-                    int B, int H, int W, int Cin, int Cout, int out_pitch, int relu, const cn_f32s_ctl *ctl,
-                    int ksplit, float *partial, hipStream_t st);
-extern int cn_tune_offconv, cn_tune_offconv_teams1;   // cn_offconv.hip
-int cn_dcn_team_f32s(const float *x, const void *w_packed, const float *bias, const float *om,
-                     int om_pitch, const float *scale, const float *shift, void *y, int out_pitch,
-                     int out_plain, int B, int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
-                     float x_mul, uint32_t *range, int nmode, int dbg, float *partial,
-                     size_t partial_bytes, int *ksplit_out, hipStream_t st);
-extern int cn_tune_dcn_team, cn_tune_dcn_team_wgs, cn_tune_dcn_team_stagger;   // cn_dcn3.hip
-int cn_dcn_wide_f32s(const float *x, const void *w_packed, const float *bias, const float *om,
-                     int om_pitch, const float *scale, const float *shift, void *y, int out_pitch,
-                     int out_plain, int B, int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
-                     float x_mul, uint32_t *range, int nb, int dbg, float *partial, size_t partial_bytes,
-                     int *ksplit_out, hipStream_t st);
-extern int cn_tune_dcn_wide, cn_tune_dcn_wide_wgs, cn_tune_dcn_wide_prefetch;   // cn_dcn4.hip
-bool cn_proj1x1_takes(int B, int H, int W, int Cin, int Cout, int stride, int in_pitch, int out_pitch);
-int cn_proj1x1_f32s(const void *x, const void *w_packed, const float *scale, const float *shift, void *y, int B, int H,
-                    int W, int Cin, int Cout, int stride, int in_pitch, int out_pitch, int relu, int out_plain,
-                    const cn_f32s_ctl *ctl, hipStream_t st);
-extern int cn_tune_proj;   // cn_proj.hip
-extern int cn_tune_stem_stagger, cn_tune_stem_dbg;                         // cn_stem.hip (probe instantiation of the stem + max-pool kernel)
-bool cn_conv3x3s2p_takes(int B, int Hi, int Wi, int Cin, int Cout, int in_pitch, int out_pitch);
-int cn_conv3x3s2_persist(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
-                         int B, int Hi, int Wi, int Cin, int Cout, int in_pitch, int out_pitch, int relu,
-                         int out_plain, const cn_f32s_ctl *ctl, hipStream_t st);
-int cn_conv3x3s1(const void *x, const void *w_packed, const float *scale, const float *shift,
-                 const void *residual, void *y, int B, int H, int W, int Cin, int Cout,
-                 int in_pitch, int out_pitch, int res_pitch, int relu, int vec_out, int setprio, int bn_class,
-                 int f16, const cn_f32s_ctl *ctl, hipStream_t st);
-int cn_conv3x3_c16(const float *x, const float *w_packed, const float *scale, const float *shift,
-                   float *y, int B, int H, int W, int Ho, int Wo, int Cin, int Cout, int stride,
-                   int in_pitch, int out_pitch, int relu, hipStream_t st);
-int cn_conv3x3_c16s(const float *x, const void *w_packed, const float *scale, const float *shift,
-                    float *y, int B, int H, int W, int Ho, int Wo, int Cin, int Cout, int stride,
-                    int in_pitch, int out_pitch, int relu, const cn_f32s_ctl *ctl, hipStream_t st);
-extern int cn_tune_stagger_pct;  // cn_conv3x3.hip
-extern int cn_tune_f32s_lds_weights;  // cn_conv3x3.hip
-extern int cn_tune_f32s_policy;       // cn_conv3x3.hip
-extern int cn_tune_heads_remap;       // cn_conv3x3.hip
-extern int cn_tune_heads_reg;         // cn_conv3x3.hip
-int cn_deconv4x4s2_halo(const void *x, const void *w_packed, const float *scale, const float *shift,
-                        void *y, int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch,
-                        int relu, int vec_out, int setprio, int dtype_flags, const cn_f32s_ctl *ctl,
-                        hipStream_t st);
-namespace {
 
 // split-K second stage: sum the partial tiles, then the usual epilogue
 // y = relu?((sum + bias) * scale + shift + residual), NHWC (element type T)
@@ -1040,15 +961,13 @@ __global__ void splitk_reduce_kernel(const IgemmArgs a)
 
 // How many K-splits a dense NHWC layer gets: enough workgroups to put ~2 on every CU,
 // at least 8 chunks of K per split, only when the plain grid is badly under-filled.
-int g_tune_split_min_chunks = 8;  // cn_set_tuning key 16: K chunks per split-K slice, at least
-int g_tune_split_max = 16;        // cn_set_tuning key 17: split-K slices, at most
 inline int plan_ksplit(int M, int Cout, int KT, int bm, int bn)
 {
     const long wgs = (long)cn_cdiv(M, bm) * cn_cdiv(Cout, bn);
     if (wgs >= 256 || KT < 16) return 1;
     int s = (int)((512 + wgs - 1) / wgs);
-    if (s > KT / g_tune_split_min_chunks) s = KT / g_tune_split_min_chunks;
-    if (s > g_tune_split_max) s = g_tune_split_max;
+    if (s > KT / cn_knobs.split_min_chunks) s = KT / cn_knobs.split_min_chunks;
+    if (s > cn_knobs.split_max) s = cn_knobs.split_max;
     return s < 2 ? 1 : s;
 }
 inline bool is_stem(int Cin, int in_layout) { return in_layout == CN_LAYOUT_NCHW && Cin == 3; }
@@ -1195,18 +1114,18 @@ static void dense_tile_class(const cn_conv_desc *d, const IgemmArgs &a, int *cls
     // 128-wide N tiles unless their padding wastes a whole 64-wide tile (e.g. Cout = 192)
     const int waste128 = cn_cdiv(d->Cout, 128) * 128 - d->Cout;
     const int waste64 = cn_cdiv(d->Cout, 64) * 64 - d->Cout;
-    const bool narrow = !g_tune_narrow && (waste128 - waste64 >= 64);
+    const bool narrow = !cn_knobs.narrow && (waste128 - waste64 >= 64);
     *cls = (d->Cout > 64 && !narrow) ? 2 : (d->Cout > 32 ? 1 : 0);
     // fewer than four workgroups per CU with 128-pixel tiles: halve the pixel tile
     const long wgs128 = (long)cn_cdiv(a.M, 128) * cn_cdiv(d->Cout, 128) * (a.zparity ? 4 : 1);
     // ... unless the 128-pixel grid is exactly one round of two workgroups per CU (512): then the
     // 64-pixel grid (1024 at three per CU = 1.33 rounds) loses (128->256/s2@32^2: 0.210 -> 0.183 ms)
-    *bm64 = (*cls == 2) && (g_tune_bm ? (g_tune_bm == 64) : (wgs128 < 1024 && wgs128 != 512));
+    *bm64 = (*cls == 2) && (cn_knobs.bm ? (cn_knobs.bm == 64) : (wgs128 < 1024 && wgs128 != 512));
 }
 
 static int dense_ksplit(const cn_conv_desc *d, const IgemmArgs &a)
 {
-    if (g_tune_nosplit || d->out_layout != CN_LAYOUT_NHWC || is_stem(d->Cin, d->in_layout) ||
+    if (cn_knobs.nosplit || d->out_layout != CN_LAYOUT_NHWC || is_stem(d->Cin, d->in_layout) ||
         a.zparity)
         return 1;
     int cls;
@@ -1229,7 +1148,7 @@ extern "C" int cn_conv2d_res_pitch_supported(const cn_conv_desc *d)
 {
     IgemmArgs a = {};
     if (!d || conv_fill_args(d, &a) != CN_OK) return 0;
-    if (g_tune_nohalo || !is_3x3s1(d) || is_stem(d->Cin, d->in_layout) || d->out_layout != CN_LAYOUT_NHWC) return 0;
+    if (cn_knobs.nohalo || !is_3x3s1(d) || is_stem(d->Cin, d->in_layout) || d->out_layout != CN_LAYOUT_NHWC) return 0;
     if (d->dtype == CN_DTYPE_F32 && d->Cin == 16 && d->Cout <= 32) return 0;     // cn_conv16.hip
     if (d->dtype == CN_DTYPE_F32S && (d->flags & CN_CONV_X_PLAIN) && (d->flags & CN_CONV_Y_PLAIN) && d->Cin == 16 &&
         d->Cout <= 32)
@@ -1322,12 +1241,12 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
                                      d->KW, d->stride, d->pad_h, d->relu, d->out_pitch, a.cin_pad,
                                      (d->flags & CN_CONV_STEM_Y_F32S) ? 1 : 0, &d->ctl, st);
         }
-        if (!g_tune_nostem && d->pad_h == d->pad_w && d->dil == 1 && d->oy_mul == 1 &&
+        if (!cn_knobs.nostem && d->pad_h == d->pad_w && d->dil == 1 && d->oy_mul == 1 &&
             d->ox_mul == 1 && d->OH == d->Ho && d->OW == d->Wo) {
             rc = cn_stem_conv_f32((const float *)x, (const float *)w_packed, scale, shift,
                                   (float *)y, d->B, d->H, d->W, d->Ho, d->Wo, d->Cout, d->KH,
                                   d->KW, d->stride, d->pad_h, d->relu, d->out_pitch, a.cin_pad,
-                                  g_tune_stem_persist | ((d->flags & CN_CONV_STEM_F32S) ? 2 : 0), &d->ctl, st);
+                                  cn_knobs.stem_persist | ((d->flags & CN_CONV_STEM_F32S) ? 2 : 0), &d->ctl, st);
             if (rc != CN_ERR_UNSUPPORTED) return rc;
         }
         if (d->Cout > 64) return launch_igemm<128, 128, 2, 2, A_STEM, false>(a, st);
@@ -1335,7 +1254,7 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
         return launch_igemm<128, 32, 4, 1, A_STEM, false>(a, st);
     }
     // 16-channel input, <= 32 output channels (DLA level0 / level1): cn_conv16.hip
-    if (!g_tune_nohalo && !f16 && !f32s && !residual && a.ksplit == 1 && d->Cin == 16 && d->Cout <= 32 &&
+    if (!cn_knobs.nohalo && !f16 && !f32s && !residual && a.ksplit == 1 && d->Cin == 16 && d->Cout <= 32 &&
         d->KH == 3 && d->KW == 3 && d->pad_h == 1 && d->pad_w == 1 && d->dil == 1 &&
         d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 && d->ox_add == 0 && d->OH == d->Ho &&
         d->OW == d->Wo && d->in_layout == CN_LAYOUT_NHWC) {
@@ -1345,7 +1264,7 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
         if (rc != CN_ERR_UNSUPPORTED) return rc;
     }
     // the same layers in f32s arithmetic: plain input split while staged, plain output (cn_conv16.hip)
-    if (!g_tune_nohalo && f32s && (d->flags & CN_CONV_X_PLAIN) && (d->flags & CN_CONV_Y_PLAIN) && !residual &&
+    if (!cn_knobs.nohalo && f32s && (d->flags & CN_CONV_X_PLAIN) && (d->flags & CN_CONV_Y_PLAIN) && !residual &&
         a.ksplit == 1 && d->Cin == 16 && d->Cout <= 32 && d->KH == 3 && d->KW == 3 && d->pad_h == 1 &&
         d->pad_w == 1 && d->dil == 1 && d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 &&
         d->ox_add == 0 && d->OH == d->Ho && d->OW == d->Wo && d->in_layout == CN_LAYOUT_NHWC) {
@@ -1370,17 +1289,15 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
     }
     // 3x3 / stride 1 / pad 1: the LDS-halo kernel (cn_conv3x3.hip) unless split-K applies
     const int res_pitch = d->res_pitch > 0 ? d->res_pitch : d->out_pitch;
-    const bool to_halo = !g_tune_nohalo && a.ksplit == 1 && is_3x3s1(d);
+    const bool to_halo = !cn_knobs.nohalo && a.ksplit == 1 && is_3x3s1(d);
     // a residual at its own pixel pitch (channel slices of wider tensors): only the 3x3 / s1 kernels
     if (residual && res_pitch != d->out_pitch && !to_halo) return CN_ERR_UNSUPPORTED;
     if (to_halo)
         return cn_conv3x3s1(x, w_packed, scale, shift, residual, y, d->B, d->H, d->W, d->Cin,
-                            d->Cout, d->in_pitch, d->out_pitch, res_pitch, d->relu, a.vec_out,
-                            g_tune_setprio | ((g_tune_bm256 & 1) << 1) | ((g_tune_bm256 >> 1) << 3) | (g_tune_waves8 << 2) | (g_tune_occ4 << 7) |
-                                ((g_tune_dbgskip & 7) << 4) | ((g_tune_dbgskip >> 3) << 9), cls, d->dtype | (d->flags << 8),
+                            d->Cout, d->in_pitch, d->out_pitch, res_pitch, d->relu, a.vec_out, cls, d->dtype, d->flags,
                             &d->ctl, st);
     // 3x3 / stride 2 / pad 1, f32s tensors on both sides: the persistent kernel's parity-plane form
-    if (!g_tune_nohalo && f32s && !(d->flags & (CN_CONV_X_PLAIN | CN_CONV_R_PLAIN)) && !residual && scale &&
+    if (!cn_knobs.nohalo && f32s && !(d->flags & (CN_CONV_X_PLAIN | CN_CONV_R_PLAIN)) && !residual && scale &&
         a.vec_out && d->KH == 3 && d->KW == 3 && d->stride == 2 && d->pad_h == 1 && d->pad_w == 1 && d->dil == 1 &&
         d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 && d->ox_add == 0 && d->OH == d->Ho && d->OW == d->Wo &&
         d->in_layout == CN_LAYOUT_NHWC && d->out_layout == CN_LAYOUT_NHWC &&
@@ -1448,8 +1365,8 @@ extern "C" int cn_conv2d_f32(const cn_conv_desc *d, const float *x, const float 
 // splitting the 9 taps over 3 or 9 workgroups per tile (fp32 partial sums + reduce kernel).
 static int dcn_ksplit(int B, int H, int W, int Cout)
 {
-    if (g_tune_nosplit || g_tune_dcn_split == 1) return 1;
-    if (g_tune_dcn_split == 3 || g_tune_dcn_split == 9) return g_tune_dcn_split;
+    if (cn_knobs.nosplit || cn_knobs.dcn_split == 1) return 1;
+    if (cn_knobs.dcn_split == 3 || cn_knobs.dcn_split == 9) return cn_knobs.dcn_split;
     const long wgs = (long)cn_cdiv(B * H * W, 64) * cn_cdiv(Cout, Cout > 64 ? 128 : 64);
     if (wgs >= 1024) return 1;
     return wgs * 3 >= 600 ? 3 : 9;  // measured (tools/bench_dcn.py): 3 wins from ~2 workgroups/CU
@@ -1496,38 +1413,38 @@ extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weigh
     if ((long)B * H * W * (long)(Cin > out_pitch ? Cin : out_pitch) >= (1L << 30)) return CN_ERR_UNSUPPORTED;  // 32-bit byte offsets
     // f32s: the LDS-window forms (cn_dcn3.hip team form, cn_dcn2.hip register-sampling form) for every
     // shape they take and every grid that fills the chip; the gather form below (tap split) serves the rest
-    if (f32s && g_tune_dcn_form != 1) {
-        const bool forced = g_tune_dcn_form >= 2;
-        const bool ws_ok = workspace && cn_aligned16(workspace) && !g_tune_nosplit;
+    if (f32s && cn_knobs.dcn_form != 1) {
+        const bool forced = cn_knobs.dcn_form >= 2;
+        const bool ws_ok = workspace && cn_aligned16(workspace) && !cn_knobs.nosplit;
         int ks = 1;
         int rc = CN_ERR_UNSUPPORTED;
         // team form: forced by key 23 = 4 (T mode) / 5 (N mode), or chosen by key 36 for grids that fill the chip
         const long tiles128 = (long)B * (H / 8) * (W / 16);
-        const bool team_auto = g_tune_dcn_form == 0 && tiles128 >= 64 &&
-                               ((cn_tune_dcn_team == 1 && Cout <= 64) || cn_tune_dcn_team >= 2);
+        const bool team_auto = cn_knobs.dcn_form == 0 && tiles128 >= 64 &&
+                               ((cn_knobs.dcn_team == 1 && Cout <= 64) || cn_knobs.dcn_team >= 2);
         // wide form (cn_dcn4.hip): every sample once per tile for ALL output channels; Cout % 128 == 0
-        const bool wide_auto = g_tune_dcn_form == 0 && cn_tune_dcn_wide && tiles128 >= 64 && (Cout & 127) == 0 && !g_tune_dbgskip;
-        if (g_tune_dcn_form == 6 || g_tune_dcn_form == 7 || wide_auto)
+        const bool wide_auto = cn_knobs.dcn_form == 0 && cn_knobs.dcn_wide && tiles128 >= 64 && (Cout & 127) == 0 && !cn_knobs.dbgskip;
+        if (cn_knobs.dcn_form == 6 || cn_knobs.dcn_form == 7 || wide_auto)
             rc = cn_dcn_wide_f32s(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift,
                                   output_nhwc, out_pitch, (flags & CN_CONV_Y_PLAIN) ? 1 : 0, B, Cin, H, W, Cout,
                                   mask_sigmoid, relu, (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f,
-                                  ctl ? ctl->range : nullptr, g_tune_dcn_form == 7 ? 4 : 0, g_tune_dbgskip,
+                                  ctl ? ctl->range : nullptr, cn_knobs.dcn_form == 7 ? 4 : 0, cn_knobs.dbgskip,
                                   ws_ok ? (float *)workspace : nullptr, ws_ok ? workspace_bytes : 0, &ks,
                                   (hipStream_t)stream);
-        if (rc == CN_ERR_UNSUPPORTED && (g_tune_dcn_form == 4 || g_tune_dcn_form == 5 || team_auto))
+        if (rc == CN_ERR_UNSUPPORTED && (cn_knobs.dcn_form == 4 || cn_knobs.dcn_form == 5 || team_auto))
             rc = cn_dcn_team_f32s(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift,
                                   output_nhwc, out_pitch, (flags & CN_CONV_Y_PLAIN) ? 1 : 0, B, Cin, H, W, Cout,
                                   mask_sigmoid, relu, (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f,
                                   ctl ? ctl->range : nullptr,
-                                  g_tune_dcn_form == 5 ? 2 : ((team_auto && cn_tune_dcn_team == 3) ? 1 : 0), g_tune_dbgskip,
+                                  cn_knobs.dcn_form == 5 ? 2 : ((team_auto && cn_knobs.dcn_team == 3) ? 1 : 0), cn_knobs.dbgskip,
                                   ws_ok ? (float *)workspace : nullptr, ws_ok ? workspace_bytes : 0, &ks,
                                   (hipStream_t)stream);
-        if (rc == CN_ERR_UNSUPPORTED && g_tune_dcn_form < 4)
+        if (rc == CN_ERR_UNSUPPORTED && cn_knobs.dcn_form < 4)
             rc = cn_dcn_window_f32s(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch,
                                     scale, shift, output_nhwc, out_pitch,
                                     (flags & CN_CONV_Y_PLAIN) ? 1 : 0, B, Cin, H, W, Cout,
                                     mask_sigmoid, relu, (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f,
-                                    ctl ? ctl->range : nullptr, forced ? 1 : 192, g_tune_dbgskip,
+                                    ctl ? ctl->range : nullptr, forced ? 1 : 192, cn_knobs.dbgskip,
                                     ws_ok ? (float *)workspace : nullptr, ws_ok ? workspace_bytes : 0,
                                     &ks, (hipStream_t)stream);
         if (rc == CN_OK && ks > 1) {
@@ -1569,7 +1486,7 @@ extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weigh
     hipStream_t st = (hipStream_t)stream;
     // tiles as pixel blocks (8 x 8, or 8 x 16 for the 128-pixel tiles of Cout <= 32) when the map
     // divides into them
-    a.tile2d = (g_tune_dcn_tile2d && (W & 7) == 0 && (H % (Cout > 32 ? 8 : 16)) == 0) ? 1 : 0;
+    a.tile2d = (cn_knobs.dcn_tile2d && (W & 7) == 0 && (H % (Cout > 32 ? 8 : 16)) == 0) ? 1 : 0;
     // 64-pixel tiles: 128-pixel tiles were measured slower at every CenterNet shape
     // (tools/bench_dcn.py) and are no longer built
     // tap split (needs the caller's workspace; without one the layer runs unsplit)
@@ -1726,10 +1643,9 @@ extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, 
     hipStream_t st = (hipStream_t)stream;
     // LDS-halo form (cn_conv3x3.hip) unless disabled (cn_set_tuning key 10) or the tile would be
     // mostly padding (Cout <= 32)
-    if (!g_tune_nohalo && Cout > 32 && a.vec_out && (in_pitch & 3) == 0)
+    if (!cn_knobs.nohalo && Cout > 32 && a.vec_out && (in_pitch & 3) == 0)
         return cn_deconv4x4s2_halo(x_nhwc, w_packed, scale, shift, y_nhwc, B, H, W, Cin, Cout,
-                                   in_pitch, out_pitch, relu, a.vec_out,
-                                   g_tune_setprio | (g_tune_occ4 << 7), dtype | (flags << 8), ctl, st);
+                                   in_pitch, out_pitch, relu, a.vec_out, dtype, flags, ctl, st);
     if (f32s) {
         if (Cout > 64) return launch_igemm_s<128, 128, 2, 2, A_DENSE, false>(a, st);
         if (Cout > 32) return launch_igemm_s<128, 64, 2, 2, A_DENSE, false>(a, st);
@@ -1757,186 +1673,48 @@ extern "C" int cn_stem_f32s_supported(const cn_conv_desc *d)
     const int kp = round_up(d->KH * d->KW * 3, 32);
     if (kp > STEM_KMAX) return 0;
     if (d->flags & CN_CONV_STEM_MAXPOOL) return cn_stem_maxpool_supported(d);
-    if (g_tune_nostem || !g_tune_stem_persist) return 0;
+    if (cn_knobs.nostem || !cn_knobs.stem_persist) return 0;
     if (d->oy_mul != 1 || d->ox_mul != 1 || d->OH != d->Ho || d->OW != d->Wo) return 0;
     // cn_stem_conv_f32: persistent 7x7 window kernel, rows of whole 128-pixel tiles, stride 2,
     // more than 16 output channels
     if (d->KH != 7 || d->KW != 7 || d->Wo % 128 != 0) return 0;
     if (d->stride == 2 && d->Cout > 16) return 1;
     // stem16s_kernel: stride 1, pad 3, <= 16 output channels (DLA base_layer)
-    return (d->stride == 1 && d->Cout <= 16 && d->pad_h == 3 && (d->W & 3) == 0 && g_tune_stem16s) ? 1 : 0;
+    return (d->stride == 1 && d->Cout <= 16 && d->pad_h == 3 && (d->W & 3) == 0 && cn_knobs.stem16s) ? 1 : 0;
 }
 
-extern int cn_tune_c3p, cn_tune_c3p_stagger, cn_tune_c3p_knobs, cn_tune_c3p_heads, cn_tune_c3p_deconv, cn_tune_c3p_s2;
+// ---- cn_set_tuning / cn_get_tuning / cn_reset_tuning: lookups in CN_TUNING_KEYS (cn_tuning.h)
+CnTuning cn_knobs = cn_tuning_defaults();
+
+static const CnTuningKey *tuning_key(int key)
+{
+    for (const CnTuningKey &k : CN_TUNING_KEYS)
+        if (k.key == key) return &k;
+    return nullptr;
+}
+
 extern "C" int cn_set_tuning(int key, int value)
 {
-    if (key == 28 && value >= 0 && value <= 7) {
-        cn_tune_c3p = value;
-        return CN_OK;
-    }
-    if (key == 29 && value >= 0 && value <= 255) {
-        cn_tune_c3p_stagger = value;
-        return CN_OK;
-    }
-    if (key == 30 && value >= 0 && value <= 255) {
-        cn_tune_c3p_knobs = value;
-        return CN_OK;
-    }
-    if (key == 31 && (value == 0 || value == 1)) {
-        cn_tune_c3p_heads = value;
-        return CN_OK;
-    }
-    if (key == 32 && (value == 0 || value == 1)) {
-        cn_tune_c3p_deconv = value;
-        return CN_OK;
-    }
-    if (key == 33 && (value == 0 || value == 1)) {
-        cn_tune_c3p_s2 = value;
-        return CN_OK;
-    }
+    const CnTuningKey *k = tuning_key(key);
+    if (!k) return CN_ERR_UNSUPPORTED;
+    bool ok = value >= k->lo && value <= k->hi;
+    for (int i = 0; i < k->n_also; ++i) ok = ok || value == k->also[i];
+    if (!ok) return CN_ERR_UNSUPPORTED;
+    if (k->field) cn_knobs.*k->field = value;
+    return CN_OK;
+}
 
-    if (key == 36 && value >= 0 && value <= 3) {
-        cn_tune_dcn_team = value;
-        return CN_OK;
-    }
-    if (key == 37 && value >= 1 && value <= 4096) {
-        cn_tune_dcn_team_wgs = value;
-        return CN_OK;
-    }
-    if (key == 39 && (value == 0 || value == 1)) {
-        cn_tune_offconv = value;
-        return CN_OK;
-    }
-    if (key == 40 && value >= 0 && value <= 1000000) {
-        cn_tune_offconv_teams1 = value;
-        return CN_OK;
-    }
-    if (key == 38 && value >= 0 && value <= 1024) {
-        cn_tune_dcn_team_stagger = value;
-        return CN_OK;
-    }
+extern "C" int cn_get_tuning(int key, int *value)
+{
+    if (!value) return CN_ERR_NULL;
+    const CnTuningKey *k = tuning_key(key);
+    if (!k) return CN_ERR_UNSUPPORTED;
+    *value = k->field ? cn_knobs.*k->field : 0;
+    return CN_OK;
+}
 
-    if (key == 20 && (value == 0 || value == 1)) {
-        cn_tune_f32s_lds_weights = value;
-        return CN_OK;
-    }
-    if (key == 21 && value >= 0 && value <= 7) {
-        cn_tune_f32s_policy = value;
-        return CN_OK;
-    }
-    if (key == 1 && value >= 0 && value <= 2) {
-        g_tune_nbuf = value;
-        return CN_OK;
-    }
-    if (key == 2 && (value == 0 || value == 1)) {
-        g_tune_narrow = value;
-        return CN_OK;
-    }
-    if (key == 3 && (value == 0 || value == 64)) return CN_OK;  // 128-pixel DCN tiles: retired
-    if (key == 4 && (value == 0 || value == 64 || value == 128)) {
-        g_tune_bm = value;
-        return CN_OK;
-    }
-    if (key == 5 && (value == 0 || value == 1)) {
-        g_tune_nosplit = value;
-        return CN_OK;
-    }
-    if (key == 6 && (value == 0 || value == 1)) {
-        g_tune_nostem = value;
-        return CN_OK;
-    }
-    if (key == 8 && (value == 0 || value == 1)) {
-        g_tune_setprio = value;
-        return CN_OK;
-    }
-    if (key == 9 && value >= 0 && value <= 2047) {
-        g_tune_dbgskip = value;
-        return CN_OK;
-    }
-    if (key == 10 && (value == 0 || value == 1)) {
-        g_tune_nohalo = value;
-        return CN_OK;
-    }
-    if (key == 11 && value == 0) return CN_OK;   // fp32 LDS-window DCN kernel: retired in round 5 (20-30 % slower than the gather form)
-    if (key == 7 && (value == 0 || value == 1 || value == 2)) {
-        g_tune_swz = value;
-        return CN_OK;
-    }
-    if (key == 13 && (value == 0 || value == 1 || value == 3 || value == 9)) {
-        g_tune_dcn_split = value;
-        return CN_OK;
-    }
-    if (key == 14 && value >= 0 && value <= 3) {
-        g_tune_bm256 = value;
-        return CN_OK;
-    }
-    if (key == 16 && value >= 1 && value <= 64) {
-        g_tune_split_min_chunks = value;
-        return CN_OK;
-    }
-    if (key == 17 && value >= 1 && value <= 64) {
-        g_tune_split_max = value;
-        return CN_OK;
-    }
-    if (key == 18 && value >= 0 && value <= 255) {
-        cn_tune_stagger_pct = value;
-        return CN_OK;
-    }
-    if (key == 19 && value >= 0 && value <= 2) {
-        g_tune_occ4 = value;
-        return CN_OK;
-    }
-    if (key == 15 && (value == 0 || value == 1)) {
-        g_tune_waves8 = value;
-        return CN_OK;
-    }
-    if (key == 12 && (value == 0 || value == 1)) {
-        g_tune_stem_persist = value;
-        return CN_OK;
-    }
-    if (key == 22 && (value == 0 || value == 1)) {
-        g_tune_dcn_tile2d = value;
-        return CN_OK;
-    }
-    if (key == 27 && (value == 0 || value == 1)) {
-        g_tune_stem16s = value;
-        return CN_OK;
-    }
-    if (key == 26 && value >= 0 && value <= 3) {
-        cn_tune_heads_reg = value;
-        return CN_OK;
-    }
-    if (key == 24 && value >= 0 && value <= 3) {
-        cn_tune_heads_remap = value;
-        return CN_OK;
-    }
-    if (key == 46 && (value == 0 || value == 1)) {
-        cn_tune_proj = value;
-        return CN_OK;
-    }
-    if (key == 45 && (value == 0 || value == 1)) {
-        cn_tune_dcn_wide_prefetch = value;
-        return CN_OK;
-    }
-    if (key == 44 && value >= 0 && value <= 1024) {
-        cn_tune_stem_stagger = value;
-        return CN_OK;
-    }
-    if (key == 43 && value >= 0 && value <= 31) {
-        cn_tune_stem_dbg = value;
-        return CN_OK;
-    }
-    if (key == 41 && (value == 0 || value == 1)) {
-        cn_tune_dcn_wide = value;
-        return CN_OK;
-    }
-    if (key == 42 && value >= 1 && value <= 4096) {
-        cn_tune_dcn_wide_wgs = value;
-        return CN_OK;
-    }
-    if (key == 23 && (value == 0 || value == 1 || value == 2 || (value >= 4 && value <= 7))) {
-        g_tune_dcn_form = value;
-        return CN_OK;
-    }
-    return CN_ERR_UNSUPPORTED;
+extern "C" int cn_reset_tuning(void)
+{
+    cn_knobs = cn_tuning_defaults();
+    return CN_OK;
 }

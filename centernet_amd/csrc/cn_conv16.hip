@@ -10,7 +10,7 @@
 // registers.  Persistent workgroups (two per CU) walk 128-pixel row tiles; the 3-row input
 // window of the next tile is fetched into registers during the MFMAs of the current one.
 // The op is balanced between the matrix pipe and HBM (AI = 36 FLOP/B for 16 -> 16).
-#include "cn_common.h"
+#include "cn_internal.h"
 
 namespace {
 

@@ -18,15 +18,10 @@
 //
 // Same numerics as the generic kernel: v_mfma_f32_32x32x2_f32, fp32 accumulate, K consumed
 // chunk-major then tap, epilogue y = relu?(acc*scale + shift + residual).
-#include "cn_common.h"
+#include "cn_internal.h"
+#include "cn_tuning.h"
 #include <type_traits>
 
-// cn_set_tuning key 18: phase shift of co-resident workgroups, percent of one tile's MFMA time
-// (0 = off); see the kernel prologue
-int cn_tune_stagger_pct = 100;
-int cn_tune_heads_reg = 1;     // cn_set_tuning key 26 (A/B): fused f32s heads with the hidden layer in registers
-int cn_tune_heads_remap = 1;   // cn_set_tuning key 24 (A/B): bit 0 = fused heads, bit 1 = multi-block Cout, on a 1-D row-interleaved grid
-int cn_tune_f32s_policy = 0;   // cn_set_tuning key 21 (A/B): bit 0 = 128-wide tiles as eight waves three taps ahead, bit 1 = 64-wide tiles two taps ahead
 // f32s: taps a weight tile is requested ahead of its use (1 = the fp32 schedule; build-time so that
 // the register allocation of each form is its own: -DCN_F32S_PREFETCH_TAPS=1 for A/B builds)
 #ifndef CN_F32S_PREFETCH_TAPS
@@ -35,22 +30,6 @@ int cn_tune_f32s_policy = 0;   // cn_set_tuning key 21 (A/B): bit 0 = 128-wide t
 #ifndef CN_F16_PREFETCH_TAPS
 #define CN_F16_PREFETCH_TAPS 2
 #endif
-
-bool cn_conv3x3p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int res_pitch,
-                       bool in_plain, bool has_res);
-bool cn_heads3x3p_takes(int B, int H, int W, int in_pitch, int head_conv, int n_heads, const cn_head_out *heads,
-                        bool in_plain);
-int cn_heads3x3p(const void *x, int B, int H, int W, int Cin, int in_pitch, const void *w1_packed,
-                 const float *scale1, const float *bias1, int n_heads, const cn_head_out *heads,
-                 const cn_f32s_ctl *ctl, hipStream_t st);
-bool cn_deconv4x4s2p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, bool in_plain);
-int cn_deconv4x4s2_persist(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
-                           int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int relu,
-                           int out_plain, const cn_f32s_ctl *ctl, hipStream_t st);
-int cn_conv3x3s1_persist(const void *x, const void *w_packed, const float *scale, const float *shift,
-                         const void *residual, void *y, int B, int H, int W, int Cin, int Cout,
-                         int in_pitch, int out_pitch, int res_pitch, int relu, int out_plain, int res_plain,
-                         const cn_f32s_ctl *ctl, hipStream_t st);
 
 namespace {
 
@@ -1150,7 +1129,7 @@ int launch_c3(const C3Args &a, hipStream_t st, const C3Heads *hd = nullptr)
     const int ny = (HEADS && hd) ? cn_cdiv(a.Cout, BN * (hd->slices > 0 ? hd->slices : 1)) : cn_cdiv(a.Cout, BN);
     dim3 grid((unsigned)(a.B * b.tiles_x * b.tiles_y), ny, DECONV ? 4 : 1);
     b.heads_remap = 0;
-    if (!DECONV && ny > 1 && grid.x % 8 == 0 && (HEADS ? (cn_tune_heads_remap & 1) : (cn_tune_heads_remap & 2))) {
+    if (!DECONV && ny > 1 && grid.x % 8 == 0 && (HEADS ? (cn_knobs.heads_remap & 1) : (cn_knobs.heads_remap & 2))) {
         b.heads_remap = ny;
         grid = dim3(grid.x * ny, 1, 1);
     }
@@ -1166,9 +1145,9 @@ int launch_c3(const C3Args &a, hipStream_t st, const C3Heads *hd = nullptr)
         const long total = (long)grid.x * grid.y * grid.z;
         const long rounds = total / (256L * slots);
         const long tile_cycles = (long)b.nchunk * (DECONV ? 4 : 9) * cyc_iter;
-        if (cn_tune_stagger_pct > 0 && rounds >= 4) {
+        if (cn_knobs.stagger_pct > 0 && rounds >= 4) {
             b.stagger_slots = slots;
-            b.stagger = (int)(tile_cycles * cn_tune_stagger_pct / 100);
+            b.stagger = (int)(tile_cycles * cn_knobs.stagger_pct / 100);
         } else {
             b.stagger = 0;
         }
@@ -1189,8 +1168,7 @@ int launch_c3(const C3Args &a, hipStream_t st, const C3Heads *hd = nullptr)
 // 5-20 % (tools/bench_f32s.py) but not inside the network (resdcn_18 B=32: 4.425 vs 4.408 ms per
 // step, two runs each on one box), where its 1-wave-per-SIMD occupancy hides less of the
 // neighbouring launches' tails.
-int cn_tune_f32s_lds_weights = 1;
-
+//
 // Measured (tools/bench_f32s.py, B = 32): 128-wide tiles as four waves of 64 x 64 with
 // register-streamed weights beat the LDS-weight form by 5-20 % (128->128@64^2 0.148 -> 0.141 ms,
 // 256->256@32^2 0.144 -> 0.126, 512->512@16^2 0.142 -> 0.115); eight waves of 32 x 64 lose
@@ -1207,7 +1185,7 @@ template <typename T>
 static int c3_dispatch(C3Args &a, int bn_class, hipStream_t st)
 {
     // 4 x 32 tiles keep an MFMA block on one halo row; key 21 bit 2 (A/B): 8 x 16 tiles everywhere
-    const bool wide = a.W >= 32 && !(std::is_same<T, cn_f32s>::value && (cn_tune_f32s_policy & 4));
+    const bool wide = a.W >= 32 && !(std::is_same<T, cn_f32s>::value && (cn_knobs.f32s_policy & 4));
     // fp32 layers whose last 32-channel chunk is less than 3/4 full skip its empty K groups
     const bool kskip = std::is_same<T, float>::value && a.nkk_last < 4;
     if (bn_class == 2) {
@@ -1220,7 +1198,7 @@ static int c3_dispatch(C3Args &a, int bn_class, hipStream_t st)
         if (wgs < 512 && (a.Cout % 64) == 0) bn_class = 1;
     }
     if constexpr (std::is_same<T, cn_f32s>::value) {
-        if (bn_class == 2 && !cn_tune_f32s_lds_weights) return c3_dispatch_f32s_wreg(a, st);
+        if (bn_class == 2 && !cn_knobs.f32s_lds_weights) return c3_dispatch_f32s_wreg(a, st);
     }
     if (bn_class == 2) {
         // 8 waves per 128 x 128 tile (wave tile 32 x 64): 4 waves/SIMD at 2 workgroups per CU
@@ -1231,7 +1209,7 @@ static int c3_dispatch(C3Args &a, int bn_class, hipStream_t st)
             // tiles two taps ahead -- 220 registers, two workgroups per CU.  Measured against
             // eight waves of 32 x 64 three taps ahead (cn_set_tuning key 21 bit 0): 128->128@64^2
             // 0.122 -> 0.115 ms, 256->256@32^2 0.117 -> 0.106, resdcn_18 B=32 +1.1 %
-            if (!(cn_tune_f32s_policy & 1))
+            if (!(cn_knobs.f32s_policy & 1))
                 return wide ? launch_c3<T, 32, 128, 2, 2, false, 128, false, false, 2, 2>(a, st)
                             : launch_c3<T, 16, 128, 2, 2, false, 128, false, false, 2, 2>(a, st);
             return wide ? launch_c3<T, 32, 128, 4, 2>(a, st) : launch_c3<T, 16, 128, 4, 2>(a, st);
@@ -1270,7 +1248,7 @@ static int c3_dispatch(C3Args &a, int bn_class, hipStream_t st)
             // deep weight prefetch costs the 64-wide tile one of its three workgroups per CU
             // (174 vs 132 registers): it pays on long K loops (512->512@16^2: 0.135 -> 0.117 ms)
             // and loses on the two-chunk 64->64 layers (0.149 -> 0.158), measured at B = 32
-            if (cn_tune_f32s_policy & 2)   // experiment: two taps ahead for every 64-wide layer
+            if (cn_knobs.f32s_policy & 2)   // experiment: two taps ahead for every 64-wide layer
                 return wide ? launch_c3<T, 32, 64, 2, 2, false, 128, false, false, 2, 2>(a, st)
                             : launch_c3<T, 16, 64, 2, 2, false, 128, false, false, 2, 2>(a, st);
             if (a.nchunk < 4)
@@ -1294,44 +1272,40 @@ static void c3_set_ctl(C3Args &a, const cn_f32s_ctl *ctl)
     a.range = ctl ? ctl->range : nullptr;
 }
 
-// bn_class: 2 = 128-wide N tiles, 1 = 64, 0 = 32 (chosen by the caller, same rule as cn_conv.hip)
-// f16: 0 = fp32 tensors, 1 = fp16 tensors (fp32 accumulate, scale/shift fp32)
+// (fp16 tensors: fp32 accumulate, scale / shift fp32)
 int cn_conv3x3s1(const void *x, const void *w_packed, const float *scale, const float *shift,
                  const void *residual, void *y, int B, int H, int W, int Cin, int Cout,
-                 int in_pitch, int out_pitch, int res_pitch, int relu, int vec_out, int setprio, int bn_class,
-                 int f16, const cn_f32s_ctl *ctl, hipStream_t st)
+                 int in_pitch, int out_pitch, int res_pitch, int relu, int vec_out, int bn_class,
+                 int dtype, int flags, const cn_f32s_ctl *ctl, hipStream_t st)
 {
     if (res_pitch <= 0) res_pitch = out_pitch;
     C3Args a = {};
     c3_set_ctl(a, ctl);
-    a.bm256 = ((setprio >> 1) & 1) | ((setprio >> 2) & 2);  // bits 1 and 3 of the knob word: cn_set_tuning key 14
-    a.waves8 = (setprio >> 2) & 1; // bit 2: cn_set_tuning key 15
-    a.dbg = ((setprio >> 4) & 7) | (((setprio >> 9) & 3) << 3);  // bits 4-6, 9-10: ablation switches (cn_set_tuning key 9)
-    a.occ4 = (setprio >> 7) & 3;   // bits 7-8: cn_set_tuning key 19
-    setprio &= 1;
+    a.bm256 = cn_knobs.bm256;
+    a.waves8 = cn_knobs.waves8;
+    a.dbg = cn_knobs.dbgskip & 31;   // the ablation switches this kernel knows
+    a.occ4 = cn_knobs.occ4;
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.residual = residual; a.y = y;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.in_pitch = in_pitch;
-    a.out_pitch = out_pitch; a.relu = relu; a.vec_out = vec_out; a.setprio = setprio;
+    a.out_pitch = out_pitch; a.relu = relu; a.vec_out = vec_out; a.setprio = cn_knobs.setprio;
     a.res_pitch = res_pitch;
-    // f16: the dtype code CN_DTYPE_F32 / F16 / F32S in the low byte, cn_conv_desc.flags above it
-    a.in_plain = (f16 >> 8) & CN_CONV_X_PLAIN ? 1 : 0;
-    a.out_plain = (f16 >> 8) & CN_CONV_Y_PLAIN ? 1 : 0;
-    a.res_plain = (f16 >> 8) & CN_CONV_R_PLAIN ? 1 : 0;
-    f16 &= 255;
-    const int bke = f16 == CN_DTYPE_F16 ? 64 : 32;
+    a.in_plain = (flags & CN_CONV_X_PLAIN) ? 1 : 0;
+    a.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
+    a.res_plain = (flags & CN_CONV_R_PLAIN) ? 1 : 0;
+    const int bke = dtype == CN_DTYPE_F16 ? 64 : 32;
     a.cin_pad = (Cin + bke - 1) / bke * bke;
     a.cout_pad = (Cout + 31) / 32 * 32;
     a.nchunk = a.cin_pad / bke;
-    a.nkk_last = f16 != CN_DTYPE_F32 ? 4 : ((Cin - (a.nchunk - 1) * 32) + 7) / 8;
+    a.nkk_last = dtype != CN_DTYPE_F32 ? 4 : ((Cin - (a.nchunk - 1) * 32) + 7) / 8;
     a.ncb = a.cout_pad / 32;
     a.wfrag_off = (size_t)9 * a.cout_pad * a.cin_pad * 4;   // behind the row-ordered copy
     // f32s tensors on both sides: the persistent loader / consumer kernel (cn_conv3x3p.hip)
-    if (f16 == CN_DTYPE_F32S && !a.dbg && vec_out && scale &&
+    if (dtype == CN_DTYPE_F32S && !a.dbg && vec_out && scale &&
         cn_conv3x3p_takes(B, H, W, Cin, Cout, in_pitch, out_pitch, res_pitch, a.in_plain != 0, residual != nullptr))
         return cn_conv3x3s1_persist(x, w_packed, scale, shift, residual, y, B, H, W, Cin, Cout, in_pitch,
                                     out_pitch, res_pitch, relu, a.out_plain, a.res_plain, ctl, st);
-    if (f16 == CN_DTYPE_F32S) return c3_dispatch<cn_f32s>(a, bn_class, st);
-    return f16 == CN_DTYPE_F16 ? c3_dispatch<_Float16>(a, bn_class, st) : c3_dispatch<float>(a, bn_class, st);
+    if (dtype == CN_DTYPE_F32S) return c3_dispatch<cn_f32s>(a, bn_class, st);
+    return dtype == CN_DTYPE_F16 ? c3_dispatch<_Float16>(a, bn_class, st) : c3_dispatch<float>(a, bn_class, st);
 }
 
 // Fused CenterNet heads: for every head h, y_h = conv1x1(relu(conv3x3(x) + bias1_h)) + bias2_h,
@@ -1393,11 +1367,11 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
     // (4 x 1 waves; 128-wide slices when the hidden width allows); cn_set_tuning key 26 = 0: LDS form
     // (one 64-channel slice, i.e. res / resdcn heads: the LDS form below with its deeper weight prefetch
     // measured faster, 0.453 vs 0.492 ms; from two slices on this form wins: dla_34 1.84 -> 1.72 ms)
-    if (f32s && W >= 32 && cn_tune_heads_reg && (head_conv > HEAD_CONV || cn_tune_heads_reg == 3)) {
+    if (f32s && W >= 32 && cn_knobs.heads_reg && (head_conv > HEAD_CONV || cn_knobs.heads_reg == 3)) {
         bool small = true;
         for (int h = 0; h < n_heads; ++h) small = small && heads[h].cout <= W2_ROWS;
         if (small) {
-            if (head_conv % 128 == 0 && cn_tune_heads_reg == 2) {   // 128-wide slices: register-bound (107 spills), A/B only
+            if (head_conv % 128 == 0 && cn_knobs.heads_reg == 2) {   // 128-wide slices: register-bound (107 spills), A/B only
                 hd.slices = head_conv / 128;
                 return launch_c3<cn_f32s, 32, 128, 4, 1, true, 128, false, false, 2, 1>(a, st, &hd);
             }
@@ -1423,27 +1397,27 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
 // w_packed: cn_pack_deconv4x4s2_weight_f32 layout [parity 4][tap 4][cout_pad][cin_pad].
 int cn_deconv4x4s2_halo(const void *x, const void *w_packed, const float *scale, const float *shift,
                         void *y, int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch,
-                        int relu, int vec_out, int setprio, int dtype_flags, const cn_f32s_ctl *ctl,
+                        int relu, int vec_out, int dtype, int flags, const cn_f32s_ctl *ctl,
                         hipStream_t st)
 {
     C3Args a = {};
     c3_set_ctl(a, ctl);
     a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.residual = nullptr; a.y = y;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.in_pitch = in_pitch;
-    a.out_pitch = out_pitch; a.relu = relu; a.vec_out = vec_out; a.setprio = setprio & 1;
+    a.out_pitch = out_pitch; a.relu = relu; a.vec_out = vec_out; a.setprio = cn_knobs.setprio;
     a.cin_pad = (Cin + 31) / 32 * 32;
     a.cout_pad = (Cout + 31) / 32 * 32;
     a.nchunk = a.cin_pad / 32;
     a.nkk_last = 4;
     a.res_pitch = out_pitch;
-    a.in_plain = (dtype_flags >> 8) & CN_CONV_X_PLAIN ? 1 : 0;
-    a.out_plain = (dtype_flags >> 8) & CN_CONV_Y_PLAIN ? 1 : 0;
+    a.in_plain = (flags & CN_CONV_X_PLAIN) ? 1 : 0;
+    a.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
     const bool wide = W >= 32;
-    if ((dtype_flags & 255) == CN_DTYPE_F32S && vec_out && scale &&
+    if (dtype == CN_DTYPE_F32S && vec_out && scale &&
         cn_deconv4x4s2p_takes(B, H, W, Cin, Cout, in_pitch, out_pitch, a.in_plain != 0))
         return cn_deconv4x4s2_persist(x, w_packed, scale, shift, y, B, H, W, Cin, Cout, in_pitch, out_pitch, relu,
                                       a.out_plain, ctl, st);
-    if ((dtype_flags & 255) == CN_DTYPE_F32S) {
+    if (dtype == CN_DTYPE_F32S) {
         if (Cout > 64)
             return wide ? launch_c3<cn_f32s, 32, 128, 4, 2, false, 128, false, true>(a, st)
                         : launch_c3<cn_f32s, 16, 128, 4, 2, false, 128, false, true>(a, st);
@@ -1455,7 +1429,7 @@ int cn_deconv4x4s2_halo(const void *x, const void *w_packed, const float *scale,
         return wide ? launch_c3<float, 32, 128, 4, 2, false, 128, false, true>(a, st)
                     : launch_c3<float, 16, 128, 4, 2, false, 128, false, true>(a, st);
     const long wgs = 4L * B * cn_cdiv(H, wide ? 4 : 8) * cn_cdiv(W, wide ? 32 : 16);
-    const int occ4 = (setprio >> 7) & 3;  // cn_set_tuning key 19
+    const int occ4 = cn_knobs.occ4;
     if (occ4 != 2 && (occ4 == 1 || c3_occ4_pays(wgs)))
         return wide ? launch_c3_occ4<float, 32, true>(a, st) : launch_c3_occ4<float, 16, true>(a, st);
     return wide ? launch_c3<float, 32, 64, 2, 2, false, 128, false, true>(a, st)

@@ -35,17 +35,9 @@
 // LDS strip into full 128-byte output rows (coalesced 16-byte stores, no cross-wave barrier).
 // Weight tiles (64 rows x 128 bytes per (tap, chunk)) stream through a ring of four 8 KB slots,
 // three steps ahead of their use; one s_barrier per (tap, chunk) step.
-#include "cn_common.h"
+#include "cn_internal.h"
+#include "cn_tuning.h"
 #include <type_traits>
-
-int cn_tune_c3p = 1;        // cn_set_tuning key 28: 0 = off, 1 = on for the shapes it takes
-int cn_tune_c3p_stagger = 0;  // cn_set_tuning key 29: start delay of the second resident workgroup, in units of 256 cycles
-                              // (64 was worth 1-2 % with the unpipelined schedule; with the pipelined one 0 is: r05_c3p_pipe.txt)
-                              // (measured 0 ... 96: 48-64 is best on every trunk shape, +6 ... +13 % over none)
-int cn_tune_c3p_knobs = 2;    // cn_set_tuning key 30 (A/B): see P3Args.knobs
-int cn_tune_c3p_heads = 1;    // cn_set_tuning key 31: the fused heads (hidden width 64) on this kernel; 0 = halo kernel
-int cn_tune_c3p_deconv = 1;   // cn_set_tuning key 32: ConvTranspose2d(4, 2, 1) in parity form on this kernel; 0 = halo kernel
-int cn_tune_c3p_s2 = 1;       // cn_set_tuning key 33: 3x3 / stride 2 / pad 1 in parity-plane form on this kernel; 0 = implicit GEMM
 
 // one 128-byte line of zeros: the DMA source of halo pixels outside the image
 __device__ __attribute__((aligned(128))) unsigned char cn_p3_zero_line[128];
@@ -1257,12 +1249,12 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
 bool cn_conv3x3p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int res_pitch,
                        bool in_plain, bool has_res)
 {
-    if (!cn_tune_c3p || in_plain) return false;   // (the caller also guarantees a non-null scale)
+    if (!cn_knobs.c3p || in_plain) return false;   // (the caller also guarantees a non-null scale)
     if ((in_pitch & 31) || (out_pitch & 31) || (has_res && (res_pitch & 31))) return false;
     if (Cout % 32) return false;
     const long items = (long)B * cn_cdiv(H, P_TH) * cn_cdiv(W, P_TW) * cn_cdiv(Cout, 64);
     // enough items that the persistent grid fills the chip (key 28 = 2: every shape, for tests)
-    if (cn_tune_c3p < 2 && items < 256) return false;
+    if (cn_knobs.c3p < 2 && items < 256) return false;
     if ((long)B * H * W * (long)max(in_pitch, max(out_pitch, res_pitch)) * 4 >= (1L << 31)) return false;
     (void)Cin;
     return true;
@@ -1272,10 +1264,10 @@ bool cn_conv3x3p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int
 // whole 32-channel groups (f32s or plain), enough items to fill the chip
 bool cn_deconv4x4s2p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, bool in_plain)
 {
-    if (!cn_tune_c3p || !(cn_tune_c3p_deconv) || in_plain) return false;
+    if (!cn_knobs.c3p || !(cn_knobs.c3p_deconv) || in_plain) return false;
     if ((in_pitch & 31) || (out_pitch & 31) || (Cout % 32)) return false;
     const long items = 4L * B * cn_cdiv(H, P_TH) * cn_cdiv(W, P_TW) * cn_cdiv(Cout, 64);
-    if (cn_tune_c3p < 2 && items < 256) return false;
+    if (cn_knobs.c3p < 2 && items < 256) return false;
     if (4L * B * H * W * (long)max(in_pitch, out_pitch) * 4 >= (1L << 31)) return false;
     (void)Cin;
     return true;
@@ -1304,8 +1296,8 @@ int cn_deconv4x4s2_persist(const void *x, const void *w_packed, const float *sca
     a.relu = relu; a.out_plain = out_plain;
     a.res_mul = 1.f;
     a.range = ctl ? ctl->range : nullptr;
-    a.stagger = cn_tune_c3p_stagger;
-    a.knobs = cn_tune_c3p_knobs;
+    a.stagger = cn_knobs.c3p_stagger;
+    a.knobs = cn_knobs.c3p_knobs;
     int per_xcd = cn_cdiv(a.items, 8);
     if (per_xcd > 64) per_xcd = 64;
     const dim3 grid(8 * per_xcd), block(p3_threads(4, false));
@@ -1328,11 +1320,11 @@ int cn_deconv4x4s2_persist(const void *x, const void *w_packed, const float *sca
 // whole 32-channel output groups, no residual
 bool cn_conv3x3s2p_takes(int B, int Hi, int Wi, int Cin, int Cout, int in_pitch, int out_pitch)
 {
-    if (!cn_tune_c3p || !cn_tune_c3p_s2) return false;
+    if (!cn_knobs.c3p || !cn_knobs.c3p_s2) return false;
     if ((in_pitch & 31) || (out_pitch & 31) || (Cout % 32)) return false;
     const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
     const long items = (long)B * cn_cdiv(Ho, P_TH) * cn_cdiv(Wo, P_TW) * cn_cdiv(Cout, 64);
-    if (cn_tune_c3p < 2 && items < 256) return false;
+    if (cn_knobs.c3p < 2 && items < 256) return false;
     if ((long)B * Hi * Wi * (long)in_pitch * 4 >= (1L << 31) || (long)B * Ho * Wo * (long)out_pitch * 4 >= (1L << 31))
         return false;
     (void)Cin;
@@ -1362,8 +1354,8 @@ int cn_conv3x3s2_persist(const void *x, const void *w_packed, const float *scale
     a.relu = relu; a.out_plain = out_plain;
     a.res_mul = 1.f;
     a.range = ctl ? ctl->range : nullptr;
-    a.stagger = cn_tune_c3p_stagger;
-    a.knobs = cn_tune_c3p_knobs;
+    a.stagger = cn_knobs.c3p_stagger;
+    a.knobs = cn_knobs.c3p_knobs;
     int per_xcd = cn_cdiv(a.items, 8);
     if (per_xcd > 64) per_xcd = 64;
     const dim3 grid(8 * per_xcd), block(p3_threads(9, true));
@@ -1437,8 +1429,8 @@ int cn_conv3x3s1_persist(const void *x, const void *w_packed, const float *scale
     a.relu = relu; a.out_plain = out_plain; a.res_plain = res_plain;
     a.res_mul = (ctl && ctl->res_mul != 0.f) ? ctl->res_mul : 1.f;
     a.range = ctl ? ctl->range : nullptr;
-    a.stagger = cn_tune_c3p_stagger;
-    a.knobs = cn_tune_c3p_knobs;
+    a.stagger = cn_knobs.c3p_stagger;
+    a.knobs = cn_knobs.c3p_knobs;
     // two workgroups per CU, a multiple of 8 (one share per XCD), never more than one per item
     int per_xcd = cn_cdiv(a.items, 8);
     if (per_xcd > 64) per_xcd = 64;
@@ -1482,12 +1474,12 @@ int cn_conv3x3s1_persist(const void *x, const void *w_packed, const float *scale
 bool cn_heads3x3p_takes(int B, int H, int W, int in_pitch, int head_conv, int n_heads, const cn_head_out *heads,
                         bool in_plain)
 {
-    if (!cn_tune_c3p || !cn_tune_c3p_heads || in_plain || head_conv != 64 || n_heads > P_MAXH) return false;
+    if (!cn_knobs.c3p || !cn_knobs.c3p_heads || in_plain || head_conv != 64 || n_heads > P_MAXH) return false;
     if (in_pitch & 31) return false;
     for (int h = 0; h < n_heads; ++h)
         if (heads[h].cout > 96 || !heads[h].w_frag || !cn_aligned16(heads[h].w_frag)) return false;
     const long items = (long)B * cn_cdiv(H, P_TH) * cn_cdiv(W, P_TW) * n_heads;
-    if (cn_tune_c3p < 2 && items < 256) return false;
+    if (cn_knobs.c3p < 2 && items < 256) return false;
     if ((long)B * H * W * (long)in_pitch * 4 >= (1L << 31)) return false;
     for (int h = 0; h < n_heads; ++h)
         if ((long)B * heads[h].cout * H * W >= (1L << 31)) return false;
@@ -1521,8 +1513,8 @@ int cn_heads3x3p(const void *x, int B, int H, int W, int Cin, int in_pitch, cons
     a.relu = 1;
     a.res_mul = 1.f;
     a.range = ctl ? ctl->range : nullptr;
-    a.stagger = cn_tune_c3p_stagger;
-    a.knobs = cn_tune_c3p_knobs;
+    a.stagger = cn_knobs.c3p_stagger;
+    a.knobs = cn_knobs.c3p_knobs;
     int per_xcd = cn_cdiv(a.items, 8);
     if (per_xcd > 64) per_xcd = 64;
     const dim3 grid(8 * per_xcd), block(384);

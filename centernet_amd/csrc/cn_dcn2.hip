@@ -17,12 +17,12 @@
 // 108 TFLOP/s with the matrix pipe 15 % busy: every (tap, chunk) step is a dependent chain
 // record -> four gathers -> blend -> LDS -> barrier -> MFMA of ~2.4 us.
 // Epilogue as everywhere: y = relu?((acc + bias) * scale + shift), plain fp32 or f32s, range words.
-#include "cn_common.h"
+#include "cn_internal.h"
 
 // K is split until a launch has this many workgroups (round-4 sweep of 256 / 512 / 1024 and of 64-wide N tiles
 // for Cout > 64, cn_set_tuning keys 34 / 35: within +-5 % on every layer shape, profiles/r04_dcn_split_sweep.txt;
 // the keys were removed in round 5)
-constexpr int cn_tune_dcn_wgs = 256;
+constexpr int DCN2_SPLIT_WGS = 256;
 
 namespace {
 
@@ -470,11 +470,11 @@ int cn_dcn_window_f32s(const float *x, const void *w_packed, const float *bias, 
     // 2 / 4 / 8 workgroups per tile -- raw fp32 partial sums in the caller's workspace, summed in a
     // fixed order by splitk_reduce_kernel (deterministic) -- when that yields >= 256 workgroups
     int ksplit = 1;
-    if (wgs < cn_tune_dcn_wgs || wgs < min_wgs) {
+    if (wgs < DCN2_SPLIT_WGS || wgs < min_wgs) {
         // the smallest split that reaches the workgroup target, else the deepest one that fits
         const int nchunk = (Cin + 31) / 32;
         const int cout_pad = (Cout + 31) / 32 * 32;
-        for (int s2 = 2; s2 <= 8 && partial && wgs * ksplit < cn_tune_dcn_wgs; s2 *= 2)
+        for (int s2 = 2; s2 <= 8 && partial && wgs * ksplit < DCN2_SPLIT_WGS; s2 *= 2)
             if (nchunk % s2 == 0 && nchunk / s2 >= 2 &&
                 (size_t)s2 * B * H * W * cout_pad * sizeof(float) <= partial_bytes)
                 ksplit = s2;

@@ -33,12 +33,8 @@
 // (dcn_v2_im2col_cuda.cu:165), corner rule (:30-41), weights hh*hw, hh*lw, lh*hw, lh*lw (:26-28,43),
 // value * mask (:174; here the mask multiplies the four corner weights -- a reassociation of
 // 1-2 ulp in fp32, far below the 2^-22 of the f32s split), bias then accumulate (dcn_v2_cuda.c:61-97).
-#include "cn_common.h"
-
-int cn_tune_dcn_team = 3;       // cn_set_tuning key 36: 0 = off, 1 = layers with <= 64 output channels, 2 = every layer it takes (T mode),
-                                // 3 = every layer, N mode where Cout is a multiple of 128 and that still fills the chip
-int cn_tune_dcn_team_wgs = 512; // cn_set_tuning key 37: K split until a launch has this many workgroups
-int cn_tune_dcn_team_stagger = 32; // cn_set_tuning key 38: start delay of the second resident workgroup of every CU, in units of 256 cycles (sweep 0 .. 128 at B = 32: 32-64 is 5-9 % faster on the multi-round shapes, nothing on the others; profiles/r05_dcn_team_stagger.txt)
+#include "cn_internal.h"
+#include "cn_tuning.h"
 
 // one 128-byte line of zeros: the DMA source of window pixels outside the image
 __device__ __attribute__((aligned(128))) unsigned char cn_d3_zero_line[128];
@@ -530,7 +526,7 @@ int cn_dcn_team_f32s(const float *x, const void *w_packed, const float *bias, co
     // N mode halves the workgroup count: only where two workgroups per CU remain (measured: 256 -> 128 @ 32^2 at
     // B = 32 has 256 tiles: 0.093 ms in T mode, 0.109 in N mode; 128 -> 128 @ 64^2 and 256 -> 256 @ 32^2: 0.179 /
     // 0.172 against 0.195 / 0.209)
-    if (nmode == 1 && (long)B * (H / T_TY) * (W / T_TX) * (Cout / 128) < cn_tune_dcn_team_wgs) nmode = 0;
+    if (nmode == 1 && (long)B * (H / T_TY) * (W / T_TX) * (Cout / 128) < cn_knobs.dcn_team_wgs) nmode = 0;
     const long wgs = (long)B * (H / T_TY) * (W / T_TX) * cn_cdiv(Cout, nmode ? 128 : 64);
     // Too few tiles for the chip but a deep K (512 -> 256 @ 16^2): split the 32-channel chunks over
     // 2 / 4 / 8 workgroups per tile -- raw fp32 partial sums in the caller's workspace, summed in a
@@ -539,7 +535,7 @@ int cn_dcn_team_f32s(const float *x, const void *w_packed, const float *bias, co
     {
         const int nchunk = Cin / 32;
         const int cout_pad = (Cout + 31) / 32 * 32;
-        for (int s2 = 2; s2 <= 8 && partial && wgs * ksplit < cn_tune_dcn_team_wgs; s2 *= 2)
+        for (int s2 = 2; s2 <= 8 && partial && wgs * ksplit < cn_knobs.dcn_team_wgs; s2 *= 2)
             if (nchunk % s2 == 0 && nchunk / s2 >= 2 &&
                 (size_t)s2 * B * H * W * cout_pad * sizeof(float) <= partial_bytes)
                 ksplit = s2;
@@ -554,7 +550,7 @@ int cn_dcn_team_f32s(const float *x, const void *w_packed, const float *bias, co
     a.tiles_x = W / T_TX;
     a.tiles_y = H / T_TY;
     a.x_mul = x_mul; a.range = range; a.dbg = dbg;
-    a.stagger = cn_tune_dcn_team_stagger;
+    a.stagger = cn_knobs.dcn_team_stagger;
     a.ksplit = ksplit;
     a.partial = ksplit > 1 ? partial : nullptr;
     if (ksplit_out) *ksplit_out = ksplit;

@@ -33,11 +33,8 @@
 // (dcn_v2_im2col_cuda.cu:165), corner rule (:30-41), weights hh*hw, hh*lw, lh*hw, lh*lw (:26-28,43),
 // value * mask (:174; the mask multiplies the four corner weights), bias then accumulate
 // (dcn_v2_cuda.c:61-97).
-#include "cn_common.h"
-
-int cn_tune_dcn_wide = 1;        // cn_set_tuning key 41: 0 = off, 1 = layers with Cout % 128 == 0 that the form takes
-int cn_tune_dcn_wide_prefetch = 1;   // cn_set_tuning key 45: L2 prefetch of the weight slabs three steps ahead
-int cn_tune_dcn_wide_wgs = 256;  // cn_set_tuning key 42: K split until a launch has this many workgroups
+#include "cn_internal.h"
+#include "cn_tuning.h"
 
 __device__ __attribute__((aligned(128))) unsigned char cn_d4_zero_line[128];
 // probe build, key 9 bit 512: cycle stamps of waves 0 and 4 of workgroup 0 over its first 64 steps
@@ -607,7 +604,7 @@ int cn_dcn_wide_f32s(const float *x, const void *w_packed, const float *bias, co
     {
         const int nchunk = Cin / 32;
         const int cout_pad = (Cout + 31) / 32 * 32;
-        for (int s2 = 2; s2 <= 8 && partial && wgs * ksplit < cn_tune_dcn_wide_wgs; s2 *= 2)
+        for (int s2 = 2; s2 <= 8 && partial && wgs * ksplit < cn_knobs.dcn_wide_wgs; s2 *= 2)
             if (nchunk % s2 == 0 && nchunk / s2 >= 2 &&
                 (size_t)s2 * B * H * W * cout_pad * sizeof(float) <= partial_bytes)
                 ksplit = s2;
@@ -623,7 +620,7 @@ int cn_dcn_wide_f32s(const float *x, const void *w_packed, const float *bias, co
     a.tiles_y = H / W_TY;
     a.x_mul = x_mul; a.range = range; a.dbg = dbg;
     // L2 prefetch: pays where the weight stream is long and cold (four-block form on deep K: +5 % cold); costs 1-4 % elsewhere
-    a.prefetch = (cn_tune_dcn_wide_prefetch && nb == 4 && Cin >= 256) ? 1 : 0;
+    a.prefetch = (cn_knobs.dcn_wide_prefetch && nb == 4 && Cin >= 256) ? 1 : 0;
     a.ksplit = ksplit;
     a.partial = ksplit > 1 ? partial : nullptr;
     if (ksplit_out) *ksplit_out = ksplit;

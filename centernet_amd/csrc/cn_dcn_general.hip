@@ -15,7 +15,7 @@
 //   * stages the 64 x 32 weight slice, and
 //   * accumulates a 4 x 4 register tile per thread.
 // No column buffer, no per-sample host loop, bias in the epilogue.
-#include "cn_common.h"
+#include "cn_internal.h"
 
 namespace {
 

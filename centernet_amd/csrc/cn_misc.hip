@@ -1,6 +1,6 @@
 // cn_misc.hip -- memory-bound helpers around the hot path: layout conversion at
 // the API edge, max pooling, and the NCHW (reference-layout) entry point of DCNv2.
-#include "cn_common.h"
+#include "cn_internal.h"
 
 namespace {
 
@@ -233,7 +233,7 @@ inline int blocks_for(size_t total, int per_block, int cap)
 
 }  // namespace
 
-extern "C" int cn_version(void) { return 310; }  // 0.3.1: batched flip average, ctdet scale merge
+extern "C" int cn_version(void) { return 311; }  // 0.3.11: cn_get_tuning, cn_reset_tuning
 
 extern "C" const char *cn_arch(void) { return "gfx950"; }
 
@@ -522,12 +522,6 @@ DcnWs dcn_ws_plan(int B, int Cin, int H, int W, int Cout, int kh, int kw)
     return p;
 }
 }  // namespace
-
-// cn_dcn_general.hip
-int cn_dcn_general_launch(const float *input, const float *weight, const float *bias,
-                          const float *offset, const float *mask, float *output, int B, int Cin,
-                          int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
-                          int dh, int dw, int dg, int mask_sigmoid, hipStream_t st);
 
 // The tuned CenterNet path (NHWC implicit GEMM on MFMA) takes 3x3 kernels at 4-aligned channel
 // counts; whether a call also has stride 1 / pad 1 / dilation 1 / one group is only known at

@@ -17,10 +17,8 @@
 //   * the input-side range word is fed by reading the thread's own DMA pieces back (a DMA cannot track).
 // y = acc * scale + shift (conv bias inside shift), optional ReLU; K split for maps with few tiles (raw partial
 // slabs, cn_conv.hip's splitk_reduce_kernel applies the epilogue).
-#include "cn_common.h"
-
-int cn_tune_offconv = 1;        // cn_set_tuning key 39: 0 = off (the LDS-halo kernel takes these layers)
-int cn_tune_offconv_teams1 = 768;   // cn_set_tuning key 40: workgroups from which the four-wave form is used
+#include "cn_internal.h"
+#include "cn_tuning.h"
 
 // one 128-byte line of zeros: the DMA source of halo pixels outside the image
 __device__ __attribute__((aligned(128))) unsigned char cn_oc_zero_line[128];
@@ -227,7 +225,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4) void offconv_kernel(const OcArgs a)
 // arithmetic with plain input and plain output, no residual)
 bool cn_offconv_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int ksplit)
 {
-    if (!cn_tune_offconv) return false;
+    if (!cn_knobs.offconv) return false;
     if (Cout > 32 || Cout < 1 || (Cin & 31) || in_pitch != Cin) return false;
     if ((H & 7) || (W & 15)) return false;
     if (out_pitch != 32) return false;     // the epilogue stores the whole 32-channel block (zeros behind Cout): the output must own it
@@ -252,7 +250,7 @@ int cn_offconv_f32s(const float *x, const void *w_packed, const float *scale, co
     a.partial = ksplit > 1 ? partial : nullptr;
     dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y), 1, (unsigned)ksplit);
     // four-wave workgroups from three tiles per CU up (four of them fit a CU), else eight waves in two teams
-    if ((long)grid.x * ksplit >= cn_tune_offconv_teams1) {
+    if ((long)grid.x * ksplit >= cn_knobs.offconv_teams1) {
         CN_SET_MAX_LDS_ONCE(offconv_kernel<1>, O_HBYTES);
         hipLaunchKernelGGL(offconv_kernel<1>, grid, dim3(256), O_HBYTES, st, a);
     } else {

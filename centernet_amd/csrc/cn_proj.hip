@@ -17,9 +17,8 @@
 //   * bias / BatchNorm as the usual (scale, shift) epilogue, then the wave's 32 x 128-byte rows go through
 //     the same strip and leave as whole 128-byte groups (16-byte stores).
 // f32s arithmetic: acc += Al*Bh + Ah*Bl + Ah*Bh per K half (cn_common.h).
-#include "cn_common.h"
-
-int cn_tune_proj = 1;   // cn_set_tuning key 46: 1 = f32s 1x1 layers without residual on this kernel (default), 0 = implicit GEMM
+#include "cn_internal.h"
+#include "cn_tuning.h"
 
 namespace {
 
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(J_NT, 2) void proj1x1_kernel(const JArgs a)
 // no residual; f32s or plain NHWC output whose pitch covers whole 32-channel groups of the padded Cout.
 bool cn_proj1x1_takes(int B, int H, int W, int Cin, int Cout, int stride, int in_pitch, int out_pitch)
 {
-    if (!cn_tune_proj) return false;
+    if (!cn_knobs.proj) return false;
     if ((Cin & 31) || (in_pitch & 31) || (out_pitch & 31) || (stride != 1 && stride != 2)) return false;
     if (out_pitch < (Cout + 31) / 32 * 32) return false;
     if ((size_t)B * H * W * in_pitch * 4 >= ((size_t)1 << 32)) return false;

@@ -15,11 +15,9 @@
 //   * the K loop has no barriers and no global loads: MFMA A fragments are read straight
 //     from the window (address = row base of the pixel + table offset of k), B fragments with
 //     ds_read_b128.
-#include "cn_common.h"
+#include "cn_internal.h"
+#include "cn_tuning.h"
 #include <type_traits>
-
-int cn_tune_stem_stagger = 0;   // cn_set_tuning key 44: start delay of the second resident workgroup of the stem + max-pool kernel, units of 256 cycles
-int cn_tune_stem_dbg = 0;   // cn_set_tuning key 43: probe switches of the stem + max-pool kernel (StemArgs.dbg)
 
 namespace {
 
@@ -958,8 +956,8 @@ int launch_stem_pool_f32s(const StemArgs &a0, int B, int R, hipStream_t st)
 {
     constexpr size_t lds = (size_t)2 * CM_PLANE + (size_t)2 * 64 * SLDW * 2 + 2 * 2 * 64 * 4;
     StemArgs a = a0;
-    a.dbg = cn_tune_stem_dbg & 255;
-    a.stagger = cn_tune_stem_stagger;
+    a.dbg = cn_knobs.stem_dbg & 255;
+    a.stagger = cn_knobs.stem_stagger;
     const int nstrips = B * (a.Ho / 2 / R);
     int wgs = nstrips < 512 ? nstrips : 512;  // two resident workgroups per CU
     if (a.stagger == 1000) { wgs = nstrips < 256 ? nstrips : 256; a.stagger = 0; }   // probe: one workgroup per CU

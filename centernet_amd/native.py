@@ -5,6 +5,7 @@ There is no fallback: if the HIP library has not been built (``python -c
 entry point raises.  PyTorch is used only for device memory and streams; tensors
 cross this boundary as raw device pointers.
 """
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -75,6 +76,9 @@ def _declare(lib):
     lib.cn_arch.restype = ctypes.c_char_p
     lib.cn_set_tuning.restype = i
     lib.cn_set_tuning.argtypes = [i, i]
+    lib.cn_get_tuning.restype = i
+    lib.cn_get_tuning.argtypes = [i, ctypes.POINTER(i)]
+    lib.cn_reset_tuning.restype = i
     lib.cn_dcn_v2_forward_workspace_bytes.restype = sz
     lib.cn_dcn_v2_forward_workspace_bytes.argtypes = [i] * 8
     lib.cn_dcn_v2_forward_f32.restype = i
@@ -246,6 +250,28 @@ def lib():
 def check(rc, what):
     if rc != CN_OK:
         raise NativeError("%s failed: %s (%d)" % (what, lib().cn_status_string(rc).decode(), rc))
+
+
+@contextlib.contextmanager
+def tuning(knobs):
+    """Run a block with ``cn_set_tuning`` keys set: ``with native.tuning({23: 2, 5: 1}): ...``.
+
+    The values the keys had on entry are put back on exit, also when the block raises.  A key or value
+    the library refuses raises NativeError (keys set before it are restored).
+    """
+    l = lib()
+    before = {}
+    for key in knobs:
+        v = ctypes.c_int()
+        check(l.cn_get_tuning(key, ctypes.byref(v)), "cn_get_tuning(%d)" % key)
+        before[key] = v.value
+    try:
+        for key, value in knobs.items():
+            check(l.cn_set_tuning(key, value), "cn_set_tuning(%d, %d)" % (key, value))
+        yield
+    finally:
+        for key, value in before.items():
+            l.cn_set_tuning(key, value)
 
 
 def stream_ptr():

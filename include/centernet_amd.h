@@ -85,65 +85,104 @@ const char *cn_arch(void);
  * while nobody calls cn_set_tuning.  Set knobs once, before the first launch (as bench.py --tune does), or
  * with all streams of the process idle; a value changed under a running launch list gives a mix of forms
  * (every form computes the same function, so results stay valid, timings do not).
- * key 1: LDS tile buffers of the dense implicit-GEMM kernels, 0 = default, 1 or 2.
- * key 2: 1 = never pick 64-wide N tiles for Cout > 64 (default 0 = pick them when they
- *        avoid a half-empty 128-wide tile).
- * key 3: (retired) pixel tile of the deformable kernel; 64-pixel tiles are the only form built.
- * key 4: pixel tile of the dense kernels for Cout > 64, 0 = default, 64 or 128.
- * key 5: 1 = never split K.
- * key 6: 1 = run the 3-channel stem on the generic implicit-GEMM kernel instead of the
- *        LDS-window kernel (cn_stem.hip).
- * key 8: s_setprio(1) around the MFMA clusters (default 1).  key 9: ablation only.
- * key 10: 1 = run 3x3/stride-1 layers on the generic implicit GEMM instead of the LDS-halo
- *         kernel (cn_conv3x3.hip).
- * key 11: 1 = LDS-window deformable kernel (cn_dcn.hip) instead of the default global-gather
- *         form (cn_conv.hip); kept for A/B: it measured 20-30 % slower.
- * key 7: XCD-aware tile order: 0 = deformable kernel only (default, +5-10 % there), 1 = also
- *        the dense implicit-GEMM kernels (no gain measured), 2 = nowhere.
- * key 19: 64-wide LDS-halo tiles at four workgroups per CU (single-buffered weight tile,
- *         <= 128 registers): 0 = when that needs fewer dispatch rounds (default), 1 = always,
- *         2 = never.
- * key 18: phase shift of the workgroups that share a CU in the LDS-halo kernel, in percent of
- *         one tile's MFMA time (default 100, 0 = off); applied to launches of >= 4 dispatch rounds.
- * key 16 / 17: split-K: least K chunks per slice (default 8) / most slices (default 16).
- * key 15: fp32 / fp16 kernels: 0 = 4-wave instead of 8-wave workgroups for the 128-wide tiles of
- *         the LDS-halo kernel (default 1: +1 %, measured).
- * key 14: 64-wide layers in the LDS-halo kernel as 256-pixel tiles: 1 = four waves, 2 / 3 = eight
- *         waves (f32s; one / three taps of weight prefetch); default 0 (measured, no gain).
- * key 21: f32s LDS-halo kernel (A/B switches): bit 0 = 128-wide tiles as eight waves of 32 x 64
- *         with weights three taps ahead instead of four waves of 64 x 64 two taps ahead
- *         (default 0: +1 % on resdcn_18); bit 1 = every 64-wide layer two taps ahead (default:
- *         one tap for two-chunk layers, three for longer K; measured); bit 2 = 8 x 16 pixel tiles
- *         on wide maps too (no difference, measured).
- * key 13: tap split of the deformable kernel, 0 = auto, 1 = never, 3 or 9 = force.
- * key 20: f32s LDS-halo kernel, 128-wide tiles: 1 = per-tap weight tile in LDS (default),
- *         0 = weights streamed into registers from the fragment-ordered copy (+5-20 % in a
- *         back-to-back micro-benchmark, no gain inside the network: measured).
+ * cn_set_tuning answers CN_ERR_UNSUPPORTED for an unknown key or a value outside the key's set, and then
+ * changes nothing.  (default) marks the value a key has at start and after cn_reset_tuning.
+ * Dense implicit GEMM and dispatch (cn_conv.hip):
+ * key 1: LDS tile buffers of the dense implicit-GEMM kernels, 0 = per-shape default (default), 1 or 2 = force.
+ * key 2: 1 = never pick 64-wide N tiles for Cout > 64; 0 (default) = pick them when they avoid a
+ *        half-empty 128-wide tile.
+ * key 3: (retired) pixel tile of the deformable kernel; 0 and 64 are accepted and ignored, 64-pixel tiles
+ *        are the only form built.  Reads back 0.
+ * key 4: pixel tile of the dense kernels for Cout > 64, 0 = by grid size (default), 64 or 128 = force.
+ * key 5: 1 = never split K (default 0).
+ * key 6: 1 = run the 3-channel stem on the generic implicit-GEMM kernel instead of the LDS-window
+ *        kernel (cn_stem.hip) (default 0).
+ * key 7: XCD-aware tile order: 0 = deformable kernel only (default, +5-10 % there), 1 = also the dense
+ *        implicit-GEMM kernels (no gain measured), 2 = nowhere.
+ * key 8: s_setprio(1) around the MFMA clusters, 0 or 1 (default 1).
+ * key 9: ablation and probe switches, a bit set, 0 ... 2047 (default 0): bit 0 / 1 = skip A / B staging
+ *        (results are then wrong), the further bits are kernel-specific; bits 8 / 9 = instrumented
+ *        instantiations of the team / wide deformable forms.
+ * key 10: 1 = run 3x3 layers and ConvTranspose2d(4, 2, 1) on the generic implicit GEMM instead of the
+ *         LDS-halo kernel (cn_conv3x3.hip) and the other specialised 3x3 kernels (default 0).
+ * key 11: (retired) fp32 LDS-window deformable kernel, removed (20-30 % slower than the gather form);
+ *         only 0 is accepted.  Reads back 0.
  * key 12: 0 = one-tile-per-workgroup stem kernel instead of the persistent, prefetching one
  *         (default 1; both in cn_stem.hip).
- * key 22: deformable kernel: 1 = a tile is an 8-wide BLOCK of pixels (8 x 8 / 8 x 16) when the map
- *         divides into them (default: the nine taps of a block sample a compact neighbourhood that
+ * key 13: tap split of the gather-form deformable kernel, 0 = auto (default), 1 = never, 3 or 9 = force.
+ * key 16: split-K: least K chunks per slice, 1 ... 64 (default 8).
+ * key 17: split-K: most slices, 1 ... 64 (default 16).
+ * key 22: gather-form deformable kernel: 1 = a tile is an 8-wide BLOCK of pixels (8 x 8 / 8 x 16) when the
+ *         map divides into them (default: the nine taps of a block sample a compact neighbourhood that
  *         stays in L1 / L2), 0 = BM consecutive pixels of a row.
- * key 23: f32s deformable kernel: 0 = the register-sampling LDS-window form (cn_dcn2.hip: every
- *         lane samples its own MFMA operand from a window of the input in LDS) for the shapes it
- *         takes when the grid has >= 192 workgroups (default), 1 = the global-gather form always,
- *         2 = the register-sampling form for every shape it takes (tests), 3 = the earlier
- *         wave-specialised window form for every shape it takes (kept for comparison: slower).
+ * key 23: form of the f32s deformable kernel.  0 = by shape and grid (default): the wide form (cn_dcn4.hip,
+ *         see key 41) or the team form (cn_dcn3.hip, see key 36) on grids that fill the chip, else the
+ *         register-sampling LDS-window form (cn_dcn2.hip: every lane samples its own MFMA operand from a
+ *         window of the input in LDS) when the grid has >= 192 workgroups, else the global-gather form.
+ *         1 = the global-gather form always.  For every shape the form takes (tests, A/B): 2 = the
+ *         register-sampling form, 4 / 5 = the team form in T / N mode, 6 / 7 = the wide form (a workgroup
+ *         owns ALL output channels of its tile; 7 = four blocks per workgroup).  3 is refused (the
+ *         wave-specialised window form it selected was removed).
  * key 27: 7x7 / stride 1 stem of <= 16 output channels with CN_CONV_STEM_F32S: 1 = f32s kernel
  *         (default), 0 = the fp32 16x16x4 kernel (then cn_stem_f32s_supported answers 0 for it).
+ * LDS-halo kernel (cn_conv3x3.hip):
+ * key 14: 64-wide layers as 256-pixel tiles: 1 = four waves, 2 / 3 = eight waves (f32s; one / three taps
+ *         of weight prefetch); default 0 (measured, no gain).
+ * key 15: fp32 / fp16 kernels: 0 = 4-wave instead of 8-wave workgroups for the 128-wide tiles
+ *         (default 1: +1 %, measured).
+ * key 18: phase shift of the workgroups that share a CU, in percent of one tile's MFMA time, 0 ... 255
+ *         (default 100, 0 = off); applied to launches of >= 4 dispatch rounds.
+ * key 19: 64-wide tiles at four workgroups per CU (single-buffered weight tile, <= 128 registers):
+ *         0 = when that needs fewer dispatch rounds (default), 1 = always, 2 = never.
+ * key 20: f32s, 128-wide tiles: 1 = per-tap weight tile in LDS (default), 0 = weights streamed into
+ *         registers from the fragment-ordered copy (+5-20 % in a back-to-back micro-benchmark, no gain
+ *         inside the network: measured).
+ * key 21: f32s (A/B switches, 0 ... 7, default 0): bit 0 = 128-wide tiles as eight waves of 32 x 64 with
+ *         weights three taps ahead instead of four waves of 64 x 64 two taps ahead (+1 % on resdcn_18
+ *         without it); bit 1 = every 64-wide layer two taps ahead (default: one tap for two-chunk layers,
+ *         three for longer K; measured); bit 2 = 8 x 16 pixel tiles on wide maps too (no difference,
+ *         measured).
+ * key 24: 1-D grid with the column blocks of a pixel tile dispatched together on one XCD (0 ... 3, default 1):
+ *         bit 0 = for the fused heads, bit 1 = for plain layers of several Cout blocks; 0 = one grid row
+ *         per head / block.
  * key 26: fused f32s heads with a hidden layer wider than 64: 1 = hidden layer kept in registers
  *         (default), 0 = staged through LDS; 2 = 128-wide slices (register-bound, A/B only),
  *         3 = the register form for 64-wide hidden layers too (slower there, A/B only).
- * key 24: fused heads: 1 = 1-D grid with the heads of a pixel tile dispatched together on one XCD
- *         (default), 0 = one grid row per head.
- * key 23 (round 5 / 6 values): 4 / 5 = the team form (cn_dcn3.hip) in T / N mode, 6 / 7 = the wide form
- *         (cn_dcn4.hip: a workgroup owns ALL output channels of its tile; 7 = four blocks per workgroup)
- *         for every shape they take.
- * key 41: 1 = layers with Cout % 128 == 0 take the wide deformable form (default), 0 = the team form.
- * key 42: wide form: K split until a launch has this many workgroups (default 256).
- * key 43 / 44: stem + max-pool kernel: probe switches of its instrumented instantiation / start delay of
- *         the second resident workgroup (measurement only; defaults 0). */
+ * Persistent loader / consumer 3x3 kernel for f32s tensors (cn_conv3x3p.hip):
+ * key 28: 0 = off (the LDS-halo kernel takes its layers), 1 = on for the shapes it takes (default),
+ *         2 ... 7 = also for launches of fewer than 256 work items.
+ * key 29: start delay of the second resident workgroup, 0 ... 255 units of 256 cycles (default 0).
+ * key 30: A/B switches, a bit set, 0 ... 255 (default 2): bit 0 = no s_setprio(1) around the consumers'
+ *         MFMA block, bit 1 = the pipelined schedule.
+ * key 31: 1 = the fused heads with a 64-wide hidden layer run on it (default), 0 = on the LDS-halo kernel.
+ * key 32: 1 = ConvTranspose2d(4, 2, 1) runs on it in parity form (default), 0 = on the LDS-halo kernel.
+ * key 33: 1 = 3x3 / stride 2 / pad 1 runs on it in parity-plane form (default), 0 = on the implicit GEMM.
+ * Team form of the f32s deformable kernel (cn_dcn3.hip):
+ * key 36: when key 23 = 0: 0 = off, 1 = layers with <= 64 output channels, 2 = every layer it takes
+ *         (T mode), 3 = every layer, N mode where Cout is a multiple of 128 and that still fills the
+ *         chip (default).
+ * key 37: K split until a launch has this many workgroups, 1 ... 4096 (default 512).
+ * key 38: start delay of the second resident workgroup of every CU, 0 ... 1024 units of 256 cycles
+ *         (default 32).
+ * Offset / mask convolution of the deformable modules (cn_offconv.hip):
+ * key 39: 1 = 3x3 layers of <= 32 output channels on a plain fp32 tensor run on it (default),
+ *         0 = on the LDS-halo kernel.
+ * key 40: workgroups from which its four-wave form is used, 0 ... 1000000 (default 768).
+ * Wide form of the f32s deformable kernel (cn_dcn4.hip):
+ * key 41: when key 23 = 0: 1 = layers with Cout % 128 == 0 take the wide form (default), 0 = the team form.
+ * key 42: K split until a launch has this many workgroups, 1 ... 4096 (default 256).
+ * key 45: 1 = L2 prefetch of the weight slabs three steps ahead (default), 0 = none.
+ * Stem + max-pool kernel (cn_stem.hip), measurement only:
+ * key 43: probe switches of its instrumented instantiation, 0 ... 31 (default 0).
+ * key 44: start delay of the second resident workgroup, 0 ... 1024 units of 256 cycles (default 0).
+ * 1x1 projections (cn_proj.hip):
+ * key 46: 1 = f32s 1x1 layers without residual run on the direct-fragment kernel (default),
+ *         0 = on the implicit GEMM. */
 int cn_set_tuning(int key, int value);
+/* Current value of a knob into *value; CN_ERR_UNSUPPORTED for a key cn_set_tuning does not know. */
+int cn_get_tuning(int key, int *value);
+/* Every knob back to its default. */
+int cn_reset_tuning(void);
 
 
 

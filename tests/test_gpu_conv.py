@@ -12,6 +12,14 @@ pytestmark = pytest.mark.gpu
 TOL = 2e-5
 
 
+@pytest.fixture(autouse=True)
+def _default_tuning():
+    """Every test of this module leaves the cn_set_tuning keys at the library's defaults."""
+    yield
+    from centernet_amd import native
+    native.lib().cn_reset_tuning()
+
+
 def _check(y, ref):
     err = (y - ref).abs() / (1 + ref.abs())
     assert float(err.max()) < TOL, float(err.max())
@@ -70,39 +78,27 @@ def test_conv_bn_relu_residual(dev, cfg, split):
 def test_conv_256_pixel_tiles(dev):
     """Opt-in 8 x 32 tiles of the LDS-halo kernel (cn_set_tuning key 14)."""
     from centernet_amd import native
-    lib = native.lib()
-    lib.cn_set_tuning(14, 1)
-    try:
+    with native.tuning({14: 1}):
         _conv_case(dev, (16, 64, 128, 128, 64, 3, 1, 1, False, True, True, True))
         _conv_case(dev, (17, 48, 100, 132, 64, 3, 1, 1, True, False, True, False))
-    finally:
-        lib.cn_set_tuning(14, 0)
 
 
 def test_conv_four_workgroups_per_cu_variant(dev):
     """64-wide halo tiles at four workgroups per CU (single-buffered weights; key 19)."""
     from centernet_amd import native
-    lib = native.lib()
-    try:
-        for v in (1, 2):
-            lib.cn_set_tuning(19, v)
+    for v in (1, 2):
+        with native.tuning({19: v}):
             _conv_case(dev, (4, 64, 64, 64, 64, 3, 1, 1, False, True, True, True))
             _conv_case(dev, (3, 96, 19, 27, 40, 3, 1, 1, True, False, True, False))
-    finally:
-        lib.cn_set_tuning(19, 0)
 
 
 def test_conv_8_wave_tiles(dev):
     """Both workgroup shapes of the 128-wide LDS-halo tiles (key 15: 8 waves default, 4 waves)."""
     from centernet_amd import native
-    lib = native.lib()
-    try:
-        for v in (1, 0):
-            lib.cn_set_tuning(15, v)
+    for v in (1, 0):
+        with native.tuning({15: v}):
             _conv_case(dev, (2, 256, 32, 32, 256, 3, 1, 1, False, True, True, True))
             _conv_case(dev, (3, 160, 19, 27, 130, 3, 1, 1, True, False, True, False))
-    finally:
-        lib.cn_set_tuning(15, 1)
 
 
 def _conv_case(dev, cfg, split=False):
@@ -233,18 +229,14 @@ def test_stem_kernels_vs_torch(dev, cfg):
     w = torch.from_numpy(synth.normal((Cout, 3, 7, 7), (2.0 / 147) ** 0.5, 2))
     bn = _bn(Cout, 4)
     ref = F.relu(bn(F.conv2d(x, w, None, stride, 3))).detach()
-    lib = native.lib()
-    try:
-        for variant in (1, 0):
-            lib.cn_set_tuning(12, variant)
+    for variant in (1, 0):
+        with native.tuning({12: variant}):
             pb = PlanBuilder(dev, B, H, W)
             xin = pb.set_input(3)
             y = pb.conv(xin, w, bn=bn, relu=True, stride=stride, padding=3)
             pb.input.t = x.to(dev)
             _run(pb)
             _check(y.t.permute(0, 3, 1, 2).cpu(), ref)
-    finally:
-        lib.cn_set_tuning(12, 1)
 
 
 def test_stem16_f32s_and_fp32_forms(dev):
@@ -254,10 +246,8 @@ def test_stem16_f32s_and_fp32_forms(dev):
     from 1 (the image exponent is applied while the window is split)."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder, exponent_for
-    lib = native.lib()
-    try:
-        for form in (1, 0):
-            assert lib.cn_set_tuning(27, form) == 0
+    for form in (1, 0):
+        with native.tuning({27: form}):
             for (B, H, W, Cout, mul) in [(2, 7, 128, 16, 1.0), (1, 33, 384, 13, 300.0)]:
                 x = synth.images(B, H, W, 7) * mul
                 w = torch.from_numpy(synth.normal((Cout, 3, 7, 7), (2.0 / 147) ** 0.5, 2))
@@ -270,8 +260,6 @@ def test_stem16_f32s_and_fp32_forms(dev):
                 got = y.t.permute(0, 3, 1, 2).cpu()
                 err = float((got - ref).abs().max()) / max(1.0, float(ref.abs().max()))
                 assert err < 2e-5, (form, B, H, W, Cout, err)
-    finally:
-        lib.cn_set_tuning(27, 1)
 
 
 @pytest.mark.parametrize("split", [True, False], ids=["f32s", "fp32mfma"])
@@ -281,11 +269,8 @@ def test_stem16_f32s_and_fp32_forms(dev):
 def test_conv_transpose_4x4_s2(dev, cfg, halo, split):
     """Both forms: LDS-halo parity kernel (default) and the generic implicit GEMM (key 10)."""
     from centernet_amd import native
-    native.lib().cn_set_tuning(10, 0 if halo else 1)
-    try:
+    with native.tuning({10: 0 if halo else 1}):
         _deconv_case(dev, cfg, split)
-    finally:
-        native.lib().cn_set_tuning(10, 0)
 
 
 def _deconv_case(dev, cfg, split=False):
@@ -318,36 +303,31 @@ def test_conv_transpose_4x4_s2_on_the_persistent_kernel(dev, cfg):
     resdcn_18's second up-sampling layer at the benchmark batch, on the library's own routing."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
-    lib = native.lib()
     B, Cin, H, W, Cout = cfg
     nref = min(B, 2)
     x = torch.from_numpy(synth.normal((B, Cin, H, W), 1.0, 1)).relu_()
     w = torch.from_numpy(synth.normal((Cin, Cout, 4, 4), (2.0 / (Cin * 4)) ** 0.5, 2))
     bn = _bn(Cout, 3)
     ref = F.relu(bn(F.conv_transpose2d(x[:nref], w, None, 2, 1, 0))).detach()
-    assert lib.cn_set_tuning(28, 2 if B < 32 else 1) == 0
-    try:
+    with native.tuning({28: 2 if B < 32 else 1}):
         for out_plain in (False, True):
             got = {}
             for key32 in (1, 0):
-                assert lib.cn_set_tuning(32, key32) == 0
-                pb = PlanBuilder(dev, B, H, W, split=True)
-                y = pb.conv_transpose4x4s2(pb.packed(_nhwc_act(x, dev)), w, bn=bn, relu=True, out_plain=out_plain)
-                assert y.fmt == ("f32" if out_plain else "f32s")
-                _run(pb)
-                got[key32] = y.to_float().clone()
-                if key32 == 1:
-                    raw = y.t.clone()
+                with native.tuning({32: key32}):
+                    pb = PlanBuilder(dev, B, H, W, split=True)
+                    y = pb.conv_transpose4x4s2(pb.packed(_nhwc_act(x, dev)), w, bn=bn, relu=True, out_plain=out_plain)
+                    assert y.fmt == ("f32" if out_plain else "f32s")
                     _run(pb)
-                    assert torch.equal(raw, y.t), "not deterministic run to run"
-                    if not out_plain and Cout % 32 == 0 and y.pitch > Cout:
-                        assert float(y.t[..., Cout:].abs().max()) == 0.0
+                    got[key32] = y.to_float().clone()
+                    if key32 == 1:
+                        raw = y.t.clone()
+                        _run(pb)
+                        assert torch.equal(raw, y.t), "not deterministic run to run"
+                        if not out_plain and Cout % 32 == 0 and y.pitch > Cout:
+                            assert float(y.t[..., Cout:].abs().max()) == 0.0
             _check(got[1][:nref].permute(0, 3, 1, 2).cpu(), ref)
             d = float((got[1] - got[0]).abs().max()) / max(1.0, float(got[0].abs().max()))
             assert d < 2e-5, d
-    finally:
-        lib.cn_set_tuning(28, 1)
-        lib.cn_set_tuning(32, 1)
 
 
 @pytest.mark.parametrize("cfg", [(2, 64, 32, 32, 128), (1, 128, 16, 32, 256), (1, 96, 17, 23, 96),
@@ -361,35 +341,30 @@ def test_conv3x3_stride2_on_the_persistent_kernel(dev, cfg):
     layer2 entry at the benchmark batch on the library's own routing."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
-    lib = native.lib()
     B, Cin, H, W, Cout = cfg
     nref = min(B, 2)
     x = torch.from_numpy(synth.normal((B, Cin, H, W), 1.0, 1)).relu_()
     w = torch.from_numpy(synth.normal((Cout, Cin, 3, 3), (2.0 / (Cin * 9)) ** 0.5, 2))
     bn = _bn(Cout, 3)
     ref = F.relu(bn(F.conv2d(x[:nref], w, None, 2, 1))).detach()
-    assert lib.cn_set_tuning(28, 2 if B < 32 else 1) == 0
-    try:
+    with native.tuning({28: 2 if B < 32 else 1}):
         for out_plain in (False, True):
             got = {}
             for key33 in (1, 0):
-                assert lib.cn_set_tuning(33, key33) == 0
-                pb = PlanBuilder(dev, B, H, W, split=True)
-                y = pb.conv(pb.packed(_nhwc_act(x, dev)), w, bn=bn, relu=True, stride=2, padding=1,
-                            out_plain=out_plain)
-                assert y.fmt == ("f32" if out_plain else "f32s") and (y.H, y.W) == tuple(ref.shape[2:])
-                _run(pb)
-                got[key33] = y.to_float().clone()
-                if key33 == 1:
-                    raw = y.t.clone()
+                with native.tuning({33: key33}):
+                    pb = PlanBuilder(dev, B, H, W, split=True)
+                    y = pb.conv(pb.packed(_nhwc_act(x, dev)), w, bn=bn, relu=True, stride=2, padding=1,
+                                out_plain=out_plain)
+                    assert y.fmt == ("f32" if out_plain else "f32s") and (y.H, y.W) == tuple(ref.shape[2:])
                     _run(pb)
-                    assert torch.equal(raw, y.t), "not deterministic run to run"
+                    got[key33] = y.to_float().clone()
+                    if key33 == 1:
+                        raw = y.t.clone()
+                        _run(pb)
+                        assert torch.equal(raw, y.t), "not deterministic run to run"
             _check(got[1][:nref].permute(0, 3, 1, 2).cpu(), ref)
             d = float((got[1] - got[0]).abs().max()) / max(1.0, float(got[0].abs().max()))
             assert d < 2e-5, d
-    finally:
-        lib.cn_set_tuning(28, 1)
-        lib.cn_set_tuning(33, 1)
 
 
 @pytest.mark.parametrize("form", ["conv", "conv_res", "conv_plain_res", "deconv", "s2", "heads"])
@@ -402,51 +377,46 @@ def test_persistent_kernel_pipelined_schedule_is_bit_identical(dev, form):
     fragment lost to an early DMA refill or a late LDS read would show as a rare differing tile)."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
-    lib = native.lib()
     shapes = {"conv": [(2, 96, 20, 24, 96), (32, 64, 128, 128, 64), (32, 256, 32, 32, 256)],
               "conv_res": [(3, 64, 17, 40, 64), (32, 64, 128, 128, 64), (32, 512, 16, 16, 512)],
               "conv_plain_res": [(2, 128, 16, 32, 128), (32, 128, 64, 64, 128)],
               "deconv": [(2, 128, 37, 45, 96), (32, 128, 64, 64, 64)],
               "s2": [(1, 96, 17, 23, 96), (32, 64, 128, 128, 128)],
               "heads": [(1, 64, 20, 24, 0), (32, 64, 128, 128, 0)]}[form]
-    try:
-        for (B, Cin, H, W, Cout) in shapes:
-            assert lib.cn_set_tuning(28, 2 if B < 32 else 1) == 0
+    for (B, Cin, H, W, Cout) in shapes:
+        with native.tuning({28: 2 if B < 32 else 1}):
             x = torch.from_numpy(synth.normal((B, Cin, H, W), 1.0, 1)).relu_()
             xa = _nhwc_act(x, dev)
             res = _nhwc_act(torch.from_numpy(synth.normal((B, Cout, H, W), 1.0, 5)), dev) if "res" in form else None
             pairs = _heads_case(Cin, 64, {"hm": 80, "wh": 2, "reg": 2}, seed=B) if form == "heads" else None
             raws = {}
             for knobs in (0, 2):
-                assert lib.cn_set_tuning(30, knobs) == 0
-                pb = PlanBuilder(dev, B, H, W, split=True)
-                xin = pb.packed(xa)
-                if form == "heads":
-                    outs = pb.heads_from_convs(xin, pairs)
-                    ts = [outs[n].t for n in ("hm", "wh", "reg")]
-                elif form == "deconv":
-                    w = torch.from_numpy(synth.normal((Cin, Cout, 4, 4), (2.0 / (Cin * 4)) ** 0.5, 2))
-                    ts = [pb.conv_transpose4x4s2(xin, w, bn=_bn(Cout, 3), relu=True).t]
-                else:
-                    w = torch.from_numpy(synth.normal((Cout, Cin, 3, 3), (2.0 / (Cin * 9)) ** 0.5, 2))
-                    r = None
-                    if res is not None:
-                        r = pb.packed(res) if form == "conv_res" else pb.plain(res)
-                    ts = [pb.conv(xin, w, bn=_bn(Cout, 3), relu=True, stride=2 if form == "s2" else 1, padding=1,
-                                  residual=r, out_plain=(form == "conv_plain_res")).t]
-                reps = 6 if B == 32 else 2
-                for rep in range(reps):
-                    for t in ts:
-                        t.zero_()
-                    _run(pb)
-                    if knobs == 0 and rep == 0:
-                        raws = [t.clone() for t in ts]
-                        assert all(float(t.abs().max()) > 0 for t in raws)
-                    for t, r0 in zip(ts, raws):
-                        assert torch.equal(t, r0), (form, (B, Cin, H, W, Cout), knobs, rep)
-    finally:
-        lib.cn_set_tuning(28, 1)
-        lib.cn_set_tuning(30, 2)
+                with native.tuning({30: knobs}):
+                    pb = PlanBuilder(dev, B, H, W, split=True)
+                    xin = pb.packed(xa)
+                    if form == "heads":
+                        outs = pb.heads_from_convs(xin, pairs)
+                        ts = [outs[n].t for n in ("hm", "wh", "reg")]
+                    elif form == "deconv":
+                        w = torch.from_numpy(synth.normal((Cin, Cout, 4, 4), (2.0 / (Cin * 4)) ** 0.5, 2))
+                        ts = [pb.conv_transpose4x4s2(xin, w, bn=_bn(Cout, 3), relu=True).t]
+                    else:
+                        w = torch.from_numpy(synth.normal((Cout, Cin, 3, 3), (2.0 / (Cin * 9)) ** 0.5, 2))
+                        r = None
+                        if res is not None:
+                            r = pb.packed(res) if form == "conv_res" else pb.plain(res)
+                        ts = [pb.conv(xin, w, bn=_bn(Cout, 3), relu=True, stride=2 if form == "s2" else 1, padding=1,
+                                      residual=r, out_plain=(form == "conv_plain_res")).t]
+                    reps = 6 if B == 32 else 2
+                    for rep in range(reps):
+                        for t in ts:
+                            t.zero_()
+                        _run(pb)
+                        if knobs == 0 and rep == 0:
+                            raws = [t.clone() for t in ts]
+                            assert all(float(t.abs().max()) > 0 for t in raws)
+                        for t, r0 in zip(ts, raws):
+                            assert torch.equal(t, r0), (form, (B, Cin, H, W, Cout), knobs, rep)
 
 
 @pytest.mark.parametrize("persistent", [1, 0])
@@ -459,35 +429,32 @@ def test_concat_members_written_in_place(dev, persistent):
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
     B, C, H, W = 8, 64, 64, 64      # (grids large enough that no layer wants split-K)
-    native.lib().cn_set_tuning(28, persistent)     # both 3x3 kernels take a residual pitch
-    x = torch.from_numpy(synth.normal((B, C, 2 * H, 2 * W), 1.0, 1)).relu_()
-    r = torch.from_numpy(synth.normal((B, C, H, W), 1.0, 2))
-    extra = torch.from_numpy(synth.normal((B, 32, H, W), 1.0, 3)).relu_()
-    w1 = torch.from_numpy(synth.normal((C, C, 3, 3), (2.0 / (C * 9)) ** 0.5, 4))
-    w2 = torch.from_numpy(synth.normal((C, C, 3, 3), (2.0 / (C * 9)) ** 0.5, 5))
-    bn1, bn2 = _bn(C, 6), _bn(C, 7)
-    bottom = F.max_pool2d(x, 2, 2)
-    x1 = F.relu(bn1(F.conv2d(bottom, w1, None, 1, 1)) + r)
-    x2 = F.relu(bn2(F.conv2d(x1, w2, None, 1, 1)) + x1)
-    ref = torch.cat([x2, x1, extra, bottom], 1).detach()
-    pb = PlanBuilder(dev, B, 2 * H, 2 * W, split=True)
-    xa = pb.packed(_nhwc_act(x, dev))
-    ra = pb.packed(_nhwc_act(r, dev))
-    ea = pb.packed(_nhwc_act(extra, dev))
-    n0 = len(pb.ops)
-    buf, slots = pb.concat_buffer(B, H, W, [C, C, 32, C])
-    assert buf is not None and buf.pitch == 3 * C + 32
-    pooled = pb.maxpool(xa, 2, 2, 0, out=slots[3])
-    a1 = pb.conv(pooled, w1, bn=bn1, relu=True, residual=ra, padding=1, out=slots[1])       # residual pitch 64, output pitch 224
-    a2 = pb.conv(a1, w2, bn=bn2, relu=True, residual=a1, padding=1, out=slots[0])
-    assert all(a.t is buf.t for a in (pooled, a1, a2))
-    cat = pb.concat([a2, a1, ea, pooled], into=buf)
-    kinds = [k for k, _ in pb.trace[n0:]]
-    assert kinds.count("copy") == 1 and kinds.count("maxpool") == 1 and kinds.count("convert") == 0, kinds
-    try:
+    with native.tuning({28: persistent}):     # both 3x3 kernels take a residual pitch
+        x = torch.from_numpy(synth.normal((B, C, 2 * H, 2 * W), 1.0, 1)).relu_()
+        r = torch.from_numpy(synth.normal((B, C, H, W), 1.0, 2))
+        extra = torch.from_numpy(synth.normal((B, 32, H, W), 1.0, 3)).relu_()
+        w1 = torch.from_numpy(synth.normal((C, C, 3, 3), (2.0 / (C * 9)) ** 0.5, 4))
+        w2 = torch.from_numpy(synth.normal((C, C, 3, 3), (2.0 / (C * 9)) ** 0.5, 5))
+        bn1, bn2 = _bn(C, 6), _bn(C, 7)
+        bottom = F.max_pool2d(x, 2, 2)
+        x1 = F.relu(bn1(F.conv2d(bottom, w1, None, 1, 1)) + r)
+        x2 = F.relu(bn2(F.conv2d(x1, w2, None, 1, 1)) + x1)
+        ref = torch.cat([x2, x1, extra, bottom], 1).detach()
+        pb = PlanBuilder(dev, B, 2 * H, 2 * W, split=True)
+        xa = pb.packed(_nhwc_act(x, dev))
+        ra = pb.packed(_nhwc_act(r, dev))
+        ea = pb.packed(_nhwc_act(extra, dev))
+        n0 = len(pb.ops)
+        buf, slots = pb.concat_buffer(B, H, W, [C, C, 32, C])
+        assert buf is not None and buf.pitch == 3 * C + 32
+        pooled = pb.maxpool(xa, 2, 2, 0, out=slots[3])
+        a1 = pb.conv(pooled, w1, bn=bn1, relu=True, residual=ra, padding=1, out=slots[1])       # residual pitch 64, output pitch 224
+        a2 = pb.conv(a1, w2, bn=bn2, relu=True, residual=a1, padding=1, out=slots[0])
+        assert all(a.t is buf.t for a in (pooled, a1, a2))
+        cat = pb.concat([a2, a1, ea, pooled], into=buf)
+        kinds = [k for k, _ in pb.trace[n0:]]
+        assert kinds.count("copy") == 1 and kinds.count("maxpool") == 1 and kinds.count("convert") == 0, kinds
         _run(pb)
-    finally:
-        native.lib().cn_set_tuning(28, 1)
     _check(cat.to_float().permute(0, 3, 1, 2).cpu(), ref)
 
 
@@ -637,14 +604,12 @@ def test_fused_heads_on_the_persistent_kernel(dev, forced):
     shapes, = 1 is the library's own routing (taken at the benchmark shape)."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
-    lib = native.lib()
     cases = [(2, 64, 32, 32, {"hm": 80, "wh": 2, "reg": 2}),
              (1, 64, 20, 24, {"hm": 80, "wh": 2, "reg": 2}),          # edge tiles in both directions
              (3, 96, 17, 40, {"hm": 33, "nobias": 96, "a": 1, "b": 64, "c": 5}),
              (2, 32, 8, 16, {"hm": 3})] if forced == 2 else \
             [(32, 64, 128, 128, {"hm": 80, "wh": 2, "reg": 2})]
-    assert lib.cn_set_tuning(28, forced) == 0
-    try:
+    with native.tuning({28: forced}):
         for (B, Fc, H, W, heads) in cases:
             pairs = _heads_case(Fc, 64, heads, seed=B + H)
             x = torch.from_numpy(synth.normal((B, Fc, H, W), 1.0, 11)).relu_()
@@ -652,24 +617,21 @@ def test_fused_heads_on_the_persistent_kernel(dev, forced):
             ref = {n: pairs[n][1](F.relu(pairs[n][0](x[:nref]))) for n in heads}
             got = {}
             for key31 in (1, 0):
-                assert lib.cn_set_tuning(31, key31) == 0
-                pb = PlanBuilder(dev, B, H, W, split=True)
-                outs = pb.heads_from_convs(pb.packed(_nhwc_act(x, dev)), pairs)
-                assert len(pb.ops) == 2, "convert + one fused launch"
-                _run(pb)
-                got[key31] = {n: outs[n].t.clone() for n in heads}
-                if key31 == 1:      # run-to-run bit equality of the persistent kernel
+                with native.tuning({31: key31}):
+                    pb = PlanBuilder(dev, B, H, W, split=True)
+                    outs = pb.heads_from_convs(pb.packed(_nhwc_act(x, dev)), pairs)
+                    assert len(pb.ops) == 2, "convert + one fused launch"
                     _run(pb)
-                    for n in heads:
-                        assert torch.equal(outs[n].t, got[1][n]), n
+                    got[key31] = {n: outs[n].t.clone() for n in heads}
+                    if key31 == 1:      # run-to-run bit equality of the persistent kernel
+                        _run(pb)
+                        for n in heads:
+                            assert torch.equal(outs[n].t, got[1][n]), n
             for n in heads:
                 _check(got[1][n][:nref].cpu(), ref[n])
                 # the two kernels sum in different orders: equal to fp32 rounding, every image
                 d = float((got[1][n] - got[0][n]).abs().max()) / max(1.0, float(got[0][n].abs().max()))
                 assert d < 2e-5, (n, d)
-    finally:
-        lib.cn_set_tuning(28, 1)
-        lib.cn_set_tuning(31, 1)
 
 
 @pytest.mark.parametrize("form", [0, 1, 2, 3])
@@ -680,9 +642,7 @@ def test_fused_heads_hidden_layer_forms(dev, form):
     at a batch that puts several workgroups on every CU."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
-    lib = native.lib()
-    assert lib.cn_set_tuning(26, form) == 0
-    try:
+    with native.tuning({26: form}):
         for (B, Fc, H, W, heads, hidden) in [(2, 64, 32, 32, {"hm": 80, "wh": 2, "reg": 2}, 256),
                                               (1, 64, 19, 33, {"hm": 1, "hps": 34, "hm_hp": 17}, 256),
                                               (1, 96, 8, 64, {"hm": 5, "wh": 2}, 128),
@@ -721,8 +681,6 @@ def test_fused_heads_hidden_layer_forms(dev, form):
             if first is None:
                 first = cur
             assert torch.equal(cur, first)
-    finally:
-        lib.cn_set_tuning(26, 1)
 
 
 def test_f32s_kernels_are_run_to_run_deterministic(dev):
@@ -761,15 +719,11 @@ def test_f32s_halo_weight_forms(dev, lds_weights):
     (default) and the per-tap LDS weight tile (cn_set_tuning key 20) -- odd channel counts,
     several chunks, narrow and wide maps, residual."""
     from centernet_amd import native
-    lib = native.lib()
-    lib.cn_set_tuning(20, lds_weights)
-    try:
+    with native.tuning({20: lds_weights}):
         _conv_case(dev, (2, 256, 32, 32, 256, 3, 1, 1, False, True, True, True), split=True)
         _conv_case(dev, (3, 160, 19, 27, 130, 3, 1, 1, True, False, True, False), split=True)
         _conv_case(dev, (20, 96, 12, 20, 200, 3, 1, 1, True, True, False, False), split=True)
         _conv_case(dev, (16, 64, 64, 64, 192, 3, 1, 1, True, False, True, False), split=True)
-    finally:
-        lib.cn_set_tuning(20, 1)
 
 
 @pytest.mark.parametrize("scale", [1.0, 1e-4, 3e3])
@@ -790,19 +744,15 @@ def test_offset_conv_kernel(dev, cfg, scale):
     ref = F.conv2d(x.double(), w.double(), bias.double(), 1, 1)
     if relu:
         ref = F.relu(ref)
-    lib = native.lib()
     outs = []
     for key39 in (1, 0):
-        assert lib.cn_set_tuning(39, key39) == 0
-        try:
+        with native.tuning({39: key39}):
             pb = PlanBuilder(dev, B, H, W, split=True, exps={"x": exponent_for(float(x.abs().max()))})
             xa = Act(x.permute(0, 2, 3, 1).contiguous().to(dev), B, H, W, Cin, exp=pb._exp("x"), lid="x")
             om = pb._new(B, H, W, Cout, pitch=32, lid="om")
             y = pb.conv(xa, w, bias=bias, relu=relu, stride=1, padding=1, out=om, lid="om")
             assert y.fmt == "f32"
             _run(pb)
-        finally:
-            lib.cn_set_tuning(39, 1)
         got = y.t[..., :Cout].permute(0, 3, 1, 2).double().cpu()
         err = ((got - ref).abs() / (scale + ref.abs())).max()
         assert float(err) < TOL, (key39, float(err))
@@ -838,11 +788,9 @@ def test_projection_1x1_kernel(dev, cfg):
     if relu:
         ref = F.relu(ref)
     ref = ref.detach()
-    lib = native.lib()
     got = {}
-    try:
-        for key46 in (1, 0):
-            assert lib.cn_set_tuning(46, key46) == 0
+    for key46 in (1, 0):
+        with native.tuning({46: key46}):
             for out_plain in (False, True):
                 pb = PlanBuilder(dev, B, H, W, split=True)
                 xs = pb.packed(_nhwc_act(x, dev))
@@ -853,7 +801,5 @@ def test_projection_1x1_kernel(dev, cfg):
                 got[key46, out_plain] = yp.t[..., :Cout].permute(0, 3, 1, 2).cpu().double()
                 err = (got[key46, out_plain] - ref).abs() / (1 + ref.abs())
                 assert float(err.max()) < TOL, (key46, out_plain, float(err.max()))
-    finally:
-        lib.cn_set_tuning(46, 1)
     # the two kernels agree far inside the bar (same arithmetic, different summation order)
     assert float((got[1, True] - got[0, True]).abs().max()) < 2e-5 * float(ref.abs().max())

@@ -18,7 +18,14 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
-DCN_FORM_DEFAULT = 0     # cn_set_tuning key 23 as the library starts (csrc/cn_conv.hip g_tune_dcn_form)
+
+
+@pytest.fixture(autouse=True)
+def _default_tuning():
+    """Every test of this module leaves the cn_set_tuning keys at the library's defaults."""
+    yield
+    from centernet_amd import native
+    native.lib().cn_reset_tuning()
 
 
 def _check(y, ref):
@@ -243,10 +250,8 @@ def _dcn_f32s_nhwc(dev, x, off, mask, w, b, tap_split, out_plain, form=1, msig=F
         m64 = om[..., 18:27].astype(np.float64)
         om[..., 18:27] = np.log(m64 / (1.0 - m64)).astype(np.float32)
     want_scale = float(np.abs(x).max())
-    lib = native.lib()
-    lib.cn_set_tuning(13, tap_split)
-    lib.cn_set_tuning(23, form)    # 1 = global-gather form, 2 = register-sampling window form, 4 / 5 = team form (T / N mode), 0 = by shape
-    try:
+    # key 23: 1 = global-gather form, 2 = register-sampling window form, 4 / 5 = team form (T / N mode), 0 = by shape
+    with native.tuning({13: tap_split, 23: form}):
         pb = PlanBuilder(dev, B, H, W, split=True,
                          exps={"x": exponent_for(want_scale), "t1": exponent_for(4.0 * want_scale)})
         xa = Act(torch.from_numpy(np.ascontiguousarray(x.transpose(0, 2, 3, 1))).to(dev), B, H, W, C,
@@ -257,9 +262,6 @@ def _dcn_f32s_nhwc(dev, x, off, mask, w, b, tap_split, out_plain, form=1, msig=F
         for op in pb.ops:
             op()
         torch.cuda.synchronize()
-    finally:
-        lib.cn_set_tuning(13, 0)
-        lib.cn_set_tuning(23, DCN_FORM_DEFAULT)
     return y.to_float().permute(0, 3, 1, 2).cpu().numpy()
 
 

@@ -32,6 +32,14 @@ SCALES = [1e-4, 1e-2, 1.0, 1e2, 1e4, 1e6]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+@pytest.fixture(autouse=True)
+def _default_tuning():
+    """Every test of this module leaves the cn_set_tuning keys at the library's defaults."""
+    yield
+    from centernet_amd import native
+    native.lib().cn_reset_tuning()
+
+
 def _report(**kw):
     """Measured errors, appended to gpurun_out/f32s_sweep.jsonl (evidence next to the asserts)."""
     try:
@@ -219,7 +227,6 @@ def test_deformable_kernel_at_every_activation_scale(dev, scale, form):
     dx = rng.uniform(-2.5, 2.5, 9).astype(np.float32).astype(np.float64)
     logit = rng.standard_normal(9).astype(np.float32)
     mask = torch.sigmoid(torch.from_numpy(logit)).double().numpy()
-    lib = native.lib()
     for (B, C, H, W, Co), split in [((2, 128, 16, 16, 64), 0), ((2, 64, 32, 32, 64), 1),
                                     ((1, 256, 16, 16, 128), 3), ((1, 128, 16, 16, 64), 9),
                                     ((2, 64, 16, 32, 256), 0), ((1, 96, 8, 16, 384), 0)]:
@@ -236,18 +243,13 @@ def test_deformable_kernel_at_every_activation_scale(dev, scale, form):
             m.bias.mul_(scale)
             ref = F.relu(_dcn_ref64(x, dy, dx, mask, m.weight.double(), m.bias.double()))
         exps = {"x": _exp(x), "t1": _exp(ref)}
-        lib.cn_set_tuning(13, split)
-        lib.cn_set_tuning(23, form)
-        try:
+        with native.tuning({13: split, 23: form}):
             pb32 = PlanBuilder(dev, B, H, W, split=False)
             y32 = pb32.dcn(_act(x, dev, pb32, "x"), m, relu=True)
             _run(pb32)
             pb = PlanBuilder(dev, B, H, W, split=True, exps=exps)
             y = pb.dcn(_act(x, dev, pb, "x"), m, relu=True)
             _run(pb)
-        finally:
-            lib.cn_set_tuning(13, 0)
-            lib.cn_set_tuning(23, 0)
         err = _rel(y.to_float().permute(0, 3, 1, 2).cpu(), ref)
         err32 = _rel(y32.to_float().permute(0, 3, 1, 2).cpu(), ref)
         wd = _words(pb)

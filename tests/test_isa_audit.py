@@ -6,10 +6,7 @@ with the LGKM queue as its state; this test holds that NO barrier of a shipped i
 persistent 3x3 kernel, the deformable team kernel and the offset convolution can be reached with a
 ds_read in flight.  (The probe instantiation `conv3x3p_kernel<., ., DBG = true, ...>` is exempt: its
 switchable paths are infeasible combinations to a path-insensitive walk, and nothing launches it
-outside `tools/bench_c3p.py PROBE=1`.  The UNPIPELINED heads form, the A/B reference behind cn_set_tuning
-key 30, is held at its three known reports: the 1x1 epilogue's last read of the output scale / bias
-stash, whose wait sits inside the `pixel exists` branch; the stash is rewritten three steps into the
-next item, each of which waits lgkmcnt(0) for its own fragments first -- LDS returns in order.)
+outside `tools/bench_c3p.py PROBE=1`.  Every other instantiation, pipelined or not, is held at zero reports.)
 """
 import importlib.util
 import os
