@@ -3,10 +3,12 @@
 so the pin survives where /root/reference (and hence `make -C oracle _ref`) is not available.
 
     python tests/golden/gen_golden_ref.py            # needs oracle/_ref built -> ref_golden.npz
+    python tests/golden/gen_golden_ref.py --wide     # -> ref_golden_wide.npz only (ref_golden.npz untouched)
     python tests/golden/gen_golden_ref.py --digests  # -> ref_digests.json (tests/test_oracle_ref.py)
 
 Inputs are regenerated from seeds by the tests (dcn_inputs / nms_inputs below); only outputs are
-stored: the full forward output and every COL_STRIDE-th column entry of sample 0.
+stored: the full forward output and every COL_STRIDE-th column entry of sample 0
+(ref_golden_wide.npz: the forward output alone -- a second file, so that each stays below 1 MiB).
 """
 import os
 import sys
@@ -17,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_golden.npz")
+OUT_WIDE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_golden_wide.npz")
 COL_STRIDE = 7
 
 # name -> B, Cin, H, W, Cout, kernel, stride, pad, dil, dg, offset sigma (px) or "stress"
@@ -29,6 +32,19 @@ DCN_CASES = {
     "c6_s2":      dict(B=2, Cin=6, H=17, W=13, Cout=5, k=3, stride=2, pad=1, dil=1, dg=1, sig=2.0),
     "c6_d2":      dict(B=1, Cin=6, H=15, W=14, Cout=4, k=3, stride=1, pad=2, dil=2, dg=3, sig=2.0),
     "c7_k5":      dict(B=1, Cin=7, H=11, W=12, Cout=3, k=5, stride=1, pad=2, dil=1, dg=1, sig=1.0),
+}
+
+# The domain of the wide deformable form (csrc/cn_dcn4.hip: whole 8 x 16 tiles, Cin % 32 == 0,
+# Cout % 128 == 0), which no case above enters.  Same fields; outputs in ref_golden_wide.npz.
+DCN_WIDE_CASES = {
+    # two 32-channel chunks: one window swap of the four-block form (Cout = 128 -> NB = 4)
+    "w64_128":    dict(B=1, Cin=64, H=16, W=32, Cout=128, k=3, stride=1, pad=1, dil=1, dg=1, sig=2.0),
+    # three chunks: both swap directions; Cout = 256 -> NB = 8 by shape, NB = 4 when forced
+    "w96_256":    dict(B=1, Cin=96, H=8, W=16, Cout=256, k=3, stride=1, pad=1, dil=1, dg=1, sig=1.5),
+    # every sample on the far path or on a rule boundary
+    "w64_stress": dict(B=1, Cin=64, H=8, W=16, Cout=128, k=3, stride=1, pad=1, dil=1, dg=1, sig="stress"),
+    # eight chunks, Cin >= 256: the weight prefetch of the four-block form is on, K splits 2 and 4 reachable
+    "w256_128":   dict(B=1, Cin=256, H=8, W=16, Cout=128, k=3, stride=1, pad=1, dil=1, dg=1, sig=2.0),
 }
 
 NMS_CASES = {
@@ -80,6 +96,14 @@ def main():
                                os.path.join(ROOT, "tests", "test_oracle_ref.py")],
                               cwd=ROOT, env=dict(os.environ, CN_RECORD_REF_DIGESTS="1"))
         print("wrote", os.path.join(os.path.dirname(OUT), "ref_digests.json"))
+        return
+    if "--wide" in sys.argv[1:]:
+        out = {}
+        for name, c in DCN_WIDE_CASES.items():
+            x, off, mask, w, b, kw = dcn_inputs(c)
+            out["dcn_" + name + "_y"] = ref.dcn_v2_forward(x, off, mask, w, b, **kw)
+        np.savez_compressed(OUT_WIDE, **out)
+        print("wrote", OUT_WIDE, os.path.getsize(OUT_WIDE), "bytes")
         return
     out = {}
     for name, c in DCN_CASES.items():

@@ -1,6 +1,7 @@
 """Fused HIP DCNv2 (through the C ABI, NCHW drop-in entry and NHWC native entry) vs
   * the reference's own sampling kernel built test-only (oracle/_ref, when present) and the
-    committed fixtures made from it (tests/golden/ref_golden.npz), and
+    committed fixtures made from it (tests/golden/ref_golden.npz; ref_golden_wide.npz for the domain
+    of the wide form, Cout % 128 == 0), and
   * the C oracle, itself bit-identical to oracle/_ref (tests/test_oracle_ref.py).
 fp32 tolerance: |diff| <= 2e-5 * (1 + |ref|) (fp32 MFMA, different summation order than the
 checker's double accumulation)."""
@@ -66,19 +67,30 @@ def _gen_ref():
     return mod
 
 
+def _ref_fixtures():
+    """(name, case, output of the reference's kernel, in the wide form's table?) of every stored case:
+    DCN_CASES from ref_golden.npz, DCN_WIDE_CASES from ref_golden_wide.npz.  Inputs come from seeds."""
+    gen = _gen_ref()
+    z = np.load(os.path.join(GOLDEN, "ref_golden.npz"))
+    zw = np.load(os.path.join(GOLDEN, "ref_golden_wide.npz"))
+    out = [(name, cfg, z["dcn_" + name + "_y"], False) for name, cfg in gen.DCN_CASES.items()]
+    out += [(name, cfg, zw["dcn_" + name + "_y"], True) for name, cfg in gen.DCN_WIDE_CASES.items()]
+    assert len(gen.DCN_WIDE_CASES) >= 4
+    return gen, out
+
+
 def test_dcn_vs_reference_kernel_fixtures(dev):
     """Outputs of the REFERENCE's kernel (oracle/_ref at fixture-generation time) for tuned and
     general-domain configurations: deformable groups, stride 2, dilation 2, 5x5, Cin = 2 / 6 / 7,
-    stress offsets."""
+    stress offsets, and the four shapes of the wide form's domain."""
     from centernet_amd.dcn_v2 import dcn_v2_forward
-    gen = _gen_ref()
-    z = np.load(os.path.join(GOLDEN, "ref_golden.npz"))
-    for name, cfg in gen.DCN_CASES.items():
+    gen, cases = _ref_fixtures()
+    for name, cfg, want, _ in cases:
         x, off, mask, w, b, kw = gen.dcn_inputs(cfg)
         y = dcn_v2_forward(*[torch.from_numpy(a).to(dev) for a in (x, off, mask, w, b)],
                            stride=kw["stride"], padding=kw["pad"], dilation=kw["dil"],
                            deformable_groups=kw["dg"])
-        err = np.abs(y.cpu().numpy() - z["dcn_" + name + "_y"]) / (1 + np.abs(z["dcn_" + name + "_y"]))
+        err = np.abs(y.cpu().numpy() - want) / (1 + np.abs(want))
         assert err.max() < TOL, (name, err.max())
 
 
@@ -267,23 +279,22 @@ def _dcn_f32s_nhwc(dev, x, off, mask, w, b, tap_split, out_plain, form=1, msig=F
 
 @pytest.mark.parametrize("tap_split", [1, 3, 9])
 def test_f32s_nhwc_kernel_vs_reference_kernel_fixtures(dev, tap_split):
-    """The product kernel against outputs of the REFERENCE's own kernel (ref_golden.npz) for
-    every fixture in its domain (3x3 / stride 1 / pad 1 / one group, Cin % 4 == 0), stress
-    offsets included."""
-    gen = _gen_ref()
-    z = np.load(os.path.join(GOLDEN, "ref_golden.npz"))
-    ran = 0
-    for name, cfg in gen.DCN_CASES.items():
+    """The product kernel against outputs of the REFERENCE's own kernel (ref_golden.npz,
+    ref_golden_wide.npz) for every fixture in its domain (3x3 / stride 1 / pad 1 / one group,
+    Cin % 4 == 0), stress offsets included."""
+    gen, cases = _ref_fixtures()
+    ran = ran_wide = 0
+    for name, cfg, want, wide in cases:
         if (cfg["k"], cfg["stride"], cfg["pad"], cfg["dil"], cfg["dg"]) != (3, 1, 1, 1, 1) or cfg["Cin"] % 4:
             continue
         x, off, mask, w, b, _ = gen.dcn_inputs(cfg)
         for out_plain in (False, True):
             y = _dcn_f32s_nhwc(dev, x, off, mask, w, b, tap_split, out_plain)
-            want = z["dcn_" + name + "_y"]
             err = np.abs(y - want) / (1 + np.abs(want))
             assert err.max() < TOL, (name, tap_split, out_plain, err.max())
         ran += 1
-    assert ran >= 3
+        ran_wide += int(wide)
+    assert ran - ran_wide >= 3 and ran_wide == len(gen.DCN_WIDE_CASES)
 
 
 def test_f32s_nhwc_kernel_stress_offsets(dev):
@@ -306,11 +317,13 @@ def test_f32s_nhwc_kernel_stress_offsets(dev):
                                    (256, 32, 64)])
 def test_f32s_nhwc_kernel_at_benchmark_batch(dev, shape, form):
     """B = 32, the layer shapes of resdcn_18 and dla_34: the launch the benchmark
-    times -- form 0 = the library's DEFAULT choice for the shape (round 5: the team form of the
-    window kernel, csrc/cn_dcn3.hip, N mode where Cout is a multiple of 128 and the grid still fills
-    the chip, K-split on the 16^2 map), form 1 = the global-gather kernel, 4 / 5 = the team form
-    forced into T / N mode -- default tap split; images 0, 13 and 31 against the C oracle (the
-    operator is per image, dcn_v2_cuda.c:61)."""
+    times.  form 0 = the library's DEFAULT choice for the shape: the wide form (csrc/cn_dcn4.hip, a
+    workgroup owns every output channel of its 8 x 16 tile) where Cout is a multiple of 128 -- eight
+    blocks of 32 channels per workgroup at Cout % 256 == 0, else four, K-split on the 16^2 map -- and
+    the team form (csrc/cn_dcn3.hip) for the 64-channel layers; form 1 = the global-gather kernel,
+    4 / 5 = the team form forced into T / N mode, 6 = the wide form with its block count by shape,
+    7 = the wide form forced to four blocks (two workgroups per tile at Cout = 256); default tap
+    split; images 0, 13 and 31 against the C oracle (the operator is per image, dcn_v2_cuda.c:61)."""
     Cin, HW, Cout = shape
     B = 32
     if form >= 6 and Cout % 128:
@@ -339,22 +352,31 @@ def _window_takes(form, Cin, H, W, Cout):
 
 @pytest.mark.parametrize("form", WINDOW_FORMS)
 def test_f32s_window_kernel_vs_reference_kernel_fixtures(dev, form):
-    gen = _gen_ref()
-    z = np.load(os.path.join(GOLDEN, "ref_golden.npz"))
-    ran = 0
-    for name, cfg in gen.DCN_CASES.items():
+    """Every window form against outputs of the REFERENCE's own kernel.  DCN_WIDE_CASES are in every
+    form's domain and are the only fixtures in that of forms 6 / 7 (Cout % 128 == 0): two and three
+    chunks (one window swap, both swap directions), stress offsets, eight chunks with the weight
+    prefetch on.  Both output formats, and the instantiation the networks launch (mask logits in,
+    sigmoid inside)."""
+    gen, cases = _ref_fixtures()
+    ran = ran_wide = 0
+    for name, cfg, want, wide in cases:
         if (cfg["k"], cfg["stride"], cfg["pad"], cfg["dil"], cfg["dg"]) != (3, 1, 1, 1, 1):
             continue
         if not _window_takes(form, cfg["Cin"], cfg["H"], cfg["W"], cfg["Cout"]):
             continue
         x, off, mask, w, b, _ = gen.dcn_inputs(cfg)
-        for out_plain in (False, True):
-            y = _dcn_f32s_nhwc(dev, x, off, mask, w, b, 0, out_plain, form=form)
-            want = z["dcn_" + name + "_y"]
+        for out_plain, msig in ((False, False), (True, False), (False, True)):
+            y = _dcn_f32s_nhwc(dev, x, off, mask, w, b, 0, out_plain, form=form, msig=msig)
             err = np.abs(y - want) / (1 + np.abs(want))
-            assert err.max() < TOL, (name, out_plain, err.max())
+            assert err.max() < TOL, (name, out_plain, msig, err.max())
         ran += 1
-    assert ran >= (1 if form < 6 else 0)     # no reference fixture has Cout % 128 == 0 (the wide form's domain)
+        ran_wide += int(wide)
+    print("form %d: %d fixtures ran, %d of them from DCN_WIDE_CASES (%d)" % (form, ran, ran_wide, len(gen.DCN_WIDE_CASES)))
+    assert ran >= 1
+    if form >= 6:
+        assert ran == ran_wide == len(gen.DCN_WIDE_CASES)
+    else:
+        assert ran_wide == len(gen.DCN_WIDE_CASES)
 
 
 @pytest.mark.parametrize("form", WINDOW_FORMS)

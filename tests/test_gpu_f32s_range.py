@@ -254,10 +254,16 @@ def test_deformable_kernel_at_every_activation_scale(dev, scale, form):
         err32 = _rel(y32.to_float().permute(0, 3, 1, 2).cpu(), ref)
         wd = _words(pb)
         _report(test="dcn", shape=[B, C, H, W, Co], tap_split=split, form=form, scale=scale, f32s=err, fp32_mfma=err32)
-        # (the two shapes added for the wide form have 49 k outputs of a short K: the MAXIMUM of |error| / rms over them
-        # is a tail statistic that reaches 6.2e-6 at one of the five scales for one form while the mean stays at the
-        # fp32 kernel's -- every form within 0.1e-6 of the others on the same shape otherwise: allowance 6.5e-6)
-        bar = max(_bar(err32), 6.5e-6) if Co >= 256 else _bar(err32)
+        # The bar is _bar(err32): 1.5x the error of the fp32-MFMA leg on the same data.  ONE allowance remains, for
+        # the wide form (6) on the two shapes with Co >= 256, where the MAXIMUM of |error| / rms over 49 k outputs
+        # of a short K is a tail statistic.  Measured over the six scales (the sweep file _report writes), largest
+        # f32s error against the bar at that scale:
+        #   64 -> 256 @ 16x32:  form 0 8.83e-6, form 4 8.83e-6, form 6 9.22e-6, all below bars of 1.27e-5 .. 1.29e-5
+        #   96 -> 384 @  8x16:  form 0 3.76e-6 (bar 4.49e-6), form 4 4.32e-6 (bar 4.52e-6),
+        #                       form 6 6.17e-6 at scale 1e2 (bar 4.49e-6) -- the one excursion; its other five
+        #                       scales stay below their bars (3.70e-6 .. 4.55e-6 against 4.52e-6 .. 5.81e-6)
+        # while the mean error stays at the fp32 kernel's.  Forms 0 and 4 never exceed the bar and are held to it.
+        bar = max(_bar(err32), 6.5e-6) if (form == 6 and Co >= 256) else _bar(err32)
         assert err <= bar, (err, err32, split)
         # blended samples never exceed the input maximum (convex combination x mask <= 1)
         assert 0 < wd["t1"][1] <= float(x.float().abs().max()) * 2.0 ** -exps["x"] * (1 + 1e-6)

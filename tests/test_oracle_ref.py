@@ -219,6 +219,25 @@ def test_ref_fixtures_pin_the_dcn_oracle():
         assert np.array_equal(_bits(cols.reshape(-1)[::gen.COL_STRIDE]), _bits(z["dcn_" + name + "_cols"])), name
 
 
+def test_ref_fixtures_pin_the_dcn_oracle_in_the_wide_domain():
+    """The shapes of the wide deformable form (DCN_WIDE_CASES -> ref_golden_wide.npz: Cout % 128 == 0,
+    whole 8 x 16 tiles): the C oracle against the reference kernel's stored output, against its recorded
+    digest and, where oracle/_ref is built, against its live output -- bit for bit."""
+    z = np.load(os.path.join(GOLDEN, "ref_golden_wide.npz"))
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_golden_ref", os.path.join(GOLDEN, "gen_golden_ref.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    assert len(gen.DCN_WIDE_CASES) >= 4 and sorted(z.files) == sorted("dcn_%s_y" % n for n in gen.DCN_WIDE_CASES)
+    for name, cfg in gen.DCN_WIDE_CASES.items():
+        assert cfg["Cout"] % 128 == 0 and cfg["Cin"] % 32 == 0 and cfg["H"] % 8 == 0 and cfg["W"] % 16 == 0, name
+        x, off, mask, w, b, kw = gen.dcn_inputs(cfg)
+        y = cref.dcn_v2_forward(x, off, mask, w, b, **kw)
+        assert np.array_equal(_bits(y), _bits(z["dcn_" + name + "_y"])), name
+        _same_as_reference("forward_wide_" + name, y,
+                           lambda: (None, ref.dcn_v2_forward(x, off, mask, w, b, **kw)))
+
+
 def test_ref_fixtures_pin_soft_nms():
     from centernet_amd.soft_nms import soft_nms, soft_nms_39
     z = np.load(os.path.join(GOLDEN, "ref_golden.npz"))

@@ -16,6 +16,10 @@ read be outstanding").  For every s_barrier it prints the ds_reads that may be o
 destination registers are first used, and what the next LDS writers behind the barrier are (ds_write,
 global_load_lds) -- the reader decides whether the barrier frees that read's source.
 
+`flagged(path)` returns the same as data -- per kernel and flagged barrier the reads in flight (opcode,
+immediate offset) and the kinds of LDS writers a wave can issue before it meets the next barrier, along every
+path of the control-flow graph -- for the expectations table of `tests/test_isa_audit.py`.
+
 Exit status 0 always: it is a review aid, `tests/test_isa_audit.py` holds the committed expectations.
 """
 import re
@@ -54,8 +58,8 @@ def split_kernels(lines):
             name = None
 
 
-def analyse(lines, first, last):
-    # basic blocks
+def build_cfg(lines, first, last):
+    """basic blocks [(first line, end line)] of one function body and their successors {block: [blocks]}"""
     heads = {first}
     label_at = {}
     for i in range(first, last):
@@ -91,6 +95,11 @@ def analyse(lines, first, last):
                 fall = False
         if fall and k + 1 < len(blocks):
             succ[k].append(k + 1)
+    return blocks, succ
+
+
+def analyse(lines, first, last):
+    blocks, succ = build_cfg(lines, first, last)
 
     def step(queue, i, reports):
         l = lines[i]
@@ -122,7 +131,10 @@ def analyse(lines, first, last):
             return queue
         m = LGKM_RE.match(l)
         if m:
-            queue = queue + ((i, m.group(1), l.strip()),)
+            # an instruction met again round a loop replaces its older entry: the queue stays bounded by the
+            # kernel's instructions (a loop that never waits for its reads would grow it without end), and a
+            # counted wait behind it keeps no fewer entries than the hardware does
+            queue = tuple(q for q in queue if q[0] != i) + ((i, m.group(1), l.strip()),)
             if len(queue) > CAP:
                 # the counter saturates at CAP entries in the model: drop the oldest NON-read entries first, an
                 # outstanding ds_read is never forgotten (it stays flagged until a wait retires it)
@@ -183,6 +195,76 @@ def next_lds_writers(lines, start, last, n=3):
                 break
         if s.startswith("s_barrier") and i > start:
             break
+    return out
+
+
+OFFSET_RE = re.compile(r"\boffset:(\d+)")
+
+
+def writer_kind(text):
+    """'ds_write' / 'dma' (global_load_lds, buffer_load ... lds) for an instruction that writes LDS, else None"""
+    s = text.strip()
+    if s.startswith(("ds_write", "ds_store")):
+        return "ds_write"
+    if "global_load_lds" in s or (s.startswith("buffer_load") and " lds" in s):
+        return "dma"
+    return None
+
+
+def writers_until_next_barrier(lines, blocks, succ, barrier):
+    """Every LDS writer a wave can issue between the s_barrier at line index `barrier` and the NEXT barrier
+    it meets, along every path of the control-flow graph (a loop iteration that branches round its barrier
+    is followed into the next one): sorted [(line index, kind)]."""
+    blk = next(k for k, (a, b) in enumerate(blocks) if a <= barrier < b)
+    found, seen = {}, set()
+    work = [(blk, barrier + 1)]
+    while work:
+        k, start = work.pop()
+        stopped = False
+        for i in range(start, blocks[k][1]):
+            if lines[i].strip().startswith("s_barrier"):
+                stopped = True
+                break
+            kind = writer_kind(lines[i])
+            if kind:
+                found[i] = kind
+        if stopped:
+            continue
+        for n in succ[k]:
+            if n not in seen:
+                seen.add(n)
+                work.append((n, blocks[n][0]))
+    return sorted(found.items())
+
+
+def flagged(path):
+    """What a reviewer needs to judge every flagged barrier, as data:
+    {mangled kernel name: [report, ...]} in listing order (kernels without a flagged barrier: []), with
+      report["line"]     1-based listing line of the s_barrier
+      report["reads"]    [(opcode, immediate offset)] of the ds_reads possibly in flight there, issue order
+      report["back_edge"] True when every one of them is issued BEHIND the barrier in the listing: it is
+                         carried round a loop back-edge
+      report["writers"]  sorted kinds ('dma', 'ds_write') of the LDS writers between this barrier and the next
+                         one on any path
+      report["text"]     the listing lines behind all of that, for a failure message"""
+    lines = open(path).read().splitlines()
+    out = {}
+    for name, a, b in split_kernels(lines):
+        if not any(lines[i].strip().startswith("s_barrier") for i in range(a, b)):
+            continue
+        blocks, succ = build_cfg(lines, a, b)
+        rep = analyse(lines, a, b)
+        out[name] = []
+        for i in sorted(rep):
+            reads = []
+            text = ["%6d  %s" % (i + 1, lines[i].strip())]
+            for (j, op, t) in rep[i]:
+                m = OFFSET_RE.search(t.split(";")[0])
+                reads.append((op, int(m.group(1)) if m else 0))
+                text.append("%6d  %s%s" % (j + 1, t, "   <- behind a back-edge" if j > i else ""))
+            w = writers_until_next_barrier(lines, blocks, succ, i)
+            text += ["%6d  %s" % (x + 1, lines[x].strip()) for x, _ in w]
+            out[name].append(dict(line=i + 1, reads=reads, back_edge=all(j > i for j, _, _ in rep[i]), writers=sorted(set(k for _, k in w)), text=text))
     return out
 
 
