@@ -1,7 +1,8 @@
 // cn_merge.hip -- the ctdet scale merge on the device (CtdetDetector.merge_outputs, detectors/ctdet.py:54-74;
 // reference ctdet.py:58-73), bit for bit.  Input: the device tail's output of every test scale
 // (cn_ctdet_post_process_f32 into slice s of rows (S, B, K, 5) / bounds (S, B, nc + 1)).  Output in the
-// tail's own format, so the host slices it as it slices a single scale.
+// tail's own format, so the host slices it as it slices a single scale.  Behind it the multi_pose scale
+// merge (multi_pose_merge_kernel): the same soft-NMS routine on 39-column rows, one segment per image.
 //
 // One workgroup of four waves per image; the image's rows (<= CN_MERGE_MAX_ROWS) live in LDS.
 //   1. per class, the rows of all scales in scale order (the np.concatenate of merge_outputs);
@@ -32,14 +33,22 @@ constexpr int MG_ROWS = CN_MERGE_MAX_ROWS;
 constexpr int MG_CLASSES = CN_MERGE_MAX_CLASSES;
 constexpr float MG_SIGMA = 0.5f, MG_THRESHOLD = 0.001f;
 
-struct MergeLds {
+struct NmsLds {
     float box[4][MG_ROWS];   // x1, y1, x2, y2 of the merged rows (class segments back to back)
     float sc[MG_ROWS];       // score
     float ns[MG_ROWS];       // soft-NMS: decayed score of the row that started the step at p; select: prefix
     int16_t orig[MG_ROWS];   // soft-NMS: start-of-step position of the row now at p
     uint8_t disc[MG_ROWS];   // soft-NMS: the row that started the step at p is discarded
+};
+struct MergeLds : NmsLds {
     int seg[MG_CLASSES + 1]; // class c = [seg[c], seg[c + 1])
     int red[MG_WAVES];
+};
+// multi_pose rows carry 34 joint columns behind the score.  They never enter LDS (2048 x 34 floats would
+// not fit): jsrc[p] names the input row whose joints sit at position p, and the joints are gathered from
+// the global input once, at the end.
+struct PoseLds : NmsLds {
+    int16_t jsrc[MG_ROWS];
 };
 
 // LDS written by one lane is read by the others of the same wave next: order the wave's own accesses
@@ -77,8 +86,12 @@ __device__ __forceinline__ float key_value(uint32_t k)
 // bits), so the result is the IEEE quotient the host computes whatever the device division flags are
 __device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
 
-// Soft-NMS of one class segment [o, o + n) by one wave (see the head of the file).
-__device__ void soft_nms_segment(MergeLds &L, int o, int n, int lane)
+// Soft-NMS of one class segment [o, o + n) by one wave (see the head of the file).  JOINTS: the rows have
+// columns behind the score (nms.pyx:260-268, cn_soft_nms_f32): the argmax swap exchanges whole rows, a
+// discarded row takes columns 0..4 of row N - 1 and EXCHANGES columns 5.. with it -- both are exchanges of
+// jsrc[], `jsrc` being the segment's slice of PoseLds::jsrc (unused without JOINTS).
+template <bool JOINTS>
+__device__ void soft_nms_segment(NmsLds &L, int o, int n, int lane, int16_t *jsrc)
 {
 #pragma clang fp contract(off)
     float *x1 = L.box[0] + o, *y1 = L.box[1] + o, *x2 = L.box[2] + o, *y2 = L.box[3] + o;
@@ -109,6 +122,9 @@ __device__ void soft_nms_segment(MergeLds &L, int o, int n, int lane)
             t = x2[i]; x2[i] = x2[bpos]; x2[bpos] = t;
             t = y2[i]; y2[i] = y2[bpos]; y2[bpos] = t;
             t = sc[i]; sc[i] = sc[bpos]; sc[bpos] = t;
+            if (JOINTS) {
+                const int16_t j = jsrc[i]; jsrc[i] = jsrc[bpos]; jsrc[bpos] = j;
+            }
         }
         wave_sync();
         const float tx1 = x1[i], ty1 = y1[i], tx2 = x2[i], ty2 = y2[i];
@@ -160,6 +176,9 @@ __device__ void soft_nms_segment(MergeLds &L, int o, int n, int lane)
                 if (lane == 0) {
                     x1[p] = x1[last]; y1[p] = y1[last]; x2[p] = x2[last]; y2[p] = y2[last]; sc[p] = sc[last];
                     orig[p] = (int16_t)last;
+                    if (JOINTS) {
+                        const int16_t j = jsrc[p]; jsrc[p] = jsrc[last]; jsrc[last] = j;
+                    }
                 }
                 N = last;
                 if (!disc[last]) break;
@@ -217,7 +236,7 @@ __global__ __launch_bounds__(MG_THREADS) void ctdet_merge_kernel(const float *__
     if (do_nms) {
         for (int c = w; c < nc; c += MG_WAVES) {
             const int o = L.seg[c], e = min(L.seg[c + 1], total);
-            if (e - o > 1) soft_nms_segment(L, o, e - o, lane);
+            if (e - o > 1) soft_nms_segment<false>(L, o, e - o, lane, nullptr);
         }
         __syncthreads();
     }
@@ -270,7 +289,61 @@ __global__ __launch_bounds__(MG_THREADS) void ctdet_merge_kernel(const float *__
         out_bounds[(size_t)b * bstride + c] = sg < total ? prefix[sg] : kept;
     }
 }
+
+// MultiPoseDetector.merge_outputs (detectors/multi_pose.py:135-142; reference multi_pose.py:74-81) on the
+// device: one workgroup per image, the image's S * K rows in scale order (row s * K + k: the np.concatenate),
+// one segment (the person class is the only one), soft-NMS by the first wave, no cut.  The whole in-place
+// array is written: rows past the kept count hold the box and score they last held and the joints that the
+// exchanges left there.
+constexpr int MG_POSE_ROW = 39;
+__global__ __launch_bounds__(MG_THREADS) void multi_pose_merge_kernel(const float *__restrict__ rows, int S, int B,
+                                                                      int K, int do_nms,
+                                                                      float *__restrict__ out_rows)
+{
+    __shared__ PoseLds L;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & (CN_WAVE - 1), w = t / CN_WAVE;
+    const int total = S * K;
+    for (int e = t; e < total; e += MG_THREADS) {
+        const int s = e / K, r = e - s * K;
+        const float *src = rows + (((size_t)s * B + b) * K + r) * MG_POSE_ROW;
+        L.box[0][e] = src[0];
+        L.box[1][e] = src[1];
+        L.box[2][e] = src[2];
+        L.box[3][e] = src[3];
+        L.sc[e] = src[4];
+        L.jsrc[e] = (int16_t)e;
+    }
+    __syncthreads();
+    if (do_nms && w == 0 && total > 1) soft_nms_segment<true>(L, 0, total, lane, L.jsrc);
+    __syncthreads();
+    float *ob = out_rows + (size_t)b * total * MG_POSE_ROW;
+    for (int e = t; e < total * MG_POSE_ROW; e += MG_THREADS) {
+        const int r = e / MG_POSE_ROW, c = e - r * MG_POSE_ROW;
+        float v;
+        if (c < 4) {
+            v = L.box[c][r];
+        } else if (c == 4) {
+            v = L.sc[r];
+        } else {
+            const int j = L.jsrc[r], s = j / K;
+            v = rows[(((size_t)s * B + b) * K + (j - s * K)) * MG_POSE_ROW + c];
+        }
+        ob[e] = v;
+    }
+}
 }  // namespace
+
+extern "C" int cn_multi_pose_merge_f32(const float *rows, int S, int B, int K, int apply_nms, float *out_rows,
+                                       void *stream)
+{
+    if (!rows || !out_rows) return CN_ERR_NULL;
+    if (S <= 0 || B <= 0 || K <= 0) return CN_ERR_SHAPE;
+    if ((long long)S * K > CN_MERGE_MAX_ROWS) return CN_ERR_SHAPE;
+    hipLaunchKernelGGL(multi_pose_merge_kernel, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, rows, S, B, K,
+                       (S > 1 || apply_nms) ? 1 : 0, out_rows);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
 
 extern "C" int cn_ctdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int K, int num_classes,
                                   int apply_nms, int max_per_image, float *out_rows, int32_t *out_bounds,

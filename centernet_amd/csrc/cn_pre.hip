@@ -416,3 +416,52 @@ extern "C" int cn_ctdet_post_process_f32(const float *dets, int B, int K, int nu
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
+
+// ---------------------------------------------------------------------------
+// multi_pose_post_process on the device (utils/post_process.py:103-114, detectors/multi_pose.py:62-72):
+// the K raw rows [x1, y1, x2, y2, score, 17 x (x, y), class] of every image in output-grid units become
+// rows [x1, y1, x2, y2, score, 17 x (x, y)] in source-frame pixels / scale.  The two box corners and the
+// 17 joints are 19 points under one inverse map, with the arithmetic of ctdet_post_kernel; the score is
+// copied, the class dropped, the row order kept (one class: nothing to group).  One item per point or
+// score, so the 39 columns of a row are written by neighbouring lanes.
+// ---------------------------------------------------------------------------
+namespace {
+constexpr int MP_THREADS = 256;
+constexpr int MP_IN = 40, MP_OUT = 39, MP_ITEMS = 20;   // 19 points + the score per row
+__global__ __launch_bounds__(MP_THREADS) void multi_pose_post_kernel(const float *__restrict__ dets, int K,
+                                                                     const double *__restrict__ to_source,
+                                                                     int per_image, float scale,
+                                                                     float *__restrict__ rows)
+{
+    const int b = blockIdx.x;
+    const double *t = to_source + (per_image ? (size_t)b * 6 : 0);
+    const double t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4], t5 = t[5];
+    for (int e = threadIdx.x; e < K * MP_ITEMS; e += MP_THREADS) {
+        const int k = e / MP_ITEMS, j = e - k * MP_ITEMS;
+        const float *d = dets + ((size_t)b * K + k) * MP_IN;
+        float *o = rows + ((size_t)b * K + k) * MP_OUT;
+        if (j == MP_ITEMS - 1) {
+            o[4] = d[4];
+            continue;
+        }
+        const int c = j < 2 ? 2 * j : 2 * j + 1;     // corners in columns 0..3, joints from column 5
+        const double x = (double)d[c], y = (double)d[c + 1];
+        const double sx = (x * t0 + y * t1) + t2;
+        const double sy = (x * t3 + y * t4) + t5;
+        o[c] = (float)sx / scale;
+        o[c + 1] = (float)sy / scale;
+    }
+}
+}  // namespace
+
+extern "C" int cn_multi_pose_post_process_f32(const float *dets, int B, int K, const double *to_source_2x3,
+                                              int per_image, float scale, float *rows, void *stream)
+{
+    if (!dets || !to_source_2x3 || !rows) return CN_ERR_NULL;
+    if (B <= 0 || K <= 0 || !(scale > 0.f)) return CN_ERR_SHAPE;
+    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(multi_pose_post_kernel, dim3(B), dim3(MP_THREADS), 0, (hipStream_t)stream, dets, K,
+                       to_source_2x3, per_image ? 1 : 0, scale, rows);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}

@@ -56,12 +56,15 @@ class _FramePipe(object):
     Per batch: the frames are copied into the pinned buffer by the staging threads (numpy releases
     the GIL), go to the device as ONE asynchronous uint8 copy on the copy stream, and everything
     else -- per test scale the batched device pre-process, network + flip average + decode
-    (``_run_scale``) and the device tail (``cn_ctdet_post_process_f32``: inverse affine + class
-    grouping, into the scale's slice), then the scale merge (``cn_ctdet_merge_f32``: soft-NMS and
-    the top-100 cut, when there are several scales or --nms) and the copies of the rows / class
-    bounds / f32s range digests into pinned memory -- is enqueued on the launch stream without a
-    single host synchronisation.  The host waits for batch i - depth + 1 only when it collects it,
-    i.e. while later batches are on the device."""
+    (``_run_scale``) and the task's device tail (ctdet: ``cn_ctdet_post_process_f32``, inverse
+    affine + class grouping; multi_pose: ``cn_multi_pose_post_process_f32``, inverse affine of the
+    box corners and joints; into the scale's slice), then the scale merge (``cn_ctdet_merge_f32``:
+    soft-NMS and the top-100 cut; ``cn_multi_pose_merge_f32``: soft-NMS of the 39-column rows, no
+    cut; when there are several scales or --nms) and the copies of the rows / class bounds / f32s
+    range digests into pinned memory -- is enqueued on the launch stream without a single host
+    synchronisation.  The host waits for batch i - depth + 1 only when it collects it, i.e. while
+    later batches are on the device.  Tasks without the ``_device_tail_*`` hooks (ddd, exdet), and
+    shapes their kernels do not take, copy the raw detections out and keep the host tail."""
 
     def __init__(self, det, B, H, W, scales, flip, depth):
         import concurrent.futures
@@ -156,10 +159,12 @@ class _FramePipe(object):
             det._device_tail_finish(self, slot)
         self.ev_done[slot].record()
 
-    def collect(self, i, frames):
-        """Results of batch i (waits for it; later batches keep the device busy)."""
+    def collect(self, i, frames, arrays=False):
+        """Results of batch i (waits for it; later batches keep the device busy).  ``arrays``: see
+        ``run_frames``."""
         from ..engine import F16_MAX_BITS
         det = self.det
+        kw = det._arrays_kw(arrays)
         slot = i % self.depth
         self.ev_done[slot].synchronize()
         det.__dict__["_unchecked"] = 0       # (the batch's range digests are looked at right here)
@@ -169,14 +174,14 @@ class _FramePipe(object):
             # device, let the module re-calibrate, and run this batch again synchronously.
             torch.cuda.synchronize()
             det.range_ok(None)
-            return det._run_frames_sync(frames, self.scales)
+            return det._run_frames_sync(frames, self.scales, **kw)
         n = len(frames)
         if self.tail is not None:
-            return det._device_tail_results(self, slot, n)
+            return det._device_tail_results(self, slot, n, **kw)
         if not self.merge:
-            return det.results_batch(self.dets_host[slot][0].numpy()[:n], [self.meta] * n, self.scale)
+            return det.results_batch(self.dets_host[slot][0].numpy()[:n], [self.meta] * n, self.scale, **kw)
         return det._results_merged([(d.numpy()[:n], [lv.meta] * n, lv.scale)
-                                    for d, lv in zip(self.dets_host[slot], self.levels)])
+                                    for d, lv in zip(self.dets_host[slot], self.levels)], **kw)
 
 
 class BaseDetector(object):
@@ -321,8 +326,14 @@ class BaseDetector(object):
         frames' metas -> what ``run(frame)['results']`` returns, per image."""
         raise NotImplementedError
 
-    # device tail of the frame pipeline: task classes that have one set the three hooks
+    # device tail of the frame pipeline: task classes that have one set the four hooks
     _device_tail_alloc = None
+    # the task's result rows are nested lists, and its tail hooks (results_batch, merge_outputs,
+    # _device_tail_results) take ``arrays=True`` to return them as float32 arrays instead
+    _list_results = False
+
+    def _arrays_kw(self, arrays):
+        return {"arrays": True} if arrays and self._list_results else {}
 
     def _run_scale(self, images, flip):
         """Task hook of the frame pipeline: network + (with ``flip``: the batched flip average of the
@@ -330,18 +341,18 @@ class BaseDetector(object):
         output-grid units, asynchronously (as ``run_batch``)."""
         raise NotImplementedError
 
-    def _results_merged(self, per_scale):
+    def _results_merged(self, per_scale, **kw):
         """Host tail of a merging frame pipeline: ``per_scale`` = [(host raw detections (n, K, .),
         metas, scale)] in test-scale order -> per image ``merge_outputs([post_process(...) per
-        scale])``, what ``run(frame)['results']`` returns."""
+        scale])``, what ``run(frame)['results']`` returns (``kw``: ``_arrays_kw``)."""
         posts = [self._post_batch(d, metas, scale) for d, metas, scale in per_scale]
-        return [self.merge_outputs([p[i] for p in posts]) for i in range(len(posts[0]))]
+        return [self.merge_outputs([p[i] for p in posts], **kw) for i in range(len(posts[0]))]
 
     def _post_batch(self, dets, metas, scale):
         """``post_process`` of every image of a host batch of raw detections (task specific)."""
         raise NotImplementedError
 
-    def _run_frames_sync(self, frames, scales):
+    def _run_frames_sync(self, frames, scales, **kw):
         """One batch, synchronously, frame by frame through ``pre_process_device`` at every test scale
         (the comparison path of the pipeline, and its re-run path after an f32s re-calibration)."""
         uploaded = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.opt.device)
@@ -361,8 +372,8 @@ class BaseDetector(object):
                     raise native.NativeError("f32s forward clamps values after re-calibration")
             per_scale.append((dets, metas, scale))
         if len(per_scale) == 1 and not getattr(self.opt, "nms", False):
-            return self.results_batch(*per_scale[0])
-        return self._results_merged(per_scale)
+            return self.results_batch(*per_scale[0], **kw)
+        return self._results_merged(per_scale, **kw)
 
     def _pipe_for(self, frames, depth):
         shapes = {tuple(f.shape) for f in frames}
@@ -380,23 +391,28 @@ class BaseDetector(object):
             pipes[key] = _FramePipe(self, len(frames), H, W, self.scales, flip, depth)
         return pipes[key]
 
-    def run_frames(self, frames):
+    def run_frames(self, frames, arrays=False):
         """A list of (H, W, 3) uint8 BGR frames of one size -> list of per-image results, what
         ``run(frame)['results']`` returns for each (every test scale, flip-test and --nms as set).
         The reference's test loop is batch_size = 1 (test.py:60-62); here the frames are uploaded as
         ONE uint8 copy, pre-processed on the device in one launch per test scale straight into one
         batch tensor (with flip-test: frame, mirror, frame, mirror, ...), each scale's batch goes
-        through the network + flip average + decode once and, for ctdet, through the device tail
-        (inverse affine + class grouping) and the device scale merge; the host slices the result."""
+        through the network + flip average + decode once and, for ctdet and multi_pose, through the
+        device tail (inverse affine; ctdet: + class grouping) and the device scale merge; the host
+        slices the result.
+        ``arrays=True``: a task whose rows are nested lists (multi_pose: ``{1: [[39 floats], ...]}``)
+        returns them as a float32 array (``{1: (n, 39) ndarray}``, the same bits, a copy of its own)
+        and saves the ``.tolist()``.  ctdet returns arrays either way."""
         pipe = self._pipe_for(frames, 1)
         pipe.submit(0, frames)
-        return pipe.collect(0, frames)
+        return pipe.collect(0, frames, arrays)
 
-    def run_frames_stream(self, batches, depth=3):
+    def run_frames_stream(self, batches, depth=3, arrays=False):
         """``run_frames`` over an iterable of batches (lists of frames, all batches of one size and
         frame geometry), pipelined: while batch i is on the device the host stages batch i + 1
         (pinned uint8 copy by a few threads, asynchronous upload on a copy stream) and builds the
-        result dictionaries of batch i - 1.  Yields the per-image results batch by batch, in order."""
+        result dictionaries of batch i - 1.  Yields the per-image results batch by batch, in order.
+        ``arrays``: as ``run_frames``."""
         pipe, pending = None, collections.deque()
         n = 0
         for frames in batches:
@@ -406,13 +422,13 @@ class BaseDetector(object):
                 raise ValueError("run_frames_stream needs batches of one size and frame geometry")
             if len(pending) == depth:
                 j, fr = pending.popleft()
-                yield pipe.collect(j, fr)
+                yield pipe.collect(j, fr, arrays)
             pipe.submit(n, frames)
             pending.append((n, frames))
             n += 1
         while pending:
             j, fr = pending.popleft()
-            yield pipe.collect(j, fr)
+            yield pipe.collect(j, fr, arrays)
 
     UNCHECKED_LIMIT = 4096     # run_batch forwards without a look at the range words before a warning
 

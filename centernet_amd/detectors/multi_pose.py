@@ -19,6 +19,8 @@ class MultiPoseDetector(BaseDetector):
         super(MultiPoseDetector, self).__init__(opt)
         self.flip_idx = opt.flip_idx
 
+    _list_results = True
+
     def _head_maps(self, out):
         """Post-sigmoid centre map and the optional branches, as the decode expects them."""
         hm = out['hm'].sigmoid_()
@@ -113,11 +115,67 @@ class MultiPoseDetector(BaseDetector):
             out.append({1: rows})
         return out
 
-    def results_batch(self, dets, metas, scale):
+    def results_batch(self, dets, metas, scale, arrays=False):
         """Host tail of ``run_frames``: (B, K, 40) host array -> per image ``{1: [[x1, y1, x2,
         y2, score, 17 x (x, y)], ...]}``, i.e. merge_outputs([post_process(...)]) for one scale
-        without NMS (multi_pose.py:62-81)."""
-        return [{1: d[1].tolist()} for d in self._post_batch(dets, metas, scale)]
+        without NMS (multi_pose.py:62-81).  ``arrays``: the same rows as a (K, 39) float32 array."""
+        return [{1: d[1] if arrays else d[1].tolist()} for d in self._post_batch(dets, metas, scale)]
+
+    # ---- device tail of the frame pipeline (base_detector._FramePipe)
+    def _device_tail_alloc(self, pipe):
+        """Buffers of cn_multi_pose_post_process_f32 (one slice per test scale) and of
+        cn_multi_pose_merge_f32 for one pipe, or None when the host tail has to serve it (more
+        detections than the kernels take)."""
+        from .. import native
+        from ..image import get_affine_transform
+        K, B, dev, S = self.opt.K, pipe.B, self.opt.device, len(pipe.scales)
+        if K > 128 or (pipe.merge and S * K > native.MERGE_MAX_ROWS):
+            return None
+        to_source = []
+        for lv in pipe.levels:
+            m = lv.meta
+            t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+            to_source.append(torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev))
+        R = S * K if pipe.merge else K
+        t = {'to_source': to_source,
+             'rows': torch.empty((S, B, K, ROW), device=dev, dtype=torch.float32),
+             'rows_host': [torch.empty((B, R, ROW), dtype=torch.float32).pin_memory() for _ in range(pipe.depth)]}
+        if pipe.merge:
+            t['merged_rows'] = torch.empty((B, R, ROW), device=dev, dtype=torch.float32)
+        return t
+
+    def _device_tail_run(self, pipe, slot, level, dets):
+        """Test scale ``level``: raw detections -> source pixels / scale, into slice ``level`` of the
+        tail's rows."""
+        from .. import native
+        t = pipe.tail
+        dets = dets.contiguous()
+        native.check(native.lib().cn_multi_pose_post_process_f32(
+            native.ptr(dets), pipe.B, self.opt.K, native.ptr(t['to_source'][level]), 0,
+            float(pipe.levels[level].scale), native.ptr(t['rows'][level]), native.stream_ptr()),
+            "cn_multi_pose_post_process_f32")
+
+    def _device_tail_finish(self, pipe, slot):
+        """After the last test scale: the scale merge (merge_outputs on the device) when there is one
+        to do, then the copy into the slot's pinned buffer."""
+        from .. import native
+        t = pipe.tail
+        rows = t['rows'][0]
+        if pipe.merge:
+            rows = t['merged_rows']
+            native.check(native.lib().cn_multi_pose_merge_f32(
+                native.ptr(t['rows']), len(pipe.scales), pipe.B, self.opt.K, int(bool(self.opt.nms)),
+                native.ptr(rows), native.stream_ptr()), "cn_multi_pose_merge_f32")
+        t['rows_host'][slot].copy_(rows, non_blocking=True)
+
+    def _device_tail_results(self, pipe, slot, n, arrays=False):
+        """Per image ``{1: rows}``: the rows are final; the host copies them out of the pinned buffer
+        (a later batch reuses it) as nested lists, or with ``arrays`` as one (S * K, 39) array each."""
+        rows = pipe.tail['rows_host'][slot].numpy()[:n]
+        if arrays:
+            rows = rows.copy()
+            return [{1: rows[i]} for i in range(n)]
+        return [{1: r} for r in rows.tolist()]
 
     def post_process(self, dets, meta, scale=1):
         """Output-grid units -> image coordinates of the unscaled frame (multi_pose.py:62-72)."""
@@ -132,11 +190,12 @@ class MultiPoseDetector(BaseDetector):
             per_class[cls] = rows
         return per_class
 
-    def merge_outputs(self, detections):
+    def merge_outputs(self, detections, arrays=False):
         """Concatenate the test scales; soft-NMS when asked or when there are several
-        (multi_pose.py:74-81).  The person class is the only one."""
+        (multi_pose.py:74-81).  The person class is the only one.  ``arrays`` (the frame pipeline's
+        opt-in): the (n, 39) float32 array instead of its list form."""
         people = np.concatenate([d[1] for d in detections], axis=0).astype(np.float32)
         if self.opt.nms or len(self.opt.test_scales) > 1:
             from ..soft_nms import soft_nms_39
             soft_nms_39(people, Nt=0.5, method=2)
-        return {1: people.tolist()}
+        return {1: people if arrays else people.tolist()}

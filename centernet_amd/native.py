@@ -25,7 +25,7 @@ DTYPE_F16 = 1
 DTYPE_F32S = 2        # fp32 values as fp16 (high, low) pairs: three fp16 MFMAs per product
 CONV_X_PLAIN, CONV_Y_PLAIN, CONV_R_PLAIN, CONV_STEM_F32S, CONV_STEM_MAXPOOL = 1, 2, 4, 8, 16
 CONV_STEM_Y_F32S = 32
-MERGE_MAX_ROWS = 2048       # CN_MERGE_MAX_ROWS: S * K rows per image that cn_ctdet_merge_f32 takes
+MERGE_MAX_ROWS = 2048       # CN_MERGE_MAX_ROWS: S * K rows per image that the merge kernels take
 MERGE_MAX_CLASSES = 1024    # CN_MERGE_MAX_CLASSES
 
 _lib = None
@@ -185,6 +185,10 @@ def _declare(lib):
     lib.cn_ctdet_post_process_f32.argtypes = [vp, i, i, i, vp, i, ctypes.c_float, vp, vp, vp]
     lib.cn_ctdet_merge_f32.restype = i
     lib.cn_ctdet_merge_f32.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp]
+    lib.cn_multi_pose_post_process_f32.restype = i
+    lib.cn_multi_pose_post_process_f32.argtypes = [vp, i, i, vp, i, ctypes.c_float, vp, vp]
+    lib.cn_multi_pose_merge_f32.restype = i
+    lib.cn_multi_pose_merge_f32.argtypes = [vp, i, i, i, i, vp, vp]
     lib.cn_resize_bilinear_u8.restype = i
     lib.cn_resize_bilinear_u8.argtypes = [vp, i, i, i, i, i, vp, vp]
     lib.cn_warp_affine_u8_host.restype = i

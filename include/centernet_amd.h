@@ -559,6 +559,24 @@ int cn_ctdet_post_process_f32(const float *dets, int B, int K, int num_classes, 
 #define CN_MERGE_MAX_CLASSES 1024
 int cn_ctdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int K, int num_classes,
                        int apply_nms, int max_per_image, float *out_rows, int32_t *out_bounds, void *stream);
+/* multi_pose_post_process + the "/ scale" of MultiPoseDetector.post_process (utils/post_process.py:103-114,
+ * detectors/multi_pose.py:62-72) on the device.  dets (B, K, 40): multi_pose_decode rows [x1, y1, x2, y2,
+ * score, 17 x (x, y), class] in output-grid units (K <= 128, CN_ERR_UNSUPPORTED above); to_source_2x3,
+ * per_image and scale (> 0) as for cn_ctdet_post_process_f32.  rows (B, K, 39): the two box corners and the
+ * 17 joints through the inverse map (float32 point -> float64 (t0*x + t1*y) + t2 -> float32, then / scale in
+ * float32), the score copied, the class dropped, the row order kept.  Bit-identical to the host tail. */
+int cn_multi_pose_post_process_f32(const float *dets, int B, int K, const double *to_source_2x3, int per_image,
+                                   float scale, float *rows, void *stream);
+/* The multi_pose scale merge (MultiPoseDetector.merge_outputs, detectors/multi_pose.py:74-81) on the device,
+ * bit for bit.  rows (S, B, K, 39): cn_multi_pose_post_process_f32's output of test scale s in slice s.
+ * out_rows (B, S*K, 39): per image the rows of all scales in scale order (row s*K + k); when S > 1 or
+ * apply_nms, after Gaussian soft-NMS (sigma 0.5, threshold 0.001) with the arithmetic and the row moves of
+ * cn_soft_nms_f32 at stride 39 -- the argmax swap exchanges whole rows, a discarded row takes columns 0..4 of
+ * the last live row and exchanges columns 5.. with it.  The WHOLE in-place array is returned, rows past the
+ * kept count included, and there is no top-100 cut (the reference has none for this task).
+ * Row cap: S*K <= CN_MERGE_MAX_ROWS, CN_ERR_SHAPE above. */
+int cn_multi_pose_merge_f32(const float *rows, int S, int B, int K, int apply_nms, float *out_rows,
+                            void *stream);
 int cn_resize_bilinear_u8(const uint8_t *image_hwc, int H, int W, int pitch_bytes, int out_h,
                           int out_w, uint8_t *out_hwc, void *stream);
 
