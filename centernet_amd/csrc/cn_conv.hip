@@ -1424,29 +1424,23 @@ extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weigh
                                ((cn_knobs.dcn_team == 1 && Cout <= 64) || cn_knobs.dcn_team >= 2);
         // wide form (cn_dcn4.hip): every sample once per tile for ALL output channels; Cout % 128 == 0
         const bool wide_auto = cn_knobs.dcn_form == 0 && cn_knobs.dcn_wide && tiles128 >= 64 && (Cout & 127) == 0 && !cn_knobs.dbgskip;
+        DcnWinCall c = {};
+        c.x = input_nhwc; c.w = weight_packed; c.bias = bias; c.om = offset_mask_nhwc; c.om_pitch = om_pitch;
+        c.scale = scale; c.shift = shift; c.y = output_nhwc; c.out_pitch = out_pitch;
+        c.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
+        c.B = B; c.Cin = Cin; c.H = H; c.W = W; c.Cout = Cout; c.mask_sigmoid = mask_sigmoid; c.relu = relu;
+        c.x_mul = (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f;
+        c.range = ctl ? ctl->range : nullptr;
+        c.dbg = cn_knobs.dbgskip;
+        c.partial = ws_ok ? (float *)workspace : nullptr;
+        c.partial_bytes = ws_ok ? workspace_bytes : 0;
+        hipStream_t st = (hipStream_t)stream;
         if (cn_knobs.dcn_form == 6 || cn_knobs.dcn_form == 7 || wide_auto)
-            rc = cn_dcn_wide_f32s(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift,
-                                  output_nhwc, out_pitch, (flags & CN_CONV_Y_PLAIN) ? 1 : 0, B, Cin, H, W, Cout,
-                                  mask_sigmoid, relu, (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f,
-                                  ctl ? ctl->range : nullptr, cn_knobs.dcn_form == 7 ? 4 : 0, cn_knobs.dbgskip,
-                                  ws_ok ? (float *)workspace : nullptr, ws_ok ? workspace_bytes : 0, &ks,
-                                  (hipStream_t)stream);
+            rc = cn_dcn_wide_f32s(c, cn_knobs.dcn_form == 7 ? 4 : 0, &ks, st);
         if (rc == CN_ERR_UNSUPPORTED && (cn_knobs.dcn_form == 4 || cn_knobs.dcn_form == 5 || team_auto))
-            rc = cn_dcn_team_f32s(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift,
-                                  output_nhwc, out_pitch, (flags & CN_CONV_Y_PLAIN) ? 1 : 0, B, Cin, H, W, Cout,
-                                  mask_sigmoid, relu, (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f,
-                                  ctl ? ctl->range : nullptr,
-                                  cn_knobs.dcn_form == 5 ? 2 : ((team_auto && cn_knobs.dcn_team == 3) ? 1 : 0), cn_knobs.dbgskip,
-                                  ws_ok ? (float *)workspace : nullptr, ws_ok ? workspace_bytes : 0, &ks,
-                                  (hipStream_t)stream);
+            rc = cn_dcn_team_f32s(c, cn_knobs.dcn_form == 5 ? 2 : ((team_auto && cn_knobs.dcn_team == 3) ? 1 : 0), &ks, st);
         if (rc == CN_ERR_UNSUPPORTED && cn_knobs.dcn_form < 4)
-            rc = cn_dcn_window_f32s(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch,
-                                    scale, shift, output_nhwc, out_pitch,
-                                    (flags & CN_CONV_Y_PLAIN) ? 1 : 0, B, Cin, H, W, Cout,
-                                    mask_sigmoid, relu, (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f,
-                                    ctl ? ctl->range : nullptr, forced ? 1 : 192, cn_knobs.dbgskip,
-                                    ws_ok ? (float *)workspace : nullptr, ws_ok ? workspace_bytes : 0,
-                                    &ks, (hipStream_t)stream);
+            rc = cn_dcn_window_f32s(c, forced ? 1 : 192, &ks, st);
         if (rc == CN_OK && ks > 1) {
             // second stage of the K split: fixed-order sum of the slabs + the usual epilogue
             IgemmArgs r = {};

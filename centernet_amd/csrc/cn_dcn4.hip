@@ -33,83 +33,29 @@
 // (dcn_v2_im2col_cuda.cu:165), corner rule (:30-41), weights hh*hw, hh*lw, lh*hw, lh*lw (:26-28,43),
 // value * mask (:174; the mask multiplies the four corner weights), bias then accumulate
 // (dcn_v2_cuda.c:61-97).
-#include "cn_internal.h"
+#include "cn_dcn_window.h"
 #include "cn_tuning.h"
 
-__device__ __attribute__((aligned(128))) unsigned char cn_d4_zero_line[128];
 // probe build, key 9 bit 512: cycle stamps of waves 0 and 4 of workgroup 0 over its first 64 steps
 __device__ unsigned long long cn_d4_trace[2 * 64 * 8];
 
 namespace {
 
 constexpr int W_NT = 512;                      // 8 waves: 4 pixel blocks x 2 K-half teams
-constexpr int W_TX = 16, W_TY = 8, W_PM = W_TX * W_TY;
-constexpr int W_RCH = 3;                       // offsets up to +-3 px sample inside the window
-constexpr int W_WX = W_TX + 2 + 2 * W_RCH;     // 24
-constexpr int W_WY = W_TY + 2 + 2 * W_RCH;     // 16
-constexpr int W_WPIX = W_WX * W_WY;            // 384
-constexpr int W_PIXB = 128;                    // bytes per window pixel: 32 plain floats, unpadded
-constexpr int W_ROWB = W_WX * W_PIXB;          // 3072 = 12 x 256: a row starts on bank group 0
-constexpr int W_WBYTES = W_WPIX * W_PIXB;      // 49152
-constexpr int W_NP = W_WPIX * 8 / W_NT;        // 6 DMA pieces (16 B) per thread and chunk
-constexpr int W_RECW = W_WBYTES;               // float4 [9][128]: corner weights (mask, exponent, validity folded in)
-constexpr int W_RECP = W_RECW + 9 * W_PM * 16; // uint2 [9][128]: swizzled LDS offsets of corners 1 and 2 | far flag + corner
-constexpr int W_EPI = W_RECP + 9 * W_PM * 8;   // 76800: float [3][256]: bias, scale, shift of the workgroup's output channels
+constexpr int W_NP = DCNW_WPIX * 8 / W_NT;     // 6 DMA pieces (16 B) per thread and chunk
+constexpr int W_EPI = DCNW_REC_END;            // 76800: float [3][256]: bias, scale, shift of the workgroup's output channels
 constexpr int W_RING = W_EPI + 3 * 256 * 4;    // 79872: two slots of NB x 4096 bytes
-constexpr int W_LDC = 68;                      // floats per staged pixel row (64 + 4)
-constexpr int W_STG = 32 * W_LDC * 4;          // 8704 bytes per wave (8 waves: 69632 <= W_EPI)
-static_assert(8 * W_STG <= W_EPI, "epilogue strips alias the window and the records only");
-static_assert(W_ROWB % 256 == 0, "window rows keep the bank-group phase");
-
-struct D4Args {
-    const float *x;            // (B, H, W, Cin) plain fp32
-    const void *w;             // f32s-packed [tap][cout_pad][cin_pad] row form + the fragment-ordered copy behind it
-    const float *bias, *scale, *shift, *om;
-    void *y;
-    int B, H, W, Cin, Cout, om_pitch, relu;
-    int cin_pad, cout_pad, nchunk, tiles_x, tiles_y, out_pitch, out_plain;
-    float x_mul;
-    uint32_t *range;
-    int ksplit;                // K-chunk ranges per tile (blockIdx.z); > 1: raw partial sums
-    float *partial;            // [ksplit][B*H*W][cout_pad] fp32 (splitk_reduce_kernel applies the epilogue)
-    int prefetch;              // 1 = L2 prefetch of the weights three steps ahead (cn_set_tuning key 45, default 1)
-    int dbg;                   // probe build (cn_set_tuning key 9): 1 = no weight DMA, 2 = no MFMAs, 4 = no sampling, 8 = no per-step barrier, 16 = no far path, 32 = no steps, 64 = no window swaps, 128 = no epilogue
-};
-
-typedef _Float16 d4_f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char d4_lds_char;
-typedef __attribute__((address_space(1))) char d4_glb_char;
-typedef __attribute__((address_space(3))) cn_f32x4 d4_lds_f32x4;
-typedef __attribute__((address_space(1))) cn_f32x4 d4_glb_f32x4;
-typedef __attribute__((address_space(3))) d4_f16x8 d4_lds_f16x8;
-typedef __attribute__((address_space(3))) void d4_lds_void;
-typedef __attribute__((address_space(1))) const void d4_glb_void;
-typedef float d4_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned d4_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void d4_barrier()
-{
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// swizzled LDS byte offsets of window pixels (wy, wx) and (wy, wx + 1), quad 0 of lane half 0:
-// physical 16-byte slot of logical quad q of a pixel = q ^ ((wx >> 1) & 7)
-__device__ __forceinline__ unsigned d4_enc(int wy, int wx)
-{
-    const unsigned p = (unsigned)(wy * W_WX + wx);
-    const unsigned q1 = p * W_PIXB + ((((unsigned)wx >> 1) & 7u) << 4);
-    const unsigned q2 = (p + 1u) * W_PIXB + (((((unsigned)wx + 1u) >> 1) & 7u) << 4);
-    return q1 | (q2 << 16);
-}
+static_assert(8 * DCNW_STG <= W_EPI, "epilogue strips alias the window and the records only");
 
 // NB:   blocks of 32 output channels per workgroup (4 or 8)
 // MSIG: the mask is sigmoid(conv output) (dcn_v2.py:67), hence in [0, 1]: a sample is a convex blend of
 //       window values times <= 1 and needs neither clamp nor range tracking of its own; false = a
 //       caller-supplied mask of any size (clamp + track per sample)
+// DBG:  probe build (DcnWinArgs.dbg, cn_set_tuning key 9): 1 = no weight DMA, 2 = no MFMAs, 4 = no sampling, 8 = no
+//       per-step barrier, 16 = no far path, 32 = no steps, 64 = no window swaps, 128 = no epilogue, 512 = cycle
+//       stamps (cn_dcn_wide_trace)
 template <int NB, bool MSIG, bool DBG>
-__global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
+__global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const DcnWinArgs a)
 {
     extern __shared__ __attribute__((aligned(128))) char smem[];
     constexpr int SLOT = NB * 4096;                // bytes of one step's weight fragments
@@ -124,22 +70,14 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
     const int l31 = lane & 31, h = lane >> 5;
     const int pb = wave & 3, kk = wave >> 2;
     const int H = a.H, W = a.W;
-    int bx = blockIdx.x;
-    {   // XCD-aware tile order: contiguous tile ranges per XCD (block b runs on XCD b % 8)
-        const int q8 = gridDim.x >> 3;
-        if (bx < (q8 << 3)) bx = (bx & 7) * q8 + (bx >> 3);
-    }
-    const int tiles = a.tiles_x * a.tiles_y;
-    const int b = bx / tiles;
-    const int tr = bx - b * tiles;
-    const int ty0 = (tr / a.tiles_x) * W_TY, tx0 = (tr % a.tiles_x) * W_TX;
-    const int wy0 = ty0 - 1 - W_RCH, wx0 = tx0 - 1 - W_RCH;
+    const DcnwTile tile = dcnw_tile(a.tiles_x, a.tiles_y);
+    const int b = tile.b, ty0 = tile.ty0, tx0 = tile.tx0, wy0 = tile.wy0, wx0 = tile.wx0;
     const int n0 = (int)blockIdx.y * (32 * NB);
     const int dbg = DBG ? a.dbg : 0;
     const unsigned pix_bytes = (unsigned)a.Cin * 4u;
     const unsigned img_base = (unsigned)(b * H) * (unsigned)W;
-    const d4_glb_char *xg = (const d4_glb_char *)a.x;
-    const d4_lds_char *lds = (const d4_lds_char *)smem;
+    const dcnw_glb_char *xg = (const dcnw_glb_char *)a.x;
+    const dcnw_lds_char *lds = (const dcnw_lds_char *)smem;
     float rng_in = 0.f, rng_out = 0.f;
     // K split (small maps with deep K): this workgroup's share of the 32-channel chunks
     const int cpw = a.nchunk / a.ksplit;
@@ -152,18 +90,18 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
     for (int p = 0; p < W_NP; ++p) {
         const int i = p * W_NT + tid;
         const int wp = i >> 3, pq = i & 7;
-        const int wy = wp / W_WX, wx = wp - wy * W_WX;
+        const int wy = wp / DCNW_WX, wx = wp - wy * DCNW_WX;
         const int lq = pq ^ ((wx >> 1) & 7);
         const int iy = wy0 + wy, ix = wx0 + wx;
         const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
         doff[p] = ok ? (img_base + (unsigned)(iy * W + ix)) * pix_bytes + 16u * (unsigned)lq : 0xffffffffu;
     }
-    const d4_glb_char *zline = (const d4_glb_char *)cn_d4_zero_line + 16 * (lane & 7);
+    const dcnw_glb_char *zline = (const dcnw_glb_char *)dcnw_zero_line + 16 * (lane & 7);
     unsigned wbase = 0;             // byte offset of the window being sampled (0 or W_WIN1)
     auto dma1 = [&](int chunk, int p, unsigned base) {
         const unsigned cb = (unsigned)chunk * 128u;
-        const d4_glb_char *src = (doff[p] != 0xffffffffu) ? xg + (doff[p] + cb) : zline;
-        __builtin_amdgcn_global_load_lds((d4_glb_void *)src, (d4_lds_void *)(smem + base + (p * W_NT + wave * 64) * 16), 16, 0, 0);
+        const dcnw_glb_char *src = (doff[p] != 0xffffffffu) ? xg + (doff[p] + cb) : zline;
+        __builtin_amdgcn_global_load_lds((dcnw_glb_void *)src, (dcnw_lds_void *)(smem + base + (p * W_NT + wave * 64) * 16), 16, 0, 0);
     };
     auto dma = [&](int chunk) {
 #pragma unroll
@@ -184,42 +122,42 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
     auto track = [&]() {
 #pragma unroll
         for (int p = 0; p < W_NP; ++p) {
-            const cn_f32x4 v = *reinterpret_cast<const d4_lds_f32x4 *>(lds + wbase + (p * W_NT + tid) * 16);
+            const cn_f32x4 v = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + wbase + (p * W_NT + tid) * 16);
             cn_rng_upd4(rng_in, v);
         }
     };
     // ---- weight fragments of one (tap, chunk) step: NB x 4 KiB, contiguous in the fragment copy
     // ([tap][chunk][block][quarter][lane] x 16 bytes), copied as 1 KiB pieces into ring slot `slot`
-    const d4_glb_char *wfrag = (const d4_glb_char *)a.w + (size_t)9 * a.cout_pad * a.cin_pad * 4;
+    const dcnw_glb_char *wfrag = (const dcnw_glb_char *)a.w + (size_t)9 * a.cout_pad * a.cin_pad * 4;
     const int ncb = a.cout_pad >> 5;
     auto dma_w = [&](int t, int chunk, int slot) {          // all eight waves: NB / 2 pieces each (prologue)
-        const d4_glb_char *src = wfrag + ((size_t)(t * a.nchunk + chunk) * ncb + (n0 >> 5)) * 4096 + (unsigned)lane * 16u;
+        const dcnw_glb_char *src = wfrag + ((size_t)(t * a.nchunk + chunk) * ncb + (n0 >> 5)) * 4096 + (unsigned)lane * 16u;
 #pragma unroll
         for (int j = 0; j < NPW; ++j) {
             const int piece = j * 8 + wave;
-            __builtin_amdgcn_global_load_lds((d4_glb_void *)(src + piece * 1024),
-                                             (d4_lds_void *)(smem + W_RING + slot * SLOT + piece * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((dcnw_glb_void *)(src + piece * 1024),
+                                             (dcnw_lds_void *)(smem + W_RING + slot * SLOT + piece * 1024), 16, 0, 0);
         }
     };
     auto dma_w1 = [&](int t, int chunk, int slot) {         // one team's four waves: NB pieces each (step loop)
-        const d4_glb_char *src = wfrag + ((size_t)(t * a.nchunk + chunk) * ncb + (n0 >> 5)) * 4096 + (unsigned)lane * 16u;
+        const dcnw_glb_char *src = wfrag + ((size_t)(t * a.nchunk + chunk) * ncb + (n0 >> 5)) * 4096 + (unsigned)lane * 16u;
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             const int piece = j * 4 + pb;
-            __builtin_amdgcn_global_load_lds((d4_glb_void *)(src + piece * 1024),
-                                             (d4_lds_void *)(smem + W_RING + slot * SLOT + piece * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((dcnw_glb_void *)(src + piece * 1024),
+                                             (dcnw_lds_void *)(smem + W_RING + slot * SLOT + piece * 1024), 16, 0, 0);
         }
     };
 
     // ---- prologue: offsets / masks of the tile, the window of the first chunk and the first step's
     // weights behind them, then the records (dcn_v2_im2col_cuda.cu:151-176; cn_dcn3.hip for the format)
     {
-        constexpr int NR = (9 * W_PM + W_NT - 1) / W_NT;   // 3 (the last trip a quarter full)
+        constexpr int NR = (9 * DCNW_PM + W_NT - 1) / W_NT;   // 3 (the last trip a quarter full)
         float off_h[NR], off_w[NR], mkv[NR];
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
-            const int i = min(p * W_NT + tid, 9 * W_PM - 1);
-            const int tap = i >> 7, m = i & (W_PM - 1);
+            const int i = min(p * W_NT + tid, 9 * DCNW_PM - 1);
+            const int tap = i >> 7, m = i & (DCNW_PM - 1);
             const int oy = ty0 + (m >> 4), ox = tx0 + (m & 15);
             const float *om = a.om + (size_t)((b * H + oy) * W + ox) * a.om_pitch;
             off_h[p] = om[2 * tap];
@@ -247,7 +185,7 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
             const int i = p * W_NT + tid;
-            const int tap = i >> 7, m = i & (W_PM - 1);
+            const int tap = i >> 7, m = i & (DCNW_PM - 1);
             const int oy = ty0 + (m >> 4), ox = tx0 + (m & 15);
             float mk = mkv[p];
             if (MSIG) mk = sigmoidf_ref(mk);            // dcn_v2.py:67
@@ -256,7 +194,7 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
             const float h_im = (float)(oy - 1 + ki) + off_h[p];
             const float w_im = (float)(ox - 1 + kj) + off_w[p];
             cn_f32x4 wv = {0.f, 0.f, 0.f, 0.f};
-            unsigned p0 = d4_enc((m >> 4) + 1 + W_RCH, (m & 15) + 1 + W_RCH), p1 = 0u;
+            unsigned p0 = dcnw_enc((m >> 4) + 1 + DCNW_RCH, (m & 15) + 1 + DCNW_RCH), p1 = 0u;
             if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {   // :165
                 const float hf = floorf(h_im), wf = floorf(w_im);
                 const int yl = (int)hf, xl = (int)wf;
@@ -269,13 +207,13 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
                 wv[2] = (yh_ok && xl_ok) ? lh * hw * mk : 0.f;
                 wv[3] = (yh_ok && xh_ok) ? lh * lw * mk : 0.f;
                 const int wyl = yl - wy0, wxl = xl - wx0;
-                const bool inwin = (unsigned)wyl <= (unsigned)(W_WY - 2) && (unsigned)wxl <= (unsigned)(W_WX - 2);
-                if (inwin) p0 = d4_enc(wyl, wxl);
+                const bool inwin = (unsigned)wyl <= (unsigned)(DCNW_WY - 2) && (unsigned)wxl <= (unsigned)(DCNW_WX - 2);
+                if (inwin) p0 = dcnw_enc(wyl, wxl);
                 else p1 = 0x80000000u | ((unsigned)(yl + 1) << 15) | (unsigned)(xl + 1);
             }
-            if (i < 9 * W_PM) {
-                *reinterpret_cast<cn_f32x4 *>(smem + W_RECW + i * 16) = wv;
-                *reinterpret_cast<d4_u32x2 *>(smem + W_RECP + i * 8) = d4_u32x2{p0, p1};
+            if (i < 9 * DCNW_PM) {
+                *reinterpret_cast<cn_f32x4 *>(smem + DCNW_RECW + i * 16) = wv;
+                *reinterpret_cast<dcnw_u32x2 *>(smem + DCNW_RECP + i * 8) = dcnw_u32x2{p0, p1};
             }
         }
     }
@@ -305,18 +243,18 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
     // in flight.  Records are read one
     // request ahead (no dependent LDS round trip inside a request).
     cn_f32x4 c1a, c1b, c2a, c2b, c3a, c3b, c4a, c4b, wv, wv_n;
-    d4_u32x2 pp_n;
-    d4_f16x8 shi = {}, slo = {};
-    d4_f16x8 fh[2][2] = {}, fl[2][2] = {};
+    dcnw_u32x2 pp_n;
+    dcnw_f16x8 shi = {}, slo = {};
+    dcnw_f16x8 fh[2][2] = {}, fl[2][2] = {};
     unsigned far_base = 0;
     auto record = [&](int t) {
-        wv_n = *reinterpret_cast<const d4_lds_f32x4 *>(lds + W_RECW + (t * W_PM + m) * 16);
-        pp_n = *reinterpret_cast<const __attribute__((address_space(3))) d4_u32x2 *>(lds + W_RECP + (t * W_PM + m) * 8);
+        wv_n = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + DCNW_RECW + (t * DCNW_PM + m) * 16);
+        pp_n = *reinterpret_cast<const dcnw_lds_u32x2 *>(lds + DCNW_RECP + (t * DCNW_PM + m) * 8);
     };
     // request(t): corners of step t (its record was read by record(t)); reads the record of step t + 1
     auto request = [&](int t) {
         wv = wv_n;
-        const d4_u32x2 pp = pp_n;
+        const dcnw_u32x2 pp = pp_n;
         if (t < 8) record(t + 1);
         const unsigned B1 = ((pp[0] & 0xffffu) ^ hx ^ kx) + wbase, B2 = ((pp[0] >> 16) ^ hx ^ kx) + wbase;
         if ((int)pp[1] < 0 && !(dbg & 16)) {
@@ -330,24 +268,24 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
             const unsigned o2 = __umul24(r0 + (unsigned)x1, pix_bytes) + far_base;
             const unsigned o3 = __umul24(r1 + (unsigned)x0, pix_bytes) + far_base;
             const unsigned o4 = __umul24(r1 + (unsigned)x1, pix_bytes) + far_base;
-            c1a = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o1);
-            c1b = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o1 + 16);
-            c2a = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o2);
-            c2b = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o2 + 16);
-            c3a = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o3);
-            c3b = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o3 + 16);
-            c4a = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o4);
-            c4b = *reinterpret_cast<const d4_glb_f32x4 *>(xg + o4 + 16);
+            c1a = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o1);
+            c1b = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o1 + 16);
+            c2a = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o2);
+            c2b = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o2 + 16);
+            c3a = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o3);
+            c3b = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o3 + 16);
+            c4a = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o4);
+            c4b = *reinterpret_cast<const dcnw_glb_f32x4 *>(xg + o4 + 16);
         } else {
             // channels 16 kk + 8 h .. + 7 of the four corners: eight window reads
-            c1a = *reinterpret_cast<const d4_lds_f32x4 *>(lds + B1);
-            c1b = *reinterpret_cast<const d4_lds_f32x4 *>(lds + (B1 ^ 16u));
-            c2a = *reinterpret_cast<const d4_lds_f32x4 *>(lds + B2);
-            c2b = *reinterpret_cast<const d4_lds_f32x4 *>(lds + (B2 ^ 16u));
-            c3a = *reinterpret_cast<const d4_lds_f32x4 *>(lds + B1 + W_ROWB);
-            c3b = *reinterpret_cast<const d4_lds_f32x4 *>(lds + (B1 ^ 16u) + W_ROWB);
-            c4a = *reinterpret_cast<const d4_lds_f32x4 *>(lds + B2 + W_ROWB);
-            c4b = *reinterpret_cast<const d4_lds_f32x4 *>(lds + (B2 ^ 16u) + W_ROWB);
+            c1a = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + B1);
+            c1b = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + (B1 ^ 16u));
+            c2a = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + B2);
+            c2b = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + (B2 ^ 16u));
+            c3a = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + B1 + DCNW_ROWB);
+            c3b = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + (B1 ^ 16u) + DCNW_ROWB);
+            c4a = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + B2 + DCNW_ROWB);
+            c4b = *reinterpret_cast<const dcnw_lds_f32x4 *>(lds + (B2 ^ 16u) + DCNW_ROWB);
         }
         // the previous MFMA block's operands stay allocated until these reads have been issued (operand
         // hazard note, DESIGN.md 3.0 / cn_dcn3.hip)
@@ -357,7 +295,7 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
     };
     // w1*v1 + w2*v2 + w3*v3 + w4*v4 (dcn_v2_im2col_cuda.cu:43-45; mask and exponent inside the weights), split
     auto blend = [&]() {
-        const d4_f32x2 w1 = {wv[0], wv[0]}, w2 = {wv[1], wv[1]}, w3 = {wv[2], wv[2]}, w4 = {wv[3], wv[3]};
+        const dcnw_f32x2 w1 = {wv[0], wv[0]}, w2 = {wv[1], wv[1]}, w3 = {wv[2], wv[2]}, w4 = {wv[3], wv[3]};
         cn_f32x4 va, vb;
         {
 // plain v_fma_f32 (this file is built with -fno-slp-vectorize): v_pk_fma_f32 issues through the matrix pipe's
@@ -416,9 +354,9 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
             const bool tr_on = DBG && (dbg & 512) && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && pb == 0 && step < 64;
             if (tr_on) ts[0] = __builtin_readcyclecounter();
             if (t != 0) {
-                // this step's weights: team 1 has waited for its pieces; the barrier also frees the other slot
+                // this step's weights: team 1 has waited for its pieces; the raw s_barrier also frees the other slot
                 if (tr_on) ts[1] = __builtin_readcyclecounter();
-                if (!(dbg & 8)) d4_barrier();
+                if (!(dbg & 8)) dcnw_barrier();
             }
             if (tr_on) ts[2] = __builtin_readcyclecounter();
             if (kk == 1) {
@@ -447,16 +385,16 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
                 if (cnx < c_hi && !(dbg & 1)) dma_w1(tn, cnx, (step + 1) & 1);
                 if (tr_on) ts[4] = __builtin_readcyclecounter();
             }
-            const d4_f16x8 bhi = shi, blo = slo;   // this step's B operand
+            const dcnw_f16x8 bhi = shi, blo = slo;   // this step's B operand
             // NB blocks of 32 output channels against this sample set; fragments of a pair of blocks are read
             // into one of two register sets whose previous readers are a full block of MFMAs back
-            const d4_lds_char *ring = lds + W_RING + (step & 1) * SLOT + laneoff;
+            const dcnw_lds_char *ring = lds + W_RING + (step & 1) * SLOT + laneoff;
             auto frag = [&](int pair, int set) {
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const d4_lds_char *g = ring + (2 * pair + e) * 4096;
-                    fh[set][e] = *reinterpret_cast<const d4_lds_f16x8 *>(g + kk * 1024);
-                    fl[set][e] = *reinterpret_cast<const d4_lds_f16x8 *>(g + (2 + kk) * 1024);
+                    const dcnw_lds_char *g = ring + (2 * pair + e) * 4096;
+                    fh[set][e] = *reinterpret_cast<const dcnw_lds_f16x8 *>(g + kk * 1024);
+                    fl[set][e] = *reinterpret_cast<const dcnw_lds_f16x8 *>(g + (2 + kk) * 1024);
                 }
             };
             frag(0, 0);
@@ -501,14 +439,14 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
     for (int pr = 0; pr < ((dbg & 128) ? 0 : NB / 2); ++pr) {
         __syncthreads();
         {
-            float *Cs = reinterpret_cast<float *>(smem + wave * W_STG);
+            float *Cs = reinterpret_cast<float *>(smem + wave * DCNW_STG);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const cn_f32x16 &A = acc[2 * pr + j];
                     const cn_f32x4 v = {A[4 * g], A[4 * g + 1], A[4 * g + 2], A[4 * g + 3]};
-                    *reinterpret_cast<cn_f32x4 *>(Cs + l31 * W_LDC + 32 * j + 8 * g + 4 * h) = v;
+                    *reinterpret_cast<cn_f32x4 *>(Cs + l31 * DCNW_LDC + 32 * j + 8 * g + 4 * h) = v;
                 }
         }
         __syncthreads();
@@ -517,15 +455,15 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
         const cn_f32x4 bs = *reinterpret_cast<const cn_f32x4 *>(epl);
         const cn_f32x4 sc = *reinterpret_cast<const cn_f32x4 *>(epl + 256);
         const cn_f32x4 sf2 = *reinterpret_cast<const cn_f32x4 *>(epl + 512);
-        const float *C0 = reinterpret_cast<const float *>(smem + pb * W_STG);
-        const float *C1 = reinterpret_cast<const float *>(smem + (pb + 4) * W_STG);
+        const float *C0 = reinterpret_cast<const float *>(smem + pb * DCNW_STG);
+        const float *C1 = reinterpret_cast<const float *>(smem + (pb + 4) * DCNW_STG);
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int row = kk * 16 + it * 4 + rr;
             const int mm = pb * 32 + row;
             const size_t off = (size_t)((b * H + ty0 + (mm >> 4)) * W + tx0 + (mm & 15));
-            cn_f32x4 v = *reinterpret_cast<const cn_f32x4 *>(C0 + row * W_LDC + cq * 4);
-            v = v + *reinterpret_cast<const cn_f32x4 *>(C1 + row * W_LDC + cq * 4);
+            cn_f32x4 v = *reinterpret_cast<const cn_f32x4 *>(C0 + row * DCNW_LDC + cq * 4);
+            v = v + *reinterpret_cast<const cn_f32x4 *>(C1 + row * DCNW_LDC + cq * 4);
             if (a.partial) {   // K split: raw sums, one slab per split; the reduce kernel does the rest
                 if (n < a.cout_pad)
                     *reinterpret_cast<cn_f32x4 *>(a.partial + ((size_t)blockIdx.z * ((size_t)a.B * H * W) + off) * a.cout_pad + n) = v;
@@ -550,26 +488,6 @@ __global__ __launch_bounds__(W_NT, 2) void dcn_wide_kernel(const D4Args a)
     }
 }
 
-template <int NB>
-int launch_dcn_wide(const D4Args &a, int mask_sigmoid, hipStream_t st)
-{
-    constexpr int LDS = W_RING + 2 * NB * 4096 + (NB == 4 ? W_WBYTES : 0);
-    static_assert(LDS <= 163840, "one workgroup per CU");
-    dim3 grid((unsigned)(a.B * a.tiles_x * a.tiles_y), (unsigned)(a.Cout / (32 * NB)), (unsigned)a.ksplit);
-    if (a.dbg && mask_sigmoid) {
-        CN_SET_MAX_LDS_ONCE((dcn_wide_kernel<NB, true, true>), LDS);
-        hipLaunchKernelGGL((dcn_wide_kernel<NB, true, true>), grid, dim3(W_NT), LDS, st, a);
-    } else if (mask_sigmoid) {
-        CN_SET_MAX_LDS_ONCE((dcn_wide_kernel<NB, true, false>), LDS);
-        hipLaunchKernelGGL((dcn_wide_kernel<NB, true, false>), grid, dim3(W_NT), LDS, st, a);
-    } else {
-        CN_SET_MAX_LDS_ONCE((dcn_wide_kernel<NB, false, false>), LDS);
-        hipLaunchKernelGGL((dcn_wide_kernel<NB, false, false>), grid, dim3(W_NT), LDS, st, a);
-    }
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
 }  // namespace
 
 // probe build: the cycle stamps of the last launch with key 9 bit 512 (2 waves x 64 steps x 8 stamps)
@@ -579,50 +497,26 @@ extern "C" int cn_dcn_wide_trace(unsigned long long *out)
 }
 
 // Shapes this kernel takes (the caller falls back to the team form otherwise): maps of whole 8 x 16 pixel
-// tiles, whole 32-channel chunks, Cout a multiple of 128.  nb: 0 = by shape (8 blocks where Cout % 256 == 0
-// and the grid still fills the chip, else 4), 4 / 8 = forced.
-int cn_dcn_wide_f32s(const float *x, const void *w_packed, const float *bias, const float *om,
-                     int om_pitch, const float *scale, const float *shift, void *y, int out_pitch,
-                     int out_plain, int B, int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
-                     float x_mul, uint32_t *range, int nb, int dbg, float *partial, size_t partial_bytes,
-                     int *ksplit_out, hipStream_t st)
+// tiles, whole 32-channel chunks, Cout a multiple of 128.  nb: 0 = by shape (8 blocks where Cout % 256 == 0,
+// else 4 -- the grid is not looked at: one too small for the chip gets the K split below), 4 / 8 = forced.
+int cn_dcn_wide_f32s(const DcnWinCall &c, int nb, int *ksplit_out, hipStream_t st)
 {
     if (ksplit_out) *ksplit_out = 1;
-    if ((H & 7) || (W & 15) || (Cin & 31) || (Cout & 127)) return CN_ERR_UNSUPPORTED;
-    if (H > 16383 || W > 16383 || (out_pitch & 3) || !cn_aligned16(y) || !cn_aligned16(x)) return CN_ERR_UNSUPPORTED;
-    if ((size_t)B * H * W * Cin * 4 >= ((size_t)1 << 32)) return CN_ERR_UNSUPPORTED;   // 32-bit byte offsets
-    // global path: 15-bit corner coordinates, 24-bit integer multiplies (pixel index, bytes per pixel)
-    if ((size_t)B * H * W >= ((size_t)1 << 24) || (size_t)Cin * 4 >= ((size_t)1 << 24)) return CN_ERR_UNSUPPORTED;
-    const long tiles = (long)B * (H / W_TY) * (W / W_TX);
-    if (nb != 4 && nb != 8) nb = (Cout % 256 == 0) ? 8 : 4;
-    if (nb == 8 && (Cout & 255)) nb = 4;
-    const long wgs = tiles * (Cout / (32 * nb));
-    // Too few tiles for the chip but a deep K (512 -> 256 @ 16^2): split the 32-channel chunks over
-    // 2 / 4 / 8 workgroups per tile -- raw fp32 partial sums in the caller's workspace, summed in a
-    // fixed order by splitk_reduce_kernel (deterministic)
-    int ksplit = 1;
-    {
-        const int nchunk = Cin / 32;
-        const int cout_pad = (Cout + 31) / 32 * 32;
-        for (int s2 = 2; s2 <= 8 && partial && wgs * ksplit < cn_knobs.dcn_wide_wgs; s2 *= 2)
-            if (nchunk % s2 == 0 && nchunk / s2 >= 2 &&
-                (size_t)s2 * B * H * W * cout_pad * sizeof(float) <= partial_bytes)
-                ksplit = s2;
-    }
-    D4Args a = {};
-    a.x = x; a.w = w_packed; a.bias = bias; a.scale = scale; a.shift = shift; a.om = om; a.y = y;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.om_pitch = om_pitch;
-    a.relu = relu; a.out_pitch = out_pitch; a.out_plain = out_plain;
-    a.cin_pad = Cin;
-    a.cout_pad = (Cout + 31) / 32 * 32;
-    a.nchunk = Cin / 32;
-    a.tiles_x = W / W_TX;
-    a.tiles_y = H / W_TY;
-    a.x_mul = x_mul; a.range = range; a.dbg = dbg;
+    if (!dcnw_shape_ok(c) || !dcnw_far_ok(c) || (c.Cout & 127)) return CN_ERR_UNSUPPORTED;
+    const long tiles = (long)c.B * (c.H / DCNW_TY) * (c.W / DCNW_TX);
+    if (nb != 4 && nb != 8) nb = (c.Cout % 256 == 0) ? 8 : 4;
+    if (nb == 8 && (c.Cout & 255)) nb = 4;
+    const unsigned nby = (unsigned)(c.Cout / (32 * nb));
+    DcnWinArgs a = dcnw_fill_args(c, dcnw_pick_ksplit(tiles * nby, cn_knobs.dcn_wide_wgs, c));
     // L2 prefetch: pays where the weight stream is long and cold (four-block form on deep K: +5 % cold); costs 1-4 % elsewhere
-    a.prefetch = (cn_knobs.dcn_wide_prefetch && nb == 4 && Cin >= 256) ? 1 : 0;
-    a.ksplit = ksplit;
-    a.partial = ksplit > 1 ? partial : nullptr;
-    if (ksplit_out) *ksplit_out = ksplit;
-    return nb == 8 ? launch_dcn_wide<8>(a, mask_sigmoid, st) : launch_dcn_wide<4>(a, mask_sigmoid, st);
+    a.prefetch = (cn_knobs.dcn_wide_prefetch && nb == 4 && c.Cin >= 256) ? 1 : 0;
+    if (ksplit_out) *ksplit_out = a.ksplit;
+    // LDS: shared regions + epilogue constants + ring; the four-block form adds its second window
+    constexpr int LDS8 = W_RING + 2 * 8 * 4096, LDS4 = W_RING + 2 * 4 * 4096 + DCNW_WBYTES;
+    static_assert(LDS8 <= 163840 && LDS4 <= 163840, "one workgroup per CU");
+    if (nb == 8)
+        return dcnw_launch<dcn_wide_kernel<8, true, true>, dcn_wide_kernel<8, true, false>,
+                           dcn_wide_kernel<8, false, false>, W_NT, LDS8>(a, nby, st);
+    return dcnw_launch<dcn_wide_kernel<4, true, true>, dcn_wide_kernel<4, true, false>,
+                       dcn_wide_kernel<4, false, false>, W_NT, LDS4>(a, nby, st);
 }

@@ -14,22 +14,27 @@ int cn_stem_pool_f32s(const float *x, const float *w_packed, const float *scale,
                       int stride, int pad, int relu, int out_pitch, int KP, int y_f32s, const cn_f32s_ctl *ctl,
                       hipStream_t st);
 
-// ---- f32s deformable kernels: cn_dcn2.hip (window), cn_dcn3.hip (team), cn_dcn4.hip (wide)
-int cn_dcn_window_f32s(const float *x, const void *w_packed, const float *bias, const float *om,
-                       int om_pitch, const float *scale, const float *shift, void *y, int out_pitch,
-                       int out_plain, int B, int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
-                       float x_mul, uint32_t *range, int min_wgs, int dbg, float *partial,
-                       size_t partial_bytes, int *ksplit_out, hipStream_t st);
-int cn_dcn_team_f32s(const float *x, const void *w_packed, const float *bias, const float *om,
-                     int om_pitch, const float *scale, const float *shift, void *y, int out_pitch,
-                     int out_plain, int B, int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
-                     float x_mul, uint32_t *range, int nmode, int dbg, float *partial,
-                     size_t partial_bytes, int *ksplit_out, hipStream_t st);
-int cn_dcn_wide_f32s(const float *x, const void *w_packed, const float *bias, const float *om,
-                     int om_pitch, const float *scale, const float *shift, void *y, int out_pitch,
-                     int out_plain, int B, int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
-                     float x_mul, uint32_t *range, int nb, int dbg, float *partial, size_t partial_bytes,
-                     int *ksplit_out, hipStream_t st);
+// ---- f32s deformable kernels: cn_dcn2.hip (window), cn_dcn3.hip (team), cn_dcn4.hip (wide); what they share is
+// in cn_dcn_window.h.  One call description for all three (cn_conv.hip fills it once)
+struct DcnWinCall {
+    const float *x;            // (B, H, W, Cin) plain fp32
+    const void *w;             // f32s-packed weights, row form + fragment copy
+    const float *bias, *om;    // om: (B, H, W, om_pitch): 18 offsets + 9 masks per pixel
+    int om_pitch;
+    const float *scale, *shift;
+    void *y;
+    int out_pitch, out_plain;
+    int B, Cin, H, W, Cout, mask_sigmoid, relu;
+    float x_mul;               // f32s input exponent (a power of two)
+    uint32_t *range;           // range words of the launch, or null
+    int dbg;                   // cn_set_tuning key 9
+    float *partial;            // K-split workspace, or null: no split
+    size_t partial_bytes;
+};
+// each returns CN_ERR_UNSUPPORTED for a shape it does not take; *ksplit_out > 1: `partial` holds that many slabs
+int cn_dcn_window_f32s(const DcnWinCall &c, int min_wgs, int *ksplit_out, hipStream_t st);
+int cn_dcn_team_f32s(const DcnWinCall &c, int nmode, int *ksplit_out, hipStream_t st);
+int cn_dcn_wide_f32s(const DcnWinCall &c, int nb, int *ksplit_out, hipStream_t st);
 
 // ---- cn_dcn_general.hip
 int cn_dcn_general_launch(const float *input, const float *weight, const float *bias,

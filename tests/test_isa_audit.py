@@ -81,33 +81,33 @@ def _listing(name, out_dir):
 
 
 # ---- dcn_wide_kernel<NB, MSIG, DBG>: the reports that are expected, and why each is safe ----------------------
-# reads of one request() of cn_dcn4.hip:317-351: four corner pairs of the window being sampled (quad and
-# quad ^ 16 of the pixels at +0 and one window row down, +W_ROWB = 3072) ...
+# reads of one request() of cn_dcn4.hip:255-289: four corner pairs of the window being sampled (quad and
+# quad ^ 16 of the pixels at +0 and one window row down, +DCNW_ROWB = 3072) ...
 _WINDOW = {("ds_read_b128", 0): 4, ("ds_read_b128", 3072): 4}
-# ... behind the record of the NEXT step (record(), :313-314): corner weights at W_RECW = 49152 + step * 2048
-# (float4 [9][128]) and the two swizzled offsets (uint2, W_RECP folded into the address register)
+# ... behind the record of the NEXT step (record(), :251-252): corner weights at DCNW_RECW = 49152 + step * 2048
+# (float4 [9][128]) and the two swizzled offsets (uint2, DCNW_RECP folded into the address register)
 _STEP_READS = {**_WINDOW, ("ds_read_b128", 49152): 1, ("ds_read_b64", 0): 1}
 # the same request seen through the loop's back-edge: the record address is a running pointer there
 _EXIT_READS = {**_WINDOW, ("ds_read_b128", 2048): 1, ("ds_read_b64", 0): 1}
 
 STEP_BARRIER = dict(
     reads=_STEP_READS, back_edge=False, writers=["dma"],
-    reason="""d4_barrier of step t >= 1 (cn_dcn4.hip:421).  In flight BY DESIGN (:296-306): team 0's request for step
-t + 1, issued at the end of step t - 1 behind the MFMAs (:484) and blended at the end of step t (:482) -- the
-record of step t + 2 in [W_RECW, W_EPI) (:313-314) and eight reads of the window being sampled,
-[wbase, wbase + W_WBYTES) (:343-350).  Every LDS writer up to the next barrier is LDS-DMA: dma_w1 into ring
-slot (step + 1) & 1, at W_RING and above (:204-211, :447), and for NB = 4 one piece of the NEXT chunk's window
-into wbase ^ W_WIN1 (:441, :443), the window that is NOT being sampled.  Records are written in the prologue
-only (:277-278).  No writer shares a region with a read; a ds_write here would void the argument.""")
+    reason="""dcnw_barrier of step t >= 1 (cn_dcn4.hip:359).  In flight BY DESIGN (:234-244): team 0's request for step
+t + 1, issued at the end of step t - 1 behind the MFMAs (:422) and blended at the end of step t (:420) -- the
+record of step t + 2 in [DCNW_RECW, W_EPI) (:251-252) and eight reads of the window being sampled,
+[wbase, wbase + DCNW_WBYTES) (:281-288).  Every LDS writer up to the next barrier is LDS-DMA: dma_w1 into ring
+slot (step + 1) & 1, at W_RING and above (:142-149, :385), and for NB = 4 one piece of the NEXT chunk's window
+into wbase ^ W_WIN1 (:379, :381), the window that is NOT being sampled.  Records are written in the prologue
+only (:215-216).  No writer shares a region with a read; a ds_write here would void the argument.""")
 SWAP_BARRIER = dict(
     reads=_EXIT_READS, back_edge=True, writers=["dma"],
-    reason="""__syncthreads of the window swap (cn_dcn4.hip:391), entered from the step loop's exit.  The walk carries
-team 0's request(t + 2) (:484) round the loop's back-edge and straight out of the loop -- a path no wave takes:
-the request is issued only while t < 7 and the loop leaves only after t = 8 (:414).  Steps t = 7 and t = 8 each
-wait lgkmcnt(0) for their ring fragments in front of the first MFMA (:462, in-order return retires everything
-older) and issue no request behind it (team 0: none at t = 7 / 8, :484; team 1: none at t = 8, :427).  So no
-record or window read is outstanding at :391, and the DMA that follows through the barrier-less step 0 (:441 /
-:443 into wbase ^ W_WIN1, after :392 the window just left; :447 into the ring) cannot overtake one.""")
+    reason="""__syncthreads of the window swap (cn_dcn4.hip:329), entered from the step loop's exit.  The walk carries
+team 0's request(t + 2) (:422) round the loop's back-edge and straight out of the loop -- a path no wave takes:
+the request is issued only while t < 7 and the loop leaves only after t = 8 (:352).  Steps t = 7 and t = 8 each
+wait lgkmcnt(0) for their ring fragments in front of the first MFMA (:400, in-order return retires everything
+older) and issue no request behind it (team 0: none at t = 7 / 8, :422; team 1: none at t = 8, :365).  So no
+record or window read is outstanding at :329, and the DMA that follows through the barrier-less step 0 (:379 /
+:381 into wbase ^ W_WIN1, after :330 the window just left; :385 into the ring) cannot overtake one.""")
 
 WIDE_EXPECTED = {
     # (NB, MSIG, DBG): reports in listing order
