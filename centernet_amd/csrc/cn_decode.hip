@@ -1844,7 +1844,7 @@ __global__ void ddd_assemble_kernel(const float *__restrict__ scores, const int3
                                     const int32_t *__restrict__ clses, const float *__restrict__ rot,
                                     const float *__restrict__ depth, const float *__restrict__ dim,
                                     const float *__restrict__ wh, const float *__restrict__ reg,
-                                    float *__restrict__ dets, int B, int K, int H, int W)
+                                    float *__restrict__ dets, int B, int K, int H, int W, int raw_depth)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * K) return;
@@ -1864,7 +1864,10 @@ __global__ void ddd_assemble_kernel(const float *__restrict__ scores, const int3
     float *d = dets + (size_t)i * D;
     d[0] = xs; d[1] = ys; d[2] = scores[i];
     for (int c = 0; c < 8; ++c) d[3 + c] = rot[((size_t)b * 8 + c) * HW + ind];
-    d[11] = depth[(size_t)b * HW + ind];
+    float dep = depth[(size_t)b * HW + ind];
+    // CN_DECODE_DDD_RAW_DEPTH: the head's raw value; detectors/ddd.py:60 on the K gathered cells only
+    if (raw_depth) dep = 1.0f / (sigmoidf_ref(dep) + 1e-6f) - 1.0f;
+    d[11] = dep;
     for (int c = 0; c < 3; ++c) d[12 + c] = dim[((size_t)b * 3 + c) * HW + ind];
     if (wh) {
         d[15] = wh[((size_t)b * 2 + 0) * HW + ind];
@@ -1936,12 +1939,12 @@ extern "C" int cn_ddd_decode_f32(const float *heat, const float *rot, const floa
     float *scores = (float *)((char *)workspace + base);
     int32_t *inds = (int32_t *)((char *)workspace + base + slot);
     int32_t *clses = (int32_t *)((char *)workspace + base + 2 * slot);
-    int rc = cn_topk_f32(heat, B, C, H, W, K, apply_sigmoid, scores, inds, clses, workspace, base,
-                         stream);
+    int rc = cn_topk_f32(heat, B, C, H, W, K, apply_sigmoid & ~CN_DECODE_DDD_RAW_DEPTH, scores, inds, clses,
+                         workspace, base, stream);
     if (rc != CN_OK) return rc;
     hipLaunchKernelGGL(ddd_assemble_kernel, dim3(cn_cdiv(B * K, 128)), dim3(128), 0,
                        (hipStream_t)stream, scores, inds, clses, rot, depth, dim, wh, reg, dets, B, K,
-                       H, W);
+                       H, W, (apply_sigmoid & CN_DECODE_DDD_RAW_DEPTH) ? 1 : 0);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

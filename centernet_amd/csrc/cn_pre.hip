@@ -465,3 +465,160 @@ extern "C" int cn_multi_pose_post_process_f32(const float *dets, int B, int K, c
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
+
+// ---------------------------------------------------------------------------
+// ddd task: the batched pre-process and the whole host tail of DddDetector on the device.
+//
+// cn_warp_table_u8_f32_batch -- the ddd class normalises with a FLOAT32 chain, (u8 / 255 - mean) / std
+// (detectors/ddd.py:45-46), not the float64-then-round of warp_normalize_kernel.  A uint8 level has 256
+// values, so the caller builds the 3 x 256 results with exactly those float32 operations once and the
+// kernel looks them up: same sampler, same zero border, out = table[c][v].
+// ---------------------------------------------------------------------------
+namespace {
+struct WarpTableArgs {
+    const uint8_t *img;
+    int H, W, pitch;
+    double m[6];
+    int oh, ow;
+    const float *table;  // (3, 256) on the device
+    float *out;          // (N, 3, oh, ow)
+    size_t img_stride, out_stride;
+};
+
+__global__ void warp_table_kernel(const WarpTableArgs a)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= a.ow) return;
+    int v[3];
+    const uint8_t *img = a.img + (size_t)blockIdx.z * a.img_stride;
+    float *out = a.out + (size_t)blockIdx.z * a.out_stride;
+    warp_pixel<3>(img, a.H, a.W, (size_t)a.pitch, a.m, x, y, row_base(a.m, 1, 2, y), row_base(a.m, 4, 5, y), v);
+    const size_t plane = (size_t)a.oh * a.ow;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c * plane + (size_t)y * a.ow + x] = a.table[c * 256 + v[c]];
+}
+}  // namespace
+
+extern "C" int cn_warp_table_u8_f32_batch(const uint8_t *images_hwc, int N, size_t image_stride_bytes, int H, int W,
+                                          int pitch_bytes, const double *dst_to_src_2x3, int out_h, int out_w,
+                                          const float *table_3x256, float *out_nchw, void *stream)
+{
+    if (!images_hwc || !dst_to_src_2x3 || !table_3x256 || !out_nchw) return CN_ERR_NULL;
+    if (H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || pitch_bytes < 3 * W || out_h > 65535 ||
+        H > 32767 || W > 32767 || N <= 0 || N > 65535)
+        return CN_ERR_SHAPE;
+    if (N > 1 && image_stride_bytes < (size_t)pitch_bytes * (size_t)H) return CN_ERR_SHAPE;
+    WarpTableArgs a = {};
+    a.img = images_hwc; a.H = H; a.W = W; a.pitch = pitch_bytes; a.oh = out_h; a.ow = out_w;
+    for (int i = 0; i < 6; ++i) a.m[i] = dst_to_src_2x3[i];
+    a.table = table_3x256; a.out = out_nchw;
+    a.img_stride = image_stride_bytes;
+    a.out_stride = (size_t)3 * out_h * out_w;
+    dim3 grid(cn_cdiv(out_w, 128), out_h, N);
+    hipLaunchKernelGGL(warp_table_kernel, grid, dim3(128), 0, (hipStream_t)stream, a);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+// ---------------------------------------------------------------------------
+// ddd_post_process_2d + ddd_post_process_3d + DddDetector.merge_outputs (utils/post_process.py:24-79,
+// utils/ddd_utils.py:68-114, detectors/ddd.py:82-88) for a batch, image b lifted with ITS matrix: the K raw
+// rows [x, y, score, rot 8, depth, dim 3, w, h, class] of ddd_decode become [alpha, x1, y1, x2, y2, h, w, l,
+// x, y, z, rotation_y, score], grouped by class as ctdet_post_kernel groups them, plus per class the length
+// of the leading run of rows with score > peak_thresh (the rows of a class are in descending score order,
+// so merge_outputs' mask is that prefix).  Types as the reference's: centre and (w, h) through the float64
+// point map (translation included for both) and rounded to float32; unproject, "+ h / 2", the box and the
+// angle sums in float32.  The two arctan2 are float64 atan2 rounded once to float32 (NumPy's float32
+// arctan2 differs from that by at most one ulp of the angle; no device form equals it bit for bit).
+// A class is taken when the float equals an integer in [0, num_classes) (`classes == j`).
+// ---------------------------------------------------------------------------
+namespace {
+constexpr int DDD_IN = 18, DDD_OUT = 13;
+__global__ __launch_bounds__(PP_KMAX) void ddd_post_kernel(const float *__restrict__ dets, int K, int num_classes,
+                                                           const double *__restrict__ to_source, int per_image,
+                                                           const float *__restrict__ calibs, float peak_thresh,
+                                                           float *__restrict__ rows, int32_t *__restrict__ bounds,
+                                                           int32_t *__restrict__ kept)
+{
+    __shared__ int cls_s[PP_KMAX];
+    __shared__ int pass_s[PP_KMAX];
+    const float HALF_PI = 1.57079637f, PI = 3.14159274f, TWO_PI = 6.28318548f;   // float32(np.pi) and kin
+    const int b = blockIdx.x, k = threadIdx.x;
+    const double *t = to_source + (per_image ? (size_t)b * 6 : 0);
+    const float *P = calibs + (size_t)b * 12;
+    float r[DDD_OUT];
+#pragma unroll
+    for (int e = 0; e < DDD_OUT; ++e) r[e] = 0.f;
+    int cls = num_classes;             // sorts behind every class
+    if (k < K) {
+        const float *d = dets + ((size_t)b * K + k) * DDD_IN;
+        const float cf = d[DDD_IN - 1];
+        if (cf >= 0.f && cf < (float)num_classes) {
+            const int c = (int)cf;
+            if ((float)c == cf) cls = c;
+        }
+        float pt[4];                   // centre, then the (w, h) pair: the same map for both
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const double x = (double)d[15 * p], y = (double)d[15 * p + 1];
+            pt[2 * p] = (float)((x * t[0] + y * t[1]) + t[2]);
+            pt[2 * p + 1] = (float)((x * t[3] + y * t[4]) + t[5]);
+        }
+        const float cx = pt[0], cy = pt[1], w2 = pt[2] / 2.f, h2 = pt[3] / 2.f;
+        // get_alpha: bin 1 (centred on -pi / 2) when its second logit is the larger one
+        const bool first = d[4] > d[8];
+        const float bin = (float)atan2((double)(first ? d[5] : d[9]), (double)(first ? d[6] : d[10]));
+        const float alpha = bin + (first ? -HALF_PI : HALF_PI);
+        const float depth = d[11], dim_h = d[12];
+        // unproject_2d_to_3d, then location[1] += h / 2
+        const float z = depth - P[11];
+        const float lx = ((cx * depth - P[3]) - P[2] * z) / P[0];
+        const float ly = ((cy * depth - P[7]) - P[6] * z) / P[5] + dim_h / 2.f;
+        // alpha2rot_y
+        float ry = alpha + (float)atan2((double)(cx - P[2]), (double)P[0]);
+        if (ry > PI) ry = ry - TWO_PI;
+        if (ry < -PI) ry = ry + TWO_PI;
+        r[0] = alpha;
+        r[1] = cx - w2; r[2] = cy - h2; r[3] = cx + w2; r[4] = cy + h2;
+        r[5] = dim_h; r[6] = d[13]; r[7] = d[14];
+        r[8] = lx; r[9] = ly; r[10] = z;
+        r[11] = ry; r[12] = d[2];
+    }
+    cls_s[k] = cls;
+    pass_s[k] = (k < K && r[12] > peak_thresh) ? 1 : 0;
+    __syncthreads();
+    if (k < K) {
+        int rank = 0;
+        for (int j = 0; j < K; ++j) rank += (cls_s[j] < cls || (cls_s[j] == cls && j < k)) ? 1 : 0;
+        float *o = rows + ((size_t)b * K + rank) * DDD_OUT;
+#pragma unroll
+        for (int e = 0; e < DDD_OUT; ++e) o[e] = r[e];
+    }
+    for (int c = k; c <= num_classes; c += PP_KMAX) {
+        int n = 0, lead = 0, open = 1;
+        for (int j = 0; j < K; ++j) {
+            n += cls_s[j] < c ? 1 : 0;
+            if (cls_s[j] == c) {
+                open &= pass_s[j];
+                lead += open;
+            }
+        }
+        bounds[(size_t)b * (num_classes + 1) + c] = n;
+        if (c < num_classes) kept[(size_t)b * num_classes + c] = lead;
+    }
+}
+}  // namespace
+
+extern "C" int cn_ddd_post_process_f32(const float *dets, int B, int K, int row_floats, int num_classes,
+                                       const double *to_source_2x3, int per_image, const float *calibs,
+                                       float peak_thresh, float *rows, int32_t *bounds, int32_t *kept, void *stream)
+{
+    if (!dets || !to_source_2x3 || !calibs || !rows || !bounds || !kept) return CN_ERR_NULL;
+    if (B <= 0 || K <= 0 || num_classes <= 0 || (row_floats != 16 && row_floats != DDD_IN)) return CN_ERR_SHAPE;
+    if (row_floats != DDD_IN) return CN_ERR_UNSUPPORTED;    // no (w, h): the reference's 3-D stage has no box either
+    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(ddd_post_kernel, dim3(B), dim3(PP_KMAX), 0, (hipStream_t)stream, dets, K, num_classes,
+                       to_source_2x3, per_image ? 1 : 0, calibs, peak_thresh, rows, bounds, kept);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}

@@ -204,8 +204,9 @@ def _transpose_and_gather_feat(feat, ind):
     return out
 
 
-def ddd_decode(heat, rot, depth, dim, wh=None, reg=None, K=40, apply_sigmoid=False):
-    """decode.py:426-462 -> (B, K, 16) or (B, K, 18) with wh."""
+def ddd_decode(heat, rot, depth, dim, wh=None, reg=None, K=40, apply_sigmoid=False, raw_depth=False):
+    """decode.py:426-462 -> (B, K, 16) or (B, K, 18) with wh.  ``raw_depth``: ``depth`` is the head's raw
+    map; the K gathered values are transformed (1 / (sigmoid + 1e-6) - 1, detectors/ddd.py:60) in the decode."""
     heat, rot, depth, dim, wh, reg = _prep(heat, rot, depth, dim, wh, reg)
     lib = native.lib()
     B, C, H, W = heat.shape
@@ -220,8 +221,8 @@ def ddd_decode(heat, rot, depth, dim, wh=None, reg=None, K=40, apply_sigmoid=Fal
     ws = _workspace(lib.cn_ddd_decode_workspace_bytes(B, C, H, W, K), heat.device)
     rc = lib.cn_ddd_decode_f32(native.ptr(heat), native.ptr(rot), native.ptr(depth), native.ptr(dim),
                                native.ptr(wh), native.ptr(reg), B, C, H, W, K,
-                               int(bool(apply_sigmoid)), native.ptr(dets), native.ptr(ws),
-                               ws.numel(), native.stream_ptr())
+                               int(bool(apply_sigmoid)) | (native.DECODE_DDD_RAW_DEPTH if raw_depth else 0),
+                               native.ptr(dets), native.ptr(ws), ws.numel(), native.stream_ptr())
     native.check(rc, "cn_ddd_decode_f32")
     return dets
 

@@ -63,8 +63,15 @@ class _FramePipe(object):
     cut; when there are several scales or --nms) and the copies of the rows / class bounds / f32s
     range digests into pinned memory -- is enqueued on the launch stream without a single host
     synchronisation.  The host waits for batch i - depth + 1 only when it collects it, i.e. while
-    later batches are on the device.  Tasks without the ``_device_tail_*`` hooks (ddd, exdet), and
-    shapes their kernels do not take, copy the raw detections out and keep the host tail."""
+    later batches are on the device.  Tasks without the ``_device_tail_*`` hooks (exdet), and
+    shapes their kernels do not take, copy the raw detections out and keep the host tail.
+
+    Two more task hooks keep the pipe free of task geometry: ``_pipe_level`` (input geometry, frame ->
+    input map and meta of one test scale) and ``_pipe_pre_process`` (the batched pre-process launch).
+    A task with per-frame side inputs (ddd: one 3 x 4 calibration matrix per frame) sets
+    ``_pipe_side_shape``: the pipe then keeps ``depth`` pinned (B, *shape) float32 buffers and their device
+    copies, ``submit`` takes the batch's side array, uploads it on the copy stream with the frames, and the
+    tail hooks read ``pipe.side_dev[slot]`` / ``pipe.side_host[slot]``."""
 
     def __init__(self, det, B, H, W, scales, flip, depth):
         import concurrent.futures
@@ -76,11 +83,10 @@ class _FramePipe(object):
         self.merge = len(self.scales) > 1 or bool(getattr(opt, "nms", False))
         self.levels = []
         for scale in self.scales:
-            g = det.input_geometry(H, W, scale)
-            to_input = get_affine_transform(g.center, g.extent, 0, [g.inp_w, g.inp_h])
+            g, to_input, meta = det._pipe_level(H, W, scale)
             resize = (g.scaled_h, g.scaled_w) != (g.src_h, g.src_w)
             self.levels.append(types.SimpleNamespace(
-                scale=scale, g=g, resize=resize, meta=det._meta(g),
+                scale=scale, g=g, resize=resize, meta=meta,
                 dst_to_src=(ctypes.c_double * 6)(*invert_affine(to_input).reshape(-1)),
                 scaled=torch.empty((B, g.scaled_h, g.scaled_w, 3), dtype=torch.uint8, device=dev) if resize else None,
                 batch=torch.empty((B * (2 if self.flip else 1), 3, g.inp_h, g.inp_w), device=dev,
@@ -101,6 +107,12 @@ class _FramePipe(object):
         self.digest_host = [torch.zeros((len(self.scales), 2), dtype=torch.int32).pin_memory() for _ in range(depth)]
         self.has_digest = [[False] * len(self.scales) for _ in range(depth)]
         self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=min(4, B))
+        side = det._pipe_side_shape
+        self.side_pinned = self.side_dev = None
+        self.side_host = [None] * depth      # the batch's side array as given (host tail, f32s re-run)
+        if side is not None:
+            self.side_pinned = [torch.empty((B,) + tuple(side), dtype=torch.float32).pin_memory() for _ in range(depth)]
+            self.side_dev = [torch.empty((B,) + tuple(side), dtype=torch.float32, device=dev) for _ in range(depth)]
         self.tail = det._device_tail_alloc(self) if det._device_tail_alloc is not None else None
         self.dets_host = None if self.tail is not None else [[None] * len(self.scales) for _ in range(depth)]
 
@@ -114,17 +126,24 @@ class _FramePipe(object):
                 np.copyto(dst[i], frames[i])
         list(self.pool.map(copy, range(0, n, step)))
 
-    def submit(self, i, frames):
+    def submit(self, i, frames, side=None):
         det, lib, B = self.det, native.lib(), self.B
         slot = i % self.depth
         if self.used[slot]:
             self.ev_h2d[slot].synchronize()      # the pinned buffer's previous upload has left it
         self._stage(slot, frames)
+        if self.side_pinned is not None:
+            self.side_host[slot] = side
+            self.side_pinned[slot].numpy()[:len(frames)] = side
         cur = torch.cuda.current_stream()
         with torch.cuda.stream(self.copy_stream):
             if self.used[slot]:
                 self.copy_stream.wait_event(self.ev_pre[slot])   # the device copy's previous reader is done
             self.dev_in[slot].copy_(self.pinned_in[slot], non_blocking=True)
+            if self.side_pinned is not None:
+                if self.used[slot]:
+                    self.copy_stream.wait_event(self.ev_done[slot])   # its reader is the tail, not the pre-process
+                self.side_dev[slot].copy_(self.side_pinned[slot], non_blocking=True)
             self.ev_h2d[slot].record(self.copy_stream)
         self.used[slot] = True
         cur.wait_event(self.ev_h2d[slot])
@@ -137,10 +156,7 @@ class _FramePipe(object):
                                                            g.scaled_h, g.scaled_w, native.ptr(lv.scaled[j]), stream),
                                  "cn_resize_bilinear_u8")
                 src = lv.scaled
-            native.check(lib.cn_warp_normalize_u8_f32_batch(
-                native.ptr(src), B, g.scaled_h * g.scaled_w * 3, g.scaled_h, g.scaled_w, g.scaled_w * 3,
-                lv.dst_to_src, g.inp_h, g.inp_w, self.mean, self.std, int(self.flip), native.ptr(lv.batch), stream),
-                "cn_warp_normalize_u8_f32_batch")
+            det._pipe_pre_process(self, lv, src, stream)
             if li == len(self.levels) - 1:
                 self.ev_pre[slot].record()
             dets = det._run_scale(lv.batch, self.flip)
@@ -166,6 +182,8 @@ class _FramePipe(object):
         det = self.det
         kw = det._arrays_kw(arrays)
         slot = i % self.depth
+        if self.side_pinned is not None:
+            kw = dict(kw, side=self.side_host[slot])
         self.ev_done[slot].synchronize()
         det.__dict__["_unchecked"] = 0       # (the batch's range digests are looked at right here)
         digest = self.digest_host[slot].tolist()
@@ -224,6 +242,24 @@ class BaseDetector(object):
         return {'c': g.center, 's': g.extent,
                 'out_height': g.inp_h // self.opt.down_ratio,
                 'out_width': g.inp_w // self.opt.down_ratio}
+
+    # ------------------------------------------------------------------ frame pipe: geometry + pre-process
+    _pipe_side_shape = None      # shape of a task's per-frame side input (ddd: (3, 4)), see _FramePipe
+
+    def _pipe_level(self, height, width, scale):
+        """Task hook of the frame pipeline: (InputGeometry, frame -> network-input map, meta) of one test
+        scale for (height, width) frames."""
+        g = self.input_geometry(height, width, scale)
+        return g, get_affine_transform(g.center, g.extent, 0, [g.inp_w, g.inp_h]), self._meta(g)
+
+    def _pipe_pre_process(self, pipe, lv, src, stream):
+        """Task hook of the frame pipeline: the batched device pre-process of level ``lv``, (B, h, w, 3)
+        uint8 ``src`` on the device -> ``lv.batch``, one launch."""
+        g = lv.g
+        native.check(native.lib().cn_warp_normalize_u8_f32_batch(
+            native.ptr(src), pipe.B, g.scaled_h * g.scaled_w * 3, g.scaled_h, g.scaled_w, g.scaled_w * 3,
+            lv.dst_to_src, g.inp_h, g.inp_w, pipe.mean, pipe.std, int(pipe.flip), native.ptr(lv.batch), stream),
+            "cn_warp_normalize_u8_f32_batch")
 
     # ------------------------------------------------------------------ pre-process
     def pre_process(self, image, scale, meta=None):
@@ -391,6 +427,10 @@ class BaseDetector(object):
             pipes[key] = _FramePipe(self, len(frames), H, W, self.scales, flip, depth)
         return pipes[key]
 
+    def _frames_and_side(self, batch):
+        """One item of ``run_frames_stream``'s iterable -> (frames, the pipe's side array or None)."""
+        return batch, None
+
     def run_frames(self, frames, arrays=False):
         """A list of (H, W, 3) uint8 BGR frames of one size -> list of per-image results, what
         ``run(frame)['results']`` returns for each (every test scale, flip-test and --nms as set).
@@ -415,7 +455,8 @@ class BaseDetector(object):
         ``arrays``: as ``run_frames``."""
         pipe, pending = None, collections.deque()
         n = 0
-        for frames in batches:
+        for batch in batches:
+            frames, side = self._frames_and_side(batch)
             if pipe is None:
                 pipe = self._pipe_for(frames, depth)
             elif (len(frames), ) + tuple(frames[0].shape) != (pipe.B, pipe.H, pipe.W, 3):
@@ -423,7 +464,7 @@ class BaseDetector(object):
             if len(pending) == depth:
                 j, fr = pending.popleft()
                 yield pipe.collect(j, fr, arrays)
-            pipe.submit(n, frames)
+            pipe.submit(n, frames, side)
             pending.append((n, frames))
             n += 1
         while pending:

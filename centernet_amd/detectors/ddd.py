@@ -2,16 +2,21 @@
 heat-map + depth + orientation bins + box dimensions (+ 2-D size and sub-pixel offset) on the HIP
 network, decoded by ``cn_ddd_decode_f32``, lifted to camera coordinates on the host
 (``post_process.ddd_post_process``).  ``run(image, calib)``: the second argument is the frame's
-3 x 4 projection matrix (test.py:37-39,105-106); without it the detector's KITTI default is used."""
+3 x 4 projection matrix (test.py:37-39,105-106); without it the detector's KITTI default is used.
+New surface: ``run_frames(frames, calibs)`` / ``run_frames_stream`` -- batches of frames, each with its
+own matrix, pre-processed (``cn_warp_table_u8_f32_batch``) and lifted (``cn_ddd_post_process_f32``) on the
+device."""
+import ctypes
 import time
 
 import numpy as np
 import torch
 
+from .. import native
 from ..decode import ddd_decode
-from ..image import get_affine_transform, warp_affine
-from ..post_process import ddd_post_process
-from .base_detector import BaseDetector
+from ..image import get_affine_transform, invert_affine, warp_affine
+from ..post_process import ddd_norm_table, ddd_post_process, ddd_results_batch
+from .base_detector import BaseDetector, InputGeometry
 
 
 class DddDetector(BaseDetector):
@@ -43,23 +48,54 @@ class DddDetector(BaseDetector):
         table per channel built with exactly those float32 operations."""
         c, s, to_input = self._frame_geometry(image.shape[0], image.shape[1])
         warped = warp_affine(image, to_input, (self.opt.input_w, self.opt.input_h))
-        levels = np.arange(256, dtype=np.float32).reshape(256, 1, 1) / 255.
-        table = ((levels - self.mean) / self.std).reshape(256, 3)             # float32 throughout
-        batch = np.stack([table[warped[:, :, ch], ch] for ch in range(3)])[None]
+        table = self.norm_table()
+        batch = np.stack([table[ch][warped[:, :, ch]] for ch in range(3)])[None]
         return torch.from_numpy(np.ascontiguousarray(batch)), self._meta(c, s, calib)
 
+    def norm_table(self, device=False):
+        """The (3, 256) float32 table of the ddd normalisation (``post_process.ddd_norm_table``), built
+        once per detector; ``device``: its copy in HBM (what ``cn_warp_table_u8_f32_batch`` reads)."""
+        d = self.__dict__
+        if "_norm_table" not in d:
+            d["_norm_table"] = ddd_norm_table(self.mean, self.std)
+        if not device:
+            return d["_norm_table"]
+        if "_norm_table_dev" not in d:
+            d["_norm_table_dev"] = torch.from_numpy(d["_norm_table"]).to(self.opt.device)
+        return d["_norm_table_dev"]
+
+    def _warp_table(self, frames, to_input, out, stream=None):
+        """(N, H, W, 3) uint8 frames on the device -> ``out`` (N, 3, input_h, input_w), one launch."""
+        N, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        dst_to_src = to_input if isinstance(to_input, ctypes.Array) else \
+            (ctypes.c_double * 6)(*invert_affine(to_input).reshape(-1))
+        native.check(native.lib().cn_warp_table_u8_f32_batch(
+            native.ptr(frames), N, H * W * 3, H, W, W * 3, dst_to_src, self.opt.input_h, self.opt.input_w,
+            native.ptr(self.norm_table(device=True)), native.ptr(out),
+            native.stream_ptr() if stream is None else stream), "cn_warp_table_u8_f32_batch")
+
     def pre_process_device(self, image, scale, calib=None, out=None):
-        """The device pre-process kernels implement the float64 normalisation of the other tasks; the
-        ddd chain differs from it in the last bit of some levels, so this task warps and normalises on
-        the host (one frame per call, as the reference) and uploads the float32 batch."""
+        """The same on the device: the uint8 frame (a numpy array, or a uint8 HIP tensor that is already
+        uploaded) through ``cn_warp_table_u8_f32_batch`` -- the warp of the other tasks with the float32
+        normalisation looked up in ``norm_table``.  Bit-identical to ``pre_process``."""
+        dev = self.opt.device
         if torch.is_tensor(image):
-            raise ValueError("the ddd task pre-processes host frames: (H, W, 3) uint8 BGR arrays")
-        images, meta = self.pre_process(image, scale, calib)
-        images = images.to(self.opt.device)
-        if out is not None:
-            out.copy_(images)
-            images = out
-        return images, meta
+            if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or \
+                    not image.is_cuda or not image.is_contiguous():
+                raise ValueError("pre_process_device needs a contiguous (H, W, 3) uint8 HIP tensor")
+            frame = image
+        else:
+            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+                raise ValueError("pre_process_device needs an (H, W, 3) uint8 BGR image")
+            frame = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+        shape = (1, 3, self.opt.input_h, self.opt.input_w)
+        if out is None:
+            out = torch.empty(shape, device=dev, dtype=torch.float32)
+        elif tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError("pre_process_device: `out` must be a contiguous %s tensor" % (shape,))
+        c, s, to_input = self._frame_geometry(int(frame.shape[0]), int(frame.shape[1]))
+        self._warp_table(frame[None], to_input, out)
+        return out, self._meta(c, s, calib)
 
     # ------------------------------------------------------------------ network + decode
     def process(self, images, return_time=False):
@@ -93,9 +129,150 @@ class DddDetector(BaseDetector):
                 results[j] = results[j][results[j][:, -1] > self.opt.peak_thresh]
         return results
 
+    # ------------------------------------------------------------------ frame pipe
+    _pipe_side_shape = (3, 4)        # one projection matrix per frame rides with the batch
+
+    def _calibs_for(self, frames, calibs):
+        """``run_frames``' ``calibs`` -> (n, 3, 4) float32, one matrix per frame: a single (3, 4) matrix
+        serves every frame; a sequence gives one per frame, ``None`` entries meaning the detector's default."""
+        n = len(frames)
+        if calibs is None:
+            raise NotImplementedError(
+                "run_frames / run_frames_stream of the ddd task need the frames' projection matrices: pass "
+                "calibs= (one (3, 4) matrix for all frames, or one per frame; a None entry = the detector's "
+                "KITTI default).  Lifting a whole video with an assumed default would return wrong metres.")
+        try:
+            if not isinstance(calibs, np.ndarray):
+                calibs = [self.calib if m is None else m for m in calibs]
+            arr = np.array(calibs, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("calibs: a (3, 4) matrix, or a sequence of %d of them (None = default)" % n)
+        if arr.shape == (3, 4):
+            arr = np.broadcast_to(arr, (n, 3, 4))
+        if arr.shape != (n, 3, 4):
+            raise ValueError("calibs: a (3, 4) matrix or %d of them for %d frames, got shape %s"
+                             % (n, n, arr.shape))
+        return np.ascontiguousarray(arr)
+
+    def _frames_and_side(self, batch):
+        try:
+            frames, calibs = batch
+        except (TypeError, ValueError):
+            raise ValueError("run_frames_stream of the ddd task takes (frames, calibs) pairs")
+        return frames, self._calibs_for(frames, calibs)
+
     def _pipe_for(self, frames, depth):
-        raise NotImplementedError("run_frames / run_frames_stream: the ddd task has a per-frame calibration "
-                                  "matrix and a host pre-process; use run(frame, calib) or run_batch")
+        scales, self.scales = self.scales, self.scales[:1]     # ddd.py:82-88: the first scale is the result
+        try:
+            return super(DddDetector, self)._pipe_for(frames, depth)
+        finally:
+            self.scales = scales
+
+    def _pipe_level(self, height, width, scale):
+        """No resize, no padding: the frame is warped straight onto the fixed input (``_frame_geometry``)."""
+        c, s, to_input = self._frame_geometry(height, width)
+        g = InputGeometry(height, width, height, width, self.opt.input_h, self.opt.input_w, c, s)
+        return g, to_input, self._meta(c, s, None)
+
+    def _pipe_pre_process(self, pipe, lv, src, stream):
+        self._warp_table(src, lv.dst_to_src, lv.batch, stream)
+
+    def run_frames(self, frames, calibs=None):
+        """A list of (H, W, 3) uint8 BGR frames of one size and their projection matrices -> per frame what
+        ``run(frame_i, calib_i)['results']`` returns: ``{class: (n, 13) float32}``, a class without rows a
+        ``(0,)`` array, a class whose rows were all cut at --peak_thresh ``(0, 13)``.  ``calibs``: one
+        (3, 4) matrix for all frames, or a sequence with one per frame (``None`` = the detector's default
+        matrix); every frame is lifted with ITS matrix (the reference's single-image detector lifts with
+        ``calibs[0]``).  One uint8 upload, one pre-process launch, one network step, one decode (the
+        depth transform inside it) and one tail launch per batch; the host slices the rows."""
+        side = self._calibs_for(frames, calibs)
+        pipe = self._pipe_for(frames, 1)
+        pipe.submit(0, frames, side)
+        return pipe.collect(0, frames)
+
+    def run_frames_stream(self, batches, depth=3):
+        """``run_frames`` over an iterable of ``(frames, calibs)`` pairs (all batches of one size and frame
+        geometry), pipelined as ``BaseDetector.run_frames_stream``; the matrices are staged in pinned
+        memory and uploaded on the copy stream with their frames."""
+        return super(DddDetector, self).run_frames_stream(batches, depth)
+
+    def _run_scale(self, images, flip):
+        """Network + decode of the frame pipeline: the centre map's sigmoid and the depth transform of
+        the K gathered cells are inside ``cn_ddd_decode_f32``; raw (B, K, 18) rows, asynchronous."""
+        self._note_unchecked_forward()
+        with torch.no_grad():
+            o = self.model(images, borrow=True)[-1]
+            return ddd_decode(o['hm'], o['rot'], o['dep'], o['dim'], wh=o['wh'] if self.opt.reg_bbox else None,
+                              reg=o['reg'] if self.opt.reg_offset else None, K=self.opt.K,
+                              apply_sigmoid=True, raw_depth=True)
+
+    def _run_frames_sync(self, frames, scales, side=None):
+        """One batch synchronously (the pipe's re-run path after an f32s re-calibration)."""
+        uploaded = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.opt.device)
+        c, s, to_input = self._frame_geometry(int(uploaded.shape[1]), int(uploaded.shape[2]))
+        batch = torch.empty((len(frames), 3, self.opt.input_h, self.opt.input_w), device=self.opt.device,
+                            dtype=torch.float32)
+        self._warp_table(uploaded, to_input, batch)
+        dets = self._run_scale(batch, False).detach().cpu().numpy()
+        if not self.range_ok(batch):    # a clamped f32s value: re-calibrated on this batch, run again
+            dets = self._run_scale(batch, False).detach().cpu().numpy()
+            if not self.range_ok(batch):
+                raise native.NativeError("f32s forward clamps values after re-calibration")
+        return self.results_batch(dets, [self._meta(c, s, None)] * len(frames), 1.0, side=side)
+
+    def results_batch(self, dets, metas, scale, side=None):
+        """Host tail of ``run_frames``: (n, K, 18) host rows, the frames' metas and their (n, 3, 4) matrices
+        (``side``; else each meta's own 'calib') -> per image what ``run(frame, calib)['results']`` returns."""
+        if side is not None:
+            metas = [dict(m, calib=p) for m, p in zip(metas, side)]
+        return ddd_results_batch(dets, metas, self.num_classes, self.opt.peak_thresh)
+
+    # ---- device tail of the frame pipeline (base_detector._FramePipe)
+    def _device_tail_alloc(self, pipe):
+        """Buffers of cn_ddd_post_process_f32 for one pipe, or None when the host tail has to serve it
+        (more rows than the kernel takes, or rows without the (w, h) columns)."""
+        K, nc, B, dev = self.opt.K, self.num_classes, pipe.B, self.opt.device
+        if K > 128 or not self.opt.reg_bbox:
+            return None
+        m = pipe.meta
+        t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+        pinned = lambda shape, dtype: [torch.empty(shape, dtype=dtype).pin_memory() for _ in range(pipe.depth)]
+        return {'to_source': torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev),
+                'rows': torch.empty((B, K, 13), device=dev, dtype=torch.float32),
+                'bounds': torch.empty((B, nc + 1), device=dev, dtype=torch.int32),
+                'kept': torch.empty((B, nc), device=dev, dtype=torch.int32),
+                'rows_host': pinned((B, K, 13), torch.float32),
+                'bounds_host': pinned((B, nc + 1), torch.int32),
+                'kept_host': pinned((B, nc), torch.int32)}
+
+    def _device_tail_run(self, pipe, slot, level, dets):
+        """Raw rows -> lifted rows grouped by class, class bounds and the --peak_thresh prefix per class;
+        image b with matrix b of the slot's uploaded batch of matrices."""
+        t = pipe.tail
+        dets = dets.contiguous()
+        native.check(native.lib().cn_ddd_post_process_f32(
+            native.ptr(dets), pipe.B, self.opt.K, int(dets.shape[2]), self.num_classes, native.ptr(t['to_source']), 0,
+            native.ptr(pipe.side_dev[slot]), float(self.opt.peak_thresh), native.ptr(t['rows']),
+            native.ptr(t['bounds']), native.ptr(t['kept']), native.stream_ptr()), "cn_ddd_post_process_f32")
+
+    def _device_tail_finish(self, pipe, slot):
+        t = pipe.tail
+        for name in ('rows', 'bounds', 'kept'):
+            t[name + '_host'][slot].copy_(t[name], non_blocking=True)
+
+    def _device_tail_results(self, pipe, slot, n, side=None):
+        """Per image ``{class: (n, 13) float32}``: slices of the grouped rows (a copy of the pinned
+        buffer), the empty class a (0,) array as the reference's ``np.array([])``."""
+        t, nc = pipe.tail, self.num_classes
+        rows = t['rows_host'][slot].numpy().copy()        # (the pinned buffer is reused by a later batch)
+        bounds = t['bounds_host'][slot].numpy().tolist()
+        kept = t['kept_host'][slot].numpy().tolist()
+        out = []
+        for i in range(n):
+            r, bd, kp = rows[i], bounds[i], kept[i]
+            out.append({j + 1: r[bd[j]:bd[j] + kp[j]] if bd[j + 1] > bd[j] else np.array([], dtype=np.float32)
+                        for j in range(nc)})
+        return out
 
     def run_batch(self, images, probe=None):
         """New surface (as CtdetDetector.run_batch): a device-resident, normalised batch -> raw

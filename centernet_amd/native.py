@@ -27,6 +27,8 @@ CONV_X_PLAIN, CONV_Y_PLAIN, CONV_R_PLAIN, CONV_STEM_F32S, CONV_STEM_MAXPOOL = 1,
 CONV_STEM_Y_F32S = 32
 MERGE_MAX_ROWS = 2048       # CN_MERGE_MAX_ROWS: S * K rows per image that the merge kernels take
 MERGE_MAX_CLASSES = 1024    # CN_MERGE_MAX_CLASSES
+DECODE_SIGMOID = 1          # CN_DECODE_SIGMOID
+DECODE_DDD_RAW_DEPTH = 16384    # CN_DECODE_DDD_RAW_DEPTH: cn_ddd_decode_f32 transforms the gathered depths
 
 _lib = None
 
@@ -181,6 +183,10 @@ def _declare(lib):
     lib.cn_warp_normalize_u8_f32_batch.argtypes = [vp, i, sz, i, i, i, ctypes.POINTER(ctypes.c_double), i, i,
                                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                                    i, vp, vp]
+    lib.cn_warp_table_u8_f32_batch.restype = i
+    lib.cn_warp_table_u8_f32_batch.argtypes = [vp, i, sz, i, i, i, ctypes.POINTER(ctypes.c_double), i, i, vp, vp, vp]
+    lib.cn_ddd_post_process_f32.restype = i
+    lib.cn_ddd_post_process_f32.argtypes = [vp, i, i, i, i, vp, i, vp, ctypes.c_float, vp, vp, vp, vp]
     lib.cn_ctdet_post_process_f32.restype = i
     lib.cn_ctdet_post_process_f32.argtypes = [vp, i, i, i, vp, i, ctypes.c_float, vp, vp, vp]
     lib.cn_ctdet_merge_f32.restype = i

@@ -163,3 +163,88 @@ def ctdet_results_batch(dets, metas, num_classes, scale=1, max_per_image=100):
         b0 = i * num_classes
         out.append({j + 1: rows[bounds[b0 + j]:bounds[b0 + j + 1]] for j in range(num_classes)})
     return out
+
+
+def ddd_norm_table(mean, std):
+    """(3, 256) float32: ``(level / 255 - mean[c]) / std[c]`` with the ddd class's float32 chain
+    (detectors/ddd.py:45-46) for every uint8 level -- what ``DddDetector.pre_process`` indexes on the
+    host and ``cn_warp_table_u8_f32_batch`` on the device."""
+    levels = np.arange(256, dtype=np.float32).reshape(256, 1, 1) / 255.
+    table = (levels - np.asarray(mean, np.float32).reshape(1, 1, 3)) / np.asarray(std, np.float32).reshape(1, 1, 3)
+    return np.ascontiguousarray(table.reshape(256, 3).T)                     # float32 throughout
+
+
+def ddd_lift_rows(dets, to_source, calibs):
+    """(B, K, 18) raw rows of ``ddd_decode``, the (2, 3) inverse map(s) ((B, 2, 3): one per image) and the
+    (B, 3, 4) float32 matrices -> (B, K, 13) float32 [alpha, x1, y1, x2, y2, h, w, l, x, y, z, rotation_y,
+    score] in the raw row order: ``ddd_post_process_2d`` + ``ddd_post_process_3d`` row by row, as array
+    arithmetic with the reference's types (float64 point map; float32 everything else)."""
+    from .image import apply_affine
+    dets = np.asarray(dets, np.float32)
+    B, K, _ = dets.shape
+    to_source = np.asarray(to_source, np.float64)
+    centre, wh = np.empty((B, K, 2), np.float32), np.empty((B, K, 2), np.float32)
+    if to_source.ndim == 2:
+        centre[:] = apply_affine(dets[:, :, 0:2], to_source).astype(np.float32).reshape(B, K, 2)
+        wh[:] = apply_affine(dets[:, :, 15:17], to_source).astype(np.float32).reshape(B, K, 2)
+    else:
+        for i in range(B):
+            centre[i] = apply_affine(dets[i, :, 0:2], to_source[i]).astype(np.float32)
+            wh[i] = apply_affine(dets[i, :, 15:17], to_source[i]).astype(np.float32)
+    alpha = get_alpha(dets.reshape(B * K, 18)[:, 3:11]).astype(np.float32).reshape(B, K)
+    depth, dims = dets[:, :, 11], dets[:, :, 12:15]
+    P = np.asarray(calibs, np.float32).reshape(B, 1, 3, 4)
+    # unproject_2d_to_3d + "location[1] += h / 2" (ddd_utils.py:68-78, :111)
+    z = depth - P[:, :, 2, 3]
+    x = (centre[:, :, 0] * depth - P[:, :, 0, 3] - P[:, :, 0, 2] * z) / P[:, :, 0, 0]
+    y = (centre[:, :, 1] * depth - P[:, :, 1, 3] - P[:, :, 1, 2] * z) / P[:, :, 1, 1]
+    y = y + dims[:, :, 0] / 2
+    # alpha2rot_y (ddd_utils.py:80-92); np.pi is a weak scalar: float32 comparisons and sums
+    ray = np.arctan2(np.ascontiguousarray(centre[:, :, 0] - P[:, :, 0, 2]),
+                     np.ascontiguousarray(np.broadcast_to(P[:, :, 0, 0], (B, K))))
+    rot_y = alpha + ray
+    rot_y = np.where(rot_y > np.pi, rot_y - 2 * np.pi, rot_y)
+    rot_y = np.where(rot_y < -np.pi, rot_y + 2 * np.pi, rot_y)
+    half_w, half_h = wh[:, :, 0] / 2, wh[:, :, 1] / 2
+    rows = np.stack([alpha, centre[:, :, 0] - half_w, centre[:, :, 1] - half_h, centre[:, :, 0] + half_w,
+                     centre[:, :, 1] + half_h, dims[:, :, 0], dims[:, :, 1], dims[:, :, 2], x, y, z, rot_y,
+                     dets[:, :, 2]], axis=2)
+    assert rows.dtype == np.float32
+    return rows
+
+
+def ddd_results_batch(dets, metas, num_classes, peak_thresh):
+    """Vectorised host tail of the ddd task for a batch: for every image exactly what
+    ``DddDetector.merge_outputs([ddd_post_process(dets[i], c_i, s_i, [calib_i], opt)[0]])`` returns -- same
+    bits, angles included (both are NumPy), same shapes: ``{class: (n, 13) float32}``, a class without rows a
+    ``(0,)`` array, a class whose rows were all cut ``(0, 13)``.  ``metas[i]``: 'c', 's', 'out_width',
+    'out_height' and image i's own 'calib' (the reference lifts a batch with ``calibs[0]``; its detector is
+    single-image).  Rows whose class is no integer in [0, num_classes) match no ``cls == j`` and are dropped."""
+    from .image import get_affine_transform
+    dets = np.asarray(dets, np.float32)
+    if dets.ndim != 3 or dets.shape[2] != 18:
+        raise ValueError("ddd_results_batch needs (B, K, 18) rows: the 3-D stage reads the (w, h) columns "
+                         "(--not_reg_bbox rows have none; the reference cannot lift them either)")
+    B, K, _ = dets.shape
+    maps = {}
+    to_source = np.empty((B, 2, 3), np.float64)
+    for i, m in enumerate(metas):
+        key = (np.asarray(m['c']).tobytes(), np.asarray(m['s']).tobytes(), int(m['out_width']), int(m['out_height']))
+        if key not in maps:
+            maps[key] = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+        to_source[i] = maps[key]
+    calibs = np.stack([np.asarray(m['calib'], np.float32).reshape(3, 4) for m in metas])
+    rows = ddd_lift_rows(dets, to_source[0] if len(maps) == 1 else to_source, calibs)
+    cls = dets[:, :, 17]
+    out = []
+    for i in range(B):
+        per_class = {}
+        for j in range(num_classes):
+            r = rows[i][cls[i] == j]
+            if len(r) == 0:
+                r = np.array([], dtype=np.float32)               # np.array([]) of the 3-D stage: shape (0,)
+            else:
+                r = r[r[:, -1] > peak_thresh]
+            per_class[j + 1] = r
+        out.append(per_class)
+    return out

@@ -580,6 +580,34 @@ int cn_multi_pose_merge_f32(const float *rows, int S, int B, int K, int apply_nm
 int cn_resize_bilinear_u8(const uint8_t *image_hwc, int H, int W, int pitch_bytes, int out_h,
                           int out_w, uint8_t *out_hwc, void *stream);
 
+/* ddd task (detectors/ddd.py:30-54, 75-88).
+ * cn_warp_table_u8_f32_batch: cn_warp_normalize_u8_f32_batch's sampler (same fixed-point warpAffine, zero
+ * border, dst_to_src_2x3 host doubles) with the normalisation taken from a DEVICE table of 3 x 256 floats,
+ * out[n, c, y, x] = table[c][v]: the ddd class normalises with a float32 chain, (u8 / 255 - mean) / std,
+ * and the caller builds the table with exactly those operations.  N frames of one geometry in one launch,
+ * output dense (N, 3, out_h, out_w); no flip form (the task has no flip test). */
+int cn_warp_table_u8_f32_batch(const uint8_t *images_hwc, int N, size_t image_stride_bytes, int H, int W,
+                               int pitch_bytes, const double *dst_to_src_2x3, int out_h, int out_w,
+                               const float *table_3x256, float *out_nchw, void *stream);
+/* ddd_post_process_2d + ddd_post_process_3d + DddDetector.merge_outputs (utils/post_process.py:24-79,
+ * utils/ddd_utils.py:68-114, detectors/ddd.py:82-88) for a batch.  dets (B, K, row_floats): the raw rows of
+ * cn_ddd_decode_f32 with wh, row_floats = 18 (16, the form without wh, -> CN_ERR_UNSUPPORTED: the
+ * reference's 3-D stage cannot process it either; K <= 128, CN_ERR_UNSUPPORTED above).  to_source_2x3 /
+ * per_image as for cn_ctdet_post_process_f32; calibs (B, 3, 4) float32 on the device, image b is lifted with
+ * matrix b.  rows (B, K, 13): [alpha, x1, y1, x2, y2, h, w, l, x, y, z, rotation_y, score], grouped by
+ * class, inside a class in their original order; bounds (B, num_classes + 1) as for ctdet (a class is a
+ * float equal to an integer in [0, num_classes); other rows lie behind the last bound); kept (B,
+ * num_classes): the number of leading rows of each class with score > peak_thresh -- the rows of a class
+ * arrive in descending score order, so merge_outputs' cut is that prefix.
+ * Arithmetic: the reference's types statement by statement (float64 point map for the centre and for the
+ * (w, h) pair, translation included; float32 unproject, box and angle sums; no FMA contraction) and columns
+ * 1..10 and 12 equal the host tail bit for bit.  The two arctan2 (get_alpha, the viewing ray of
+ * alpha2rot_y) are float64 atan2 rounded once to float32: NumPy's float32 arctan2 is within one ulp of
+ * that, so alpha and rotation_y agree with the host to a few 2^-22 (modulo 2 pi at the wrap). */
+int cn_ddd_post_process_f32(const float *dets, int B, int K, int row_floats, int num_classes,
+                            const double *to_source_2x3, int per_image, const float *calibs, float peak_thresh,
+                            float *rows, int32_t *bounds, int32_t *kept, void *stream);
+
 /* The same two operations on the HOST, for callers that keep BaseDetector.pre_process on host
  * cores (DataLoader workers; base_detector.py:37-65): identical integer arithmetic, results
  * equal the device kernels bit for bit.  channels <= 4; dst_to_src_2x3 as above. */
@@ -673,8 +701,13 @@ int cn_gather_feat_f32(const float *feat, const int32_t *inds, float *out, int B
 /* ddd_decode(heat, rot, depth, dim, wh=None, reg=None, K=40) (models/decode.py:426-462):
  * dets (B,K,16) = [xs, ys, score, rot x8, depth, dim x3, cls], or (B,K,18) with wh x2 before
  * cls when wh != NULL.  heat is post-sigmoid unless apply_sigmoid; depth is passed as the
- * caller prepared it (the detector applies 1/(sigmoid(dep)+1e-6)-1 first, detectors/ddd.py:55). */
+ * caller prepared it (the detector applies 1/(sigmoid(dep)+1e-6)-1 first, detectors/ddd.py:55) unless
+ * CN_DECODE_DDD_RAW_DEPTH is set. */
 size_t cn_ddd_decode_workspace_bytes(int B, int C, int H, int W, int K);
+/* Flag bit of cn_ddd_decode_f32's `apply_sigmoid`: `depth` is the head's RAW map and the K gathered values
+ * are transformed here, 1 / (logistic(v) + 1e-6f) - 1 in float32 with the library's logistic, instead of
+ * an element-wise pass over the whole map in front of the call. */
+#define CN_DECODE_DDD_RAW_DEPTH 16384
 int cn_ddd_decode_f32(const float *heat, const float *rot, const float *depth, const float *dim,
                       const float *wh, const float *reg, int B, int C, int H, int W, int K,
                       int apply_sigmoid, float *dets, void *workspace, size_t workspace_bytes,
