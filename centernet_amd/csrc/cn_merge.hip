@@ -2,7 +2,9 @@
 // reference ctdet.py:58-73), bit for bit.  Input: the device tail's output of every test scale
 // (cn_ctdet_post_process_f32 into slice s of rows (S, B, K, 5) / bounds (S, B, nc + 1)).  Output in the
 // tail's own format, so the host slices it as it slices a single scale.  Behind it the multi_pose scale
-// merge (multi_pose_merge_kernel): the same soft-NMS routine on 39-column rows, one segment per image.
+// merge (multi_pose_merge_kernel): the same soft-NMS routine on 39-column rows, one segment per image.  And the
+// exdet tail: exdet_post_kernel (post_process + the positive-score filter + a stable class grouping of up to
+// MG_ROWS rows) in front of the same merge kernel with the row cap checked per image (class_merge_kernel<true>).
 //
 // One workgroup of four waves per image; the image's rows (<= CN_MERGE_MAX_ROWS) live in LDS.
 //   1. per class, the rows of all scales in scale order (the np.concatenate of merge_outputs);
@@ -192,15 +194,21 @@ __device__ void soft_nms_segment(NmsLds &L, int o, int n, int lane, int16_t *jsr
     }
 }
 
-__global__ __launch_bounds__(MG_THREADS) void ctdet_merge_kernel(const float *__restrict__ rows,
+// CHECKED (exdet): the row cap holds for the rows that are present, not for S * K -- an image with more than
+// MG_ROWS rows over all scales is not merged, status[b] says so and its bounds are zero (status is unused
+// without CHECKED: the ctdet entry refuses S * K > MG_ROWS before the launch).
+template <bool CHECKED>
+__global__ __launch_bounds__(MG_THREADS) void class_merge_kernel(const float *__restrict__ rows,
                                                                  const int32_t *__restrict__ bounds, int S, int B,
                                                                  int K, int nc, int do_nms, int max_per_image,
                                                                  float *__restrict__ out_rows,
-                                                                 int32_t *__restrict__ out_bounds)
+                                                                 int32_t *__restrict__ out_bounds,
+                                                                 int32_t *__restrict__ status)
 {
     __shared__ MergeLds L;
     const int b = blockIdx.x, t = threadIdx.x, lane = t & (CN_WAVE - 1), w = t / CN_WAVE;
     const size_t bstride = (size_t)nc + 1;
+    const int cap = min(S * K, MG_ROWS);          // rows of one image in out_rows
     // 1. merged class segments: class c starts behind every row of classes < c of every scale
     for (int c = t; c <= nc; c += MG_THREADS) {
         int n = 0;
@@ -208,7 +216,15 @@ __global__ __launch_bounds__(MG_THREADS) void ctdet_merge_kernel(const float *__
         L.seg[c] = n;
     }
     __syncthreads();
-    const int total = min(L.seg[nc], S * K);
+    if (CHECKED) {
+        const bool over = L.seg[nc] > cap;        // the same word for every thread: the whole workgroup leaves
+        if (t == 0) status[b] = over ? 1 : 0;
+        if (over) {
+            for (int c = t; c <= nc; c += MG_THREADS) out_bounds[(size_t)b * bstride + c] = 0;
+            return;
+        }
+    }
+    const int total = min(L.seg[nc], cap);
     for (int e = t; e < S * K; e += MG_THREADS) {
         const int s = e / K, r = e - s * K;
         const int32_t *bd = bounds + ((size_t)s * B + b) * bstride;
@@ -270,7 +286,7 @@ __global__ __launch_bounds__(MG_THREADS) void ctdet_merge_kernel(const float *__
     int kept = 0;
     for (int k = 0; k < MG_WAVES; ++k) kept += L.red[k];
     int *prefix = reinterpret_cast<int *>(L.ns);
-    float *ob = out_rows + (size_t)b * S * K * 5;
+    float *ob = out_rows + (size_t)b * cap * 5;
     for (int r = r0; r < r1; ++r) {
         prefix[r] = run;
         if (!cut || L.sc[r] >= thresh) {
@@ -331,6 +347,118 @@ __global__ __launch_bounds__(MG_THREADS) void multi_pose_merge_kernel(const floa
         ob[e] = v;
     }
 }
+
+// ExdetDetector.post_process + the `score > 0` filter and the per-class selection of merge_outputs
+// (detectors/exdet.py:51-74; reference exdet.py:86-110) for one test scale: one workgroup per frame, the
+// frame's R <= MG_ROWS raw rows [x1, y1, x2, y2, score, 8 extreme-point coordinates, class] -> rows
+// [x1, y1, x2, y2, score] in source pixels / scale, grouped by class and inside a class in input order.
+// The grouping is a stable counting sort.  Every wave owns a contiguous quarter of the rows:
+//   1. class of every row (PX_NONE: not kept), a class histogram per wave (LDS atomics: counts only);
+//   2. exclusive scan of the class totals = the bounds; hist[w][c] becomes the position of wave w's first
+//      row of class c, i.e. bounds[c] + the counts of the waves in front of it;
+//   3. every wave walks its rows 64 at a time in input order; the rows of a step that share a class are
+//      found by ballot, take positions hist[w][c] + (rank among them by lane) and move hist[w][c] on.
+//      hist[w][.] is touched by wave w alone from here on: wave_sync() orders it, no workgroup barrier.
+constexpr int PX_ROW = 14;
+constexpr int16_t PX_NONE = -1;
+struct ExdetPostLds {
+    int hist[MG_WAVES][MG_CLASSES + 1];
+    int16_t cls[MG_ROWS];
+    int red[MG_WAVES];
+};
+__global__ __launch_bounds__(MG_THREADS) void exdet_post_kernel(const float *__restrict__ dets, int R, int nc,
+                                                                float out_w, const double *__restrict__ to_source,
+                                                                int per_image, float scale,
+                                                                float *__restrict__ rows,
+                                                                int32_t *__restrict__ bounds)
+{
+#pragma clang fp contract(off)
+    __shared__ ExdetPostLds L;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & (CN_WAVE - 1), w = t / CN_WAVE;
+    const float *in = dets + (size_t)b * R * PX_ROW;
+    float *out = rows + (size_t)b * R * 5;
+    const double *tr = to_source + (per_image ? (size_t)b * 6 : 0);
+    const double t0 = tr[0], t1 = tr[1], t2 = tr[2], t3 = tr[3], t4 = tr[4], t5 = tr[5];
+    // rows of wave w: [w0, w1), whole steps of 64
+    const int per = (R + MG_THREADS - 1) / MG_THREADS * CN_WAVE;
+    const int w0 = min(w * per, R), w1 = min(w0 + per, R);
+    for (int c = t; c < MG_WAVES * (MG_CLASSES + 1); c += MG_THREADS) (&L.hist[0][0])[c] = 0;
+    __syncthreads();
+    // 1. classes and the histograms
+    for (int r = w0 + lane; r < w1; r += CN_WAVE) {
+        const float score = in[(size_t)r * PX_ROW + 4], cf = in[(size_t)r * PX_ROW + 13];
+        int16_t c = PX_NONE;
+        if (score > 0.f && cf >= 0.f && cf < (float)nc) {      // (a NaN fails every comparison)
+            const int ci = (int)cf;
+            if ((float)ci == cf) c = (int16_t)ci;              // `classes == j`: an integer value only
+        }
+        L.cls[r] = c;
+        if (c != PX_NONE) atomicAdd(&L.hist[w][c], 1);
+    }
+    __syncthreads();
+    // 2. bounds: exclusive scan of the class totals, a chunk of classes per thread
+    const int cper = (nc + MG_THREADS) / MG_THREADS, c0 = min(t * cper, nc), c1 = min(c0 + cper, nc);
+    int n = 0;
+    for (int c = c0; c < c1; ++c)
+        for (int k = 0; k < MG_WAVES; ++k) n += L.hist[k][c];
+    int incl = n;
+    for (int o = 1; o < CN_WAVE; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == CN_WAVE - 1) L.red[w] = incl;
+    __syncthreads();
+    int run = incl - n, total = 0;
+    for (int k = 0; k < MG_WAVES; ++k) {
+        if (k < w) run += L.red[k];
+        total += L.red[k];
+    }
+    for (int c = c0; c < c1; ++c) {
+        bounds[(size_t)b * (nc + 1) + c] = run;
+        for (int k = 0; k < MG_WAVES; ++k) {
+            const int h = L.hist[k][c];
+            L.hist[k][c] = run;
+            run += h;
+        }
+    }
+    if (t == 0) bounds[(size_t)b * (nc + 1) + nc] = total;
+    __syncthreads();
+    // 3. positions, the arithmetic of post_process, the rows
+    int *cur = L.hist[w];
+    for (int base = w0; base < w1; base += CN_WAVE) {
+        const int r = base + lane;
+        const int c = r < w1 ? (int)L.cls[r] : (int)PX_NONE;
+        int pos = -1;
+        unsigned long long todo = __ballot(c != PX_NONE);
+        while (todo) {                                          // wave-uniform: one class of the step per turn
+            const int leader = __builtin_ctzll(todo);
+            const int cl = __shfl(c, leader);
+            const unsigned long long m = __ballot(c == cl);
+            if (c == cl) pos = cur[cl] + __popcll(m & ((1ull << lane) - 1ull));
+            wave_sync();
+            if (lane == leader) cur[cl] += __popcll(m);
+            wave_sync();
+            todo &= ~m;
+        }
+        if (pos < 0 || pos >= R) continue;
+        const float *d = in + (size_t)r * PX_ROW;
+        float x1 = d[0], x2 = d[2];
+        const float y1 = d[1], y2 = d[3];
+        if (r >= R / 2) {                                       // the mirror image's half (exdet.py:87-91)
+            const float l = x1;
+            x1 = out_w - x2;
+            x2 = out_w - l;
+        }
+        float *o = out + (size_t)pos * 5;
+        o[0] = (float)(((double)x1 * t0 + (double)y1 * t1) + t2) / scale;
+        o[1] = (float)(((double)x1 * t3 + (double)y1 * t4) + t5) / scale;
+        o[2] = (float)(((double)x2 * t0 + (double)y2 * t1) + t2) / scale;
+        o[3] = (float)(((double)x2 * t3 + (double)y2 * t4) + t5) / scale;
+        o[4] = d[4];
+    }
+    // rows behind the last bound: zeros, so that the array is a function of the input
+    for (int e = total * 5 + t; e < R * 5; e += MG_THREADS) out[e] = 0.f;
+}
 }  // namespace
 
 extern "C" int cn_multi_pose_merge_f32(const float *rows, int S, int B, int K, int apply_nms, float *out_rows,
@@ -352,8 +480,36 @@ extern "C" int cn_ctdet_merge_f32(const float *rows, const int32_t *bounds, int 
     if (!rows || !bounds || !out_rows || !out_bounds) return CN_ERR_NULL;
     if (S <= 0 || B <= 0 || K <= 0 || num_classes <= 0 || max_per_image <= 0) return CN_ERR_SHAPE;
     if ((long long)S * K > CN_MERGE_MAX_ROWS || num_classes > CN_MERGE_MAX_CLASSES) return CN_ERR_SHAPE;
-    hipLaunchKernelGGL(ctdet_merge_kernel, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, rows, bounds, S, B,
-                       K, num_classes, (S > 1 || apply_nms) ? 1 : 0, max_per_image, out_rows, out_bounds);
+    hipLaunchKernelGGL(class_merge_kernel<false>, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, rows, bounds,
+                       S, B, K, num_classes, (S > 1 || apply_nms) ? 1 : 0, max_per_image, out_rows, out_bounds,
+                       (int32_t *)nullptr);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_exdet_post_process_f32(const float *dets, int B, int R, int num_classes, int out_width,
+                                         const double *to_source_2x3, int per_image, float scale, float *rows,
+                                         int32_t *bounds, void *stream)
+{
+    if (!dets || !to_source_2x3 || !rows || !bounds) return CN_ERR_NULL;
+    if (B <= 0 || R <= 0 || (R & 1) || num_classes <= 0 || out_width <= 0 || !(scale > 0.f)) return CN_ERR_SHAPE;
+    if (R > CN_MERGE_MAX_ROWS || num_classes > CN_MERGE_MAX_CLASSES) return CN_ERR_SHAPE;
+    hipLaunchKernelGGL(exdet_post_kernel, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, dets, R, num_classes,
+                       (float)out_width, to_source_2x3, per_image ? 1 : 0, scale, rows, bounds);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_exdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int R, int num_classes,
+                                  int max_per_image, float *out_rows, int32_t *out_bounds, int32_t *status,
+                                  void *stream)
+{
+    if (!rows || !bounds || !out_rows || !out_bounds || !status) return CN_ERR_NULL;
+    if (S <= 0 || B <= 0 || R <= 0 || (R & 1) || num_classes <= 0 || max_per_image <= 0) return CN_ERR_SHAPE;
+    if (R > CN_MERGE_MAX_ROWS || num_classes > CN_MERGE_MAX_CLASSES) return CN_ERR_SHAPE;
+    if ((long long)S * R > (1 << 24)) return CN_ERR_SHAPE;        // (S * R is an int inside the kernel)
+    hipLaunchKernelGGL(class_merge_kernel<true>, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, rows, bounds, S,
+                       B, R, num_classes, 1, max_per_image, out_rows, out_bounds, status);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

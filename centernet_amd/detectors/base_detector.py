@@ -60,11 +60,15 @@ class _FramePipe(object):
     affine + class grouping; multi_pose: ``cn_multi_pose_post_process_f32``, inverse affine of the
     box corners and joints; into the scale's slice), then the scale merge (``cn_ctdet_merge_f32``:
     soft-NMS and the top-100 cut; ``cn_multi_pose_merge_f32``: soft-NMS of the 39-column rows, no
-    cut; when there are several scales or --nms) and the copies of the rows / class bounds / f32s
+    cut; when there are several scales or --nms; exdet: ``cn_exdet_post_process_f32`` +
+    ``cn_exdet_merge_f32``, always) and the copies of the rows / class bounds / f32s
     range digests into pinned memory -- is enqueued on the launch stream without a single host
     synchronisation.  The host waits for batch i - depth + 1 only when it collects it, i.e. while
-    later batches are on the device.  Tasks without the ``_device_tail_*`` hooks (exdet), and
-    shapes their kernels do not take, copy the raw detections out and keep the host tail.
+    later batches are on the device.  Shapes the tail kernels do not take (``_device_tail_alloc``
+    returns None) copy the raw detections out and keep the host tail; a tail can also hand ONE batch
+    back when only the batch's own data tell that it does not fit (``_device_tail_results`` returns
+    None: exdet, more positive rows in a frame than the merge kernel holds) -- ``collect`` then drains
+    the device, runs that batch through ``_run_frames_sync`` and counts it in ``det.tail_fallbacks``.
 
     Two more task hooks keep the pipe free of task geometry: ``_pipe_level`` (input geometry, frame ->
     input map and meta of one test scale) and ``_pipe_pre_process`` (the batched pre-process launch).
@@ -195,7 +199,14 @@ class _FramePipe(object):
             return det._run_frames_sync(frames, self.scales, **kw)
         n = len(frames)
         if self.tail is not None:
-            return det._device_tail_results(self, slot, n, **kw)
+            results = det._device_tail_results(self, slot, n, **kw)
+            if results is not None:
+                return results
+            # the batch does not fit the task's device tail (exdet: a frame with more positive rows than
+            # the merge kernel holds): drain the device and run this batch again synchronously, host tail
+            torch.cuda.synchronize()
+            det.tail_fallbacks += 1
+            return det._run_frames_sync(frames, self.scales, **kw)
         if not self.merge:
             return det.results_batch(self.dets_host[slot][0].numpy()[:n], [self.meta] * n, self.scale, **kw)
         return det._results_merged([(d.numpy()[:n], [lv.meta] * n, lv.scale)
@@ -222,6 +233,7 @@ class BaseDetector(object):
         self.num_classes = opt.num_classes
         self.max_per_image = 100
         self.pause = True
+        self.tail_fallbacks = 0      # batches of the frame pipe that its device tail handed back to the host
 
     # ------------------------------------------------------------------ input geometry
     def input_geometry(self, height, width, scale):
@@ -437,9 +449,9 @@ class BaseDetector(object):
         The reference's test loop is batch_size = 1 (test.py:60-62); here the frames are uploaded as
         ONE uint8 copy, pre-processed on the device in one launch per test scale straight into one
         batch tensor (with flip-test: frame, mirror, frame, mirror, ...), each scale's batch goes
-        through the network + flip average + decode once and, for ctdet and multi_pose, through the
-        device tail (inverse affine; ctdet: + class grouping) and the device scale merge; the host
-        slices the result.
+        through the network + flip average + decode once and through the task's device tail (inverse
+        affine; ctdet, exdet: + class grouping) and the device scale merge (exdet: always, and there
+        is no flip average -- the mirror image's rows are rows); the host slices the result.
         ``arrays=True``: a task whose rows are nested lists (multi_pose: ``{1: [[39 floats], ...]}``)
         returns them as a float32 array (``{1: (n, 39) ndarray}``, the same bits, a copy of its own)
         and saves the ``.tolist()``.  ctdet returns arrays either way."""

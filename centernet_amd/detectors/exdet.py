@@ -11,14 +11,18 @@ Two things the reference's class does are kept as they are, because they ARE its
 * only the box corners go through the inverse affine; the eight extreme-point coordinates of a row
   stay in output-grid units (exdet.py:92-96) and are dropped by ``merge_outputs``.
 One thing differs: the reference's ``merge_outputs`` calls ``soft_nms`` without importing it
-(exdet.py:110 -- a NameError as shipped); here it is the library's (external/nms.pyx:77-170)."""
+(exdet.py:110 -- a NameError as shipped); here it is the library's (external/nms.pyx:77-170).
+New surface: ``run_batch`` (device-resident batches) and ``run_frames`` / ``run_frames_stream`` with the
+task's tail on the device (``cn_exdet_post_process_f32`` + ``cn_exdet_merge_f32``)."""
 import time
 
 import numpy as np
 import torch
 
 from ..decode import agnex_ct_decode, exct_decode
-from ..image import transform_preds
+from .. import native
+from ..image import get_affine_transform, transform_preds
+from ..post_process import exdet_post_batch, exdet_results_batch
 from ..soft_nms import soft_nms
 from .base_detector import BaseDetector
 
@@ -80,5 +84,100 @@ class ExdetDetector(BaseDetector):
                 results[j] = results[j][results[j][:, -1] >= thresh]
         return results
 
-    def _pipe_for(self, frames, depth):
-        raise NotImplementedError("run_frames / run_frames_stream: not built for the exdet task; use run(frame)")
+    # ------------------------------------------------------------------ new surface
+    def run_batch(self, images):
+        """``images`` (N, 3, H, W) fp32, already normalised, on the device -> raw (N, 1000, 14) rows of the
+        decode in output-grid units (device tensor); the five maps are left post-sigmoid, as ``process``
+        leaves them.  Asynchronous, as ``CtdetDetector.run_batch``: nothing here waits for the device, the
+        caller owes a ``range_ok()`` where it consumes the rows."""
+        self._note_unchecked_forward()
+        with torch.no_grad():
+            output = self.model(images, borrow=True)[-1]
+            heats = [output[n].sigmoid_() for n in EDGE_MAPS]
+            offsets = [output[n] for n in EDGE_OFFSETS] if self.opt.reg_offset else []
+            return self.decode(*(heats + offsets), K=self.opt.K, scores_thresh=self.opt.scores_thresh,
+                               center_thresh=self.opt.center_thresh, aggr_weight=self.opt.aggr_weight)
+
+    def _run_scale(self, images, flip):
+        """One test scale of the frame pipeline: ``run_batch``, the rows seen per FRAME -- (B, R, 14) with
+        R = 2000 under ``flip`` ((2B, 3, H, W) frame / mirror pairs: a frame's rows, then its mirror
+        image's, the ``reshape(2, -1, 14)`` of ``post_process``) and 1000 without.  This task has no flip
+        average: the mirror image's rows are rows."""
+        dets = self.run_batch(images)
+        return dets.view(-1, (2 if flip else 1) * dets.shape[1], dets.shape[2])
+
+    # ---- host tail of the frame pipeline: the fallback, and the comparison side of the device tail
+    def results_batch(self, dets, metas, scale):
+        """(n, R, 14) host rows of one test scale -> per frame ``{class: (n, 5) float32}``."""
+        return exdet_results_batch([(dets, metas, scale)], self.num_classes, self.max_per_image)
+
+    def _post_batch(self, dets, metas, scale):
+        """``post_process`` of every frame of a (n, R, 14) host array: a list of (R, 14) arrays."""
+        return list(exdet_post_batch(dets, metas, scale))
+
+    # ---- device tail of the frame pipeline (base_detector._FramePipe)
+    def _device_tail_alloc(self, pipe):
+        """Buffers of cn_exdet_post_process_f32 (one slice per test scale) and cn_exdet_merge_f32 for one
+        pipe, or None (host tail) for more classes than the kernels take.  The row cap is not decided here:
+        it holds for the rows with a positive score, which only the batch itself tells (``status``)."""
+        nc, B, dev, S = self.num_classes, pipe.B, self.opt.device, len(pipe.scales)
+        if nc > native.MERGE_MAX_CLASSES:
+            return None
+        R = (2 if pipe.flip else 1) * 1000          # (num_dets of exct_decode / agnex_ct_decode)
+        cap = min(S * R, native.MERGE_MAX_ROWS)
+        to_source = []
+        for lv in pipe.levels:
+            m = lv.meta
+            t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+            to_source.append(torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev))
+        pinned = lambda shape, dtype: [torch.empty(shape, dtype=dtype).pin_memory() for _ in range(pipe.depth)]
+        return {'R': R, 'to_source': to_source,
+                'rows': torch.empty((S, B, R, 5), device=dev, dtype=torch.float32),
+                'bounds': torch.empty((S, B, nc + 1), device=dev, dtype=torch.int32),
+                'merged_rows': torch.empty((B, cap, 5), device=dev, dtype=torch.float32),
+                'merged_bounds': torch.empty((B, nc + 1), device=dev, dtype=torch.int32),
+                'status': torch.empty((B,), device=dev, dtype=torch.int32),
+                'rows_host': pinned((B, cap, 5), torch.float32),
+                'bounds_host': pinned((B, nc + 1), torch.int32),
+                'status_host': pinned((B,), torch.int32)}
+
+    def _device_tail_run(self, pipe, slot, level, dets):
+        """Test scale ``level``: raw rows -> un-mirrored, in source pixels / scale, positive scores only,
+        grouped by class, into slice ``level`` of the tail's rows / bounds."""
+        t, lv = pipe.tail, pipe.levels[level]
+        dets = dets.contiguous()
+        if tuple(dets.shape) != (pipe.B, t['R'], 14):
+            raise native.NativeError("exdet tail: rows of shape %s, expected %s"
+                                     % (tuple(dets.shape), (pipe.B, t['R'], 14)))
+        native.check(native.lib().cn_exdet_post_process_f32(
+            native.ptr(dets), pipe.B, t['R'], self.num_classes, int(lv.meta['out_width']),
+            native.ptr(t['to_source'][level]), 0, float(lv.scale), native.ptr(t['rows'][level]),
+            native.ptr(t['bounds'][level]), native.stream_ptr()), "cn_exdet_post_process_f32")
+
+    def _device_tail_finish(self, pipe, slot):
+        """After the last test scale: the merge -- always, whatever ``pipe.merge`` says: soft-NMS and the
+        cut are this task's ``merge_outputs`` for one scale too -- then the copies into the slot's pinned
+        buffers."""
+        t = pipe.tail
+        native.check(native.lib().cn_exdet_merge_f32(
+            native.ptr(t['rows']), native.ptr(t['bounds']), len(pipe.scales), pipe.B, t['R'], self.num_classes,
+            self.max_per_image, native.ptr(t['merged_rows']), native.ptr(t['merged_bounds']),
+            native.ptr(t['status']), native.stream_ptr()), "cn_exdet_merge_f32")
+        t['rows_host'][slot].copy_(t['merged_rows'], non_blocking=True)
+        t['bounds_host'][slot].copy_(t['merged_bounds'], non_blocking=True)
+        t['status_host'][slot].copy_(t['status'], non_blocking=True)
+
+    def _device_tail_results(self, pipe, slot, n):
+        """Per frame ``{class: (n, 5) float32}``, slices of a copy of the merged rows -- or None when a
+        frame of the batch had more positive rows than the merge kernel holds: the pipe then runs the
+        batch through the host tail."""
+        t, nc = pipe.tail, self.num_classes
+        if t['status_host'][slot].numpy().any():
+            return None
+        rows = t['rows_host'][slot].numpy().copy()        # (the pinned buffer is reused by a later batch)
+        bounds = t['bounds_host'][slot].numpy().tolist()
+        out = []
+        for i in range(n):
+            r, bd = rows[i], bounds[i]
+            out.append({j + 1: r[bd[j]:bd[j + 1]] for j in range(nc)})
+        return out

@@ -191,6 +191,10 @@ def _declare(lib):
     lib.cn_ctdet_post_process_f32.argtypes = [vp, i, i, i, vp, i, ctypes.c_float, vp, vp, vp]
     lib.cn_ctdet_merge_f32.restype = i
     lib.cn_ctdet_merge_f32.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp]
+    lib.cn_exdet_post_process_f32.restype = i
+    lib.cn_exdet_post_process_f32.argtypes = [vp, i, i, i, i, vp, i, ctypes.c_float, vp, vp, vp]
+    lib.cn_exdet_merge_f32.restype = i
+    lib.cn_exdet_merge_f32.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.cn_multi_pose_post_process_f32.restype = i
     lib.cn_multi_pose_post_process_f32.argtypes = [vp, i, i, vp, i, ctypes.c_float, vp, vp]
     lib.cn_multi_pose_merge_f32.restype = i

@@ -248,3 +248,65 @@ def ddd_results_batch(dets, metas, num_classes, peak_thresh):
             per_class[j + 1] = r
         out.append(per_class)
     return out
+
+
+def exdet_post_batch(dets, metas, scale=1):
+    """``ExdetDetector.post_process`` of every frame of a host batch: (n, R, 14) raw rows -- R = the frame's
+    decode rows and, with flip-test, its mirror image's behind them -> (n, R, 14) float32, a copy: the
+    second half of every frame's rows un-mirrored (``x1' = out_w - x2``, ``x2' = out_w - x1`` in float32),
+    both box corners through the float64 inverse map and rounded once to float32, then ``/ scale`` in
+    float32.  Frames that share their geometry go through one inverse map together."""
+    from .image import apply_affine, get_affine_transform
+    rows = np.array(dets, dtype=np.float32)
+    n, R, _ = rows.shape
+    half = R // 2
+    groups = {}
+    for i, m in enumerate(metas):
+        key = (np.asarray(m['c'], np.float32).tobytes(), np.asarray(m['s'], np.float32).tobytes(),
+               int(m['out_width']), int(m['out_height']))
+        groups.setdefault(key, []).append(i)
+    for idx in groups.values():
+        m = metas[idx[0]]
+        sel = idx if len(idx) < n else slice(None)
+        out_w = m['out_width']
+        left, right = rows[sel, half:, 0].copy(), rows[sel, half:, 2].copy()
+        rows[sel, half:, 0], rows[sel, half:, 2] = out_w - right, out_w - left
+        to_source = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+        pts = rows[sel, :, 0:4].reshape(-1, 2)
+        rows[sel, :, 0:4] = apply_affine(pts, to_source).astype(np.float32).reshape(-1, R, 4)
+    rows[:, :, 0:4] /= scale
+    return rows
+
+
+def exdet_merge_rows(rows, num_classes, max_per_image=100):
+    """``ExdetDetector.merge_outputs`` of one frame, (N, 14) post-processed rows of all its test scales in
+    scale order -> ``{class: (n, 5) float32}``: one stable sort instead of ``num_classes`` boolean masks,
+    soft-NMS only where a class has two rows or more (it does nothing to fewer), the same bits."""
+    from .soft_nms import soft_nms
+    score, cls = rows[:, 4], rows[:, 13]
+    with np.errstate(invalid='ignore'):
+        keep = (score > 0) & (cls >= 0) & (cls < num_classes) & (cls == np.floor(cls))    # `classes == j`
+    kept = rows[keep]
+    cls = kept[:, 13].astype(np.int64)
+    order = np.argsort(cls, kind='stable')
+    boxes = np.ascontiguousarray(kept[order][:, 0:5])
+    edges = np.searchsorted(cls[order], np.arange(num_classes + 1)).tolist()
+    for j in range(num_classes):
+        if edges[j + 1] - edges[j] > 1:
+            soft_nms(boxes[edges[j]:edges[j + 1]], Nt=0.5, method=2)       # in place, on the class's slice
+    results = {j + 1: boxes[edges[j]:edges[j + 1]] for j in range(num_classes)}
+    if len(boxes) > max_per_image:
+        kth = len(boxes) - max_per_image
+        thresh = np.partition(boxes[:, 4], kth)[kth]
+        results = {j: r[r[:, 4] >= thresh] for j, r in results.items()}
+    return results
+
+
+def exdet_results_batch(per_scale, num_classes, max_per_image=100):
+    """Vectorised host tail of the exdet task for a batch.  ``per_scale``: [(raw rows (n, R, 14), the frames'
+    metas, scale)] in test-scale order -> for every frame exactly what ``merge_outputs([post_process(...)
+    per scale])`` returns (detectors/exdet.py:51-81), bit for bit.  Post-process AND merge: this task merges
+    always (soft-NMS of every class and the ``max_per_image`` cut, one scale or several)."""
+    posts = [exdet_post_batch(d, metas, scale) for d, metas, scale in per_scale]
+    return [exdet_merge_rows(np.concatenate([p[i] for p in posts], axis=0), num_classes, max_per_image)
+            for i in range(posts[0].shape[0])]

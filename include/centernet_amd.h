@@ -559,6 +559,32 @@ int cn_ctdet_post_process_f32(const float *dets, int B, int K, int num_classes, 
 #define CN_MERGE_MAX_CLASSES 1024
 int cn_ctdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int K, int num_classes,
                        int apply_nms, int max_per_image, float *out_rows, int32_t *out_bounds, void *stream);
+/* exdet task, the device tail of its frame pipe (detectors/exdet.py:51-81; reference exdet.py:86-123).
+ * cn_exdet_post_process_f32: ExdetDetector.post_process, the `score > 0` filter and the per-class selection of
+ * merge_outputs for one test scale of a batch.  dets (B, R, 14): the raw rows of cn_exct_decode_f32 /
+ * cn_agnex_ct_decode_f32 [x1, y1, x2, y2, score, 8 extreme-point coordinates, class] of every FRAME -- R = 2000
+ * with flip-test (the frame's 1000 rows, then its mirror image's: the reshape(2, -1, 14) of the reference),
+ * 1000 without; R even, R <= CN_MERGE_MAX_ROWS, num_classes <= CN_MERGE_MAX_CLASSES, CN_ERR_SHAPE otherwise.
+ * Per frame: the second half of the rows gets x1' = out_width - x2, x2' = out_width - x1 in float32 (without
+ * flip-test too, as the reference does); both corners go through to_source_2x3 (float32 point -> float64
+ * (t0*x + t1*y) + t2 -> float32; to_source_2x3 / per_image as for cn_ctdet_post_process_f32), then / scale
+ * (> 0) in float32.  rows (B, R, 5): [x1, y1, x2, y2, score] of the rows with score > 0 whose class column
+ * equals an integer in [0, num_classes) -- NaN scores and every other class value drop out -- grouped by
+ * class, inside a class in input order (a stable sort: soft-NMS depends on the order); rows behind the last
+ * bound are zero.  bounds (B, num_classes + 1) as for ctdet.  Bit-identical to the host tail.
+ * cn_exdet_merge_f32: the rest of merge_outputs.  rows (S, B, R, 5) / bounds (S, B, num_classes + 1): the
+ * entry above, test scale s in slice s.  Per frame: per class the rows of all scales in scale order, Gaussian
+ * soft-NMS of every class ALWAYS (sigma 0.5, threshold 0.001; the task has no --nms condition; the whole
+ * in-place array kept, as cn_ctdet_merge_f32 keeps it), then the max_per_image cut with ties kept.
+ * out_rows (B, min(S*R, CN_MERGE_MAX_ROWS), 5) / out_bounds (B, num_classes + 1).  The row cap holds for the
+ * rows that are present, S*R may be anything: a frame with more than CN_MERGE_MAX_ROWS rows over all scales
+ * is not merged -- status[b] != 0, its bounds all zero, its rows undefined; every other frame has status[b]
+ * == 0 and its result.  status (B) int32. */
+int cn_exdet_post_process_f32(const float *dets, int B, int R, int num_classes, int out_width,
+                              const double *to_source_2x3, int per_image, float scale, float *rows,
+                              int32_t *bounds, void *stream);
+int cn_exdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int R, int num_classes,
+                       int max_per_image, float *out_rows, int32_t *out_bounds, int32_t *status, void *stream);
 /* multi_pose_post_process + the "/ scale" of MultiPoseDetector.post_process (utils/post_process.py:103-114,
  * detectors/multi_pose.py:62-72) on the device.  dets (B, K, 40): multi_pose_decode rows [x1, y1, x2, y2,
  * score, 17 x (x, y), class] in output-grid units (K <= 128, CN_ERR_UNSUPPORTED above); to_source_2x3,
