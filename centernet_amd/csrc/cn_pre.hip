@@ -352,127 +352,11 @@ extern "C" int cn_resize_linear_u8_host(const uint8_t *img, int h_in, int w_in, 
 
 
 // ---------------------------------------------------------------------------
-// ctdet_post_process + the per-class split on the device (utils/post_process.py:83-100,
-// utils/image.py:19-24,63-66, detectors/ctdet.py:47-56), so that the host tail of a batch is one small
-// copy and 80 slices per image: for every image the K raw detections [x1, y1, x2, y2, score, class]
-// in output-grid units become rows [x1, y1, x2, y2, score] in source-frame pixels, grouped by class
-// (ascending; inside a class in their original, score-descending order: a stable sort), plus the
-// class boundaries.  Arithmetic as the reference's: float32 point -> float64 (t0*x + t1*y) + t2 ->
-// float32, then / scale in float32; rows whose class lies outside [0, num_classes) are dropped
-// (they match no `classes == j`).
-// ---------------------------------------------------------------------------
-namespace {
-constexpr int PP_KMAX = 128;
-__global__ __launch_bounds__(PP_KMAX) void ctdet_post_kernel(const float *__restrict__ dets, int K, int num_classes,
-                                                             const double *__restrict__ to_source, int per_image,
-                                                             float scale, float *__restrict__ rows,
-                                                             int32_t *__restrict__ bounds)
-{
-    __shared__ int cls_s[PP_KMAX];
-    const int b = blockIdx.x, k = threadIdx.x;
-    const double *t = to_source + (per_image ? (size_t)b * 6 : 0);
-    float r[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    int cls = num_classes;             // sorts behind every class
-    if (k < K) {
-        const float *d = dets + ((size_t)b * K + k) * 6;
-        const int c = (int)(long long)d[5];        // astype(np.int64): truncation
-        if (c >= 0 && c < num_classes) cls = c;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const double x = (double)d[2 * p], y = (double)d[2 * p + 1];
-            const double sx = (x * t[0] + y * t[1]) + t[2];
-            const double sy = (x * t[3] + y * t[4]) + t[5];
-            r[2 * p] = (float)sx / scale;
-            r[2 * p + 1] = (float)sy / scale;
-        }
-        r[4] = d[4];
-    }
-    cls_s[k] = cls;
-    __syncthreads();
-    if (k < K) {
-        int rank = 0;
-        for (int j = 0; j < K; ++j) rank += (cls_s[j] < cls || (cls_s[j] == cls && j < k)) ? 1 : 0;
-        float *o = rows + ((size_t)b * K + rank) * 5;
-#pragma unroll
-        for (int e = 0; e < 5; ++e) o[e] = r[e];
-    }
-    for (int c = k; c <= num_classes; c += PP_KMAX) {
-        int n = 0;
-        for (int j = 0; j < K; ++j) n += cls_s[j] < c ? 1 : 0;
-        bounds[(size_t)b * (num_classes + 1) + c] = n;
-    }
-}
-}  // namespace
-
-extern "C" int cn_ctdet_post_process_f32(const float *dets, int B, int K, int num_classes,
-                                         const double *to_source_2x3, int per_image, float scale,
-                                         float *rows, int32_t *bounds, void *stream)
-{
-    if (!dets || !to_source_2x3 || !rows || !bounds) return CN_ERR_NULL;
-    if (B <= 0 || K <= 0 || num_classes <= 0 || !(scale > 0.f)) return CN_ERR_SHAPE;
-    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(ctdet_post_kernel, dim3(B), dim3(PP_KMAX), 0, (hipStream_t)stream, dets, K, num_classes,
-                       to_source_2x3, per_image ? 1 : 0, scale, rows, bounds);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// multi_pose_post_process on the device (utils/post_process.py:103-114, detectors/multi_pose.py:62-72):
-// the K raw rows [x1, y1, x2, y2, score, 17 x (x, y), class] of every image in output-grid units become
-// rows [x1, y1, x2, y2, score, 17 x (x, y)] in source-frame pixels / scale.  The two box corners and the
-// 17 joints are 19 points under one inverse map, with the arithmetic of ctdet_post_kernel; the score is
-// copied, the class dropped, the row order kept (one class: nothing to group).  One item per point or
-// score, so the 39 columns of a row are written by neighbouring lanes.
-// ---------------------------------------------------------------------------
-namespace {
-constexpr int MP_THREADS = 256;
-constexpr int MP_IN = 40, MP_OUT = 39, MP_ITEMS = 20;   // 19 points + the score per row
-__global__ __launch_bounds__(MP_THREADS) void multi_pose_post_kernel(const float *__restrict__ dets, int K,
-                                                                     const double *__restrict__ to_source,
-                                                                     int per_image, float scale,
-                                                                     float *__restrict__ rows)
-{
-    const int b = blockIdx.x;
-    const double *t = to_source + (per_image ? (size_t)b * 6 : 0);
-    const double t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4], t5 = t[5];
-    for (int e = threadIdx.x; e < K * MP_ITEMS; e += MP_THREADS) {
-        const int k = e / MP_ITEMS, j = e - k * MP_ITEMS;
-        const float *d = dets + ((size_t)b * K + k) * MP_IN;
-        float *o = rows + ((size_t)b * K + k) * MP_OUT;
-        if (j == MP_ITEMS - 1) {
-            o[4] = d[4];
-            continue;
-        }
-        const int c = j < 2 ? 2 * j : 2 * j + 1;     // corners in columns 0..3, joints from column 5
-        const double x = (double)d[c], y = (double)d[c + 1];
-        const double sx = (x * t0 + y * t1) + t2;
-        const double sy = (x * t3 + y * t4) + t5;
-        o[c] = (float)sx / scale;
-        o[c + 1] = (float)sy / scale;
-    }
-}
-}  // namespace
-
-extern "C" int cn_multi_pose_post_process_f32(const float *dets, int B, int K, const double *to_source_2x3,
-                                              int per_image, float scale, float *rows, void *stream)
-{
-    if (!dets || !to_source_2x3 || !rows) return CN_ERR_NULL;
-    if (B <= 0 || K <= 0 || !(scale > 0.f)) return CN_ERR_SHAPE;
-    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(multi_pose_post_kernel, dim3(B), dim3(MP_THREADS), 0, (hipStream_t)stream, dets, K,
-                       to_source_2x3, per_image ? 1 : 0, scale, rows);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// ddd task: the batched pre-process and the whole host tail of DddDetector on the device.
-//
-// cn_warp_table_u8_f32_batch -- the ddd class normalises with a FLOAT32 chain, (u8 / 255 - mean) / std
-// (detectors/ddd.py:45-46), not the float64-then-round of warp_normalize_kernel.  A uint8 level has 256
-// values, so the caller builds the 3 x 256 results with exactly those float32 operations once and the
-// kernel looks them up: same sampler, same zero border, out = table[c][v].
+// ddd task, the batched pre-process: cn_warp_table_u8_f32_batch -- the ddd class normalises with a
+// FLOAT32 chain, (u8 / 255 - mean) / std (detectors/ddd.py:45-46), not the float64-then-round of
+// warp_normalize_kernel.  A uint8 level has 256 values, so the caller builds the 3 x 256 results with
+// exactly those float32 operations once and the kernel looks them up: same sampler, same zero border,
+// out = table[c][v].
 // ---------------------------------------------------------------------------
 namespace {
 struct WarpTableArgs {
@@ -516,109 +400,6 @@ extern "C" int cn_warp_table_u8_f32_batch(const uint8_t *images_hwc, int N, size
     a.out_stride = (size_t)3 * out_h * out_w;
     dim3 grid(cn_cdiv(out_w, 128), out_h, N);
     hipLaunchKernelGGL(warp_table_kernel, grid, dim3(128), 0, (hipStream_t)stream, a);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// ddd_post_process_2d + ddd_post_process_3d + DddDetector.merge_outputs (utils/post_process.py:24-79,
-// utils/ddd_utils.py:68-114, detectors/ddd.py:82-88) for a batch, image b lifted with ITS matrix: the K raw
-// rows [x, y, score, rot 8, depth, dim 3, w, h, class] of ddd_decode become [alpha, x1, y1, x2, y2, h, w, l,
-// x, y, z, rotation_y, score], grouped by class as ctdet_post_kernel groups them, plus per class the length
-// of the leading run of rows with score > peak_thresh (the rows of a class are in descending score order,
-// so merge_outputs' mask is that prefix).  Types as the reference's: centre and (w, h) through the float64
-// point map (translation included for both) and rounded to float32; unproject, "+ h / 2", the box and the
-// angle sums in float32.  The two arctan2 are float64 atan2 rounded once to float32 (NumPy's float32
-// arctan2 differs from that by at most one ulp of the angle; no device form equals it bit for bit).
-// A class is taken when the float equals an integer in [0, num_classes) (`classes == j`).
-// ---------------------------------------------------------------------------
-namespace {
-constexpr int DDD_IN = 18, DDD_OUT = 13;
-__global__ __launch_bounds__(PP_KMAX) void ddd_post_kernel(const float *__restrict__ dets, int K, int num_classes,
-                                                           const double *__restrict__ to_source, int per_image,
-                                                           const float *__restrict__ calibs, float peak_thresh,
-                                                           float *__restrict__ rows, int32_t *__restrict__ bounds,
-                                                           int32_t *__restrict__ kept)
-{
-    __shared__ int cls_s[PP_KMAX];
-    __shared__ int pass_s[PP_KMAX];
-    const float HALF_PI = 1.57079637f, PI = 3.14159274f, TWO_PI = 6.28318548f;   // float32(np.pi) and kin
-    const int b = blockIdx.x, k = threadIdx.x;
-    const double *t = to_source + (per_image ? (size_t)b * 6 : 0);
-    const float *P = calibs + (size_t)b * 12;
-    float r[DDD_OUT];
-#pragma unroll
-    for (int e = 0; e < DDD_OUT; ++e) r[e] = 0.f;
-    int cls = num_classes;             // sorts behind every class
-    if (k < K) {
-        const float *d = dets + ((size_t)b * K + k) * DDD_IN;
-        const float cf = d[DDD_IN - 1];
-        if (cf >= 0.f && cf < (float)num_classes) {
-            const int c = (int)cf;
-            if ((float)c == cf) cls = c;
-        }
-        float pt[4];                   // centre, then the (w, h) pair: the same map for both
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const double x = (double)d[15 * p], y = (double)d[15 * p + 1];
-            pt[2 * p] = (float)((x * t[0] + y * t[1]) + t[2]);
-            pt[2 * p + 1] = (float)((x * t[3] + y * t[4]) + t[5]);
-        }
-        const float cx = pt[0], cy = pt[1], w2 = pt[2] / 2.f, h2 = pt[3] / 2.f;
-        // get_alpha: bin 1 (centred on -pi / 2) when its second logit is the larger one
-        const bool first = d[4] > d[8];
-        const float bin = (float)atan2((double)(first ? d[5] : d[9]), (double)(first ? d[6] : d[10]));
-        const float alpha = bin + (first ? -HALF_PI : HALF_PI);
-        const float depth = d[11], dim_h = d[12];
-        // unproject_2d_to_3d, then location[1] += h / 2
-        const float z = depth - P[11];
-        const float lx = ((cx * depth - P[3]) - P[2] * z) / P[0];
-        const float ly = ((cy * depth - P[7]) - P[6] * z) / P[5] + dim_h / 2.f;
-        // alpha2rot_y
-        float ry = alpha + (float)atan2((double)(cx - P[2]), (double)P[0]);
-        if (ry > PI) ry = ry - TWO_PI;
-        if (ry < -PI) ry = ry + TWO_PI;
-        r[0] = alpha;
-        r[1] = cx - w2; r[2] = cy - h2; r[3] = cx + w2; r[4] = cy + h2;
-        r[5] = dim_h; r[6] = d[13]; r[7] = d[14];
-        r[8] = lx; r[9] = ly; r[10] = z;
-        r[11] = ry; r[12] = d[2];
-    }
-    cls_s[k] = cls;
-    pass_s[k] = (k < K && r[12] > peak_thresh) ? 1 : 0;
-    __syncthreads();
-    if (k < K) {
-        int rank = 0;
-        for (int j = 0; j < K; ++j) rank += (cls_s[j] < cls || (cls_s[j] == cls && j < k)) ? 1 : 0;
-        float *o = rows + ((size_t)b * K + rank) * DDD_OUT;
-#pragma unroll
-        for (int e = 0; e < DDD_OUT; ++e) o[e] = r[e];
-    }
-    for (int c = k; c <= num_classes; c += PP_KMAX) {
-        int n = 0, lead = 0, open = 1;
-        for (int j = 0; j < K; ++j) {
-            n += cls_s[j] < c ? 1 : 0;
-            if (cls_s[j] == c) {
-                open &= pass_s[j];
-                lead += open;
-            }
-        }
-        bounds[(size_t)b * (num_classes + 1) + c] = n;
-        if (c < num_classes) kept[(size_t)b * num_classes + c] = lead;
-    }
-}
-}  // namespace
-
-extern "C" int cn_ddd_post_process_f32(const float *dets, int B, int K, int row_floats, int num_classes,
-                                       const double *to_source_2x3, int per_image, const float *calibs,
-                                       float peak_thresh, float *rows, int32_t *bounds, int32_t *kept, void *stream)
-{
-    if (!dets || !to_source_2x3 || !calibs || !rows || !bounds || !kept) return CN_ERR_NULL;
-    if (B <= 0 || K <= 0 || num_classes <= 0 || (row_floats != 16 && row_floats != DDD_IN)) return CN_ERR_SHAPE;
-    if (row_floats != DDD_IN) return CN_ERR_UNSUPPORTED;    // no (w, h): the reference's 3-D stage has no box either
-    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(ddd_post_kernel, dim3(B), dim3(PP_KMAX), 0, (hipStream_t)stream, dets, K, num_classes,
-                       to_source_2x3, per_image ? 1 : 0, calibs, peak_thresh, rows, bounds, kept);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

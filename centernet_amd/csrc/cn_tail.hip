@@ -1,10 +1,14 @@
-// cn_merge.hip -- the ctdet scale merge on the device (CtdetDetector.merge_outputs, detectors/ctdet.py:54-74;
-// reference ctdet.py:58-73), bit for bit.  Input: the device tail's output of every test scale
-// (cn_ctdet_post_process_f32 into slice s of rows (S, B, K, 5) / bounds (S, B, nc + 1)).  Output in the
-// tail's own format, so the host slices it as it slices a single scale.  Behind it the multi_pose scale
-// merge (multi_pose_merge_kernel): the same soft-NMS routine on 39-column rows, one segment per image.  And the
-// exdet tail: exdet_post_kernel (post_process + the positive-score filter + a stable class grouping of up to
-// MG_ROWS rows) in front of the same merge kernel with the row cap checked per image (class_merge_kernel<true>).
+// cn_tail.hip -- the tasks' tails of the frame pipe on the device (frame_pipe.py: DeviceTail), bit for bit what
+// the host tails compute.  Per test scale a post-process kernel: ctdet_post_kernel, multi_pose_post_kernel,
+// ddd_post_kernel (raw detections of the decode -> rows in source pixels; ctdet and ddd grouped by class, with
+// the class bounds) and exdet_post_kernel (post_process + the positive-score filter + a stable class grouping of
+// up to MG_ROWS rows).  Behind the last scale the merge kernels.
+//
+// class_merge_kernel<false> is the ctdet scale merge (CtdetDetector.merge_outputs, detectors/ctdet.py:54-74;
+// reference ctdet.py:58-73).  Input: cn_ctdet_post_process_f32's output of every test scale, slice s of rows
+// (S, B, K, 5) / bounds (S, B, nc + 1).  Output in the same format, so the host slices it as it slices a single
+// scale.  class_merge_kernel<true> is the same merge behind exdet_post_kernel with the row cap checked per image;
+// multi_pose_merge_kernel runs the same soft-NMS routine on 39-column rows, one segment per image.
 //
 // One workgroup of four waves per image; the image's rows (<= CN_MERGE_MAX_ROWS) live in LDS.
 //   1. per class, the rows of all scales in scale order (the np.concatenate of merge_outputs);
@@ -28,7 +32,12 @@
 //              equal to cn_soft_nms_f32 on seeded arrays before any GPU run.
 #include "cn_common.h"
 
+// hipcc defaults to -ffp-contract=fast-honor-pragmas: the float64 point map and the float32 chains below are
+// the host's operations one by one only without FMA contraction, anywhere in this file.
+#pragma clang fp contract(off)
+
 namespace {
+constexpr int PP_KMAX = 128;     // rows per image of the ctdet / multi_pose / ddd post-process kernels
 constexpr int MG_THREADS = 256;
 constexpr int MG_WAVES = MG_THREADS / CN_WAVE;
 constexpr int MG_ROWS = CN_MERGE_MAX_ROWS;
@@ -73,6 +82,72 @@ __device__ __forceinline__ int block_sum(int v, int *red)
     return s;
 }
 
+// Workgroup exclusive scan of one int per thread (MG_THREADS threads, all of them call it): the sum over the
+// threads in front of this one; `total`: over all of them.
+__device__ __forceinline__ int block_exclusive_scan(int n, int *red, int &total)
+{
+    const int lane = threadIdx.x & (CN_WAVE - 1), w = threadIdx.x / CN_WAVE;
+    int incl = n;
+    for (int o = 1; o < CN_WAVE; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    __syncthreads();                      // red[] of an earlier use has been read
+    if (lane == CN_WAVE - 1) red[w] = incl;
+    __syncthreads();
+    int run = incl - n;
+    total = 0;
+    for (int k = 0; k < MG_WAVES; ++k) {
+        if (k < w) run += red[k];
+        total += red[k];
+    }
+    return run;
+}
+
+// Output grid -> source pixels, the arithmetic of utils/image.py:63-66: float32 point -> float64
+// (x * t0 + y * t1) + t2 -> ONE rounding to float32.  The map of image b, or the one map of the batch.
+struct PointMap {
+    double t0, t1, t2, t3, t4, t5;
+    __device__ __forceinline__ PointMap(const double *to_source, int per_image, int b)
+    {
+        const double *t = to_source + (per_image ? (size_t)b * 6 : 0);
+        t0 = t[0]; t1 = t[1]; t2 = t[2]; t3 = t[3]; t4 = t[4]; t5 = t[5];
+    }
+    __device__ __forceinline__ void operator()(float x, float y, float &sx, float &sy) const
+    {
+        sx = (float)(((double)x * t0 + (double)y * t1) + t2);
+        sy = (float)(((double)x * t3 + (double)y * t4) + t5);
+    }
+};
+
+// Stable grouping by class of the K <= PP_KMAX rows of one image, thread k = row k, cls_s[k] = its class
+// (num_classes: no class, behind every class).  The position of row k: behind the rows of lower classes and the
+// earlier rows of its own.
+__device__ __forceinline__ int class_rank(const int *cls_s, int K, int cls, int k)
+{
+    int rank = 0;
+    for (int j = 0; j < K; ++j) rank += (cls_s[j] < cls || (cls_s[j] == cls && j < k)) ? 1 : 0;
+    return rank;
+}
+// bounds[c] = rows of classes < c, c in [0, num_classes].  With pass_s (ddd): kept[c] = the length of class c's
+// leading run of rows with pass_s set.
+__device__ __forceinline__ void class_bounds(const int *cls_s, const int *pass_s, int K, int num_classes, int k,
+                                             int32_t *bounds, int32_t *kept)
+{
+    for (int c = k; c <= num_classes; c += PP_KMAX) {
+        int n = 0, lead = 0, open = 1;
+        for (int j = 0; j < K; ++j) {
+            n += cls_s[j] < c ? 1 : 0;
+            if (pass_s && cls_s[j] == c) {
+                open &= pass_s[j];
+                lead += open;
+            }
+        }
+        bounds[c] = n;
+        if (pass_s && c < num_classes) kept[c] = lead;
+    }
+}
+
 // float -> unsigned key of the same order
 __device__ __forceinline__ uint32_t order_key(float f)
 {
@@ -95,7 +170,6 @@ __device__ __forceinline__ float div_rn(float a, float b) { return (float)((doub
 template <bool JOINTS>
 __device__ void soft_nms_segment(NmsLds &L, int o, int n, int lane, int16_t *jsrc)
 {
-#pragma clang fp contract(off)
     float *x1 = L.box[0] + o, *y1 = L.box[1] + o, *x2 = L.box[2] + o, *y2 = L.box[3] + o;
     float *sc = L.sc + o, *ns = L.ns + o;
     int16_t *orig = L.orig + o;
@@ -271,20 +345,9 @@ __global__ __launch_bounds__(MG_THREADS) void class_merge_kernel(const float *__
         thresh = key_value(T);
     }
     // order-preserving compaction: exclusive prefix of the kept flags (chunk per thread, then a scan)
-    int n = 0;
+    int n = 0, kept;
     for (int r = r0; r < r1; ++r) n += (!cut || L.sc[r] >= thresh) ? 1 : 0;
-    int incl = n;
-    for (int o = 1; o < CN_WAVE; o <<= 1) {
-        const int v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    __syncthreads();
-    if (lane == CN_WAVE - 1) L.red[w] = incl;
-    __syncthreads();
-    int run = incl - n;
-    for (int k = 0; k < w; ++k) run += L.red[k];
-    int kept = 0;
-    for (int k = 0; k < MG_WAVES; ++k) kept += L.red[k];
+    int run = block_exclusive_scan(n, L.red, kept);
     int *prefix = reinterpret_cast<int *>(L.ns);
     float *ob = out_rows + (size_t)b * cap * 5;
     for (int r = r0; r < r1; ++r) {
@@ -348,6 +411,142 @@ __global__ __launch_bounds__(MG_THREADS) void multi_pose_merge_kernel(const floa
     }
 }
 
+// ctdet_post_process + the per-class split (utils/post_process.py:83-100, utils/image.py:19-24,63-66,
+// detectors/ctdet.py:47-56), so that the host tail of a batch is one small copy and 80 slices per image: for
+// every image the K raw detections [x1, y1, x2, y2, score, class] in output-grid units become rows [x1, y1, x2,
+// y2, score] in source-frame pixels (PointMap, then / scale in float32), grouped by class (ascending; inside a
+// class in their original, score-descending order), plus the class bounds.  The class is the float truncated
+// (astype(np.int64)); rows whose class lies outside [0, num_classes) are dropped (they match no `classes == j`).
+__global__ __launch_bounds__(PP_KMAX) void ctdet_post_kernel(const float *__restrict__ dets, int K, int num_classes,
+                                                             const double *__restrict__ to_source, int per_image,
+                                                             float scale, float *__restrict__ rows,
+                                                             int32_t *__restrict__ bounds)
+{
+    __shared__ int cls_s[PP_KMAX];
+    const int b = blockIdx.x, k = threadIdx.x;
+    const PointMap to_src(to_source, per_image, b);
+    float r[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    int cls = num_classes;             // sorts behind every class
+    if (k < K) {
+        const float *d = dets + ((size_t)b * K + k) * 6;
+        const int c = (int)(long long)d[5];        // astype(np.int64): truncation
+        if (c >= 0 && c < num_classes) cls = c;
+        to_src(d[0], d[1], r[0], r[1]);
+        to_src(d[2], d[3], r[2], r[3]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = r[e] / scale;
+        r[4] = d[4];
+    }
+    cls_s[k] = cls;
+    __syncthreads();
+    if (k < K) {
+        float *o = rows + ((size_t)b * K + class_rank(cls_s, K, cls, k)) * 5;
+#pragma unroll
+        for (int e = 0; e < 5; ++e) o[e] = r[e];
+    }
+    class_bounds(cls_s, nullptr, K, num_classes, k, bounds + (size_t)b * (num_classes + 1), nullptr);
+}
+
+// multi_pose_post_process (utils/post_process.py:103-114, detectors/multi_pose.py:62-72): the K raw rows [x1,
+// y1, x2, y2, score, 17 x (x, y), class] of every image in output-grid units become rows [x1, y1, x2, y2,
+// score, 17 x (x, y)] in source-frame pixels / scale.  The two box corners and the 17 joints are 19 points
+// under one inverse map, with the arithmetic of ctdet_post_kernel; the score is copied, the class dropped, the
+// row order kept (one class: nothing to group).  One item per point or score, so the 39 columns of a row are
+// written by neighbouring lanes.
+constexpr int MP_IN = 40, MP_OUT = 39, MP_ITEMS = 20;   // 19 points + the score per row
+__global__ __launch_bounds__(MG_THREADS) void multi_pose_post_kernel(const float *__restrict__ dets, int K,
+                                                                     const double *__restrict__ to_source,
+                                                                     int per_image, float scale,
+                                                                     float *__restrict__ rows)
+{
+    const int b = blockIdx.x;
+    const PointMap to_src(to_source, per_image, b);
+    for (int e = threadIdx.x; e < K * MP_ITEMS; e += MG_THREADS) {
+        const int k = e / MP_ITEMS, j = e - k * MP_ITEMS;
+        const float *d = dets + ((size_t)b * K + k) * MP_IN;
+        float *o = rows + ((size_t)b * K + k) * MP_OUT;
+        if (j == MP_ITEMS - 1) {
+            o[4] = d[4];
+            continue;
+        }
+        const int c = j < 2 ? 2 * j : 2 * j + 1;     // corners in columns 0..3, joints from column 5
+        float sx, sy;
+        to_src(d[c], d[c + 1], sx, sy);
+        o[c] = sx / scale;
+        o[c + 1] = sy / scale;
+    }
+}
+
+// ddd_post_process_2d + ddd_post_process_3d + DddDetector.merge_outputs (utils/post_process.py:24-79,
+// utils/ddd_utils.py:68-114, detectors/ddd.py:82-88) for a batch, image b lifted with ITS matrix: the K raw
+// rows [x, y, score, rot 8, depth, dim 3, w, h, class] of ddd_decode become [alpha, x1, y1, x2, y2, h, w, l,
+// x, y, z, rotation_y, score], grouped by class as ctdet_post_kernel groups them, plus per class the length
+// of the leading run of rows with score > peak_thresh (the rows of a class are in descending score order,
+// so merge_outputs' mask is that prefix).  Types as the reference's: centre and (w, h) through the float64
+// point map (translation included for both) and rounded to float32; unproject, "+ h / 2", the box and the
+// angle sums in float32.  The two arctan2 are float64 atan2 rounded once to float32 (NumPy's float32
+// arctan2 differs from that by at most one ulp of the angle; no device form equals it bit for bit).
+// A class is taken when the float equals an integer in [0, num_classes) (`classes == j`).
+constexpr int DDD_IN = 18, DDD_OUT = 13;
+__global__ __launch_bounds__(PP_KMAX) void ddd_post_kernel(const float *__restrict__ dets, int K, int num_classes,
+                                                           const double *__restrict__ to_source, int per_image,
+                                                           const float *__restrict__ calibs, float peak_thresh,
+                                                           float *__restrict__ rows, int32_t *__restrict__ bounds,
+                                                           int32_t *__restrict__ kept)
+{
+    __shared__ int cls_s[PP_KMAX];
+    __shared__ int pass_s[PP_KMAX];
+    const float HALF_PI = 1.57079637f, PI = 3.14159274f, TWO_PI = 6.28318548f;   // float32(np.pi) and kin
+    const int b = blockIdx.x, k = threadIdx.x;
+    const PointMap to_src(to_source, per_image, b);
+    const float *P = calibs + (size_t)b * 12;
+    float r[DDD_OUT];
+#pragma unroll
+    for (int e = 0; e < DDD_OUT; ++e) r[e] = 0.f;
+    int cls = num_classes;             // sorts behind every class
+    if (k < K) {
+        const float *d = dets + ((size_t)b * K + k) * DDD_IN;
+        const float cf = d[DDD_IN - 1];
+        if (cf >= 0.f && cf < (float)num_classes) {
+            const int c = (int)cf;
+            if ((float)c == cf) cls = c;
+        }
+        float cx, cy, w2, h2;          // centre, then the (w, h) pair: the same map for both
+        to_src(d[0], d[1], cx, cy);
+        to_src(d[15], d[16], w2, h2);
+        w2 = w2 / 2.f;
+        h2 = h2 / 2.f;
+        // get_alpha: bin 1 (centred on -pi / 2) when its second logit is the larger one
+        const bool first = d[4] > d[8];
+        const float bin = (float)atan2((double)(first ? d[5] : d[9]), (double)(first ? d[6] : d[10]));
+        const float alpha = bin + (first ? -HALF_PI : HALF_PI);
+        const float depth = d[11], dim_h = d[12];
+        // unproject_2d_to_3d, then location[1] += h / 2
+        const float z = depth - P[11];
+        const float lx = ((cx * depth - P[3]) - P[2] * z) / P[0];
+        const float ly = ((cy * depth - P[7]) - P[6] * z) / P[5] + dim_h / 2.f;
+        // alpha2rot_y
+        float ry = alpha + (float)atan2((double)(cx - P[2]), (double)P[0]);
+        if (ry > PI) ry = ry - TWO_PI;
+        if (ry < -PI) ry = ry + TWO_PI;
+        r[0] = alpha;
+        r[1] = cx - w2; r[2] = cy - h2; r[3] = cx + w2; r[4] = cy + h2;
+        r[5] = dim_h; r[6] = d[13]; r[7] = d[14];
+        r[8] = lx; r[9] = ly; r[10] = z;
+        r[11] = ry; r[12] = d[2];
+    }
+    cls_s[k] = cls;
+    pass_s[k] = (k < K && r[12] > peak_thresh) ? 1 : 0;
+    __syncthreads();
+    if (k < K) {
+        float *o = rows + ((size_t)b * K + class_rank(cls_s, K, cls, k)) * DDD_OUT;
+#pragma unroll
+        for (int e = 0; e < DDD_OUT; ++e) o[e] = r[e];
+    }
+    class_bounds(cls_s, pass_s, K, num_classes, k, bounds + (size_t)b * (num_classes + 1),
+                 kept + (size_t)b * num_classes);
+}
+
 // ExdetDetector.post_process + the `score > 0` filter and the per-class selection of merge_outputs
 // (detectors/exdet.py:51-74; reference exdet.py:86-110) for one test scale: one workgroup per frame, the
 // frame's R <= MG_ROWS raw rows [x1, y1, x2, y2, score, 8 extreme-point coordinates, class] -> rows
@@ -372,13 +571,11 @@ __global__ __launch_bounds__(MG_THREADS) void exdet_post_kernel(const float *__r
                                                                 float *__restrict__ rows,
                                                                 int32_t *__restrict__ bounds)
 {
-#pragma clang fp contract(off)
     __shared__ ExdetPostLds L;
     const int b = blockIdx.x, t = threadIdx.x, lane = t & (CN_WAVE - 1), w = t / CN_WAVE;
     const float *in = dets + (size_t)b * R * PX_ROW;
     float *out = rows + (size_t)b * R * 5;
-    const double *tr = to_source + (per_image ? (size_t)b * 6 : 0);
-    const double t0 = tr[0], t1 = tr[1], t2 = tr[2], t3 = tr[3], t4 = tr[4], t5 = tr[5];
+    const PointMap to_src(to_source, per_image, b);
     // rows of wave w: [w0, w1), whole steps of 64
     const int per = (R + MG_THREADS - 1) / MG_THREADS * CN_WAVE;
     const int w0 = min(w * per, R), w1 = min(w0 + per, R);
@@ -401,18 +598,7 @@ __global__ __launch_bounds__(MG_THREADS) void exdet_post_kernel(const float *__r
     int n = 0;
     for (int c = c0; c < c1; ++c)
         for (int k = 0; k < MG_WAVES; ++k) n += L.hist[k][c];
-    int incl = n;
-    for (int o = 1; o < CN_WAVE; o <<= 1) {
-        const int v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    if (lane == CN_WAVE - 1) L.red[w] = incl;
-    __syncthreads();
-    int run = incl - n, total = 0;
-    for (int k = 0; k < MG_WAVES; ++k) {
-        if (k < w) run += L.red[k];
-        total += L.red[k];
-    }
+    int total, run = block_exclusive_scan(n, L.red, total);
     for (int c = c0; c < c1; ++c) {
         bounds[(size_t)b * (nc + 1) + c] = run;
         for (int k = 0; k < MG_WAVES; ++k) {
@@ -449,17 +635,57 @@ __global__ __launch_bounds__(MG_THREADS) void exdet_post_kernel(const float *__r
             x1 = out_w - x2;
             x2 = out_w - l;
         }
+        float p[4];
+        to_src(x1, y1, p[0], p[1]);
+        to_src(x2, y2, p[2], p[3]);
         float *o = out + (size_t)pos * 5;
-        o[0] = (float)(((double)x1 * t0 + (double)y1 * t1) + t2) / scale;
-        o[1] = (float)(((double)x1 * t3 + (double)y1 * t4) + t5) / scale;
-        o[2] = (float)(((double)x2 * t0 + (double)y2 * t1) + t2) / scale;
-        o[3] = (float)(((double)x2 * t3 + (double)y2 * t4) + t5) / scale;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = p[e] / scale;
         o[4] = d[4];
     }
     // rows behind the last bound: zeros, so that the array is a function of the input
     for (int e = total * 5 + t; e < R * 5; e += MG_THREADS) out[e] = 0.f;
 }
 }  // namespace
+
+extern "C" int cn_ctdet_post_process_f32(const float *dets, int B, int K, int num_classes,
+                                         const double *to_source_2x3, int per_image, float scale,
+                                         float *rows, int32_t *bounds, void *stream)
+{
+    if (!dets || !to_source_2x3 || !rows || !bounds) return CN_ERR_NULL;
+    if (B <= 0 || K <= 0 || num_classes <= 0 || !(scale > 0.f)) return CN_ERR_SHAPE;
+    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(ctdet_post_kernel, dim3(B), dim3(PP_KMAX), 0, (hipStream_t)stream, dets, K, num_classes,
+                       to_source_2x3, per_image ? 1 : 0, scale, rows, bounds);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_multi_pose_post_process_f32(const float *dets, int B, int K, const double *to_source_2x3,
+                                              int per_image, float scale, float *rows, void *stream)
+{
+    if (!dets || !to_source_2x3 || !rows) return CN_ERR_NULL;
+    if (B <= 0 || K <= 0 || !(scale > 0.f)) return CN_ERR_SHAPE;
+    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(multi_pose_post_kernel, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, dets, K,
+                       to_source_2x3, per_image ? 1 : 0, scale, rows);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_ddd_post_process_f32(const float *dets, int B, int K, int row_floats, int num_classes,
+                                       const double *to_source_2x3, int per_image, const float *calibs,
+                                       float peak_thresh, float *rows, int32_t *bounds, int32_t *kept, void *stream)
+{
+    if (!dets || !to_source_2x3 || !calibs || !rows || !bounds || !kept) return CN_ERR_NULL;
+    if (B <= 0 || K <= 0 || num_classes <= 0 || (row_floats != 16 && row_floats != DDD_IN)) return CN_ERR_SHAPE;
+    if (row_floats != DDD_IN) return CN_ERR_UNSUPPORTED;    // no (w, h): the reference's 3-D stage has no box either
+    if (K > PP_KMAX) return CN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(ddd_post_kernel, dim3(B), dim3(PP_KMAX), 0, (hipStream_t)stream, dets, K, num_classes,
+                       to_source_2x3, per_image ? 1 : 0, calibs, peak_thresh, rows, bounds, kept);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
 
 extern "C" int cn_multi_pose_merge_f32(const float *rows, int S, int B, int K, int apply_nms, float *out_rows,
                                        void *stream)

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import native
+from ..frame_pipe import FramePipe
 from ..image import get_affine_transform, invert_affine, normalize_chw, resize_bilinear, warp_affine
 from ..model import create_model, load_model
 
@@ -44,173 +45,6 @@ class _PhaseClock(object):
     def finish(self):
         self.t["tot"] = self._last - self._start
         return self.t
-
-
-class _FramePipe(object):
-    """Persistent resources of ``run_frames`` / ``run_frames_stream`` for one batch geometry
-    (B frames of (H, W, 3) uint8, the detector's test scales and flip setting): per test scale the
-    input geometry and meta, the resize buffer and the network batch ((B or 2B, 3, h, w): with
-    flip-test every frame is followed by its mirror image); ``depth`` sets of a pinned uint8 staging
-    buffer, its device copy and pinned result buffers, one copy stream, a few staging threads.
-
-    Per batch: the frames are copied into the pinned buffer by the staging threads (numpy releases
-    the GIL), go to the device as ONE asynchronous uint8 copy on the copy stream, and everything
-    else -- per test scale the batched device pre-process, network + flip average + decode
-    (``_run_scale``) and the task's device tail (ctdet: ``cn_ctdet_post_process_f32``, inverse
-    affine + class grouping; multi_pose: ``cn_multi_pose_post_process_f32``, inverse affine of the
-    box corners and joints; into the scale's slice), then the scale merge (``cn_ctdet_merge_f32``:
-    soft-NMS and the top-100 cut; ``cn_multi_pose_merge_f32``: soft-NMS of the 39-column rows, no
-    cut; when there are several scales or --nms; exdet: ``cn_exdet_post_process_f32`` +
-    ``cn_exdet_merge_f32``, always) and the copies of the rows / class bounds / f32s
-    range digests into pinned memory -- is enqueued on the launch stream without a single host
-    synchronisation.  The host waits for batch i - depth + 1 only when it collects it, i.e. while
-    later batches are on the device.  Shapes the tail kernels do not take (``_device_tail_alloc``
-    returns None) copy the raw detections out and keep the host tail; a tail can also hand ONE batch
-    back when only the batch's own data tell that it does not fit (``_device_tail_results`` returns
-    None: exdet, more positive rows in a frame than the merge kernel holds) -- ``collect`` then drains
-    the device, runs that batch through ``_run_frames_sync`` and counts it in ``det.tail_fallbacks``.
-
-    Two more task hooks keep the pipe free of task geometry: ``_pipe_level`` (input geometry, frame ->
-    input map and meta of one test scale) and ``_pipe_pre_process`` (the batched pre-process launch).
-    A task with per-frame side inputs (ddd: one 3 x 4 calibration matrix per frame) sets
-    ``_pipe_side_shape``: the pipe then keeps ``depth`` pinned (B, *shape) float32 buffers and their device
-    copies, ``submit`` takes the batch's side array, uploads it on the copy stream with the frames, and the
-    tail hooks read ``pipe.side_dev[slot]`` / ``pipe.side_host[slot]``."""
-
-    def __init__(self, det, B, H, W, scales, flip, depth):
-        import concurrent.futures
-        import types
-        opt, dev = det.opt, det.opt.device
-        self.det, self.B, self.H, self.W, self.depth = det, B, H, W, depth
-        self.scales, self.flip = tuple(scales), bool(flip)
-        # merge_outputs does more than pass one scale through: soft-NMS, and a cut of S * K rows
-        self.merge = len(self.scales) > 1 or bool(getattr(opt, "nms", False))
-        self.levels = []
-        for scale in self.scales:
-            g, to_input, meta = det._pipe_level(H, W, scale)
-            resize = (g.scaled_h, g.scaled_w) != (g.src_h, g.src_w)
-            self.levels.append(types.SimpleNamespace(
-                scale=scale, g=g, resize=resize, meta=meta,
-                dst_to_src=(ctypes.c_double * 6)(*invert_affine(to_input).reshape(-1)),
-                scaled=torch.empty((B, g.scaled_h, g.scaled_w, 3), dtype=torch.uint8, device=dev) if resize else None,
-                batch=torch.empty((B * (2 if self.flip else 1), 3, g.inp_h, g.inp_w), device=dev,
-                                  dtype=torch.float32)))
-        first = self.levels[0]        # (the single-scale pipe's own names)
-        self.scale, self.g, self.meta, self.batch = first.scale, first.g, first.meta, first.batch
-        self.mean = (ctypes.c_float * 3)(*[float(v) for v in det.mean.reshape(-1)])
-        self.std = (ctypes.c_float * 3)(*[float(v) for v in det.std.reshape(-1)])
-        self.pinned_in = [torch.empty((B, H, W, 3), dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        self.np_in = [t.numpy() for t in self.pinned_in]
-        self.dev_in = [torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(depth)]
-        self.copy_stream = torch.cuda.Stream()
-        self.ev_h2d = [torch.cuda.Event() for _ in range(depth)]
-        self.ev_pre = [torch.cuda.Event() for _ in range(depth)]
-        self.ev_done = [torch.cuda.Event() for _ in range(depth)]
-        self.used = [False] * depth
-        # one range digest per test scale: every scale's plan is looked at
-        self.digest_host = [torch.zeros((len(self.scales), 2), dtype=torch.int32).pin_memory() for _ in range(depth)]
-        self.has_digest = [[False] * len(self.scales) for _ in range(depth)]
-        self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=min(4, B))
-        side = det._pipe_side_shape
-        self.side_pinned = self.side_dev = None
-        self.side_host = [None] * depth      # the batch's side array as given (host tail, f32s re-run)
-        if side is not None:
-            self.side_pinned = [torch.empty((B,) + tuple(side), dtype=torch.float32).pin_memory() for _ in range(depth)]
-            self.side_dev = [torch.empty((B,) + tuple(side), dtype=torch.float32, device=dev) for _ in range(depth)]
-        self.tail = det._device_tail_alloc(self) if det._device_tail_alloc is not None else None
-        self.dets_host = None if self.tail is not None else [[None] * len(self.scales) for _ in range(depth)]
-
-    def _stage(self, slot, frames):
-        dst = self.np_in[slot]
-        n = len(frames)
-        step = -(-n // self.pool._max_workers)
-
-        def copy(lo):
-            for i in range(lo, min(lo + step, n)):
-                np.copyto(dst[i], frames[i])
-        list(self.pool.map(copy, range(0, n, step)))
-
-    def submit(self, i, frames, side=None):
-        det, lib, B = self.det, native.lib(), self.B
-        slot = i % self.depth
-        if self.used[slot]:
-            self.ev_h2d[slot].synchronize()      # the pinned buffer's previous upload has left it
-        self._stage(slot, frames)
-        if self.side_pinned is not None:
-            self.side_host[slot] = side
-            self.side_pinned[slot].numpy()[:len(frames)] = side
-        cur = torch.cuda.current_stream()
-        with torch.cuda.stream(self.copy_stream):
-            if self.used[slot]:
-                self.copy_stream.wait_event(self.ev_pre[slot])   # the device copy's previous reader is done
-            self.dev_in[slot].copy_(self.pinned_in[slot], non_blocking=True)
-            if self.side_pinned is not None:
-                if self.used[slot]:
-                    self.copy_stream.wait_event(self.ev_done[slot])   # its reader is the tail, not the pre-process
-                self.side_dev[slot].copy_(self.side_pinned[slot], non_blocking=True)
-            self.ev_h2d[slot].record(self.copy_stream)
-        self.used[slot] = True
-        cur.wait_event(self.ev_h2d[slot])
-        stream = native.stream_ptr()
-        for li, lv in enumerate(self.levels):
-            g, src = lv.g, self.dev_in[slot]
-            if lv.resize:
-                for j in range(B):
-                    native.check(lib.cn_resize_bilinear_u8(native.ptr(src[j]), g.src_h, g.src_w, g.src_w * 3,
-                                                           g.scaled_h, g.scaled_w, native.ptr(lv.scaled[j]), stream),
-                                 "cn_resize_bilinear_u8")
-                src = lv.scaled
-            det._pipe_pre_process(self, lv, src, stream)
-            if li == len(self.levels) - 1:
-                self.ev_pre[slot].record()
-            dets = det._run_scale(lv.batch, self.flip)
-            plan = det.model.plan_for(lv.batch.shape[0], g.inp_h, g.inp_w, lv.batch.device)
-            rs = getattr(plan.b, "range_sum", None) if plan.b.range is not None else None
-            self.has_digest[slot][li] = rs is not None
-            if rs is not None:
-                self.digest_host[slot][li].copy_(rs, non_blocking=True)
-            if self.tail is not None:
-                det._device_tail_run(self, slot, li, dets)
-            else:
-                dh = self.dets_host[slot]
-                dh[li] = torch.empty(dets.shape, dtype=dets.dtype).pin_memory() if dh[li] is None else dh[li]
-                dh[li].copy_(dets, non_blocking=True)
-        if self.tail is not None:
-            det._device_tail_finish(self, slot)
-        self.ev_done[slot].record()
-
-    def collect(self, i, frames, arrays=False):
-        """Results of batch i (waits for it; later batches keep the device busy).  ``arrays``: see
-        ``run_frames``."""
-        from ..engine import F16_MAX_BITS
-        det = self.det
-        kw = det._arrays_kw(arrays)
-        slot = i % self.depth
-        if self.side_pinned is not None:
-            kw = dict(kw, side=self.side_host[slot])
-        self.ev_done[slot].synchronize()
-        det.__dict__["_unchecked"] = 0       # (the batch's range digests are looked at right here)
-        digest = self.digest_host[slot].tolist()
-        if any(has and (int(d[0]) & 0xffffffff) > F16_MAX_BITS for has, d in zip(self.has_digest[slot], digest)):
-            # an f32s value was clamped somewhere up to this batch: results invalid.  Drain the
-            # device, let the module re-calibrate, and run this batch again synchronously.
-            torch.cuda.synchronize()
-            det.range_ok(None)
-            return det._run_frames_sync(frames, self.scales, **kw)
-        n = len(frames)
-        if self.tail is not None:
-            results = det._device_tail_results(self, slot, n, **kw)
-            if results is not None:
-                return results
-            # the batch does not fit the task's device tail (exdet: a frame with more positive rows than
-            # the merge kernel holds): drain the device and run this batch again synchronously, host tail
-            torch.cuda.synchronize()
-            det.tail_fallbacks += 1
-            return det._run_frames_sync(frames, self.scales, **kw)
-        if not self.merge:
-            return det.results_batch(self.dets_host[slot][0].numpy()[:n], [self.meta] * n, self.scale, **kw)
-        return det._results_merged([(d.numpy()[:n], [lv.meta] * n, lv.scale)
-                                    for d, lv in zip(self.dets_host[slot], self.levels)], **kw)
 
 
 class BaseDetector(object):
@@ -256,7 +90,16 @@ class BaseDetector(object):
                 'out_width': g.inp_w // self.opt.down_ratio}
 
     # ------------------------------------------------------------------ frame pipe: geometry + pre-process
-    _pipe_side_shape = None      # shape of a task's per-frame side input (ddd: (3, 4)), see _FramePipe
+    _pipe_side_shape = None      # shape of a task's per-frame side input (ddd: (3, 4)), see FramePipe
+
+    def _pipe_scales(self):
+        """Task hook of the frame pipeline: the test scales a pipe runs."""
+        return self.scales
+
+    def _device_tail(self, pipe):
+        """Task hook of the frame pipeline: the task's ``DeviceTail`` for ``pipe``, or None when the host
+        tail (``results_batch`` / ``_results_merged``) serves it."""
+        return None
 
     def _pipe_level(self, height, width, scale):
         """Task hook of the frame pipeline: (InputGeometry, frame -> network-input map, meta) of one test
@@ -286,6 +129,18 @@ class BaseDetector(object):
             batch = np.concatenate((batch, batch[:, :, :, ::-1]), axis=0)
         return torch.from_numpy(np.ascontiguousarray(batch)), self._meta(g)
 
+    def _device_frame(self, image):
+        """``pre_process_device``'s frame on the device: a contiguous (H, W, 3) uint8 HIP tensor as it is, a
+        uint8 numpy image uploaded."""
+        if torch.is_tensor(image):
+            if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or \
+                    not image.is_cuda or not image.is_contiguous():
+                raise ValueError("pre_process_device needs a contiguous (H, W, 3) uint8 HIP tensor")
+            return image
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("pre_process_device needs an (H, W, 3) uint8 BGR image")
+        return torch.from_numpy(np.ascontiguousarray(image)).to(self.opt.device)
+
     def pre_process_device(self, image, scale, meta=None, out=None):
         """The same steps on the device: the uint8 frame (a numpy array, or a uint8 HIP tensor
         that is already uploaded) goes through ``cn_resize_bilinear_u8`` (scale != 1) and
@@ -293,15 +148,7 @@ class BaseDetector(object):
         ``out`` when given.  Bit-identical to ``pre_process``."""
         lib = native.lib()
         dev = self.opt.device
-        if torch.is_tensor(image):
-            if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or \
-                    not image.is_cuda or not image.is_contiguous():
-                raise ValueError("pre_process_device needs a contiguous (H, W, 3) uint8 HIP tensor")
-            frame = image
-        else:
-            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-                raise ValueError("pre_process_device needs an (H, W, 3) uint8 BGR image")
-            frame = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+        frame = self._device_frame(image)
         g = self.input_geometry(int(frame.shape[0]), int(frame.shape[1]), scale)
         stream = native.stream_ptr()
         if (g.scaled_h, g.scaled_w) != (g.src_h, g.src_w):
@@ -374,10 +221,8 @@ class BaseDetector(object):
         frames' metas -> what ``run(frame)['results']`` returns, per image."""
         raise NotImplementedError
 
-    # device tail of the frame pipeline: task classes that have one set the four hooks
-    _device_tail_alloc = None
-    # the task's result rows are nested lists, and its tail hooks (results_batch, merge_outputs,
-    # _device_tail_results) take ``arrays=True`` to return them as float32 arrays instead
+    # the task's result rows are nested lists, and its host tail (results_batch, merge_outputs) takes
+    # ``arrays=True`` to return them as float32 arrays instead
     _list_results = False
 
     def _arrays_kw(self, arrays):
@@ -400,6 +245,16 @@ class BaseDetector(object):
         """``post_process`` of every image of a host batch of raw detections (task specific)."""
         raise NotImplementedError
 
+    def _forward_checked(self, batch, flip):
+        """``_run_scale`` of one batch with the f32s range words looked at: the raw detections on the host; after
+        a clamped value the network is re-calibrated on this batch and run once more."""
+        dets = self._run_scale(batch, flip).detach().cpu().numpy()
+        if not self.range_ok(batch):
+            dets = self._run_scale(batch, flip).detach().cpu().numpy()
+            if not self.range_ok(batch):
+                raise native.NativeError("f32s forward clamps values after re-calibration")
+        return dets
+
     def _run_frames_sync(self, frames, scales, **kw):
         """One batch, synchronously, frame by frame through ``pre_process_device`` at every test scale
         (the comparison path of the pipeline, and its re-run path after an f32s re-calibration)."""
@@ -413,12 +268,7 @@ class BaseDetector(object):
                                 dtype=torch.float32)
             metas = [self.pre_process_device(frame, scale, out=batch[k * i:k * i + k])[1]
                      for i, frame in enumerate(uploaded)]
-            dets = self._run_scale(batch, flip).detach().cpu().numpy()
-            if not self.range_ok(batch):    # a clamped f32s value: re-calibrated on this batch, run again
-                dets = self._run_scale(batch, flip).detach().cpu().numpy()
-                if not self.range_ok(batch):
-                    raise native.NativeError("f32s forward clamps values after re-calibration")
-            per_scale.append((dets, metas, scale))
+            per_scale.append((self._forward_checked(batch, flip), metas, scale))
         if len(per_scale) == 1 and not getattr(self.opt, "nms", False):
             return self.results_batch(*per_scale[0], **kw)
         return self._results_merged(per_scale, **kw)
@@ -431,12 +281,13 @@ class BaseDetector(object):
         if C != 3 or any(f.dtype != np.uint8 for f in frames):
             raise ValueError("run_frames needs (H, W, 3) uint8 BGR frames")
         flip = bool(self.opt.flip_test)
-        key = (len(frames), H, W, tuple(self.scales), flip, bool(getattr(self.opt, "nms", False)), depth)
+        scales = self._pipe_scales()
+        key = (len(frames), H, W, tuple(scales), flip, bool(getattr(self.opt, "nms", False)), depth)
         pipes = self.__dict__.setdefault("_pipes", {})
         if key not in pipes:
             if len(pipes) >= 4:
                 pipes.pop(next(iter(pipes))).pool.shutdown(wait=False)
-            pipes[key] = _FramePipe(self, len(frames), H, W, self.scales, flip, depth)
+            pipes[key] = FramePipe(self, len(frames), H, W, scales, flip, depth)
         return pipes[key]
 
     def _frames_and_side(self, batch):

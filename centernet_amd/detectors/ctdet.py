@@ -6,7 +6,9 @@ import time
 import numpy as np
 import torch
 
+from .. import native
 from ..decode import ctdet_decode
+from ..frame_pipe import DeviceTail
 from ..post_process import ctdet_results_batch
 from ..utils import flip_average, flip_average_batch
 from .base_detector import BaseDetector
@@ -115,71 +117,8 @@ class CtdetDetector(BaseDetector):
             reg = flip_average_batch(out['reg'], first=True) if self.opt.reg_offset else None
             return self._decode(hm, wh, reg, False)
 
-    # ---- device tail of the frame pipeline (base_detector._FramePipe)
-    def _device_tail_alloc(self, pipe):
-        """Buffers of cn_ctdet_post_process_f32 (one slice per test scale) and of cn_ctdet_merge_f32
-        for one pipe, or None when the host tail has to serve it (more detections than the kernels
-        take or than max_per_image keeps)."""
-        from .. import native
-        from ..image import get_affine_transform
-        K, nc, B, dev, S = self.opt.K, self.opt.num_classes, pipe.B, self.opt.device, len(pipe.scales)
-        if K > 128 or K > self.max_per_image:
-            return None
-        if pipe.merge and (S * K > native.MERGE_MAX_ROWS or nc > native.MERGE_MAX_CLASSES):
-            return None
-        to_source = []
-        for lv in pipe.levels:
-            m = lv.meta
-            t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
-            to_source.append(torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev))
-        R = S * K if pipe.merge else K
-        t = {'to_source': to_source,
-             'rows': torch.empty((S, B, K, 5), device=dev, dtype=torch.float32),
-             'bounds': torch.empty((S, B, nc + 1), device=dev, dtype=torch.int32),
-             'rows_host': [torch.empty((B, R, 5), dtype=torch.float32).pin_memory() for _ in range(pipe.depth)],
-             'bounds_host': [torch.empty((B, nc + 1), dtype=torch.int32).pin_memory() for _ in range(pipe.depth)]}
-        if pipe.merge:
-            t['merged_rows'] = torch.empty((B, R, 5), device=dev, dtype=torch.float32)
-            t['merged_bounds'] = torch.empty((B, nc + 1), device=dev, dtype=torch.int32)
-        return t
-
-    def _device_tail_run(self, pipe, slot, level, dets):
-        """Test scale ``level``: raw detections -> source pixels / scale, grouped by class, into slice
-        ``level`` of the tail's rows / bounds."""
-        from .. import native
-        t, K, nc = pipe.tail, self.opt.K, self.opt.num_classes
-        dets = dets.contiguous()
-        native.check(native.lib().cn_ctdet_post_process_f32(
-            native.ptr(dets), pipe.B, K, nc, native.ptr(t['to_source'][level]), 0, float(pipe.levels[level].scale),
-            native.ptr(t['rows'][level]), native.ptr(t['bounds'][level]), native.stream_ptr()),
-            "cn_ctdet_post_process_f32")
-
-    def _device_tail_finish(self, pipe, slot):
-        """After the last test scale: the scale merge (merge_outputs on the device) when there is
-        one to do, then the copies into the slot's pinned buffers."""
-        from .. import native
-        t = pipe.tail
-        rows, bounds = t['rows'][0], t['bounds'][0]
-        if pipe.merge:
-            rows, bounds = t['merged_rows'], t['merged_bounds']
-            native.check(native.lib().cn_ctdet_merge_f32(
-                native.ptr(t['rows']), native.ptr(t['bounds']), len(pipe.scales), pipe.B, self.opt.K,
-                self.opt.num_classes, int(bool(self.opt.nms)), self.max_per_image, native.ptr(rows),
-                native.ptr(bounds), native.stream_ptr()), "cn_ctdet_merge_f32")
-        t['rows_host'][slot].copy_(rows, non_blocking=True)
-        t['bounds_host'][slot].copy_(bounds, non_blocking=True)
-
-    def _device_tail_results(self, pipe, slot, n):
-        """Per image ``{class: (n, 5) float32}`` -- the rows are already in source pixels and grouped
-        by class; what is left is 80 slices per image."""
-        t, nc = pipe.tail, self.opt.num_classes
-        rows = t['rows_host'][slot].numpy().copy()        # (the pinned buffer is reused by a later batch)
-        bounds = t['bounds_host'][slot].numpy().tolist()
-        out = []
-        for i in range(n):
-            r, bd = rows[i], bounds[i]
-            out.append({j + 1: r[bd[j]:bd[j + 1]] for j in range(nc)})
-        return out
+    def _device_tail(self, pipe):
+        return CtdetTail(pipe) if CtdetTail.admits(pipe) else None
 
     def results_batch(self, dets, metas, scale):
         """Host tail of ``run_frames``: (B, K, 6) host array -> per-image ``{class: (n, 5)}``."""
@@ -188,3 +127,50 @@ class CtdetDetector(BaseDetector):
     def _post_batch(self, dets, metas, scale):
         """``post_process`` of every image of a (B, K, 6) host array (no cut: merge_outputs makes it)."""
         return ctdet_results_batch(dets, metas, self.opt.num_classes, scale, max_per_image=dets.shape[1])
+
+
+class CtdetTail(DeviceTail):
+    """cn_ctdet_post_process_f32 per test scale and, when the pipe merges, cn_ctdet_merge_f32
+    (``merge_outputs`` on the device): final rows in source pixels grouped by class, and the class bounds."""
+
+    @classmethod
+    def admits(cls, pipe):
+        """Not with more detections than the kernels take or than max_per_image keeps."""
+        det, K, S = pipe.det, pipe.det.opt.K, len(pipe.scales)
+        if K > 128 or K > det.max_per_image:
+            return False
+        return not (pipe.merge and (S * K > native.MERGE_MAX_ROWS or det.opt.num_classes > native.MERGE_MAX_CLASSES))
+
+    def __init__(self, pipe):
+        super(CtdetTail, self).__init__(pipe)
+        K, nc, B, S = self.det.opt.K, self.det.opt.num_classes, pipe.B, len(pipe.scales)
+        rows = self.output('rows', (B, S * K if pipe.merge else K, 5), torch.float32)
+        bounds = self.output('bounds', (B, nc + 1), torch.int32)
+        # one slice per test scale; a pipe without a merge has one scale, and its slice is the result
+        self.scale_rows, self.scale_bounds = rows[None], bounds[None]
+        if pipe.merge:
+            self.scale_rows = torch.empty((S, B, K, 5), device=self.device, dtype=torch.float32)
+            self.scale_bounds = torch.empty((S, B, nc + 1), device=self.device, dtype=torch.int32)
+
+    def run(self, slot, level, dets):
+        """Raw detections -> source pixels / scale, grouped by class, into slice ``level``."""
+        pipe, opt = self.pipe, self.det.opt
+        dets = dets.contiguous()
+        native.check(native.lib().cn_ctdet_post_process_f32(
+            native.ptr(dets), pipe.B, opt.K, opt.num_classes, native.ptr(self.to_source[level]), 0,
+            float(pipe.levels[level].scale), native.ptr(self.scale_rows[level]), native.ptr(self.scale_bounds[level]),
+            native.stream_ptr()), "cn_ctdet_post_process_f32")
+
+    def finish(self, slot):
+        pipe, det = self.pipe, self.det
+        if pipe.merge:
+            native.check(native.lib().cn_ctdet_merge_f32(
+                native.ptr(self.scale_rows), native.ptr(self.scale_bounds), len(pipe.scales), pipe.B, det.opt.K,
+                det.opt.num_classes, int(bool(det.opt.nms)), det.max_per_image, native.ptr(self.out['rows']),
+                native.ptr(self.out['bounds']), native.stream_ptr()), "cn_ctdet_merge_f32")
+        super(CtdetTail, self).finish(slot)
+
+    def results(self, slot, n):
+        """Per image ``{class: (n, 5) float32}``: what is left is 80 slices per image."""
+        return self.class_slices(self.host('rows', slot).numpy().copy(), self.host('bounds', slot).numpy().tolist(),
+                                 n, self.det.opt.num_classes)

@@ -14,6 +14,7 @@ import torch
 
 from .. import native
 from ..decode import ddd_decode
+from ..frame_pipe import DeviceTail
 from ..image import get_affine_transform, invert_affine, warp_affine
 from ..post_process import ddd_norm_table, ddd_post_process, ddd_results_batch
 from .base_detector import BaseDetector, InputGeometry
@@ -79,15 +80,7 @@ class DddDetector(BaseDetector):
         uploaded) through ``cn_warp_table_u8_f32_batch`` -- the warp of the other tasks with the float32
         normalisation looked up in ``norm_table``.  Bit-identical to ``pre_process``."""
         dev = self.opt.device
-        if torch.is_tensor(image):
-            if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or \
-                    not image.is_cuda or not image.is_contiguous():
-                raise ValueError("pre_process_device needs a contiguous (H, W, 3) uint8 HIP tensor")
-            frame = image
-        else:
-            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-                raise ValueError("pre_process_device needs an (H, W, 3) uint8 BGR image")
-            frame = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+        frame = self._device_frame(image)
         shape = (1, 3, self.opt.input_h, self.opt.input_w)
         if out is None:
             out = torch.empty(shape, device=dev, dtype=torch.float32)
@@ -161,12 +154,8 @@ class DddDetector(BaseDetector):
             raise ValueError("run_frames_stream of the ddd task takes (frames, calibs) pairs")
         return frames, self._calibs_for(frames, calibs)
 
-    def _pipe_for(self, frames, depth):
-        scales, self.scales = self.scales, self.scales[:1]     # ddd.py:82-88: the first scale is the result
-        try:
-            return super(DddDetector, self)._pipe_for(frames, depth)
-        finally:
-            self.scales = scales
+    def _pipe_scales(self):
+        return self.scales[:1]       # ddd.py:82-88: the first scale is the result
 
     def _pipe_level(self, height, width, scale):
         """No resize, no padding: the frame is warped straight onto the fixed input (``_frame_geometry``)."""
@@ -213,11 +202,7 @@ class DddDetector(BaseDetector):
         batch = torch.empty((len(frames), 3, self.opt.input_h, self.opt.input_w), device=self.opt.device,
                             dtype=torch.float32)
         self._warp_table(uploaded, to_input, batch)
-        dets = self._run_scale(batch, False).detach().cpu().numpy()
-        if not self.range_ok(batch):    # a clamped f32s value: re-calibrated on this batch, run again
-            dets = self._run_scale(batch, False).detach().cpu().numpy()
-            if not self.range_ok(batch):
-                raise native.NativeError("f32s forward clamps values after re-calibration")
+        dets = self._forward_checked(batch, False)
         return self.results_batch(dets, [self._meta(c, s, None)] * len(frames), 1.0, side=side)
 
     def results_batch(self, dets, metas, scale, side=None):
@@ -227,52 +212,8 @@ class DddDetector(BaseDetector):
             metas = [dict(m, calib=p) for m, p in zip(metas, side)]
         return ddd_results_batch(dets, metas, self.num_classes, self.opt.peak_thresh)
 
-    # ---- device tail of the frame pipeline (base_detector._FramePipe)
-    def _device_tail_alloc(self, pipe):
-        """Buffers of cn_ddd_post_process_f32 for one pipe, or None when the host tail has to serve it
-        (more rows than the kernel takes, or rows without the (w, h) columns)."""
-        K, nc, B, dev = self.opt.K, self.num_classes, pipe.B, self.opt.device
-        if K > 128 or not self.opt.reg_bbox:
-            return None
-        m = pipe.meta
-        t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
-        pinned = lambda shape, dtype: [torch.empty(shape, dtype=dtype).pin_memory() for _ in range(pipe.depth)]
-        return {'to_source': torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev),
-                'rows': torch.empty((B, K, 13), device=dev, dtype=torch.float32),
-                'bounds': torch.empty((B, nc + 1), device=dev, dtype=torch.int32),
-                'kept': torch.empty((B, nc), device=dev, dtype=torch.int32),
-                'rows_host': pinned((B, K, 13), torch.float32),
-                'bounds_host': pinned((B, nc + 1), torch.int32),
-                'kept_host': pinned((B, nc), torch.int32)}
-
-    def _device_tail_run(self, pipe, slot, level, dets):
-        """Raw rows -> lifted rows grouped by class, class bounds and the --peak_thresh prefix per class;
-        image b with matrix b of the slot's uploaded batch of matrices."""
-        t = pipe.tail
-        dets = dets.contiguous()
-        native.check(native.lib().cn_ddd_post_process_f32(
-            native.ptr(dets), pipe.B, self.opt.K, int(dets.shape[2]), self.num_classes, native.ptr(t['to_source']), 0,
-            native.ptr(pipe.side_dev[slot]), float(self.opt.peak_thresh), native.ptr(t['rows']),
-            native.ptr(t['bounds']), native.ptr(t['kept']), native.stream_ptr()), "cn_ddd_post_process_f32")
-
-    def _device_tail_finish(self, pipe, slot):
-        t = pipe.tail
-        for name in ('rows', 'bounds', 'kept'):
-            t[name + '_host'][slot].copy_(t[name], non_blocking=True)
-
-    def _device_tail_results(self, pipe, slot, n, side=None):
-        """Per image ``{class: (n, 13) float32}``: slices of the grouped rows (a copy of the pinned
-        buffer), the empty class a (0,) array as the reference's ``np.array([])``."""
-        t, nc = pipe.tail, self.num_classes
-        rows = t['rows_host'][slot].numpy().copy()        # (the pinned buffer is reused by a later batch)
-        bounds = t['bounds_host'][slot].numpy().tolist()
-        kept = t['kept_host'][slot].numpy().tolist()
-        out = []
-        for i in range(n):
-            r, bd, kp = rows[i], bounds[i], kept[i]
-            out.append({j + 1: r[bd[j]:bd[j] + kp[j]] if bd[j + 1] > bd[j] else np.array([], dtype=np.float32)
-                        for j in range(nc)})
-        return out
+    def _device_tail(self, pipe):
+        return DddTail(pipe) if DddTail.admits(pipe) else None
 
     def run_batch(self, images, probe=None):
         """New surface (as CtdetDetector.run_batch): a device-resident, normalised batch -> raw
@@ -284,3 +225,42 @@ class DddDetector(BaseDetector):
             return ddd_decode(o['hm'], o['rot'], dep, o['dim'], wh=o['wh'] if self.opt.reg_bbox else None,
                               reg=o['reg'] if self.opt.reg_offset else None, K=self.opt.K,
                               apply_sigmoid=True)
+
+
+class DddTail(DeviceTail):
+    """cn_ddd_post_process_f32: lifted rows grouped by class, the class bounds and per class the length of
+    the --peak_thresh prefix; image b with matrix b of the slot's uploaded batch of matrices.  No merge."""
+
+    @classmethod
+    def admits(cls, pipe):
+        """Not with more rows than the kernel takes, or rows without the (w, h) columns."""
+        return not (pipe.det.opt.K > 128 or not pipe.det.opt.reg_bbox)
+
+    def __init__(self, pipe):
+        super(DddTail, self).__init__(pipe)
+        K, nc, B = self.det.opt.K, self.det.num_classes, pipe.B
+        self.output('rows', (B, K, 13), torch.float32)
+        self.output('bounds', (B, nc + 1), torch.int32)
+        self.output('kept', (B, nc), torch.int32)
+
+    def run(self, slot, level, dets):
+        pipe, det, out = self.pipe, self.det, self.out
+        dets = dets.contiguous()
+        native.check(native.lib().cn_ddd_post_process_f32(
+            native.ptr(dets), pipe.B, det.opt.K, int(dets.shape[2]), det.num_classes, native.ptr(self.to_source[level]),
+            0, native.ptr(pipe.side_dev[slot]), float(det.opt.peak_thresh), native.ptr(out['rows']),
+            native.ptr(out['bounds']), native.ptr(out['kept']), native.stream_ptr()), "cn_ddd_post_process_f32")
+
+    def results(self, slot, n):
+        """Per image ``{class: (n, 13) float32}``: slices of the grouped rows (a copy of the pinned
+        buffer), the empty class a (0,) array as the reference's ``np.array([])``."""
+        nc = self.det.num_classes
+        rows = self.host('rows', slot).numpy().copy()        # (the pinned buffer is reused by a later batch)
+        bounds = self.host('bounds', slot).numpy().tolist()
+        kept = self.host('kept', slot).numpy().tolist()
+        out = []
+        for i in range(n):
+            r, bd, kp = rows[i], bounds[i], kept[i]
+            out.append({j + 1: r[bd[j]:bd[j] + kp[j]] if bd[j + 1] > bd[j] else np.array([], dtype=np.float32)
+                        for j in range(nc)})
+        return out

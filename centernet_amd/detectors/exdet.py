@@ -21,7 +21,8 @@ import torch
 
 from ..decode import agnex_ct_decode, exct_decode
 from .. import native
-from ..image import get_affine_transform, transform_preds
+from ..frame_pipe import DeviceTail
+from ..image import transform_preds
 from ..post_process import exdet_post_batch, exdet_results_batch
 from ..soft_nms import soft_nms
 from .base_detector import BaseDetector
@@ -115,69 +116,56 @@ class ExdetDetector(BaseDetector):
         """``post_process`` of every frame of a (n, R, 14) host array: a list of (R, 14) arrays."""
         return list(exdet_post_batch(dets, metas, scale))
 
-    # ---- device tail of the frame pipeline (base_detector._FramePipe)
-    def _device_tail_alloc(self, pipe):
-        """Buffers of cn_exdet_post_process_f32 (one slice per test scale) and cn_exdet_merge_f32 for one
-        pipe, or None (host tail) for more classes than the kernels take.  The row cap is not decided here:
-        it holds for the rows with a positive score, which only the batch itself tells (``status``)."""
-        nc, B, dev, S = self.num_classes, pipe.B, self.opt.device, len(pipe.scales)
-        if nc > native.MERGE_MAX_CLASSES:
-            return None
-        R = (2 if pipe.flip else 1) * 1000          # (num_dets of exct_decode / agnex_ct_decode)
-        cap = min(S * R, native.MERGE_MAX_ROWS)
-        to_source = []
-        for lv in pipe.levels:
-            m = lv.meta
-            t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
-            to_source.append(torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev))
-        pinned = lambda shape, dtype: [torch.empty(shape, dtype=dtype).pin_memory() for _ in range(pipe.depth)]
-        return {'R': R, 'to_source': to_source,
-                'rows': torch.empty((S, B, R, 5), device=dev, dtype=torch.float32),
-                'bounds': torch.empty((S, B, nc + 1), device=dev, dtype=torch.int32),
-                'merged_rows': torch.empty((B, cap, 5), device=dev, dtype=torch.float32),
-                'merged_bounds': torch.empty((B, nc + 1), device=dev, dtype=torch.int32),
-                'status': torch.empty((B,), device=dev, dtype=torch.int32),
-                'rows_host': pinned((B, cap, 5), torch.float32),
-                'bounds_host': pinned((B, nc + 1), torch.int32),
-                'status_host': pinned((B,), torch.int32)}
+    def _device_tail(self, pipe):
+        return ExdetTail(pipe) if ExdetTail.admits(pipe) else None
 
-    def _device_tail_run(self, pipe, slot, level, dets):
-        """Test scale ``level``: raw rows -> un-mirrored, in source pixels / scale, positive scores only,
-        grouped by class, into slice ``level`` of the tail's rows / bounds."""
-        t, lv = pipe.tail, pipe.levels[level]
+
+class ExdetTail(DeviceTail):
+    """cn_exdet_post_process_f32 per test scale and cn_exdet_merge_f32 -- always, whatever ``pipe.merge`` says:
+    soft-NMS and the cut are this task's ``merge_outputs`` for one scale too."""
+
+    @classmethod
+    def admits(cls, pipe):
+        """Not with more classes than the kernels take.  The row cap is not decided here: it holds for the rows
+        with a positive score, which only the batch itself tells (``status``)."""
+        return pipe.det.num_classes <= native.MERGE_MAX_CLASSES
+
+    def __init__(self, pipe):
+        super(ExdetTail, self).__init__(pipe)
+        nc, B, S = self.det.num_classes, pipe.B, len(pipe.scales)
+        self.R = R = (2 if pipe.flip else 1) * 1000          # (num_dets of exct_decode / agnex_ct_decode)
+        self.scale_rows = torch.empty((S, B, R, 5), device=self.device, dtype=torch.float32)
+        self.scale_bounds = torch.empty((S, B, nc + 1), device=self.device, dtype=torch.int32)
+        self.output('rows', (B, min(S * R, native.MERGE_MAX_ROWS), 5), torch.float32)
+        self.output('bounds', (B, nc + 1), torch.int32)
+        self.output('status', (B,), torch.int32)
+
+    def run(self, slot, level, dets):
+        """Raw rows -> un-mirrored, in source pixels / scale, positive scores only, grouped by class, into
+        slice ``level``."""
+        pipe, lv = self.pipe, self.pipe.levels[level]
         dets = dets.contiguous()
-        if tuple(dets.shape) != (pipe.B, t['R'], 14):
+        if tuple(dets.shape) != (pipe.B, self.R, 14):
             raise native.NativeError("exdet tail: rows of shape %s, expected %s"
-                                     % (tuple(dets.shape), (pipe.B, t['R'], 14)))
+                                     % (tuple(dets.shape), (pipe.B, self.R, 14)))
         native.check(native.lib().cn_exdet_post_process_f32(
-            native.ptr(dets), pipe.B, t['R'], self.num_classes, int(lv.meta['out_width']),
-            native.ptr(t['to_source'][level]), 0, float(lv.scale), native.ptr(t['rows'][level]),
-            native.ptr(t['bounds'][level]), native.stream_ptr()), "cn_exdet_post_process_f32")
+            native.ptr(dets), pipe.B, self.R, self.det.num_classes, int(lv.meta['out_width']),
+            native.ptr(self.to_source[level]), 0, float(lv.scale), native.ptr(self.scale_rows[level]),
+            native.ptr(self.scale_bounds[level]), native.stream_ptr()), "cn_exdet_post_process_f32")
 
-    def _device_tail_finish(self, pipe, slot):
-        """After the last test scale: the merge -- always, whatever ``pipe.merge`` says: soft-NMS and the
-        cut are this task's ``merge_outputs`` for one scale too -- then the copies into the slot's pinned
-        buffers."""
-        t = pipe.tail
+    def finish(self, slot):
+        pipe, det, out = self.pipe, self.det, self.out
         native.check(native.lib().cn_exdet_merge_f32(
-            native.ptr(t['rows']), native.ptr(t['bounds']), len(pipe.scales), pipe.B, t['R'], self.num_classes,
-            self.max_per_image, native.ptr(t['merged_rows']), native.ptr(t['merged_bounds']),
-            native.ptr(t['status']), native.stream_ptr()), "cn_exdet_merge_f32")
-        t['rows_host'][slot].copy_(t['merged_rows'], non_blocking=True)
-        t['bounds_host'][slot].copy_(t['merged_bounds'], non_blocking=True)
-        t['status_host'][slot].copy_(t['status'], non_blocking=True)
+            native.ptr(self.scale_rows), native.ptr(self.scale_bounds), len(pipe.scales), pipe.B, self.R,
+            det.num_classes, det.max_per_image, native.ptr(out['rows']), native.ptr(out['bounds']),
+            native.ptr(out['status']), native.stream_ptr()), "cn_exdet_merge_f32")
+        super(ExdetTail, self).finish(slot)
 
-    def _device_tail_results(self, pipe, slot, n):
-        """Per frame ``{class: (n, 5) float32}``, slices of a copy of the merged rows -- or None when a
-        frame of the batch had more positive rows than the merge kernel holds: the pipe then runs the
-        batch through the host tail."""
-        t, nc = pipe.tail, self.num_classes
-        if t['status_host'][slot].numpy().any():
+    def results(self, slot, n):
+        """Per frame ``{class: (n, 5) float32}``, slices of a copy of the merged rows -- or None when a frame of
+        the batch had more positive rows than the merge kernel holds: the pipe then runs the batch through the
+        host tail."""
+        if self.host('status', slot).numpy().any():
             return None
-        rows = t['rows_host'][slot].numpy().copy()        # (the pinned buffer is reused by a later batch)
-        bounds = t['bounds_host'][slot].numpy().tolist()
-        out = []
-        for i in range(n):
-            r, bd = rows[i], bounds[i]
-            out.append({j + 1: r[bd[j]:bd[j + 1]] for j in range(nc)})
-        return out
+        return self.class_slices(self.host('rows', slot).numpy().copy(), self.host('bounds', slot).numpy().tolist(),
+                                 n, self.det.num_classes)

@@ -6,7 +6,9 @@ import time
 import numpy as np
 import torch
 
+from .. import native
 from ..decode import multi_pose_decode
+from ..frame_pipe import DeviceTail
 from ..post_process import multi_pose_post_process
 from ..utils import flip_average, flip_average_batch
 from .base_detector import BaseDetector
@@ -121,61 +123,8 @@ class MultiPoseDetector(BaseDetector):
         without NMS (multi_pose.py:62-81).  ``arrays``: the same rows as a (K, 39) float32 array."""
         return [{1: d[1] if arrays else d[1].tolist()} for d in self._post_batch(dets, metas, scale)]
 
-    # ---- device tail of the frame pipeline (base_detector._FramePipe)
-    def _device_tail_alloc(self, pipe):
-        """Buffers of cn_multi_pose_post_process_f32 (one slice per test scale) and of
-        cn_multi_pose_merge_f32 for one pipe, or None when the host tail has to serve it (more
-        detections than the kernels take)."""
-        from .. import native
-        from ..image import get_affine_transform
-        K, B, dev, S = self.opt.K, pipe.B, self.opt.device, len(pipe.scales)
-        if K > 128 or (pipe.merge and S * K > native.MERGE_MAX_ROWS):
-            return None
-        to_source = []
-        for lv in pipe.levels:
-            m = lv.meta
-            t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
-            to_source.append(torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(dev))
-        R = S * K if pipe.merge else K
-        t = {'to_source': to_source,
-             'rows': torch.empty((S, B, K, ROW), device=dev, dtype=torch.float32),
-             'rows_host': [torch.empty((B, R, ROW), dtype=torch.float32).pin_memory() for _ in range(pipe.depth)]}
-        if pipe.merge:
-            t['merged_rows'] = torch.empty((B, R, ROW), device=dev, dtype=torch.float32)
-        return t
-
-    def _device_tail_run(self, pipe, slot, level, dets):
-        """Test scale ``level``: raw detections -> source pixels / scale, into slice ``level`` of the
-        tail's rows."""
-        from .. import native
-        t = pipe.tail
-        dets = dets.contiguous()
-        native.check(native.lib().cn_multi_pose_post_process_f32(
-            native.ptr(dets), pipe.B, self.opt.K, native.ptr(t['to_source'][level]), 0,
-            float(pipe.levels[level].scale), native.ptr(t['rows'][level]), native.stream_ptr()),
-            "cn_multi_pose_post_process_f32")
-
-    def _device_tail_finish(self, pipe, slot):
-        """After the last test scale: the scale merge (merge_outputs on the device) when there is one
-        to do, then the copy into the slot's pinned buffer."""
-        from .. import native
-        t = pipe.tail
-        rows = t['rows'][0]
-        if pipe.merge:
-            rows = t['merged_rows']
-            native.check(native.lib().cn_multi_pose_merge_f32(
-                native.ptr(t['rows']), len(pipe.scales), pipe.B, self.opt.K, int(bool(self.opt.nms)),
-                native.ptr(rows), native.stream_ptr()), "cn_multi_pose_merge_f32")
-        t['rows_host'][slot].copy_(rows, non_blocking=True)
-
-    def _device_tail_results(self, pipe, slot, n, arrays=False):
-        """Per image ``{1: rows}``: the rows are final; the host copies them out of the pinned buffer
-        (a later batch reuses it) as nested lists, or with ``arrays`` as one (S * K, 39) array each."""
-        rows = pipe.tail['rows_host'][slot].numpy()[:n]
-        if arrays:
-            rows = rows.copy()
-            return [{1: rows[i]} for i in range(n)]
-        return [{1: r} for r in rows.tolist()]
+    def _device_tail(self, pipe):
+        return MultiPoseTail(pipe) if MultiPoseTail.admits(pipe) else None
 
     def post_process(self, dets, meta, scale=1):
         """Output-grid units -> image coordinates of the unscaled frame (multi_pose.py:62-72)."""
@@ -199,3 +148,49 @@ class MultiPoseDetector(BaseDetector):
             from ..soft_nms import soft_nms_39
             soft_nms_39(people, Nt=0.5, method=2)
         return {1: people if arrays else people.tolist()}
+
+
+class MultiPoseTail(DeviceTail):
+    """cn_multi_pose_post_process_f32 per test scale and, when the pipe merges, cn_multi_pose_merge_f32
+    (``merge_outputs`` on the device): final 39-column rows in source pixels."""
+
+    @classmethod
+    def admits(cls, pipe):
+        """Not with more detections than the kernels take."""
+        K = pipe.det.opt.K
+        return not (K > 128 or (pipe.merge and len(pipe.scales) * K > native.MERGE_MAX_ROWS))
+
+    def __init__(self, pipe):
+        super(MultiPoseTail, self).__init__(pipe)
+        K, B, S = self.det.opt.K, pipe.B, len(pipe.scales)
+        rows = self.output('rows', (B, S * K if pipe.merge else K, ROW), torch.float32)
+        # one slice per test scale; a pipe without a merge has one scale, and its slice is the result
+        self.scale_rows = rows[None]
+        if pipe.merge:
+            self.scale_rows = torch.empty((S, B, K, ROW), device=self.device, dtype=torch.float32)
+
+    def run(self, slot, level, dets):
+        """Raw detections -> source pixels / scale, into slice ``level``."""
+        pipe = self.pipe
+        dets = dets.contiguous()
+        native.check(native.lib().cn_multi_pose_post_process_f32(
+            native.ptr(dets), pipe.B, self.det.opt.K, native.ptr(self.to_source[level]), 0,
+            float(pipe.levels[level].scale), native.ptr(self.scale_rows[level]), native.stream_ptr()),
+            "cn_multi_pose_post_process_f32")
+
+    def finish(self, slot):
+        pipe, det = self.pipe, self.det
+        if pipe.merge:
+            native.check(native.lib().cn_multi_pose_merge_f32(
+                native.ptr(self.scale_rows), len(pipe.scales), pipe.B, det.opt.K, int(bool(det.opt.nms)),
+                native.ptr(self.out['rows']), native.stream_ptr()), "cn_multi_pose_merge_f32")
+        super(MultiPoseTail, self).finish(slot)
+
+    def results(self, slot, n):
+        """Per image ``{1: rows}``: the rows are final; the host copies them out of the pinned buffer as nested
+        lists, or with ``arrays`` as one (S * K, 39) array each."""
+        rows = self.host('rows', slot).numpy()[:n]
+        if self.arrays:
+            rows = rows.copy()
+            return [{1: rows[i]} for i in range(n)]
+        return [{1: r} for r in rows.tolist()]

@@ -6,11 +6,33 @@ from .ddd_utils import ddd2locrot
 from .image import transform_preds
 
 
-def _split_by_class(rows, classes, num_classes):
-    """{1-based class: rows of that class in their original order} via one stable sort."""
+def _class_order(classes, num_classes):
+    """One stable sort by class instead of ``num_classes`` boolean masks: (the order that groups integer
+    ``classes`` ascending, rows of a class in their original order; the num_classes + 1 class bounds in it)."""
     order = np.argsort(classes, kind='stable')
-    rows, classes = rows[order], classes[order]
-    edges = np.searchsorted(classes, np.arange(num_classes + 1))
+    return order, np.searchsorted(classes[order], np.arange(num_classes + 1))
+
+
+def _inverse_maps(metas):
+    """The frames grouped by geometry: [(indices of the frames, their (2, 3) float64 output grid -> source
+    map)], one entry per distinct (centre, extent, output grid) in order of first appearance -- every frame of a
+    video shares one.  ``get_affine_transform`` reads centre and extent as float32, so their float32 bytes
+    decide the map."""
+    from .image import get_affine_transform
+    groups = {}
+    for i, m in enumerate(metas):
+        key = (np.asarray(m['c'], np.float32).tobytes(), np.asarray(m['s'], np.float32).tobytes(),
+               int(m['out_width']), int(m['out_height']))
+        groups.setdefault(key, []).append(i)
+    return [(idx, get_affine_transform(metas[idx[0]]['c'], metas[idx[0]]['s'], 0,
+                                       (metas[idx[0]]['out_width'], metas[idx[0]]['out_height']), inv=1))
+            for idx in groups.values()]
+
+
+def _split_by_class(rows, classes, num_classes):
+    """{1-based class: rows of that class in their original order}."""
+    order, edges = _class_order(classes, num_classes)
+    rows = rows[order]
     return {j + 1: rows[edges[j]:edges[j + 1]].tolist() for j in range(num_classes)}
 
 
@@ -112,19 +134,11 @@ def ctdet_results_batch(dets, metas, num_classes, scale=1, max_per_image=100):
     80-class Python loop per image.  Images that share their geometry (every frame of a video:
     same centre, extent and output grid) share ONE inverse map and go through it together; the
     class grouping of the whole batch is one stable sort."""
-    from .image import apply_affine, get_affine_transform
+    from .image import apply_affine
     dets = np.asarray(dets)
     B, K, _ = dets.shape
-    # inverse maps: one per distinct (centre, extent, output grid)
-    groups = {}
-    for i, m in enumerate(metas):
-        key = (np.asarray(m['c'], np.float32).tobytes(), np.asarray(m['s'], np.float32).tobytes(),
-               int(m['out_width']), int(m['out_height']))
-        groups.setdefault(key, []).append(i)
     xy = np.empty((B, K, 4), np.float32)
-    for idx in groups.values():
-        m = metas[idx[0]]
-        to_source = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+    for idx, to_source in _inverse_maps(metas):
         sel = idx if len(idx) < B else slice(None)
         pts = dets[sel, :, 0:4].reshape(-1, 2)
         xy[sel] = apply_affine(pts, to_source).astype(np.float32).reshape(-1, K, 4)
@@ -145,10 +159,8 @@ def ctdet_results_batch(dets, metas, num_classes, scale=1, max_per_image=100):
                 kth = K - max_per_image
                 thresh = np.partition(rows[i, :, 4], kth)[kth]
                 keep = rows[i, :, 4] >= thresh
-            r, c = rows[i][keep], cls[i][keep]
-            order = np.argsort(c, kind='stable')
-            r, c = r[order], c[order]
-            bounds = np.searchsorted(c, np.arange(num_classes + 1))
+            order, bounds = _class_order(cls[i][keep], num_classes)
+            r = rows[i][keep][order]
             out.append({j + 1: r[bounds[j]:bounds[j + 1]] for j in range(num_classes)})
         return out
     order = np.argsort(cls, axis=1, kind='stable')
@@ -220,19 +232,15 @@ def ddd_results_batch(dets, metas, num_classes, peak_thresh):
     ``(0,)`` array, a class whose rows were all cut ``(0, 13)``.  ``metas[i]``: 'c', 's', 'out_width',
     'out_height' and image i's own 'calib' (the reference lifts a batch with ``calibs[0]``; its detector is
     single-image).  Rows whose class is no integer in [0, num_classes) match no ``cls == j`` and are dropped."""
-    from .image import get_affine_transform
     dets = np.asarray(dets, np.float32)
     if dets.ndim != 3 or dets.shape[2] != 18:
         raise ValueError("ddd_results_batch needs (B, K, 18) rows: the 3-D stage reads the (w, h) columns "
                          "(--not_reg_bbox rows have none; the reference cannot lift them either)")
     B, K, _ = dets.shape
-    maps = {}
+    maps = _inverse_maps(metas)
     to_source = np.empty((B, 2, 3), np.float64)
-    for i, m in enumerate(metas):
-        key = (np.asarray(m['c']).tobytes(), np.asarray(m['s']).tobytes(), int(m['out_width']), int(m['out_height']))
-        if key not in maps:
-            maps[key] = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
-        to_source[i] = maps[key]
+    for idx, t in maps:
+        to_source[idx] = t
     calibs = np.stack([np.asarray(m['calib'], np.float32).reshape(3, 4) for m in metas])
     rows = ddd_lift_rows(dets, to_source[0] if len(maps) == 1 else to_source, calibs)
     cls = dets[:, :, 17]
@@ -256,22 +264,15 @@ def exdet_post_batch(dets, metas, scale=1):
     second half of every frame's rows un-mirrored (``x1' = out_w - x2``, ``x2' = out_w - x1`` in float32),
     both box corners through the float64 inverse map and rounded once to float32, then ``/ scale`` in
     float32.  Frames that share their geometry go through one inverse map together."""
-    from .image import apply_affine, get_affine_transform
+    from .image import apply_affine
     rows = np.array(dets, dtype=np.float32)
     n, R, _ = rows.shape
     half = R // 2
-    groups = {}
-    for i, m in enumerate(metas):
-        key = (np.asarray(m['c'], np.float32).tobytes(), np.asarray(m['s'], np.float32).tobytes(),
-               int(m['out_width']), int(m['out_height']))
-        groups.setdefault(key, []).append(i)
-    for idx in groups.values():
-        m = metas[idx[0]]
+    for idx, to_source in _inverse_maps(metas):
         sel = idx if len(idx) < n else slice(None)
-        out_w = m['out_width']
+        out_w = metas[idx[0]]['out_width']
         left, right = rows[sel, half:, 0].copy(), rows[sel, half:, 2].copy()
         rows[sel, half:, 0], rows[sel, half:, 2] = out_w - right, out_w - left
-        to_source = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
         pts = rows[sel, :, 0:4].reshape(-1, 2)
         rows[sel, :, 0:4] = apply_affine(pts, to_source).astype(np.float32).reshape(-1, R, 4)
     rows[:, :, 0:4] /= scale
@@ -287,10 +288,9 @@ def exdet_merge_rows(rows, num_classes, max_per_image=100):
     with np.errstate(invalid='ignore'):
         keep = (score > 0) & (cls >= 0) & (cls < num_classes) & (cls == np.floor(cls))    # `classes == j`
     kept = rows[keep]
-    cls = kept[:, 13].astype(np.int64)
-    order = np.argsort(cls, kind='stable')
+    order, edges = _class_order(kept[:, 13].astype(np.int64), num_classes)
     boxes = np.ascontiguousarray(kept[order][:, 0:5])
-    edges = np.searchsorted(cls[order], np.arange(num_classes + 1)).tolist()
+    edges = edges.tolist()
     for j in range(num_classes):
         if edges[j + 1] - edges[j] > 1:
             soft_nms(boxes[edges[j]:edges[j + 1]], Nt=0.5, method=2)       # in place, on the class's slice

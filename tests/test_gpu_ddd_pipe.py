@@ -321,7 +321,7 @@ def test_run_frames_equals_the_host_tail_on_its_own_raw_rows(dev):
     assert 0 < kept < 4 * 40                                       # a real cut
     _note(test="pipe_vs_host_tail", U=bars[0], alpha_bar=bars[1], rotation_y_bar=bars[2], alpha_max=seen[0],
           rotation_y_max=seen[1])
-    pinned = pipe.tail['rows_host'][0].numpy()
+    pinned = pipe.tail.host('rows', 0).numpy()
     assert not any(np.shares_memory(r[j], pinned) for r in got for j in r)
 
 

@@ -352,9 +352,9 @@ def test_stream_equals_run_frames_batch_by_batch(dev, hourglass):
 def test_more_classes_than_the_kernels_take_keep_the_host_tail(dev, hourglass):
     det = _configure(hourglass, True)
     pipe = det._pipe_for(_frames(1, 2), 1)
-    assert pipe.tail is not None and pipe.tail['R'] == 2000
+    assert pipe.tail is not None and pipe.tail.R == 2000
     nc, det.num_classes = det.num_classes, native.MERGE_MAX_CLASSES + 1
     try:
-        assert det._device_tail_alloc(pipe) is None
+        assert det._device_tail(pipe) is None
     finally:
         det.num_classes = nc

@@ -250,7 +250,7 @@ def test_device_tail_equals_host_tail_on_the_same_detections(dev, args):
         assert np.array_equal(_bits(np.array(a[1], np.float32)), _bits(np.array(b[1], np.float32)))
         assert isinstance(arr[1], np.ndarray) and arr[1].dtype == np.float32 and arr[1].shape == (S * opt.K, ROW)
         assert np.array_equal(_bits(arr[1]), _bits(np.array(a[1], np.float32)))
-    pinned = pipe.tail['rows_host'][0].numpy()
+    pinned = pipe.tail.host('rows', 0).numpy()
     assert not any(np.shares_memory(arr[1], pinned) for arr in got_arrays)      # a copy, not a view
     assert det.run_frames(frames, arrays=True)[0][1].shape == (S * opt.K, ROW)
 

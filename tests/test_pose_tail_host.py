@@ -1,6 +1,6 @@
 """The multi_pose device tail, the parts that need no GPU.
 
-1. The form of soft-NMS that ``multi_pose_merge_kernel`` (cn_merge.hip) runs on 39-column rows, restated
+1. The form of soft-NMS that ``multi_pose_merge_kernel`` (cn_tail.hip) runs on 39-column rows, restated
    in numpy: only boxes and scores move during the greedy steps; which input row's joints sit at a position
    is tracked in ``jsrc`` (exchanged by the argmax swap and by every discard) and the joints are gathered
    once at the end.  Held equal to ``soft_nms_39`` (``cn_soft_nms_f32``, pinned to the reference's cython
@@ -169,9 +169,10 @@ def _stub(scales, nms):
 def test_arrays_keyword_on_the_host_tail():
     """run_frames(arrays=True) / run_frames_stream(arrays=True): the pose host tail returns {1: (n, 39)
     float32 array} with the bits of the list form; the default is the list form."""
-    from centernet_amd.detectors.base_detector import BaseDetector, _FramePipe
+    from centernet_amd.detectors.base_detector import BaseDetector
+    from centernet_amd.frame_pipe import FramePipe
     from centernet_amd.detectors.ctdet import CtdetDetector
-    for fn in (BaseDetector.run_frames, BaseDetector.run_frames_stream, _FramePipe.collect):
+    for fn in (BaseDetector.run_frames, BaseDetector.run_frames_stream, FramePipe.collect):
         assert inspect.signature(fn).parameters["arrays"].default is False, fn
     assert object.__new__(CtdetDetector)._arrays_kw(True) == {}       # ctdet returns arrays as it is
     rng = np.random.RandomState(5)

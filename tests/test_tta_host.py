@@ -1,4 +1,4 @@
-"""The parallel form of soft-NMS that the device merge (cn_merge.hip) runs, restated in numpy and held
+"""The parallel form of soft-NMS that the device merge (cn_tail.hip) runs, restated in numpy and held
 equal to the host soft-NMS ``cn_soft_nms_f32`` (pinned to the reference's cython, test_oracle_ref.py)
 on seeded arrays: the whole in-place array, rows past the kept count included, bit for bit.
 

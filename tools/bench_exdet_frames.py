@@ -103,10 +103,10 @@ def main():
     seeded = torch.from_numpy(seeded_rows(rng, B, 2000, lv.meta['out_width'], lv.meta['out_height'], 600)).to(net_rows.device)
 
     def device_tail(raw):
-        det._device_tail_run(pipe, 0, 0, raw)
-        det._device_tail_finish(pipe, 0)
+        pipe.tail.run(0, 0, raw)
+        pipe.tail.finish(0)
         torch.cuda.synchronize()
-        return det._device_tail_results(pipe, 0, B)
+        return pipe.tail.results(0, B)
 
     def host_tail(raw):
         return det.results_batch(raw.cpu().numpy(), [lv.meta] * B, lv.scale)
