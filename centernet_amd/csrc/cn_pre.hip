@@ -244,6 +244,99 @@ extern "C" int cn_resize_bilinear_u8(const uint8_t *image_hwc, int H, int W, int
     return CN_OK;
 }
 
+// ---- mixed-size batches: N images of their own sizes, packed in one uint8 buffer, one launch ----
+// The geometry of image blockIdx.z comes from its cn_image_desc in device memory (it travels with the
+// frames on the copy stream); the pixel arithmetic is warp_pixel / row_base / resize_pixel above.
+namespace {
+
+struct RaggedWarpArgs {
+    int oh, ow;
+    double mean[3], stdv[3];
+    float *out;          // (N, 3|6, oh, ow)
+    int flip;
+    size_t out_stride;
+};
+
+__global__ void warp_normalize_ragged_kernel(const uint8_t *__restrict__ packed,
+                                             const cn_image_desc *__restrict__ descs, const RaggedWarpArgs a)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    // uniform over the workgroup: one read through the const __restrict__ pointer, kept in scalar registers
+    const cn_image_desc d = descs[blockIdx.z];
+    if (x >= a.ow || d.H <= 0 || d.W <= 0) return;
+    int v[3];
+    float *out = a.out + (size_t)blockIdx.z * a.out_stride;
+    warp_pixel<3>(packed + d.offset, d.H, d.W, (size_t)d.pitch, d.dst_to_src, x, y,
+                  row_base(d.dst_to_src, 1, 2, y), row_base(d.dst_to_src, 4, 5, y), v);
+    const size_t plane = (size_t)a.oh * a.ow;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double n = ((double)v[c] / 255.0 - a.mean[c]) / a.stdv[c];
+        const float f = (float)n;
+        out[c * plane + (size_t)y * a.ow + x] = f;
+        if (a.flip) out[(3 + c) * plane + (size_t)y * a.ow + (a.ow - 1 - x)] = f;
+    }
+}
+
+__global__ void resize_u8_ragged_kernel(const uint8_t *__restrict__ packed_in,
+                                        const cn_image_desc *__restrict__ in_descs,
+                                        uint8_t *__restrict__ packed_out,
+                                        const cn_image_desc *__restrict__ out_descs)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    const cn_image_desc s = in_descs[blockIdx.z], d = out_descs[blockIdx.z];
+    if (x >= d.W || y >= d.H || s.H <= 0 || s.W <= 0) return;
+    const uint8_t *img = packed_in + s.offset;
+    uint8_t *o = packed_out + d.offset + (size_t)y * d.pitch + (size_t)x * 3;
+    if (s.H == d.H && s.W == d.W) {      // cv::resize: same size = copy
+        const uint8_t *p = img + (size_t)y * s.pitch + (size_t)x * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = p[c];
+        return;
+    }
+    int v[3];
+    resize_pixel<3>(img, s.H, s.W, (size_t)s.pitch, d.scale_x, d.scale_y,
+                    (s.H == 2 * d.H && s.W == 2 * d.W) ? 1 : 0, x, y, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (uint8_t)v[c];
+}
+
+}  // namespace
+
+extern "C" int cn_warp_normalize_u8_f32_ragged(const uint8_t *packed, const cn_image_desc *descs_dev, int N,
+                                               int out_h, int out_w, const float *mean3, const float *std3,
+                                               int flip_concat, float *out_nchw, void *stream)
+{
+    if (!packed || !descs_dev || !mean3 || !std3 || !out_nchw) return CN_ERR_NULL;
+    if (out_h <= 0 || out_w <= 0 || out_h > 65535 || N <= 0 || N > 65535) return CN_ERR_SHAPE;
+    RaggedWarpArgs a = {};
+    a.oh = out_h; a.ow = out_w;
+    for (int c = 0; c < 3; ++c) {
+        if (std3[c] == 0.f) return CN_ERR_SHAPE;
+        a.mean[c] = (double)mean3[c];
+        a.stdv[c] = (double)std3[c];
+    }
+    a.out = out_nchw; a.flip = flip_concat ? 1 : 0;
+    a.out_stride = (size_t)(a.flip ? 6 : 3) * out_h * out_w;
+    dim3 grid(cn_cdiv(out_w, 128), out_h, N);
+    hipLaunchKernelGGL(warp_normalize_ragged_kernel, grid, dim3(128), 0, (hipStream_t)stream, packed, descs_dev, a);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_resize_bilinear_u8_ragged(const uint8_t *packed_in, const cn_image_desc *in_descs_dev,
+                                            uint8_t *packed_out, const cn_image_desc *out_descs_dev, int N,
+                                            int max_out_h, int max_out_w, void *stream)
+{
+    if (!packed_in || !in_descs_dev || !packed_out || !out_descs_dev) return CN_ERR_NULL;
+    if (max_out_h <= 0 || max_out_w <= 0 || max_out_h > 65535 || N <= 0 || N > 65535) return CN_ERR_SHAPE;
+    dim3 grid(cn_cdiv(max_out_w, 128), max_out_h, N);
+    hipLaunchKernelGGL(resize_u8_ragged_kernel, grid, dim3(128), 0, (hipStream_t)stream, packed_in, in_descs_dev,
+                       packed_out, out_descs_dev);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 // ---- the same two operations on the HOST (callers that keep BaseDetector.pre_process on host
 // cores, e.g. DataLoader workers: base_detector.py:37-65): the integer algorithms above, pixel by
 // pixel in C; channels <= 4.

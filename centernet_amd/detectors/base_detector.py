@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import native
-from ..frame_pipe import FramePipe
+from ..frame_pipe import FramePipe, ImagePipe
 from ..image import get_affine_transform, invert_affine, normalize_chw, resize_bilinear, warp_affine
 from ..model import create_model, load_model
 
@@ -259,12 +259,21 @@ class BaseDetector(object):
         """One batch, synchronously, frame by frame through ``pre_process_device`` at every test scale
         (the comparison path of the pipeline, and its re-run path after an f32s re-calibration)."""
         uploaded = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.opt.device)
+        return self._run_uploaded_sync(uploaded, scales, **kw)
+
+    def _run_images_sync(self, images, scales, **kw):
+        """``_run_frames_sync`` for images of any sizes in the fixed-resolution mode (every image gives the same
+        network input size): each image uploaded on its own, pre-processed into its slice of the batch, with
+        its own meta."""
+        return self._run_uploaded_sync([self._device_frame(f) for f in images], scales, **kw)
+
+    def _run_uploaded_sync(self, uploaded, scales, **kw):
         flip = bool(self.opt.flip_test)
         k = 2 if flip else 1
         per_scale = []
         for scale in scales:
-            g = self.input_geometry(uploaded.shape[1], uploaded.shape[2], scale)
-            batch = torch.empty((k * len(frames), 3, g.inp_h, g.inp_w), device=self.opt.device,
+            g = self.input_geometry(int(uploaded[0].shape[0]), int(uploaded[0].shape[1]), scale)
+            batch = torch.empty((k * len(uploaded), 3, g.inp_h, g.inp_w), device=self.opt.device,
                                 dtype=torch.float32)
             metas = [self.pre_process_device(frame, scale, out=batch[k * i:k * i + k])[1]
                      for i, frame in enumerate(uploaded)]
@@ -329,6 +338,72 @@ class BaseDetector(object):
                 yield pipe.collect(j, fr, arrays)
             pipe.submit(n, frames, side)
             pending.append((n, frames))
+            n += 1
+        while pending:
+            j, fr = pending.popleft()
+            yield pipe.collect(j, fr, arrays)
+
+    # ------------------------------------------------------------------ images of mixed sizes
+    def _images_one_size(self, images, what):
+        """Argument check of ``run_images`` / ``run_images_stream``; True when the images have one size."""
+        if len(images) == 0:
+            raise ValueError("%s needs at least one image" % what)
+        for f in images:
+            if not isinstance(f, np.ndarray) or f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8:
+                raise ValueError("%s needs (H, W, 3) uint8 BGR images" % what)
+        one = len({f.shape for f in images}) == 1
+        if not self.opt.fix_res and not one:
+            raise ValueError("%s with --keep_res: images of mixed sizes give network inputs of mixed sizes, which "
+                             "one batch cannot hold (drop --keep_res, or batch images of one size)" % what)
+        return one
+
+    def _image_pipe_for(self, images, depth):
+        flip = bool(self.opt.flip_test)
+        scales = self._pipe_scales()
+        key = ("images", len(images), tuple(scales), flip, bool(getattr(self.opt, "nms", False)), depth)
+        pipes = self.__dict__.setdefault("_pipes", {})
+        if key not in pipes:
+            if len(pipes) >= 4:
+                pipes.pop(next(iter(pipes))).pool.shutdown(wait=False)
+            pipes[key] = ImagePipe(self, len(images), scales, flip, depth)
+        return pipes[key]
+
+    def run_images(self, images, arrays=False):
+        """A list of (H_i, W_i, 3) uint8 BGR images of ANY sizes -> list of per-image results, what
+        ``run(image)['results']`` returns for each (every test scale, flip-test and --nms as set) -- ``run_frames``
+        for a dataset instead of a video.  Fixed-resolution mode: every image is warped into the same network
+        input, so the batch is ``run_frames``' batch; the images are packed back to back into ONE uint8 upload
+        with a table of per-image descriptors, pre-processed in one launch per test scale (plus one resize
+        launch where the scale resizes), and the tail kernels map every image back with its own inverse map.
+        With --keep_res mixed sizes raise ``ValueError`` (images of one size go to ``run_frames``).
+        ``arrays``: as ``run_frames``."""
+        if self._images_one_size(images, "run_images") and not self.opt.fix_res:
+            return self.run_frames(images, arrays)
+        pipe = self._image_pipe_for(images, 1)
+        pipe.submit(0, images)
+        return pipe.collect(0, images, arrays)
+
+    def run_images_stream(self, batches, depth=3, arrays=False):
+        """``run_images`` over an iterable of batches (lists of images of any sizes, every batch of one length
+        B -- another length raises ``ValueError``), pipelined as ``run_frames_stream``.  Yields the per-image
+        results batch by batch, in order.  With --keep_res every batch goes to ``run_frames`` on its own."""
+        pipe, B, pending, n = None, None, collections.deque(), 0
+        for images in batches:
+            self._images_one_size(images, "run_images_stream")
+            if B is None:
+                B = len(images)
+            elif len(images) != B:
+                raise ValueError("run_images_stream needs batches of one length (%d, then %d)" % (B, len(images)))
+            if not self.opt.fix_res:             # (images of one size, or the check above has raised)
+                yield self.run_frames(images, arrays)
+                continue
+            if pipe is None:
+                pipe = self._image_pipe_for(images, depth)
+            if len(pending) == depth:
+                j, fr = pending.popleft()
+                yield pipe.collect(j, fr, arrays)
+            pipe.submit(n, images)
+            pending.append((n, images))
             n += 1
         while pending:
             j, fr = pending.popleft()

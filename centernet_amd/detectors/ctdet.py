@@ -157,7 +157,7 @@ class CtdetTail(DeviceTail):
         pipe, opt = self.pipe, self.det.opt
         dets = dets.contiguous()
         native.check(native.lib().cn_ctdet_post_process_f32(
-            native.ptr(dets), pipe.B, opt.K, opt.num_classes, native.ptr(self.to_source[level]), 0,
+            native.ptr(dets), pipe.B, opt.K, opt.num_classes, *self.source_map(slot, level),
             float(pipe.levels[level].scale), native.ptr(self.scale_rows[level]), native.ptr(self.scale_bounds[level]),
             native.stream_ptr()), "cn_ctdet_post_process_f32")
 

@@ -185,6 +185,13 @@ class DddDetector(BaseDetector):
         memory and uploaded on the copy stream with their frames."""
         return super(DddDetector, self).run_frames_stream(batches, depth)
 
+    def run_images(self, images, arrays=False):
+        raise NotImplementedError("run_images: the ddd task has its own pre-process and a projection matrix per "
+                                  "frame; use run_frames(frames, calibs=) on frames of one size")
+
+    def run_images_stream(self, batches, depth=3, arrays=False):
+        self.run_images(None)
+
     def _run_scale(self, images, flip):
         """Network + decode of the frame pipeline: the centre map's sigmoid and the depth transform of
         the K gathered cells are inside ``cn_ddd_decode_f32``; raw (B, K, 18) rows, asynchronous."""

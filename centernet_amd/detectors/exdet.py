@@ -150,7 +150,7 @@ class ExdetTail(DeviceTail):
                                      % (tuple(dets.shape), (pipe.B, self.R, 14)))
         native.check(native.lib().cn_exdet_post_process_f32(
             native.ptr(dets), pipe.B, self.R, self.det.num_classes, int(lv.meta['out_width']),
-            native.ptr(self.to_source[level]), 0, float(lv.scale), native.ptr(self.scale_rows[level]),
+            *self.source_map(slot, level), float(lv.scale), native.ptr(self.scale_rows[level]),
             native.ptr(self.scale_bounds[level]), native.stream_ptr()), "cn_exdet_post_process_f32")
 
     def finish(self, slot):

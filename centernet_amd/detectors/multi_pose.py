@@ -174,7 +174,7 @@ class MultiPoseTail(DeviceTail):
         pipe = self.pipe
         dets = dets.contiguous()
         native.check(native.lib().cn_multi_pose_post_process_f32(
-            native.ptr(dets), pipe.B, self.det.opt.K, native.ptr(self.to_source[level]), 0,
+            native.ptr(dets), pipe.B, self.det.opt.K, *self.source_map(slot, level),
             float(pipe.levels[level].scale), native.ptr(self.scale_rows[level]), native.stream_ptr()),
             "cn_multi_pose_post_process_f32")
 

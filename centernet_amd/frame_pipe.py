@@ -1,5 +1,6 @@
-"""The frame pipe of ``run_frames`` / ``run_frames_stream`` (``FramePipe``) and the base class of a task's
-device tail (``DeviceTail``): what runs behind the decode of every test scale, on the launch stream, so
+"""The frame pipe of ``run_frames`` / ``run_frames_stream`` (``FramePipe``), its form for batches of images of
+mixed sizes (``ImagePipe`` with ``ImageTables``: ``run_images`` / ``run_images_stream``) and the base class of a
+task's device tail (``DeviceTail``): what runs behind the decode of every test scale, on the launch stream, so
 that the host only slices pinned rows.  The task classes (``detectors/*.py``) supply a ``DeviceTail``
 subclass each -- the admission test, the kernel calls and the result shape -- through one hook,
 ``BaseDetector._device_tail(pipe)``."""
@@ -31,12 +32,21 @@ class DeviceTail(object):
     def __init__(self, pipe):
         self.pipe, self.det, self.device = pipe, pipe.det, pipe.det.opt.device
         self.out, self._host = {}, {}
-        # output grid -> source pixels of every test scale, float64 (2, 3) row-major, on the device
+        # output grid -> source pixels of every test scale, float64 (2, 3) row-major, on the device (a pipe of
+        # mixed-size images keeps one map per image, per slot, itself: ``source_map``)
         self.to_source = []
-        for lv in pipe.levels:
+        for lv in ([] if pipe.to_source_dev is not None else pipe.levels):
             m = lv.meta
             t = get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
             self.to_source.append(torch.from_numpy(np.ascontiguousarray(t, np.float64).reshape(-1)).to(self.device))
+
+    def source_map(self, slot, level):
+        """(device pointer, per_image) of test scale ``level`` for the post-process kernels: the level's one map,
+        or under a pipe of mixed-size images the (B, 6) maps of the batch in ``slot``."""
+        per_slot = self.pipe.to_source_dev
+        if per_slot is None:
+            return native.ptr(self.to_source[level]), 0
+        return native.ptr(per_slot[slot][level]), 1
 
     def output(self, name, shape, dtype):
         """Declare a final buffer: its device tensor (returned, and ``self.out[name]``) and one pinned host
@@ -102,12 +112,12 @@ class FramePipe(object):
     copies, ``submit`` takes the batch's side array, uploads it on the copy stream with the frames, and the
     tail reads ``pipe.side_dev[slot]`` / ``pipe.side_host[slot]``."""
 
+    to_source_dev = None     # (ImagePipe: per slot the (S, B, 6) output grid -> source maps of its batch)
+
     def __init__(self, det, B, H, W, scales, flip, depth):
-        opt, dev = det.opt, det.opt.device
-        self.det, self.B, self.H, self.W, self.depth = det, B, H, W, depth
-        self.scales, self.flip = tuple(scales), bool(flip)
-        # merge_outputs does more than pass one scale through: soft-NMS, and a cut of S * K rows
-        self.merge = len(self.scales) > 1 or bool(getattr(opt, "nms", False))
+        dev = det.opt.device
+        self._setup(det, B, scales, flip, depth)
+        self.H, self.W = H, W
         self.levels = []
         for scale in self.scales:
             g, to_input, meta = det._pipe_level(H, W, scale)
@@ -120,11 +130,20 @@ class FramePipe(object):
                                   dtype=torch.float32)))
         first = self.levels[0]        # (the single-scale pipe's own names)
         self.scale, self.g, self.meta, self.batch = first.scale, first.g, first.meta, first.batch
-        self.mean = (ctypes.c_float * 3)(*[float(v) for v in det.mean.reshape(-1)])
-        self.std = (ctypes.c_float * 3)(*[float(v) for v in det.std.reshape(-1)])
         self.pinned_in = [torch.empty((B, H, W, 3), dtype=torch.uint8).pin_memory() for _ in range(depth)]
         self.np_in = [t.numpy() for t in self.pinned_in]
         self.dev_in = [torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(depth)]
+        self._setup_tail()
+
+    def _setup(self, det, B, scales, flip, depth):
+        """What does not depend on the frames' geometry: streams, events, digests, staging threads, side input."""
+        opt, dev = det.opt, det.opt.device
+        self.det, self.B, self.depth = det, B, depth
+        self.scales, self.flip = tuple(scales), bool(flip)
+        # merge_outputs does more than pass one scale through: soft-NMS, and a cut of S * K rows
+        self.merge = len(self.scales) > 1 or bool(getattr(opt, "nms", False))
+        self.mean = (ctypes.c_float * 3)(*[float(v) for v in det.mean.reshape(-1)])
+        self.std = (ctypes.c_float * 3)(*[float(v) for v in det.std.reshape(-1)])
         self.copy_stream = torch.cuda.Stream()
         self.ev_h2d = [torch.cuda.Event() for _ in range(depth)]
         self.ev_pre = [torch.cuda.Event() for _ in range(depth)]
@@ -140,8 +159,10 @@ class FramePipe(object):
         if side is not None:
             self.side_pinned = [torch.empty((B,) + tuple(side), dtype=torch.float32).pin_memory() for _ in range(depth)]
             self.side_dev = [torch.empty((B,) + tuple(side), dtype=torch.float32, device=dev) for _ in range(depth)]
-        self.tail = det._device_tail(self)
-        self.dets_host = None if self.tail is not None else [[None] * len(self.scales) for _ in range(depth)]
+
+    def _setup_tail(self):
+        self.tail = self.det._device_tail(self)
+        self.dets_host = None if self.tail is not None else [[None] * len(self.scales) for _ in range(self.depth)]
 
     def _stage(self, slot, frames):
         dst = self.np_in[slot]
@@ -153,8 +174,32 @@ class FramePipe(object):
                 np.copyto(dst[i], frames[i])
         list(self.pool.map(copy, range(0, n, step)))
 
+    def _upload(self, slot):
+        """On the copy stream: the staged batch to the device."""
+        self.dev_in[slot].copy_(self.pinned_in[slot], non_blocking=True)
+
+    def _pre_process(self, slot, level, stream):
+        """On the launch stream: the uploaded batch of ``slot`` -> the batch of test scale ``level``."""
+        lv = self.levels[level]
+        lib, g, src = native.lib(), lv.g, self.dev_in[slot]
+        if lv.resize:
+            for j in range(self.B):
+                native.check(lib.cn_resize_bilinear_u8(native.ptr(src[j]), g.src_h, g.src_w, g.src_w * 3,
+                                                       g.scaled_h, g.scaled_w, native.ptr(lv.scaled[j]), stream),
+                             "cn_resize_bilinear_u8")
+            src = lv.scaled
+        self.det._pipe_pre_process(self, lv, src, stream)
+
+    def _metas(self, slot, level, n):
+        """The metas of the first ``n`` images of the batch in ``slot`` at test scale ``level`` (host tail)."""
+        return [self.levels[level].meta] * n
+
+    def _run_sync(self, frames, **kw):
+        """The batch once more, synchronously, host tail: both hand-back routes of ``collect``."""
+        return self.det._run_frames_sync(frames, self.scales, **kw)
+
     def submit(self, i, frames, side=None):
-        det, lib, B = self.det, native.lib(), self.B
+        det = self.det
         slot = i % self.depth
         if self.used[slot]:
             self.ev_h2d[slot].synchronize()      # the pinned buffer's previous upload has left it
@@ -166,7 +211,7 @@ class FramePipe(object):
         with torch.cuda.stream(self.copy_stream):
             if self.used[slot]:
                 self.copy_stream.wait_event(self.ev_pre[slot])   # the device copy's previous reader is done
-            self.dev_in[slot].copy_(self.pinned_in[slot], non_blocking=True)
+            self._upload(slot)
             if self.side_pinned is not None:
                 if self.used[slot]:
                     self.copy_stream.wait_event(self.ev_done[slot])   # its reader is the tail, not the pre-process
@@ -176,18 +221,11 @@ class FramePipe(object):
         cur.wait_event(self.ev_h2d[slot])
         stream = native.stream_ptr()
         for li, lv in enumerate(self.levels):
-            g, src = lv.g, self.dev_in[slot]
-            if lv.resize:
-                for j in range(B):
-                    native.check(lib.cn_resize_bilinear_u8(native.ptr(src[j]), g.src_h, g.src_w, g.src_w * 3,
-                                                           g.scaled_h, g.scaled_w, native.ptr(lv.scaled[j]), stream),
-                                 "cn_resize_bilinear_u8")
-                src = lv.scaled
-            det._pipe_pre_process(self, lv, src, stream)
+            self._pre_process(slot, li, stream)
             if li == len(self.levels) - 1:
                 self.ev_pre[slot].record()
             dets = det._run_scale(lv.batch, self.flip)
-            plan = det.model.plan_for(lv.batch.shape[0], g.inp_h, g.inp_w, lv.batch.device)
+            plan = det.model.plan_for(lv.batch.shape[0], lv.batch.shape[2], lv.batch.shape[3], lv.batch.device)
             rs = getattr(plan.b, "range_sum", None) if plan.b.range is not None else None
             self.has_digest[slot][li] = rs is not None
             if rs is not None:
@@ -219,7 +257,7 @@ class FramePipe(object):
             # device, let the module re-calibrate, and run this batch again synchronously.
             torch.cuda.synchronize()
             det.range_ok(None)
-            return det._run_frames_sync(frames, self.scales, **kw)
+            return self._run_sync(frames, **kw)
         n = len(frames)
         if self.tail is not None:
             self.tail.arrays = bool(arrays)
@@ -230,8 +268,177 @@ class FramePipe(object):
             # the merge kernel holds): drain the device and run this batch again synchronously, host tail
             torch.cuda.synchronize()
             det.tail_fallbacks += 1
-            return det._run_frames_sync(frames, self.scales, **kw)
+            return self._run_sync(frames, **kw)
         if not self.merge:
-            return det.results_batch(self.dets_host[slot][0].numpy()[:n], [self.meta] * n, self.scale, **kw)
-        return det._results_merged([(d.numpy()[:n], [lv.meta] * n, lv.scale)
-                                    for d, lv in zip(self.dets_host[slot], self.levels)], **kw)
+            return det.results_batch(self.dets_host[slot][0].numpy()[:n], self._metas(slot, 0, n), self.scale, **kw)
+        return det._results_merged([(d.numpy()[:n], self._metas(slot, li, n), lv.scale)
+                                    for li, (d, lv) in enumerate(zip(self.dets_host[slot], self.levels))], **kw)
+
+
+class ImageTables(object):
+    """Host bookkeeping of ``ImagePipe`` (no device needed): per image size the geometry of every test scale, and
+    the tables of a batch.  The geometry of an image size -- ``input_geometry``, ``get_affine_transform``,
+    ``invert_affine``, ``_meta`` through the task's ``_pipe_level``, what ``run(image)`` computes -- is kept per
+    (H, W): a dataset has few distinct sizes, and these calls would otherwise outweigh the batch's time on the
+    device."""
+    GEOMETRY_CACHE = 8192
+
+    def __init__(self, det, scales):
+        self.det, self.scales, self._geometry = det, tuple(scales), {}
+
+    def of(self, H, W):
+        """What one (H, W) image needs at every test scale: ``rec`` (S, 2) descriptors without their offsets,
+        ``to_source`` (S, 6), ``metas`` [S], ``scaled`` [S] (h, w), ``resize`` [S]."""
+        e = self._geometry.get((H, W))
+        if e is not None:
+            return e
+        if not (0 < H <= 32767 and 0 < W <= 32767):
+            raise ValueError("run_images needs images of 1 .. 32767 rows and columns, got %d x %d" % (H, W))
+        S = len(self.scales)
+        rec = np.zeros((S, 2), native.IMAGE_DESC)
+        e = types.SimpleNamespace(rec=rec, to_source=np.zeros((S, 6), np.float64), metas=[], scaled=[], resize=[],
+                                  nbytes=H * W * 3)
+        for l, scale in enumerate(self.scales):
+            g, to_input, meta = self.det._pipe_level(H, W, scale)
+            if g.scaled_h <= 0 or g.scaled_w <= 0:
+                raise ValueError("run_images: a %d x %d image has no pixels at test scale %s" % (H, W, scale))
+            src, dst = rec[l, 0], rec[l, 1]
+            src['H'], src['W'], src['pitch'] = H, W, 3 * W
+            dst['H'], dst['W'], dst['pitch'] = g.scaled_h, g.scaled_w, 3 * g.scaled_w
+            dst['dst_to_src'] = invert_affine(to_input).reshape(-1)
+            # as cn_resize_bilinear_u8 forms them (Python floats are doubles)
+            dst['scale'] = (1.0 / (float(g.scaled_w) / float(W)), 1.0 / (float(g.scaled_h) / float(H)))
+            e.to_source[l] = np.asarray(get_affine_transform(meta['c'], meta['s'], 0,
+                                                             (meta['out_width'], meta['out_height']), inv=1),
+                                        np.float64).reshape(-1)
+            e.metas.append(meta)
+            e.scaled.append((g.scaled_h, g.scaled_w))
+            e.resize.append((g.scaled_h, g.scaled_w) != (H, W))
+        if len(self._geometry) >= self.GEOMETRY_CACHE:
+            self._geometry.clear()
+        self._geometry[(H, W)] = e
+        return e
+
+    def fill(self, shapes, desc, to_source):
+        """Fill the (S, 2, B) descriptor table and the (S, B, 6) map table for images of ``shapes`` [(H, W)]
+        packed back to back -> (bytes of the packed images, their byte offsets, per level [metas], per level
+        (resize, max scaled h, max scaled w, bytes of the packed scaled images))."""
+        S, n = len(self.scales), len(shapes)
+        es = [self.of(H, W) for H, W in shapes]
+        for j, e in enumerate(es):
+            desc[:, :, j] = e.rec
+            to_source[:, j] = e.to_source
+        sizes = np.array([e.nbytes for e in es], np.uint64)
+        offsets = np.cumsum(sizes) - sizes
+        desc['offset'][:, :, :n] = offsets
+        plan = []
+        for l in range(S):
+            if not any(e.resize[l] for e in es):
+                plan.append((False, 0, 0, 0))
+                continue
+            sz = np.array([e.scaled[l][0] * e.scaled[l][1] * 3 for e in es], np.uint64)
+            desc['offset'][l, 1, :n] = np.cumsum(sz) - sz
+            plan.append((True, max(e.scaled[l][0] for e in es), max(e.scaled[l][1] for e in es), int(sz.sum())))
+        return int(sizes.sum()), offsets, [[e.metas[l] for e in es] for l in range(S)], plan
+
+
+class ImagePipe(FramePipe):
+    """``FramePipe`` for batches of B images of ANY sizes (``run_images`` / ``run_images_stream``), in the
+    fixed-resolution mode: every image is warped into the same (input_h, input_w) tensor, so the network, the
+    decode and the tail see the batches ``FramePipe`` gives them; only the map in and the map out differ per
+    image.  Per slot: one pinned uint8 buffer with the images packed back to back and its device copy (byte
+    capacities: the first batch sizes them, a larger batch grows them geometrically once the slot's previous
+    upload and its readers are done); a pinned (S, 2, B) table of ``cn_image_desc`` -- per test scale the
+    source descriptors and the descriptors the warp reads (the scaled images where the level resizes, else
+    the sources again, with the image's dst -> src matrix) -- and a pinned (S, B, 6) float64 table of the
+    output grid -> source maps, each with its device copy.  All three go up on the copy stream under
+    ``FramePipe``'s events.  Per test scale: ``cn_resize_bilinear_u8_ragged`` where at least one image of the
+    batch is resized (the others are copied by it), ``cn_warp_normalize_u8_f32_ragged`` into ``lv.batch``,
+    then ``FramePipe``'s own steps, the tail reading the slot's maps (``DeviceTail.source_map``).  The host
+    side of the tables is ``ImageTables``."""
+
+    def __init__(self, det, B, scales, flip, depth):
+        opt, dev = det.opt, det.opt.device
+        self._setup(det, B, scales, flip, depth)
+        S, k = len(self.scales), 2 if self.flip else 1
+        meta = {'out_height': opt.input_h // opt.down_ratio, 'out_width': opt.input_w // opt.down_ratio}
+        # lv.meta: what all images share (no 'c' / 's'); lv.scaled: the level's packed resized images
+        self.levels = [types.SimpleNamespace(
+            scale=scale, g=None, meta=meta, scaled=None,
+            batch=torch.empty((B * k, 3, opt.input_h, opt.input_w), device=dev, dtype=torch.float32))
+            for scale in self.scales]
+        self.scale, self.batch = self.scales[0], self.levels[0].batch
+        self.capacity = [0] * depth
+        self.pinned_in, self.np_in, self.dev_in = [None] * depth, [None] * depth, [None] * depth
+        self.desc_pinned = [torch.zeros((S * 2 * B * native.IMAGE_DESC.itemsize,), dtype=torch.uint8).pin_memory()
+                            for _ in range(depth)]
+        self.desc_host = [t.numpy().view(native.IMAGE_DESC).reshape(S, 2, B) for t in self.desc_pinned]
+        self.desc_dev = [torch.empty_like(t, device=dev) for t in self.desc_pinned]
+        self.to_source_pinned = [torch.zeros((S, B, 6), dtype=torch.float64).pin_memory() for _ in range(depth)]
+        self.to_source_dev = [torch.empty((S, B, 6), dtype=torch.float64, device=dev) for _ in range(depth)]
+        self.metas = [None] * depth          # per slot [level][image]
+        self.plan = [None] * depth           # per slot, per level (resize, max scaled_h, max scaled_w)
+        self.nbytes = [0] * depth
+        self.tables = ImageTables(det, self.scales)
+        self._setup_tail()
+
+    def _grow(self, slot, nbytes):
+        """The slot's staging buffers for ``nbytes`` (the caller has waited for ``ev_h2d``)."""
+        if self.used[slot]:
+            self.ev_pre[slot].synchronize()      # the device copy's last reader, before it is let go
+        cap = max(nbytes, 2 * self.capacity[slot])
+        self.pinned_in[slot] = torch.empty((cap,), dtype=torch.uint8).pin_memory()
+        self.np_in[slot] = self.pinned_in[slot].numpy()
+        with torch.cuda.stream(self.copy_stream):    # written on the copy stream: its allocator's block
+            self.dev_in[slot] = torch.empty((cap,), dtype=torch.uint8, device=self.det.opt.device)
+        self.capacity[slot] = cap
+
+    def _stage(self, slot, frames):
+        shapes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
+        nbytes, offsets, self.metas[slot], self.plan[slot] = self.tables.fill(shapes, self.desc_host[slot],
+                                                                         self.to_source_pinned[slot].numpy())
+        if nbytes > self.capacity[slot]:
+            self._grow(slot, nbytes)
+        self.nbytes[slot] = nbytes
+        for lv, (resize, _, _, scaled_bytes) in zip(self.levels, self.plan[slot]):
+            # read and written on the launch stream only: its allocator orders a new buffer behind the old one's use
+            if resize and (lv.scaled is None or lv.scaled.numel() < scaled_bytes):
+                lv.scaled = torch.empty((max(scaled_bytes, 2 * (0 if lv.scaled is None else lv.scaled.numel())),),
+                                        dtype=torch.uint8, device=self.det.opt.device)
+        dst, n = self.np_in[slot], len(frames)
+        step = -(-n // self.pool._max_workers)
+
+        def copy(lo):
+            for i in range(lo, min(lo + step, n)):
+                (H, W), off = shapes[i], int(offsets[i])
+                np.copyto(dst[off:off + H * W * 3].reshape(H, W, 3), frames[i])
+        list(self.pool.map(copy, range(0, n, step)))
+
+    def _upload(self, slot):
+        n = self.nbytes[slot]
+        self.dev_in[slot][:n].copy_(self.pinned_in[slot][:n], non_blocking=True)
+        self.desc_dev[slot].copy_(self.desc_pinned[slot], non_blocking=True)
+        if self.used[slot]:
+            self.copy_stream.wait_event(self.ev_done[slot])      # the maps' reader is the tail, not the pre-process
+        self.to_source_dev[slot].copy_(self.to_source_pinned[slot], non_blocking=True)
+
+    def _pre_process(self, slot, level, stream):
+        lib, B, lv = native.lib(), self.B, self.levels[level]
+        item = native.IMAGE_DESC.itemsize
+        descs = self.desc_dev[slot].data_ptr() + level * 2 * B * item
+        src = self.dev_in[slot]
+        resize, max_h, max_w, _ = self.plan[slot][level]
+        if resize:
+            native.check(lib.cn_resize_bilinear_u8_ragged(native.ptr(src), ctypes.c_void_p(descs), native.ptr(lv.scaled),
+                                                          ctypes.c_void_p(descs + B * item), B, max_h, max_w, stream),
+                         "cn_resize_bilinear_u8_ragged")
+            src = lv.scaled
+        native.check(lib.cn_warp_normalize_u8_f32_ragged(
+            native.ptr(src), ctypes.c_void_p(descs + B * item), B, int(lv.batch.shape[2]), int(lv.batch.shape[3]),
+            self.mean, self.std, int(self.flip), native.ptr(lv.batch), stream), "cn_warp_normalize_u8_f32_ragged")
+
+    def _metas(self, slot, level, n):
+        return self.metas[slot][level][:n]
+
+    def _run_sync(self, frames, **kw):
+        return self.det._run_images_sync(frames, self.scales, **kw)

@@ -10,6 +10,7 @@ import ctypes
 import os
 import subprocess
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -29,6 +30,11 @@ MERGE_MAX_ROWS = 2048       # CN_MERGE_MAX_ROWS: S * K rows per image that the m
 MERGE_MAX_CLASSES = 1024    # CN_MERGE_MAX_CLASSES
 DECODE_SIGMOID = 1          # CN_DECODE_SIGMOID
 DECODE_DDD_RAW_DEPTH = 16384    # CN_DECODE_DDD_RAW_DEPTH: cn_ddd_decode_f32 transforms the gathered depths
+
+# cn_image_desc, one image of a mixed-size batch (cn_warp_normalize_u8_f32_ragged / cn_resize_bilinear_u8_ragged)
+IMAGE_DESC = np.dtype([("offset", np.uint64), ("H", np.int32), ("W", np.int32), ("pitch", np.int32),
+                       ("reserved", np.int32), ("dst_to_src", np.float64, (6,)), ("scale", np.float64, (2,))])
+assert IMAGE_DESC.itemsize == 88
 
 _lib = None
 
@@ -183,6 +189,11 @@ def _declare(lib):
     lib.cn_warp_normalize_u8_f32_batch.argtypes = [vp, i, sz, i, i, i, ctypes.POINTER(ctypes.c_double), i, i,
                                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                                    i, vp, vp]
+    lib.cn_warp_normalize_u8_f32_ragged.restype = i
+    lib.cn_warp_normalize_u8_f32_ragged.argtypes = [vp, vp, i, i, i, ctypes.POINTER(ctypes.c_float),
+                                                    ctypes.POINTER(ctypes.c_float), i, vp, vp]
+    lib.cn_resize_bilinear_u8_ragged.restype = i
+    lib.cn_resize_bilinear_u8_ragged.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     lib.cn_warp_table_u8_f32_batch.restype = i
     lib.cn_warp_table_u8_f32_batch.argtypes = [vp, i, sz, i, i, i, ctypes.POINTER(ctypes.c_double), i, i, vp, vp, vp]
     lib.cn_ddd_post_process_f32.restype = i

@@ -537,6 +537,32 @@ int cn_warp_normalize_u8_f32_batch(const uint8_t *images_hwc, int N, size_t imag
                                    int pitch_bytes, const double *dst_to_src_2x3, int out_h, int out_w,
                                    const float *mean3, const float *std3, int flip_concat,
                                    float *out_nchw, void *stream);
+/* Mixed-size batches (a dataset, not a video): N images of their own sizes packed into ONE uint8 buffer,
+ * one descriptor per image in DEVICE memory (it travels with the images on the caller's copy stream; N
+ * matrices do not fit a kernel argument).  The layout is fixed, 8-byte aligned, 88 bytes. */
+typedef struct cn_image_desc {
+    uint64_t offset;       /* bytes from the start of the packed buffer to the image; any value, no alignment */
+    int32_t H, W, pitch;   /* rows, columns, row pitch in bytes (>= 3 * W) */
+    int32_t reserved;      /* 0 */
+    double dst_to_src[6];  /* cn_warp_normalize_u8_f32_ragged: dst_to_src_2x3 of this image */
+    double scale_x, scale_y;   /* cn_resize_bilinear_u8_ragged, the OUTPUT's descriptor: 1. / ((double)out_w /
+                                  (double)in_w) and the same for y, formed on the host as cv::resize forms them */
+} cn_image_desc;
+/* cn_warp_normalize_u8_f32_ragged: cn_warp_normalize_u8_f32 of image n of `packed` as descs_dev[n] describes
+ * it, n < N, in ONE launch; output dense (N, 3 | 6, out_h, out_w), the layout of the batch entry.  The same
+ * arithmetic, bit for bit.  mean3 / std3: HOST floats.  H, W, pitch and offset are only known on the device:
+ * the caller validates them before the upload (H, W in 1..32767, pitch >= 3 * W, the image inside the
+ * buffer); an image with H <= 0 or W <= 0 is skipped.
+ * cn_resize_bilinear_u8_ragged: cn_resize_bilinear_u8 of N images in one launch, image n from in_descs_dev[n]
+ * of packed_in to out_descs_dev[n] of packed_out (H, W = the output size; pitch normally 3 * W); per image the
+ * copy at equal size, the 2 x 2 mean at exactly half size, the separable 11-bit form otherwise, with the
+ * output descriptor's scale_x / scale_y.  max_out_h / max_out_w: the largest output of the batch (the grid). */
+int cn_warp_normalize_u8_f32_ragged(const uint8_t *packed, const cn_image_desc *descs_dev, int N, int out_h,
+                                    int out_w, const float *mean3, const float *std3, int flip_concat,
+                                    float *out_nchw, void *stream);
+int cn_resize_bilinear_u8_ragged(const uint8_t *packed_in, const cn_image_desc *in_descs_dev, uint8_t *packed_out,
+                                 const cn_image_desc *out_descs_dev, int N, int max_out_h, int max_out_w,
+                                 void *stream);
 /* ctdet_post_process + the per-class split (utils/post_process.py:83-100, utils/image.py:19-24,63-66,
  * detectors/ctdet.py:47-56) on the device.  dets (B, K, 6) raw detections in output-grid units (K <= 128);
  * to_source_2x3: the float64 inverse map of get_affine_transform(c, s, 0, out_size, inv=1) -- one for
