@@ -496,3 +496,38 @@ extern "C" int cn_warp_table_u8_f32_batch(const uint8_t *images_hwc, int N, size
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
+
+// ---- the same for a mixed-size batch (KITTI's images come in several sizes): the geometry of image
+// blockIdx.z from its cn_image_desc, as warp_normalize_ragged_kernel reads it; warp_table_kernel's
+// arithmetic and its table read.
+namespace {
+__global__ void warp_table_ragged_kernel(const uint8_t *__restrict__ packed, const cn_image_desc *__restrict__ descs,
+                                         const float *__restrict__ table, float *__restrict__ out_nchw,
+                                         const int oh, const int ow)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    // uniform over the workgroup: one read through the const __restrict__ pointer, kept in scalar registers
+    const cn_image_desc d = descs[blockIdx.z];
+    if (x >= ow || d.H <= 0 || d.W <= 0) return;
+    int v[3];
+    const size_t plane = (size_t)oh * ow;
+    float *out = out_nchw + (size_t)blockIdx.z * 3 * plane;
+    warp_pixel<3>(packed + d.offset, d.H, d.W, (size_t)d.pitch, d.dst_to_src, x, y,
+                  row_base(d.dst_to_src, 1, 2, y), row_base(d.dst_to_src, 4, 5, y), v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c * plane + (size_t)y * ow + x] = table[c * 256 + v[c]];
+}
+}  // namespace
+
+extern "C" int cn_warp_table_u8_f32_ragged(const uint8_t *packed, const cn_image_desc *descs_dev, int N,
+                                           int out_h, int out_w, const float *table_3x256,
+                                           float *out_nchw, void *stream)
+{
+    if (!packed || !descs_dev || !table_3x256 || !out_nchw) return CN_ERR_NULL;
+    if (out_h <= 0 || out_w <= 0 || out_h > 65535 || N <= 0 || N > 65535) return CN_ERR_SHAPE;
+    dim3 grid(cn_cdiv(out_w, 128), out_h, N);
+    hipLaunchKernelGGL(warp_table_ragged_kernel, grid, dim3(128), 0, (hipStream_t)stream, packed, descs_dev,
+                       table_3x256, out_nchw, out_h, out_w);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}

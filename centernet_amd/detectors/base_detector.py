@@ -116,6 +116,14 @@ class BaseDetector(object):
             lv.dst_to_src, g.inp_h, g.inp_w, pipe.mean, pipe.std, int(pipe.flip), native.ptr(lv.batch), stream),
             "cn_warp_normalize_u8_f32_batch")
 
+    def _pipe_pre_process_images(self, pipe, lv, src, descs, stream):
+        """Task hook of the frame pipeline, ``_pipe_pre_process`` for a batch of mixed-size images: the packed
+        uint8 images ``src`` on the device as the B ``cn_image_desc`` at ``descs`` (device memory) describe them
+        -> ``lv.batch``, one launch."""
+        native.check(native.lib().cn_warp_normalize_u8_f32_ragged(
+            native.ptr(src), descs, pipe.B, int(lv.batch.shape[2]), int(lv.batch.shape[3]), pipe.mean, pipe.std,
+            int(pipe.flip), native.ptr(lv.batch), stream), "cn_warp_normalize_u8_f32_ragged")
+
     # ------------------------------------------------------------------ pre-process
     def pre_process(self, image, scale, meta=None):
         """Host form (base_detector.py:37-65): resize, affine warp, normalise, CHW, flip concat.
@@ -344,6 +352,15 @@ class BaseDetector(object):
             yield pipe.collect(j, fr, arrays)
 
     # ------------------------------------------------------------------ images of mixed sizes
+    def _fixed_input(self):
+        """Whether images of any sizes give ONE network input size, ``run_images``' condition: not with
+        --keep_res (a task whose input never follows the image says otherwise: ddd)."""
+        return self.opt.fix_res
+
+    def _images_and_side(self, batch):
+        """One item of ``run_images_stream``'s iterable -> (images, the pipe's side array or None)."""
+        return batch, None
+
     def _images_one_size(self, images, what):
         """Argument check of ``run_images`` / ``run_images_stream``; True when the images have one size."""
         if len(images) == 0:
@@ -352,7 +369,7 @@ class BaseDetector(object):
             if not isinstance(f, np.ndarray) or f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8:
                 raise ValueError("%s needs (H, W, 3) uint8 BGR images" % what)
         one = len({f.shape for f in images}) == 1
-        if not self.opt.fix_res and not one:
+        if not self._fixed_input() and not one:
             raise ValueError("%s with --keep_res: images of mixed sizes give network inputs of mixed sizes, which "
                              "one batch cannot hold (drop --keep_res, or batch images of one size)" % what)
         return one
@@ -377,7 +394,7 @@ class BaseDetector(object):
         launch where the scale resizes), and the tail kernels map every image back with its own inverse map.
         With --keep_res mixed sizes raise ``ValueError`` (images of one size go to ``run_frames``).
         ``arrays``: as ``run_frames``."""
-        if self._images_one_size(images, "run_images") and not self.opt.fix_res:
+        if self._images_one_size(images, "run_images") and not self._fixed_input():
             return self.run_frames(images, arrays)
         pipe = self._image_pipe_for(images, 1)
         pipe.submit(0, images)
@@ -388,13 +405,14 @@ class BaseDetector(object):
         B -- another length raises ``ValueError``), pipelined as ``run_frames_stream``.  Yields the per-image
         results batch by batch, in order.  With --keep_res every batch goes to ``run_frames`` on its own."""
         pipe, B, pending, n = None, None, collections.deque(), 0
-        for images in batches:
+        for batch in batches:
+            images, side = self._images_and_side(batch)
             self._images_one_size(images, "run_images_stream")
             if B is None:
                 B = len(images)
             elif len(images) != B:
                 raise ValueError("run_images_stream needs batches of one length (%d, then %d)" % (B, len(images)))
-            if not self.opt.fix_res:             # (images of one size, or the check above has raised)
+            if not self._fixed_input():          # (images of one size, or the check above has raised)
                 yield self.run_frames(images, arrays)
                 continue
             if pipe is None:
@@ -402,7 +420,7 @@ class BaseDetector(object):
             if len(pending) == depth:
                 j, fr = pending.popleft()
                 yield pipe.collect(j, fr, arrays)
-            pipe.submit(n, images)
+            pipe.submit(n, images, side)
             pending.append((n, images))
             n += 1
         while pending:

@@ -5,8 +5,11 @@ network, decoded by ``cn_ddd_decode_f32``, lifted to camera coordinates on the h
 3 x 4 projection matrix (test.py:37-39,105-106); without it the detector's KITTI default is used.
 New surface: ``run_frames(frames, calibs)`` / ``run_frames_stream`` -- batches of frames, each with its
 own matrix, pre-processed (``cn_warp_table_u8_f32_batch``) and lifted (``cn_ddd_post_process_f32``) on the
-device."""
+device -- and ``run_images(images, calibs)`` / ``run_images_stream``, the same for images of mixed sizes (KITTI
+has several): the pre-process never resizes, so a mixed-size batch is the ``run_frames`` batch with one map in
+(``cn_warp_table_u8_f32_ragged``) and one map out per image."""
 import ctypes
+import itertools
 import time
 
 import numpy as np
@@ -185,12 +188,48 @@ class DddDetector(BaseDetector):
         memory and uploaded on the copy stream with their frames."""
         return super(DddDetector, self).run_frames_stream(batches, depth)
 
-    def run_images(self, images, arrays=False):
-        raise NotImplementedError("run_images: the ddd task has its own pre-process and a projection matrix per "
-                                  "frame; use run_frames(frames, calibs=) on frames of one size")
+    # ------------------------------------------------------------------ images of mixed sizes
+    def _fixed_input(self):
+        return True      # --keep_res changes the extent only (_frame_geometry): the input size never follows the image
 
-    def run_images_stream(self, batches, depth=3, arrays=False):
-        self.run_images(None)
+    def _pipe_pre_process_images(self, pipe, lv, src, descs, stream):
+        native.check(native.lib().cn_warp_table_u8_f32_ragged(
+            native.ptr(src), descs, pipe.B, self.opt.input_h, self.opt.input_w,
+            native.ptr(self.norm_table(device=True)), native.ptr(lv.batch), stream), "cn_warp_table_u8_f32_ragged")
+
+    def _images_and_side(self, batch):
+        """An item of ``run_images_stream`` -> (images, their (n, 3, 4) matrices); an item that is no
+        ``(images, calibs)`` pair, or has no matrices, is refused as ``run_frames`` refuses missing matrices."""
+        try:
+            images, calibs = batch
+        except (TypeError, ValueError):
+            images, calibs = batch, None
+        if isinstance(images, np.ndarray) and images.ndim == 3:      # a list of two images, not a pair
+            images, calibs = batch, None
+        return images, self._calibs_for(images, calibs)
+
+    def run_images(self, images, calibs=None):
+        """A list of (H_i, W_i, 3) uint8 BGR images of ANY sizes and their projection matrices -> per image what
+        ``run(image_i, calib_i)['results']`` returns (the result shapes of ``run_frames``).  ``calibs``: as
+        ``run_frames`` takes them.  The images are packed back to back into one uint8 upload with a table of
+        per-image descriptors, warped by ONE ``cn_warp_table_u8_f32_ragged`` launch (no level resizes), and the
+        tail lifts image b with its own inverse map and matrix b.  --keep_res changes only the extent, the
+        network input stays (input_h, input_w): mixed sizes are valid with it too."""
+        side = self._calibs_for(images, calibs)
+        self._images_one_size(images, "run_images")
+        pipe = self._image_pipe_for(images, 1)
+        pipe.submit(0, images, side)
+        return pipe.collect(0, images)
+
+    def run_images_stream(self, batches, depth=3):
+        """``run_images`` over an iterable of ``(images, calibs)`` pairs, every batch of one length, pipelined as
+        ``run_frames_stream``.  The first item is looked at here, at the call: a stream without matrices is
+        refused before anything is yielded."""
+        batches = iter(batches)
+        first = list(itertools.islice(batches, 1))
+        for batch in first:
+            self._images_and_side(batch)
+        return super(DddDetector, self).run_images_stream(itertools.chain(first, batches), depth)
 
     def _run_scale(self, images, flip):
         """Network + decode of the frame pipeline: the centre map's sigmoid and the depth transform of
@@ -211,6 +250,15 @@ class DddDetector(BaseDetector):
         self._warp_table(uploaded, to_input, batch)
         dets = self._forward_checked(batch, False)
         return self.results_batch(dets, [self._meta(c, s, None)] * len(frames), 1.0, side=side)
+
+    def _run_images_sync(self, images, scales, side=None):
+        """``_run_frames_sync`` for images of any sizes: each image uploaded on its own, warped into its slice
+        of the batch, with its own meta (the comparison path of ``run_images`` and its re-run path)."""
+        batch = torch.empty((len(images), 3, self.opt.input_h, self.opt.input_w), device=self.opt.device,
+                            dtype=torch.float32)
+        metas = [self.pre_process_device(f, 1.0, out=batch[i:i + 1])[1] for i, f in enumerate(images)]
+        dets = self._forward_checked(batch, False)
+        return self.results_batch(dets, metas, 1.0, side=side)
 
     def results_batch(self, dets, metas, scale, side=None):
         """Host tail of ``run_frames``: (n, K, 18) host rows, the frames' metas and their (n, 3, 4) matrices
@@ -253,9 +301,10 @@ class DddTail(DeviceTail):
     def run(self, slot, level, dets):
         pipe, det, out = self.pipe, self.det, self.out
         dets = dets.contiguous()
+        to_source, per_image = self.source_map(slot, level)
         native.check(native.lib().cn_ddd_post_process_f32(
-            native.ptr(dets), pipe.B, det.opt.K, int(dets.shape[2]), det.num_classes, native.ptr(self.to_source[level]),
-            0, native.ptr(pipe.side_dev[slot]), float(det.opt.peak_thresh), native.ptr(out['rows']),
+            native.ptr(dets), pipe.B, det.opt.K, int(dets.shape[2]), det.num_classes, to_source,
+            per_image, native.ptr(pipe.side_dev[slot]), float(det.opt.peak_thresh), native.ptr(out['rows']),
             native.ptr(out['bounds']), native.ptr(out['kept']), native.stream_ptr()), "cn_ddd_post_process_f32")
 
     def results(self, slot, n):

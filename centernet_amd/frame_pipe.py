@@ -3,7 +3,9 @@ mixed sizes (``ImagePipe`` with ``ImageTables``: ``run_images`` / ``run_images_s
 task's device tail (``DeviceTail``): what runs behind the decode of every test scale, on the launch stream, so
 that the host only slices pinned rows.  The task classes (``detectors/*.py``) supply a ``DeviceTail``
 subclass each -- the admission test, the kernel calls and the result shape -- through one hook,
-``BaseDetector._device_tail(pipe)``."""
+``BaseDetector._device_tail(pipe)``, and the pre-process launch through ``_pipe_pre_process`` (frames of one size)
+and ``_pipe_pre_process_images`` (mixed sizes); ddd, with its own warp kernels and one matrix per image, runs
+through both pipes like the other tasks."""
 import concurrent.futures
 import ctypes
 import types
@@ -106,7 +108,8 @@ class FramePipe(object):
     drains the device, runs that batch through ``_run_frames_sync`` and counts it in ``det.tail_fallbacks``.
 
     Two more task hooks keep the pipe free of task geometry: ``_pipe_level`` (input geometry, frame ->
-    input map and meta of one test scale) and ``_pipe_pre_process`` (the batched pre-process launch).
+    input map and meta of one test scale) and ``_pipe_pre_process`` (the batched pre-process launch;
+    ``_pipe_pre_process_images`` is its twin for ``ImagePipe``'s packed images and descriptors).
     A task with per-frame side inputs (ddd: one 3 x 4 calibration matrix per frame) sets
     ``_pipe_side_shape``: the pipe then keeps ``depth`` pinned (B, *shape) float32 buffers and their device
     copies, ``submit`` takes the batch's side array, uploads it on the copy stream with the frames, and the
@@ -353,9 +356,11 @@ class ImagePipe(FramePipe):
     the sources again, with the image's dst -> src matrix) -- and a pinned (S, B, 6) float64 table of the
     output grid -> source maps, each with its device copy.  All three go up on the copy stream under
     ``FramePipe``'s events.  Per test scale: ``cn_resize_bilinear_u8_ragged`` where at least one image of the
-    batch is resized (the others are copied by it), ``cn_warp_normalize_u8_f32_ragged`` into ``lv.batch``,
-    then ``FramePipe``'s own steps, the tail reading the slot's maps (``DeviceTail.source_map``).  The host
-    side of the tables is ``ImageTables``."""
+    batch is resized (the others are copied by it), the task's ``_pipe_pre_process_images`` into ``lv.batch``
+    (``cn_warp_normalize_u8_f32_ragged``; ddd, whose levels never resize: ``cn_warp_table_u8_f32_ragged``),
+    then ``FramePipe``'s own steps, the tail reading the slot's maps (``DeviceTail.source_map``).  A task's
+    side array (ddd: the images' matrices) rides as under ``FramePipe``.  The host side of the tables is
+    ``ImageTables``."""
 
     def __init__(self, det, B, scales, flip, depth):
         opt, dev = det.opt, det.opt.device
@@ -433,9 +438,7 @@ class ImagePipe(FramePipe):
                                                           ctypes.c_void_p(descs + B * item), B, max_h, max_w, stream),
                          "cn_resize_bilinear_u8_ragged")
             src = lv.scaled
-        native.check(lib.cn_warp_normalize_u8_f32_ragged(
-            native.ptr(src), ctypes.c_void_p(descs + B * item), B, int(lv.batch.shape[2]), int(lv.batch.shape[3]),
-            self.mean, self.std, int(self.flip), native.ptr(lv.batch), stream), "cn_warp_normalize_u8_f32_ragged")
+        self.det._pipe_pre_process_images(self, lv, src, ctypes.c_void_p(descs + B * item), stream)
 
     def _metas(self, slot, level, n):
         return self.metas[slot][level][:n]

@@ -196,6 +196,8 @@ def _declare(lib):
     lib.cn_resize_bilinear_u8_ragged.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     lib.cn_warp_table_u8_f32_batch.restype = i
     lib.cn_warp_table_u8_f32_batch.argtypes = [vp, i, sz, i, i, i, ctypes.POINTER(ctypes.c_double), i, i, vp, vp, vp]
+    lib.cn_warp_table_u8_f32_ragged.restype = i
+    lib.cn_warp_table_u8_f32_ragged.argtypes = [vp, vp, i, i, i, vp, vp, vp]
     lib.cn_ddd_post_process_f32.restype = i
     lib.cn_ddd_post_process_f32.argtypes = [vp, i, i, i, i, vp, i, vp, ctypes.c_float, vp, vp, vp, vp]
     lib.cn_ctdet_post_process_f32.restype = i

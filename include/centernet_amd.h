@@ -641,6 +641,13 @@ int cn_resize_bilinear_u8(const uint8_t *image_hwc, int H, int W, int pitch_byte
 int cn_warp_table_u8_f32_batch(const uint8_t *images_hwc, int N, size_t image_stride_bytes, int H, int W,
                                int pitch_bytes, const double *dst_to_src_2x3, int out_h, int out_w,
                                const float *table_3x256, float *out_nchw, void *stream);
+/* cn_warp_table_u8_f32_ragged: the same for N images of their own sizes in ONE launch, as
+ * cn_warp_normalize_u8_f32_ragged takes them: image n at packed + descs_dev[n].offset with that descriptor's
+ * H, W, pitch and dst_to_src (DEVICE memory; the caller validates them before the upload), an image with
+ * H <= 0 or W <= 0 skipped (its output slice is not written).  cn_warp_table_u8_f32_batch's arithmetic and
+ * table read, bit for bit; output dense (N, 3, out_h, out_w); no flip form. */
+int cn_warp_table_u8_f32_ragged(const uint8_t *packed, const cn_image_desc *descs_dev, int N, int out_h,
+                                int out_w, const float *table_3x256, float *out_nchw, void *stream);
 /* ddd_post_process_2d + ddd_post_process_3d + DddDetector.merge_outputs (utils/post_process.py:24-79,
  * utils/ddd_utils.py:68-114, detectors/ddd.py:82-88) for a batch.  dets (B, K, row_floats): the raw rows of
  * cn_ddd_decode_f32 with wh, row_floats = 18 (16, the form without wh, -> CN_ERR_UNSUPPORTED: the
