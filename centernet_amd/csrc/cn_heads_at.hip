@@ -1,0 +1,289 @@
+// cn_heads_at.hip -- the gather-only ctdet heads (wh, reg) evaluated at the K decoded centres.
+//
+// ctdet_decode (decode.py:472-486) reads `wh` and `reg` at the K winning cells of every image and
+// nowhere else, so a detector that does not need the dense maps runs the fused heads launch for `hm`
+// alone, the image-level top-K on it (cn_topk_f32), and then this kernel: for each of the B x K cells
+// and each deferred head
+//     hidden = ReLU(conv3x3(feature, w1) + b1)   at that one cell (padding = 1: taps outside read 0)
+//     out    = w2 . hidden + b2                  (two outputs per head)
+// followed by the box arithmetic of emit_rows (cn_decode.hip), written the same way.
+//
+// Arithmetic: plain fp32 FMA on the decoded feature values ((hi + lo) * 2^e is exact in fp32) and the
+// original, unsplit fp32 weights: no range words, nothing can clamp.
+//
+// Shape of the launch: one workgroup of 256 threads per (image, 16 consecutive cells).  The 3x3 x 64
+// channel patches of its cells sit in LDS (16 x 576 floats per 64-channel chunk of Cin); a thread owns
+// one or two hidden channels of the concatenated heads and CT of the 16 cells, streams its weights as
+// float4 (four consecutive k of one channel: cn_pack_cell_heads_w1 order) with the next group of loads
+// in flight, and reads the patch values as LDS broadcasts (all lanes of a wave share the cell).  The
+// hidden values then replace the patches in LDS, four lanes share one 1x1 output, and the first
+// threads assemble the rows.  Weight traffic: the whole first-layer weight once per workgroup from L2
+// (295 KB for two 64-wide heads, B * ceil(K / 16) workgroups).
+#include "cn_common.h"
+#include "cn_internal.h"
+
+namespace {
+
+constexpr int HA_NT = 256;      // threads per workgroup
+constexpr int HA_CELLS = 16;    // cells per workgroup
+constexpr int HA_CC = 64;       // channels of Cin per staged chunk
+constexpr int HA_ROW = 9 * HA_CC;   // floats of one cell's patch (one chunk)
+constexpr int HA_MAXN = 512;    // hidden channels of all deferred heads together
+constexpr int HA_PF = 4;        // float4 weight groups in flight per channel slot
+
+struct HeadsAtArgs {
+    const char *feat;           // NHWC, row pitch `pitch` channels; f32s or plain fp32
+    const float *scores;        // (B, K)
+    const int32_t *inds, *clses;  // (B, K)
+    const cn_f32x4 *w1;         // (9 * Cin / 4, N) float4: cn_pack_cell_heads_w1
+    const float *b1;            // (N)
+    const float *w2;            // (n_heads, 2, hidden)
+    const float *b2;            // (n_heads, 2) or null
+    float *dets;                // (B, K, 6)
+    float *vals;                // (B, K, 2 * n_heads) or null: the raw head values
+    float mul;                  // 2^e of an f32s feature map (1 for plain)
+    int H, W, Cin, pitch, K, hidden, n_heads, N;
+};
+
+// CT cells per thread (16 / CT cell groups of 16 * CT threads), NS channel slots per thread
+template <bool F32S, int CT, int NS>
+__global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const HeadsAtArgs a)
+{
+    constexpr int CG = HA_CELLS / CT;     // cell groups
+    constexpr int TPC = HA_NT / CG;       // threads across the channels (a multiple of 64: a wave shares its cells)
+    static_assert(TPC % 64 == 0, "the lanes of a wave read one cell's patch");
+    __shared__ __attribute__((aligned(16))) float lds[HA_CELLS * HA_ROW];   // patches, then the hidden values
+    __shared__ int s_ind[HA_CELLS];
+    __shared__ float s_out[HA_CELLS * 4];
+
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y;
+    const int k0 = blockIdx.x * HA_CELLS;
+    const int ncell = min(HA_CELLS, a.K - k0);
+    const int HW = a.H * a.W;
+    const int N = a.N;
+
+    if (tid < HA_CELLS) {
+        int ind = -1;
+        if (tid < ncell) {
+            ind = a.inds[(size_t)b * a.K + k0 + tid];
+            if ((uint32_t)ind >= (uint32_t)HW) ind = -1;   // never read outside the map (the row becomes NaN)
+        }
+        s_ind[tid] = ind;
+    }
+
+    const int nl = tid % TPC, cg = tid / TPC;
+    float acc[NS][CT];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int i = 0; i < CT; ++i) acc[s][i] = 0.f;
+
+    size_t kq_base = 0;   // float4 rows of w1 in front of this chunk
+    for (int c0 = 0; c0 < a.Cin; c0 += HA_CC) {
+        const int cc = min(HA_CC, a.Cin - c0);     // 64, or 32 in the last chunk
+        const int cq = cc >> 2;
+        __syncthreads();   // s_ind is written / the previous chunk's patches are consumed
+        // stage: patch[cell][tap * cc + ci], zeros outside the map and for absent cells
+        for (int i = tid; i < HA_CELLS * 9 * cq; i += HA_NT) {
+            const int q = i % cq, r = i / cq;
+            const int tap = r % 9, cell = r / 9;
+            const int ind = s_ind[cell];
+            cn_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (ind >= 0) {
+                const int y = ind / a.W + tap / 3 - 1, x = ind % a.W + tap % 3 - 1;
+                if ((unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W) {
+                    const size_t pix = ((size_t)b * a.H + y) * a.W + x;
+                    if (F32S) {
+                        v = cn_load4_f32s(a.feat, pix, a.pitch, c0 + 4 * q);
+                        v *= a.mul;
+                    } else {
+                        v = *reinterpret_cast<const cn_f32x4 *>(a.feat + (pix * (size_t)a.pitch + c0 + 4 * q) * 4);
+                    }
+                }
+            }
+            *reinterpret_cast<cn_f32x4 *>(&lds[cell * HA_ROW + tap * cc + 4 * q]) = v;
+        }
+        __syncthreads();
+
+        const int nkq = 9 * cq;    // float4 groups of this chunk (a multiple of HA_PF: 72 or 144)
+        const cn_f32x4 *wq = a.w1 + kq_base * N;
+        cn_f32x4 wn[HA_PF][NS];
+#pragma unroll
+        for (int p = 0; p < HA_PF; ++p)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int n = nl + s * TPC;
+                wn[p][s] = n < N ? wq[(size_t)p * N + n] : cn_f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        for (int kq = 0; kq < nkq; kq += HA_PF) {
+            cn_f32x4 wv[HA_PF][NS];
+#pragma unroll
+            for (int p = 0; p < HA_PF; ++p)
+#pragma unroll
+                for (int s = 0; s < NS; ++s) wv[p][s] = wn[p][s];
+            if (kq + HA_PF < nkq) {
+#pragma unroll
+                for (int p = 0; p < HA_PF; ++p)
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        const int n = nl + s * TPC;
+                        if (n < N) wn[p][s] = wq[(size_t)(kq + HA_PF + p) * N + n];
+                    }
+            }
+#pragma unroll
+            for (int p = 0; p < HA_PF; ++p)
+#pragma unroll
+                for (int i = 0; i < CT; ++i) {
+                    const cn_f32x4 pv = *reinterpret_cast<const cn_f32x4 *>(&lds[(i * CG + cg) * HA_ROW + 4 * (kq + p)]);
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        float t = acc[s][i];
+                        t = __builtin_fmaf(wv[p][s][0], pv[0], t);
+                        t = __builtin_fmaf(wv[p][s][1], pv[1], t);
+                        t = __builtin_fmaf(wv[p][s][2], pv[2], t);
+                        t = __builtin_fmaf(wv[p][s][3], pv[3], t);
+                        acc[s][i] = t;
+                    }
+                }
+        }
+        kq_base += (size_t)nkq;
+    }
+
+    // hidden[cell][n] = ReLU(acc + b1[n]) replaces the patches (N <= 512 <= HA_ROW)
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int n = nl + s * TPC;
+        if (n < N) {
+            const float bias = a.b1[n];
+#pragma unroll
+            for (int i = 0; i < CT; ++i)
+                lds[(i * CG + cg) * HA_ROW + n] = __builtin_fmaxf(acc[s][i] + bias, 0.f);
+        }
+    }
+    __syncthreads();
+
+    // 1x1: output o = (cell, head, j) of 16 x 2 x 2, four lanes each (all 256 threads take part in the
+    // shuffles; an absent head contributes nothing)
+    {
+        const int o = tid >> 2, sub = tid & 3;
+        const int cell = o >> 2, head = (o >> 1) & 1, j = o & 1;
+        float sum = 0.f;
+        if (head < a.n_heads) {
+            const float *w = a.w2 + ((size_t)head * 2 + j) * a.hidden;
+            const float *h = &lds[cell * HA_ROW + head * a.hidden];
+            for (int c = sub; c < a.hidden; c += 4) sum = __builtin_fmaf(w[c], h[c], sum);
+        }
+        sum += __shfl_xor(sum, 1);
+        sum += __shfl_xor(sum, 2);
+        if (sub == 0) {
+            if (head < a.n_heads && a.b2) sum += a.b2[head * 2 + j];
+            s_out[o] = sum;
+        }
+    }
+    __syncthreads();
+
+    if (tid < ncell) {
+        const size_t row = (size_t)b * a.K + k0 + tid;
+        const int ind = s_ind[tid];
+        float *d = a.dets + row * 6;
+        const float score = a.scores[row];
+        const float cls = (float)a.clses[row];
+        if (ind < 0) {
+            const float nan = __builtin_nanf("");
+            d[0] = nan; d[1] = nan; d[2] = nan; d[3] = nan; d[4] = score; d[5] = cls;
+            if (a.vals)
+                for (int v = 0; v < 2 * a.n_heads; ++v) a.vals[row * (2 * a.n_heads) + v] = nan;
+            return;
+        }
+        const int yi = ind / a.W, xi = ind - yi * a.W;
+        float xs = (float)xi, ys = (float)yi;
+        if (a.n_heads > 1) {  // decode.py:472-476
+            xs = xs + s_out[tid * 4 + 2];
+            ys = ys + s_out[tid * 4 + 3];
+        } else {  // decode.py:477-479
+            xs = xs + 0.5f;
+            ys = ys + 0.5f;
+        }
+        const float w = s_out[tid * 4 + 0];
+        const float h = s_out[tid * 4 + 1];
+        d[0] = xs - w / 2;  // decode.py:489-492
+        d[1] = ys - h / 2;
+        d[2] = xs + w / 2;
+        d[3] = ys + h / 2;
+        d[4] = score;
+        d[5] = cls;
+        if (a.vals)
+            for (int v = 0; v < 2 * a.n_heads; ++v) a.vals[row * (2 * a.n_heads) + v] = s_out[tid * 4 + v];
+    }
+}
+
+// w (N, Cin, 3, 3) -> out (9 * Cin / 4, N, 4): k = (64-channel chunk of Cin, tap, channel in the chunk),
+// four consecutive k of one output channel per float4
+__global__ void decode_pack_cell_w1_kernel(const float *__restrict__ w, float *__restrict__ out, int N, int Cin,
+                                           size_t total)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int e = (int)(i & 3);
+    const int n = (int)((i >> 2) % N);
+    const int k = (int)((i >> 2) / N) * 4 + e;
+    const int chunk = k / (9 * HA_CC);          // only the last chunk can be shorter, so this is exact
+    const int c0 = chunk * HA_CC;
+    const int cc = min(HA_CC, Cin - c0);
+    const int r = k - chunk * 9 * HA_CC;
+    const int tap = r / cc, ci = c0 + r % cc;
+    out[i] = w[((size_t)n * Cin + ci) * 9 + tap];
+}
+
+}  // namespace
+
+extern "C" int cn_pack_cell_heads_w1(const float *w, float *out, int N, int Cin, void *stream)
+{
+    if (!w || !out) return CN_ERR_NULL;
+    if (N <= 0 || Cin <= 0) return CN_ERR_SHAPE;
+    if (N > HA_MAXN || (N & 63) || (Cin & 31)) return CN_ERR_UNSUPPORTED;
+    if (!cn_aligned16(out)) return CN_ERR_ALIGN;
+    const size_t total = (size_t)N * Cin * 9;
+    hipLaunchKernelGGL(decode_pack_cell_w1_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, w, out, N, Cin, total);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_ctdet_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
+                                           float feat_mul, const float *scores, const int32_t *inds,
+                                           const int32_t *clses, int K, const float *w1_packed,
+                                           const float *bias1, int hidden, int n_heads, const float *w2,
+                                           const float *bias2, float *dets, float *head_vals, void *stream)
+{
+    if (!feat || !scores || !inds || !clses || !w1_packed || !bias1 || !w2 || !dets) return CN_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || K <= 0 || pitch < Cin) return CN_ERR_SHAPE;
+    if (dtype != CN_DTYPE_F32S && dtype != CN_DTYPE_F32) return CN_ERR_UNSUPPORTED;
+    if (n_heads < 1 || n_heads > 2 || hidden < 64 || hidden > 256 || (hidden & 63)) return CN_ERR_UNSUPPORTED;
+    if ((Cin & 31) || (pitch & 3) || (dtype == CN_DTYPE_F32S && (pitch & 31))) return CN_ERR_UNSUPPORTED;
+    if ((long)H * W >= (1L << 31) || B > 65535) return CN_ERR_UNSUPPORTED;
+    if (!cn_aligned16(feat) || !cn_aligned16(w1_packed)) return CN_ERR_ALIGN;
+    HeadsAtArgs a;
+    a.feat = (const char *)feat; a.scores = scores; a.inds = inds; a.clses = clses;
+    a.w1 = (const cn_f32x4 *)w1_packed; a.b1 = bias1; a.w2 = w2; a.b2 = bias2;
+    a.dets = dets; a.vals = head_vals; a.mul = dtype == CN_DTYPE_F32S ? feat_mul : 1.f;
+    a.H = H; a.W = W; a.Cin = Cin; a.pitch = pitch; a.K = K; a.hidden = hidden; a.n_heads = n_heads;
+    a.N = hidden * n_heads;
+    const dim3 grid((unsigned)cn_cdiv(K, HA_CELLS), (unsigned)B), block(HA_NT);
+    hipStream_t st = (hipStream_t)stream;
+    const bool s = dtype == CN_DTYPE_F32S;
+#define HA_LAUNCH(CT, NS)                                                                               \
+    do {                                                                                                \
+        if (s) hipLaunchKernelGGL((decode_heads_at_cells_kernel<true, CT, NS>), grid, block, 0, st, a); \
+        else hipLaunchKernelGGL((decode_heads_at_cells_kernel<false, CT, NS>), grid, block, 0, st, a);  \
+    } while (0)
+    if (a.N <= 64) HA_LAUNCH(4, 1);
+    else if (a.N <= 128) HA_LAUNCH(8, 1);
+    else if (a.N <= 256) HA_LAUNCH(16, 1);
+    else HA_LAUNCH(16, 2);
+#undef HA_LAUNCH
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}

@@ -110,6 +110,55 @@ def ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100, apply_sigmoid=Fal
     return (dets, inds.long()) if return_inds else dets
 
 
+def ctdet_decode_at_cells(heat, late, K=100, apply_sigmoid=False, return_inds=False, return_vals=False):
+    """``ctdet_decode`` without dense ``wh`` / ``reg`` maps: ``late`` is the ``engine.DeferredHeads`` of a
+    deferred-heads plan (heads ``('wh',)`` or ``('wh', 'reg')``).  Two launches on the current stream: the
+    image-level top-K of ``heat`` (``cn_topk_f32`` with the peak test: the scores, cells and classes of
+    ``ctdet_decode``, bit for bit) and ``cn_ctdet_heads_at_cells_f32``, which evaluates the heads at
+    those cells in plain fp32 and assembles the (B, K, 6) rows.  ``return_vals``: also the raw head
+    values (B, K, 2 * heads)."""
+    (heat,) = _prep(heat)
+    lib = native.lib()
+    if heat.dim() != 4:
+        raise RuntimeError("heat must be (B, C, H, W)")
+    B, C, H, W = heat.shape
+    f = late.feat
+    if late.names not in (("wh",), ("wh", "reg")):
+        raise RuntimeError("ctdet_decode_at_cells takes the heads ('wh',) or ('wh', 'reg'), got %r" % (late.names,))
+    if (f.B, f.H, f.W) != (B, H, W) or f.nchw or f.fmt not in ("f32s", "f32") or f.t.device != heat.device:
+        raise RuntimeError("the deferred heads' feature map must be an NHWC fp32 / f32s (%d, %d, %d, .) "
+                           "activation on the heat-map's device" % (B, H, W))
+    if K > H * W:
+        raise RuntimeError("selected index k out of range")
+    dev = heat.device
+    scores = torch.empty((B, K), device=dev, dtype=torch.float32)
+    inds = torch.empty((B, K), device=dev, dtype=torch.int32)
+    clses = torch.empty((B, K), device=dev, dtype=torch.int32)
+    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
+    st = native.stream_ptr()
+    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN,
+                         native.ptr(scores), native.ptr(inds), native.ptr(clses), native.ptr(ws), ws.numel(), st)
+    if rc:
+        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
+    native.check(rc, "cn_topk_f32")
+    nh = len(late.names)
+    dets = torch.empty((B, K, 6), device=dev, dtype=torch.float32)
+    vals = torch.empty((B, K, 2 * nh), device=dev, dtype=torch.float32) if return_vals else None
+    s = f.fmt == "f32s"
+    rc = lib.cn_ctdet_heads_at_cells_f32(
+        f.ptr(), B, H, W, f.C, f.pitch, native.DTYPE_F32S if s else native.DTYPE_F32,
+        float(2.0 ** f.exp) if s else 1.0, native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
+        native.ptr(late.w1), native.ptr(late.b1), late.hidden, nh, native.ptr(late.w2), native.ptr(late.b2),
+        native.ptr(dets), native.ptr(vals), st)
+    native.check(rc, "cn_ctdet_heads_at_cells_f32")
+    out = (dets,)
+    if return_inds:
+        out += (inds.long(),)
+    if return_vals:
+        out += (vals,)
+    return out if len(out) > 1 else dets
+
+
 _NO_PEAK_TEST = 512   # flag bit of the decode entry points: rank every cell (plain topk)
 _EXCT_CLAMP_ONE = 2   # CN_EXCT_CLAMP_ONE (cn_exct_decode_f32): clamp the peak-tested edge maps to 1
 

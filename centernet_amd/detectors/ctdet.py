@@ -1,5 +1,6 @@
 """ctdet task (public behaviour of src/lib/detectors/ctdet.py:23-73): centre heat-map, box size
-and sub-pixel offset decoded by the fused ``cn_ctdet_decode_f32`` kernels.  New surface:
+and sub-pixel offset decoded by the fused ``cn_ctdet_decode_f32`` kernels (``run_batch``: top-K on ``hm``,
+then the ``wh`` / ``reg`` heads at the K cells only, ``cn_ctdet_heads_at_cells_f32``).  New surface:
 ``run_batch`` (device-resident batches) and ``run_frames`` (lists of uint8 frames)."""
 import time
 
@@ -7,7 +8,7 @@ import numpy as np
 import torch
 
 from .. import native
-from ..decode import ctdet_decode
+from ..decode import ctdet_decode, ctdet_decode_at_cells
 from ..frame_pipe import DeviceTail
 from ..post_process import ctdet_results_batch
 from ..utils import flip_average, flip_average_batch
@@ -17,6 +18,38 @@ from .base_detector import BaseDetector
 class CtdetDetector(BaseDetector):
     def __init__(self, opt):
         super(CtdetDetector, self).__init__(opt)
+        self.model.defer_heads(self._deferred_heads())
+
+    def _deferred_heads(self):
+        """The heads ``run_batch`` leaves to the decode: ``wh`` (and ``reg``) are only gathered at the K
+        decoded centres (decode.py:472-486), so their dense maps are not computed.  Not with flip-test
+        (the averaged maps are needed), ``cat_spec_wh`` (2 x classes outputs) or K > 128; the network
+        side (fp32 compute mode, fusable 3x3 + 1x1 heads) is the plan builder's decision."""
+        opt = self.opt
+        if opt.flip_test or opt.cat_spec_wh or opt.K > 128 or 'wh' not in opt.heads:
+            return ()
+        if 'reg' in opt.heads:
+            return ('wh', 'reg') if opt.reg_offset else ()
+        return ('wh',)
+
+    def _sync_deferral(self):
+        """Keep the module's mode in step with the options (one may have changed after construction): the
+        frame pipe reads the range words of ``plan_for(...)``, which must be the plan that ran."""
+        names = self._deferred_heads()
+        if names != self.model.deferral():
+            self.model.defer_heads(names)
+
+    def _forward_batch(self, images, **kw):
+        """The network of ``run_batch``: the deferred-heads plan where it applies, else the dense one."""
+        self._sync_deferral()
+        return self.model(images, borrow=True, deferred=True, **kw)[-1]
+
+    def _decode_batch(self, out):
+        """Decode of ``_forward_batch``'s output (``hm`` stays logits: the sigmoid is in the kernel)."""
+        late = out.get('_deferred')
+        if late is not None:
+            return ctdet_decode_at_cells(out['hm'], late, K=self.opt.K, apply_sigmoid=True)
+        return self._decode(out['hm'], out['wh'], out['reg'] if self.opt.reg_offset else None, True)
 
     def _decode(self, hm, wh, reg, logits):
         return ctdet_decode(hm, wh, reg=reg, cat_spec_wh=self.opt.cat_spec_wh, K=self.opt.K,
@@ -88,16 +121,13 @@ class CtdetDetector(BaseDetector):
         self._note_unchecked_forward()
         with torch.no_grad():
             if probe is None:
-                out = self.model(images, borrow=True)[-1]
-                return self._decode(out['hm'], out['wh'],
-                                    out['reg'] if self.opt.reg_offset else None, True)
+                return self._decode_batch(self._forward_batch(images))
             probe['net_events'] = []
-            out = self.model(images, borrow=True, events=probe['net_events'],
-                             event_after=probe.get('event_after'))[-1]
+            out = self._forward_batch(images, events=probe['net_events'],
+                                      event_after=probe.get('event_after'))
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
-            dets = self._decode(out['hm'], out['wh'], out['reg'] if self.opt.reg_offset else None,
-                                True)
+            dets = self._decode_batch(out)
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
             probe['dec_events'] = (e0, e1)
@@ -110,6 +140,7 @@ class CtdetDetector(BaseDetector):
         if not flip:
             return self.run_batch(images)
         self._note_unchecked_forward()
+        self._sync_deferral()        # flip-test defers nothing: plan_for(...) is then this dense plan
         with torch.no_grad():
             out = self.model(images, borrow=True)[-1]
             hm = flip_average_batch(out['hm'], sigmoid=True)

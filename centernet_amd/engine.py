@@ -113,6 +113,37 @@ def _pow2(e):
     return math.ldexp(1.0, int(e))
 
 
+def pack_cell_heads(firsts, lasts, device):
+    """Weights of gather-only heads for ``cn_ctdet_heads_at_cells_f32``: ``firsts`` the 3x3 convolutions
+    (hidden, Cin, 3, 3) and ``lasts`` the 1x1 convolutions (2, hidden) of the heads, in order.  The ORIGINAL
+    fp32 values (no split, no pre-scale): first layers concatenated along Cout and re-ordered by
+    ``cn_pack_cell_heads_w1`` on the current stream.  Returns (w1, b1, w2, b2) device tensors."""
+    lib = native.lib()
+    w = torch.cat([c.weight.detach() for c in firsts], 0).to(device=device, dtype=torch.float32).contiguous()
+    b1 = torch.cat([c.bias.detach() for c in firsts], 0).to(device=device, dtype=torch.float32).contiguous()
+    N, ci = int(w.shape[0]), int(w.shape[1])
+    hidden = int(firsts[0].weight.shape[0])
+    w1 = torch.empty((9 * ci // 4, N, 4), device=device, dtype=torch.float32)
+    native.check(lib.cn_pack_cell_heads_w1(native.ptr(w), native.ptr(w1), N, ci, native.stream_ptr()),
+                 "cn_pack_cell_heads_w1")
+    w2 = torch.stack([c.weight.detach().reshape(2, hidden) for c in lasts], 0)
+    w2 = w2.to(device=device, dtype=torch.float32).contiguous()
+    b2 = torch.stack([torch.zeros(2) if c.bias is None else c.bias.detach().cpu().float() for c in lasts], 0)
+    b2 = b2.to(device=device, dtype=torch.float32).contiguous()
+    return w1, b1, w2, b2
+
+
+class DeferredHeads:
+    """What a deferred-heads plan hands to the decode instead of dense maps: the feature ``Act`` the heads
+    read (pointer, pitch, format, exponent) and the packed weights of the heads ``names``
+    (``pack_cell_heads``), evaluated at the decoded cells only (``decode.ctdet_decode_at_cells``)."""
+    __slots__ = ("names", "feat", "hidden", "w1", "b1", "w2", "b2")
+
+    def __init__(self, names, feat, hidden, w1, b1, w2, b2):
+        self.names, self.feat, self.hidden = tuple(names), feat, int(hidden)
+        self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
+
+
 def fold_bn(conv_bias, bn, cout, device):
     """BatchNorm2d(eval) [+ conv bias] -> per-channel (scale, shift), fp32.
 
@@ -141,9 +172,13 @@ class PlanBuilder:
     RANGE_WORDS = 2 * 64 * 16   # CN_RANGE_WORDS: 2 sides x 64 slots x one word per 64-byte line
 
     def __init__(self, device, B, H, W, dtype=torch.float32, wcache=None, split=None, exps=None,
-                 calibrating=False, track=None):
+                 calibrating=False, track=None, defer=()):
         assert dtype in (torch.float32, torch.float16)
         self.device = device
+        # heads that are NOT launched densely (PlannedModule.defer_heads): ``heads_from_convs`` leaves
+        # them out of the fused launch and puts a DeferredHeads handle into ``self.deferred``
+        self.defer = () if calibrating else tuple(defer)
+        self.deferred = None
         # fp32 networks compute in f32s (three fp16 MFMAs per product, fp32-level accuracy, 5.3x
         # the matrix rate of v_mfma_f32_32x32x2_f32) unless split=False / CN_F32S=0 asks for the
         # plain fp32 matrix instruction
@@ -858,8 +893,6 @@ class PlanBuilder:
         lid = self._lid()
         names = list(pairs.keys())
         firsts = [pairs[n][0] for n in names]
-        w = torch.cat([c.weight.detach() for c in firsts], 0)
-        b = torch.cat([c.bias.detach() for c in firsts], 0)
         k = firsts[0].kernel_size[0]
         if (self.fuse_heads and self.dtype == torch.float32 and k == 3 and
                 not x.nchw and x.c_off == 0 and
@@ -868,16 +901,19 @@ class PlanBuilder:
                 all(c.padding[0] == 1 and c.stride[0] == 1 for c in firsts) and
                 all(tuple(pairs[n][1].kernel_size) == (1, 1) for n in names)):
             if len(names) <= 8:
-                return self._heads_fused(x, names, pairs, w, b, lid)
+                late = self._deferrable(x, names, pairs)
+                if late:
+                    dense = [n for n in names if n not in late]
+                    self.deferred = self._cell_heads(x, late, pairs)
+                    return self._heads_fused(x, dense, pairs, *self._cat_firsts(dense, pairs), lid)
+                return self._heads_fused(x, names, pairs, *self._cat_firsts(names, pairs), lid)
             # more heads than one launch takes (the exdet task's nine, opts.py:299-306): groups of up
             # to six (head counts the kernel is exercised with: 3 and 6), each its own fused launch
             # over the same feature map; one hidden exponent (lid)
             outs = {}
             for g in range(0, len(names), 6):
                 sub = names[g:g + 6]
-                outs.update(self._heads_fused(
-                    x, sub, pairs, torch.cat([pairs[n][0].weight.detach() for n in sub], 0),
-                    torch.cat([pairs[n][0].bias.detach() for n in sub], 0), lid))
+                outs.update(self._heads_fused(x, sub, pairs, *self._cat_firsts(sub, pairs), lid))
             return {n: outs[n] for n in names}
         hcs = [c.weight.shape[0] for c in firsts]
         # an f32s tensor is addressable in whole 32-channel groups only: hidden widths that are
@@ -894,6 +930,7 @@ class PlanBuilder:
                                     padding=last.kernel_size[0] // 2, out_nchw=True,
                                     lid=lid + "/" + n)
             return outs
+        w, b = self._cat_firsts(names, pairs)
         mid = self.conv(x, w, bias=b, relu=True, stride=1, padding=k // 2,
                         wsources=[c.weight for c in firsts], out_plain=mid_plain, lid=lid + "/hid")
         off = 0
@@ -909,6 +946,12 @@ class PlanBuilder:
 
 
     @staticmethod
+    def _cat_firsts(names, pairs):
+        """Weights and biases of the first convolutions of ``names``, concatenated along Cout."""
+        return (torch.cat([pairs[n][0].weight.detach() for n in names], 0),
+                torch.cat([pairs[n][0].bias.detach() for n in names], 0))
+
+    @staticmethod
     def _fusable_hidden(hidden, couts):
         """Hidden widths the fused head kernel takes: 64 (one slice) or 128 / 192 / 256 (64-channel
         slices one after the other; their 1x1 outputs accumulate in one 96-row register tile)."""
@@ -918,6 +961,35 @@ class PlanBuilder:
         if hc > 64 and (max(couts) > 96 or os.environ.get("CN_FUSE_HEADS_WIDE", "1") == "0"):
             return False
         return True
+
+    def _deferrable(self, x, names, pairs):
+        """The heads of ``self.defer`` this plan leaves to the decode (all of them or none): one or two
+        heads of two outputs each on a feature map of whole 32-channel groups, all present, and something
+        left for the dense launch."""
+        late = [n for n in self.defer if n in names]
+        if not late or len(late) != len(self.defer) or len(late) > 2 or len(late) >= len(names) or x.C % 32:
+            return []
+        if any(pairs[n][1].weight.shape[0] != 2 for n in late):
+            return []
+        return late
+
+    def _cell_heads(self, x, late, pairs):
+        """DeferredHeads of the heads ``late`` on the feature map ``x``; the packed weights live in the
+        module's weight cache."""
+        firsts, lasts = [pairs[n][0] for n in late], [pairs[n][1] for n in late]
+        sources = [c.weight for c in firsts + lasts] + [c.bias for c in firsts + lasts if c.bias is not None]
+        cacheable = all(isinstance(t, torch.nn.Parameter) for t in sources)
+        key = self._wkey("cell_heads", sources) if cacheable else None
+        hit = self.wcache.get(key) if cacheable else None
+        if hit is None:
+            ev = torch.cuda.Event()
+            hit = pack_cell_heads(firsts, lasts, self.device) + (ev,)
+            ev.record()
+            if cacheable:
+                self._wput(key, hit)
+        self.keep += list(hit[:4])
+        self._pack_events.append(hit[4])
+        return DeferredHeads(late, x, firsts[0].weight.shape[0], *hit[:4])
 
     def _heads_fused(self, x, names, pairs, w1, b1, lid):
         """All heads as ONE launch (cn_heads3x3_1x1): the hidden channels of a head stay in LDS
@@ -1033,6 +1105,7 @@ class Plan:
         builder.finish()
         self.b = builder
         self.outputs = outputs  # name -> Act (NCHW)
+        self.deferred = builder.deferred   # DeferredHeads of a deferred-heads plan, else None
         self.graph = None
         self._static_in = None
 
@@ -1088,9 +1161,11 @@ class Plan:
                 b.range_sum_host.copy_(b.range_sum, non_blocking=True)
                 b.range_sum_event.record()
             self._digest_fresh = bool(digest)
-        if borrow:
-            return {k: v.t for k, v in self.outputs.items()}
-        return {k: v.t.clone() for k, v in self.outputs.items()}
+        out = {k: (v.t if borrow else v.t.clone()) for k, v in self.outputs.items()}
+        if self.deferred is not None:
+            # (the feature map behind the handle is the plan's own buffer either way: overwritten by the next run)
+            out["_deferred"] = self.deferred
+        return out
 
     # ---- f32s range words ------------------------------------------------------------------
     def range_report(self, reset=True):
@@ -1222,6 +1297,27 @@ class PlannedModule(torch.nn.Module):
         """Drop the launch lists only (mode switches): calibrated exponents and packed weights stay."""
         self.__dict__["_plans"] = {}
 
+    def defer_heads(self, names=()):
+        """Heads (by name) that callers of the deferred plan do not need as dense maps: that plan launches
+        the fused heads kernel for the other heads only and returns, under ``"_deferred"``, a
+        ``DeferredHeads`` handle from which the decode evaluates the named heads at the cells it selects.
+        The default is nothing deferred.  The mode is part of the plan key and survives ``drop_plans`` /
+        ``invalidate_plans``; ``forward`` stays dense unless asked (``deferred=True``); calibration always
+        runs the full description, so every exponent is what it is without the mode."""
+        self.__dict__["_defer"] = tuple(names)
+        return self
+
+    def deferral(self):
+        """The names ``defer_heads`` was last given (whatever the compute mode makes of them)."""
+        return self.__dict__.get("_defer", ())
+
+    def deferred_names(self):
+        """The heads the deferred plan leaves out: ``defer_heads``' names in an fp32 compute mode (f32s or
+        fp32-MFMA), nothing with ``half_compute()``."""
+        if self.compute_dtype != torch.float32:
+            return ()
+        return self.deferral()
+
     max_plans = int(os.environ.get("CN_PLAN_CACHE", "8"))   # LRU bound on cached input shapes
 
     # ---- f32s exponents ---------------------------------------------------------------------
@@ -1294,12 +1390,15 @@ class PlannedModule(torch.nn.Module):
         self.__dict__["_plans"] = {}      # plans bake the exponents into their epilogue constants
         return exps
 
-    def plan_for(self, B, H, W, device):
+    def plan_for(self, B, H, W, device, deferred=None):
         """The plan of one input shape.  Plans (activations + launch list) are kept in an LRU of
         ``max_plans`` shapes -- --keep_res / multi-scale evaluation sees many (H, W) -- while the
-        packed weights live in one per-module cache shared by all of them."""
+        packed weights live in one per-module cache shared by all of them.  ``deferred``: False = the
+        dense plan (every head a map); otherwise the plan the batch entry points of the detectors run,
+        which leaves out the heads of ``defer_heads`` (the same dense plan when none are set)."""
         cache = self.__dict__.setdefault("_plans", {})
-        key = (B, H, W, str(device), self.compute_dtype, self.f32s, self.range_tracking_on)
+        defer = () if deferred is False else self.deferred_names()
+        key = (B, H, W, str(device), self.compute_dtype, self.f32s, self.range_tracking_on, defer)
         plan = cache.pop(key, None)
         if plan is None:
             native.lib()  # raises if the HIP library is missing
@@ -1307,7 +1406,7 @@ class PlannedModule(torch.nn.Module):
                 pb = PlanBuilder(device, B, H, W, dtype=self.compute_dtype,
                                  wcache=self.__dict__.setdefault("_wcache", {}), split=self.f32s,
                                  exps=self.__dict__.get("_exps"),
-                                 track=None if self.range_tracking_on else False)
+                                 track=None if self.range_tracking_on else False, defer=defer)
                 x = pb.set_input(3)
                 outs = self.describe(pb, x)
             plan = Plan(pb, outs)
@@ -1375,8 +1474,11 @@ class PlannedModule(torch.nn.Module):
         self.__dict__["_low_cal_at"] = nf
         self.__dict__["_recalibrate"] = "decay"
 
-    def forward(self, x, borrow=False, events=None, event_after=None, check=None):
-        """[{head: (B,C,H/4,W/4)}] like the reference modules (fresh tensors).  ``borrow`` /
+    def forward(self, x, borrow=False, events=None, event_after=None, check=None, deferred=False):
+        """[{head: (B,C,H/4,W/4)}] like the reference modules (fresh tensors).  ``deferred=True`` runs the
+        deferred-heads plan instead (``defer_heads``): the maps of the remaining heads plus the handle
+        under ``"_deferred"`` -- or the dense result when the mode or the network's head form defers
+        nothing.  ``borrow`` /
         ``events``: see Plan.run.  ``check``: f32s range check of THIS forward before it returns
         (one stream synchronisation; on a clamped value the module re-calibrates on ``x`` and
         runs again).  Default: on for the fresh-tensor form, off with ``borrow=True`` -- those
@@ -1398,13 +1500,14 @@ class PlannedModule(torch.nn.Module):
             self.__dict__["_nfwd"] = self.__dict__.get("_nfwd", 0) + 1
         if check is None:
             check = f32s and not borrow
-        plan = self.plan_for(B, H, W, x.device)
+        deferred = bool(deferred)
+        plan = self.plan_for(B, H, W, x.device, deferred)
         out = plan.run(x, events=events, event_after=event_after, borrow=borrow, digest=bool(check and f32s))
         if check and f32s:
             st, bad = plan.range_status()
             if st == "overflow":
                 self.calibrate(x, merge=True)
-                plan = self.plan_for(B, H, W, x.device)
+                plan = self.plan_for(B, H, W, x.device, deferred)
                 if events is not None:
                     del events[:]          # the markers of the invalid forward
                 out = plan.run(x, events=events, event_after=event_after, borrow=borrow)

@@ -236,6 +236,11 @@ def _declare(lib):
     lib.cn_nms_topk_channel_f32.argtypes = [vp] + [i] * 6 + [vp, vp, vp, sz, vp]
     lib.cn_topk_f32.restype = i
     lib.cn_topk_f32.argtypes = [vp] + [i] * 6 + [vp, vp, vp, vp, sz, vp]
+    lib.cn_pack_cell_heads_w1.restype = i
+    lib.cn_pack_cell_heads_w1.argtypes = [vp, vp, i, i, vp]
+    lib.cn_ctdet_heads_at_cells_f32.restype = i
+    lib.cn_ctdet_heads_at_cells_f32.argtypes = [vp, i, i, i, i, i, i, ctypes.c_float, vp, vp, vp, i, vp, vp, i, i,
+                                                vp, vp, vp, vp, vp]
     lib.cn_gather_feat_f32.restype = i
     lib.cn_gather_feat_f32.argtypes = [vp, vp, vp] + [i] * 5 + [vp]
     lib.cn_ddd_decode_workspace_bytes.restype = sz

@@ -752,6 +752,28 @@ int cn_topk_f32(const float *heat, int B, int C, int H, int W, int K, int apply_
                 float *scores, int32_t *inds, int32_t *clses, void *workspace,
                 size_t workspace_bytes, void *stream);
 
+/* The gather-only ctdet heads at the decoded centres (cn_heads_at.hip).  ctdet_decode reads `wh` and `reg`
+ * only at the K winning cells of an image (decode.py:472-486), so a caller that does not need the dense
+ * maps runs the fused heads for `hm` alone, cn_topk_f32 on it (with the logistic and the peak test:
+ * scores, inds, clses) and then this ONE launch: for every (b, k) and each deferred head
+ *   ReLU(conv3x3(feat, w1) + bias1) at cell inds[b, k] (padding 1), then the 1x1 (two outputs per head),
+ * and the box arithmetic of cn_ctdet_decode_f32: dets (B, K, 6) = [x1, y1, x2, y2, score, cls].
+ * feat: NHWC with row pitch `pitch` channels; dtype CN_DTYPE_F32S (real = stored * feat_mul, feat_mul the
+ *   tensor's 2^e; pitch a multiple of 32) or CN_DTYPE_F32 (plain floats; feat_mul ignored).  Cin % 32 == 0.
+ * n_heads: 1 = wh only (the centre is then cell + 0.5), 2 = wh, reg.  hidden: 64, 128, 192 or 256.
+ * w1_packed: cn_pack_cell_heads_w1 of the first convolutions concatenated along Cout,
+ *   (n_heads * hidden, Cin, 3, 3) -- the ORIGINAL fp32 weights, not split and not pre-scaled;
+ *   bias1 (n_heads * hidden); w2 (n_heads, 2, hidden); bias2 (n_heads, 2) or NULL.
+ * Plain fp32 FMA throughout: no range words, nothing clamps.  head_vals: optional (B, K, 2 * n_heads), the
+ * raw head outputs [w, h, (reg_x, reg_y)].  A cell index outside the map gives a NaN box, never an
+ * out-of-bounds read.  Asynchronous on `stream`, no workspace, no allocation; the same cell may repeat. */
+int cn_pack_cell_heads_w1(const float *w, float *out, int N, int Cin, void *stream);
+int cn_ctdet_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
+                                float feat_mul, const float *scores, const int32_t *inds,
+                                const int32_t *clses, int K, const float *w1_packed, const float *bias1,
+                                int hidden, int n_heads, const float *w2, const float *bias2, float *dets,
+                                float *head_vals, void *stream);
+
 /* _transpose_and_gather_feat (models/utils.py:12-26): out[b,k,c] = feat[b,c,inds[b,k]] for an
  * NCHW map, without the reference's full-tensor permute().contiguous(). */
 int cn_gather_feat_f32(const float *feat, const int32_t *inds, float *out, int B, int C, int H,
