@@ -1755,6 +1755,34 @@ bool pose_ws_plan(int B, int C, int H, int W, int J, int K, PoseWs *p, BandPlan 
     return true;
 }
 
+// stages B and C on rows that hold stage A (cn_multi_pose_decode_f32 and cn_multi_pose_match_f32 both end here)
+int pose_match_stages(const float *hm_hp, const float *hp_offset, int B, int J, int H, int W, int K,
+                      int apply_sigmoid, const BandPlan &bph, float *dets, float *cand_s, int32_t *cand_i,
+                      float *hp_s, int32_t *hp_i, hipStream_t st)
+{
+    const int D = 4 + 1 + 2 * J + 1;
+    int rc;
+    // stage B: per-joint top-K of the keypoint heat-map
+    if (bph.nbands == 1) {
+        rc = launch_nms_topk(hm_hp, B, J, H, W, K, apply_sigmoid, bph, hp_s, hp_i, st);
+        if (rc != CN_OK) return rc;
+    } else {
+        rc = launch_nms_topk(hm_hp, B, J, H, W, K, apply_sigmoid, bph, cand_s, cand_i, st);
+        if (rc != CN_OK) return rc;
+        hipLaunchKernelGGL(merge_topk_kernel<MODE_CHANNEL>, dim3(B * J), dim3(NTM),
+                           sizeof(SelShared), st, cand_s, cand_i, bph.nbands * K, bph.nbands * K, H,
+                           W, K, J, (const float *)nullptr, (const float *)nullptr, 0,
+                           (float *)nullptr, 0, hp_i, hp_s, (const float *)nullptr, 0,
+                           (int32_t *)nullptr);
+        CN_CHECK_LAUNCH();
+    }
+    // stage C
+    hipLaunchKernelGGL(pose_match_kernel, dim3(J, B), dim3(KMAX), 0, st, hp_s, hp_i, hp_offset,
+                       dets, J, K, H, W, D);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 }  // namespace
 
 extern "C" size_t cn_multi_pose_decode_workspace_bytes(int B, int C, int H, int W, int J, int K)
@@ -1795,25 +1823,26 @@ extern "C" int cn_multi_pose_decode_f32(const float *heat, const float *wh, cons
                        dets, D, (int32_t *)nullptr, (float *)nullptr, kps, J, (int32_t *)nullptr);
     CN_CHECK_LAUNCH();
     if (!hm_hp) return CN_OK;
-    // stage B: per-joint top-K of the keypoint heat-map
-    if (bph.nbands == 1) {
-        rc = launch_nms_topk(hm_hp, B, J, H, W, K, apply_sigmoid, bph, hp_s, hp_i, st);
-        if (rc != CN_OK) return rc;
-    } else {
-        rc = launch_nms_topk(hm_hp, B, J, H, W, K, apply_sigmoid, bph, cand_s, cand_i, st);
-        if (rc != CN_OK) return rc;
-        hipLaunchKernelGGL(merge_topk_kernel<MODE_CHANNEL>, dim3(B * J), dim3(NTM),
-                           sizeof(SelShared), st, cand_s, cand_i, bph.nbands * K, bph.nbands * K, H,
-                           W, K, J, (const float *)nullptr, (const float *)nullptr, 0,
-                           (float *)nullptr, 0, hp_i, hp_s, (const float *)nullptr, 0,
-                           (int32_t *)nullptr);
-        CN_CHECK_LAUNCH();
-    }
-    // stage C
-    hipLaunchKernelGGL(pose_match_kernel, dim3(J, B), dim3(KMAX), 0, st, hp_s, hp_i, hp_offset,
-                       dets, J, K, H, W, D);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    return pose_match_stages(hm_hp, hp_offset, B, J, H, W, K, apply_sigmoid, bph, dets, cand_s, cand_i, hp_s, hp_i,
+                             st);
+}
+
+extern "C" int cn_multi_pose_match_f32(const float *hm_hp, const float *hp_offset, int B, int J, int H, int W,
+                                       int K, int flags, float *dets, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    BandPlan bp, bph;
+    if (J <= 0) return hm_hp ? CN_ERR_SHAPE : CN_ERR_NULL;
+    int rc = decode_checks(hm_hp, B, J, H, W, K, &bph);
+    if (rc != CN_OK) return rc;
+    if (!dets || !workspace) return CN_ERR_NULL;
+    PoseWs p;   // the layout of cn_multi_pose_decode_f32 with a one-class centre map
+    if (!pose_ws_plan(B, 1, H, W, J, K, &p, &bp, &bph)) return CN_ERR_UNSUPPORTED;
+    if (workspace_bytes < p.total) return CN_ERR_WORKSPACE;
+    char *ws = (char *)workspace;
+    return pose_match_stages(hm_hp, hp_offset, B, J, H, W, K, flags & CN_DECODE_SIGMOID, bph, dets,
+                             (float *)(ws + p.cand_s), (int32_t *)(ws + p.cand_i), (float *)(ws + p.hp_s),
+                             (int32_t *)(ws + p.hp_i), (hipStream_t)stream);
 }
 
 

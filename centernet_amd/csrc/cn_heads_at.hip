@@ -1,4 +1,5 @@
-// cn_heads_at.hip -- the gather-only ctdet heads (wh, reg) evaluated at the K decoded centres.
+// cn_heads_at.hip -- the gather-only heads evaluated at the K decoded centres: wh, reg of ctdet
+// (cn_ctdet_heads_at_cells_f32) and wh, hps, reg of multi_pose (cn_multi_pose_heads_at_cells_f32).
 //
 // ctdet_decode (decode.py:472-486) reads `wh` and `reg` at the K winning cells of every image and
 // nowhere else, so a detector that does not need the dense maps runs the fused heads launch for `hm`
@@ -8,17 +9,30 @@
 //     out    = w2 . hidden + b2                  (two outputs per head)
 // followed by the box arithmetic of emit_rows (cn_decode.hip), written the same way.
 //
+// multi_pose_decode (decode.py:506-519) gathers `hps`, `reg` and `wh` at the K centres in the same way; the
+// pose entry runs the same kernel body with the heads (wh, hps[, reg]) -- 2 + 2J [+ 2] outputs per cell --
+// and the row writer of emit_rows<MODE_POSE> (stage A of cn_multi_pose_decode_f32).  Staging and weight
+// stream are shared; the task only selects the row writer (template parameter TASK).
+//
 // Arithmetic: plain fp32 FMA on the decoded feature values ((hi + lo) * 2^e is exact in fp32) and the
 // original, unsplit fp32 weights: no range words, nothing can clamp.
 //
 // Shape of the launch: one workgroup of 256 threads per (image, 16 consecutive cells).  The 3x3 x 64
 // channel patches of its cells sit in LDS (16 x 576 floats per 64-channel chunk of Cin); a thread owns
-// one or two hidden channels of the concatenated heads and CT of the 16 cells, streams its weights as
+// one to three hidden channels of the concatenated heads and CT of the 16 cells, streams its weights as
 // float4 (four consecutive k of one channel: cn_pack_cell_heads_w1 order) with the next group of loads
 // in flight, and reads the patch values as LDS broadcasts (all lanes of a wave share the cell).  The
-// hidden values then replace the patches in LDS, four lanes share one 1x1 output, and the first
-// threads assemble the rows.  Weight traffic: the whole first-layer weight once per workgroup from L2
-// (295 KB for two 64-wide heads, B * ceil(K / 16) workgroups).
+// hidden values then replace the patches in LDS, four lanes share one 1x1 output (a loop over the
+// 16 x outputs-per-cell values, 64 per pass), and the rows are assembled from them.  Weight traffic:
+// the whole first-layer weight once per workgroup from L2 (295 KB for two 64-wide heads, 1.77 MB for
+// three 256-wide ones; B * ceil(K / 16) workgroups).
+//
+// LDS: the patches take 16 x 576 floats (36 KB).  The hidden rows overwrite them, which holds N <= 576
+// hidden channels.  Three 256-wide heads (N = 768) run on a three-slot instantiation whose rows are
+// 768 floats wide (16 x 768 floats = 48 KB, still static LDS): the patches are staged once and every
+// weight is read once, where walking the heads in groups would stage the patches per group and keep a
+// second pass over the chunk loop alive for one shape.  The narrower instantiations keep 36 KB, so the
+// ctdet launches are what they were.
 #include "cn_common.h"
 #include "cn_internal.h"
 
@@ -28,7 +42,10 @@ constexpr int HA_NT = 256;      // threads per workgroup
 constexpr int HA_CELLS = 16;    // cells per workgroup
 constexpr int HA_CC = 64;       // channels of Cin per staged chunk
 constexpr int HA_ROW = 9 * HA_CC;   // floats of one cell's patch (one chunk)
-constexpr int HA_MAXN = 512;    // hidden channels of all deferred heads together
+constexpr int HA_MAXN = 768;    // hidden channels of all deferred heads together
+constexpr int HA_MAXJ = 17;     // joints of the pose task's hps head
+constexpr int HA_MAXOUT = 2 + 2 * HA_MAXJ + 2;   // 1x1 outputs per cell: wh, hps, reg
+enum { HA_CTDET = 0, HA_POSE = 1 };
 constexpr int HA_PF = 4;        // float4 weight groups in flight per channel slot
 
 struct HeadsAtArgs {
@@ -37,24 +54,85 @@ struct HeadsAtArgs {
     const int32_t *inds, *clses;  // (B, K)
     const cn_f32x4 *w1;         // (9 * Cin / 4, N) float4: cn_pack_cell_heads_w1
     const float *b1;            // (N)
-    const float *w2;            // (n_heads, 2, hidden)
-    const float *b2;            // (n_heads, 2) or null
-    float *dets;                // (B, K, 6)
-    float *vals;                // (B, K, 2 * n_heads) or null: the raw head values
+    const float *w2;            // (out, hidden): the 1x1 rows of the heads, concatenated in head order
+    const float *b2;            // (out) or null
+    float *dets;                // (B, K, 6), pose: (B, K, 5 + 2J + 1)
+    float *vals;                // (B, K, out) or null: the raw head values
     float mul;                  // 2^e of an f32s feature map (1 for plain)
     int H, W, Cin, pitch, K, hidden, n_heads, N;
+    int c0, c1;                 // outputs of head 0 and head 1 (head 2 has the rest)
+    int out;                    // 1x1 outputs per cell, all heads
+    int J;                      // pose: joints
 };
 
+// rows of ctdet_decode (emit_rows<MODE_CTDET>): [x1, y1, x2, y2, score, cls]; o = this cell's head values
+__device__ __forceinline__ void ha_ctdet_row(const HeadsAtArgs &a, size_t row, int ind, const float *o)
+{
+    float *d = a.dets + row * 6;
+    const float score = a.scores[row];
+    const float cls = (float)a.clses[row];
+    if (ind < 0) {
+        const float nan = __builtin_nanf("");
+        d[0] = nan; d[1] = nan; d[2] = nan; d[3] = nan; d[4] = score; d[5] = cls;
+        if (a.vals)
+            for (int v = 0; v < a.out; ++v) a.vals[row * a.out + v] = nan;
+        return;
+    }
+    const int yi = ind / a.W, xi = ind - yi * a.W;
+    float xs = (float)xi, ys = (float)yi;
+    if (a.n_heads > 1) {  // decode.py:472-476
+        xs = xs + o[2];
+        ys = ys + o[3];
+    } else {  // decode.py:477-479
+        xs = xs + 0.5f;
+        ys = ys + 0.5f;
+    }
+    const float w = o[0];
+    const float h = o[1];
+    d[0] = xs - w / 2;  // decode.py:489-492
+    d[1] = ys - h / 2;
+    d[2] = xs + w / 2;
+    d[3] = ys + h / 2;
+    d[4] = score;
+    d[5] = cls;
+    if (a.vals)
+        for (int v = 0; v < a.out; ++v) a.vals[row * a.out + v] = o[v];
+}
+
+// column `col` of a multi_pose_decode stage-A row (emit_rows<MODE_POSE>): [x1, y1, x2, y2, score, 2J kps,
+// cls]; o = this cell's head values [w, h, 2J hps, (reg_x, reg_y)].  One rounding per line, as there.
+__device__ __forceinline__ float ha_pose_col(const HeadsAtArgs &a, size_t row, int ind, const float *o, int col)
+{
+    const int D = 5 + 2 * a.J + 1;
+    if (col == 4) return a.scores[row];
+    if (col == D - 1) return (float)a.clses[row];
+    if (ind < 0) return __builtin_nanf("");
+    const int yi = ind / a.W, xi = ind - yi * a.W;
+    if (col >= 5) {  // decode.py:506-509: kps = hps[ind] + (xs, ys) with the un-offset centre
+        const int v = col - 5;
+        return o[2 + v] + (float)((v & 1) ? yi : xi);
+    }
+    const bool isy = col & 1;
+    float c = (float)(isy ? yi : xi);
+    if (a.n_heads > 2) c = c + o[2 + 2 * a.J + (isy ? 1 : 0)];   // decode.py:510-514
+    else c = c + 0.5f;                                          // decode.py:515-517
+    const float half = o[isy ? 1 : 0] / 2;                       // decode.py:523-526
+    return col < 2 ? c - half : c + half;
+}
+
 // CT cells per thread (16 / CT cell groups of 16 * CT threads), NS channel slots per thread
-template <bool F32S, int CT, int NS>
+template <bool F32S, int CT, int NS, int TASK = HA_CTDET>
 __global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const HeadsAtArgs a)
 {
     constexpr int CG = HA_CELLS / CT;     // cell groups
     constexpr int TPC = HA_NT / CG;       // threads across the channels (a multiple of 64: a wave shares its cells)
     static_assert(TPC % 64 == 0, "the lanes of a wave read one cell's patch");
-    __shared__ __attribute__((aligned(16))) float lds[HA_CELLS * HA_ROW];   // patches, then the hidden values
+    // a cell's hidden row: as wide as its patch row, or the channels this form holds when those are more
+    constexpr int HROW = NS * TPC > HA_ROW ? NS * TPC : HA_ROW;
+    static_assert(NS * TPC <= HA_MAXN && HA_CELLS * HROW * 4 <= 48 * 1024, "static LDS");
+    __shared__ __attribute__((aligned(16))) float lds[HA_CELLS * HROW];   // patches, then the hidden values
     __shared__ int s_ind[HA_CELLS];
-    __shared__ float s_out[HA_CELLS * 4];
+    __shared__ float s_out[HA_CELLS * (TASK == HA_POSE ? HA_MAXOUT : 4)];
 
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
@@ -150,7 +228,7 @@ __global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const Head
         kq_base += (size_t)nkq;
     }
 
-    // hidden[cell][n] = ReLU(acc + b1[n]) replaces the patches (N <= 512 <= HA_ROW)
+    // hidden[cell][n] = ReLU(acc + b1[n]) replaces the patches (N <= NS * TPC <= HROW)
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -159,63 +237,48 @@ __global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const Head
             const float bias = a.b1[n];
 #pragma unroll
             for (int i = 0; i < CT; ++i)
-                lds[(i * CG + cg) * HA_ROW + n] = __builtin_fmaxf(acc[s][i] + bias, 0.f);
+                lds[(i * CG + cg) * HROW + n] = __builtin_fmaxf(acc[s][i] + bias, 0.f);
         }
     }
     __syncthreads();
 
-    // 1x1: output o = (cell, head, j) of 16 x 2 x 2, four lanes each (all 256 threads take part in the
-    // shuffles; an absent head contributes nothing)
-    {
-        const int o = tid >> 2, sub = tid & 3;
-        const int cell = o >> 2, head = (o >> 1) & 1, j = o & 1;
+    // 1x1: output o = (cell, r) of 16 x a.out, four lanes each, 64 outputs per pass (all 256 threads take
+    // part in the shuffles; a pass's absent outputs contribute nothing)
+    const int nout = HA_CELLS * a.out;
+    for (int o0 = 0; o0 < nout; o0 += HA_NT / 4) {
+        const int o = o0 + (tid >> 2), sub = tid & 3;
+        const bool live = o < nout;
+        const int cell = o / a.out, r = o - cell * a.out;
+        const int head = (r >= a.c0) + (r >= a.c0 + a.c1);
         float sum = 0.f;
-        if (head < a.n_heads) {
-            const float *w = a.w2 + ((size_t)head * 2 + j) * a.hidden;
-            const float *h = &lds[cell * HA_ROW + head * a.hidden];
+        if (live) {
+            const float *w = a.w2 + (size_t)r * a.hidden;
+            const float *h = &lds[cell * HROW + head * a.hidden];
             for (int c = sub; c < a.hidden; c += 4) sum = __builtin_fmaf(w[c], h[c], sum);
         }
         sum += __shfl_xor(sum, 1);
         sum += __shfl_xor(sum, 2);
-        if (sub == 0) {
-            if (head < a.n_heads && a.b2) sum += a.b2[head * 2 + j];
+        if (live && sub == 0) {
+            if (a.b2) sum += a.b2[r];
             s_out[o] = sum;
         }
     }
     __syncthreads();
 
-    if (tid < ncell) {
-        const size_t row = (size_t)b * a.K + k0 + tid;
-        const int ind = s_ind[tid];
-        float *d = a.dets + row * 6;
-        const float score = a.scores[row];
-        const float cls = (float)a.clses[row];
-        if (ind < 0) {
-            const float nan = __builtin_nanf("");
-            d[0] = nan; d[1] = nan; d[2] = nan; d[3] = nan; d[4] = score; d[5] = cls;
-            if (a.vals)
-                for (int v = 0; v < 2 * a.n_heads; ++v) a.vals[row * (2 * a.n_heads) + v] = nan;
-            return;
+    if (TASK == HA_CTDET) {
+        if (tid < ncell) ha_ctdet_row(a, (size_t)b * a.K + k0 + tid, s_ind[tid], &s_out[tid * a.out]);
+    } else {
+        const int D = 5 + 2 * a.J + 1;
+        for (int i = tid; i < ncell * D; i += HA_NT) {
+            const int cell = i / D, col = i - cell * D;
+            const size_t row = (size_t)b * a.K + k0 + cell;
+            a.dets[row * D + col] = ha_pose_col(a, row, s_ind[cell], &s_out[cell * a.out], col);
         }
-        const int yi = ind / a.W, xi = ind - yi * a.W;
-        float xs = (float)xi, ys = (float)yi;
-        if (a.n_heads > 1) {  // decode.py:472-476
-            xs = xs + s_out[tid * 4 + 2];
-            ys = ys + s_out[tid * 4 + 3];
-        } else {  // decode.py:477-479
-            xs = xs + 0.5f;
-            ys = ys + 0.5f;
-        }
-        const float w = s_out[tid * 4 + 0];
-        const float h = s_out[tid * 4 + 1];
-        d[0] = xs - w / 2;  // decode.py:489-492
-        d[1] = ys - h / 2;
-        d[2] = xs + w / 2;
-        d[3] = ys + h / 2;
-        d[4] = score;
-        d[5] = cls;
         if (a.vals)
-            for (int v = 0; v < 2 * a.n_heads; ++v) a.vals[row * (2 * a.n_heads) + v] = s_out[tid * 4 + v];
+            for (int i = tid; i < ncell * a.out; i += HA_NT) {
+                const int cell = i / a.out;
+                a.vals[((size_t)b * a.K + k0) * a.out + i] = s_ind[cell] < 0 ? __builtin_nanf("") : s_out[i];
+            }
     }
 }
 
@@ -252,16 +315,21 @@ extern "C" int cn_pack_cell_heads_w1(const float *w, float *out, int N, int Cin,
     return CN_OK;
 }
 
-extern "C" int cn_ctdet_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
-                                           float feat_mul, const float *scores, const int32_t *inds,
-                                           const int32_t *clses, int K, const float *w1_packed,
-                                           const float *bias1, int hidden, int n_heads, const float *w2,
-                                           const float *bias2, float *dets, float *head_vals, void *stream)
+namespace {
+
+// the checks and the launch of both entries
+template <int TASK>
+int heads_at_cells(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype, float feat_mul,
+                   const float *scores, const int32_t *inds, const int32_t *clses, int K,
+                   const float *w1_packed, const float *bias1, int hidden, int n_heads, int J, const float *w2,
+                   const float *bias2, float *dets, float *head_vals, void *stream)
 {
     if (!feat || !scores || !inds || !clses || !w1_packed || !bias1 || !w2 || !dets) return CN_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || K <= 0 || pitch < Cin) return CN_ERR_SHAPE;
     if (dtype != CN_DTYPE_F32S && dtype != CN_DTYPE_F32) return CN_ERR_UNSUPPORTED;
-    if (n_heads < 1 || n_heads > 2 || hidden < 64 || hidden > 256 || (hidden & 63)) return CN_ERR_UNSUPPORTED;
+    constexpr int H0 = TASK == HA_POSE ? 2 : 1;     // ctdet: wh[, reg]; pose: wh, hps[, reg]
+    if (n_heads < H0 || n_heads > H0 + 1 || hidden < 64 || hidden > 256 || (hidden & 63)) return CN_ERR_UNSUPPORTED;
+    if (TASK == HA_POSE && (J < 1 || J > HA_MAXJ)) return CN_ERR_UNSUPPORTED;
     if ((Cin & 31) || (pitch & 3) || (dtype == CN_DTYPE_F32S && (pitch & 31))) return CN_ERR_UNSUPPORTED;
     if ((long)H * W >= (1L << 31) || B > 65535) return CN_ERR_UNSUPPORTED;
     if (!cn_aligned16(feat) || !cn_aligned16(w1_packed)) return CN_ERR_ALIGN;
@@ -271,19 +339,49 @@ extern "C" int cn_ctdet_heads_at_cells_f32(const void *feat, int B, int H, int W
     a.dets = dets; a.vals = head_vals; a.mul = dtype == CN_DTYPE_F32S ? feat_mul : 1.f;
     a.H = H; a.W = W; a.Cin = Cin; a.pitch = pitch; a.K = K; a.hidden = hidden; a.n_heads = n_heads;
     a.N = hidden * n_heads;
+    a.J = J;
+    a.c0 = 2;
+    a.c1 = TASK == HA_POSE ? 2 * J : 2;
+    a.out = TASK == HA_POSE ? 2 + 2 * J + (n_heads > 2 ? 2 : 0) : 2 * n_heads;
     const dim3 grid((unsigned)cn_cdiv(K, HA_CELLS), (unsigned)B), block(HA_NT);
     hipStream_t st = (hipStream_t)stream;
     const bool s = dtype == CN_DTYPE_F32S;
-#define HA_LAUNCH(CT, NS)                                                                               \
-    do {                                                                                                \
-        if (s) hipLaunchKernelGGL((decode_heads_at_cells_kernel<true, CT, NS>), grid, block, 0, st, a); \
-        else hipLaunchKernelGGL((decode_heads_at_cells_kernel<false, CT, NS>), grid, block, 0, st, a);  \
+#define HA_LAUNCH(CT, NS)                                                                                     \
+    do {                                                                                                      \
+        if (s) hipLaunchKernelGGL((decode_heads_at_cells_kernel<true, CT, NS, TASK>), grid, block, 0, st, a); \
+        else hipLaunchKernelGGL((decode_heads_at_cells_kernel<false, CT, NS, TASK>), grid, block, 0, st, a);  \
     } while (0)
-    if (a.N <= 64) HA_LAUNCH(4, 1);
-    else if (a.N <= 128) HA_LAUNCH(8, 1);
+    // N = 64 is one ctdet head; N > 512 is three pose heads: each form exists for the task that reaches it
+    if (a.N <= 64) {
+        if constexpr (TASK == HA_CTDET) HA_LAUNCH(4, 1);
+    } else if (a.N <= 128) HA_LAUNCH(8, 1);
     else if (a.N <= 256) HA_LAUNCH(16, 1);
-    else HA_LAUNCH(16, 2);
+    else if (a.N <= 512) HA_LAUNCH(16, 2);
+    else if constexpr (TASK == HA_POSE) HA_LAUNCH(16, 3);
 #undef HA_LAUNCH
     CN_CHECK_LAUNCH();
     return CN_OK;
+}
+
+}  // namespace
+
+extern "C" int cn_ctdet_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
+                                           float feat_mul, const float *scores, const int32_t *inds,
+                                           const int32_t *clses, int K, const float *w1_packed,
+                                           const float *bias1, int hidden, int n_heads, const float *w2,
+                                           const float *bias2, float *dets, float *head_vals, void *stream)
+{
+    return heads_at_cells<HA_CTDET>(feat, B, H, W, Cin, pitch, dtype, feat_mul, scores, inds, clses, K, w1_packed,
+                                    bias1, hidden, n_heads, 0, w2, bias2, dets, head_vals, stream);
+}
+
+extern "C" int cn_multi_pose_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch,
+                                                int dtype, float feat_mul, const float *scores,
+                                                const int32_t *inds, const int32_t *clses, int K,
+                                                const float *w1_packed, const float *bias1, int hidden,
+                                                int n_heads, int J, const float *w2, const float *bias2,
+                                                float *dets, float *head_vals, void *stream)
+{
+    return heads_at_cells<HA_POSE>(feat, B, H, W, Cin, pitch, dtype, feat_mul, scores, inds, clses, K, w1_packed,
+                                   bias1, hidden, n_heads, J, w2, bias2, dets, head_vals, stream);
 }

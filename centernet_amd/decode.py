@@ -4,6 +4,7 @@ fused HIP kernels in csrc/cn_decode.hip / cn_pose.hip.
 Same callables, same argument meaning, tensors in / tensor out:
     ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100)      decode.py:464-495
     multi_pose_decode(heat, wh, kps, reg, hm_hp, hp_offset, K)      decode.py:497-571
+    ctdet_decode_at_cells / multi_pose_decode_at_cells              the same rows from a deferred-heads plan
     _nms / _topk / _topk_channel                                    decode.py:9-15, 92-119
 ``heat`` is post-sigmoid as in the reference; pass ``apply_sigmoid=True`` with logits
 to fuse ``hm.sigmoid_()`` (detectors/ctdet.py:31) into the same pass over the heat-map.
@@ -151,6 +152,71 @@ def ctdet_decode_at_cells(heat, late, K=100, apply_sigmoid=False, return_inds=Fa
         native.ptr(late.w1), native.ptr(late.b1), late.hidden, nh, native.ptr(late.w2), native.ptr(late.b2),
         native.ptr(dets), native.ptr(vals), st)
     native.check(rc, "cn_ctdet_heads_at_cells_f32")
+    out = (dets,)
+    if return_inds:
+        out += (inds.long(),)
+    if return_vals:
+        out += (vals,)
+    return out if len(out) > 1 else dets
+
+
+def multi_pose_decode_at_cells(heat, late, hm_hp=None, hp_offset=None, K=100, apply_sigmoid=False,
+                               return_inds=False, return_vals=False):
+    """``multi_pose_decode`` without dense ``wh`` / ``hps`` / ``reg`` maps: ``late`` is the
+    ``engine.DeferredHeads`` of a deferred-heads plan (heads ``('wh', 'hps')`` or ``('wh', 'hps', 'reg')``).
+    Three calls on the current stream: the image-level top-K of ``heat`` (``cn_topk_f32``),
+    ``cn_multi_pose_heads_at_cells_f32``, which evaluates the heads at those cells in plain fp32 and writes
+    the stage-A rows (B, K, 5 + 2J + 1), and -- with ``hm_hp`` -- ``cn_multi_pose_match_f32``, the joint
+    candidates and the match of ``multi_pose_decode`` on the dense ``hm_hp`` / ``hp_offset``.
+    ``apply_sigmoid``: ``heat`` and ``hm_hp`` hold logits.  ``return_vals``: also the raw head values
+    (B, K, 2 + 2J [+ 2]) in head order."""
+    heat, hm_hp, hp_offset = _prep(heat, hm_hp, hp_offset)
+    lib = native.lib()
+    if heat.dim() != 4:
+        raise RuntimeError("heat must be (B, C, H, W)")
+    B, C, H, W = heat.shape
+    f = late.feat
+    if late.names not in (("wh", "hps"), ("wh", "hps", "reg")):
+        raise RuntimeError("multi_pose_decode_at_cells takes the heads ('wh', 'hps') or ('wh', 'hps', 'reg'), "
+                           "got %r" % (late.names,))
+    couts = tuple(late.couts)
+    if couts[0] != 2 or couts[1] % 2 or not 2 <= couts[1] <= 34 or couts[2:] not in ((), (2,)):
+        raise RuntimeError("multi_pose_decode_at_cells: head outputs %r are not (2, 2J[, 2])" % (couts,))
+    J = couts[1] // 2
+    if (f.B, f.H, f.W) != (B, H, W) or f.nchw or f.fmt not in ("f32s", "f32") or f.t.device != heat.device:
+        raise RuntimeError("the deferred heads' feature map must be an NHWC fp32 / f32s (%d, %d, %d, .) "
+                           "activation on the heat-map's device" % (B, H, W))
+    dev = heat.device
+    _expect("hm_hp", hm_hp, B, J, H, W, dev)
+    _expect("hp_offset", hp_offset, B, 2, H, W, dev)
+    if K > H * W:
+        raise RuntimeError("selected index k out of range")
+    scores = torch.empty((B, K), device=dev, dtype=torch.float32)
+    inds = torch.empty((B, K), device=dev, dtype=torch.int32)
+    clses = torch.empty((B, K), device=dev, dtype=torch.int32)
+    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
+    st = native.stream_ptr()
+    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN,
+                         native.ptr(scores), native.ptr(inds), native.ptr(clses), native.ptr(ws), ws.numel(), st)
+    if rc:
+        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
+    native.check(rc, "cn_topk_f32")
+    nh, nout = len(late.names), sum(couts)
+    dets = torch.empty((B, K, 5 + 2 * J + 1), device=dev, dtype=torch.float32)
+    vals = torch.empty((B, K, nout), device=dev, dtype=torch.float32) if return_vals else None
+    s = f.fmt == "f32s"
+    rc = lib.cn_multi_pose_heads_at_cells_f32(
+        f.ptr(), B, H, W, f.C, f.pitch, native.DTYPE_F32S if s else native.DTYPE_F32,
+        float(2.0 ** f.exp) if s else 1.0, native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
+        native.ptr(late.w1), native.ptr(late.b1), late.hidden, nh, J, native.ptr(late.w2), native.ptr(late.b2),
+        native.ptr(dets), native.ptr(vals), st)
+    native.check(rc, "cn_multi_pose_heads_at_cells_f32")
+    if hm_hp is not None:
+        mws = _workspace(lib.cn_multi_pose_decode_workspace_bytes(B, 1, H, W, J, K), dev)
+        rc = lib.cn_multi_pose_match_f32(native.ptr(hm_hp), native.ptr(hp_offset), B, J, H, W, K,
+                                         int(bool(apply_sigmoid)), native.ptr(dets), native.ptr(mws),
+                                         mws.numel(), st)
+        native.check(rc, "cn_multi_pose_match_f32")
     out = (dets,)
     if return_inds:
         out += (inds.long(),)

@@ -1,13 +1,15 @@
 """multi_pose task (public behaviour of src/lib/detectors/multi_pose.py:24-81): centre
 heat-map + box size + 17 joint offsets, optional joint heat-maps / sub-pixel offsets, decoded
-by the fused ``cn_multi_pose_decode_f32`` kernels."""
+by the fused ``cn_multi_pose_decode_f32`` kernels (``run_batch``: top-K on ``hm``, the ``wh`` / ``hps`` /
+``reg`` heads at the K cells only, ``cn_multi_pose_heads_at_cells_f32``, then the joint match on the dense
+``hm_hp`` / ``hp_offset``, ``cn_multi_pose_match_f32``)."""
 import time
 
 import numpy as np
 import torch
 
 from .. import native
-from ..decode import multi_pose_decode
+from ..decode import multi_pose_decode, multi_pose_decode_at_cells
 from ..frame_pipe import DeviceTail
 from ..post_process import multi_pose_post_process
 from ..utils import flip_average, flip_average_batch
@@ -16,10 +18,30 @@ from .base_detector import BaseDetector
 ROW = 39  # [x1, y1, x2, y2, score, 17 x (x, y)]
 
 
+def deferred_pose_heads(opt):
+    """The heads ``run_batch`` leaves to the decode: ``multi_pose_decode`` only gathers ``wh``, ``hps`` (and
+    ``reg``) at the K decoded centres (decode.py:506-519), so their dense maps are not computed.  ``hm``,
+    ``hm_hp`` and ``hp_offset`` stay dense.  Not with flip-test (the averaged maps are needed) or K > 128; the
+    network side (fp32 compute mode, fusable 3x3 + 1x1 heads) is the plan builder's decision."""
+    if opt.flip_test or opt.K > 128 or 'wh' not in opt.heads or 'hps' not in opt.heads:
+        return ()
+    if 'reg' in opt.heads:
+        return ('wh', 'hps', 'reg') if opt.reg_offset else ()
+    return ('wh', 'hps')
+
+
 class MultiPoseDetector(BaseDetector):
     def __init__(self, opt):
         super(MultiPoseDetector, self).__init__(opt)
         self.flip_idx = opt.flip_idx
+        self.model.defer_heads(deferred_pose_heads(opt))
+
+    def _sync_deferral(self):
+        """Keep the module's mode in step with the options (one may have changed after construction): the
+        frame pipe reads the range words of ``plan_for(...)``, which must be the plan that ran."""
+        names = deferred_pose_heads(self.opt)
+        if names != self.model.deferral():
+            self.model.defer_heads(names)
 
     _list_results = True
 
@@ -69,18 +91,24 @@ class MultiPoseDetector(BaseDetector):
             ev = None
             if probe is not None:
                 ev = probe['net_events'] = []
-            o = self.model(images, borrow=True, events=ev,
+            self._sync_deferral()
+            o = self.model(images, borrow=True, deferred=True, events=ev,
                            event_after=None if probe is None else probe.get('event_after'))[-1]
             if probe is not None:
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record()
             if self.opt.mse_loss and self.opt.hm_hp:
                 raise NotImplementedError("run_batch: mse_loss joint heat-maps are not logits")
-            dets = multi_pose_decode(o['hm'], o['wh'], o['hps'],
-                                     reg=o['reg'] if self.opt.reg_offset else None,
-                                     hm_hp=o['hm_hp'] if self.opt.hm_hp else None,
-                                     hp_offset=o['hp_offset'] if self.opt.reg_hp_offset else None,
-                                     K=self.opt.K, apply_sigmoid=True)
+            hm_hp = o['hm_hp'] if self.opt.hm_hp else None
+            hp_offset = o['hp_offset'] if self.opt.reg_hp_offset else None
+            late = o.get('_deferred')
+            if late is not None:
+                dets = multi_pose_decode_at_cells(o['hm'], late, hm_hp=hm_hp, hp_offset=hp_offset,
+                                                  K=self.opt.K, apply_sigmoid=True)
+            else:
+                dets = multi_pose_decode(o['hm'], o['wh'], o['hps'],
+                                         reg=o['reg'] if self.opt.reg_offset else None,
+                                         hm_hp=hm_hp, hp_offset=hp_offset, K=self.opt.K, apply_sigmoid=True)
             if probe is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
@@ -94,6 +122,7 @@ class MultiPoseDetector(BaseDetector):
         if not flip:
             return self.run_batch(images)
         self._note_unchecked_forward()
+        self._sync_deferral()        # flip-test defers nothing: plan_for(...) is then this dense plan
         opt = self.opt
         with torch.no_grad():
             o = self.model(images, borrow=True)[-1]

@@ -114,10 +114,12 @@ def _pow2(e):
 
 
 def pack_cell_heads(firsts, lasts, device):
-    """Weights of gather-only heads for ``cn_ctdet_heads_at_cells_f32``: ``firsts`` the 3x3 convolutions
-    (hidden, Cin, 3, 3) and ``lasts`` the 1x1 convolutions (2, hidden) of the heads, in order.  The ORIGINAL
-    fp32 values (no split, no pre-scale): first layers concatenated along Cout and re-ordered by
-    ``cn_pack_cell_heads_w1`` on the current stream.  Returns (w1, b1, w2, b2) device tensors."""
+    """Weights of gather-only heads for ``cn_ctdet_heads_at_cells_f32`` / ``cn_multi_pose_heads_at_cells_f32``:
+    ``firsts`` the 3x3 convolutions (hidden, Cin, 3, 3) and ``lasts`` the 1x1 convolutions (cout, hidden) of the
+    heads, in order.  The ORIGINAL fp32 values (no split, no pre-scale): first layers concatenated along Cout
+    and re-ordered by ``cn_pack_cell_heads_w1`` on the current stream; the 1x1 rows concatenated in head order,
+    ``w2`` (sum of couts, hidden) and ``b2`` (sum of couts,) -- for two-output heads the bytes of
+    (n, 2, hidden) / (n, 2).  Returns (w1, b1, w2, b2) device tensors."""
     lib = native.lib()
     w = torch.cat([c.weight.detach() for c in firsts], 0).to(device=device, dtype=torch.float32).contiguous()
     b1 = torch.cat([c.bias.detach() for c in firsts], 0).to(device=device, dtype=torch.float32).contiguous()
@@ -126,9 +128,10 @@ def pack_cell_heads(firsts, lasts, device):
     w1 = torch.empty((9 * ci // 4, N, 4), device=device, dtype=torch.float32)
     native.check(lib.cn_pack_cell_heads_w1(native.ptr(w), native.ptr(w1), N, ci, native.stream_ptr()),
                  "cn_pack_cell_heads_w1")
-    w2 = torch.stack([c.weight.detach().reshape(2, hidden) for c in lasts], 0)
+    w2 = torch.cat([c.weight.detach().reshape(-1, hidden) for c in lasts], 0)
     w2 = w2.to(device=device, dtype=torch.float32).contiguous()
-    b2 = torch.stack([torch.zeros(2) if c.bias is None else c.bias.detach().cpu().float() for c in lasts], 0)
+    b2 = torch.cat([torch.zeros(c.weight.shape[0]) if c.bias is None else c.bias.detach().cpu().float()
+                    for c in lasts], 0)
     b2 = b2.to(device=device, dtype=torch.float32).contiguous()
     return w1, b1, w2, b2
 
@@ -136,12 +139,15 @@ def pack_cell_heads(firsts, lasts, device):
 class DeferredHeads:
     """What a deferred-heads plan hands to the decode instead of dense maps: the feature ``Act`` the heads
     read (pointer, pitch, format, exponent) and the packed weights of the heads ``names``
-    (``pack_cell_heads``), evaluated at the decoded cells only (``decode.ctdet_decode_at_cells``)."""
-    __slots__ = ("names", "feat", "hidden", "w1", "b1", "w2", "b2")
+    (``pack_cell_heads``), evaluated at the decoded cells only (``decode.ctdet_decode_at_cells``,
+    ``decode.multi_pose_decode_at_cells``).  ``couts``: the outputs per head, in order (two each when not
+    given)."""
+    __slots__ = ("names", "feat", "hidden", "w1", "b1", "w2", "b2", "couts")
 
-    def __init__(self, names, feat, hidden, w1, b1, w2, b2):
+    def __init__(self, names, feat, hidden, w1, b1, w2, b2, couts=None):
         self.names, self.feat, self.hidden = tuple(names), feat, int(hidden)
         self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
+        self.couts = tuple(int(c) for c in couts) if couts is not None else (2,) * len(self.names)
 
 
 def fold_bn(conv_bias, bn, cout, device):
@@ -963,13 +969,17 @@ class PlanBuilder:
         return True
 
     def _deferrable(self, x, names, pairs):
-        """The heads of ``self.defer`` this plan leaves to the decode (all of them or none): one or two
-        heads of two outputs each on a feature map of whole 32-channel groups, all present, and something
-        left for the dense launch."""
+        """The heads of ``self.defer`` this plan leaves to the decode (all of them or none): up to three
+        heads of 2 .. 34 outputs each and one hidden width, ``len(late) * hidden <= 768`` (what the cells
+        kernel holds), on a feature map of whole 32-channel groups, all present, and something left for the
+        dense launch."""
         late = [n for n in self.defer if n in names]
-        if not late or len(late) != len(self.defer) or len(late) > 2 or len(late) >= len(names) or x.C % 32:
+        if not late or len(late) != len(self.defer) or len(late) > 3 or len(late) >= len(names) or x.C % 32:
             return []
-        if any(pairs[n][1].weight.shape[0] != 2 for n in late):
+        if any(not 2 <= pairs[n][1].weight.shape[0] <= 34 for n in late):
+            return []
+        hidden = [pairs[n][0].weight.shape[0] for n in late]
+        if any(h != hidden[0] for h in hidden) or len(late) * hidden[0] > 768:
             return []
         return late
 
@@ -989,7 +999,8 @@ class PlanBuilder:
                 self._wput(key, hit)
         self.keep += list(hit[:4])
         self._pack_events.append(hit[4])
-        return DeferredHeads(late, x, firsts[0].weight.shape[0], *hit[:4])
+        return DeferredHeads(late, x, firsts[0].weight.shape[0], *hit[:4],
+                             couts=[c.weight.shape[0] for c in lasts])
 
     def _heads_fused(self, x, names, pairs, w1, b1, lid):
         """All heads as ONE launch (cn_heads3x3_1x1): the hidden channels of a head stay in LDS

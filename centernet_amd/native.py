@@ -241,6 +241,9 @@ def _declare(lib):
     lib.cn_ctdet_heads_at_cells_f32.restype = i
     lib.cn_ctdet_heads_at_cells_f32.argtypes = [vp, i, i, i, i, i, i, ctypes.c_float, vp, vp, vp, i, vp, vp, i, i,
                                                 vp, vp, vp, vp, vp]
+    lib.cn_multi_pose_heads_at_cells_f32.restype = i
+    lib.cn_multi_pose_heads_at_cells_f32.argtypes = [vp, i, i, i, i, i, i, ctypes.c_float, vp, vp, vp, i, vp, vp,
+                                                     i, i, i, vp, vp, vp, vp, vp]
     lib.cn_gather_feat_f32.restype = i
     lib.cn_gather_feat_f32.argtypes = [vp, vp, vp] + [i] * 5 + [vp]
     lib.cn_ddd_decode_workspace_bytes.restype = sz
@@ -263,6 +266,8 @@ def _declare(lib):
     lib.cn_multi_pose_decode_workspace_bytes.argtypes = [i] * 6
     lib.cn_multi_pose_decode_f32.restype = i
     lib.cn_multi_pose_decode_f32.argtypes = [vp] * 6 + [i] * 7 + [vp, vp, sz, vp]
+    lib.cn_multi_pose_match_f32.restype = i
+    lib.cn_multi_pose_match_f32.argtypes = [vp, vp] + [i] * 6 + [vp, vp, sz, vp]
 
 
 def lib():

@@ -767,12 +767,35 @@ int cn_topk_f32(const float *heat, int B, int C, int H, int W, int K, int apply_
  * Plain fp32 FMA throughout: no range words, nothing clamps.  head_vals: optional (B, K, 2 * n_heads), the
  * raw head outputs [w, h, (reg_x, reg_y)].  A cell index outside the map gives a NaN box, never an
  * out-of-bounds read.  Asynchronous on `stream`, no workspace, no allocation; the same cell may repeat. */
+/* cn_pack_cell_heads_w1: w (N, Cin, 3, 3) -> out (9 * Cin / 4, N, 4) floats, 16-byte aligned; N a multiple of
+ * 64 up to 768 (three 256-wide heads), Cin % 32 == 0. */
 int cn_pack_cell_heads_w1(const float *w, float *out, int N, int Cin, void *stream);
 int cn_ctdet_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
                                 float feat_mul, const float *scores, const int32_t *inds,
                                 const int32_t *clses, int K, const float *w1_packed, const float *bias1,
                                 int hidden, int n_heads, const float *w2, const float *bias2, float *dets,
                                 float *head_vals, void *stream);
+
+/* The same launch for the multi_pose task: multi_pose_decode gathers `wh`, `hps` and `reg` at the K centres
+ * only (decode.py:506-519), so a caller that does not need those dense maps leaves them out of the fused
+ * heads launch, runs cn_topk_f32 on `hm` and then this ONE launch, which evaluates the deferred heads at the
+ * B x K cells and writes stage A of cn_multi_pose_decode_f32:
+ *   dets (B, K, 5 + 2J + 1) = [x1, y1, x2, y2, score, 2J kps, cls],
+ *   kps[2j] = hps[2j] + xi, kps[2j + 1] = hps[2j + 1] + yi (the un-offset integer centre, decode.py:508-509),
+ *   xs = xi + reg_x (xi + 0.5 without reg), box = xs -+ w / 2, ys -+ h / 2; one float32 rounding per step.
+ * Feature, dtype, alignment and `inds` rules are those of cn_ctdet_heads_at_cells_f32 (a cell outside the map
+ * gives a NaN row that keeps score and class; a repeated cell is computed again with the same bits).
+ * n_heads: 2 = wh, hps; 3 = wh, hps, reg (this order).  J: joints, 1 .. 17; hps has 2J outputs.
+ * hidden: 64, 128, 192 or 256, the same for all heads (n_heads * hidden <= 768).
+ * w1_packed / bias1: as above, (n_heads * hidden) rows.  w2 (2 + 2J [+ 2], hidden): the 1x1 rows of the heads
+ * concatenated in head order; bias2 (2 + 2J [+ 2]) or NULL.  head_vals: optional (B, K, 2 + 2J [+ 2]), the raw
+ * head outputs in head order.  Plain fp32 FMA, no range words, nothing clamps.  Asynchronous on `stream`, no
+ * workspace, no allocation, capturable. */
+int cn_multi_pose_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
+                                     float feat_mul, const float *scores, const int32_t *inds,
+                                     const int32_t *clses, int K, const float *w1_packed, const float *bias1,
+                                     int hidden, int n_heads, int J, const float *w2, const float *bias2,
+                                     float *dets, float *head_vals, void *stream);
 
 /* _transpose_and_gather_feat (models/utils.py:12-26): out[b,k,c] = feat[b,c,inds[b,k]] for an
  * NCHW map, without the reference's full-tensor permute().contiguous(). */
@@ -845,6 +868,15 @@ int cn_multi_pose_decode_f32(const float *heat, const float *wh, const float *kp
                              const float *hp_offset, int B, int C, int H, int W,
                              int J, int K, int apply_sigmoid, float *dets,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* Stages B and C of cn_multi_pose_decode_f32 on rows that already hold stage A (from that function without
+ * hm_hp, or from cn_multi_pose_heads_at_cells_f32): _nms + _topk_channel on hm_hp (B, J, H, W) -- one or two
+ * launches, by the band plan -- then the joint match (decode.py:528-569) with the dense hp_offset (B, 2, H, W)
+ * or NULL (candidate + 0.5); dets (B, K, 5 + 2J + 1) is updated in place.  cn_multi_pose_decode_f32 runs the
+ * same internal function, so the two give the same bits.  flags: CN_DECODE_SIGMOID = hm_hp holds logits.
+ * K <= 128.  Workspace: cn_multi_pose_decode_workspace_bytes(B, 1, H, W, J, K) suffices. */
+int cn_multi_pose_match_f32(const float *hm_hp, const float *hp_offset, int B, int J, int H, int W, int K,
+                            int flags, float *dets, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
