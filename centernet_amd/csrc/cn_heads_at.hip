@@ -1,5 +1,6 @@
 // cn_heads_at.hip -- the gather-only heads evaluated at the K decoded centres: wh, reg of ctdet
-// (cn_ctdet_heads_at_cells_f32) and wh, hps, reg of multi_pose (cn_multi_pose_heads_at_cells_f32).
+// (cn_ctdet_heads_at_cells_f32), wh, hps, reg of multi_pose (cn_multi_pose_heads_at_cells_f32) and dep, rot,
+// dim, wh, reg of ddd (cn_ddd_heads_at_cells_f32).
 //
 // ctdet_decode (decode.py:472-486) reads `wh` and `reg` at the K winning cells of every image and
 // nowhere else, so a detector that does not need the dense maps runs the fused heads launch for `hm`
@@ -27,6 +28,13 @@
 // the whole first-layer weight once per workgroup from L2 (295 KB for two 64-wide heads, 1.77 MB for
 // three 256-wide ones; B * ceil(K / 16) workgroups).
 //
+// ddd_decode (decode.py:426-462) gathers `dep`, `rot`, `dim`, `wh` and `reg` at the K centres.  Five 256-wide
+// heads are 1280 hidden channels, more than one workgroup holds, and every column of a ddd row depends on one
+// head only: the ddd task walks *head groups* in a third grid dimension.  A workgroup evaluates the one to three
+// heads of its group (its own packed first layer, N <= 768) for its 16 cells and writes those heads' columns
+// straight into the rows (ddd_assemble_kernel's arithmetic); group 0 adds score and class, the group that owns
+// `reg` (group 0 without `reg`) the centre.  No second pass, nothing shared between workgroups, no atomics.
+//
 // LDS: the patches take 16 x 576 floats (36 KB).  The hidden rows overwrite them, which holds N <= 576
 // hidden channels.  Three 256-wide heads (N = 768) run on a three-slot instantiation whose rows are
 // 768 floats wide (16 x 768 floats = 48 KB, still static LDS): the patches are staged once and every
@@ -45,8 +53,21 @@ constexpr int HA_ROW = 9 * HA_CC;   // floats of one cell's patch (one chunk)
 constexpr int HA_MAXN = 768;    // hidden channels of all deferred heads together
 constexpr int HA_MAXJ = 17;     // joints of the pose task's hps head
 constexpr int HA_MAXOUT = 2 + 2 * HA_MAXJ + 2;   // 1x1 outputs per cell: wh, hps, reg
-enum { HA_CTDET = 0, HA_POSE = 1 };
+enum { HA_CTDET = 0, HA_POSE = 1, HA_DDD = 2 };
 constexpr int HA_PF = 4;        // float4 weight groups in flight per channel slot
+constexpr int HA_MAXGROUPS = 5; // ddd: head groups of one launch (one head each at the most)
+constexpr int HA_GROUP_HEADS = 3;   // heads of one group (the channel slots of the widest form)
+constexpr int HA_DDD_OUT = 16;  // ddd: 1x1 outputs per cell of one group (rot + dim + wh = 13 at the most)
+
+// ddd: one group of consecutive heads -- its weights and, per head, the outputs and where they go
+struct HeadsAtGroup {
+    const cn_f32x4 *w1;         // (9 * Cin / 4, n_heads * hidden) float4
+    const float *b1, *w2, *b2;  // (n_heads * hidden), (out, hidden), (out) or null
+    int n_heads;
+    int cout[HA_GROUP_HEADS];   // outputs per head
+    int col[HA_GROUP_HEADS];    // first column of the head in a row of dets
+    int voff[HA_GROUP_HEADS];   // first column of the head in a row of head_vals
+};
 
 struct HeadsAtArgs {
     const char *feat;           // NHWC, row pitch `pitch` channels; f32s or plain fp32
@@ -63,6 +84,12 @@ struct HeadsAtArgs {
     int c0, c1;                 // outputs of head 0 and head 1 (head 2 has the rest)
     int out;                    // 1x1 outputs per cell, all heads
     int J;                      // pose: joints
+    // ddd only (behind everything the other tasks read: their argument offsets are what they were)
+    HeadsAtGroup grp[HA_MAXGROUPS];   // indexed by blockIdx.z
+    int D;                      // columns of a row of dets: 18 with wh, else 16
+    int vals_out;               // columns of a row of head_vals: all heads of all groups
+    int raw_depth;              // CN_DECODE_DDD_RAW_DEPTH: column 11 = 1 / (sigmoid(dep) + 1e-6) - 1
+    int half_group;             // the group that writes the centre as cell + 0.5 (no reg head), or -1
 };
 
 // rows of ctdet_decode (emit_rows<MODE_CTDET>): [x1, y1, x2, y2, score, cls]; o = this cell's head values
@@ -132,14 +159,25 @@ __global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const Head
     static_assert(NS * TPC <= HA_MAXN && HA_CELLS * HROW * 4 <= 48 * 1024, "static LDS");
     __shared__ __attribute__((aligned(16))) float lds[HA_CELLS * HROW];   // patches, then the hidden values
     __shared__ int s_ind[HA_CELLS];
-    __shared__ float s_out[HA_CELLS * (TASK == HA_POSE ? HA_MAXOUT : 4)];
+    __shared__ float s_out[HA_CELLS * (TASK == HA_POSE ? HA_MAXOUT : TASK == HA_DDD ? HA_DDD_OUT : 4)];
 
     const int tid = threadIdx.x;
     const int b = blockIdx.y;
     const int k0 = blockIdx.x * HA_CELLS;
     const int ncell = min(HA_CELLS, a.K - k0);
     const int HW = a.H * a.W;
-    const int N = a.N;
+    // the heads this workgroup evaluates: the launch's (ctdet, pose) or those of its group (ddd)
+    int N = a.N, out = a.out, hc0 = a.c0, hc1 = a.c1;
+    const cn_f32x4 *w1 = a.w1;
+    const float *b1 = a.b1, *w2 = a.w2, *b2 = a.b2;
+    if constexpr (TASK == HA_DDD) {
+        const HeadsAtGroup &g = a.grp[blockIdx.z];
+        N = g.n_heads * a.hidden;
+        hc0 = g.cout[0];
+        hc1 = g.cout[1];
+        out = hc0 + hc1 + g.cout[2];
+        w1 = g.w1; b1 = g.b1; w2 = g.w2; b2 = g.b2;
+    }
 
     if (tid < HA_CELLS) {
         int ind = -1;
@@ -185,7 +223,7 @@ __global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const Head
         __syncthreads();
 
         const int nkq = 9 * cq;    // float4 groups of this chunk (a multiple of HA_PF: 72 or 144)
-        const cn_f32x4 *wq = a.w1 + kq_base * N;
+        const cn_f32x4 *wq = w1 + kq_base * N;
         cn_f32x4 wn[HA_PF][NS];
 #pragma unroll
         for (int p = 0; p < HA_PF; ++p)
@@ -234,7 +272,7 @@ __global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const Head
     for (int s = 0; s < NS; ++s) {
         const int n = nl + s * TPC;
         if (n < N) {
-            const float bias = a.b1[n];
+            const float bias = b1[n];
 #pragma unroll
             for (int i = 0; i < CT; ++i)
                 lds[(i * CG + cg) * HROW + n] = __builtin_fmaxf(acc[s][i] + bias, 0.f);
@@ -242,30 +280,70 @@ __global__ __launch_bounds__(HA_NT) void decode_heads_at_cells_kernel(const Head
     }
     __syncthreads();
 
-    // 1x1: output o = (cell, r) of 16 x a.out, four lanes each, 64 outputs per pass (all 256 threads take
+    // 1x1: output o = (cell, r) of 16 x out, four lanes each, 64 outputs per pass (all 256 threads take
     // part in the shuffles; a pass's absent outputs contribute nothing)
-    const int nout = HA_CELLS * a.out;
+    const int nout = HA_CELLS * out;
     for (int o0 = 0; o0 < nout; o0 += HA_NT / 4) {
         const int o = o0 + (tid >> 2), sub = tid & 3;
         const bool live = o < nout;
-        const int cell = o / a.out, r = o - cell * a.out;
-        const int head = (r >= a.c0) + (r >= a.c0 + a.c1);
+        const int cell = o / out, r = o - cell * out;
+        const int head = (r >= hc0) + (r >= hc0 + hc1);
         float sum = 0.f;
         if (live) {
-            const float *w = a.w2 + (size_t)r * a.hidden;
+            const float *w = w2 + (size_t)r * a.hidden;
             const float *h = &lds[cell * HROW + head * a.hidden];
             for (int c = sub; c < a.hidden; c += 4) sum = __builtin_fmaf(w[c], h[c], sum);
         }
         sum += __shfl_xor(sum, 1);
         sum += __shfl_xor(sum, 2);
         if (live && sub == 0) {
-            if (a.b2) sum += a.b2[r];
+            if (b2) sum += b2[r];
             s_out[o] = sum;
         }
     }
     __syncthreads();
 
-    if (TASK == HA_CTDET) {
+    if constexpr (TASK == HA_DDD) {
+        // ddd_assemble_kernel's row [xs, ys, score, rot(8), depth, dim(3), (wh(2),) cls]: this group's columns
+        const HeadsAtGroup &g = a.grp[blockIdx.z];
+        const int D = a.D;
+        for (int i = tid; i < ncell * out; i += HA_NT) {
+            const int cell = i / out, r = i - cell * out;
+            const int head = (r >= hc0) + (r >= hc0 + hc1);
+            const int j = r - (head > 0 ? hc0 : 0) - (head > 1 ? hc1 : 0);
+            const int col = (head == 0 ? g.col[0] : head == 1 ? g.col[1] : g.col[2]) + j;
+            const int vcol = (head == 0 ? g.voff[0] : head == 1 ? g.voff[1] : g.voff[2]) + j;
+            const size_t row = (size_t)b * a.K + k0 + cell;
+            const int ind = s_ind[cell];
+            const float raw = ind < 0 ? __builtin_nanf("") : s_out[i];
+            float v = raw;
+            if (ind >= 0) {
+                if (col < 2) {   // reg: decode.py:433-436
+                    const int yi = ind / a.W, xi = ind - yi * a.W;
+                    v = (float)(col ? yi : xi) + raw;
+                } else if (col == 11 && a.raw_depth) {   // detectors/ddd.py:60, as CN_DECODE_DDD_RAW_DEPTH
+                    v = 1.0f / (sigmoidf_ref(raw) + 1e-6f) - 1.0f;
+                }
+            }
+            a.dets[row * D + col] = v;
+            if (a.vals) a.vals[row * a.vals_out + vcol] = raw;
+        }
+        // the columns no head of this group owns
+        if (tid < ncell) {
+            const size_t row = (size_t)b * a.K + k0 + tid;
+            float *d = a.dets + row * D;
+            if (blockIdx.z == 0) {
+                d[2] = a.scores[row];
+                d[D - 1] = (float)a.clses[row];
+            }
+            if ((int)blockIdx.z == a.half_group) {   // decode.py:437-439
+                const int ind = s_ind[tid];
+                const int yi = ind / a.W, xi = ind - yi * a.W;
+                d[0] = ind < 0 ? __builtin_nanf("") : (float)xi + 0.5f;
+                d[1] = ind < 0 ? __builtin_nanf("") : (float)yi + 0.5f;
+            }
+        }
+    } else if (TASK == HA_CTDET) {
         if (tid < ncell) ha_ctdet_row(a, (size_t)b * a.K + k0 + tid, s_ind[tid], &s_out[tid * a.out]);
     } else {
         const int D = 5 + 2 * a.J + 1;
@@ -317,7 +395,27 @@ extern "C" int cn_pack_cell_heads_w1(const float *w, float *out, int N, int Cin,
 
 namespace {
 
-// the checks and the launch of both entries
+// the instantiation that holds N hidden channels (N = 64 is one head of 64: ctdet and ddd; N > 512 is three
+// 256-wide heads: pose and ddd -- each form exists for the tasks that reach it)
+template <int TASK>
+void ha_launch(const HeadsAtArgs &a, int N, dim3 grid, bool s, hipStream_t st)
+{
+    const dim3 block(HA_NT);
+#define HA_LAUNCH(CT, NS)                                                                                     \
+    do {                                                                                                      \
+        if (s) hipLaunchKernelGGL((decode_heads_at_cells_kernel<true, CT, NS, TASK>), grid, block, 0, st, a); \
+        else hipLaunchKernelGGL((decode_heads_at_cells_kernel<false, CT, NS, TASK>), grid, block, 0, st, a);  \
+    } while (0)
+    if (N <= 64) {
+        if constexpr (TASK != HA_POSE) HA_LAUNCH(4, 1);
+    } else if (N <= 128) HA_LAUNCH(8, 1);
+    else if (N <= 256) HA_LAUNCH(16, 1);
+    else if (N <= 512) HA_LAUNCH(16, 2);
+    else if constexpr (TASK != HA_CTDET) HA_LAUNCH(16, 3);
+#undef HA_LAUNCH
+}
+
+// the checks and the launch of the ctdet and pose entries
 template <int TASK>
 int heads_at_cells(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype, float feat_mul,
                    const float *scores, const int32_t *inds, const int32_t *clses, int K,
@@ -343,22 +441,8 @@ int heads_at_cells(const void *feat, int B, int H, int W, int Cin, int pitch, in
     a.c0 = 2;
     a.c1 = TASK == HA_POSE ? 2 * J : 2;
     a.out = TASK == HA_POSE ? 2 + 2 * J + (n_heads > 2 ? 2 : 0) : 2 * n_heads;
-    const dim3 grid((unsigned)cn_cdiv(K, HA_CELLS), (unsigned)B), block(HA_NT);
-    hipStream_t st = (hipStream_t)stream;
-    const bool s = dtype == CN_DTYPE_F32S;
-#define HA_LAUNCH(CT, NS)                                                                                     \
-    do {                                                                                                      \
-        if (s) hipLaunchKernelGGL((decode_heads_at_cells_kernel<true, CT, NS, TASK>), grid, block, 0, st, a); \
-        else hipLaunchKernelGGL((decode_heads_at_cells_kernel<false, CT, NS, TASK>), grid, block, 0, st, a);  \
-    } while (0)
-    // N = 64 is one ctdet head; N > 512 is three pose heads: each form exists for the task that reaches it
-    if (a.N <= 64) {
-        if constexpr (TASK == HA_CTDET) HA_LAUNCH(4, 1);
-    } else if (a.N <= 128) HA_LAUNCH(8, 1);
-    else if (a.N <= 256) HA_LAUNCH(16, 1);
-    else if (a.N <= 512) HA_LAUNCH(16, 2);
-    else if constexpr (TASK == HA_POSE) HA_LAUNCH(16, 3);
-#undef HA_LAUNCH
+    ha_launch<TASK>(a, a.N, dim3((unsigned)cn_cdiv(K, HA_CELLS), (unsigned)B), dtype == CN_DTYPE_F32S,
+                    (hipStream_t)stream);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -384,4 +468,61 @@ extern "C" int cn_multi_pose_heads_at_cells_f32(const void *feat, int B, int H, 
 {
     return heads_at_cells<HA_POSE>(feat, B, H, W, Cin, pitch, dtype, feat_mul, scores, inds, clses, K, w1_packed,
                                    bias1, hidden, n_heads, J, w2, bias2, dets, head_vals, stream);
+}
+
+extern "C" int cn_ddd_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
+                                         float feat_mul, const float *scores, const int32_t *inds,
+                                         const int32_t *clses, int K, int hidden, int n_groups,
+                                         const cn_cell_head_group *groups, int has_wh, int has_reg, int flags,
+                                         float *dets, float *head_vals, void *stream)
+{
+    if (!feat || !scores || !inds || !clses || !groups || !dets) return CN_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || K <= 0 || pitch < Cin || n_groups <= 0) return CN_ERR_SHAPE;
+    if (dtype != CN_DTYPE_F32S && dtype != CN_DTYPE_F32) return CN_ERR_UNSUPPORTED;
+    if (hidden < 64 || hidden > 256 || (hidden & 63) || n_groups > HA_MAXGROUPS) return CN_ERR_UNSUPPORTED;
+    const int n_heads = 3 + (has_wh ? 1 : 0) + (has_reg ? 1 : 0);
+    int total = 0, widest = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int n = groups[g].n_heads;
+        if (n < 1 || n > HA_GROUP_HEADS || n * hidden > HA_MAXN) return CN_ERR_UNSUPPORTED;
+        total += n;
+        widest = n > widest ? n : widest;
+    }
+    if (total != n_heads) return CN_ERR_UNSUPPORTED;
+    for (int g = 0; g < n_groups; ++g)
+        if (!groups[g].w1_packed || !groups[g].bias1 || !groups[g].w2) return CN_ERR_NULL;
+    if ((Cin & 31) || (pitch & 3) || (dtype == CN_DTYPE_F32S && (pitch & 31))) return CN_ERR_UNSUPPORTED;
+    if ((long)H * W >= (1L << 31) || B > 65535) return CN_ERR_UNSUPPORTED;
+    if (!cn_aligned16(feat)) return CN_ERR_ALIGN;
+    for (int g = 0; g < n_groups; ++g)
+        if (!cn_aligned16(groups[g].w1_packed)) return CN_ERR_ALIGN;
+    // the heads in their order: dep, rot, dim[, wh][, reg] -- outputs and first column in a row of dets
+    const int couts[5] = {1, 8, 3, 2, 2};
+    const int cols[5] = {11, 3, 12, has_wh ? 15 : 0, 0};
+    HeadsAtArgs a = {};
+    a.feat = (const char *)feat; a.scores = scores; a.inds = inds; a.clses = clses;
+    a.dets = dets; a.vals = head_vals; a.mul = dtype == CN_DTYPE_F32S ? feat_mul : 1.f;
+    a.H = H; a.W = W; a.Cin = Cin; a.pitch = pitch; a.K = K; a.hidden = hidden; a.n_heads = n_heads;
+    a.D = has_wh ? 18 : 16;
+    a.raw_depth = (flags & CN_DECODE_DDD_RAW_DEPTH) ? 1 : 0;
+    a.half_group = has_reg ? -1 : 0;
+    int head = 0, voff = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        HeadsAtGroup &d = a.grp[g];
+        d.w1 = (const cn_f32x4 *)groups[g].w1_packed;
+        d.b1 = groups[g].bias1; d.w2 = groups[g].w2; d.b2 = groups[g].bias2;
+        d.n_heads = groups[g].n_heads;
+        for (int h = 0; h < d.n_heads; ++h, ++head) {
+            const int t = head < 3 || has_wh ? head : 4;   // without wh the fourth head is reg
+            d.cout[h] = couts[t];
+            d.col[h] = cols[t];
+            d.voff[h] = voff;
+            voff += couts[t];
+        }
+    }
+    a.vals_out = voff;
+    ha_launch<HA_DDD>(a, widest * hidden, dim3((unsigned)cn_cdiv(K, HA_CELLS), (unsigned)B, (unsigned)n_groups),
+                      dtype == CN_DTYPE_F32S, (hipStream_t)stream);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
 }

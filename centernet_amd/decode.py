@@ -4,7 +4,9 @@ fused HIP kernels in csrc/cn_decode.hip / cn_pose.hip.
 Same callables, same argument meaning, tensors in / tensor out:
     ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100)      decode.py:464-495
     multi_pose_decode(heat, wh, kps, reg, hm_hp, hp_offset, K)      decode.py:497-571
-    ctdet_decode_at_cells / multi_pose_decode_at_cells              the same rows from a deferred-heads plan
+    ddd_decode(heat, rot, depth, dim, wh, reg, K)                   decode.py:426-462
+    ctdet_decode_at_cells / multi_pose_decode_at_cells / ddd_decode_at_cells
+                                                                    the same rows from a deferred-heads plan
     _nms / _topk / _topk_channel                                    decode.py:9-15, 92-119
 ``heat`` is post-sigmoid as in the reference; pass ``apply_sigmoid=True`` with logits
 to fuse ``hm.sigmoid_()`` (detectors/ctdet.py:31) into the same pass over the heat-map.
@@ -340,6 +342,64 @@ def ddd_decode(heat, rot, depth, dim, wh=None, reg=None, K=40, apply_sigmoid=Fal
                                native.ptr(dets), native.ptr(ws), ws.numel(), native.stream_ptr())
     native.check(rc, "cn_ddd_decode_f32")
     return dets
+
+
+_DDD_HEADS = (("dep", 1), ("rot", 8), ("dim", 3), ("wh", 2), ("reg", 2))
+
+
+def ddd_decode_at_cells(heat, late, K=40, apply_sigmoid=False, raw_depth=False, return_inds=False,
+                        return_vals=False):
+    """``ddd_decode`` without dense ``dep`` / ``rot`` / ``dim`` / ``wh`` / ``reg`` maps: ``late`` is the
+    ``engine.DeferredHeads`` of a deferred-heads plan with the heads ``('dep', 'rot', 'dim')`` + optional
+    ``'wh'`` + optional ``'reg'``, packed per group.  Two launches on the current stream: the image-level top-K
+    of ``heat`` (``cn_topk_f32``: the scores, cells and classes of ``ddd_decode``, bit for bit) and
+    ``cn_ddd_heads_at_cells_f32``, which evaluates the heads at those cells in plain fp32 and writes the
+    (B, K, 18) rows -- (B, K, 16) without ``wh``.  ``raw_depth``: column 11 is 1 / (sigmoid(dep) + 1e-6) - 1 as
+    ``ddd_decode(raw_depth=True)`` computes it, else the head's value.  ``return_vals``: also the raw head
+    values (B, K, 12 [+ 2] [+ 2]) in head order."""
+    (heat,) = _prep(heat)
+    lib = native.lib()
+    if heat.dim() != 4:
+        raise RuntimeError("heat must be (B, C, H, W)")
+    B, C, H, W = heat.shape
+    f = late.feat
+    names, couts = tuple(late.names), tuple(late.couts)
+    has_wh, has_reg = "wh" in names, "reg" in names
+    want = [hc for hc in _DDD_HEADS if hc[0] not in ("wh", "reg") or (has_wh if hc[0] == "wh" else has_reg)]
+    if names != tuple(n for n, _ in want) or couts != tuple(c for _, c in want) or late.groups is None:
+        raise RuntimeError("ddd_decode_at_cells takes the heads ('dep', 'rot', 'dim'[, 'wh'][, 'reg']) with "
+                           "(1, 8, 3[, 2][, 2]) outputs, packed per group; got %r with %r" % (names, couts))
+    if (f.B, f.H, f.W) != (B, H, W) or f.nchw or f.fmt not in ("f32s", "f32") or f.t.device != heat.device:
+        raise RuntimeError("the deferred heads' feature map must be an NHWC fp32 / f32s (%d, %d, %d, .) "
+                           "activation on the heat-map's device" % (B, H, W))
+    if K > H * W:
+        raise RuntimeError("selected index k out of range")
+    dev = heat.device
+    scores = torch.empty((B, K), device=dev, dtype=torch.float32)
+    inds = torch.empty((B, K), device=dev, dtype=torch.int32)
+    clses = torch.empty((B, K), device=dev, dtype=torch.int32)
+    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
+    st = native.stream_ptr()
+    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN,
+                         native.ptr(scores), native.ptr(inds), native.ptr(clses), native.ptr(ws), ws.numel(), st)
+    if rc:
+        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
+    native.check(rc, "cn_topk_f32")
+    dets = torch.empty((B, K, 18 if has_wh else 16), device=dev, dtype=torch.float32)
+    vals = torch.empty((B, K, sum(couts)), device=dev, dtype=torch.float32) if return_vals else None
+    s = f.fmt == "f32s"
+    rc = lib.cn_ddd_heads_at_cells_f32(
+        f.ptr(), B, H, W, f.C, f.pitch, native.DTYPE_F32S if s else native.DTYPE_F32,
+        float(2.0 ** f.exp) if s else 1.0, native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
+        late.hidden, len(late.groups), late.group_table(), int(has_wh), int(has_reg),
+        native.DECODE_DDD_RAW_DEPTH if raw_depth else 0, native.ptr(dets), native.ptr(vals), st)
+    native.check(rc, "cn_ddd_heads_at_cells_f32")
+    out = (dets,)
+    if return_inds:
+        out += (inds.long(),)
+    if return_vals:
+        out += (vals,)
+    return out if len(out) > 1 else dets
 
 
 def agnex_ct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr=None, l_regr=None, b_regr=None,

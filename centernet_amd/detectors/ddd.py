@@ -1,6 +1,7 @@
 """ddd task -- monocular 3-D detection (public behaviour of src/lib/detectors/ddd.py:22-91): centre
 heat-map + depth + orientation bins + box dimensions (+ 2-D size and sub-pixel offset) on the HIP
-network, decoded by ``cn_ddd_decode_f32``, lifted to camera coordinates on the host
+network, decoded by ``cn_ddd_decode_f32`` (``run_batch`` and the frame pipe: top-K on ``hm``, then the other heads at
+the K cells only, ``cn_ddd_heads_at_cells_f32``), lifted to camera coordinates on the host
 (``post_process.ddd_post_process``).  ``run(image, calib)``: the second argument is the frame's
 3 x 4 projection matrix (test.py:37-39,105-106); without it the detector's KITTI default is used.
 New surface: ``run_frames(frames, calibs)`` / ``run_frames_stream`` -- batches of frames, each with its
@@ -16,16 +17,29 @@ import numpy as np
 import torch
 
 from .. import native
-from ..decode import ddd_decode
+from ..decode import ddd_decode, ddd_decode_at_cells
 from ..frame_pipe import DeviceTail
 from ..image import get_affine_transform, invert_affine, warp_affine
 from ..post_process import ddd_norm_table, ddd_post_process, ddd_results_batch
 from .base_detector import BaseDetector, InputGeometry
 
 
+def deferred_ddd_heads(opt):
+    """The heads ``run_batch`` (and with it the frame pipe) leaves to the decode: ``ddd_decode`` scans only
+    ``hm`` densely and gathers ``dep``, ``rot``, ``dim`` (``wh`` with --reg_bbox, ``reg`` with --reg_offset) at the
+    K decoded centres (decode.py:426-462), so their dense maps are not computed.  Nothing with K > 128 or when a
+    head the options ask for is missing; the network side (fp32 compute mode, fusable 3x3 + 1x1 heads) is the
+    plan builder's decision."""
+    names = ('dep', 'rot', 'dim') + (('wh',) if opt.reg_bbox else ()) + (('reg',) if opt.reg_offset else ())
+    if opt.K > 128 or any(n not in opt.heads for n in names):
+        return ()
+    return names
+
+
 class DddDetector(BaseDetector):
     def __init__(self, opt):
         super(DddDetector, self).__init__(opt)
+        self.model.defer_heads(deferred_ddd_heads(opt))
         self.calib = np.array([[707.0493, 0, 604.0814, 45.75831],
                                [0, 707.0493, 180.5066, -0.3454157],
                                [0, 0, 1., 0.004981016]], dtype=np.float32)     # ddd.py:25-27
@@ -94,6 +108,17 @@ class DddDetector(BaseDetector):
         return out, self._meta(c, s, calib)
 
     # ------------------------------------------------------------------ network + decode
+    def _sync_deferral(self):
+        """Keep the module's mode in step with the options (one may have changed after construction): the
+        frame pipe reads the range words of ``plan_for(...)``, which must be the plan that ran."""
+        names = deferred_ddd_heads(self.opt)
+        if names != self.model.deferral():
+            self.model.defer_heads(names)
+
+    def _decode_at_cells(self, o):
+        """The rows of a deferred-heads forward: top-K on ``hm``, the other heads at the K cells only."""
+        return ddd_decode_at_cells(o['hm'], o['_deferred'], K=self.opt.K, apply_sigmoid=True, raw_depth=True)
+
     def process(self, images, return_time=False):
         """ddd.py:56-73: post-sigmoid centre map, depth = 1 / (sigmoid(dep) + 1e-6) - 1, then
         ``ddd_decode``.  The returned ``output`` holds the maps in that transformed state."""
@@ -236,7 +261,10 @@ class DddDetector(BaseDetector):
         the K gathered cells are inside ``cn_ddd_decode_f32``; raw (B, K, 18) rows, asynchronous."""
         self._note_unchecked_forward()
         with torch.no_grad():
-            o = self.model(images, borrow=True)[-1]
+            self._sync_deferral()
+            o = self.model(images, borrow=True, deferred=True)[-1]
+            if '_deferred' in o:
+                return self._decode_at_cells(o)
             return ddd_decode(o['hm'], o['rot'], o['dep'], o['dim'], wh=o['wh'] if self.opt.reg_bbox else None,
                               reg=o['reg'] if self.opt.reg_offset else None, K=self.opt.K,
                               apply_sigmoid=True, raw_depth=True)
@@ -275,7 +303,10 @@ class DddDetector(BaseDetector):
         (B, K, 18) rows of ``ddd_decode``; the centre map's sigmoid is fused into the decode."""
         self._note_unchecked_forward()
         with torch.no_grad():
-            o = self.model(images, borrow=True)[-1]
+            self._sync_deferral()
+            o = self.model(images, borrow=True, deferred=True)[-1]
+            if '_deferred' in o:
+                return self._decode_at_cells(o)
             dep = 1. / (o['dep'].sigmoid() + 1e-6) - 1.
             return ddd_decode(o['hm'], o['rot'], dep, o['dim'], wh=o['wh'] if self.opt.reg_bbox else None,
                               reg=o['reg'] if self.opt.reg_offset else None, K=self.opt.K,

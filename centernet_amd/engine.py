@@ -136,18 +136,54 @@ def pack_cell_heads(firsts, lasts, device):
     return w1, b1, w2, b2
 
 
+def cell_head_group_sizes(n_heads, hidden, wide=None):
+    """How a head set that one ``pack_cell_heads`` buffer does not hold (ddd's) is split into groups of
+    consecutive heads for ``cn_ddd_heads_at_cells_f32``: one head per group (the default: most workgroups for a
+    kernel that is starved for them), or with ``wide`` (``CN_CELL_HEAD_GROUPS=wide``, the A/B
+    alternative) groups as large as the entry takes -- three heads and 768 hidden channels."""
+    if wide is None:
+        wide = os.environ.get("CN_CELL_HEAD_GROUPS", "") == "wide"
+    per = min(native.CELL_GROUP_MAX_HEADS, 768 // int(hidden)) if wide else 1
+    return tuple(min(per, n_heads - g) for g in range(0, n_heads, per))
+
+
+def pack_cell_head_groups(firsts, lasts, device, sizes):
+    """``pack_cell_heads`` per group of consecutive heads (``sizes``: heads per group) ->
+    ((w1, b1, w2, b2, n_heads), ...), the groups of ``cn_ddd_heads_at_cells_f32``."""
+    groups, at = [], 0
+    for n in sizes:
+        groups.append(pack_cell_heads(firsts[at:at + n], lasts[at:at + n], device) + (int(n),))
+        at += n
+    assert at == len(firsts)
+    return tuple(groups)
+
+
 class DeferredHeads:
     """What a deferred-heads plan hands to the decode instead of dense maps: the feature ``Act`` the heads
     read (pointer, pitch, format, exponent) and the packed weights of the heads ``names``
     (``pack_cell_heads``), evaluated at the decoded cells only (``decode.ctdet_decode_at_cells``,
     ``decode.multi_pose_decode_at_cells``).  ``couts``: the outputs per head, in order (two each when not
-    given)."""
-    __slots__ = ("names", "feat", "hidden", "w1", "b1", "w2", "b2", "couts")
+    given).  ``groups``: for a head set that is packed per group of consecutive heads
+    (``pack_cell_head_groups``; ``decode.ddd_decode_at_cells``) the groups' (w1, b1, w2, b2, n_heads) --
+    ``w1`` .. ``b2`` are then None."""
+    __slots__ = ("names", "feat", "hidden", "w1", "b1", "w2", "b2", "couts", "groups", "_table")
 
-    def __init__(self, names, feat, hidden, w1, b1, w2, b2, couts=None):
+    def __init__(self, names, feat, hidden, w1=None, b1=None, w2=None, b2=None, couts=None, groups=None):
         self.names, self.feat, self.hidden = tuple(names), feat, int(hidden)
         self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
         self.couts = tuple(int(c) for c in couts) if couts is not None else (2,) * len(self.names)
+        self.groups = None if groups is None else tuple(groups)
+        self._table = None
+
+    def group_table(self):
+        """The ``cn_cell_head_group`` array of ``groups`` (built once; it holds raw pointers into them)."""
+        if self._table is None:
+            tab = (native.CellHeadGroup * len(self.groups))()
+            for t, (w1, b1, w2, b2, n) in zip(tab, self.groups):
+                t.w1_packed, t.bias1, t.w2, t.bias2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+                t.n_heads = n
+            self._table = tab
+        return self._table
 
 
 def fold_bn(conv_bias, bn, cout, device):
@@ -970,18 +1006,29 @@ class PlanBuilder:
 
     def _deferrable(self, x, names, pairs):
         """The heads of ``self.defer`` this plan leaves to the decode (all of them or none): up to three
-        heads of 2 .. 34 outputs each and one hidden width, ``len(late) * hidden <= 768`` (what the cells
-        kernel holds), on a feature map of whole 32-channel groups, all present, and something left for the
-        dense launch."""
+        heads of 2 .. 34 outputs each and one hidden width, ``len(late) * hidden <= 768`` (what one launch
+        of the cells kernel holds in one group) -- or, evaluated in groups (``_one_group``), up to five heads
+        of 1 .. 34 outputs and one hidden width <= 256 (ddd's set) -- on a feature map of whole 32-channel
+        groups, all present, and something left for the dense launch."""
         late = [n for n in self.defer if n in names]
-        if not late or len(late) != len(self.defer) or len(late) > 3 or len(late) >= len(names) or x.C % 32:
-            return []
-        if any(not 2 <= pairs[n][1].weight.shape[0] <= 34 for n in late):
+        if not late or len(late) != len(self.defer) or len(late) >= len(names) or x.C % 32:
             return []
         hidden = [pairs[n][0].weight.shape[0] for n in late]
-        if any(h != hidden[0] for h in hidden) or len(late) * hidden[0] > 768:
+        if any(h != hidden[0] for h in hidden):
+            return []
+        if self._one_group(late, pairs):
+            return late
+        if len(late) > native.CELL_GROUPS_MAX or hidden[0] > 256:
+            return []
+        if any(not 1 <= pairs[n][1].weight.shape[0] <= 34 for n in late):
             return []
         return late
+
+    @staticmethod
+    def _one_group(late, pairs):
+        """The head sets one packed buffer holds (those of ctdet and multi_pose)."""
+        return (len(late) <= 3 and len(late) * pairs[late[0]][0].weight.shape[0] <= 768 and
+                all(2 <= pairs[n][1].weight.shape[0] <= 34 for n in late))
 
     def _cell_heads(self, x, late, pairs):
         """DeferredHeads of the heads ``late`` on the feature map ``x``; the packed weights live in the
@@ -989,6 +1036,21 @@ class PlanBuilder:
         firsts, lasts = [pairs[n][0] for n in late], [pairs[n][1] for n in late]
         sources = [c.weight for c in firsts + lasts] + [c.bias for c in firsts + lasts if c.bias is not None]
         cacheable = all(isinstance(t, torch.nn.Parameter) for t in sources)
+        if not self._one_group(late, pairs):
+            # packed per group of consecutive heads, under a key of its own (the grouping is part of it)
+            sizes = cell_head_group_sizes(len(late), firsts[0].weight.shape[0])
+            key = self._wkey("cell_head_groups/" + ".".join(map(str, sizes)), sources) if cacheable else None
+            hit = self.wcache.get(key) if cacheable else None
+            if hit is None:
+                ev = torch.cuda.Event()
+                hit = (pack_cell_head_groups(firsts, lasts, self.device, sizes), ev)
+                ev.record()
+                if cacheable:
+                    self._wput(key, hit)
+            self.keep += [t for g in hit[0] for t in g[:4]]
+            self._pack_events.append(hit[1])
+            return DeferredHeads(late, x, firsts[0].weight.shape[0], couts=[c.weight.shape[0] for c in lasts],
+                                 groups=hit[0])
         key = self._wkey("cell_heads", sources) if cacheable else None
         hit = self.wcache.get(key) if cacheable else None
         if hit is None:

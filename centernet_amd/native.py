@@ -64,6 +64,17 @@ class HeadOut(ctypes.Structure):
                 ("w_frag", ctypes.c_void_p)]
 
 
+class CellHeadGroup(ctypes.Structure):
+    """Mirror of ``cn_cell_head_group`` (include/centernet_amd.h): one group of consecutive heads of
+    ``cn_ddd_heads_at_cells_f32``."""
+    _fields_ = [("w1_packed", ctypes.c_void_p), ("bias1", ctypes.c_void_p), ("w2", ctypes.c_void_p),
+                ("bias2", ctypes.c_void_p), ("n_heads", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+CELL_GROUP_MAX_HEADS = 3    # heads of one cn_cell_head_group
+CELL_GROUPS_MAX = 5         # groups of one cn_ddd_heads_at_cells_f32 call
+
+
 def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     args = ["make", "-C", CSRC, "-j8"]
@@ -244,6 +255,9 @@ def _declare(lib):
     lib.cn_multi_pose_heads_at_cells_f32.restype = i
     lib.cn_multi_pose_heads_at_cells_f32.argtypes = [vp, i, i, i, i, i, i, ctypes.c_float, vp, vp, vp, i, vp, vp,
                                                      i, i, i, vp, vp, vp, vp, vp]
+    lib.cn_ddd_heads_at_cells_f32.restype = i
+    lib.cn_ddd_heads_at_cells_f32.argtypes = [vp, i, i, i, i, i, i, ctypes.c_float, vp, vp, vp, i, i, i,
+                                              ctypes.POINTER(CellHeadGroup), i, i, i, vp, vp, vp]
     lib.cn_gather_feat_f32.restype = i
     lib.cn_gather_feat_f32.argtypes = [vp, vp, vp] + [i] * 5 + [vp]
     lib.cn_ddd_decode_workspace_bytes.restype = sz

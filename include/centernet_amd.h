@@ -797,6 +797,38 @@ int cn_multi_pose_heads_at_cells_f32(const void *feat, int B, int H, int W, int 
                                      int hidden, int n_heads, int J, const float *w2, const float *bias2,
                                      float *dets, float *head_vals, void *stream);
 
+/* The same launch for the ddd task: ddd_decode gathers `dep`, `rot`, `dim`, `wh` and `reg` at the K centres only
+ * (decode.py:426-462), so a caller that does not need those dense maps runs the fused heads for `hm` alone,
+ * cn_topk_f32 on it and then this ONE launch, which evaluates the deferred heads at the B x K cells and writes the
+ * rows of cn_ddd_decode_f32:
+ *   dets (B, K, 18) = [xs, ys, score, rot x8, depth, dim x3, wh x2, cls], (B, K, 16) without wh;
+ *   xs = xi + reg_x (xi + 0.5 without reg); rot, dim, wh copied; depth copied, or with CN_DECODE_DDD_RAW_DEPTH in
+ *   `flags` 1 / (sigmoid(dep) + 1e-6) - 1 -- the same bits as cn_ddd_decode_f32 with that flag on these values.
+ * The heads are, in this order, dep (1 output), rot (8), dim (3)[, wh (2) if has_wh][, reg (2) if has_reg], all with
+ * `hidden` (64, 128, 192 or 256) hidden channels.  They are evaluated in `n_groups` (1 .. 5) groups of consecutive
+ * heads, one workgroup per (image, 16 cells, group): group g takes the next groups[g].n_heads (1 .. 3,
+ * n_heads * hidden <= 768) heads of the list, and the groups together take every head once.  Each group has its
+ * own weights, laid out as for cn_ctdet_heads_at_cells_f32: w1_packed = cn_pack_cell_heads_w1 of the group's
+ * first convolutions concatenated along Cout, bias1 (n_heads * hidden), w2 (sum of the group's outputs, hidden),
+ * bias2 (sum of the group's outputs) or NULL.  Every column of a row depends on one head, so the result does
+ * not depend on the grouping and is the same from run to run.
+ * Feature, dtype, alignment and `inds` rules are those of cn_ctdet_heads_at_cells_f32 (a cell outside the map gives
+ * NaN in every head-derived column and in head_vals; score and class are still written).  head_vals: optional
+ * (B, K, 12 [+ 2] [+ 2]), the raw (untransformed) head outputs in head order.  Plain fp32 FMA, no range words,
+ * nothing clamps.  Asynchronous on `stream`, no workspace, no allocation, capturable. */
+typedef struct cn_cell_head_group {
+    const float *w1_packed;
+    const float *bias1;
+    const float *w2;
+    const float *bias2;
+    int n_heads;
+    int reserved;
+} cn_cell_head_group;
+int cn_ddd_heads_at_cells_f32(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype,
+                              float feat_mul, const float *scores, const int32_t *inds, const int32_t *clses,
+                              int K, int hidden, int n_groups, const cn_cell_head_group *groups, int has_wh,
+                              int has_reg, int flags, float *dets, float *head_vals, void *stream);
+
 /* _transpose_and_gather_feat (models/utils.py:12-26): out[b,k,c] = feat[b,c,inds[b,k]] for an
  * NCHW map, without the reference's full-tensor permute().contiguous(). */
 int cn_gather_feat_f32(const float *feat, const int32_t *inds, float *out, int B, int C, int H,
