@@ -415,6 +415,31 @@ void ha_launch(const HeadsAtArgs &a, int N, dim3 grid, bool s, hipStream_t st)
 #undef HA_LAUNCH
 }
 
+// What the single-buffer entries (ctdet, pose) and the grouped one (ddd) share: the argument checks, in the order
+// the error classes are reported -- null, shape, dtype, hidden width and the task's head / group limits, Cin and
+// pitch, H * W and B, alignment -- and the HeadsAtArgs fields every task reads.  The task's own part of a class
+// comes in as a flag (`ptrs`: its pointers are there, `counts`: its counts are positive) or, where it may only be
+// looked at once the classes in front of it have passed, as a callable: `limits()` returns CN_OK or the task's
+// error, `w1_aligned()` whether its packed first layers are 16-byte aligned.
+template <class Limits, class Aligned>
+int ha_prepare(HeadsAtArgs &a, const void *feat, int B, int H, int W, int Cin, int pitch, int dtype, float feat_mul,
+               const float *scores, const int32_t *inds, const int32_t *clses, int K, int hidden, int n_heads,
+               float *dets, float *head_vals, bool ptrs, bool counts, Limits limits, Aligned w1_aligned)
+{
+    if (!feat || !scores || !inds || !clses || !dets || !ptrs) return CN_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || K <= 0 || pitch < Cin || !counts) return CN_ERR_SHAPE;
+    if (dtype != CN_DTYPE_F32S && dtype != CN_DTYPE_F32) return CN_ERR_UNSUPPORTED;
+    if (hidden < 64 || hidden > 256 || (hidden & 63)) return CN_ERR_UNSUPPORTED;
+    if (const int rc = limits()) return rc;
+    if ((Cin & 31) || (pitch & 3) || (dtype == CN_DTYPE_F32S && (pitch & 31))) return CN_ERR_UNSUPPORTED;
+    if ((long)H * W >= (1L << 31) || B > 65535) return CN_ERR_UNSUPPORTED;
+    if (!cn_aligned16(feat) || !w1_aligned()) return CN_ERR_ALIGN;
+    a.feat = (const char *)feat; a.scores = scores; a.inds = inds; a.clses = clses;
+    a.dets = dets; a.vals = head_vals; a.mul = dtype == CN_DTYPE_F32S ? feat_mul : 1.f;
+    a.H = H; a.W = W; a.Cin = Cin; a.pitch = pitch; a.K = K; a.hidden = hidden; a.n_heads = n_heads;
+    return CN_OK;
+}
+
 // the checks and the launch of the ctdet and pose entries
 template <int TASK>
 int heads_at_cells(const void *feat, int B, int H, int W, int Cin, int pitch, int dtype, float feat_mul,
@@ -422,20 +447,18 @@ int heads_at_cells(const void *feat, int B, int H, int W, int Cin, int pitch, in
                    const float *w1_packed, const float *bias1, int hidden, int n_heads, int J, const float *w2,
                    const float *bias2, float *dets, float *head_vals, void *stream)
 {
-    if (!feat || !scores || !inds || !clses || !w1_packed || !bias1 || !w2 || !dets) return CN_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || K <= 0 || pitch < Cin) return CN_ERR_SHAPE;
-    if (dtype != CN_DTYPE_F32S && dtype != CN_DTYPE_F32) return CN_ERR_UNSUPPORTED;
     constexpr int H0 = TASK == HA_POSE ? 2 : 1;     // ctdet: wh[, reg]; pose: wh, hps[, reg]
-    if (n_heads < H0 || n_heads > H0 + 1 || hidden < 64 || hidden > 256 || (hidden & 63)) return CN_ERR_UNSUPPORTED;
-    if (TASK == HA_POSE && (J < 1 || J > HA_MAXJ)) return CN_ERR_UNSUPPORTED;
-    if ((Cin & 31) || (pitch & 3) || (dtype == CN_DTYPE_F32S && (pitch & 31))) return CN_ERR_UNSUPPORTED;
-    if ((long)H * W >= (1L << 31) || B > 65535) return CN_ERR_UNSUPPORTED;
-    if (!cn_aligned16(feat) || !cn_aligned16(w1_packed)) return CN_ERR_ALIGN;
     HeadsAtArgs a;
-    a.feat = (const char *)feat; a.scores = scores; a.inds = inds; a.clses = clses;
+    const int rc = ha_prepare(
+        a, feat, B, H, W, Cin, pitch, dtype, feat_mul, scores, inds, clses, K, hidden, n_heads, dets, head_vals,
+        w1_packed && bias1 && w2, true,
+        [&] {
+            if (n_heads < H0 || n_heads > H0 + 1) return CN_ERR_UNSUPPORTED;
+            return TASK == HA_POSE && (J < 1 || J > HA_MAXJ) ? CN_ERR_UNSUPPORTED : CN_OK;
+        },
+        [&] { return cn_aligned16(w1_packed); });
+    if (rc) return rc;
     a.w1 = (const cn_f32x4 *)w1_packed; a.b1 = bias1; a.w2 = w2; a.b2 = bias2;
-    a.dets = dets; a.vals = head_vals; a.mul = dtype == CN_DTYPE_F32S ? feat_mul : 1.f;
-    a.H = H; a.W = W; a.Cin = Cin; a.pitch = pitch; a.K = K; a.hidden = hidden; a.n_heads = n_heads;
     a.N = hidden * n_heads;
     a.J = J;
     a.c0 = 2;
@@ -476,33 +499,35 @@ extern "C" int cn_ddd_heads_at_cells_f32(const void *feat, int B, int H, int W, 
                                          const cn_cell_head_group *groups, int has_wh, int has_reg, int flags,
                                          float *dets, float *head_vals, void *stream)
 {
-    if (!feat || !scores || !inds || !clses || !groups || !dets) return CN_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || K <= 0 || pitch < Cin || n_groups <= 0) return CN_ERR_SHAPE;
-    if (dtype != CN_DTYPE_F32S && dtype != CN_DTYPE_F32) return CN_ERR_UNSUPPORTED;
-    if (hidden < 64 || hidden > 256 || (hidden & 63) || n_groups > HA_MAXGROUPS) return CN_ERR_UNSUPPORTED;
     const int n_heads = 3 + (has_wh ? 1 : 0) + (has_reg ? 1 : 0);
-    int total = 0, widest = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        const int n = groups[g].n_heads;
-        if (n < 1 || n > HA_GROUP_HEADS || n * hidden > HA_MAXN) return CN_ERR_UNSUPPORTED;
-        total += n;
-        widest = n > widest ? n : widest;
-    }
-    if (total != n_heads) return CN_ERR_UNSUPPORTED;
-    for (int g = 0; g < n_groups; ++g)
-        if (!groups[g].w1_packed || !groups[g].bias1 || !groups[g].w2) return CN_ERR_NULL;
-    if ((Cin & 31) || (pitch & 3) || (dtype == CN_DTYPE_F32S && (pitch & 31))) return CN_ERR_UNSUPPORTED;
-    if ((long)H * W >= (1L << 31) || B > 65535) return CN_ERR_UNSUPPORTED;
-    if (!cn_aligned16(feat)) return CN_ERR_ALIGN;
-    for (int g = 0; g < n_groups; ++g)
-        if (!cn_aligned16(groups[g].w1_packed)) return CN_ERR_ALIGN;
+    int widest = 0;
+    HeadsAtArgs a = {};
+    const int rc = ha_prepare(
+        a, feat, B, H, W, Cin, pitch, dtype, feat_mul, scores, inds, clses, K, hidden, n_heads, dets, head_vals,
+        groups != nullptr, n_groups > 0,
+        [&] {
+            if (n_groups > HA_MAXGROUPS) return CN_ERR_UNSUPPORTED;
+            int total = 0;
+            for (int g = 0; g < n_groups; ++g) {
+                const int n = groups[g].n_heads;
+                if (n < 1 || n > HA_GROUP_HEADS || n * hidden > HA_MAXN) return CN_ERR_UNSUPPORTED;
+                total += n;
+                widest = n > widest ? n : widest;
+            }
+            if (total != n_heads) return CN_ERR_UNSUPPORTED;
+            for (int g = 0; g < n_groups; ++g)
+                if (!groups[g].w1_packed || !groups[g].bias1 || !groups[g].w2) return CN_ERR_NULL;
+            return CN_OK;
+        },
+        [&] {
+            for (int g = 0; g < n_groups; ++g)
+                if (!cn_aligned16(groups[g].w1_packed)) return false;
+            return true;
+        });
+    if (rc) return rc;
     // the heads in their order: dep, rot, dim[, wh][, reg] -- outputs and first column in a row of dets
     const int couts[5] = {1, 8, 3, 2, 2};
     const int cols[5] = {11, 3, 12, has_wh ? 15 : 0, 0};
-    HeadsAtArgs a = {};
-    a.feat = (const char *)feat; a.scores = scores; a.inds = inds; a.clses = clses;
-    a.dets = dets; a.vals = head_vals; a.mul = dtype == CN_DTYPE_F32S ? feat_mul : 1.f;
-    a.H = H; a.W = W; a.Cin = Cin; a.pitch = pitch; a.K = K; a.hidden = hidden; a.n_heads = n_heads;
     a.D = has_wh ? 18 : 16;
     a.raw_depth = (flags & CN_DECODE_DDD_RAW_DEPTH) ? 1 : 0;
     a.half_group = has_reg ? -1 : 0;

@@ -113,6 +113,62 @@ def ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100, apply_sigmoid=Fal
     return (dets, inds.long()) if return_inds else dets
 
 
+def _topk_f32(lib, heat, B, C, H, W, K, flags, ws, stream):
+    """``cn_topk_f32`` into fresh (B, K) buffers -> (scores, inds, clses, return code)."""
+    scores = torch.empty((B, K), device=heat.device, dtype=torch.float32)
+    inds = torch.empty((B, K), device=heat.device, dtype=torch.int32)
+    clses = torch.empty((B, K), device=heat.device, dtype=torch.int32)
+    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, flags, native.ptr(scores), native.ptr(inds),
+                         native.ptr(clses), native.ptr(ws), ws.numel(), stream)
+    return scores, inds, clses, rc
+
+
+def _cells_topk(heat, late, K, apply_sigmoid, maps=()):
+    """What the ``*_decode_at_cells`` functions share in front of their heads call, behind their own check of
+    the head set: the heat-map and the feature map of ``late`` (an ``engine.DeferredHeads``) must fit each
+    other, further dense ``maps`` ((name, tensor or None, channels), ...) the heat-map, and K the map; then the
+    image-level top-K with the peak test, ONE launch on an owned workspace (``_own_workspace``).
+    Returns (heat, B, C, H, W, scores, inds, clses, stream)."""
+    (heat,) = _prep(heat)
+    lib = native.lib()
+    if heat.dim() != 4:
+        raise RuntimeError("heat must be (B, C, H, W)")
+    B, C, H, W = heat.shape
+    f, dev = late.feat, heat.device
+    if (f.B, f.H, f.W) != (B, H, W) or f.nchw or f.fmt not in ("f32s", "f32") or f.t.device != dev:
+        raise RuntimeError("the deferred heads' feature map must be an NHWC fp32 / f32s (%d, %d, %d, .) "
+                           "activation on the heat-map's device" % (B, H, W))
+    for name, t, channels in maps:
+        _expect(name, t, B, channels, H, W, dev)
+    if K > H * W:
+        raise RuntimeError("selected index k out of range")
+    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
+    st = native.stream_ptr()
+    scores, inds, clses, rc = _topk_f32(lib, heat, B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN, ws, st)
+    if rc:
+        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
+    native.check(rc, "cn_topk_f32")
+    return heat, B, C, H, W, scores, inds, clses, st
+
+
+def _feat_args(f):
+    """The feature ``Act`` as the ``*_heads_at_cells_f32`` entries take it: (pointer, B, H, W, C, pitch,
+    dtype, 2^exponent)."""
+    s = f.fmt == "f32s"
+    return (f.ptr(), f.B, f.H, f.W, f.C, f.pitch, native.DTYPE_F32S if s else native.DTYPE_F32,
+            float(2.0 ** f.exp) if s else 1.0)
+
+
+def _cells_result(dets, inds, vals, return_inds, return_vals):
+    """``dets``, or the tuple (dets[, inds as int64][, head values]) the caller asked for."""
+    out = (dets,)
+    if return_inds:
+        out += (inds.long(),)
+    if return_vals:
+        out += (vals,)
+    return out if len(out) > 1 else dets
+
+
 def ctdet_decode_at_cells(heat, late, K=100, apply_sigmoid=False, return_inds=False, return_vals=False):
     """``ctdet_decode`` without dense ``wh`` / ``reg`` maps: ``late`` is the ``engine.DeferredHeads`` of a
     deferred-heads plan (heads ``('wh',)`` or ``('wh', 'reg')``).  Two launches on the current stream: the
@@ -120,46 +176,18 @@ def ctdet_decode_at_cells(heat, late, K=100, apply_sigmoid=False, return_inds=Fa
     ``ctdet_decode``, bit for bit) and ``cn_ctdet_heads_at_cells_f32``, which evaluates the heads at
     those cells in plain fp32 and assembles the (B, K, 6) rows.  ``return_vals``: also the raw head
     values (B, K, 2 * heads)."""
-    (heat,) = _prep(heat)
-    lib = native.lib()
-    if heat.dim() != 4:
-        raise RuntimeError("heat must be (B, C, H, W)")
-    B, C, H, W = heat.shape
-    f = late.feat
     if late.names not in (("wh",), ("wh", "reg")):
         raise RuntimeError("ctdet_decode_at_cells takes the heads ('wh',) or ('wh', 'reg'), got %r" % (late.names,))
-    if (f.B, f.H, f.W) != (B, H, W) or f.nchw or f.fmt not in ("f32s", "f32") or f.t.device != heat.device:
-        raise RuntimeError("the deferred heads' feature map must be an NHWC fp32 / f32s (%d, %d, %d, .) "
-                           "activation on the heat-map's device" % (B, H, W))
-    if K > H * W:
-        raise RuntimeError("selected index k out of range")
-    dev = heat.device
-    scores = torch.empty((B, K), device=dev, dtype=torch.float32)
-    inds = torch.empty((B, K), device=dev, dtype=torch.int32)
-    clses = torch.empty((B, K), device=dev, dtype=torch.int32)
-    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
-    st = native.stream_ptr()
-    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN,
-                         native.ptr(scores), native.ptr(inds), native.ptr(clses), native.ptr(ws), ws.numel(), st)
-    if rc:
-        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
-    native.check(rc, "cn_topk_f32")
+    heat, B, C, H, W, scores, inds, clses, st = _cells_topk(heat, late, K, apply_sigmoid)
     nh = len(late.names)
-    dets = torch.empty((B, K, 6), device=dev, dtype=torch.float32)
-    vals = torch.empty((B, K, 2 * nh), device=dev, dtype=torch.float32) if return_vals else None
-    s = f.fmt == "f32s"
-    rc = lib.cn_ctdet_heads_at_cells_f32(
-        f.ptr(), B, H, W, f.C, f.pitch, native.DTYPE_F32S if s else native.DTYPE_F32,
-        float(2.0 ** f.exp) if s else 1.0, native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
+    dets = torch.empty((B, K, 6), device=heat.device, dtype=torch.float32)
+    vals = torch.empty((B, K, 2 * nh), device=heat.device, dtype=torch.float32) if return_vals else None
+    rc = native.lib().cn_ctdet_heads_at_cells_f32(
+        *_feat_args(late.feat), native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
         native.ptr(late.w1), native.ptr(late.b1), late.hidden, nh, native.ptr(late.w2), native.ptr(late.b2),
         native.ptr(dets), native.ptr(vals), st)
     native.check(rc, "cn_ctdet_heads_at_cells_f32")
-    out = (dets,)
-    if return_inds:
-        out += (inds.long(),)
-    if return_vals:
-        out += (vals,)
-    return out if len(out) > 1 else dets
+    return _cells_result(dets, inds, vals, return_inds, return_vals)
 
 
 def multi_pose_decode_at_cells(heat, late, hm_hp=None, hp_offset=None, K=100, apply_sigmoid=False,
@@ -172,12 +200,6 @@ def multi_pose_decode_at_cells(heat, late, hm_hp=None, hp_offset=None, K=100, ap
     candidates and the match of ``multi_pose_decode`` on the dense ``hm_hp`` / ``hp_offset``.
     ``apply_sigmoid``: ``heat`` and ``hm_hp`` hold logits.  ``return_vals``: also the raw head values
     (B, K, 2 + 2J [+ 2]) in head order."""
-    heat, hm_hp, hp_offset = _prep(heat, hm_hp, hp_offset)
-    lib = native.lib()
-    if heat.dim() != 4:
-        raise RuntimeError("heat must be (B, C, H, W)")
-    B, C, H, W = heat.shape
-    f = late.feat
     if late.names not in (("wh", "hps"), ("wh", "hps", "reg")):
         raise RuntimeError("multi_pose_decode_at_cells takes the heads ('wh', 'hps') or ('wh', 'hps', 'reg'), "
                            "got %r" % (late.names,))
@@ -185,33 +207,16 @@ def multi_pose_decode_at_cells(heat, late, hm_hp=None, hp_offset=None, K=100, ap
     if couts[0] != 2 or couts[1] % 2 or not 2 <= couts[1] <= 34 or couts[2:] not in ((), (2,)):
         raise RuntimeError("multi_pose_decode_at_cells: head outputs %r are not (2, 2J[, 2])" % (couts,))
     J = couts[1] // 2
-    if (f.B, f.H, f.W) != (B, H, W) or f.nchw or f.fmt not in ("f32s", "f32") or f.t.device != heat.device:
-        raise RuntimeError("the deferred heads' feature map must be an NHWC fp32 / f32s (%d, %d, %d, .) "
-                           "activation on the heat-map's device" % (B, H, W))
-    dev = heat.device
-    _expect("hm_hp", hm_hp, B, J, H, W, dev)
-    _expect("hp_offset", hp_offset, B, 2, H, W, dev)
-    if K > H * W:
-        raise RuntimeError("selected index k out of range")
-    scores = torch.empty((B, K), device=dev, dtype=torch.float32)
-    inds = torch.empty((B, K), device=dev, dtype=torch.int32)
-    clses = torch.empty((B, K), device=dev, dtype=torch.int32)
-    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
-    st = native.stream_ptr()
-    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN,
-                         native.ptr(scores), native.ptr(inds), native.ptr(clses), native.ptr(ws), ws.numel(), st)
-    if rc:
-        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
-    native.check(rc, "cn_topk_f32")
-    nh, nout = len(late.names), sum(couts)
+    hm_hp, hp_offset = _prep(hm_hp, hp_offset)
+    heat, B, C, H, W, scores, inds, clses, st = _cells_topk(
+        heat, late, K, apply_sigmoid, maps=(("hm_hp", hm_hp, J), ("hp_offset", hp_offset, 2)))
+    lib, dev = native.lib(), heat.device
     dets = torch.empty((B, K, 5 + 2 * J + 1), device=dev, dtype=torch.float32)
-    vals = torch.empty((B, K, nout), device=dev, dtype=torch.float32) if return_vals else None
-    s = f.fmt == "f32s"
+    vals = torch.empty((B, K, sum(couts)), device=dev, dtype=torch.float32) if return_vals else None
     rc = lib.cn_multi_pose_heads_at_cells_f32(
-        f.ptr(), B, H, W, f.C, f.pitch, native.DTYPE_F32S if s else native.DTYPE_F32,
-        float(2.0 ** f.exp) if s else 1.0, native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
-        native.ptr(late.w1), native.ptr(late.b1), late.hidden, nh, J, native.ptr(late.w2), native.ptr(late.b2),
-        native.ptr(dets), native.ptr(vals), st)
+        *_feat_args(late.feat), native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
+        native.ptr(late.w1), native.ptr(late.b1), late.hidden, len(late.names), J, native.ptr(late.w2),
+        native.ptr(late.b2), native.ptr(dets), native.ptr(vals), st)
     native.check(rc, "cn_multi_pose_heads_at_cells_f32")
     if hm_hp is not None:
         mws = _workspace(lib.cn_multi_pose_decode_workspace_bytes(B, 1, H, W, J, K), dev)
@@ -219,12 +224,7 @@ def multi_pose_decode_at_cells(heat, late, hm_hp=None, hp_offset=None, K=100, ap
                                          int(bool(apply_sigmoid)), native.ptr(dets), native.ptr(mws),
                                          mws.numel(), st)
         native.check(rc, "cn_multi_pose_match_f32")
-    out = (dets,)
-    if return_inds:
-        out += (inds.long(),)
-    if return_vals:
-        out += (vals,)
-    return out if len(out) > 1 else dets
+    return _cells_result(dets, inds, vals, return_inds, return_vals)
 
 
 _NO_PEAK_TEST = 512   # flag bit of the decode entry points: rank every cell (plain topk)
@@ -291,13 +291,8 @@ def _topk(scores, K=40, apply_sigmoid=False, nms=False):
     if K > H * W:
         raise RuntimeError("selected index k out of range")
     flags = int(bool(apply_sigmoid)) | (0 if nms else _NO_PEAK_TEST)
-    s = torch.empty((B, K), device=scores.device, dtype=torch.float32)
-    i = torch.empty((B, K), device=scores.device, dtype=torch.int32)
-    c = torch.empty((B, K), device=scores.device, dtype=torch.int32)
     ws = _workspace(lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), scores.device)
-    rc = lib.cn_topk_f32(native.ptr(scores), B, C, H, W, K, flags, native.ptr(s),
-                         native.ptr(i), native.ptr(c), native.ptr(ws), ws.numel(),
-                         native.stream_ptr())
+    s, i, c, rc = _topk_f32(lib, scores, B, C, H, W, K, flags, ws, native.stream_ptr())
     native.check(rc, "cn_topk_f32")
     i = i.long()
     return s, i, c.int(), (i // W).float(), (i % W).float()
@@ -357,49 +352,21 @@ def ddd_decode_at_cells(heat, late, K=40, apply_sigmoid=False, raw_depth=False, 
     (B, K, 18) rows -- (B, K, 16) without ``wh``.  ``raw_depth``: column 11 is 1 / (sigmoid(dep) + 1e-6) - 1 as
     ``ddd_decode(raw_depth=True)`` computes it, else the head's value.  ``return_vals``: also the raw head
     values (B, K, 12 [+ 2] [+ 2]) in head order."""
-    (heat,) = _prep(heat)
-    lib = native.lib()
-    if heat.dim() != 4:
-        raise RuntimeError("heat must be (B, C, H, W)")
-    B, C, H, W = heat.shape
-    f = late.feat
     names, couts = tuple(late.names), tuple(late.couts)
     has_wh, has_reg = "wh" in names, "reg" in names
     want = [hc for hc in _DDD_HEADS if hc[0] not in ("wh", "reg") or (has_wh if hc[0] == "wh" else has_reg)]
-    if names != tuple(n for n, _ in want) or couts != tuple(c for _, c in want) or late.groups is None:
+    if names != tuple(n for n, _ in want) or couts != tuple(c for _, c in want):
         raise RuntimeError("ddd_decode_at_cells takes the heads ('dep', 'rot', 'dim'[, 'wh'][, 'reg']) with "
                            "(1, 8, 3[, 2][, 2]) outputs, packed per group; got %r with %r" % (names, couts))
-    if (f.B, f.H, f.W) != (B, H, W) or f.nchw or f.fmt not in ("f32s", "f32") or f.t.device != heat.device:
-        raise RuntimeError("the deferred heads' feature map must be an NHWC fp32 / f32s (%d, %d, %d, .) "
-                           "activation on the heat-map's device" % (B, H, W))
-    if K > H * W:
-        raise RuntimeError("selected index k out of range")
-    dev = heat.device
-    scores = torch.empty((B, K), device=dev, dtype=torch.float32)
-    inds = torch.empty((B, K), device=dev, dtype=torch.int32)
-    clses = torch.empty((B, K), device=dev, dtype=torch.int32)
-    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
-    st = native.stream_ptr()
-    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN,
-                         native.ptr(scores), native.ptr(inds), native.ptr(clses), native.ptr(ws), ws.numel(), st)
-    if rc:
-        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
-    native.check(rc, "cn_topk_f32")
-    dets = torch.empty((B, K, 18 if has_wh else 16), device=dev, dtype=torch.float32)
-    vals = torch.empty((B, K, sum(couts)), device=dev, dtype=torch.float32) if return_vals else None
-    s = f.fmt == "f32s"
-    rc = lib.cn_ddd_heads_at_cells_f32(
-        f.ptr(), B, H, W, f.C, f.pitch, native.DTYPE_F32S if s else native.DTYPE_F32,
-        float(2.0 ** f.exp) if s else 1.0, native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
+    heat, B, C, H, W, scores, inds, clses, st = _cells_topk(heat, late, K, apply_sigmoid)
+    dets = torch.empty((B, K, 18 if has_wh else 16), device=heat.device, dtype=torch.float32)
+    vals = torch.empty((B, K, sum(couts)), device=heat.device, dtype=torch.float32) if return_vals else None
+    rc = native.lib().cn_ddd_heads_at_cells_f32(
+        *_feat_args(late.feat), native.ptr(scores), native.ptr(inds), native.ptr(clses), K,
         late.hidden, len(late.groups), late.group_table(), int(has_wh), int(has_reg),
         native.DECODE_DDD_RAW_DEPTH if raw_depth else 0, native.ptr(dets), native.ptr(vals), st)
     native.check(rc, "cn_ddd_heads_at_cells_f32")
-    out = (dets,)
-    if return_inds:
-        out += (inds.long(),)
-    if return_vals:
-        out += (vals,)
-    return out if len(out) > 1 else dets
+    return _cells_result(dets, inds, vals, return_inds, return_vals)
 
 
 def agnex_ct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr=None, l_regr=None, b_regr=None,

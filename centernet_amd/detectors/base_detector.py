@@ -68,6 +68,7 @@ class BaseDetector(object):
         self.max_per_image = 100
         self.pause = True
         self.tail_fallbacks = 0      # batches of the frame pipe that its device tail handed back to the host
+        self.model.defer_heads(self._deferred_heads())
 
     # ------------------------------------------------------------------ input geometry
     def input_geometry(self, height, width, scale):
@@ -426,6 +427,57 @@ class BaseDetector(object):
         while pending:
             j, fr = pending.popleft()
             yield pipe.collect(j, fr, arrays)
+
+    # ------------------------------------------------------------------ run_batch: deferred heads
+    def _deferred_heads(self):
+        """Task hook: the heads ``run_batch`` leaves to the decode, which evaluates them at the K decoded
+        centres only (a task's ``deferred_*_heads(opt)``); the network side (fp32 compute mode, fusable
+        3x3 + 1x1 heads) is the plan builder's decision.  Nothing by default."""
+        return ()
+
+    def _sync_deferral(self):
+        """Keep the module's mode in step with the options (one may have changed after construction): the
+        frame pipe reads the range words of ``plan_for(...)``, which must be the plan that ran."""
+        names = self._deferred_heads()
+        if names != self.model.deferral():
+            self.model.defer_heads(names)
+
+    def _forward_deferred(self, images, probe=None):
+        """The network of ``run_batch``: the deferred-heads plan where it applies, else the dense one.
+        ``probe``: see ``run_batch``; its ``net_events`` are filled here."""
+        self._sync_deferral()
+        if probe is None:
+            return self.model(images, borrow=True, deferred=True)[-1]
+        probe['net_events'] = []
+        return self.model(images, borrow=True, deferred=True, events=probe['net_events'],
+                          event_after=probe.get('event_after'))[-1]
+
+    def _decode_batch(self, out):
+        """Task hook: decode of ``_forward_deferred``'s output -- at the cells where the plan deferred heads
+        (``out['_deferred']``), else the dense decode; the maps are logits, the sigmoids are in the kernels."""
+        raise NotImplementedError
+
+    def run_batch(self, images, probe=None):
+        """``images`` (B,3,H,W) fp32, already normalised, on the device -> the task's raw (B,K,.)
+        detections in output-grid units (device tensor).  Asynchronous: nothing here waits for
+        the device, so the f32s range words of the forward are NOT looked at yet -- call
+        ``range_ok()`` where the results are consumed (``run_frames`` does; a pipeline checks
+        once per synchronisation point, the words accumulate over the forwards in between).
+        ``probe``: optional dict for measurement (bench.py): ``event_after`` (set of launch
+        indices) in, ``net_events`` (HIP events at those launch boundaries) and ``dec_events``
+        (before / after the decode) out."""
+        self._note_unchecked_forward()
+        with torch.no_grad():
+            out = self._forward_deferred(images, probe)
+            if probe is None:
+                return self._decode_batch(out)
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dets = self._decode_batch(out)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            probe['dec_events'] = (e0, e1)
+            return dets
 
     UNCHECKED_LIMIT = 4096     # run_batch forwards without a look at the range words before a warning
 

@@ -15,37 +15,23 @@ from ..utils import flip_average, flip_average_batch
 from .base_detector import BaseDetector
 
 
+def deferred_ctdet_heads(opt):
+    """The heads ``run_batch`` leaves to the decode: ``wh`` (and ``reg``) are only gathered at the K
+    decoded centres (decode.py:472-486), so their dense maps are not computed.  Not with flip-test
+    (the averaged maps are needed), ``cat_spec_wh`` (2 x classes outputs) or K > 128; the network
+    side (fp32 compute mode, fusable 3x3 + 1x1 heads) is the plan builder's decision."""
+    if opt.flip_test or opt.cat_spec_wh or opt.K > 128 or 'wh' not in opt.heads:
+        return ()
+    if 'reg' in opt.heads:
+        return ('wh', 'reg') if opt.reg_offset else ()
+    return ('wh',)
+
+
 class CtdetDetector(BaseDetector):
-    def __init__(self, opt):
-        super(CtdetDetector, self).__init__(opt)
-        self.model.defer_heads(self._deferred_heads())
-
     def _deferred_heads(self):
-        """The heads ``run_batch`` leaves to the decode: ``wh`` (and ``reg``) are only gathered at the K
-        decoded centres (decode.py:472-486), so their dense maps are not computed.  Not with flip-test
-        (the averaged maps are needed), ``cat_spec_wh`` (2 x classes outputs) or K > 128; the network
-        side (fp32 compute mode, fusable 3x3 + 1x1 heads) is the plan builder's decision."""
-        opt = self.opt
-        if opt.flip_test or opt.cat_spec_wh or opt.K > 128 or 'wh' not in opt.heads:
-            return ()
-        if 'reg' in opt.heads:
-            return ('wh', 'reg') if opt.reg_offset else ()
-        return ('wh',)
-
-    def _sync_deferral(self):
-        """Keep the module's mode in step with the options (one may have changed after construction): the
-        frame pipe reads the range words of ``plan_for(...)``, which must be the plan that ran."""
-        names = self._deferred_heads()
-        if names != self.model.deferral():
-            self.model.defer_heads(names)
-
-    def _forward_batch(self, images, **kw):
-        """The network of ``run_batch``: the deferred-heads plan where it applies, else the dense one."""
-        self._sync_deferral()
-        return self.model(images, borrow=True, deferred=True, **kw)[-1]
+        return deferred_ctdet_heads(self.opt)
 
     def _decode_batch(self, out):
-        """Decode of ``_forward_batch``'s output (``hm`` stays logits: the sigmoid is in the kernel)."""
         late = out.get('_deferred')
         if late is not None:
             return ctdet_decode_at_cells(out['hm'], late, K=self.opt.K, apply_sigmoid=True)
@@ -109,30 +95,6 @@ class CtdetDetector(BaseDetector):
         return results
 
     # ------------------------------------------------------------------ new surface
-    def run_batch(self, images, probe=None):
-        """``images`` (B,3,H,W) fp32, already normalised, on the device -> raw (B,K,6)
-        detections in output-grid units (device tensor).  Asynchronous: nothing here waits for
-        the device, so the f32s range words of the forward are NOT looked at yet -- call
-        ``range_ok()`` where the results are consumed (``run_frames`` does; a pipeline checks
-        once per synchronisation point, the words accumulate over the forwards in between).
-        ``probe``: optional dict for measurement (bench.py): ``event_after`` (set of launch
-        indices) in, ``net_events`` (HIP events at those launch boundaries) and ``dec_events``
-        (before / after the decode) out."""
-        self._note_unchecked_forward()
-        with torch.no_grad():
-            if probe is None:
-                return self._decode_batch(self._forward_batch(images))
-            probe['net_events'] = []
-            out = self._forward_batch(images, events=probe['net_events'],
-                                      event_after=probe.get('event_after'))
-            e0 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-            dets = self._decode_batch(out)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            probe['dec_events'] = (e0, e1)
-            return dets
-
     def _run_scale(self, images, flip):
         """One test scale of the frame pipeline: ``run_batch``, or with ``flip`` the (2B, 3, H, W)
         frame / mirror pairs -> network -> batched flip average (``hm`` after the sigmoid, ``reg`` of

@@ -39,7 +39,6 @@ def deferred_ddd_heads(opt):
 class DddDetector(BaseDetector):
     def __init__(self, opt):
         super(DddDetector, self).__init__(opt)
-        self.model.defer_heads(deferred_ddd_heads(opt))
         self.calib = np.array([[707.0493, 0, 604.0814, 45.75831],
                                [0, 707.0493, 180.5066, -0.3454157],
                                [0, 0, 1., 0.004981016]], dtype=np.float32)     # ddd.py:25-27
@@ -108,16 +107,21 @@ class DddDetector(BaseDetector):
         return out, self._meta(c, s, calib)
 
     # ------------------------------------------------------------------ network + decode
-    def _sync_deferral(self):
-        """Keep the module's mode in step with the options (one may have changed after construction): the
-        frame pipe reads the range words of ``plan_for(...)``, which must be the plan that ran."""
-        names = deferred_ddd_heads(self.opt)
-        if names != self.model.deferral():
-            self.model.defer_heads(names)
+    def _deferred_heads(self):
+        return deferred_ddd_heads(self.opt)
 
-    def _decode_at_cells(self, o):
-        """The rows of a deferred-heads forward: top-K on ``hm``, the other heads at the K cells only."""
-        return ddd_decode_at_cells(o['hm'], o['_deferred'], K=self.opt.K, apply_sigmoid=True, raw_depth=True)
+    def _decode_batch(self, o, raw_depth=False):
+        """Raw (B, K, 18) rows of ``ddd_decode``, the centre map's sigmoid fused into the decode: from a
+        deferred-heads forward the top-K on ``hm`` and the other heads at the K cells only, the depth transform
+        of the K values in that kernel.  From dense maps ``run_batch`` transforms the depth map on the host side
+        as ``process`` does; the frame pipe (``raw_depth``) leaves the K gathered values to ``cn_ddd_decode_f32``."""
+        opt = self.opt
+        if '_deferred' in o:
+            return ddd_decode_at_cells(o['hm'], o['_deferred'], K=opt.K, apply_sigmoid=True, raw_depth=True)
+        dep = o['dep'] if raw_depth else 1. / (o['dep'].sigmoid() + 1e-6) - 1.
+        return ddd_decode(o['hm'], o['rot'], dep, o['dim'], wh=o['wh'] if opt.reg_bbox else None,
+                          reg=o['reg'] if opt.reg_offset else None, K=opt.K, apply_sigmoid=True,
+                          raw_depth=raw_depth)
 
     def process(self, images, return_time=False):
         """ddd.py:56-73: post-sigmoid centre map, depth = 1 / (sigmoid(dep) + 1e-6) - 1, then
@@ -258,16 +262,10 @@ class DddDetector(BaseDetector):
 
     def _run_scale(self, images, flip):
         """Network + decode of the frame pipeline: the centre map's sigmoid and the depth transform of
-        the K gathered cells are inside ``cn_ddd_decode_f32``; raw (B, K, 18) rows, asynchronous."""
+        the K gathered cells are inside the decode kernels; raw (B, K, 18) rows, asynchronous."""
         self._note_unchecked_forward()
         with torch.no_grad():
-            self._sync_deferral()
-            o = self.model(images, borrow=True, deferred=True)[-1]
-            if '_deferred' in o:
-                return self._decode_at_cells(o)
-            return ddd_decode(o['hm'], o['rot'], o['dep'], o['dim'], wh=o['wh'] if self.opt.reg_bbox else None,
-                              reg=o['reg'] if self.opt.reg_offset else None, K=self.opt.K,
-                              apply_sigmoid=True, raw_depth=True)
+            return self._decode_batch(self._forward_deferred(images), raw_depth=True)
 
     def _run_frames_sync(self, frames, scales, side=None):
         """One batch synchronously (the pipe's re-run path after an f32s re-calibration)."""
@@ -297,20 +295,6 @@ class DddDetector(BaseDetector):
 
     def _device_tail(self, pipe):
         return DddTail(pipe) if DddTail.admits(pipe) else None
-
-    def run_batch(self, images, probe=None):
-        """New surface (as CtdetDetector.run_batch): a device-resident, normalised batch -> raw
-        (B, K, 18) rows of ``ddd_decode``; the centre map's sigmoid is fused into the decode."""
-        self._note_unchecked_forward()
-        with torch.no_grad():
-            self._sync_deferral()
-            o = self.model(images, borrow=True, deferred=True)[-1]
-            if '_deferred' in o:
-                return self._decode_at_cells(o)
-            dep = 1. / (o['dep'].sigmoid() + 1e-6) - 1.
-            return ddd_decode(o['hm'], o['rot'], dep, o['dim'], wh=o['wh'] if self.opt.reg_bbox else None,
-                              reg=o['reg'] if self.opt.reg_offset else None, K=self.opt.K,
-                              apply_sigmoid=True)
 
 
 class DddTail(DeviceTail):

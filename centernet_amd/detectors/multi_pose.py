@@ -34,14 +34,9 @@ class MultiPoseDetector(BaseDetector):
     def __init__(self, opt):
         super(MultiPoseDetector, self).__init__(opt)
         self.flip_idx = opt.flip_idx
-        self.model.defer_heads(deferred_pose_heads(opt))
 
-    def _sync_deferral(self):
-        """Keep the module's mode in step with the options (one may have changed after construction): the
-        frame pipe reads the range words of ``plan_for(...)``, which must be the plan that ran."""
-        names = deferred_pose_heads(self.opt)
-        if names != self.model.deferral():
-            self.model.defer_heads(names)
+    def _deferred_heads(self):
+        return deferred_pose_heads(self.opt)
 
     _list_results = True
 
@@ -83,37 +78,18 @@ class MultiPoseDetector(BaseDetector):
                                      K=self.opt.K)
         return (output, dets, forward_time) if return_time else (output, dets)
 
-    def run_batch(self, images, probe=None):
-        """New surface (as CtdetDetector.run_batch): a device-resident, normalised batch ->
-        raw (B,K,40) detections in output-grid units; sigmoids fused into the decode kernels."""
-        self._note_unchecked_forward()
-        with torch.no_grad():
-            ev = None
-            if probe is not None:
-                ev = probe['net_events'] = []
-            self._sync_deferral()
-            o = self.model(images, borrow=True, deferred=True, events=ev,
-                           event_after=None if probe is None else probe.get('event_after'))[-1]
-            if probe is not None:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-            if self.opt.mse_loss and self.opt.hm_hp:
-                raise NotImplementedError("run_batch: mse_loss joint heat-maps are not logits")
-            hm_hp = o['hm_hp'] if self.opt.hm_hp else None
-            hp_offset = o['hp_offset'] if self.opt.reg_hp_offset else None
-            late = o.get('_deferred')
-            if late is not None:
-                dets = multi_pose_decode_at_cells(o['hm'], late, hm_hp=hm_hp, hp_offset=hp_offset,
-                                                  K=self.opt.K, apply_sigmoid=True)
-            else:
-                dets = multi_pose_decode(o['hm'], o['wh'], o['hps'],
-                                         reg=o['reg'] if self.opt.reg_offset else None,
-                                         hm_hp=hm_hp, hp_offset=hp_offset, K=self.opt.K, apply_sigmoid=True)
-            if probe is not None:
-                e1 = torch.cuda.Event(enable_timing=True)
-                e1.record()
-                probe['dec_events'] = (e0, e1)
-            return dets
+    def _decode_batch(self, o):
+        """``run_batch``'s decode -> raw (B,K,40) detections; sigmoids fused into the decode kernels."""
+        if self.opt.mse_loss and self.opt.hm_hp:
+            raise NotImplementedError("run_batch: mse_loss joint heat-maps are not logits")
+        hm_hp = o['hm_hp'] if self.opt.hm_hp else None
+        hp_offset = o['hp_offset'] if self.opt.reg_hp_offset else None
+        late = o.get('_deferred')
+        if late is not None:
+            return multi_pose_decode_at_cells(o['hm'], late, hm_hp=hm_hp, hp_offset=hp_offset,
+                                              K=self.opt.K, apply_sigmoid=True)
+        return multi_pose_decode(o['hm'], o['wh'], o['hps'], reg=o['reg'] if self.opt.reg_offset else None,
+                                 hm_hp=hm_hp, hp_offset=hp_offset, K=self.opt.K, apply_sigmoid=True)
 
     def _run_scale(self, images, flip):
         """One test scale of the frame pipeline: ``run_batch``, or with ``flip`` the (2B, 3, H, W)

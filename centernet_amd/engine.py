@@ -160,20 +160,37 @@ def pack_cell_head_groups(firsts, lasts, device, sizes):
 
 class DeferredHeads:
     """What a deferred-heads plan hands to the decode instead of dense maps: the feature ``Act`` the heads
-    read (pointer, pitch, format, exponent) and the packed weights of the heads ``names``
-    (``pack_cell_heads``), evaluated at the decoded cells only (``decode.ctdet_decode_at_cells``,
-    ``decode.multi_pose_decode_at_cells``).  ``couts``: the outputs per head, in order (two each when not
-    given).  ``groups``: for a head set that is packed per group of consecutive heads
-    (``pack_cell_head_groups``; ``decode.ddd_decode_at_cells``) the groups' (w1, b1, w2, b2, n_heads) --
-    ``w1`` .. ``b2`` are then None."""
-    __slots__ = ("names", "feat", "hidden", "w1", "b1", "w2", "b2", "couts", "groups", "_table")
+    read (pointer, pitch, format, exponent) and the packed weights of the heads ``names``, evaluated at the
+    decoded cells only (``decode.ctdet_decode_at_cells``, ``decode.multi_pose_decode_at_cells``,
+    ``decode.ddd_decode_at_cells``).  ``groups``: the packed buffers (``pack_cell_head_groups``), one
+    (w1, b1, w2, b2, n_heads) per group of consecutive heads -- one group for ctdet and multi_pose, whose C
+    entries take its tensors as ``w1`` .. ``b2``; ddd's entry takes ``group_table()``.  ``couts``: the outputs
+    per head, in order (two each when not given).  A single group may also be given as ``pack_cell_heads``
+    returns it, ``DeferredHeads(names, feat, hidden, w1, b1, w2, b2)``: it is stored as ``groups`` all the same."""
+    __slots__ = ("names", "feat", "hidden", "groups", "couts", "_table")
 
-    def __init__(self, names, feat, hidden, w1=None, b1=None, w2=None, b2=None, couts=None, groups=None):
+    def __init__(self, names, feat, hidden, *packed, couts=None, groups=None):
         self.names, self.feat, self.hidden = tuple(names), feat, int(hidden)
-        self.w1, self.b1, self.w2, self.b2 = w1, b1, w2, b2
+        if len(packed) == 4 and groups is None:
+            groups = (packed + (len(self.names),),)
+        elif len(packed) == 1 and groups is None:
+            groups = packed[0]
+        elif packed or groups is None:
+            raise TypeError("DeferredHeads takes groups, or the (w1, b1, w2, b2) of a single group")
+        self.groups = tuple(tuple(g) for g in groups)
         self.couts = tuple(int(c) for c in couts) if couts is not None else (2,) * len(self.names)
-        self.groups = None if groups is None else tuple(groups)
         self._table = None
+
+    def _only(self):
+        if len(self.groups) != 1:
+            raise RuntimeError("w1 .. b2 are the tensors of a single group; these heads %r are packed in %d"
+                               % (self.names, len(self.groups)))
+        return self.groups[0]
+
+    w1 = property(lambda self: self._only()[0])
+    b1 = property(lambda self: self._only()[1])
+    w2 = property(lambda self: self._only()[2])
+    b2 = property(lambda self: self._only()[3])
 
     def group_table(self):
         """The ``cn_cell_head_group`` array of ``groups`` (built once; it holds raw pointers into them)."""
@@ -1005,64 +1022,49 @@ class PlanBuilder:
         return True
 
     def _deferrable(self, x, names, pairs):
-        """The heads of ``self.defer`` this plan leaves to the decode (all of them or none): up to three
-        heads of 2 .. 34 outputs each and one hidden width, ``len(late) * hidden <= 768`` (what one launch
-        of the cells kernel holds in one group) -- or, evaluated in groups (``_one_group``), up to five heads
-        of 1 .. 34 outputs and one hidden width <= 256 (ddd's set) -- on a feature map of whole 32-channel
-        groups, all present, and something left for the dense launch."""
+        """The heads of ``self.defer`` this plan leaves to the decode (all of them or none): a set one group
+        holds (``_one_group``) -- or, evaluated in groups, up to five heads of 1 .. 34 outputs and one hidden
+        width <= 256 (ddd's set) -- on a feature map of whole 32-channel groups, all present, and something
+        left for the dense launch."""
         late = [n for n in self.defer if n in names]
         if not late or len(late) != len(self.defer) or len(late) >= len(names) or x.C % 32:
             return []
         hidden = [pairs[n][0].weight.shape[0] for n in late]
+        couts = [pairs[n][1].weight.shape[0] for n in late]
         if any(h != hidden[0] for h in hidden):
             return []
-        if self._one_group(late, pairs):
+        if self._one_group(hidden[0], couts):
             return late
-        if len(late) > native.CELL_GROUPS_MAX or hidden[0] > 256:
-            return []
-        if any(not 1 <= pairs[n][1].weight.shape[0] <= 34 for n in late):
+        if len(late) > native.CELL_GROUPS_MAX or hidden[0] > 256 or any(not 1 <= c <= 34 for c in couts):
             return []
         return late
 
     @staticmethod
-    def _one_group(late, pairs):
-        """The head sets one packed buffer holds (those of ctdet and multi_pose)."""
-        return (len(late) <= 3 and len(late) * pairs[late[0]][0].weight.shape[0] <= 768 and
-                all(2 <= pairs[n][1].weight.shape[0] <= 34 for n in late))
+    def _one_group(hidden, couts):
+        """What one launch of the cells kernel holds in ONE group (the head sets of ctdet and multi_pose): up
+        to three heads of one hidden width, ``n * hidden <= 768``, of 2 .. 34 outputs each."""
+        return len(couts) <= 3 and len(couts) * hidden <= 768 and all(2 <= c <= 34 for c in couts)
 
     def _cell_heads(self, x, late, pairs):
-        """DeferredHeads of the heads ``late`` on the feature map ``x``; the packed weights live in the
-        module's weight cache."""
+        """DeferredHeads of the heads ``late`` on the feature map ``x``, packed as one group where one holds
+        them and else per ``cell_head_group_sizes``; the packed weights live in the module's weight cache,
+        under a key that carries the grouping."""
         firsts, lasts = [pairs[n][0] for n in late], [pairs[n][1] for n in late]
+        hidden, couts = firsts[0].weight.shape[0], [c.weight.shape[0] for c in lasts]
+        sizes = (len(late),) if self._one_group(hidden, couts) else cell_head_group_sizes(len(late), hidden)
         sources = [c.weight for c in firsts + lasts] + [c.bias for c in firsts + lasts if c.bias is not None]
         cacheable = all(isinstance(t, torch.nn.Parameter) for t in sources)
-        if not self._one_group(late, pairs):
-            # packed per group of consecutive heads, under a key of its own (the grouping is part of it)
-            sizes = cell_head_group_sizes(len(late), firsts[0].weight.shape[0])
-            key = self._wkey("cell_head_groups/" + ".".join(map(str, sizes)), sources) if cacheable else None
-            hit = self.wcache.get(key) if cacheable else None
-            if hit is None:
-                ev = torch.cuda.Event()
-                hit = (pack_cell_head_groups(firsts, lasts, self.device, sizes), ev)
-                ev.record()
-                if cacheable:
-                    self._wput(key, hit)
-            self.keep += [t for g in hit[0] for t in g[:4]]
-            self._pack_events.append(hit[1])
-            return DeferredHeads(late, x, firsts[0].weight.shape[0], couts=[c.weight.shape[0] for c in lasts],
-                                 groups=hit[0])
-        key = self._wkey("cell_heads", sources) if cacheable else None
+        key = self._wkey("cell_head_groups/" + ".".join(map(str, sizes)), sources) if cacheable else None
         hit = self.wcache.get(key) if cacheable else None
         if hit is None:
             ev = torch.cuda.Event()
-            hit = pack_cell_heads(firsts, lasts, self.device) + (ev,)
+            hit = (pack_cell_head_groups(firsts, lasts, self.device, sizes), ev)
             ev.record()
             if cacheable:
                 self._wput(key, hit)
-        self.keep += list(hit[:4])
-        self._pack_events.append(hit[4])
-        return DeferredHeads(late, x, firsts[0].weight.shape[0], *hit[:4],
-                             couts=[c.weight.shape[0] for c in lasts])
+        self.keep += [t for g in hit[0] for t in g[:4]]
+        self._pack_events.append(hit[1])
+        return DeferredHeads(late, x, hidden, hit[0], couts=couts)
 
     def _heads_fused(self, x, names, pairs, w1, b1, lid):
         """All heads as ONE launch (cn_heads3x3_1x1): the hidden channels of a head stay in LDS
