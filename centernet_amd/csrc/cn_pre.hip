@@ -531,3 +531,173 @@ extern "C" int cn_warp_table_u8_f32_ragged(const uint8_t *packed, const cn_image
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
+
+
+// ---------------------------------------------------------------------------
+// NV12 video frames (what hardware and software decoders deliver: a full-resolution Y plane of H rows,
+// then H / 2 rows of interleaved U, V at half resolution, both with the same row pitch) -> dense BGR
+// uint8 (H, W, 3), in front of the pre-process above.  Integer BT.601 limited range in 20-bit fixed point,
+// the arithmetic OpenCV documents for COLOR_YUV2BGR_NV12; one (U, V) pair serves its 2 x 2 block, no chroma
+// interpolation:
+//   yy = max(0, Y - 16) * 1220542
+//   B = clamp((yy + 2116026 (U - 128)                    + 2^19) >> 20)
+//   G = clamp((yy -  409993 (U - 128) - 852492 (V - 128) + 2^19) >> 20)
+//   R = clamp((yy + 1673527 (V - 128)                    + 2^19) >> 20)
+// (arithmetic shift; |every intermediate| < 2^30).  A pure streaming kernel, 1.5 bytes in and 3 bytes out per
+// pixel: a thread converts 2 rows x 16 pixels -- one 16-byte load of each Y row and one of the 8 (U, V)
+// pairs under them, three 16-byte stores per row -- where the frame allows it: every row of both buffers
+// 16-byte aligned, which on the dense output side needs W % 16 == 0 (the widths video comes in).  Any other
+// even W, pitch or pointer takes the same 2 x 16 groups byte by byte, the last group of a row partial.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int NV12_ROUND = 1 << 19, NV12_SHIFT = 20, NV12_VEC = 16;
+
+// the chroma terms of one (U, V) pair, rounding constant included: c[0..2] for B, G, R
+__host__ __device__ inline void nv12_chroma(int U, int V, int c[3])
+{
+    c[0] = 2116026 * (U - 128) + NV12_ROUND;
+    c[1] = -409993 * (U - 128) - 852492 * (V - 128) + NV12_ROUND;
+    c[2] = 1673527 * (V - 128) + NV12_ROUND;
+}
+
+// one pixel: its luma and its block's chroma terms -> B | G << 8 | R << 16
+__host__ __device__ inline uint32_t nv12_pixel(int Y, const int c[3])
+{
+    // clamp((v) >> 20, 0, 255) written as clamp(v, 0, 2^28 - 1) >> 20, the same integer for every v.  In the
+    // first form hipcc (ROCm 7.2, gfx950) selects v_ashr_pk_u8_i32 for two neighbouring channels and ORs its
+    // result into the output word as if the upper half of the register were zero; on the MI355X bytes 2 and
+    // 3 of the word came out wrong (tests/test_gpu_nv12.py, the 16-byte form, is the guard; the listing and
+    // how to re-check it: profiles/nv12_frames_ab.txt section 4).
+    const int yy = (Y > 16 ? Y - 16 : 0) * 1220542, top = (256 << NV12_SHIFT) - 1;
+    const uint32_t b = (uint32_t)clamp_i(yy + c[0], 0, top) >> NV12_SHIFT;
+    const uint32_t g = (uint32_t)clamp_i(yy + c[1], 0, top) >> NV12_SHIFT;
+    const uint32_t r = (uint32_t)clamp_i(yy + c[2], 0, top) >> NV12_SHIFT;
+    return b | (g << 8) | (r << 16);
+}
+
+// `count` (even) pixels of two rows, byte by byte: y0 / y1 the two luma rows, uv the pairs under them
+__host__ __device__ inline void nv12_rows_bytes(const uint8_t *y0, const uint8_t *y1, const uint8_t *uv, int count,
+                                                uint8_t *o0, uint8_t *o1)
+{
+    for (int i = 0; i < count; i += 2) {
+        int c[3];
+        nv12_chroma(uv[i], uv[i + 1], c);
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t p0 = nv12_pixel(y0[i + k], c), p1 = nv12_pixel(y1[i + k], c);
+            for (int ch = 0; ch < 3; ++ch) {
+                o0[(i + k) * 3 + ch] = (uint8_t)(p0 >> (8 * ch));
+                o1[(i + k) * 3 + ch] = (uint8_t)(p1 >> (8 * ch));
+            }
+        }
+    }
+}
+
+struct Nv12Args {
+    const uint8_t *nv12;
+    uint8_t *out;            // (N, H, W, 3) dense
+    int H, W, pitch;
+    int groups_x;            // 16-pixel groups of a row (the last one may be partial)
+    int groups;              // groups_x * (H / 2): one thread each
+    int wide;                // every row of both buffers is 16-byte aligned
+    size_t frame_stride;
+};
+
+// 16 pixels of one row from their luma word by word and the 8 chroma triples -> the row's 48 output bytes
+__host__ __device__ inline void nv12_row16(const uint4 y, const int c[8][3], uint4 o[3])
+{
+    const uint32_t yw[4] = {y.x, y.y, y.z, y.w};
+    uint32_t px[16], w[12];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) px[i] = nv12_pixel((int)((yw[i >> 2] >> (8 * (i & 3))) & 255u), c[i >> 1]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {      // four 3-byte pixels = three words
+        w[3 * q + 0] = px[4 * q] | (px[4 * q + 1] << 24);
+        w[3 * q + 1] = (px[4 * q + 1] >> 8) | (px[4 * q + 2] << 16);
+        w[3 * q + 2] = (px[4 * q + 2] >> 16) | (px[4 * q + 3] << 8);
+    }
+#pragma unroll
+    for (int v = 0; v < 3; ++v) o[v] = make_uint4(w[4 * v], w[4 * v + 1], w[4 * v + 2], w[4 * v + 3]);
+}
+
+// 16 pixels of two rows with 16-byte accesses: all five pointers 16-byte aligned
+__host__ __device__ inline void nv12_rows_wide(const uint8_t *y0, const uint8_t *y1, const uint8_t *uv, uint8_t *o0,
+                                               uint8_t *o1)
+{
+    const uint4 ya = *reinterpret_cast<const uint4 *>(y0), yb = *reinterpret_cast<const uint4 *>(y1);
+    const uint4 cw = *reinterpret_cast<const uint4 *>(uv);
+    const uint32_t uvw[4] = {cw.x, cw.y, cw.z, cw.w};
+    int c[8][3];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const uint32_t pair = uvw[p >> 1] >> (16 * (p & 1));
+        nv12_chroma((int)(pair & 255u), (int)((pair >> 8) & 255u), c[p]);
+    }
+    uint4 r0[3], r1[3];
+    nv12_row16(ya, c, r0);
+    nv12_row16(yb, c, r1);
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        reinterpret_cast<uint4 *>(o0)[v] = r0[v];
+        reinterpret_cast<uint4 *>(o1)[v] = r1[v];
+    }
+}
+
+__global__ void __launch_bounds__(256) nv12_to_bgr_kernel(const Nv12Args a)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.groups) return;
+    const int yp = g / a.groups_x, x0 = (g - yp * a.groups_x) * NV12_VEC;
+    const uint8_t *frame = a.nv12 + (size_t)blockIdx.y * a.frame_stride;
+    const uint8_t *y0 = frame + (size_t)(2 * yp) * a.pitch + x0, *y1 = y0 + a.pitch;
+    const uint8_t *uv = frame + (size_t)(a.H + yp) * a.pitch + x0;
+    uint8_t *o0 = a.out + (((size_t)blockIdx.y * a.H + 2 * yp) * a.W + x0) * 3, *o1 = o0 + (size_t)a.W * 3;
+    if (!a.wide) {       // (uniform over the launch; wide implies W % 16 == 0: no partial group)
+        nv12_rows_bytes(y0, y1, uv, a.W - x0 < NV12_VEC ? a.W - x0 : NV12_VEC, o0, o1);
+        return;
+    }
+    nv12_rows_wide(y0, y1, uv, o0, o1);
+}
+
+// argument rules shared by the device and the host entry (the limits of the warp entry points)
+inline int nv12_check(const void *nv12, const void *out, int H, int W, int pitch_bytes)
+{
+    if (!nv12 || !out) return CN_ERR_NULL;
+    if (H <= 0 || W <= 0 || (H & 1) || (W & 1) || pitch_bytes < W || H > 32767 || W > 32767) return CN_ERR_SHAPE;
+    return CN_OK;
+}
+
+}  // namespace
+
+extern "C" int cn_nv12_to_bgr_u8_batch(const uint8_t *nv12, int N, size_t frame_stride_bytes, int H, int W,
+                                       int pitch_bytes, uint8_t *out_bgr_hwc, void *stream)
+{
+    const int rc = nv12_check(nv12, out_bgr_hwc, H, W, pitch_bytes);
+    if (rc != CN_OK) return rc;
+    if (N <= 0 || N > 65535) return CN_ERR_SHAPE;
+    if (N > 1 && frame_stride_bytes < (size_t)pitch_bytes * (size_t)H * 3 / 2) return CN_ERR_SHAPE;
+    Nv12Args a = {};
+    a.nv12 = nv12; a.out = out_bgr_hwc; a.H = H; a.W = W; a.pitch = pitch_bytes;
+    a.groups_x = cn_cdiv(W, NV12_VEC);
+    a.groups = a.groups_x * (H / 2);        // <= 2048 * 16383
+    a.frame_stride = frame_stride_bytes;
+    a.wide = (((uintptr_t)nv12 | (uintptr_t)out_bgr_hwc | (uintptr_t)pitch_bytes | (uintptr_t)W |
+               (N > 1 ? (uintptr_t)frame_stride_bytes : 0)) & 15) == 0;
+    dim3 grid(cn_cdiv(a.groups, 256), N);
+    hipLaunchKernelGGL(nv12_to_bgr_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+// the same for one frame on the HOST (tests, tools, the frame pipe's hand-back routes): nv12_pixel's integers
+extern "C" int cn_nv12_to_bgr_u8_host(const uint8_t *nv12, int H, int W, int pitch_bytes, uint8_t *out_bgr_hwc)
+{
+    const int rc = nv12_check(nv12, out_bgr_hwc, H, W, pitch_bytes);
+    if (rc != CN_OK) return rc;
+    for (int y = 0; y < H; y += 2) {
+        const uint8_t *y0 = nv12 + (size_t)y * pitch_bytes;
+        uint8_t *o0 = out_bgr_hwc + (size_t)y * W * 3;
+        nv12_rows_bytes(y0, y0 + pitch_bytes, nv12 + (size_t)(H + y / 2) * pitch_bytes, W, o0, o0 + (size_t)W * 3);
+    }
+    return CN_OK;
+}

@@ -19,7 +19,8 @@ import torch
 
 from .. import native
 from ..frame_pipe import FramePipe, ImagePipe
-from ..image import get_affine_transform, invert_affine, normalize_chw, resize_bilinear, warp_affine
+from ..image import (check_pixel_format, get_affine_transform, invert_affine, normalize_chw, nv12_size,
+                     resize_bilinear, warp_affine)
 from ..model import create_model, load_model
 
 InputGeometry = collections.namedtuple(
@@ -138,9 +139,33 @@ class BaseDetector(object):
             batch = np.concatenate((batch, batch[:, :, :, ::-1]), axis=0)
         return torch.from_numpy(np.ascontiguousarray(batch)), self._meta(g)
 
-    def _device_frame(self, image):
+    def _nv12_to_bgr_device(self, nv12, out=None, stream=None):
+        """(N, H * 3 // 2, W) uint8 NV12 frames on the device -> (N, H, W, 3) uint8 BGR on the device (``out``
+        when given), one ``cn_nv12_to_bgr_u8_batch`` launch on ``stream`` (the current one by default)."""
+        N = int(nv12.shape[0])
+        H, W = nv12_size(tuple(nv12.shape[1:]))
+        if out is None:
+            out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=nv12.device)
+        native.check(native.lib().cn_nv12_to_bgr_u8_batch(
+            native.ptr(nv12), N, H * 3 // 2 * W, H, W, W, native.ptr(out),
+            native.stream_ptr() if stream is None else stream), "cn_nv12_to_bgr_u8_batch")
+        return out
+
+    def _device_frame(self, image, pixel_format='bgr'):
         """``pre_process_device``'s frame on the device: a contiguous (H, W, 3) uint8 HIP tensor as it is, a
-        uint8 numpy image uploaded."""
+        uint8 numpy image uploaded; with ``pixel_format='nv12'`` an (H * 3 // 2, W) uint8 frame (numpy, or a
+        contiguous HIP tensor), converted to BGR on the device."""
+        if check_pixel_format(pixel_format) == 'nv12':
+            if torch.is_tensor(image):
+                if image.dtype != torch.uint8 or image.dim() != 2 or not image.is_cuda or not image.is_contiguous():
+                    raise ValueError("pre_process_device needs a contiguous (H * 3 // 2, W) uint8 HIP tensor "
+                                     "as an NV12 frame")
+            elif not isinstance(image, np.ndarray) or image.dtype != np.uint8 or image.ndim != 2:
+                raise ValueError("pre_process_device needs an (H * 3 // 2, W) uint8 array as an NV12 frame")
+            nv12_size(tuple(image.shape))
+            if not torch.is_tensor(image):
+                image = torch.from_numpy(np.ascontiguousarray(image)).to(self.opt.device)
+            return self._nv12_to_bgr_device(image[None])[0]
         if torch.is_tensor(image):
             if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or \
                     not image.is_cuda or not image.is_contiguous():
@@ -150,14 +175,18 @@ class BaseDetector(object):
             raise ValueError("pre_process_device needs an (H, W, 3) uint8 BGR image")
         return torch.from_numpy(np.ascontiguousarray(image)).to(self.opt.device)
 
-    def pre_process_device(self, image, scale, meta=None, out=None):
+    def pre_process_device(self, image, scale, meta=None, out=None, pixel_format='bgr'):
         """The same steps on the device: the uint8 frame (a numpy array, or a uint8 HIP tensor
         that is already uploaded) goes through ``cn_resize_bilinear_u8`` (scale != 1) and
         ``cn_warp_normalize_u8_f32``; the fp32 (1|2,3,H,W) batch is produced in HBM -- into
-        ``out`` when given.  Bit-identical to ``pre_process``."""
+        ``out`` when given.  Bit-identical to ``pre_process``.  ``pixel_format='nv12'``: ``image`` is an
+        (H * 3 // 2, W) uint8 NV12 frame (numpy, or a contiguous HIP tensor), converted on the device first
+        (``cn_nv12_to_bgr_u8_batch``); the result is that of ``image.nv12_to_bgr(frame)``, bit for bit.  Any
+        other value raises ``ValueError``."""
+        check_pixel_format(pixel_format)
         lib = native.lib()
         dev = self.opt.device
-        frame = self._device_frame(image)
+        frame = self._device_frame(image, pixel_format)
         g = self.input_geometry(int(frame.shape[0]), int(frame.shape[1]), scale)
         stream = native.stream_ptr()
         if (g.scaled_h, g.scaled_w) != (g.src_h, g.src_w):
@@ -291,28 +320,47 @@ class BaseDetector(object):
             return self.results_batch(*per_scale[0], **kw)
         return self._results_merged(per_scale, **kw)
 
-    def _pipe_for(self, frames, depth):
+    @staticmethod
+    def _frames_geometry(frames, pixel_format='bgr'):
+        """Argument check of ``run_frames`` / ``run_frames_stream`` (no device needed): (B, H, W) of a batch of
+        frames in ``pixel_format``."""
+        if check_pixel_format(pixel_format) == 'nv12' and torch.is_tensor(frames):
+            if frames.dtype != torch.uint8 or frames.dim() != 3 or frames.shape[0] == 0 or not frames.is_cuda \
+                    or not frames.is_contiguous():
+                raise ValueError("run_frames takes device-resident NV12 frames as one contiguous "
+                                 "(B, H * 3 // 2, W) uint8 HIP tensor")
+            return (int(frames.shape[0]),) + nv12_size(tuple(frames.shape[1:]))
+        if torch.is_tensor(frames) or len(frames) == 0:
+            raise ValueError("run_frames needs a list of frames")
         shapes = {tuple(f.shape) for f in frames}
         if len(shapes) != 1:
             raise ValueError("run_frames needs frames of one size")
-        (H, W, C), = shapes
-        if C != 3 or any(f.dtype != np.uint8 for f in frames):
+        shape, = shapes
+        if pixel_format == 'nv12':
+            if len(shape) != 2 or any(f.dtype != np.uint8 for f in frames):
+                raise ValueError("run_frames with pixel_format='nv12' needs (H * 3 // 2, W) uint8 NV12 frames")
+            return (len(frames),) + nv12_size(shape)
+        if len(shape) != 3 or shape[2] != 3 or any(f.dtype != np.uint8 for f in frames):
             raise ValueError("run_frames needs (H, W, 3) uint8 BGR frames")
+        return len(frames), shape[0], shape[1]
+
+    def _pipe_for(self, frames, depth, pixel_format='bgr'):
+        B, H, W = self._frames_geometry(frames, pixel_format)
         flip = bool(self.opt.flip_test)
         scales = self._pipe_scales()
-        key = (len(frames), H, W, tuple(scales), flip, bool(getattr(self.opt, "nms", False)), depth)
+        key = (B, H, W, tuple(scales), flip, bool(getattr(self.opt, "nms", False)), depth, pixel_format)
         pipes = self.__dict__.setdefault("_pipes", {})
         if key not in pipes:
             if len(pipes) >= 4:
                 pipes.pop(next(iter(pipes))).pool.shutdown(wait=False)
-            pipes[key] = FramePipe(self, len(frames), H, W, scales, flip, depth)
+            pipes[key] = FramePipe(self, B, H, W, scales, flip, depth, pixel_format)
         return pipes[key]
 
     def _frames_and_side(self, batch):
         """One item of ``run_frames_stream``'s iterable -> (frames, the pipe's side array or None)."""
         return batch, None
 
-    def run_frames(self, frames, arrays=False):
+    def run_frames(self, frames, arrays=False, pixel_format='bgr'):
         """A list of (H, W, 3) uint8 BGR frames of one size -> list of per-image results, what
         ``run(frame)['results']`` returns for each (every test scale, flip-test and --nms as set).
         The reference's test loop is batch_size = 1 (test.py:60-62); here the frames are uploaded as
@@ -323,25 +371,37 @@ class BaseDetector(object):
         is no flip average -- the mirror image's rows are rows); the host slices the result.
         ``arrays=True``: a task whose rows are nested lists (multi_pose: ``{1: [[39 floats], ...]}``)
         returns them as a float32 array (``{1: (n, 39) ndarray}``, the same bits, a copy of its own)
-        and saves the ``.tolist()``.  ctdet returns arrays either way."""
-        pipe = self._pipe_for(frames, 1)
+        and saves the ``.tolist()``.  ctdet returns arrays either way.
+        ``pixel_format='nv12'``: the frames as a video decoder delivers them, every frame an (H * 3 // 2, W)
+        uint8 array (H rows of luma, then H / 2 rows of interleaved U, V; H and W even).  Half the bytes are
+        staged and uploaded, ``cn_nv12_to_bgr_u8_batch`` converts the batch on the device and everything
+        behind it is unchanged: the results are those of ``run_frames([image.nv12_to_bgr(f) for f in
+        frames])``, bit for bit.  With 'nv12' ``frames`` may also be ONE contiguous (B, H * 3 // 2, W) uint8 HIP
+        tensor, what a GPU decoder leaves behind: nothing is staged or uploaded, the converter reads the
+        tensor on the current stream -- the caller must not overwrite it before the batch has been collected
+        (here: before the call returns).  Any other ``pixel_format`` raises ``ValueError``."""
+        pipe = self._pipe_for(frames, 1, pixel_format)
         pipe.submit(0, frames)
         return pipe.collect(0, frames, arrays)
 
-    def run_frames_stream(self, batches, depth=3, arrays=False):
+    def run_frames_stream(self, batches, depth=3, arrays=False, pixel_format='bgr'):
         """``run_frames`` over an iterable of batches (lists of frames, all batches of one size and
         frame geometry), pipelined: while batch i is on the device the host stages batch i + 1
         (pinned uint8 copy by a few threads, asynchronous upload on a copy stream) and builds the
         result dictionaries of batch i - 1.  Yields the per-image results batch by batch, in order.
-        ``arrays``: as ``run_frames``."""
+        ``arrays``: as ``run_frames``.  ``pixel_format``: as ``run_frames``, one format for the whole stream
+        (a batch in the other format raises ``ValueError``); a device-resident NV12 batch must stay untouched
+        until its results have been yielded, i.e. for ``depth`` further batches."""
+        check_pixel_format(pixel_format)
         pipe, pending = None, collections.deque()
         n = 0
         for batch in batches:
             frames, side = self._frames_and_side(batch)
             if pipe is None:
-                pipe = self._pipe_for(frames, depth)
-            elif (len(frames), ) + tuple(frames[0].shape) != (pipe.B, pipe.H, pipe.W, 3):
-                raise ValueError("run_frames_stream needs batches of one size and frame geometry")
+                pipe = self._pipe_for(frames, depth, pixel_format)
+            elif self._frames_geometry(frames, pixel_format) != (pipe.B, pipe.H, pipe.W):
+                raise ValueError("run_frames_stream needs batches of one size, frame geometry and pixel format "
+                                 "(%d %s frames of shape %s)" % (pipe.B, pipe.pixel_format, pipe.frame_shape))
             if len(pending) == depth:
                 j, fr = pending.popleft()
                 yield pipe.collect(j, fr, arrays)

@@ -91,12 +91,13 @@ class DddDetector(BaseDetector):
             native.ptr(self.norm_table(device=True)), native.ptr(out),
             native.stream_ptr() if stream is None else stream), "cn_warp_table_u8_f32_batch")
 
-    def pre_process_device(self, image, scale, calib=None, out=None):
+    def pre_process_device(self, image, scale, calib=None, out=None, pixel_format='bgr'):
         """The same on the device: the uint8 frame (a numpy array, or a uint8 HIP tensor that is already
         uploaded) through ``cn_warp_table_u8_f32_batch`` -- the warp of the other tasks with the float32
-        normalisation looked up in ``norm_table``.  Bit-identical to ``pre_process``."""
+        normalisation looked up in ``norm_table``.  Bit-identical to ``pre_process``.  ``pixel_format``: as
+        ``BaseDetector.pre_process_device`` ('nv12': an (H * 3 // 2, W) frame, converted on the device first)."""
         dev = self.opt.device
-        frame = self._device_frame(image)
+        frame = self._device_frame(image, pixel_format)
         shape = (1, 3, self.opt.input_h, self.opt.input_w)
         if out is None:
             out = torch.empty(shape, device=dev, dtype=torch.float32)
@@ -198,24 +199,26 @@ class DddDetector(BaseDetector):
     def _pipe_pre_process(self, pipe, lv, src, stream):
         self._warp_table(src, lv.dst_to_src, lv.batch, stream)
 
-    def run_frames(self, frames, calibs=None):
+    def run_frames(self, frames, calibs=None, pixel_format='bgr'):
         """A list of (H, W, 3) uint8 BGR frames of one size and their projection matrices -> per frame what
         ``run(frame_i, calib_i)['results']`` returns: ``{class: (n, 13) float32}``, a class without rows a
         ``(0,)`` array, a class whose rows were all cut at --peak_thresh ``(0, 13)``.  ``calibs``: one
         (3, 4) matrix for all frames, or a sequence with one per frame (``None`` = the detector's default
         matrix); every frame is lifted with ITS matrix (the reference's single-image detector lifts with
         ``calibs[0]``).  One uint8 upload, one pre-process launch, one network step, one decode (the
-        depth transform inside it) and one tail launch per batch; the host slices the rows."""
+        depth transform inside it) and one tail launch per batch; the host slices the rows.
+        ``pixel_format='nv12'``: (H * 3 // 2, W) NV12 frames, or one (B, H * 3 // 2, W) uint8 HIP tensor, as
+        ``BaseDetector.run_frames`` takes them; converted on the device in front of the warp."""
         side = self._calibs_for(frames, calibs)
-        pipe = self._pipe_for(frames, 1)
+        pipe = self._pipe_for(frames, 1, pixel_format)
         pipe.submit(0, frames, side)
         return pipe.collect(0, frames)
 
-    def run_frames_stream(self, batches, depth=3):
+    def run_frames_stream(self, batches, depth=3, pixel_format='bgr'):
         """``run_frames`` over an iterable of ``(frames, calibs)`` pairs (all batches of one size and frame
         geometry), pipelined as ``BaseDetector.run_frames_stream``; the matrices are staged in pinned
-        memory and uploaded on the copy stream with their frames."""
-        return super(DddDetector, self).run_frames_stream(batches, depth)
+        memory and uploaded on the copy stream with their frames.  ``pixel_format``: as ``run_frames``."""
+        return super(DddDetector, self).run_frames_stream(batches, depth, pixel_format=pixel_format)
 
     # ------------------------------------------------------------------ images of mixed sizes
     def _fixed_input(self):
@@ -270,12 +273,16 @@ class DddDetector(BaseDetector):
     def _run_frames_sync(self, frames, scales, side=None):
         """One batch synchronously (the pipe's re-run path after an f32s re-calibration)."""
         uploaded = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.opt.device)
+        return self._run_uploaded_sync(uploaded, scales, side=side)
+
+    def _run_uploaded_sync(self, uploaded, scales, side=None):
+        """``_run_frames_sync`` of a (n, H, W, 3) uint8 batch that is on the device."""
+        n = int(uploaded.shape[0])
         c, s, to_input = self._frame_geometry(int(uploaded.shape[1]), int(uploaded.shape[2]))
-        batch = torch.empty((len(frames), 3, self.opt.input_h, self.opt.input_w), device=self.opt.device,
-                            dtype=torch.float32)
+        batch = torch.empty((n, 3, self.opt.input_h, self.opt.input_w), device=self.opt.device, dtype=torch.float32)
         self._warp_table(uploaded, to_input, batch)
         dets = self._forward_checked(batch, False)
-        return self.results_batch(dets, [self._meta(c, s, None)] * len(frames), 1.0, side=side)
+        return self.results_batch(dets, [self._meta(c, s, None)] * n, 1.0, side=side)
 
     def _run_images_sync(self, images, scales, side=None):
         """``_run_frames_sync`` for images of any sizes: each image uploaded on its own, warped into its slice

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import native
-from .image import get_affine_transform, invert_affine
+from .image import get_affine_transform, invert_affine, nv12_to_bgr
 
 
 class DeviceTail(object):
@@ -113,14 +113,28 @@ class FramePipe(object):
     A task with per-frame side inputs (ddd: one 3 x 4 calibration matrix per frame) sets
     ``_pipe_side_shape``: the pipe then keeps ``depth`` pinned (B, *shape) float32 buffers and their device
     copies, ``submit`` takes the batch's side array, uploads it on the copy stream with the frames, and the
-    tail reads ``pipe.side_dev[slot]`` / ``pipe.side_host[slot]``."""
+    tail reads ``pipe.side_dev[slot]`` / ``pipe.side_host[slot]``.
+
+    ``pixel_format='nv12'``: the frames are (H * 3 // 2, W) uint8 NV12, and so are the pinned buffers and their
+    device copies (1.5 bytes per pixel staged and uploaded instead of 3).  ``submit`` converts the uploaded
+    batch with one ``cn_nv12_to_bgr_u8_batch`` launch on the launch stream into ``self.bgr`` -- ONE (B, H, W, 3)
+    buffer per pipe: it is written and read on the launch stream only -- and the levels pre-process that.  The
+    converter is then the only reader of the uploaded buffer, so ``ev_pre``, which lets the next upload into
+    the slot start, is recorded right behind it.  A batch that is already on the device (one (B, H * 3 // 2, W)
+    uint8 HIP tensor) is neither staged nor uploaded: the converter reads it on the current stream.  The
+    hand-back routes of ``collect`` convert the batch to BGR (host frames on the host, a device batch on the
+    device) and take the synchronous BGR path."""
 
     to_source_dev = None     # (ImagePipe: per slot the (S, B, 6) output grid -> source maps of its batch)
 
-    def __init__(self, det, B, H, W, scales, flip, depth):
+    pixel_format = 'bgr'
+    bgr = None               # ('nv12': the converted batch, (B, H, W, 3) uint8 on the device)
+
+    def __init__(self, det, B, H, W, scales, flip, depth, pixel_format='bgr'):
         dev = det.opt.device
         self._setup(det, B, scales, flip, depth)
-        self.H, self.W = H, W
+        self.H, self.W, self.pixel_format = H, W, pixel_format
+        self.frame_shape = (H * 3 // 2, W) if pixel_format == 'nv12' else (H, W, 3)
         self.levels = []
         for scale in self.scales:
             g, to_input, meta = det._pipe_level(H, W, scale)
@@ -133,9 +147,11 @@ class FramePipe(object):
                                   dtype=torch.float32)))
         first = self.levels[0]        # (the single-scale pipe's own names)
         self.scale, self.g, self.meta, self.batch = first.scale, first.g, first.meta, first.batch
-        self.pinned_in = [torch.empty((B, H, W, 3), dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        self.pinned_in = [torch.empty((B,) + self.frame_shape, dtype=torch.uint8).pin_memory() for _ in range(depth)]
         self.np_in = [t.numpy() for t in self.pinned_in]
-        self.dev_in = [torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(depth)]
+        self.dev_in = [torch.empty((B,) + self.frame_shape, dtype=torch.uint8, device=dev) for _ in range(depth)]
+        if pixel_format == 'nv12':
+            self.bgr = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
         self._setup_tail()
 
     def _setup(self, det, B, scales, flip, depth):
@@ -184,7 +200,7 @@ class FramePipe(object):
     def _pre_process(self, slot, level, stream):
         """On the launch stream: the uploaded batch of ``slot`` -> the batch of test scale ``level``."""
         lv = self.levels[level]
-        lib, g, src = native.lib(), lv.g, self.dev_in[slot]
+        lib, g, src = native.lib(), lv.g, self.dev_in[slot] if self.bgr is None else self.bgr
         if lv.resize:
             for j in range(self.B):
                 native.check(lib.cn_resize_bilinear_u8(native.ptr(src[j]), g.src_h, g.src_w, g.src_w * 3,
@@ -198,23 +214,31 @@ class FramePipe(object):
         return [self.levels[level].meta] * n
 
     def _run_sync(self, frames, **kw):
-        """The batch once more, synchronously, host tail: both hand-back routes of ``collect``."""
+        """The batch once more, synchronously, host tail: both hand-back routes of ``collect``.  NV12 frames
+        are converted first: a device-resident batch on the device, host frames on the host."""
+        if self.pixel_format == 'nv12':
+            if torch.is_tensor(frames):
+                return self.det._run_uploaded_sync(self.det._nv12_to_bgr_device(frames), self.scales, **kw)
+            frames = [nv12_to_bgr(f) for f in frames]
         return self.det._run_frames_sync(frames, self.scales, **kw)
 
     def submit(self, i, frames, side=None):
         det = self.det
         slot = i % self.depth
+        resident = torch.is_tensor(frames)       # (NV12 only: the batch is on the device already)
         if self.used[slot]:
             self.ev_h2d[slot].synchronize()      # the pinned buffer's previous upload has left it
-        self._stage(slot, frames)
+        if not resident:
+            self._stage(slot, frames)
         if self.side_pinned is not None:
             self.side_host[slot] = side
             self.side_pinned[slot].numpy()[:len(frames)] = side
         cur = torch.cuda.current_stream()
         with torch.cuda.stream(self.copy_stream):
-            if self.used[slot]:
-                self.copy_stream.wait_event(self.ev_pre[slot])   # the device copy's previous reader is done
-            self._upload(slot)
+            if not resident:
+                if self.used[slot]:
+                    self.copy_stream.wait_event(self.ev_pre[slot])   # the device copy's previous reader is done
+                self._upload(slot)
             if self.side_pinned is not None:
                 if self.used[slot]:
                     self.copy_stream.wait_event(self.ev_done[slot])   # its reader is the tail, not the pre-process
@@ -223,9 +247,12 @@ class FramePipe(object):
         self.used[slot] = True
         cur.wait_event(self.ev_h2d[slot])
         stream = native.stream_ptr()
+        if self.bgr is not None:
+            det._nv12_to_bgr_device(frames if resident else self.dev_in[slot], self.bgr, stream)
+            self.ev_pre[slot].record()           # the converter is the uploaded buffer's only reader
         for li, lv in enumerate(self.levels):
             self._pre_process(slot, li, stream)
-            if li == len(self.levels) - 1:
+            if li == len(self.levels) - 1 and self.bgr is None:
                 self.ev_pre[slot].record()
             dets = det._run_scale(lv.batch, self.flip)
             plan = det.model.plan_for(lv.batch.shape[0], lv.batch.shape[2], lv.batch.shape[3], lv.batch.device)

@@ -162,6 +162,67 @@ def resize_bilinear(img, dsize):
     return out
 
 
+PIXEL_FORMATS = ("bgr", "nv12")
+
+
+def check_pixel_format(pixel_format):
+    """The ``pixel_format`` argument of the frame entry points: 'bgr' or 'nv12', anything else a ``ValueError``."""
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError("pixel_format must be one of %s, got %r" % (PIXEL_FORMATS, pixel_format))
+    return pixel_format
+
+
+def nv12_size(shape):
+    """(H, W) of the picture in an NV12 frame of ``shape`` (H * 3 // 2, W), H and W even; ``ValueError`` for
+    any other shape."""
+    if len(shape) != 2 or shape[0] <= 0 or shape[1] <= 0 or shape[0] % 3 or shape[1] % 2:
+        raise ValueError("an NV12 frame is a (H * 3 // 2, W) array with H and W even, got shape %s" % (tuple(shape),))
+    return int(shape[0]) // 3 * 2, int(shape[1])
+
+
+def nv12_to_bgr(frame):
+    """An NV12 frame -- (H * 3 // 2, W) uint8: H rows of luma, then H / 2 rows of interleaved (U, V) at half
+    resolution -- to (H, W, 3) uint8 BGR: integer BT.601 limited range, 20-bit fixed point, no chroma
+    interpolation, what OpenCV documents for ``cv2.cvtColor(frame, cv2.COLOR_YUV2BGR_NV12)`` (library host
+    routine ``cn_nv12_to_bgr_u8_host``; the device form ``cn_nv12_to_bgr_u8_batch`` gives the same bytes)."""
+    import ctypes
+    from . import native
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8:
+        raise ValueError("nv12_to_bgr needs a uint8 numpy array")
+    H, W = nv12_size(frame.shape)
+    frame = np.ascontiguousarray(frame)
+    out = np.empty((H, W, 3), np.uint8)
+    native.check(native.lib().cn_nv12_to_bgr_u8_host(
+        frame.ctypes.data_as(ctypes.c_void_p), H, W, W, out.ctypes.data_as(ctypes.c_void_p)),
+        "cn_nv12_to_bgr_u8_host")
+    return out
+
+
+def bgr_to_nv12(image):
+    """(H, W, 3) uint8 BGR, H and W even -> an (H * 3 // 2, W) uint8 NV12 frame, for tests and tools (frames of
+    a real video come from its decoder).  Integer BT.601 limited range with 8-bit coefficients, the common
+    forward form:
+        Y = (( 66 R + 129 G +  25 B + 128) >> 8) +  16
+        U = ((-38 R -  74 G + 112 B + 128) >> 8) + 128
+        V = ((112 R -  94 G -  18 B + 128) >> 8) + 128
+    Y per pixel; U and V from the rounded mean ``(a + b + c + d + 2) >> 2`` of each channel over the 2 x 2
+    block.  Not an exact inverse of ``nv12_to_bgr``: chroma is sub-sampled and both directions round."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("bgr_to_nv12 needs an (H, W, 3) uint8 image")
+    H, W = image.shape[:2]
+    if H <= 0 or W <= 0 or H % 2 or W % 2:
+        raise ValueError("bgr_to_nv12 needs even H and W, got %d x %d" % (H, W))
+    px = image.astype(np.int32)
+    b, g, r = px[:, :, 0], px[:, :, 1], px[:, :, 2]
+    out = np.empty((H * 3 // 2, W), np.uint8)
+    out[:H] = ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16
+    m = (px[0::2, 0::2] + px[0::2, 1::2] + px[1::2, 0::2] + px[1::2, 1::2] + 2) >> 2
+    b, g, r = m[:, :, 0], m[:, :, 1], m[:, :, 2]
+    out[H:, 0::2] = ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128
+    out[H:, 1::2] = ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128
+    return out
+
+
 def normalize_chw(inp_u8, mean, std):
     """((inp / 255. - mean) / std).astype(float32) then HWC -> CHW (base_detector.py:56-58), in the
     library's host routine (numpy's float64 arithmetic through a 256-entry table per channel;

@@ -229,6 +229,10 @@ def _declare(lib):
     lib.cn_warp_affine_u8_host.argtypes = [vp, i, i, i, ctypes.POINTER(ctypes.c_double), i, i, vp]
     lib.cn_resize_linear_u8_host.restype = i
     lib.cn_resize_linear_u8_host.argtypes = [vp, i, i, i, i, i, vp]
+    lib.cn_nv12_to_bgr_u8_batch.restype = i
+    lib.cn_nv12_to_bgr_u8_batch.argtypes = [vp, i, sz, i, i, i, vp, vp]
+    lib.cn_nv12_to_bgr_u8_host.restype = i
+    lib.cn_nv12_to_bgr_u8_host.argtypes = [vp, i, i, i, vp]
     lib.cn_normalize_u8_chw_f32_host.restype = i
     lib.cn_normalize_u8_chw_f32_host.argtypes = [vp, i, i, vp, vp, vp]
     lib.cn_soft_nms_f32.restype = i

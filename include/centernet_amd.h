@@ -675,6 +675,25 @@ int cn_warp_affine_u8_host(const uint8_t *image_hwc, int h_in, int w_in, int cha
 int cn_resize_linear_u8_host(const uint8_t *image_hwc, int h_in, int w_in, int channels, int h_out,
                              int w_out, uint8_t *out_hwc);
 
+/* NV12 video frames -> BGR, in front of the pre-process entry points above (decoders deliver NV12; the
+ * pre-process takes packed BGR).  A frame is H rows of luma, then H / 2 rows of interleaved (U, V) at half
+ * resolution, every row pitch_bytes (>= W) apart, the chroma plane at pitch_bytes * H; H and W even.
+ * Arithmetic: integer BT.601 limited range in 20-bit fixed point, as OpenCV documents COLOR_YUV2BGR_NV12 --
+ *   yy = max(0, Y - 16) * 1220542
+ *   B = clamp((yy + 2116026 (U - 128)                    + 2^19) >> 20, 0, 255)
+ *   G = clamp((yy -  409993 (U - 128) - 852492 (V - 128) + 2^19) >> 20, 0, 255)
+ *   R = clamp((yy + 1673527 (V - 128)                    + 2^19) >> 20, 0, 255)
+ * with an arithmetic shift of int32 values; one (U, V) pair serves its 2 x 2 block (no chroma interpolation).
+ * cn_nv12_to_bgr_u8_batch: N frames on the device, frame_stride_bytes apart (>= pitch_bytes * H * 3 / 2 when
+ *   N > 1), to dense (N, H, W, 3) uint8 in one launch.  16-byte loads and stores where every row of both
+ *   buffers is 16-byte aligned (pointers, pitch and frame stride multiples of 16, W % 16 == 0), byte accesses
+ *   otherwise: any even W and any pitch work.  H, W <= 32767, N <= 65535; CN_ERR_SHAPE for odd or
+ *   non-positive H or W, pitch_bytes < W, a short stride or sizes above those limits.
+ * cn_nv12_to_bgr_u8_host: one frame on the HOST, the same integers; needs no device. */
+int cn_nv12_to_bgr_u8_batch(const uint8_t *nv12, int N, size_t frame_stride_bytes, int H, int W, int pitch_bytes,
+                            uint8_t *out_bgr_hwc, void *stream);
+int cn_nv12_to_bgr_u8_host(const uint8_t *nv12, int H, int W, int pitch_bytes, uint8_t *out_bgr_hwc);
+
 /* ((image / 255. - mean) / std).astype(float32) + HWC -> CHW of a 3-channel uint8 image on the HOST
  * (base_detector.py:56-58), numpy's float64 arithmetic, one rounding to float32. */
 int cn_normalize_u8_chw_f32_host(const uint8_t *image_hwc, int h, int w, const float *mean3,
