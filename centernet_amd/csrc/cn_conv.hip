@@ -813,6 +813,37 @@ int launch_igemm(const IgemmArgs &a, hipStream_t st)
     return launch_igemm_n<float, BM, BN, WM, WN, AMODE, OUT_NCHW, 2>(a, st);
 }
 
+// dtype leg of one tile shape.  fp16: dense and stem forms only; f32s: not the stem
+template <int BM, int BN, int WM, int WN, int AMODE, bool OUT_NCHW>
+int launch_igemm_t(int dtype, const IgemmArgs &a, hipStream_t st)
+{
+    if constexpr (AMODE != A_STEM) {
+        if (dtype == CN_DTYPE_F32S) return launch_igemm_s<BM, BN, WM, WN, AMODE, OUT_NCHW>(a, st);
+    }
+    if constexpr (AMODE == A_DENSE || AMODE == A_STEM) {
+        if (dtype == CN_DTYPE_F16) return launch_igemm_h<BM, BN, WM, WN, AMODE, OUT_NCHW>(a, st);
+    }
+    return launch_igemm<BM, BN, WM, WN, AMODE, OUT_NCHW>(a, st);
+}
+
+// The one dtype-by-class ladder.  cls: N tile 128 / 64 / 32 wide (2 / 1 / 0); bm64: 64-pixel tiles for the 128-wide
+// class, built for the dense NHWC form only.  The deformable forms run 64-pixel tiles (128-pixel tiles were measured
+// slower at every CenterNet shape, tools/bench_dcn.py, and are no longer built) except at <= 32 output channels.
+inline int cout_class(int Cout) { return Cout > 64 ? 2 : (Cout > 32 ? 1 : 0); }
+template <int AMODE, bool OUT_NCHW>
+int igemm_dispatch(int dtype, int cls, bool bm64, const IgemmArgs &a, hipStream_t st)
+{
+    constexpr bool DCN = AMODE == A_DCN || AMODE == A_DCN_PAD;
+    if (cls == 2) {
+        if constexpr (DCN || (AMODE == A_DENSE && !OUT_NCHW)) {
+            if (DCN || bm64) return launch_igemm_t<64, 128, 2, 2, AMODE, OUT_NCHW>(dtype, a, st);
+        }
+        if constexpr (!DCN) return launch_igemm_t<128, 128, 2, 2, AMODE, OUT_NCHW>(dtype, a, st);
+    }
+    if (cls == 1) return launch_igemm_t<DCN ? 64 : 128, 64, 2, 2, AMODE, OUT_NCHW>(dtype, a, st);
+    return launch_igemm_t<128, 32, 4, 1, AMODE, OUT_NCHW>(dtype, a, st);
+}
+
 // ---- weight packing: (Cout,Cin,KH,KW) -> [tap][cout_pad][cin_pad], zero padded
 template <typename T>
 __global__ void pack_weight_kernel(const float *__restrict__ w, T *__restrict__ wp, int Cout,
@@ -959,6 +990,21 @@ __global__ void splitk_reduce_kernel(const IgemmArgs a)
     }
 }
 
+// cap: most blocks of the launch (the callers keep the caps they were measured with)
+int launch_splitk_reduce(int dtype, const IgemmArgs &a, int cap, hipStream_t st)
+{
+    const size_t total = (size_t)a.M * (a.cout_pad >> 2);
+    const dim3 grid((unsigned)((total + 255) / 256 < (size_t)cap ? (total + 255) / 256 : cap));
+    if (dtype == CN_DTYPE_F32S)
+        hipLaunchKernelGGL(splitk_reduce_kernel<cn_f32s>, grid, dim3(256), 0, st, a);
+    else if (dtype == CN_DTYPE_F16)
+        hipLaunchKernelGGL(splitk_reduce_kernel<_Float16>, grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(splitk_reduce_kernel<float>, grid, dim3(256), 0, st, a);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 // How many K-splits a dense NHWC layer gets: enough workgroups to put ~2 on every CU,
 // at least 8 chunks of K per split, only when the plain grid is badly under-filled.
 inline int plan_ksplit(int M, int Cout, int KT, int bm, int bn)
@@ -970,7 +1016,6 @@ inline int plan_ksplit(int M, int Cout, int KT, int bm, int bn)
     if (s > cn_knobs.split_max) s = cn_knobs.split_max;
     return s < 2 ? 1 : s;
 }
-inline bool is_stem(int Cin, int in_layout) { return in_layout == CN_LAYOUT_NCHW && Cin == 3; }
 inline void set_ctl(IgemmArgs &a, const cn_f32s_ctl *ctl)
 {
     a.x_mul = (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f;
@@ -1059,7 +1104,13 @@ extern "C" int cn_pack_conv_weight_f32(const float *w_oihw, float *w_packed, int
     return cn_pack_conv_weight(w_oihw, w_packed, Cout, Cin, KH, KW, CN_DTYPE_F32, stream);
 }
 
-static int conv_fill_args(const cn_conv_desc *d, IgemmArgs *a)
+static bool plain_geometry(const cn_conv_desc *d)
+{
+    return d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 && d->ox_add == 0 && d->OH == d->Ho && d->OW == d->Wo;
+}
+
+// The descriptor checks of cn_conv2d and its queries, then every field of the call that needs no pointer
+static int conv_fill(const cn_conv_desc *d, ConvCall &c)
 {
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 ||
         d->KW <= 0 || d->stride <= 0 || d->dil <= 0 || d->Ho <= 0 || d->Wo <= 0)
@@ -1074,16 +1125,6 @@ static int conv_fill_args(const cn_conv_desc *d, IgemmArgs *a)
     if ((long)d->B * d->OH * d->OW * (long)(d->out_layout == CN_LAYOUT_NHWC ? d->out_pitch : d->Cout) >=
         (1L << 31))
         return CN_ERR_UNSUPPORTED;
-    a->B = d->B; a->H = d->H; a->W = d->W; a->Cin = d->Cin;
-    a->Ho = d->Ho; a->Wo = d->Wo; a->Cout = d->Cout;
-    a->KH = d->KH; a->KW = d->KW; a->stride = d->stride;
-    a->pad_h = d->pad_h; a->pad_w = d->pad_w; a->dil = d->dil;
-    a->in_pitch = d->in_pitch; a->out_pitch = d->out_pitch;
-    a->OH = d->OH; a->OW = d->OW;
-    a->oy_mul = d->oy_mul; a->oy_add = d->oy_add; a->ox_mul = d->ox_mul; a->ox_add = d->ox_add;
-    a->relu = d->relu;
-    a->M = d->B * d->Ho * d->Wo;
-    a->cout_pad = round_up(d->Cout, 32);
     const int f16 = (d->dtype == CN_DTYPE_F16);
     const int f32s = (d->dtype == CN_DTYPE_F32S);
     if (d->dtype != CN_DTYPE_F32 && !f16 && !f32s) return CN_ERR_UNSUPPORTED;
@@ -1092,79 +1133,188 @@ static int conv_fill_args(const cn_conv_desc *d, IgemmArgs *a)
         return CN_ERR_UNSUPPORTED;
     if (f32s && d->out_layout == CN_LAYOUT_NHWC && !(d->flags & CN_CONV_Y_PLAIN) && (d->out_pitch & 31))
         return CN_ERR_UNSUPPORTED;
+    c = {};
+    c.B = d->B; c.H = d->H; c.W = d->W; c.Cin = d->Cin; c.Ho = d->Ho; c.Wo = d->Wo; c.Cout = d->Cout;
+    c.KH = d->KH; c.KW = d->KW; c.stride = d->stride; c.pad_h = d->pad_h; c.pad_w = d->pad_w; c.dil = d->dil;
+    c.in_pitch = d->in_pitch; c.out_pitch = d->out_pitch;
+    c.res_pitch = d->res_pitch > 0 ? d->res_pitch : d->out_pitch;
+    c.relu = d->relu; c.dtype = d->dtype;
+    c.in_plain = (d->flags & CN_CONV_X_PLAIN) ? 1 : 0;
+    c.out_plain = (d->flags & CN_CONV_Y_PLAIN) ? 1 : 0;
+    c.res_plain = (d->flags & CN_CONV_R_PLAIN) ? 1 : 0;
+    c.stem = (d->in_layout == CN_LAYOUT_NCHW && d->Cin == 3) ? 1 : 0;
+    c.stem_f32s = (d->flags & CN_CONV_STEM_F32S) ? 1 : 0;
+    c.stem_pool = (d->flags & CN_CONV_STEM_MAXPOOL) ? 1 : 0;
+    c.stem_y_f32s = (d->flags & CN_CONV_STEM_Y_F32S) ? 1 : 0;
+    c.out_nchw = d->out_layout != CN_LAYOUT_NHWC;
+    c.plain_geo = plain_geometry(d);
+    c.ctl = &d->ctl;
+    c.ksplit = 1;
     const int bke = f16 ? 64 : 32, epv = f16 ? 8 : 4;
-    if (is_stem(d->Cin, d->in_layout)) {
-        a->cin_pad = round_up(d->KH * d->KW * 3, bke);
-        if (a->cin_pad > STEM_KMAX) return CN_ERR_UNSUPPORTED;
-        a->nchunk = a->cin_pad / bke;
-        a->KT = a->nchunk;
+    c.cout_pad = round_up(d->Cout, 32);
+    if (c.stem) {
+        c.cin_pad = round_up(d->KH * d->KW * 3, bke);
+        if (c.cin_pad > STEM_KMAX) return CN_ERR_UNSUPPORTED;
     } else {
         if (d->in_layout != CN_LAYOUT_NHWC) return CN_ERR_UNSUPPORTED;
         if ((d->Cin % epv) || (d->in_pitch % epv) || d->in_pitch < d->Cin) return CN_ERR_UNSUPPORTED;
-        a->cin_pad = round_up(d->Cin, bke);
-        a->nchunk = a->cin_pad / bke;
-        a->KT = d->KH * d->KW * a->nchunk;
+        c.cin_pad = round_up(d->Cin, bke);
     }
+    c.nchunk = c.cin_pad / bke;
     return CN_OK;
 }
 
-// tile class of a dense layer: N tile 128 / 64 / 32 wide, pixel tile 128 or 64
-static void dense_tile_class(const cn_conv_desc *d, const IgemmArgs &a, int *cls, bool *bm64)
-{
-    // 128-wide N tiles unless their padding wastes a whole 64-wide tile (e.g. Cout = 192)
-    const int waste128 = cn_cdiv(d->Cout, 128) * 128 - d->Cout;
-    const int waste64 = cn_cdiv(d->Cout, 64) * 64 - d->Cout;
-    const bool narrow = !cn_knobs.narrow && (waste128 - waste64 >= 64);
-    *cls = (d->Cout > 64 && !narrow) ? 2 : (d->Cout > 32 ? 1 : 0);
-    // fewer than four workgroups per CU with 128-pixel tiles: halve the pixel tile
-    const long wgs128 = (long)cn_cdiv(a.M, 128) * cn_cdiv(d->Cout, 128) * (a.zparity ? 4 : 1);
-    // ... unless the 128-pixel grid is exactly one round of two workgroups per CU (512): then the
-    // 64-pixel grid (1024 at three per CU = 1.33 rounds) loses (128->256/s2@32^2: 0.210 -> 0.183 ms)
-    *bm64 = (*cls == 2) && (cn_knobs.bm ? (cn_knobs.bm == 64) : (wgs128 < 1024 && wgs128 != 512));
-}
-
-static int dense_ksplit(const cn_conv_desc *d, const IgemmArgs &a)
-{
-    if (cn_knobs.nosplit || d->out_layout != CN_LAYOUT_NHWC || is_stem(d->Cin, d->in_layout) ||
-        a.zparity)
-        return 1;
-    int cls;
-    bool bm64;
-    dense_tile_class(d, a, &cls, &bm64);
-    const int bm = bm64 ? 64 : 128, bn = cls == 2 ? 128 : (cls == 1 ? 64 : 32);
-    return plan_ksplit(a.M, d->Cout, a.KT, bm, bn);
-}
-
-static bool is_3x3s1(const cn_conv_desc *d)
-{
-    return d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_h == 1 && d->pad_w == 1 && d->dil == 1 &&
-           d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 && d->ox_add == 0 && d->OH == d->Ho &&
-           d->OW == d->Wo;
-}
-
-// (mirror of cn_conv2d's route to cn_conv3x3s1; the caller passes the workspace its query asked for,
-// so a layer that wants split-K gets it and stays on the implicit-GEMM kernel)
-extern "C" int cn_conv2d_res_pitch_supported(const cn_conv_desc *d)
+// The implicit-GEMM kernel's view of a call; d: where the output pixels go (null: the caller sets OH .. ox_add)
+static IgemmArgs igemm_args(const ConvCall &c, const cn_conv_desc *d)
 {
     IgemmArgs a = {};
-    if (!d || conv_fill_args(d, &a) != CN_OK) return 0;
-    if (cn_knobs.nohalo || !is_3x3s1(d) || is_stem(d->Cin, d->in_layout) || d->out_layout != CN_LAYOUT_NHWC) return 0;
-    if (d->dtype == CN_DTYPE_F32 && d->Cin == 16 && d->Cout <= 32) return 0;     // cn_conv16.hip
-    if (d->dtype == CN_DTYPE_F32S && (d->flags & CN_CONV_X_PLAIN) && (d->flags & CN_CONV_Y_PLAIN) && d->Cin == 16 &&
-        d->Cout <= 32)
-        return 0;
-    a.in_plain = (d->flags & CN_CONV_X_PLAIN) ? 1 : 0;
-    a.out_plain = (d->flags & CN_CONV_Y_PLAIN) ? 1 : 0;
-    a.res_plain = (d->flags & CN_CONV_R_PLAIN) ? 1 : 0;
-    return dense_ksplit(d, a) > 1 ? 0 : 1;
+    if (d) {
+        a.OH = d->OH; a.OW = d->OW;
+        a.oy_mul = d->oy_mul; a.oy_add = d->oy_add; a.ox_mul = d->ox_mul; a.ox_add = d->ox_add;
+    }
+    a.x = c.x; a.w = c.w; a.scale = c.scale; a.shift = c.shift; a.residual = c.residual; a.y = c.y;
+    set_ctl(a, c.ctl);
+    a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout = c.Cout;
+    a.KH = c.KH; a.KW = c.KW; a.stride = c.stride; a.pad_h = c.pad_h; a.pad_w = c.pad_w; a.dil = c.dil;
+    a.in_pitch = c.in_pitch; a.out_pitch = c.out_pitch;
+    a.relu = c.relu;
+    a.M = c.B * c.Ho * c.Wo;
+    a.cin_pad = c.cin_pad; a.cout_pad = c.cout_pad; a.nchunk = c.nchunk;
+    a.KT = c.stem ? c.nchunk : c.KH * c.KW * c.nchunk;
+    a.vec_out = c.vec_out;
+    a.ksplit = c.ksplit; a.partial = c.partial;
+    a.in_plain = c.in_plain; a.out_plain = c.out_plain; a.res_plain = c.res_plain;
+    return a;
+}
+
+// ---- routing: which kernel runs a cn_conv2d call.  Decided here and nowhere else: cn_conv2d switches on
+// the answer, the four queries below read it.  Order: stem + max-pool, stem, cn_conv16 (fp32 / f32s),
+// cn_offconv, LDS-halo 3x3 / s1, persistent 3x3 / s2, cn_proj 1x1, implicit GEMM.
+enum { R_NONE = 0, R_STEM_POOL, R_STEM, R_CONV16, R_CONV16S, R_OFFCONV, R_HALO, R_S2P, R_PROJ, R_IGEMM };
+struct ConvRoute {
+    int route;      // R_NONE: CN_ERR_UNSUPPORTED
+    int cls;        // N tile of the layer: 2 = 128 wide, 1 = 64, 0 = 32
+    bool bm64;      // implicit GEMM: 64-pixel tiles
+    int want;       // K slices the layer wants (needs a workspace of want * M * cout_pad floats)
+    int ksplit;     // ... and gets: `want` if the workspace holds them, else 1
+};
+
+// 16 input channels, <= 32 output channels, 3x3 / pad 1 (DLA level0 / level1): the layers cn_conv16.hip is for
+static bool conv16_shape(const ConvCall &c)
+{
+    return c.Cin == 16 && c.Cout <= 32 && c.KH == 3 && c.KW == 3 && c.pad_h == 1 && c.pad_w == 1 && c.dil == 1 &&
+           c.plain_geo && !c.stem && !c.out_nchw &&
+           (c.dtype == CN_DTYPE_F32 || (c.dtype == CN_DTYPE_F32S && c.in_plain && c.out_plain));
+}
+
+// The facts that come with pointers are inputs: c.vec_out, has_res / has_scale, and ws_bytes, the size of an
+// aligned workspace (0 = none).  Nothing here reads c.x .. c.y, c.ksplit or c.partial.
+static ConvRoute conv_route(const ConvCall &c, bool has_res, bool has_scale, size_t ws_bytes)
+{
+    ConvRoute r = {};
+    r.want = r.ksplit = 1;
+    const bool f16 = c.dtype == CN_DTYPE_F16, f32s = c.dtype == CN_DTYPE_F32S;
+    // 128-wide N tiles unless their padding wastes a whole 64-wide tile (e.g. Cout = 192)
+    const int waste128 = cn_cdiv(c.Cout, 128) * 128 - c.Cout;
+    const int waste64 = cn_cdiv(c.Cout, 64) * 64 - c.Cout;
+    const bool narrow = !cn_knobs.narrow && (waste128 - waste64 >= 64);
+    r.cls = (c.Cout > 64 && !narrow) ? 2 : (c.Cout > 32 ? 1 : 0);
+    // the stem reads the fp32 image and keeps fp32 packed weights; CN_CONV_STEM_F32S asks the
+    // persistent stem kernel for f32s arithmetic (split inside the kernel), output plain fp32
+    if (f32s && c.stem) return r;
+    if (c.out_nchw) {   // 128-pixel tiles, never split
+        r.route = (has_res || c.stem) ? R_NONE : R_IGEMM;
+        return r;
+    }
+    if (c.stem) {
+        // LDS-window kernels (cn_stem.hip) when they take the shape; else generic
+        const bool square = c.pad_h == c.pad_w && c.dil == 1;
+        if (f16)
+            r.route = R_IGEMM;
+        else if (c.stem_pool)   // y is the max-pooled map (B, Ho/2, Wo/2): only the fused f32s kernel produces it
+            r.route = (c.stem_f32s && !has_res && square && cn_stem_pool_rows(c) > 0) ? R_STEM_POOL : R_NONE;
+        else
+            r.route = (!cn_knobs.nostem && square && c.plain_geo && cn_stem_form(c, cn_knobs.stem_persist)) ? R_STEM
+                                                                                                        : R_IGEMM;
+        return r;
+    }
+    const int M = c.B * c.Ho * c.Wo;
+    // fewer than four workgroups per CU with 128-pixel tiles: halve the pixel tile
+    const long wgs128 = (long)cn_cdiv(M, 128) * cn_cdiv(c.Cout, 128);
+    // ... unless the 128-pixel grid is exactly one round of two workgroups per CU (512): then the
+    // 64-pixel grid (1024 at three per CU = 1.33 rounds) loses (128->256/s2@32^2: 0.210 -> 0.183 ms)
+    r.bm64 = (r.cls == 2) && (cn_knobs.bm ? (cn_knobs.bm == 64) : (wgs128 < 1024 && wgs128 != 512));
+    // split-K for under-filled grids (needs the caller's workspace; skipped without it)
+    if (!cn_knobs.nosplit)
+        r.want = plan_ksplit(M, c.Cout, c.KH * c.KW * c.nchunk, r.bm64 ? 64 : 128,
+                             r.cls == 2 ? 128 : (r.cls == 1 ? 64 : 32));
+    if (r.want > 1 && ws_bytes >= (size_t)r.want * M * c.cout_pad * sizeof(float)) r.ksplit = r.want;
+    const bool is3x3 = c.KH == 3 && c.KW == 3 && c.pad_h == 1 && c.pad_w == 1 && c.dil == 1 && c.plain_geo;
+    const bool f32s_packed = f32s && !c.in_plain && !c.res_plain && !has_res && has_scale && c.vec_out;
+    if (!cn_knobs.nohalo && !has_res && r.ksplit == 1 && conv16_shape(c) && cn_conv16_takes(c))
+        r.route = f32s ? R_CONV16S : R_CONV16;
+    // <= 32 output channels on a plain fp32 tensor, plain output (the offset / mask convolution of the deformable
+    // modules): cn_offconv.hip, with or without the K split
+    else if (f32s && c.in_plain && c.out_plain && !has_res && is3x3 && c.stride == 1 && c.vec_out &&
+             cn_offconv_takes(c, r.ksplit))
+        r.route = R_OFFCONV;
+    // 3x3 / stride 1 / pad 1: the LDS-halo kernel (cn_conv3x3.hip) unless split-K applies
+    else if (!cn_knobs.nohalo && r.ksplit == 1 && is3x3 && c.stride == 1)
+        r.route = R_HALO;
+    // a residual at its own pixel pitch (channel slices of wider tensors): only the 3x3 / s1 kernels
+    else if (has_res && c.res_pitch != c.out_pitch)
+        r.route = R_NONE;
+    // 3x3 / stride 2 / pad 1, f32s tensors on both sides: the persistent kernel's parity-plane form
+    else if (!cn_knobs.nohalo && f32s_packed && is3x3 && c.stride == 2 && cn_conv3x3s2p_takes(c))
+        r.route = R_S2P;
+    // 1x1 (stride 1 or 2), f32s tensors, no residual -- the `downsample` projections: the direct-fragment kernel
+    // (cn_proj.hip), bound by the layer's HBM bytes instead of the implicit GEMM's fixed costs
+    else if (f32s_packed && c.KH == 1 && c.KW == 1 && c.pad_h == 0 && c.pad_w == 0 && c.dil == 1 && c.plain_geo &&
+             c.Ho == (c.H - 1) / c.stride + 1 && c.Wo == (c.W - 1) / c.stride + 1 && cn_proj1x1_takes(c))
+        r.route = R_PROJ;
+    else
+        r.route = R_IGEMM;
+    return r;
+}
+
+static bool route_query(const cn_conv_desc *d, ConvCall &c) { return d && conv_fill(d, c) == CN_OK; }
+
+// Does cn_conv2d honour d->res_pitch != d->out_pitch?  Only the LDS-halo kernel does.  The caller passes the
+// workspace its query asked for, so a layer that wants split-K gets it and stays on the implicit-GEMM kernel.
+// (The 16-channel layers answer 0 although, with a residual, they run on the halo kernel: kept as it was.)
+extern "C" int cn_conv2d_res_pitch_supported(const cn_conv_desc *d)
+{
+    ConvCall c;
+    if (!route_query(d, c)) return 0;
+    return conv_route(c, true, true, SIZE_MAX).route == R_HALO && !conv16_shape(c);
 }
 
 extern "C" size_t cn_conv2d_workspace_bytes(const cn_conv_desc *d)
 {
-    IgemmArgs a = {};
-    if (!d || conv_fill_args(d, &a) != CN_OK) return 0;
-    const int s = dense_ksplit(d, a);
-    return s > 1 ? (size_t)s * a.M * a.cout_pad * sizeof(float) : 0;
+    ConvCall c;
+    if (!route_query(d, c)) return 0;
+    const int s = conv_route(c, false, true, 0).want;
+    return s > 1 ? (size_t)s * c.B * c.Ho * c.Wo * c.cout_pad * sizeof(float) : 0;
+}
+
+extern "C" int cn_stem_maxpool_supported(const cn_conv_desc *d)
+{
+    ConvCall c;
+    if (!route_query(d, c)) return 0;
+    c.stem_f32s = c.stem_pool = 1;   // the question: would these flags be accepted
+    return conv_route(c, false, true, 0).route == R_STEM_POOL;
+}
+
+// Will cn_conv2d honour CN_CONV_STEM_F32S for this stem descriptor?
+extern "C" int cn_stem_f32s_supported(const cn_conv_desc *d)
+{
+    ConvCall c;
+    if (!route_query(d, c)) return 0;
+    c.stem_f32s = 1;
+    const int route = conv_route(c, false, true, 0).route;
+    if (route != R_STEM) return route == R_STEM_POOL;
+    const int form = cn_stem_form(c, cn_knobs.stem_persist);
+    return form == CN_STEM_PERSIST_F32S || form == CN_STEM_16S;
 }
 
 extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_packed,
@@ -1173,183 +1323,44 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
 {
     if (!d || !x || !w_packed || !y) return CN_ERR_NULL;
     if (!cn_aligned16(x) || !cn_aligned16(w_packed)) return CN_ERR_ALIGN;
-    IgemmArgs a = {};
-    int rc = conv_fill_args(d, &a);
+    ConvCall c;
+    int rc = conv_fill(d, c);
     if (rc != CN_OK) return rc;
-    a.x = x; a.w = w_packed; a.bias = nullptr; a.scale = scale; a.shift = shift;
-    a.residual = residual; a.y = y; a.om = nullptr;
-    set_ctl(a, &d->ctl);
+    c.x = x; c.w = w_packed; c.scale = scale; c.shift = shift; c.residual = residual; c.y = y;
     if (d->dtype == CN_DTYPE_F32S) {
-        if (d->in_layout == CN_LAYOUT_NHWC && !(d->flags & CN_CONV_X_PLAIN) && !aligned128(x)) return CN_ERR_ALIGN;
-        if (d->out_layout == CN_LAYOUT_NHWC && !(d->flags & CN_CONV_Y_PLAIN) && !aligned128(y)) return CN_ERR_ALIGN;
-        if (residual && !(d->flags & CN_CONV_R_PLAIN) && !aligned128(residual)) return CN_ERR_ALIGN;
+        if (!c.stem && !c.in_plain && !aligned128(x)) return CN_ERR_ALIGN;
+        if (!c.out_nchw && !c.out_plain && !aligned128(y)) return CN_ERR_ALIGN;
+        if (residual && !c.res_plain && !aligned128(residual)) return CN_ERR_ALIGN;
     }
-    const bool f16 = (d->dtype == CN_DTYPE_F16);
-    const size_t valign = f16 ? 8 : 16;  // 4 output elements per store
-    a.vec_out = (d->out_layout == CN_LAYOUT_NHWC && (d->out_pitch & 3) == 0 &&
-                 (((uintptr_t)y) % valign) == 0 &&
-                 (!residual || (((uintptr_t)residual) % valign) == 0)) ? 1 : 0;
+    const size_t valign = d->dtype == CN_DTYPE_F16 ? 8 : 16;  // 4 output elements per store
+    c.vec_out = (!c.out_nchw && (d->out_pitch & 3) == 0 && (((uintptr_t)y) % valign) == 0 &&
+                 (!residual || ((((uintptr_t)residual) % valign) == 0 && (c.res_pitch & 3) == 0))) ? 1 : 0;
+    const ConvRoute r = conv_route(c, residual != nullptr, scale != nullptr,
+                                   (workspace && cn_aligned16(workspace)) ? workspace_bytes : 0);
+    c.ksplit = r.ksplit;
+    c.partial = r.ksplit > 1 ? (float *)workspace : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    const bool stem = is_stem(d->Cin, d->in_layout);
-    const bool f32s = (d->dtype == CN_DTYPE_F32S);
-    int cls;
-    bool bm64;
-    dense_tile_class(d, a, &cls, &bm64);
-    // split-K for under-filled grids (needs the caller's workspace; skipped without it)
-    a.ksplit = 1;
-    a.in_plain = (d->flags & CN_CONV_X_PLAIN) ? 1 : 0;
-    a.out_plain = (d->flags & CN_CONV_Y_PLAIN) ? 1 : 0;
-    a.res_plain = (d->flags & CN_CONV_R_PLAIN) ? 1 : 0;
-    const int want = dense_ksplit(d, a);
-    if (want > 1 && workspace && cn_aligned16(workspace) &&
-        workspace_bytes >= (size_t)want * a.M * a.cout_pad * sizeof(float)) {
-        a.ksplit = want;
-        a.partial = (float *)workspace;
+    switch (r.route) {
+    case R_STEM_POOL: return cn_stem_pool_f32s(c, st);
+    case R_STEM: return cn_stem_conv_f32(c, cn_knobs.stem_persist, st);
+    case R_CONV16: return cn_conv3x3_c16(c, st);
+    case R_CONV16S: return cn_conv3x3_c16s(c, st);
+    case R_HALO: return cn_conv3x3s1(c, r.cls, st);
+    case R_S2P: return cn_conv3x3s2_persist(c, st);
+    case R_PROJ: return cn_proj1x1_f32s(c, st);
+    case R_OFFCONV:   // its K split ends in the implicit GEMM's second stage
+        rc = cn_offconv_f32s(c, st);
+        if (rc != CN_OK || c.ksplit == 1) return rc;
+        return launch_splitk_reduce(c.dtype, igemm_args(c, d), 8192, st);
+    case R_IGEMM: break;
+    default: return CN_ERR_UNSUPPORTED;
     }
-    // the stem reads the fp32 image and keeps fp32 packed weights; CN_CONV_STEM_F32S asks the
-    // persistent stem kernel for f32s arithmetic (split inside the kernel), output plain fp32
-    if (f32s && stem) return CN_ERR_UNSUPPORTED;
-    if (d->out_layout == CN_LAYOUT_NCHW) {
-        if (residual || stem) return CN_ERR_UNSUPPORTED;
-        if (f32s) {
-            if (cls == 2) return launch_igemm_s<128, 128, 2, 2, A_DENSE, true>(a, st);
-            if (cls == 1) return launch_igemm_s<128, 64, 2, 2, A_DENSE, true>(a, st);
-            return launch_igemm_s<128, 32, 4, 1, A_DENSE, true>(a, st);
-        }
-        if (f16) {
-            if (cls == 2) return launch_igemm_h<128, 128, 2, 2, A_DENSE, true>(a, st);
-            if (cls == 1) return launch_igemm_h<128, 64, 2, 2, A_DENSE, true>(a, st);
-            return launch_igemm_h<128, 32, 4, 1, A_DENSE, true>(a, st);
-        }
-        if (cls == 2) return launch_igemm<128, 128, 2, 2, A_DENSE, true>(a, st);
-        if (cls == 1) return launch_igemm<128, 64, 2, 2, A_DENSE, true>(a, st);
-        return launch_igemm<128, 32, 4, 1, A_DENSE, true>(a, st);
-    }
-    if (stem) {
-        if (f16) {
-            if (d->Cout > 64) return launch_igemm_h<128, 128, 2, 2, A_STEM, false>(a, st);
-            if (d->Cout > 32) return launch_igemm_h<128, 64, 2, 2, A_STEM, false>(a, st);
-            return launch_igemm_h<128, 32, 4, 1, A_STEM, false>(a, st);
-        }
-        // LDS-window kernel (cn_stem.hip) when the tile's input window fits; else generic
-        if (d->flags & CN_CONV_STEM_MAXPOOL) {
-            // y is the max-pooled map (B, Ho/2, Wo/2): only the fused f32s kernel produces it
-            if (!(d->flags & CN_CONV_STEM_F32S) || residual || d->pad_h != d->pad_w || d->dil != 1)
-                return CN_ERR_UNSUPPORTED;
-            return cn_stem_pool_f32s((const float *)x, (const float *)w_packed, scale, shift,
-                                     (float *)y, d->B, d->H, d->W, d->Ho, d->Wo, d->Cout, d->KH,
-                                     d->KW, d->stride, d->pad_h, d->relu, d->out_pitch, a.cin_pad,
-                                     (d->flags & CN_CONV_STEM_Y_F32S) ? 1 : 0, &d->ctl, st);
-        }
-        if (!cn_knobs.nostem && d->pad_h == d->pad_w && d->dil == 1 && d->oy_mul == 1 &&
-            d->ox_mul == 1 && d->OH == d->Ho && d->OW == d->Wo) {
-            rc = cn_stem_conv_f32((const float *)x, (const float *)w_packed, scale, shift,
-                                  (float *)y, d->B, d->H, d->W, d->Ho, d->Wo, d->Cout, d->KH,
-                                  d->KW, d->stride, d->pad_h, d->relu, d->out_pitch, a.cin_pad,
-                                  cn_knobs.stem_persist | ((d->flags & CN_CONV_STEM_F32S) ? 2 : 0), &d->ctl, st);
-            if (rc != CN_ERR_UNSUPPORTED) return rc;
-        }
-        if (d->Cout > 64) return launch_igemm<128, 128, 2, 2, A_STEM, false>(a, st);
-        if (d->Cout > 32) return launch_igemm<128, 64, 2, 2, A_STEM, false>(a, st);
-        return launch_igemm<128, 32, 4, 1, A_STEM, false>(a, st);
-    }
-    // 16-channel input, <= 32 output channels (DLA level0 / level1): cn_conv16.hip
-    if (!cn_knobs.nohalo && !f16 && !f32s && !residual && a.ksplit == 1 && d->Cin == 16 && d->Cout <= 32 &&
-        d->KH == 3 && d->KW == 3 && d->pad_h == 1 && d->pad_w == 1 && d->dil == 1 &&
-        d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 && d->ox_add == 0 && d->OH == d->Ho &&
-        d->OW == d->Wo && d->in_layout == CN_LAYOUT_NHWC) {
-        rc = cn_conv3x3_c16((const float *)x, (const float *)w_packed, scale, shift, (float *)y, d->B,
-                            d->H, d->W, d->Ho, d->Wo, d->Cin, d->Cout, d->stride, d->in_pitch,
-                            d->out_pitch, d->relu, st);
-        if (rc != CN_ERR_UNSUPPORTED) return rc;
-    }
-    // the same layers in f32s arithmetic: plain input split while staged, plain output (cn_conv16.hip)
-    if (!cn_knobs.nohalo && f32s && (d->flags & CN_CONV_X_PLAIN) && (d->flags & CN_CONV_Y_PLAIN) && !residual &&
-        a.ksplit == 1 && d->Cin == 16 && d->Cout <= 32 && d->KH == 3 && d->KW == 3 && d->pad_h == 1 &&
-        d->pad_w == 1 && d->dil == 1 && d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 &&
-        d->ox_add == 0 && d->OH == d->Ho && d->OW == d->Wo && d->in_layout == CN_LAYOUT_NHWC) {
-        rc = cn_conv3x3_c16s((const float *)x, w_packed, scale, shift, (float *)y, d->B, d->H, d->W,
-                             d->Ho, d->Wo, d->Cin, d->Cout, d->stride, d->in_pitch, d->out_pitch,
-                             d->relu, &d->ctl, st);
-        if (rc != CN_ERR_UNSUPPORTED) return rc;
-    }
-    // <= 32 output channels on a plain fp32 tensor, plain output (the offset / mask convolution of the deformable
-    // modules): cn_offconv.hip, with or without the K split
-    if (f32s && (d->flags & CN_CONV_X_PLAIN) && (d->flags & CN_CONV_Y_PLAIN) && !residual && is_3x3s1(d) &&
-        d->in_layout == CN_LAYOUT_NHWC && d->out_layout == CN_LAYOUT_NHWC && a.vec_out &&
-        cn_offconv_takes(d->B, d->H, d->W, d->Cin, d->Cout, d->in_pitch, d->out_pitch, a.ksplit)) {
-        rc = cn_offconv_f32s((const float *)x, w_packed, scale, shift, (float *)y, d->B, d->H, d->W, d->Cin, d->Cout,
-                             d->out_pitch, d->relu, &d->ctl, a.ksplit, a.partial, st);
-        if (rc != CN_OK || a.ksplit == 1) return rc;
-        const size_t tot = (size_t)a.M * (a.cout_pad >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel<cn_f32s>, dim3((unsigned)((tot + 255) / 256 < 8192 ? (tot + 255) / 256 : 8192)),
-                           dim3(256), 0, st, a);
-        CN_CHECK_LAUNCH();
-        return CN_OK;
-    }
-    // 3x3 / stride 1 / pad 1: the LDS-halo kernel (cn_conv3x3.hip) unless split-K applies
-    const int res_pitch = d->res_pitch > 0 ? d->res_pitch : d->out_pitch;
-    const bool to_halo = !cn_knobs.nohalo && a.ksplit == 1 && is_3x3s1(d);
-    // a residual at its own pixel pitch (channel slices of wider tensors): only the 3x3 / s1 kernels
-    if (residual && res_pitch != d->out_pitch && !to_halo) return CN_ERR_UNSUPPORTED;
-    if (to_halo)
-        return cn_conv3x3s1(x, w_packed, scale, shift, residual, y, d->B, d->H, d->W, d->Cin,
-                            d->Cout, d->in_pitch, d->out_pitch, res_pitch, d->relu, a.vec_out, cls, d->dtype, d->flags,
-                            &d->ctl, st);
-    // 3x3 / stride 2 / pad 1, f32s tensors on both sides: the persistent kernel's parity-plane form
-    if (!cn_knobs.nohalo && f32s && !(d->flags & (CN_CONV_X_PLAIN | CN_CONV_R_PLAIN)) && !residual && scale &&
-        a.vec_out && d->KH == 3 && d->KW == 3 && d->stride == 2 && d->pad_h == 1 && d->pad_w == 1 && d->dil == 1 &&
-        d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 && d->ox_add == 0 && d->OH == d->Ho && d->OW == d->Wo &&
-        d->in_layout == CN_LAYOUT_NHWC && d->out_layout == CN_LAYOUT_NHWC &&
-        cn_conv3x3s2p_takes(d->B, d->H, d->W, d->Cin, d->Cout, d->in_pitch, d->out_pitch))
-        return cn_conv3x3s2_persist(x, w_packed, scale, shift, y, d->B, d->H, d->W, d->Cin, d->Cout, d->in_pitch,
-                                    d->out_pitch, d->relu, (d->flags & CN_CONV_Y_PLAIN) ? 1 : 0, &d->ctl, st);
-    // 1x1 (stride 1 or 2), f32s tensors, no residual -- the `downsample` projections: the direct-fragment kernel
-    // (cn_proj.hip), bound by the layer's HBM bytes instead of the implicit GEMM's fixed costs
-    if (f32s && !(d->flags & (CN_CONV_X_PLAIN | CN_CONV_R_PLAIN)) && !residual && scale && a.vec_out && d->KH == 1 &&
-        d->KW == 1 && d->pad_h == 0 && d->pad_w == 0 && d->dil == 1 && d->oy_mul == 1 && d->ox_mul == 1 &&
-        d->oy_add == 0 && d->ox_add == 0 && d->OH == d->Ho && d->OW == d->Wo && d->in_layout == CN_LAYOUT_NHWC &&
-        d->out_layout == CN_LAYOUT_NHWC && d->Ho == (d->H - 1) / d->stride + 1 && d->Wo == (d->W - 1) / d->stride + 1 &&
-        cn_proj1x1_takes(d->B, d->H, d->W, d->Cin, d->Cout, d->stride, d->in_pitch, d->out_pitch))
-        return cn_proj1x1_f32s(x, w_packed, scale, shift, y, d->B, d->H, d->W, d->Cin, d->Cout, d->stride, d->in_pitch,
-                               d->out_pitch, d->relu, (d->flags & CN_CONV_Y_PLAIN) ? 1 : 0, &d->ctl, st);
-    if (f32s) {
-        if (cls == 2)
-            rc = bm64 ? launch_igemm_s<64, 128, 2, 2, A_DENSE, false>(a, st)
-                      : launch_igemm_s<128, 128, 2, 2, A_DENSE, false>(a, st);
-        else if (cls == 1)
-            rc = launch_igemm_s<128, 64, 2, 2, A_DENSE, false>(a, st);
-        else
-            rc = launch_igemm_s<128, 32, 4, 1, A_DENSE, false>(a, st);
-    } else if (f16) {
-        if (cls == 2)
-            rc = bm64 ? launch_igemm_h<64, 128, 2, 2, A_DENSE, false>(a, st)
-                      : launch_igemm_h<128, 128, 2, 2, A_DENSE, false>(a, st);
-        else if (cls == 1)
-            rc = launch_igemm_h<128, 64, 2, 2, A_DENSE, false>(a, st);
-        else
-            rc = launch_igemm_h<128, 32, 4, 1, A_DENSE, false>(a, st);
-    } else {
-        if (cls == 2)
-            rc = bm64 ? launch_igemm<64, 128, 2, 2, A_DENSE, false>(a, st)
-                      : launch_igemm<128, 128, 2, 2, A_DENSE, false>(a, st);
-        else if (cls == 1)
-            rc = launch_igemm<128, 64, 2, 2, A_DENSE, false>(a, st);
-        else
-            rc = launch_igemm<128, 32, 4, 1, A_DENSE, false>(a, st);
-    }
-    if (rc != CN_OK || a.ksplit == 1) return rc;
-    const size_t total = (size_t)a.M * (a.cout_pad >> 2);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    if (f32s)
-        hipLaunchKernelGGL(splitk_reduce_kernel<cn_f32s>, dim3(blocks), dim3(256), 0, st, a);
-    else if (f16)
-        hipLaunchKernelGGL(splitk_reduce_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, a);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    const IgemmArgs a = igemm_args(c, d);
+    if (c.out_nchw) return igemm_dispatch<A_DENSE, true>(c.dtype, r.cls, false, a, st);
+    if (c.stem) return igemm_dispatch<A_STEM, false>(c.dtype, cout_class(c.Cout), false, a, st);
+    rc = igemm_dispatch<A_DENSE, false>(c.dtype, r.cls, r.bm64, a, st);
+    if (rc != CN_OK || c.ksplit == 1) return rc;
+    return launch_splitk_reduce(c.dtype, a, 8192, st);
 }
 
 extern "C" int cn_conv2d_f32(const cn_conv_desc *d, const float *x, const float *w_packed,
@@ -1451,11 +1462,7 @@ extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weigh
             r.OH = H; r.OW = W; r.oy_mul = 1; r.oy_add = 0; r.ox_mul = 1; r.ox_add = 0;
             r.relu = relu; r.M = B * H * W; r.cout_pad = round_up(Cout, 32);
             r.ksplit = ks; r.partial = (float *)workspace;
-            const size_t tot = (size_t)r.M * (r.cout_pad >> 2);
-            const int nb = (int)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
-            hipLaunchKernelGGL(splitk_reduce_kernel<cn_f32s>, dim3(nb), dim3(256), 0, (hipStream_t)stream, r);
-            CN_CHECK_LAUNCH();
-            return CN_OK;
+            return launch_splitk_reduce(CN_DTYPE_F32S, r, 4096, (hipStream_t)stream);
         }
         if (rc != CN_ERR_UNSUPPORTED) return rc;
     }
@@ -1481,8 +1488,6 @@ extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weigh
     // tiles as pixel blocks (8 x 8, or 8 x 16 for the 128-pixel tiles of Cout <= 32) when the map
     // divides into them
     a.tile2d = (cn_knobs.dcn_tile2d && (W & 7) == 0 && (H % (Cout > 32 ? 8 : 16)) == 0) ? 1 : 0;
-    // 64-pixel tiles: 128-pixel tiles were measured slower at every CenterNet shape
-    // (tools/bench_dcn.py) and are no longer built
     // tap split (needs the caller's workspace; without one the layer runs unsplit)
     a.ksplit = 1;
     if (Cout > 32) {
@@ -1493,40 +1498,10 @@ extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weigh
             a.partial = (float *)workspace;
         }
     }
-    int rc;
-    const bool padk = (Cin & 31) != 0;
-    if (f32s) {
-        if (Cout > 64)
-            rc = padk ? launch_igemm_s<64, 128, 2, 2, A_DCN_PAD, false>(a, st)
-                      : launch_igemm_s<64, 128, 2, 2, A_DCN, false>(a, st);
-        else if (Cout > 32)
-            rc = padk ? launch_igemm_s<64, 64, 2, 2, A_DCN_PAD, false>(a, st)
-                      : launch_igemm_s<64, 64, 2, 2, A_DCN, false>(a, st);
-        else
-            rc = padk ? launch_igemm_s<128, 32, 4, 1, A_DCN_PAD, false>(a, st)
-                      : launch_igemm_s<128, 32, 4, 1, A_DCN, false>(a, st);
-        if (rc != CN_OK || a.ksplit == 1) return rc;
-        const size_t tot = (size_t)a.M * (a.cout_pad >> 2);
-        const int nb = (int)((tot + 255) / 256 < 4096 ? (tot + 255) / 256 : 4096);
-        hipLaunchKernelGGL(splitk_reduce_kernel<cn_f32s>, dim3(nb), dim3(256), 0, st, a);
-        CN_CHECK_LAUNCH();
-        return CN_OK;
-    }
-    if (Cout > 64)
-        rc = padk ? launch_igemm<64, 128, 2, 2, A_DCN_PAD, false>(a, st)
-                  : launch_igemm<64, 128, 2, 2, A_DCN, false>(a, st);
-    else if (Cout > 32)
-        rc = padk ? launch_igemm<64, 64, 2, 2, A_DCN_PAD, false>(a, st)
-                  : launch_igemm<64, 64, 2, 2, A_DCN, false>(a, st);
-    else
-        rc = padk ? launch_igemm<128, 32, 4, 1, A_DCN_PAD, false>(a, st)
-                  : launch_igemm<128, 32, 4, 1, A_DCN, false>(a, st);
+    const int rc = (Cin & 31) ? igemm_dispatch<A_DCN_PAD, false>(dtype, cout_class(Cout), false, a, st)
+                              : igemm_dispatch<A_DCN, false>(dtype, cout_class(Cout), false, a, st);
     if (rc != CN_OK || a.ksplit == 1) return rc;
-    const size_t total = (size_t)a.M * (a.cout_pad >> 2);
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, a);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    return launch_splitk_reduce(dtype, a, 4096, st);
 }
 
 // ---- ConvTranspose2d(kernel 4, stride 2, padding 1, no output padding) -----------------
@@ -1616,65 +1591,28 @@ extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, 
         return CN_ERR_ALIGN;
     if ((long)B * H * W * 4 * (long)out_pitch >= (1L << 31) || (long)B * H * W * (long)in_pitch >= (1L << 31))
         return CN_ERR_UNSUPPORTED;
-    IgemmArgs a = {};
-    set_ctl(a, ctl);
-    a.x = x_nhwc; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y_nhwc;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = H; a.Wo = W; a.Cout = Cout;
-    a.KH = 2; a.KW = 2; a.stride = 1; a.pad_h = 1; a.pad_w = 1; a.dil = 1;
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
-    a.OH = 2 * H; a.OW = 2 * W; a.oy_mul = 2; a.ox_mul = 2; a.oy_add = 0; a.ox_add = 0;
-    a.relu = relu;
-    a.M = B * H * W;
-    a.cin_pad = round_up(Cin, 32);
-    a.cout_pad = round_up(Cout, 32);
-    a.nchunk = a.cin_pad / 32;
-    a.KT = 4 * a.nchunk;
-    a.zparity = 1;
-    a.w_zstride = 4 * a.cout_pad * a.cin_pad;
-    a.vec_out = ((out_pitch & 3) == 0 && cn_aligned16(y_nhwc)) ? 1 : 0;
-    a.in_plain = (flags & CN_CONV_X_PLAIN) ? 1 : 0;
-    a.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
+    // the four parity classes as 2x2 convolutions over the input map (Ho x Wo = H x W)
+    ConvCall c = {};
+    c.x = x_nhwc; c.w = w_packed; c.scale = scale; c.shift = shift; c.y = y_nhwc;
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Ho = H; c.Wo = W; c.Cout = Cout;
+    c.KH = 2; c.KW = 2; c.stride = 1; c.pad_h = 1; c.pad_w = 1; c.dil = 1;
+    c.in_pitch = in_pitch; c.out_pitch = out_pitch; c.res_pitch = out_pitch;
+    c.relu = relu; c.dtype = dtype;
+    c.in_plain = (flags & CN_CONV_X_PLAIN) ? 1 : 0;
+    c.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
+    c.vec_out = ((out_pitch & 3) == 0 && cn_aligned16(y_nhwc)) ? 1 : 0;
+    c.ctl = ctl;
+    c.ksplit = 1;
+    c.cin_pad = round_up(Cin, 32); c.cout_pad = round_up(Cout, 32); c.nchunk = c.cin_pad / 32;
     hipStream_t st = (hipStream_t)stream;
     // LDS-halo form (cn_conv3x3.hip) unless disabled (cn_set_tuning key 10) or the tile would be
     // mostly padding (Cout <= 32)
-    if (!cn_knobs.nohalo && Cout > 32 && a.vec_out && (in_pitch & 3) == 0)
-        return cn_deconv4x4s2_halo(x_nhwc, w_packed, scale, shift, y_nhwc, B, H, W, Cin, Cout,
-                                   in_pitch, out_pitch, relu, a.vec_out, dtype, flags, ctl, st);
-    if (f32s) {
-        if (Cout > 64) return launch_igemm_s<128, 128, 2, 2, A_DENSE, false>(a, st);
-        if (Cout > 32) return launch_igemm_s<128, 64, 2, 2, A_DENSE, false>(a, st);
-        return launch_igemm_s<128, 32, 4, 1, A_DENSE, false>(a, st);
-    }
-    if (Cout > 64) return launch_igemm<128, 128, 2, 2, A_DENSE, false>(a, st);
-    if (Cout > 32) return launch_igemm<128, 64, 2, 2, A_DENSE, false>(a, st);
-    return launch_igemm<128, 32, 4, 1, A_DENSE, false>(a, st);
-}
-
-extern "C" int cn_stem_maxpool_supported(const cn_conv_desc *d)
-{
-    if (!d || !is_stem(d->Cin, d->in_layout) || d->out_layout != CN_LAYOUT_NHWC) return 0;
-    if (d->dtype != CN_DTYPE_F32 || d->pad_h != d->pad_w || d->dil != 1) return 0;
-    if (round_up(d->KH * d->KW * 3, 32) > STEM_KMAX) return 0;
-    return cn_stem_pool_rows(d->B, d->Ho, d->Wo, d->Cout, d->KH, d->KW, d->stride,
-                             round_up(d->KH * d->KW * 3, 32)) > 0;
-}
-
-// Will cn_conv2d honour CN_CONV_STEM_F32S for this stem descriptor (mirror of its dispatch)?
-extern "C" int cn_stem_f32s_supported(const cn_conv_desc *d)
-{
-    if (!d || !is_stem(d->Cin, d->in_layout) || d->out_layout != CN_LAYOUT_NHWC) return 0;
-    if (d->dtype != CN_DTYPE_F32 || d->pad_h != d->pad_w || d->dil != 1) return 0;
-    const int kp = round_up(d->KH * d->KW * 3, 32);
-    if (kp > STEM_KMAX) return 0;
-    if (d->flags & CN_CONV_STEM_MAXPOOL) return cn_stem_maxpool_supported(d);
-    if (cn_knobs.nostem || !cn_knobs.stem_persist) return 0;
-    if (d->oy_mul != 1 || d->ox_mul != 1 || d->OH != d->Ho || d->OW != d->Wo) return 0;
-    // cn_stem_conv_f32: persistent 7x7 window kernel, rows of whole 128-pixel tiles, stride 2,
-    // more than 16 output channels
-    if (d->KH != 7 || d->KW != 7 || d->Wo % 128 != 0) return 0;
-    if (d->stride == 2 && d->Cout > 16) return 1;
-    // stem16s_kernel: stride 1, pad 3, <= 16 output channels (DLA base_layer)
-    return (d->stride == 1 && d->Cout <= 16 && d->pad_h == 3 && (d->W & 3) == 0 && cn_knobs.stem16s) ? 1 : 0;
+    if (!cn_knobs.nohalo && Cout > 32 && c.vec_out) return cn_deconv4x4s2_halo(c, st);
+    IgemmArgs a = igemm_args(c, nullptr);
+    a.OH = 2 * H; a.OW = 2 * W; a.oy_mul = 2; a.ox_mul = 2;
+    a.zparity = 1;   // blockIdx.z = parity class
+    a.w_zstride = 4 * a.cout_pad * a.cin_pad;
+    return igemm_dispatch<A_DENSE, false>(dtype, cout_class(Cout), false, a, st);
 }
 
 // ---- cn_set_tuning / cn_get_tuning / cn_reset_tuning: lookups in CN_TUNING_KEYS (cn_tuning.h)

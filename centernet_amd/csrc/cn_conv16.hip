@@ -342,46 +342,49 @@ int launch_c16s(const C16sArgs &a, int B, hipStream_t st)
 
 }  // namespace
 
-// Returns CN_ERR_UNSUPPORTED when the layer is not of this form (the caller then takes the
-// LDS-halo / generic kernels).
-int cn_conv3x3_c16(const float *x, const float *w_packed, const float *scale, const float *shift,
-                   float *y, int B, int H, int W, int Ho, int Wo, int Cin, int Cout, int stride,
-                   int in_pitch, int out_pitch, int relu, hipStream_t st)
+// Is the layer of this file's form?  (the caller has checked: 3x3 / pad 1 / dilation 1, NHWC both sides, no
+// residual; fp32 tensors, or f32s arithmetic with plain input and plain output)
+bool cn_conv16_takes(const ConvCall &c)
 {
-    if (Cin != CI || Cout > 32 || (stride != 1 && stride != 2) || Wo % BM != 0 || (in_pitch & 3))
-        return CN_ERR_UNSUPPORTED;
-    if (Ho != (H + 2 - 3) / stride + 1 || Wo != (W + 2 - 3) / stride + 1) return CN_ERR_UNSUPPORTED;
-    if ((long)H * W * in_pitch >= (1L << 29)) return CN_ERR_UNSUPPORTED;  // 32-bit byte offsets per image
-    C16Args a;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y;
-    a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.cout_pad = (Cout + 31) / 32 * 32;
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch; a.relu = relu;
-    if (Cout <= 16)
-        return stride == 1 ? launch_c16<1, 1>(a, B, st) : launch_c16<1, 2>(a, B, st);
-    return stride == 1 ? launch_c16<2, 1>(a, B, st) : launch_c16<2, 2>(a, B, st);
+    if (c.Cin != CI || c.Cout > 32 || (c.stride != 1 && c.stride != 2) || c.Wo % BM != 0 || (c.in_pitch & 3))
+        return false;
+    if (c.Ho != (c.H + 2 - 3) / c.stride + 1 || c.Wo != (c.W + 2 - 3) / c.stride + 1) return false;
+    if ((long)c.H * c.W * c.in_pitch >= (1L << 29)) return false;  // 32-bit byte offsets per image
+    // f32s, stride 2 (level1) was measured slower in this form than on the fp32 kernel (0.476 vs 0.245 ms:
+    // a 257-column window = 52 staging registers next to 80 fragment + 80 weight registers, 2-way
+    // bank conflicts at the 64-byte pixel stride): not built
+    return c.dtype == CN_DTYPE_F32 || c.stride == 1;
+}
+
+template <typename Args>
+static Args c16_args(const ConvCall &c)
+{
+    Args a;
+    a.x = (const float *)c.x; a.scale = c.scale; a.shift = c.shift; a.y = (float *)c.y;
+    a.H = c.H; a.W = c.W; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout = c.Cout; a.cout_pad = c.cout_pad;
+    a.in_pitch = c.in_pitch; a.out_pitch = c.out_pitch; a.relu = c.relu;
+    return a;
+}
+
+int cn_conv3x3_c16(const ConvCall &c, hipStream_t st)
+{
+    if (!cn_conv16_takes(c)) return CN_ERR_UNSUPPORTED;
+    C16Args a = c16_args<C16Args>(c);
+    a.w = (const float *)c.w;
+    if (c.Cout <= 16)
+        return c.stride == 1 ? launch_c16<1, 1>(a, c.B, st) : launch_c16<1, 2>(a, c.B, st);
+    return c.stride == 1 ? launch_c16<2, 1>(a, c.B, st) : launch_c16<2, 2>(a, c.B, st);
 }
 
 // f32s form: plain fp32 input (split while it is staged: ctl->x_mul, range word side 1), f32s-packed
 // weight (cn_pack_conv_weight, CN_DTYPE_F32S: 128-byte groups, channels 16..31 zero), plain fp32
-// output.  Stride 1 only (see below).
-int cn_conv3x3_c16s(const float *x, const void *w_packed, const float *scale, const float *shift,
-                    float *y, int B, int H, int W, int Ho, int Wo, int Cin, int Cout, int stride,
-                    int in_pitch, int out_pitch, int relu, const cn_f32s_ctl *ctl, hipStream_t st)
+// output.  Stride 1 only (cn_conv16_takes).
+int cn_conv3x3_c16s(const ConvCall &c, hipStream_t st)
 {
-    if (Cin != CI || Cout > 32 || (stride != 1 && stride != 2) || Wo % BM != 0 || (in_pitch & 3))
-        return CN_ERR_UNSUPPORTED;
-    if (Ho != (H + 2 - 3) / stride + 1 || Wo != (W + 2 - 3) / stride + 1) return CN_ERR_UNSUPPORTED;
-    if ((long)H * W * in_pitch >= (1L << 29)) return CN_ERR_UNSUPPORTED;  // 32-bit byte offsets per image
-    if (!cn_aligned16(x) || !cn_aligned16(w_packed)) return CN_ERR_UNSUPPORTED;
-    C16sArgs a;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y;
-    a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.cout_pad = (Cout + 31) / 32 * 32;
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch; a.relu = relu;
-    a.x_mul = (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f;
-    a.range = ctl ? ctl->range : nullptr;
-    // stride 2 (level1) was measured slower in this form than on the fp32 kernel (0.476 vs 0.245 ms:
-    // a 257-column window = 52 staging registers next to 80 fragment + 80 weight registers, 2-way
-    // bank conflicts at the 64-byte pixel stride): not built
-    if (stride != 1) return CN_ERR_UNSUPPORTED;
-    return Cout <= 16 ? launch_c16s<1, 1>(a, B, st) : launch_c16s<2, 1>(a, B, st);
+    if (!cn_conv16_takes(c)) return CN_ERR_UNSUPPORTED;
+    C16sArgs a = c16_args<C16sArgs>(c);
+    a.w = c.w;
+    a.x_mul = (c.ctl && c.ctl->x_mul != 0.f) ? c.ctl->x_mul : 1.f;
+    a.range = c.ctl ? c.ctl->range : nullptr;
+    return c.Cout <= 16 ? launch_c16s<1, 1>(a, c.B, st) : launch_c16s<2, 1>(a, c.B, st);
 }

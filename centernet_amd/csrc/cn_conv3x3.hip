@@ -991,7 +991,7 @@ __device__ __forceinline__ void conv3x3s1_body(const C3Args &a, const C3Heads &h
                                                      a.res_pitch, n);
                     else
                         res[k] = c3_load4(reinterpret_cast<const T *>(a.residual) +
-                                          (size_t)(offs[k] >= 0 ? offs[k] : 0) * a.out_pitch + n);
+                                          (size_t)(offs[k] >= 0 ? offs[k] : 0) * a.res_pitch + n);
                 }
             }
         }
@@ -1055,7 +1055,7 @@ __device__ __forceinline__ void conv3x3s1_body(const C3Args &a, const C3Heads &h
                             cn_store1_f32s(a.y, (size_t)off, a.out_pitch, n + e, t);
                         }
                     } else {
-                        if (a.residual) t += (float)reinterpret_cast<const T *>(a.residual)[o];
+                        if (a.residual) t += (float)reinterpret_cast<const T *>(a.residual)[(size_t)off * a.res_pitch + n + e];
                         reinterpret_cast<T *>(a.y)[o] = (T)(a.relu ? fmaxf(t, 0.f) : t);
                     }
                 }
@@ -1272,40 +1272,36 @@ static void c3_set_ctl(C3Args &a, const cn_f32s_ctl *ctl)
     a.range = ctl ? ctl->range : nullptr;
 }
 
-// (fp16 tensors: fp32 accumulate, scale / shift fp32)
-int cn_conv3x3s1(const void *x, const void *w_packed, const float *scale, const float *shift,
-                 const void *residual, void *y, int B, int H, int W, int Cin, int Cout,
-                 int in_pitch, int out_pitch, int res_pitch, int relu, int vec_out, int bn_class,
-                 int dtype, int flags, const cn_f32s_ctl *ctl, hipStream_t st)
+// what cn_conv3x3s1 and cn_deconv4x4s2_halo share (fp16: 64-channel chunks, ConvCall's)
+static void c3_fill(C3Args &a, const ConvCall &c)
 {
-    if (res_pitch <= 0) res_pitch = out_pitch;
+    c3_set_ctl(a, c.ctl);
+    a.x = c.x; a.w = c.w; a.scale = c.scale; a.shift = c.shift; a.residual = c.residual; a.y = c.y;
+    a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout; a.in_pitch = c.in_pitch;
+    a.out_pitch = c.out_pitch; a.relu = c.relu; a.vec_out = c.vec_out; a.setprio = cn_knobs.setprio;
+    a.res_pitch = c.res_pitch;
+    a.in_plain = c.in_plain; a.out_plain = c.out_plain; a.res_plain = c.res_plain;
+    a.cin_pad = c.cin_pad; a.cout_pad = c.cout_pad; a.nchunk = c.nchunk;
+    a.nkk_last = 4;
+}
+
+// (fp16 tensors: fp32 accumulate, scale / shift fp32)
+int cn_conv3x3s1(const ConvCall &c, int bn_class, hipStream_t st)
+{
     C3Args a = {};
-    c3_set_ctl(a, ctl);
+    c3_fill(a, c);
     a.bm256 = cn_knobs.bm256;
     a.waves8 = cn_knobs.waves8;
     a.dbg = cn_knobs.dbgskip & 31;   // the ablation switches this kernel knows
     a.occ4 = cn_knobs.occ4;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.residual = residual; a.y = y;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.in_pitch = in_pitch;
-    a.out_pitch = out_pitch; a.relu = relu; a.vec_out = vec_out; a.setprio = cn_knobs.setprio;
-    a.res_pitch = res_pitch;
-    a.in_plain = (flags & CN_CONV_X_PLAIN) ? 1 : 0;
-    a.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
-    a.res_plain = (flags & CN_CONV_R_PLAIN) ? 1 : 0;
-    const int bke = dtype == CN_DTYPE_F16 ? 64 : 32;
-    a.cin_pad = (Cin + bke - 1) / bke * bke;
-    a.cout_pad = (Cout + 31) / 32 * 32;
-    a.nchunk = a.cin_pad / bke;
-    a.nkk_last = dtype != CN_DTYPE_F32 ? 4 : ((Cin - (a.nchunk - 1) * 32) + 7) / 8;
+    if (c.dtype == CN_DTYPE_F32) a.nkk_last = ((c.Cin - (a.nchunk - 1) * 32) + 7) / 8;
     a.ncb = a.cout_pad / 32;
     a.wfrag_off = (size_t)9 * a.cout_pad * a.cin_pad * 4;   // behind the row-ordered copy
     // f32s tensors on both sides: the persistent loader / consumer kernel (cn_conv3x3p.hip)
-    if (dtype == CN_DTYPE_F32S && !a.dbg && vec_out && scale &&
-        cn_conv3x3p_takes(B, H, W, Cin, Cout, in_pitch, out_pitch, res_pitch, a.in_plain != 0, residual != nullptr))
-        return cn_conv3x3s1_persist(x, w_packed, scale, shift, residual, y, B, H, W, Cin, Cout, in_pitch,
-                                    out_pitch, res_pitch, relu, a.out_plain, a.res_plain, ctl, st);
-    if (dtype == CN_DTYPE_F32S) return c3_dispatch<cn_f32s>(a, bn_class, st);
-    return dtype == CN_DTYPE_F16 ? c3_dispatch<_Float16>(a, bn_class, st) : c3_dispatch<float>(a, bn_class, st);
+    if (c.dtype == CN_DTYPE_F32S && !a.dbg && c.vec_out && c.scale && cn_conv3x3p_takes(c))
+        return cn_conv3x3s1_persist(c, st);
+    if (c.dtype == CN_DTYPE_F32S) return c3_dispatch<cn_f32s>(a, bn_class, st);
+    return c.dtype == CN_DTYPE_F16 ? c3_dispatch<_Float16>(a, bn_class, st) : c3_dispatch<float>(a, bn_class, st);
 }
 
 // Fused CenterNet heads: for every head h, y_h = conv1x1(relu(conv3x3(x) + bias1_h)) + bias2_h,
@@ -1395,28 +1391,14 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
 // ConvTranspose2d(kernel 4, stride 2, padding 1) through the LDS-halo kernel: the four output
 // parities are 2x2 convolutions over the 3x3 neighbourhood the halo already holds.
 // w_packed: cn_pack_deconv4x4s2_weight_f32 layout [parity 4][tap 4][cout_pad][cin_pad].
-int cn_deconv4x4s2_halo(const void *x, const void *w_packed, const float *scale, const float *shift,
-                        void *y, int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch,
-                        int relu, int vec_out, int dtype, int flags, const cn_f32s_ctl *ctl,
-                        hipStream_t st)
+int cn_deconv4x4s2_halo(const ConvCall &c, hipStream_t st)
 {
     C3Args a = {};
-    c3_set_ctl(a, ctl);
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.residual = nullptr; a.y = y;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.in_pitch = in_pitch;
-    a.out_pitch = out_pitch; a.relu = relu; a.vec_out = vec_out; a.setprio = cn_knobs.setprio;
-    a.cin_pad = (Cin + 31) / 32 * 32;
-    a.cout_pad = (Cout + 31) / 32 * 32;
-    a.nchunk = a.cin_pad / 32;
-    a.nkk_last = 4;
-    a.res_pitch = out_pitch;
-    a.in_plain = (flags & CN_CONV_X_PLAIN) ? 1 : 0;
-    a.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
+    c3_fill(a, c);
+    const int B = c.B, H = c.H, W = c.W, Cout = c.Cout, dtype = c.dtype;
     const bool wide = W >= 32;
-    if (dtype == CN_DTYPE_F32S && vec_out && scale &&
-        cn_deconv4x4s2p_takes(B, H, W, Cin, Cout, in_pitch, out_pitch, a.in_plain != 0))
-        return cn_deconv4x4s2_persist(x, w_packed, scale, shift, y, B, H, W, Cin, Cout, in_pitch, out_pitch, relu,
-                                      a.out_plain, ctl, st);
+    if (dtype == CN_DTYPE_F32S && c.vec_out && c.scale && cn_deconv4x4s2p_takes(c))
+        return cn_deconv4x4s2_persist(c, st);
     if (dtype == CN_DTYPE_F32S) {
         if (Cout > 64)
             return wide ? launch_c3<cn_f32s, 32, 128, 4, 2, false, 128, false, true>(a, st)

@@ -1246,58 +1246,60 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
 
 // Does the persistent kernel take this layer?  f32s input (whole 128-byte groups per pixel), output
 // and residual as whole 32-channel groups (f32s, or plain fp32 at a pitch that is a multiple of 32).
-bool cn_conv3x3p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int res_pitch,
-                       bool in_plain, bool has_res)
+bool cn_conv3x3p_takes(const ConvCall &c)
 {
-    if (!cn_knobs.c3p || in_plain) return false;   // (the caller also guarantees a non-null scale)
-    if ((in_pitch & 31) || (out_pitch & 31) || (has_res && (res_pitch & 31))) return false;
-    if (Cout % 32) return false;
-    const long items = (long)B * cn_cdiv(H, P_TH) * cn_cdiv(W, P_TW) * cn_cdiv(Cout, 64);
+    if (!cn_knobs.c3p || c.in_plain) return false;   // (the caller also guarantees a non-null scale)
+    if ((c.in_pitch & 31) || (c.out_pitch & 31) || (c.residual && (c.res_pitch & 31))) return false;
+    if (c.Cout % 32) return false;
+    const long items = (long)c.B * cn_cdiv(c.H, P_TH) * cn_cdiv(c.W, P_TW) * cn_cdiv(c.Cout, 64);
     // enough items that the persistent grid fills the chip (key 28 = 2: every shape, for tests)
     if (cn_knobs.c3p < 2 && items < 256) return false;
-    if ((long)B * H * W * (long)max(in_pitch, max(out_pitch, res_pitch)) * 4 >= (1L << 31)) return false;
-    (void)Cin;
+    if ((long)c.B * c.H * c.W * (long)max(c.in_pitch, max(c.out_pitch, c.res_pitch)) * 4 >= (1L << 31)) return false;
     return true;
 }
 
 // ConvTranspose2d(4, stride 2, pad 1) in parity form on the persistent kernel: f32s input, output as
 // whole 32-channel groups (f32s or plain), enough items to fill the chip
-bool cn_deconv4x4s2p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, bool in_plain)
+bool cn_deconv4x4s2p_takes(const ConvCall &c)
 {
-    if (!cn_knobs.c3p || !(cn_knobs.c3p_deconv) || in_plain) return false;
-    if ((in_pitch & 31) || (out_pitch & 31) || (Cout % 32)) return false;
-    const long items = 4L * B * cn_cdiv(H, P_TH) * cn_cdiv(W, P_TW) * cn_cdiv(Cout, 64);
+    if (!cn_knobs.c3p || !(cn_knobs.c3p_deconv) || c.in_plain) return false;
+    if ((c.in_pitch & 31) || (c.out_pitch & 31) || (c.Cout % 32)) return false;
+    const long items = 4L * c.B * cn_cdiv(c.H, P_TH) * cn_cdiv(c.W, P_TW) * cn_cdiv(c.Cout, 64);
     if (cn_knobs.c3p < 2 && items < 256) return false;
-    if (4L * B * H * W * (long)max(in_pitch, out_pitch) * 4 >= (1L << 31)) return false;
-    (void)Cin;
+    if (4L * c.B * c.H * c.W * (long)max(c.in_pitch, c.out_pitch) * 4 >= (1L << 31)) return false;
     return true;
 }
 
-int cn_deconv4x4s2_persist(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
-                           int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int relu,
-                           int out_plain, const cn_f32s_ctl *ctl, hipStream_t st)
+// what the three forms share; H x W: the map the tiles cover (the output; the deconvolution: its input), npar:
+// parity classes per tile
+static P3Args p3_args(const ConvCall &c, int H, int W, int npar)
 {
     P3Args a = {};
-    a.x = (const char *)x; a.w = (const char *)w_packed; a.scale = scale; a.shift = shift;
-    a.y = (char *)y;
+    a.x = (const char *)c.x; a.w = (const char *)c.w; a.scale = c.scale; a.shift = c.shift;
+    a.y = (char *)c.y;
     a.H = H; a.W = W;
-    a.Hi = H; a.Wi = W;
-    a.in_pitchB = in_pitch * 4; a.out_pitchB = out_pitch * 4;
-    const int cin_pad = (Cin + 31) / 32 * 32;
-    a.cin_padB = cin_pad * 4;
-    a.cout_pad = (Cout + 31) / 32 * 32;
+    a.Hi = c.H; a.Wi = c.W;
+    a.in_pitchB = c.in_pitch * 4; a.out_pitchB = c.out_pitch * 4;
+    a.cin_padB = c.cin_pad * 4;
+    a.cout_pad = c.cout_pad;
     a.ngroups = a.cout_pad / 32;
-    a.nchunk = cin_pad / 32;
-    a.nblk = cn_cdiv(Cout, 64);
-    a.npar = 4;
+    a.nchunk = c.nchunk;
+    a.nblk = cn_cdiv(c.Cout, 64);
+    a.npar = npar;
     a.tiles_x = cn_cdiv(W, P_TW);
     a.tiles_y = cn_cdiv(H, P_TH);
-    a.items = B * a.tiles_y * a.tiles_x * a.npar * a.nblk;
-    a.relu = relu; a.out_plain = out_plain;
+    a.items = c.B * a.tiles_y * a.tiles_x * a.npar * a.nblk;
+    a.relu = c.relu; a.out_plain = c.out_plain;
     a.res_mul = 1.f;
-    a.range = ctl ? ctl->range : nullptr;
+    a.range = c.ctl ? c.ctl->range : nullptr;
     a.stagger = cn_knobs.c3p_stagger;
     a.knobs = cn_knobs.c3p_knobs;
+    return a;
+}
+
+int cn_deconv4x4s2_persist(const ConvCall &c, hipStream_t st)
+{
+    const P3Args a = p3_args(c, c.H, c.W, 4);
     int per_xcd = cn_cdiv(a.items, 8);
     if (per_xcd > 64) per_xcd = 64;
     const dim3 grid(8 * per_xcd), block(p3_threads(4, false));
@@ -1307,9 +1309,9 @@ int cn_deconv4x4s2_persist(const void *x, const void *w_packed, const float *sca
         hipLaunchKernelGGL((conv3x3p_kernel<0, OP, false, false, 4, false, PIPE>), grid, block, P_LDS, st, a, P3Heads{}); \
     } while (0)
     if (a.knobs & 2) {
-        if (out_plain) P3_LAUNCH4(true, true); else P3_LAUNCH4(false, true);
+        if (c.out_plain) P3_LAUNCH4(true, true); else P3_LAUNCH4(false, true);
     } else {
-        if (out_plain) P3_LAUNCH4(true, false); else P3_LAUNCH4(false, false);
+        if (c.out_plain) P3_LAUNCH4(true, false); else P3_LAUNCH4(false, false);
     }
 #undef P3_LAUNCH4
     CN_CHECK_LAUNCH();
@@ -1318,44 +1320,21 @@ int cn_deconv4x4s2_persist(const void *x, const void *w_packed, const float *sca
 
 // 3x3 / stride 2 / pad 1 on the persistent kernel (parity-plane form): f32s tensors on both sides,
 // whole 32-channel output groups, no residual
-bool cn_conv3x3s2p_takes(int B, int Hi, int Wi, int Cin, int Cout, int in_pitch, int out_pitch)
+bool cn_conv3x3s2p_takes(const ConvCall &c)
 {
     if (!cn_knobs.c3p || !cn_knobs.c3p_s2) return false;
-    if ((in_pitch & 31) || (out_pitch & 31) || (Cout % 32)) return false;
-    const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
-    const long items = (long)B * cn_cdiv(Ho, P_TH) * cn_cdiv(Wo, P_TW) * cn_cdiv(Cout, 64);
+    if ((c.in_pitch & 31) || (c.out_pitch & 31) || (c.Cout % 32)) return false;
+    const long items = (long)c.B * cn_cdiv(c.Ho, P_TH) * cn_cdiv(c.Wo, P_TW) * cn_cdiv(c.Cout, 64);
     if (cn_knobs.c3p < 2 && items < 256) return false;
-    if ((long)B * Hi * Wi * (long)in_pitch * 4 >= (1L << 31) || (long)B * Ho * Wo * (long)out_pitch * 4 >= (1L << 31))
+    if ((long)c.B * c.H * c.W * (long)c.in_pitch * 4 >= (1L << 31) ||
+        (long)c.B * c.Ho * c.Wo * (long)c.out_pitch * 4 >= (1L << 31))
         return false;
-    (void)Cin;
     return true;
 }
 
-int cn_conv3x3s2_persist(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
-                         int B, int Hi, int Wi, int Cin, int Cout, int in_pitch, int out_pitch, int relu,
-                         int out_plain, const cn_f32s_ctl *ctl, hipStream_t st)
+int cn_conv3x3s2_persist(const ConvCall &c, hipStream_t st)
 {
-    P3Args a = {};
-    a.x = (const char *)x; a.w = (const char *)w_packed; a.scale = scale; a.shift = shift;
-    a.y = (char *)y;
-    a.H = (Hi - 1) / 2 + 1; a.W = (Wi - 1) / 2 + 1;
-    a.Hi = Hi; a.Wi = Wi;
-    a.in_pitchB = in_pitch * 4; a.out_pitchB = out_pitch * 4;
-    const int cin_pad = (Cin + 31) / 32 * 32;
-    a.cin_padB = cin_pad * 4;
-    a.cout_pad = (Cout + 31) / 32 * 32;
-    a.ngroups = a.cout_pad / 32;
-    a.nchunk = cin_pad / 32;
-    a.nblk = cn_cdiv(Cout, 64);
-    a.npar = 1;
-    a.tiles_x = cn_cdiv(a.W, P_TW);
-    a.tiles_y = cn_cdiv(a.H, P_TH);
-    a.items = B * a.tiles_y * a.tiles_x * a.nblk;
-    a.relu = relu; a.out_plain = out_plain;
-    a.res_mul = 1.f;
-    a.range = ctl ? ctl->range : nullptr;
-    a.stagger = cn_knobs.c3p_stagger;
-    a.knobs = cn_knobs.c3p_knobs;
+    const P3Args a = p3_args(c, c.Ho, c.Wo, 1);   // Ho = (H - 1) / 2 + 1: the caller's route checks the geometry
     int per_xcd = cn_cdiv(a.items, 8);
     if (per_xcd > 64) per_xcd = 64;
     const dim3 grid(8 * per_xcd), block(p3_threads(9, true));
@@ -1365,9 +1344,9 @@ int cn_conv3x3s2_persist(const void *x, const void *w_packed, const float *scale
         hipLaunchKernelGGL((conv3x3p_kernel<0, OP, false, false, 9, true, PIPE>), grid, block, P_LDS, st, a, P3Heads{}); \
     } while (0)
     if (a.knobs & 2) {
-        if (out_plain) P3_LAUNCHS2(true, true); else P3_LAUNCHS2(false, true);
+        if (c.out_plain) P3_LAUNCHS2(true, true); else P3_LAUNCHS2(false, true);
     } else {
-        if (out_plain) P3_LAUNCHS2(true, false); else P3_LAUNCHS2(false, false);
+        if (c.out_plain) P3_LAUNCHS2(true, false); else P3_LAUNCHS2(false, false);
     }
 #undef P3_LAUNCHS2
     CN_CHECK_LAUNCH();
@@ -1404,33 +1383,14 @@ extern "C" int cn_conv3x3p_probe(int dbg, void *prof)
     return CN_OK;
 }
 
-int cn_conv3x3s1_persist(const void *x, const void *w_packed, const float *scale, const float *shift,
-                         const void *residual, void *y, int B, int H, int W, int Cin, int Cout,
-                         int in_pitch, int out_pitch, int res_pitch, int relu, int out_plain, int res_plain,
-                         const cn_f32s_ctl *ctl, hipStream_t st)
+int cn_conv3x3s1_persist(const ConvCall &c, hipStream_t st)
 {
-    P3Args a = {};
-    a.x = (const char *)x; a.w = (const char *)w_packed; a.scale = scale; a.shift = shift;
-    a.residual = (const char *)residual; a.y = (char *)y;
-    a.H = H; a.W = W;
-    a.Hi = H; a.Wi = W;
-    a.in_pitchB = in_pitch * 4; a.out_pitchB = out_pitch * 4; a.res_pitchB = res_pitch * 4;
-    a.res_bytes = (int)((long)B * H * W * res_pitch * 4);   // < 2^31 (cn_conv3x3p_takes)
-    const int cin_pad = (Cin + 31) / 32 * 32;
-    a.cin_padB = cin_pad * 4;
-    a.cout_pad = (Cout + 31) / 32 * 32;
-    a.ngroups = a.cout_pad / 32;
-    a.nchunk = cin_pad / 32;
-    a.nblk = cn_cdiv(Cout, 64);
-    a.npar = 1;
-    a.tiles_x = cn_cdiv(W, P_TW);
-    a.tiles_y = cn_cdiv(H, P_TH);
-    a.items = B * a.tiles_y * a.tiles_x * a.nblk;
-    a.relu = relu; a.out_plain = out_plain; a.res_plain = res_plain;
-    a.res_mul = (ctl && ctl->res_mul != 0.f) ? ctl->res_mul : 1.f;
-    a.range = ctl ? ctl->range : nullptr;
-    a.stagger = cn_knobs.c3p_stagger;
-    a.knobs = cn_knobs.c3p_knobs;
+    P3Args a = p3_args(c, c.H, c.W, 1);
+    a.residual = (const char *)c.residual;
+    a.res_pitchB = c.res_pitch * 4;
+    a.res_bytes = (int)((long)c.B * c.H * c.W * c.res_pitch * 4);   // < 2^31 (cn_conv3x3p_takes)
+    a.res_plain = c.res_plain;
+    a.res_mul = (c.ctl && c.ctl->res_mul != 0.f) ? c.ctl->res_mul : 1.f;
     // two workgroups per CU, a multiple of 8 (one share per XCD), never more than one per item
     int per_xcd = cn_cdiv(a.items, 8);
     if (per_xcd > 64) per_xcd = 64;
@@ -1444,8 +1404,8 @@ int cn_conv3x3s1_persist(const void *x, const void *w_packed, const float *scale
     do {                                                                    \
         if (a.knobs & 2) P3_LAUNCH_(R, OP, true); else P3_LAUNCH_(R, OP, false); \
     } while (0)
-    const int rmode = !residual ? 0 : (res_plain ? 2 : 1);
-    if ((p3_probe_dbg || p3_probe_prof) && !out_plain && rmode < 2) {
+    const int rmode = !c.residual ? 0 : (c.res_plain ? 2 : 1);
+    if ((p3_probe_dbg || p3_probe_prof) && !c.out_plain && rmode < 2) {
         a.dbg = p3_probe_dbg;
         a.prof = p3_probe_prof;
         if (rmode == 0) {
@@ -1458,7 +1418,7 @@ int cn_conv3x3s1_persist(const void *x, const void *w_packed, const float *scale
         CN_CHECK_LAUNCH();
         return CN_OK;
     }
-    if (out_plain) {
+    if (c.out_plain) {
         if (rmode == 0) P3_LAUNCH(0, true); else if (rmode == 1) P3_LAUNCH(1, true); else P3_LAUNCH(2, true);
     } else {
         if (rmode == 0) P3_LAUNCH(0, false); else if (rmode == 1) P3_LAUNCH(1, false); else P3_LAUNCH(2, false);

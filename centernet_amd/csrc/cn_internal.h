@@ -1,18 +1,37 @@
-// cn_internal.h -- prototypes of the functions one .hip file defines and another calls.  Included by both
-// sides, so the defining file is compiled against the declaration its callers see.
+// cn_internal.h -- prototypes of the functions one .hip file defines and another calls, and the two call
+// descriptions they pass (ConvCall: the convolution family, DcnWinCall: the f32s deformable kernels).  Included
+// by both sides, so the defining file is compiled against the declaration its callers see.
 #pragma once
 #include "cn_common.h"
 
+// ---- the convolution family: one call description.  cn_conv.hip fills it once per cn_conv2d /
+// cn_conv_transpose4x4s2 call (after the descriptor checks); conv_route() there and every launcher and `takes`
+// predicate below read it.  An extra argument only for what is not a fact of the call (tile class, tuning key).
+struct ConvCall {
+    const void *x, *w;                    // tensors of `dtype` (the stem: fp32 NCHW image and fp32 weights)
+    const float *scale, *shift;
+    const void *residual;
+    void *y;
+    int B, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad_h, pad_w, dil;
+    int in_pitch, out_pitch, res_pitch;   // floats per pixel; res_pitch is resolved (never 0)
+    int relu, dtype;                      // CN_DTYPE_*
+    int in_plain, out_plain, res_plain;   // CN_CONV_X_PLAIN / Y_PLAIN / R_PLAIN
+    int stem, stem_f32s, stem_pool, stem_y_f32s;   // 3-channel NCHW image; CN_CONV_STEM_F32S / _MAXPOOL / _Y_F32S
+    int out_nchw, plain_geo;              // plain_geo: output pixel (oy, ox) goes to (oy, ox) of a (B, Ho, Wo) map
+    int vec_out;                          // y (and the residual) allow 4-element vector stores
+    const cn_f32s_ctl *ctl;               // may be null
+    int ksplit;                           // K slices of this launch (1 = no split)
+    float *partial;                       // split-K workspace when ksplit > 1
+    int cin_pad, cout_pad, nchunk;        // packed weight: K per tap (stem: of all taps), rows per tap, K chunks
+};
+
 // ---- cn_stem.hip
-int cn_stem_conv_f32(const float *x, const float *w_packed, const float *scale, const float *shift,
-                     float *y, int B, int H, int W, int Ho, int Wo, int Cout, int KH, int KW,
-                     int stride, int pad, int relu, int out_pitch, int KP, int persistent,
-                     const cn_f32s_ctl *ctl, hipStream_t st);
-int cn_stem_pool_rows(int B, int Ho, int Wo, int Cout, int KH, int KW, int stride, int KP);
-int cn_stem_pool_f32s(const float *x, const float *w_packed, const float *scale, const float *shift,
-                      float *y, int B, int H, int W, int Ho, int Wo, int Cout, int KH, int KW,
-                      int stride, int pad, int relu, int out_pitch, int KP, int y_f32s, const cn_f32s_ctl *ctl,
-                      hipStream_t st);
+int cn_stem_pool_rows(const ConvCall &c);   // pooled rows per strip of the stem + max-pool kernel, 0 = not taken
+int cn_stem_pool_f32s(const ConvCall &c, hipStream_t st);
+// the kernel cn_stem_conv_f32 runs for the call; persistent: cn_set_tuning key 12
+enum { CN_STEM_NONE = 0, CN_STEM_WINDOW, CN_STEM_PERSIST, CN_STEM_PERSIST_F32S, CN_STEM_16S };
+int cn_stem_form(const ConvCall &c, int persistent);
+int cn_stem_conv_f32(const ConvCall &c, int persistent, hipStream_t st);
 
 // ---- f32s deformable kernels: cn_dcn2.hip (window), cn_dcn3.hip (team), cn_dcn4.hip (wide); what they share is
 // in cn_dcn_window.h.  One call description for all three (cn_conv.hip fills it once)
@@ -42,53 +61,31 @@ int cn_dcn_general_launch(const float *input, const float *weight, const float *
                           int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                           int dh, int dw, int dg, int mask_sigmoid, hipStream_t st);
 
-// ---- cn_offconv.hip
-bool cn_offconv_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int ksplit);
-int cn_offconv_f32s(const float *x, const void *w_packed, const float *scale, const float *shift, float *y,
-                    int B, int H, int W, int Cin, int Cout, int out_pitch, int relu, const cn_f32s_ctl *ctl,
-                    int ksplit, float *partial, hipStream_t st);
+// ---- cn_offconv.hip (f32s, plain in / plain out, <= 32 output channels; ksplit: the slices the launch would get)
+bool cn_offconv_takes(const ConvCall &c, int ksplit);
+int cn_offconv_f32s(const ConvCall &c, hipStream_t st);
 
-// ---- cn_proj.hip
-bool cn_proj1x1_takes(int B, int H, int W, int Cin, int Cout, int stride, int in_pitch, int out_pitch);
-int cn_proj1x1_f32s(const void *x, const void *w_packed, const float *scale, const float *shift, void *y, int B, int H,
-                    int W, int Cin, int Cout, int stride, int in_pitch, int out_pitch, int relu, int out_plain,
-                    const cn_f32s_ctl *ctl, hipStream_t st);
+// ---- cn_proj.hip (f32s 1x1, stride 1 or 2)
+bool cn_proj1x1_takes(const ConvCall &c);
+int cn_proj1x1_f32s(const ConvCall &c, hipStream_t st);
 
-// ---- cn_conv16.hip
-int cn_conv3x3_c16(const float *x, const float *w_packed, const float *scale, const float *shift,
-                   float *y, int B, int H, int W, int Ho, int Wo, int Cin, int Cout, int stride,
-                   int in_pitch, int out_pitch, int relu, hipStream_t st);
-int cn_conv3x3_c16s(const float *x, const void *w_packed, const float *scale, const float *shift,
-                    float *y, int B, int H, int W, int Ho, int Wo, int Cin, int Cout, int stride,
-                    int in_pitch, int out_pitch, int relu, const cn_f32s_ctl *ctl, hipStream_t st);
+// ---- cn_conv16.hip (3x3 / pad 1 with 16 input and <= 32 output channels; fp32, or f32s arithmetic on plain tensors)
+bool cn_conv16_takes(const ConvCall &c);
+int cn_conv3x3_c16(const ConvCall &c, hipStream_t st);
+int cn_conv3x3_c16s(const ConvCall &c, hipStream_t st);
 
-// ---- cn_conv3x3.hip (LDS-halo kernel)
-// bn_class: 2 = 128-wide N tiles, 1 = 64, 0 = 32 (chosen by the caller, same rule as cn_conv.hip);
-// dtype: CN_DTYPE_*; flags: cn_conv_desc.flags (CN_CONV_X_PLAIN / Y_PLAIN / R_PLAIN)
-int cn_conv3x3s1(const void *x, const void *w_packed, const float *scale, const float *shift,
-                 const void *residual, void *y, int B, int H, int W, int Cin, int Cout,
-                 int in_pitch, int out_pitch, int res_pitch, int relu, int vec_out, int bn_class,
-                 int dtype, int flags, const cn_f32s_ctl *ctl, hipStream_t st);
-int cn_deconv4x4s2_halo(const void *x, const void *w_packed, const float *scale, const float *shift,
-                        void *y, int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch,
-                        int relu, int vec_out, int dtype, int flags, const cn_f32s_ctl *ctl,
-                        hipStream_t st);
+// ---- cn_conv3x3.hip (LDS-halo kernel); each forwards the call to cn_conv3x3p.hip when that kernel takes it
+// bn_class: 2 = 128-wide N tiles, 1 = 64, 0 = 32 (conv_route's)
+int cn_conv3x3s1(const ConvCall &c, int bn_class, hipStream_t st);
+int cn_deconv4x4s2_halo(const ConvCall &c, hipStream_t st);
 
 // ---- cn_conv3x3p.hip (persistent loader / consumer kernel)
-bool cn_conv3x3p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int res_pitch,
-                       bool in_plain, bool has_res);
-int cn_conv3x3s1_persist(const void *x, const void *w_packed, const float *scale, const float *shift,
-                         const void *residual, void *y, int B, int H, int W, int Cin, int Cout,
-                         int in_pitch, int out_pitch, int res_pitch, int relu, int out_plain, int res_plain,
-                         const cn_f32s_ctl *ctl, hipStream_t st);
-bool cn_conv3x3s2p_takes(int B, int Hi, int Wi, int Cin, int Cout, int in_pitch, int out_pitch);
-int cn_conv3x3s2_persist(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
-                         int B, int Hi, int Wi, int Cin, int Cout, int in_pitch, int out_pitch, int relu,
-                         int out_plain, const cn_f32s_ctl *ctl, hipStream_t st);
-bool cn_deconv4x4s2p_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, bool in_plain);
-int cn_deconv4x4s2_persist(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
-                           int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int relu,
-                           int out_plain, const cn_f32s_ctl *ctl, hipStream_t st);
+bool cn_conv3x3p_takes(const ConvCall &c);
+int cn_conv3x3s1_persist(const ConvCall &c, hipStream_t st);
+bool cn_conv3x3s2p_takes(const ConvCall &c);
+int cn_conv3x3s2_persist(const ConvCall &c, hipStream_t st);
+bool cn_deconv4x4s2p_takes(const ConvCall &c);
+int cn_deconv4x4s2_persist(const ConvCall &c, hipStream_t st);
 bool cn_heads3x3p_takes(int B, int H, int W, int in_pitch, int head_conv, int n_heads, const cn_head_out *heads,
                         bool in_plain);
 int cn_heads3x3p(const void *x, int B, int H, int W, int Cin, int in_pitch, const void *w1_packed,

@@ -223,34 +223,32 @@ __global__ __launch_bounds__(256 * TEAMS, 4) void offconv_kernel(const OcArgs a)
 
 // Does this kernel take the layer?  (the caller has checked: 3x3 / stride 1 / pad 1, NHWC both sides, f32s
 // arithmetic with plain input and plain output, no residual)
-bool cn_offconv_takes(int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch, int ksplit)
+bool cn_offconv_takes(const ConvCall &c, int ksplit)
 {
     if (!cn_knobs.offconv) return false;
-    if (Cout > 32 || Cout < 1 || (Cin & 31) || in_pitch != Cin) return false;
-    if ((H & 7) || (W & 15)) return false;
-    if (out_pitch != 32) return false;     // the epilogue stores the whole 32-channel block (zeros behind Cout): the output must own it
-    if ((size_t)B * H * W * Cin * 4 >= ((size_t)1 << 32)) return false;
-    if (ksplit < 1 || (Cin / 32) % ksplit) return false;
+    if (c.Cout > 32 || c.Cout < 1 || (c.Cin & 31) || c.in_pitch != c.Cin) return false;
+    if ((c.H & 7) || (c.W & 15)) return false;
+    if (c.out_pitch != 32) return false;   // the epilogue stores the whole 32-channel block (zeros behind Cout): the output must own it
+    if ((size_t)c.B * c.H * c.W * c.Cin * 4 >= ((size_t)1 << 32)) return false;
+    if (ksplit < 1 || (c.Cin / 32) % ksplit) return false;
     return true;
 }
 
-int cn_offconv_f32s(const float *x, const void *w_packed, const float *scale, const float *shift, float *y,
-                    int B, int H, int W, int Cin, int Cout, int out_pitch, int relu, const cn_f32s_ctl *ctl,
-                    int ksplit, float *partial, hipStream_t st)
+int cn_offconv_f32s(const ConvCall &c, hipStream_t st)
 {
-    if (!cn_aligned16(x) || !cn_aligned16(y) || !cn_aligned16(w_packed)) return CN_ERR_ALIGN;
+    if (!cn_aligned16(c.x) || !cn_aligned16(c.y) || !cn_aligned16(c.w)) return CN_ERR_ALIGN;
     OcArgs a = {};
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.out_pitch = out_pitch; a.relu = relu;
-    a.nchunk = Cin / 32;
-    a.tiles_x = W / O_TX; a.tiles_y = H / O_TY;
-    a.x_mul = (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f;
-    a.range = ctl ? ctl->range : nullptr;
-    a.ksplit = ksplit;
-    a.partial = ksplit > 1 ? partial : nullptr;
-    dim3 grid((unsigned)(B * a.tiles_x * a.tiles_y), 1, (unsigned)ksplit);
+    a.x = (const float *)c.x; a.w = c.w; a.scale = c.scale; a.shift = c.shift; a.y = (float *)c.y;
+    a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout; a.out_pitch = c.out_pitch; a.relu = c.relu;
+    a.nchunk = c.Cin / 32;
+    a.tiles_x = c.W / O_TX; a.tiles_y = c.H / O_TY;
+    a.x_mul = (c.ctl && c.ctl->x_mul != 0.f) ? c.ctl->x_mul : 1.f;
+    a.range = c.ctl ? c.ctl->range : nullptr;
+    a.ksplit = c.ksplit;
+    a.partial = c.ksplit > 1 ? c.partial : nullptr;
+    dim3 grid((unsigned)(c.B * a.tiles_x * a.tiles_y), 1, (unsigned)c.ksplit);
     // four-wave workgroups from three tiles per CU up (four of them fit a CU), else eight waves in two teams
-    if ((long)grid.x * ksplit >= cn_knobs.offconv_teams1) {
+    if ((long)grid.x * c.ksplit >= cn_knobs.offconv_teams1) {
         CN_SET_MAX_LDS_ONCE(offconv_kernel<1>, O_HBYTES);
         hipLaunchKernelGGL(offconv_kernel<1>, grid, dim3(256), O_HBYTES, st, a);
     } else {

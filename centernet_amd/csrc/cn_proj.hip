@@ -194,38 +194,37 @@ __global__ __launch_bounds__(J_NT, 2) void proj1x1_kernel(const JArgs a)
 
 // Shapes this kernel takes: f32s NHWC input (pitch = whole 32-channel groups), 1x1, stride 1 or 2, no padding,
 // no residual; f32s or plain NHWC output whose pitch covers whole 32-channel groups of the padded Cout.
-bool cn_proj1x1_takes(int B, int H, int W, int Cin, int Cout, int stride, int in_pitch, int out_pitch)
+bool cn_proj1x1_takes(const ConvCall &c)
 {
     if (!cn_knobs.proj) return false;
-    if ((Cin & 31) || (in_pitch & 31) || (out_pitch & 31) || (stride != 1 && stride != 2)) return false;
-    if (out_pitch < (Cout + 31) / 32 * 32) return false;
-    if ((size_t)B * H * W * in_pitch * 4 >= ((size_t)1 << 32)) return false;
-    return Cin <= 1024 && Cout >= 32;
+    if ((c.Cin & 31) || (c.in_pitch & 31) || (c.out_pitch & 31) || (c.stride != 1 && c.stride != 2)) return false;
+    if (c.out_pitch < c.cout_pad) return false;
+    if ((size_t)c.B * c.H * c.W * c.in_pitch * 4 >= ((size_t)1 << 32)) return false;
+    return c.Cin <= 1024 && c.Cout >= 32;
 }
 
-int cn_proj1x1_f32s(const void *x, const void *w_packed, const float *scale, const float *shift, void *y,
-                    int B, int H, int W, int Cin, int Cout, int stride, int in_pitch, int out_pitch, int relu,
-                    int out_plain, const cn_f32s_ctl *ctl, hipStream_t st)
+int cn_proj1x1_f32s(const ConvCall &c, hipStream_t st)
 {
     JArgs a = {};
     // the fragment-ordered copy sits behind the row form ([1][cout_pad][cin_pad] x 4 bytes)
-    a.x = (const char *)x; a.w = (const char *)w_packed + (size_t)((Cout + 31) / 32 * 32) * Cin * 4; a.scale = scale; a.shift = shift; a.y = (char *)y;
-    a.H = H; a.W = W; a.stride = stride;
-    a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
-    a.M = B * a.Ho * a.Wo;
-    a.in_pitchB = in_pitch * 4; a.out_pitchB = out_pitch * 4;
-    a.cout_pad = (Cout + 31) / 32 * 32;
+    a.x = (const char *)c.x; a.w = (const char *)c.w + (size_t)c.cout_pad * c.Cin * 4; a.scale = c.scale; a.shift = c.shift;
+    a.y = (char *)c.y;
+    a.H = c.H; a.W = c.W; a.stride = c.stride;
+    a.Ho = c.Ho; a.Wo = c.Wo;   // (H - 1) / stride + 1: the caller's route checks it
+    a.M = c.B * a.Ho * a.Wo;
+    a.in_pitchB = c.in_pitch * 4; a.out_pitchB = c.out_pitch * 4;
+    a.cout_pad = c.cout_pad;
     a.ncb = a.cout_pad / 32;
-    a.nchunk = Cin / 32;
-    a.Cout = Cout; a.relu = relu;
-    a.range = ctl ? ctl->range : nullptr;
+    a.nchunk = c.Cin / 32;
+    a.Cout = c.Cout; a.relu = c.relu;
+    a.range = c.ctl ? c.ctl->range : nullptr;
     const dim3 grid((unsigned)cn_cdiv(a.M, 128), (unsigned)cn_cdiv(a.cout_pad, 32 * J_NB));
     const int pre = a.nchunk <= 2 ? 2 : 4;
     const int lds = 4 * pre * J_SLOT + 2 * 128 * 4;
-    if (out_plain && pre == 2) {
+    if (c.out_plain && pre == 2) {
         CN_SET_MAX_LDS_ONCE((proj1x1_kernel<true, 2>), 4 * 2 * J_SLOT + 1024);
         hipLaunchKernelGGL((proj1x1_kernel<true, 2>), grid, dim3(J_NT), lds, st, a);
-    } else if (out_plain) {
+    } else if (c.out_plain) {
         CN_SET_MAX_LDS_ONCE((proj1x1_kernel<true, 4>), 4 * 4 * J_SLOT + 1024);
         hipLaunchKernelGGL((proj1x1_kernel<true, 4>), grid, dim3(J_NT), lds, st, a);
     } else if (pre == 2) {

@@ -1217,70 +1217,90 @@ int launch_stem_persist(const StemArgs &a, int B, hipStream_t st)
 // Pooled rows per strip of the fused stem + max-pool kernel, or 0 when the shape is outside it:
 // 7x7 / stride 2, 33..64 output channels, rows of 1..4 whole 128-pixel tiles, an even number of
 // rows, and enough strips to fill the chip (shorter strips recompute more rows: 1 in 2R).
-int cn_stem_pool_rows(int B, int Ho, int Wo, int Cout, int KH, int KW, int stride, int KP)
+int cn_stem_pool_rows(const ConvCall &c)
 {
-    if (KH != PKH || KW != PKW || stride != 2 || Cout <= 32 || Cout > 64) return 0;
-    if ((KP & 7) || KP < PKH * PKW * 3) return 0;
-    if (Wo % BM || Wo / BM > 4 || (Ho & 1)) return 0;
-    const int PH = Ho / 2;
-    if (PH % 8 == 0 && (long)B * (PH / 8) >= 384) return 8;
-    if (PH % 4 == 0 && (long)B * (PH / 4) >= 192) return 4;
+    if (c.KH != PKH || c.KW != PKW || c.stride != 2 || c.Cout <= 32 || c.Cout > 64) return 0;
+    if ((c.cin_pad & 7) || c.cin_pad < PKH * PKW * 3) return 0;
+    if (c.Wo % BM || c.Wo / BM > 4 || (c.Ho & 1)) return 0;
+    const int PH = c.Ho / 2;
+    if (PH % 8 == 0 && (long)c.B * (PH / 8) >= 384) return 8;
+    if (PH % 4 == 0 && (long)c.B * (PH / 4) >= 192) return 4;
     return 0;
 }
 
-int cn_stem_pool_f32s(const float *x, const float *w_packed, const float *scale, const float *shift,
-                      float *y, int B, int H, int W, int Ho, int Wo, int Cout, int KH, int KW,
-                      int stride, int pad, int relu, int out_pitch, int KP, int y_f32s, const cn_f32s_ctl *ctl,
-                      hipStream_t st)
+// use_ctl = false: the fp32 window kernel, which splits nothing
+static StemArgs stem_args(const ConvCall &c, bool use_ctl, int tiles_per_image)
 {
-    const int R = cn_stem_pool_rows(B, Ho, Wo, Cout, KH, KW, stride, KP);
+    StemArgs a = {};
+    a.x_mul = (use_ctl && c.ctl && c.ctl->x_mul != 0.f) ? c.ctl->x_mul : 1.f;
+    a.range = (use_ctl && c.ctl) ? c.ctl->range : nullptr;
+    a.x = (const float *)c.x; a.w = (const float *)c.w; a.scale = c.scale; a.shift = c.shift; a.y = (float *)c.y;
+    a.H = c.H; a.W = c.W; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout = c.Cout; a.KH = c.KH; a.KW = c.KW;
+    a.stride = c.stride; a.pad = c.pad_h; a.relu = c.relu; a.out_pitch = c.out_pitch; a.KP = c.cin_pad;
+    a.tiles_per_image = tiles_per_image;
+    a.cout_pad = c.cout_pad;
+    return a;
+}
+
+int cn_stem_pool_f32s(const ConvCall &c, hipStream_t st)
+{
+    const int R = cn_stem_pool_rows(c);
     if (!R) return CN_ERR_UNSUPPORTED;
-    if (y_f32s && ((out_pitch & 31) || (((uintptr_t)y) & 127u))) return CN_ERR_ALIGN;
-    StemArgs a;
-    a.y_f32s = y_f32s;
-    a.x_mul = (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f;
-    a.range = ctl ? ctl->range : nullptr;
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y;
-    a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.KH = KH; a.KW = KW;
-    a.stride = stride; a.pad = pad; a.relu = relu; a.out_pitch = out_pitch; a.KP = KP;
-    a.tiles_per_image = Ho * (Wo / BM);
-    a.cout_pad = (Cout + 31) / 32 * 32;
-    switch (Wo / BM) {
-    case 1: return launch_stem_pool_f32s<1>(a, B, R, st);
-    case 2: return launch_stem_pool_f32s<2>(a, B, R, st);
-    case 3: return launch_stem_pool_f32s<3>(a, B, R, st);
-    default: return launch_stem_pool_f32s<4>(a, B, R, st);
+    if (c.stem_y_f32s && ((c.out_pitch & 31) || (((uintptr_t)c.y) & 127u))) return CN_ERR_ALIGN;
+    StemArgs a = stem_args(c, true, c.Ho * (c.Wo / BM));
+    a.y_f32s = c.stem_y_f32s;
+    switch (c.Wo / BM) {
+    case 1: return launch_stem_pool_f32s<1>(a, c.B, R, st);
+    case 2: return launch_stem_pool_f32s<2>(a, c.B, R, st);
+    case 3: return launch_stem_pool_f32s<3>(a, c.B, R, st);
+    default: return launch_stem_pool_f32s<4>(a, c.B, R, st);
     }
 }
 
-// Returns CN_ERR_UNSUPPORTED when the shape does not fit this kernel (the caller then uses
-// the generic implicit-GEMM stem).
-int cn_stem_conv_f32(const float *x, const float *w_packed, const float *scale, const float *shift,
-                     float *y, int B, int H, int W, int Ho, int Wo, int Cout, int KH, int KW,
-                     int stride, int pad, int relu, int out_pitch, int KP, int persistent,
-                     const cn_f32s_ctl *ctl, hipStream_t st)
+// Which kernel runs the stem: CN_STEM_NONE when the shape does not fit this file (the caller then uses the
+// generic implicit-GEMM stem).
+int cn_stem_form(const ConvCall &c, int persistent)
 {
-    if (KP & 7) return CN_ERR_UNSUPPORTED;
-    const float ctl_x_mul = (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f;
-    uint32_t *const ctl_range = ctl ? ctl->range : nullptr;
-    if (persistent && KH == PKH && KW == PKW && Wo % BM == 0 && (stride == 1 || stride == 2) &&
+    const int KP = c.cin_pad;
+    if (KP & 7) return CN_STEM_NONE;
+    if (persistent && c.KH == PKH && c.KW == PKW && c.Wo % BM == 0 && (c.stride == 1 || c.stride == 2) &&
         KP >= PKH * PKW * 3) {
-        StemArgs a;
-        a.y_f32s = 0;
-        a.x_mul = ctl_x_mul; a.range = ctl_range;
-        a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y;
-        a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.KH = KH; a.KW = KW;
-        a.stride = stride; a.pad = pad; a.relu = relu; a.out_pitch = out_pitch; a.KP = KP;
-        a.tiles_per_image = Ho * (Wo / BM);
-        a.cout_pad = (Cout + 31) / 32 * 32;
-        // bit 1 of `persistent`: f32s arithmetic (three fp16 MFMAs per product), stride-2 stems
-        // of more than 16 output channels
-        if ((persistent & 2) && stride == 2 && Cout > 16)
+        // f32s arithmetic (three fp16 MFMAs per product): stride-2 stems of more than 16 output channels
+        if (c.stem_f32s && c.stride == 2 && c.Cout > 16) return CN_STEM_PERSIST_F32S;
+        // ... and the stride-1 stem of <= 16 output channels (DLA base_layer; cn_set_tuning key 27)
+        if (c.stem_f32s && cn_knobs.stem16s && c.stride == 1 && c.Cout <= 16 && c.pad_h == 3 && (c.W & 3) == 0)
+            return CN_STEM_16S;
+        return CN_STEM_PERSIST;
+    }
+    // worst-case window of a 128-pixel tile
+    int wy, wx;
+    if (c.Wo >= BM) {
+        wy = c.stride + c.KH;  // a tile touches at most two output rows
+        wx = (c.Wo - 1) * c.stride + c.KW;
+        if (c.Wo % BM == 0) {  // tiles never straddle rows
+            wy = c.KH;
+            wx = (BM - 1) * c.stride + c.KW;
+        }
+    } else {
+        const int rows = BM / c.Wo + 2;
+        wy = (rows - 1) * c.stride + c.KH;
+        wx = (c.Wo - 1) * c.stride + c.KW;
+    }
+    if ((long)3 * wy * (wx | 1) > WIN_MAX || wx > 2 * NT) return CN_STEM_NONE;
+    return CN_STEM_WINDOW;
+}
+
+int cn_stem_conv_f32(const ConvCall &c, int persistent, hipStream_t st)
+{
+    const int form = cn_stem_form(c, persistent);
+    const int B = c.B, Cout = c.Cout, stride = c.stride;
+    if (form == CN_STEM_NONE) return CN_ERR_UNSUPPORTED;
+    if (form != CN_STEM_WINDOW) {
+        const StemArgs a = stem_args(c, true, c.Ho * (c.Wo / BM));
+        if (form == CN_STEM_PERSIST_F32S)
             return Cout > 32 ? launch_stem_persist_f32s<64>(a, B, st)
                              : launch_stem_persist_f32s<32>(a, B, st);
-        // ... and the stride-1 stem of <= 16 output channels (DLA base_layer)
-        if ((persistent & 2) && stride == 1 && Cout <= 16 && pad == 3 && (W & 3) == 0)
-            return launch_stem16s(a, B, st);
+        if (form == CN_STEM_16S) return launch_stem16s(a, B, st);
         if (Cout > 32)
             return stride == 2 ? launch_stem_persist<64, 2>(a, B, st)
                                : launch_stem_persist<64, 1>(a, B, st);
@@ -1290,29 +1310,8 @@ int cn_stem_conv_f32(const float *x, const float *w_packed, const float *scale, 
         return stride == 2 ? launch_stem_persist<32, 2>(a, B, st)
                            : launch_stem_persist<32, 1>(a, B, st);
     }
-    // worst-case window of a 128-pixel tile
-    int wy, wx;
-    if (Wo >= BM) {
-        wy = stride + KH;  // a tile touches at most two output rows
-        wx = (Wo - 1) * stride + KW;
-        if (Wo % BM == 0) {  // tiles never straddle rows
-            wy = KH;
-            wx = (BM - 1) * stride + KW;
-        }
-    } else {
-        const int rows = BM / Wo + 2;
-        wy = (rows - 1) * stride + KH;
-        wx = (Wo - 1) * stride + KW;
-    }
-    if ((long)3 * wy * (wx | 1) > WIN_MAX || wx > 2 * NT) return CN_ERR_UNSUPPORTED;
-    StemArgs a;
-    a.y_f32s = 0;
-    a.x_mul = 1.f; a.range = nullptr;   // fp32 kernel: nothing is split
-    a.x = x; a.w = w_packed; a.scale = scale; a.shift = shift; a.y = y;
-    a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.KH = KH; a.KW = KW;
-    a.stride = stride; a.pad = pad; a.relu = relu; a.out_pitch = out_pitch; a.KP = KP;
-    a.tiles_per_image = cn_cdiv(Ho * Wo, BM);
-    a.cout_pad = (Cout + 31) / 32 * 32;
+    const StemArgs a = stem_args(c, false, cn_cdiv(c.Ho * c.Wo, BM));
+    const int KP = c.cin_pad;
     const int bn = Cout > 32 ? 64 : 32;
     const size_t lds = (size_t)WIN_MAX * 4 + (size_t)bn * (KP + 4) * 4 + (size_t)KP * 4 + BM * 4;
     dim3 grid(a.tiles_per_image, cn_cdiv(Cout, bn), B);

@@ -469,6 +469,9 @@ class PlanBuilder:
         lid = self._lid(lid)
         Ho = _out_size(x.H, kh, stride, padding, dilation)
         Wo = _out_size(x.W, kw, stride, padding, dilation)
+        # the layer's descriptor: what every probe and the launch share (they add what differs)
+        base = dict(B=x.B, H=x.H, W=x.W, Cin=ci, Ho=Ho, Wo=Wo, Cout=co, KH=kh, KW=kw, stride=stride,
+                    pad_h=padding, pad_w=padding, dil=dilation)
         use_s = self.split and not x.nchw and self._f32s_conv_form(kh, kw, stride, padding,
                                                                   dilation, out_nchw, ci, co)
         if use_s and self._narrow_form(kh, kw, padding, dilation, out_nchw, ci, co) and residual is None:
@@ -478,9 +481,7 @@ class PlanBuilder:
         fuse_pool = False
         if pool is not None and tuple(pool) == (3, 2, 1) and self.split and x.nchw and out is None \
                 and not out_nchw and residual is None and os.environ.get("CN_FUSE_STEM_POOL", "1") != "0":
-            probe = ConvDesc(B=x.B, H=x.H, W=x.W, Cin=ci, Ho=Ho, Wo=Wo, Cout=co, KH=kh, KW=kw,
-                             stride=stride, pad_h=padding, pad_w=padding, dil=dilation,
-                             in_layout=LAYOUT_NCHW, out_layout=LAYOUT_NHWC, dtype=self.cdtype)
+            probe = ConvDesc(in_layout=LAYOUT_NCHW, out_layout=LAYOUT_NHWC, dtype=self.cdtype, **base)
             fuse_pool = bool(self.lib.cn_stem_maxpool_supported(ctypes.byref(probe)))
         scale, shift = fold_bn(bias, bn, co, self.device)
         flags = 0
@@ -488,11 +489,9 @@ class PlanBuilder:
         # has that form for the shape; otherwise the plain fp32 stem
         stem_s = False
         if self.split and x.nchw and not use_s:
-            probe = ConvDesc(B=x.B, H=x.H, W=x.W, Cin=ci, Ho=Ho, Wo=Wo, Cout=co, KH=kh, KW=kw,
-                             stride=stride, pad_h=padding, pad_w=padding, dil=dilation,
-                             in_layout=LAYOUT_NCHW, out_layout=LAYOUT_NHWC, dtype=self.cdtype,
+            probe = ConvDesc(in_layout=LAYOUT_NCHW, out_layout=LAYOUT_NHWC, dtype=self.cdtype,
                              OH=Ho, OW=Wo, oy_mul=1, ox_mul=1,
-                             flags=CONV_STEM_F32S | (CONV_STEM_MAXPOOL if fuse_pool else 0))
+                             flags=CONV_STEM_F32S | (CONV_STEM_MAXPOOL if fuse_pool else 0), **base)
             stem_s = bool(self.lib.cn_stem_f32s_supported(ctypes.byref(probe)))
         if use_s:
             wp, factor = self._pack(weight, wsources, f32s=True)
@@ -551,14 +550,13 @@ class PlanBuilder:
                     residual = self.plain(residual)
                     flags |= CONV_R_PLAIN
                 assert residual.pitch == out.pitch
+        # tensors, dtype and flags are final from here on: the launch's descriptor (ctl follows below)
+        base.update(in_layout=LAYOUT_NCHW if x.nchw else LAYOUT_NHWC, in_pitch=x.pitch,
+                    out_layout=LAYOUT_NCHW if out.nchw else LAYOUT_NHWC, out_pitch=out.pitch,
+                    OH=Ho, OW=Wo, oy_mul=1, oy_add=0, ox_mul=1, ox_add=0, relu=int(relu),
+                    dtype=cd, flags=flags, res_pitch=res_pitch)
         if res_pitch:
-            probe = ConvDesc(B=x.B, H=x.H, W=x.W, Cin=ci, Ho=Ho, Wo=Wo, Cout=co, KH=kh, KW=kw,
-                             stride=stride, pad_h=padding, pad_w=padding, dil=dilation,
-                             in_layout=LAYOUT_NCHW if x.nchw else LAYOUT_NHWC, in_pitch=x.pitch,
-                             out_layout=LAYOUT_NCHW if out.nchw else LAYOUT_NHWC, out_pitch=out.pitch,
-                             OH=Ho, OW=Wo, oy_mul=1, oy_add=0, ox_mul=1, ox_add=0, relu=int(relu),
-                             dtype=cd, flags=flags, res_pitch=res_pitch)
-            if not self.lib.cn_conv2d_res_pitch_supported(ctypes.byref(probe)):
+            if not self.lib.cn_conv2d_res_pitch_supported(ctypes.byref(ConvDesc(**base))):
                 # this layer's kernel wants the residual at the output's pitch: write a private tensor
                 # (the caller's concat copies it into the buffer)
                 assert out_given and residual.pitch == (residual.C if residual.fmt != "f32s"
@@ -582,16 +580,9 @@ class PlanBuilder:
         scale = None if scale is None else scale.contiguous()
         shift = None if shift is None else shift.contiguous()
         self.keep += [scale, shift]
-        d = ConvDesc(B=x.B, H=x.H, W=x.W, Cin=ci, Ho=Ho, Wo=Wo, Cout=co, KH=kh, KW=kw,
-                     stride=stride, pad_h=padding, pad_w=padding, dil=dilation,
-                     in_layout=LAYOUT_NCHW if x.nchw else LAYOUT_NHWC, in_pitch=x.pitch,
-                     out_layout=LAYOUT_NCHW if out.nchw else LAYOUT_NHWC, out_pitch=out.pitch,
-                     OH=Ho, OW=Wo, oy_mul=1, oy_add=0, ox_mul=1, ox_add=0, relu=int(relu),
-                     dtype=cd, flags=flags)
+        d = ConvDesc(**base)
         if ctl is not None:
             d.ctl = ctl
-        if res_pitch:
-            d.res_pitch = res_pitch
         fl = 2 * x.B * Ho * Wo * co * ci * kh * kw
         by = 4 * (x.B * x.H * x.W * ci + x.B * out.H * out.W * co * (2 if residual is not None else 1)
                   + co * ci * kh * kw)

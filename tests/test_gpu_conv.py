@@ -803,3 +803,73 @@ def test_projection_1x1_kernel(dev, cfg):
                 assert float(err.max()) < TOL, (key46, out_plain, float(err.max()))
     # the two kernels agree far inside the bar (same arithmetic, different summation order)
     assert float((got[1, True] - got[0, True]).abs().max()) < 2e-5 * float(ref.abs().max())
+
+
+@pytest.mark.parametrize("mode", ["f32s_c3p", "f32s_halo", "fp32"])
+@pytest.mark.parametrize("W", [16, 32], ids=["8x16tile", "4x32tile"])
+@pytest.mark.parametrize("Cin", [32, 64], ids=["nosplit", "split2"])
+def test_residual_slice_pitch_contract(dev, Cin, W, mode):
+    """cn_conv2d_res_pitch_supported is the contract of cn_conv2d for a residual at its own pixel pitch
+    (3x3 / s1 / p1, B = 1, H = 8, Cout = 64; the residual is channels 32..95 of a 128-channel tensor, the
+    output has its own pitch), on the persistent kernel (key 28 = 2: every shape), the LDS-halo kernel
+    (key 28 = 0) and in fp32, called on the C ABI with the workspace cn_conv2d_workspace_bytes asks for.
+    Cin = 32: KT = 9 < 16, no split is wanted: the query says 1, cn_conv2d returns CN_OK and the result is
+    torch's.  Cin = 64: KT = 18, two K slices at the default keys 16 / 17: the layer would run on the
+    implicit-GEMM kernel, which has no residual pitch: the query says 0, cn_conv2d answers
+    CN_ERR_UNSUPPORTED from the host and launches nothing."""
+    import ctypes
+    from centernet_amd import native
+    from centernet_amd.engine import Act, prescale_rows
+    lib = native.lib()
+    B, H, Cout, RC, R0 = 1, 8, 64, 128, 32
+    f32s = mode != "fp32"
+    x = torch.from_numpy(synth.normal((B, Cin, H, W), 1.0, 41))
+    w = torch.from_numpy(synth.normal((Cout, Cin, 3, 3), (2.0 / (Cin * 9)) ** 0.5, 42))
+    scale = torch.from_numpy(synth.normal((Cout,), 0.2, 43)) + 1.0
+    shift = torch.from_numpy(synth.normal((Cout,), 0.3, 44))
+    wide = torch.from_numpy(synth.normal((B, RC, H, W), 1.0, 45))
+    ref = F.relu(F.conv2d(x, w, None, 1, 1) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+                 + wide[:, R0:R0 + Cout])
+
+    def to_dev(t_nchw):     # NHWC on the device; f32s modes: as an f32s tensor (exponent 0)
+        t = t_nchw.permute(0, 2, 3, 1).contiguous().to(dev)
+        if not f32s:
+            return t
+        C = t.shape[-1]
+        s = torch.zeros_like(t)
+        native.check(lib.cn_f32_to_f32s_scaled(native.ptr(t), native.ptr(s), B * H * W, C, C, C, 1.0, None,
+                                               native.stream_ptr()), "cn_f32_to_f32s")
+        return s
+    with native.tuning({28: 2 if mode == "f32s_c3p" else 0}):
+        cd = native.DTYPE_F32S if f32s else native.DTYPE_F32
+        wd, k = w.to(dev), scale.to(dev)
+        if f32s:
+            wd, factor = prescale_rows(wd)
+            k = k * factor
+        wd, k, sh = wd.contiguous(), k.contiguous(), shift.to(dev)
+        wp = torch.empty(lib.cn_packed_conv_weight_elems(Cout, Cin, 3, 3, cd), device=dev, dtype=torch.float32)
+        native.check(lib.cn_pack_conv_weight(native.ptr(wd), native.ptr(wp), Cout, Cin, 3, 3, cd,
+                                             native.stream_ptr()), "cn_pack_conv_weight")
+        xd, rd = to_dev(x), to_dev(wide)
+        y = torch.full((B, H, W, Cout), 7.0, device=dev)
+        d = native.ConvDesc(B=B, H=H, W=W, Cin=Cin, Ho=H, Wo=W, Cout=Cout, KH=3, KW=3, stride=1, pad_h=1,
+                            pad_w=1, dil=1, in_layout=native.LAYOUT_NHWC, in_pitch=Cin,
+                            out_layout=native.LAYOUT_NHWC, out_pitch=Cout, OH=H, OW=W, oy_mul=1, ox_mul=1,
+                            relu=1, dtype=cd, res_pitch=RC)
+        d.ctl.x_mul = d.ctl.res_mul = 1.0
+        supported = lib.cn_conv2d_res_pitch_supported(ctypes.byref(d))
+        need = lib.cn_conv2d_workspace_bytes(ctypes.byref(d))
+        ws = torch.empty(max(need, 16) // 4, device=dev, dtype=torch.float32)
+        rc = lib.cn_conv2d(ctypes.byref(d), native.ptr(xd), native.ptr(wp), native.ptr(k), native.ptr(sh),
+                           ctypes.c_void_p(rd.data_ptr() + 4 * R0), native.ptr(y),
+                           native.ptr(ws) if need else None, need, native.stream_ptr())
+        torch.cuda.synchronize()
+    print("Cin %d W %d %s: supported %d, workspace %d bytes, rc %d" % (Cin, W, mode, supported, need, rc))
+    if Cin == 32:
+        assert (supported, need, rc) == (1, 0, native.CN_OK)
+        got = Act(y, B, H, W, Cout, fmt="f32s" if f32s else "f32").to_float()
+        _check(got.permute(0, 3, 1, 2).cpu(), ref)
+    else:
+        assert supported == 0 and need == 2 * B * H * W * Cout * 4
+        assert rc == -2                                 # CN_ERR_UNSUPPORTED
+        assert bool((y == 7.0).all())                   # nothing was launched on y
