@@ -1297,12 +1297,19 @@ static P3Args p3_args(const ConvCall &c, int H, int W, int npar)
     return a;
 }
 
+// The persistent grid: a multiple of 8 (one share per XCD), never more than one workgroup per item, and per XCD
+// at most cn_set_tuning key 47 workgroups (default 64: two per CU)
+static dim3 p3_grid(const P3Args &a)
+{
+    int per_xcd = cn_cdiv(a.items, 8);
+    if (per_xcd > cn_knobs.c3p_grid) per_xcd = cn_knobs.c3p_grid;
+    return dim3(8 * per_xcd);
+}
+
 int cn_deconv4x4s2_persist(const ConvCall &c, hipStream_t st)
 {
     const P3Args a = p3_args(c, c.H, c.W, 4);
-    int per_xcd = cn_cdiv(a.items, 8);
-    if (per_xcd > 64) per_xcd = 64;
-    const dim3 grid(8 * per_xcd), block(p3_threads(4, false));
+    const dim3 grid = p3_grid(a), block(p3_threads(4, false));
 #define P3_LAUNCH4(OP, PIPE)                                                                                     \
     do {                                                                                                         \
         CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, OP, false, false, 4, false, PIPE>), P_LDS);                       \
@@ -1335,9 +1342,7 @@ bool cn_conv3x3s2p_takes(const ConvCall &c)
 int cn_conv3x3s2_persist(const ConvCall &c, hipStream_t st)
 {
     const P3Args a = p3_args(c, c.Ho, c.Wo, 1);   // Ho = (H - 1) / 2 + 1: the caller's route checks the geometry
-    int per_xcd = cn_cdiv(a.items, 8);
-    if (per_xcd > 64) per_xcd = 64;
-    const dim3 grid(8 * per_xcd), block(p3_threads(9, true));
+    const dim3 grid = p3_grid(a), block(p3_threads(9, true));
 #define P3_LAUNCHS2(OP, PIPE)                                                                                    \
     do {                                                                                                         \
         CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, OP, false, false, 9, true, PIPE>), P_LDS);                        \
@@ -1391,10 +1396,7 @@ int cn_conv3x3s1_persist(const ConvCall &c, hipStream_t st)
     a.res_bytes = (int)((long)c.B * c.H * c.W * c.res_pitch * 4);   // < 2^31 (cn_conv3x3p_takes)
     a.res_plain = c.res_plain;
     a.res_mul = (c.ctl && c.ctl->res_mul != 0.f) ? c.ctl->res_mul : 1.f;
-    // two workgroups per CU, a multiple of 8 (one share per XCD), never more than one per item
-    int per_xcd = cn_cdiv(a.items, 8);
-    if (per_xcd > 64) per_xcd = 64;
-    const dim3 grid(8 * per_xcd), block(384);
+    const dim3 grid = p3_grid(a), block(384);
 #define P3_LAUNCH_(R, OP, PIPE)                                                                                  \
     do {                                                                                                         \
         CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<R, OP, false, false, 9, false, PIPE>), P_LDS);                       \
@@ -1475,9 +1477,7 @@ int cn_heads3x3p(const void *x, int B, int H, int W, int Cin, int in_pitch, cons
     a.range = ctl ? ctl->range : nullptr;
     a.stagger = cn_knobs.c3p_stagger;
     a.knobs = cn_knobs.c3p_knobs;
-    int per_xcd = cn_cdiv(a.items, 8);
-    if (per_xcd > 64) per_xcd = 64;
-    const dim3 grid(8 * per_xcd), block(384);
+    const dim3 grid = p3_grid(a), block(384);
     // the heads exist in the pipelined schedule only: their unpipelined instantiation kept three barriers
     // reachable with an LDS read in flight (tools/audit_barriers.py) and is no longer built; key 30 bit 1
     // does not reach this launch

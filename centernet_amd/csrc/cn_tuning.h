@@ -9,7 +9,7 @@ struct CnTuning {
         split_min_chunks, split_max, stagger_pct, occ4, f32s_lds_weights, f32s_policy, dcn_tile2d, dcn_form,
         heads_remap, heads_reg, stem16s, c3p, c3p_stagger, c3p_knobs, c3p_heads, c3p_deconv, c3p_s2, dcn_team,
         dcn_team_wgs, dcn_team_stagger, offconv, offconv_teams1, dcn_wide, dcn_wide_wgs, stem_dbg, stem_stagger,
-        dcn_wide_prefetch, proj;
+        dcn_wide_prefetch, proj, c3p_grid;
 };
 extern CnTuning cn_knobs;   // the one instance (cn_conv.hip, next to cn_set_tuning / cn_get_tuning / cn_reset_tuning)
 
@@ -63,6 +63,9 @@ constexpr CnTuningKey CN_TUNING_KEYS[] = {
     {31, &CnTuning::c3p_heads, 1, 0, 1},          // the fused heads (hidden width 64) on this kernel; 0 = halo kernel
     {32, &CnTuning::c3p_deconv, 1, 0, 1},         // ConvTranspose2d(4, 2, 1) in parity form on this kernel; 0 = halo kernel
     {33, &CnTuning::c3p_s2, 1, 0, 1},             // 3x3 / stride 2 / pad 1 in parity-plane form on this kernel; 0 = implicit GEMM
+    // workgroups per XCD of a launch, at most (64 = two per CU).  For tests: a smaller cap gives every workgroup
+    // several items at shapes whose float64 reference is cheap (tests/test_gpu_c3p_items.py)
+    {47, &CnTuning::c3p_grid, 64, 1, 64},
     // team form of the deformable kernel (cn_dcn3.hip)
     // 0 = off, 1 = layers with <= 64 output channels, 2 = every layer it takes (T mode), 3 = every layer, N mode
     // where Cout is a multiple of 128 and that still fills the chip

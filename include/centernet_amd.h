@@ -157,6 +157,8 @@ const char *cn_arch(void);
  * key 31: 1 = the fused heads with a 64-wide hidden layer run on it (default), 0 = on the LDS-halo kernel.
  * key 32: 1 = ConvTranspose2d(4, 2, 1) runs on it in parity form (default), 0 = on the LDS-halo kernel.
  * key 33: 1 = 3x3 / stride 2 / pad 1 runs on it in parity-plane form (default), 0 = on the implicit GEMM.
+ * key 47: workgroups per XCD of one of its launches, at most, 1 ... 64 (default 64: two per CU).  For tests:
+ *         with a smaller cap every workgroup walks several items at small shapes.
  * Team form of the f32s deformable kernel (cn_dcn3.hip):
  * key 36: when key 23 = 0: 0 = off, 1 = layers with <= 64 output channels, 2 = every layer it takes
  *         (T mode), 3 = every layer, N mode where Cout is a multiple of 128 and that still fills the

@@ -3,7 +3,7 @@ pairs the library accepts, every key's default, and that the header documents ex
 
 EXPECTED is written out here on purpose, independent of the table in csrc/cn_tuning.h: it is the set the
 library accepted before the knobs moved into that table (a sweep of keys -1 ... 64 over the values below:
-43 keys, 17 414 accepted pairs) and the initialisers the knobs had."""
+43 keys, 17 414 accepted pairs) and the initialisers the knobs had, plus key 47 (1 ... 64: 44 keys, 17 478 pairs)."""
 import ctypes
 import os
 import re
@@ -31,6 +31,7 @@ EXPECTED = {
     29: (_r(0, 255), 0), 30: (_r(0, 255), 2), 31: ({0, 1}, 1), 32: ({0, 1}, 1), 33: ({0, 1}, 1), 36: (_r(0, 3), 3),
     37: (_r(1, 4096), 512), 38: (_r(0, 1024), 32), 39: ({0, 1}, 1), 40: (_r(0, 1000000), 768), 41: ({0, 1}, 1),
     42: (_r(1, 4096), 256), 43: (_r(0, 31), 0), 44: (_r(0, 1024), 0), 45: ({0, 1}, 1), 46: ({0, 1}, 1),
+    47: (_r(1, 64), 64),
 }
 RETIRED = (3, 11)
 
@@ -56,10 +57,10 @@ def test_version():
 
 
 def test_accepted_pairs_are_exactly_the_recorded_ones(lib):
-    assert len(EXPECTED) == 43
+    assert len(EXPECTED) == 44
     swept = set(VALUES)
     want = {(k, v) for k, (vals, _) in EXPECTED.items() for v in vals & swept}
-    assert len(want) == 17414
+    assert len(want) == 17478
     got = set()
     for key in KEYS:
         for value in VALUES:
@@ -93,7 +94,7 @@ def test_set_then_get_round_trips_and_a_refused_set_changes_nothing(lib):
 
 def test_unknown_keys_cannot_be_read(lib):
     v = ctypes.c_int(7)
-    for key in (0, 25, 34, 35, 47):
+    for key in (0, 25, 34, 35, 48):
         assert lib.cn_get_tuning(key, ctypes.byref(v)) == UNSUPPORTED, key
         assert v.value == 7
 
