@@ -824,6 +824,108 @@ extern "C" int cn_flip_average_f32(float *x_pair, float *out, int C, int H, int 
     return cn_flip_average_f32_batch(x_pair, out, 1, C, H, W, chan_src, chan_sign, apply_sigmoid, 0, stream);
 }
 
+// ---- canvas masks (--keep_res batches of mixed input sizes): image b of a batch owns the
+// rectangle rects[b] of a common canvas; what a launch wrote outside it is put back to the value the
+// convolution's zero padding has there.  Store-only: no loads of the tensor, no LDS, no atomics.  One
+// workgroup per (row block, image); a workgroup of an image whose rectangle is the whole tensor returns at
+// once, a row inside the rectangle's rows clears its left and right margins only (nothing when there are none).
+namespace {
+
+constexpr int MASK_ROWS = 8;      // rows of one workgroup (NHWC), rows of C * H (NCHW)
+
+struct mask_span { int x0, x1, y0, y1; };
+
+// rects[b] >> shift, clipped to the H x W tensor (an inverted rectangle keeps nothing)
+__device__ inline mask_span mask_kept(const cn_rect *__restrict__ rects, int b, int shift, int H, int W)
+{
+    const cn_rect r = rects[b];
+    mask_span k;
+    k.x0 = min(max(r.x0 >> shift, 0), W);
+    k.x1 = min(max(r.x1 >> shift, k.x0), W);
+    k.y0 = min(max(r.y0 >> shift, 0), H);
+    k.y1 = min(max(r.y1 >> shift, k.y0), H);
+    if (k.x0 == k.x1 || k.y0 == k.y1) k.x0 = k.x1 = k.y0 = k.y1 = 0;
+    return k;
+}
+
+// t: the first masked channel of pixel (0, 0, 0); a pixel is `pitch` floats, q4 16-byte units of it are cleared
+__global__ __launch_bounds__(256) void mask_rects_nhwc_kernel(float *__restrict__ t, int H, int W, int pitch,
+                                                              int q4, const cn_rect *__restrict__ rects, int shift)
+{
+    const int b = blockIdx.y;
+    const mask_span k = mask_kept(rects, b, shift, H, W);
+    if (k.x0 == 0 && k.x1 == W && k.y0 == 0 && k.y1 == H) return;
+    const int ya = blockIdx.x * MASK_ROWS, yb = min(ya + MASK_ROWS, H);
+    const cn_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int y = ya; y < yb; ++y) {
+        const bool inside = y >= k.y0 && y < k.y1;
+        const int left = inside ? k.x0 : W;            // columns [0, left) and [right, W) are cleared
+        const int right = inside ? k.x1 : W;
+        const int n = (left + (W - right)) * q4;
+        float *row = t + ((size_t)b * H + y) * (size_t)W * pitch;
+        for (int i = threadIdx.x; i < n; i += blockDim.x) {
+            const int px = i / q4, q = i - px * q4;
+            const int x = px < left ? px : px - left + right;
+            *reinterpret_cast<cn_f32x4 *>(row + (size_t)x * pitch + q * 4) = zero;
+        }
+    }
+}
+
+// t (B, C, H, W): rows of C * H, W floats each
+__global__ __launch_bounds__(256) void mask_rects_nchw_kernel(float *__restrict__ t, int C, int H, int W,
+                                                              const cn_rect *__restrict__ rects, int shift, float fill)
+{
+    const int b = blockIdx.y;
+    const mask_span k = mask_kept(rects, b, shift, H, W);
+    if (k.x0 == 0 && k.x1 == W && k.y0 == 0 && k.y1 == H) return;
+    const int rows = C * H;
+    const int ra = blockIdx.x * MASK_ROWS, rb = min(ra + MASK_ROWS, rows);
+    for (int r = ra; r < rb; ++r) {
+        const int y = r % H;
+        const bool inside = y >= k.y0 && y < k.y1;
+        const int left = inside ? k.x0 : W;
+        const int right = inside ? k.x1 : W;
+        const int n = left + (W - right);
+        float *row = t + ((size_t)b * rows + r) * (size_t)W;
+        for (int i = threadIdx.x; i < n; i += blockDim.x)
+            row[i < left ? i : i - left + right] = fill;
+    }
+}
+}  // namespace
+
+extern "C" int cn_mask_rects_f32(void *t_nhwc, int B, int H, int W, int pitch, int c_off, int C,
+                                 const cn_rect *rects_dev, int shift, void *stream)
+{
+    if (!t_nhwc || !rects_dev) return CN_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || pitch <= 0 || c_off < 0 || c_off + C > pitch || B > 65535)
+        return CN_ERR_SHAPE;
+    if (shift < 0 || shift > 30) return CN_ERR_SHAPE;
+    // whole 32-channel groups (128 bytes, both activation encodings), cut at the pitch: a tensor narrower
+    // than a group (the 16-channel plain layers) is cleared in whole pixels
+    const int width = min(cn_cdiv(C, 32) * 32, pitch - c_off);
+    if ((pitch & 3) || (c_off & 3) || (width & 3)) return CN_ERR_ALIGN;
+    float *t = (float *)t_nhwc + c_off;
+    if (!cn_aligned16(t)) return CN_ERR_ALIGN;
+    dim3 grid(cn_cdiv(H, MASK_ROWS), B);
+    hipLaunchKernelGGL(mask_rects_nhwc_kernel, grid, dim3(256), 0, (hipStream_t)stream, t, H, W, pitch, width >> 2,
+                       rects_dev, shift);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_mask_rects_nchw_f32(float *t, int B, int C, int H, int W, const cn_rect *rects_dev, int shift,
+                                      float fill, void *stream)
+{
+    if (!t || !rects_dev) return CN_ERR_NULL;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (long long)C * H > 0x7fffffffLL) return CN_ERR_SHAPE;
+    if (shift < 0 || shift > 30) return CN_ERR_SHAPE;
+    dim3 grid(cn_cdiv(C * H, MASK_ROWS), B);
+    hipLaunchKernelGGL(mask_rects_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, t, C, H, W, rects_dev,
+                       shift, fill);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 // ---- box calibration (bench.py "box_calibration"): what THIS box's matrix pipe and HBM deliver
 // right now, so that a headline can be read against the box it ran on.  Not on the product path.
 namespace {

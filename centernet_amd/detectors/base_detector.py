@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import native
-from ..frame_pipe import FramePipe, ImagePipe
+from ..frame_pipe import FramePipe, ImagePipe, ImageTables
 from ..image import (check_pixel_format, get_affine_transform, invert_affine, normalize_chw, nv12_size,
                      resize_bilinear, warp_affine)
 from ..model import create_model, load_model
@@ -266,10 +266,11 @@ class BaseDetector(object):
     def _arrays_kw(self, arrays):
         return {"arrays": True} if arrays and self._list_results else {}
 
-    def _run_scale(self, images, flip):
+    def _run_scale(self, images, flip, rects=None):
         """Task hook of the frame pipeline: network + (with ``flip``: the batched flip average of the
         (2B, 3, H, W) frame / mirror pairs) + decode of one test scale -> raw (B, K, .) detections in
-        output-grid units, asynchronously (as ``run_batch``)."""
+        output-grid units, asynchronously (as ``run_batch``).  ``rects``: the rectangles of a canvas batch
+        (tasks with ``_canvas_task``), handed to the network as they are."""
         raise NotImplementedError
 
     def _results_merged(self, per_scale, **kw):
@@ -304,6 +305,12 @@ class BaseDetector(object):
         network input size): each image uploaded on its own, pre-processed into its slice of the batch, with
         its own meta."""
         return self._run_uploaded_sync([self._device_frame(f) for f in images], scales, **kw)
+
+    def _run_images_sync_keep_res(self, images, scales, **kw):
+        """``_run_images_sync`` under --keep_res, where every image has its own network input size: each image
+        through its own single-image forward at every test scale, host tail (the comparison path of the canvas
+        pipe, and its re-run path after an f32s re-calibration)."""
+        return [self._run_uploaded_sync([self._device_frame(f)], scales, **kw)[0] for f in images]
 
     def _run_uploaded_sync(self, uploaded, scales, **kw):
         flip = bool(self.opt.flip_test)
@@ -422,6 +429,13 @@ class BaseDetector(object):
         """One item of ``run_images_stream``'s iterable -> (images, the pipe's side array or None)."""
         return batch, None
 
+    _canvas_task = False     # the task batches mixed input sizes on a canvas (ctdet, multi_pose)
+
+    def _canvas_batches(self):
+        """Whether --keep_res batches of mixed sizes run on a canvas (``ImagePipe`` with ``canvas=True``): the
+        task takes rectangles (``_canvas_task``) and the --keep_res option is set."""
+        return self._canvas_task and bool(getattr(self.opt, "keep_res", False)) and not self.opt.fix_res
+
     def _images_one_size(self, images, what):
         """Argument check of ``run_images`` / ``run_images_stream``; True when the images have one size."""
         if len(images) == 0:
@@ -430,53 +444,87 @@ class BaseDetector(object):
             if not isinstance(f, np.ndarray) or f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8:
                 raise ValueError("%s needs (H, W, 3) uint8 BGR images" % what)
         one = len({f.shape for f in images}) == 1
-        if not self._fixed_input() and not one:
+        if not self._fixed_input() and not one and not self._canvas_batches():
             raise ValueError("%s with --keep_res: images of mixed sizes give network inputs of mixed sizes, which "
                              "one batch cannot hold (drop --keep_res, or batch images of one size)" % what)
         return one
 
-    def _image_pipe_for(self, images, depth):
+    def _image_pipe_for(self, images, depth, canvas=False, pinned=None):
         flip = bool(self.opt.flip_test)
         scales = self._pipe_scales()
         key = ("images", len(images), tuple(scales), flip, bool(getattr(self.opt, "nms", False)), depth)
+        if canvas:
+            key += ("canvas", pinned)
         pipes = self.__dict__.setdefault("_pipes", {})
         if key not in pipes:
             if len(pipes) >= 4:
                 pipes.pop(next(iter(pipes))).pool.shutdown(wait=False)
-            pipes[key] = ImagePipe(self, len(images), scales, flip, depth)
+            pipes[key] = ImagePipe(self, len(images), scales, flip, depth, canvas, pinned)
         return pipes[key]
 
-    def run_images(self, images, arrays=False):
+    def _canvas_pipe_for(self, images, depth, canvas, what):
+        """The canvas pipe of a --keep_res batch; ``canvas``: ``run_images``' argument, checked here against
+        the batch (``ImageTables.check_canvas``)."""
+        if not self._canvas_batches():
+            raise ValueError("%s: canvas= is for --keep_res batches of the ctdet and multi_pose tasks" % what)
+        if canvas is not None:
+            canvas = ImageTables(self, ()).check_canvas([(int(f.shape[0]), int(f.shape[1])) for f in images], canvas)
+        return self._image_pipe_for(images, depth, True, canvas)
+
+    def run_images(self, images, arrays=False, canvas=None):
         """A list of (H_i, W_i, 3) uint8 BGR images of ANY sizes -> list of per-image results, what
         ``run(image)['results']`` returns for each (every test scale, flip-test and --nms as set) -- ``run_frames``
         for a dataset instead of a video.  Fixed-resolution mode: every image is warped into the same network
         input, so the batch is ``run_frames``' batch; the images are packed back to back into ONE uint8 upload
         with a table of per-image descriptors, pre-processed in one launch per test scale (plus one resize
         launch where the scale resizes), and the tail kernels map every image back with its own inverse map.
-        With --keep_res mixed sizes raise ``ValueError`` (images of one size go to ``run_frames``).
+        With --keep_res the network input follows the image: images of one size go to ``run_frames``; images of
+        mixed sizes share, per test scale, a CANVAS -- the maxima of the batch's input heights and widths --
+        in which every image's own padded input sits at the origin of its slice, and the network runs a plan
+        whose masks keep each image apart from the rest of the canvas (ctdet and multi_pose; the other tasks
+        raise ``ValueError`` for mixed sizes).  ``canvas=(h, w)`` pins the canvas of scale 1 -- multiples of
+        pad + 1, at least every image's input at scale 1; other test scales take the pinned canvas through the
+        images' own rule -- so that a data set runs ONE plan per test scale, one-size batches included; anything
+        else raises ``ValueError``.  Without it every new canvas is a new plan (the plans are an LRU of
+        ``CN_PLAN_CACHE`` shapes, 8 by default: raise it for a data set of many sizes).
         ``arrays``: as ``run_frames``."""
-        if self._images_one_size(images, "run_images") and not self._fixed_input():
+        one = self._images_one_size(images, "run_images")
+        if canvas is None and not self._fixed_input() and one:
             return self.run_frames(images, arrays)
-        pipe = self._image_pipe_for(images, 1)
+        if canvas is not None or not self._fixed_input():
+            pipe = self._canvas_pipe_for(images, 1, canvas, "run_images")
+        else:
+            pipe = self._image_pipe_for(images, 1)
         pipe.submit(0, images)
         return pipe.collect(0, images, arrays)
 
-    def run_images_stream(self, batches, depth=3, arrays=False):
+    def run_images_stream(self, batches, depth=3, arrays=False, canvas=None):
         """``run_images`` over an iterable of batches (lists of images of any sizes, every batch of one length
         B -- another length raises ``ValueError``), pipelined as ``run_frames_stream``.  Yields the per-image
-        results batch by batch, in order.  With --keep_res every batch goes to ``run_frames`` on its own."""
+        results batch by batch, in order.  With --keep_res a task without canvas batches sends every batch to
+        ``run_frames`` on its own; ctdet and multi_pose pipeline the mixed-size batches on their canvases
+        (``run_images``) and send a one-size batch to ``run_frames`` once the batches before it are out.
+        ``canvas``: as ``run_images``, one canvas for the whole stream, one-size batches included; without it
+        the stream may see a new canvas, which means a new plan, with every batch (``CN_PLAN_CACHE`` bounds the
+        plans kept: raise it for a data set of many sizes, or pin the canvas)."""
         pipe, B, pending, n = None, None, collections.deque(), 0
         for batch in batches:
             images, side = self._images_and_side(batch)
-            self._images_one_size(images, "run_images_stream")
+            one = self._images_one_size(images, "run_images_stream")
             if B is None:
                 B = len(images)
             elif len(images) != B:
                 raise ValueError("run_images_stream needs batches of one length (%d, then %d)" % (B, len(images)))
-            if not self._fixed_input():          # (images of one size, or the check above has raised)
-                yield self.run_frames(images, arrays)
+            keep_res = canvas is not None or not self._fixed_input()
+            if keep_res and canvas is None and (one or not self._canvas_batches()):
+                while pending:                             # (canvas batches still on the device come first)
+                    j, fr = pending.popleft()
+                    yield pipe.collect(j, fr, arrays)
+                yield self.run_frames(images, arrays)      # (images of one size, or the check above has raised)
                 continue
-            if pipe is None:
+            if keep_res:
+                pipe = self._canvas_pipe_for(images, depth, canvas, "run_images_stream")
+            elif pipe is None:
                 pipe = self._image_pipe_for(images, depth)
             if len(pending) == depth:
                 j, fr = pending.popleft()
@@ -502,22 +550,23 @@ class BaseDetector(object):
         if names != self.model.deferral():
             self.model.defer_heads(names)
 
-    def _forward_deferred(self, images, probe=None):
+    def _forward_deferred(self, images, probe=None, rects=None):
         """The network of ``run_batch``: the deferred-heads plan where it applies, else the dense one.
-        ``probe``: see ``run_batch``; its ``net_events`` are filled here."""
+        ``probe``: see ``run_batch``; its ``net_events`` are filled here.  ``rects``: see ``run_batch``."""
         self._sync_deferral()
+        kw = {} if rects is None else {"rects": rects}
         if probe is None:
-            return self.model(images, borrow=True, deferred=True)[-1]
+            return self.model(images, borrow=True, deferred=True, **kw)[-1]
         probe['net_events'] = []
         return self.model(images, borrow=True, deferred=True, events=probe['net_events'],
-                          event_after=probe.get('event_after'))[-1]
+                          event_after=probe.get('event_after'), **kw)[-1]
 
     def _decode_batch(self, out):
         """Task hook: decode of ``_forward_deferred``'s output -- at the cells where the plan deferred heads
         (``out['_deferred']``), else the dense decode; the maps are logits, the sigmoids are in the kernels."""
         raise NotImplementedError
 
-    def run_batch(self, images, probe=None):
+    def run_batch(self, images, probe=None, rects=None):
         """``images`` (B,3,H,W) fp32, already normalised, on the device -> the task's raw (B,K,.)
         detections in output-grid units (device tensor).  Asynchronous: nothing here waits for
         the device, so the f32s range words of the forward are NOT looked at yet -- call
@@ -525,10 +574,14 @@ class BaseDetector(object):
         once per synchronisation point, the words accumulate over the forwards in between).
         ``probe``: optional dict for measurement (bench.py): ``event_after`` (set of launch
         indices) in, ``net_events`` (HIP events at those launch boundaries) and ``dec_events``
-        (before / after the decode) out."""
+        (before / after the decode) out.
+        ``rects``: a canvas batch (``PlannedModule.forward``): image b is the rectangle ``rects[b]`` =
+        (x0, y0, x1, y1) of ``images``, a host (B, 4) integer array with every edge a multiple of pad + 1;
+        its detections are those of the image alone, in the output-grid units of the canvas.  ``images`` is
+        zeroed outside the rectangles in place."""
         self._note_unchecked_forward()
         with torch.no_grad():
-            out = self._forward_deferred(images, probe)
+            out = self._forward_deferred(images, probe, rects)
             if probe is None:
                 return self._decode_batch(out)
             e0 = torch.cuda.Event(enable_timing=True)

@@ -95,16 +95,20 @@ class CtdetDetector(BaseDetector):
         return results
 
     # ------------------------------------------------------------------ new surface
-    def _run_scale(self, images, flip):
+    _canvas_task = True
+
+    def _run_scale(self, images, flip, rects=None):
         """One test scale of the frame pipeline: ``run_batch``, or with ``flip`` the (2B, 3, H, W)
         frame / mirror pairs -> network -> batched flip average (``hm`` after the sigmoid, ``reg`` of
-        the un-mirrored frame, as ``process``) -> decode: (B, K, 6), asynchronous."""
+        the un-mirrored frame, as ``process``) -> decode: (B, K, 6), asynchronous.  ``rects``: a canvas
+        batch; with ``flip`` the mirror image's rectangle sits at the canvas' right edge, and the whole-width
+        flip average brings it back onto the frame's."""
         if not flip:
-            return self.run_batch(images)
+            return self.run_batch(images, rects=rects)
         self._note_unchecked_forward()
         self._sync_deferral()        # flip-test defers nothing: plan_for(...) is then this dense plan
         with torch.no_grad():
-            out = self.model(images, borrow=True)[-1]
+            out = self.model(images, borrow=True, **({} if rects is None else {"rects": rects}))[-1]
             hm = flip_average_batch(out['hm'], sigmoid=True)
             wh = flip_average_batch(out['wh'])
             reg = flip_average_batch(out['reg'], first=True) if self.opt.reg_offset else None

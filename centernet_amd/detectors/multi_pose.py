@@ -91,17 +91,20 @@ class MultiPoseDetector(BaseDetector):
         return multi_pose_decode(o['hm'], o['wh'], o['hps'], reg=o['reg'] if self.opt.reg_offset else None,
                                  hm_hp=hm_hp, hp_offset=hp_offset, K=self.opt.K, apply_sigmoid=True)
 
-    def _run_scale(self, images, flip):
+    _canvas_task = True
+
+    def _run_scale(self, images, flip, rects=None):
         """One test scale of the frame pipeline: ``run_batch``, or with ``flip`` the (2B, 3, H, W)
         frame / mirror pairs -> network -> batched flip average (sigmoids in the flip kernel, joints
-        exchanged, offsets of the un-mirrored frame, as ``process``) -> decode: (B, K, 40)."""
+        exchanged, offsets of the un-mirrored frame, as ``process``) -> decode: (B, K, 40).  ``rects``: a canvas
+        batch, as ``CtdetDetector._run_scale``."""
         if not flip:
-            return self.run_batch(images)
+            return self.run_batch(images, rects=rects)
         self._note_unchecked_forward()
         self._sync_deferral()        # flip-test defers nothing: plan_for(...) is then this dense plan
         opt = self.opt
         with torch.no_grad():
-            o = self.model(images, borrow=True)[-1]
+            o = self.model(images, borrow=True, **({} if rects is None else {"rects": rects}))[-1]
             hm = flip_average_batch(o['hm'], sigmoid=True)
             wh = flip_average_batch(o['wh'])
             hps = flip_average_batch(o['hps'], self.flip_idx, offsets=True)

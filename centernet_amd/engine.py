@@ -31,6 +31,10 @@ from .native import (ConvDesc, F32sCtl, LAYOUT_NCHW, LAYOUT_NHWC, DTYPE_F16, DTY
 # below the fp16 limit, and the (high, low) pair keeps its 22 bits down to values 2^-12 of that
 # maximum (absolute error floor 2^-25 stored = 2^-34 of the maximum).
 TOP_LOG2 = 10
+# canvas batches (PlanBuilder ``ragged``): what the heat-map heads hold outside the images' rectangles -- a
+# logit whose logistic is exactly 0 in fp32 -- and the heads that get it
+HM_FILL = -1.0e4
+HEAT_MAPS = ("hm", "hm_hp")
 F16_MAX = 65504.0
 LOW_WATER = 2.0 ** -3      # a per-forward maximum below this (stored units) asks for re-calibration
 LOW_STEP = 6               # ... which lowers an exponent by at most this many binades at a time
@@ -51,6 +55,16 @@ def exponent_for(absmax):
 
 def _out_size(n, k, s, p, d=1):
     return (n + 2 * p - (d * (k - 1) + 1)) // s + 1
+
+
+class CanvasRects(tuple):
+    """The rectangles of a canvas batch as a pipe hands them to ``PlannedModule.forward(x, rects=...)``:
+    ``(host, dev, origin)`` -- the (B, 4) int32 table on the host, its copy on the device (or None) and
+    whether the plan to run is the one for rectangles at the canvas origin (None: as the rectangles say)."""
+    __slots__ = ()
+
+    def __new__(cls, host, dev=None, origin=None):
+        return tuple.__new__(cls, (host, dev, origin))
 
 
 class Act:
@@ -231,9 +245,20 @@ class PlanBuilder:
     RANGE_WORDS = 2 * 64 * 16   # CN_RANGE_WORDS: 2 sides x 64 slots x one word per 64-byte line
 
     def __init__(self, device, B, H, W, dtype=torch.float32, wcache=None, split=None, exps=None,
-                 calibrating=False, track=None, defer=()):
+                 calibrating=False, track=None, defer=(), ragged=False, origin=True):
         assert dtype in (torch.float32, torch.float16)
         self.device = device
+        # ``ragged``: (H, W) is a canvas and image b owns the rectangle ``rects[b]`` of it (network-input
+        # pixels, half-open; Plan.run fills the table): ``add_masks`` puts one store-only launch behind every
+        # op, which returns the op's output outside the rectangles to what zero padding has there.
+        # ``origin``: every rectangle starts at the canvas origin -- the only case in which the stem may keep
+        # its max-pool inside the launch
+        self.ragged, self.origin = bool(ragged), bool(origin)
+        self.rects, self.rect_align = None, 1
+        if self.ragged:
+            if dtype != torch.float32:
+                raise native.NativeError("canvas batches (rects=) are built for the fp32 compute modes only")
+            self.rects = torch.zeros((B, 4), device=device, dtype=torch.int32)
         # heads that are NOT launched densely (PlannedModule.defer_heads): ``heads_from_convs`` leaves
         # them out of the fused launch and puts a DeferredHeads handle into ``self.deferred``
         self.defer = () if calibrating else tuple(defer)
@@ -480,7 +505,8 @@ class PlanBuilder:
         # resnet_dcn.py:138-141): inside the stem kernel when it takes the shape, else a second launch
         fuse_pool = False
         if pool is not None and tuple(pool) == (3, 2, 1) and self.split and x.nchw and out is None \
-                and not out_nchw and residual is None and os.environ.get("CN_FUSE_STEM_POOL", "1") != "0":
+                and not out_nchw and residual is None and os.environ.get("CN_FUSE_STEM_POOL", "1") != "0" \
+                and not (self.ragged and not self.origin):
             probe = ConvDesc(in_layout=LAYOUT_NCHW, out_layout=LAYOUT_NHWC, dtype=self.cdtype, **base)
             fuse_pool = bool(self.lib.cn_stem_maxpool_supported(ctypes.byref(probe)))
         scale, shift = fold_bn(bias, bn, co, self.device)
@@ -1131,6 +1157,61 @@ class PlanBuilder:
         self.flops += fl
         return outs
 
+    def _mask_shift(self, a):
+        """log2 of the canvas size over the size of ``a``: the level of the tensor below the network input."""
+        shift = (self.H // a.H).bit_length() - 1
+        if a.H << shift != self.H or a.W << shift != self.W:
+            raise native.NativeError("canvas batch: a %d x %d tensor is no power-of-two level of the %d x %d canvas"
+                                     % (a.H, a.W, self.H, self.W))
+        self.rect_align = max(self.rect_align, 1 << shift)
+        return shift
+
+    def _mask_op(self, a, fill=None):
+        """The mask launch of activation ``a``: ``cn_mask_rects_f32`` on its channel groups, or for an NCHW
+        tensor ``cn_mask_rects_nchw_f32`` with ``fill`` (the network input is bound at run time)."""
+        lib, rects, shift = self.lib, ctypes.c_void_p(self.rects.data_ptr()), self._mask_shift(a)
+        if a.nchw:
+            is_input, fill = a is self.input, float(fill)
+
+            def run():
+                t = self.input.t if is_input else a.t
+                rc = lib.cn_mask_rects_nchw_f32(ctypes.c_void_p(t.data_ptr()), a.B, a.C, a.H, a.W, rects, shift,
+                                                fill, native.stream_ptr())
+                if rc:
+                    native.check(rc, "cn_mask_rects_nchw_f32")
+            return run, 4 * a.B * a.C * a.H * a.W
+        base = ctypes.c_void_p(a.t.data_ptr())
+
+        def run():
+            rc = lib.cn_mask_rects_f32(base, a.B, a.H, a.W, a.pitch, a.c_off, a.C, rects, shift,
+                                       native.stream_ptr())
+            if rc:
+                native.check(rc, "cn_mask_rects_f32")
+        return run, 4 * a.B * a.H * a.W * a.C
+
+    def add_masks(self, outputs):
+        """Ragged plans: the launch list with its masks -- one on the network input, one behind every op on the
+        tensor the op wrote (a concatenation slice: its own groups), and ``HM_FILL`` on the heat-map heads
+        (their logistic is 0: no cell outside an image becomes a peak).  Tensors that are only read at the pixel
+        they were written for keep what they hold: the deformable stage's offset map and the other head maps."""
+        ops, meta, trace = [], [], []
+
+        def put(run, nbytes):
+            ops.append(run)
+            meta.append(dict(kind="mask", flops=0, bytes=nbytes))
+            trace.append(("mask", None))
+        put(*self._mask_op(self.input, 0.0))
+        for op, m, (kind, a) in zip(self.ops, self.meta, self.trace):
+            ops.append(op)
+            meta.append(m)
+            trace.append((kind, a))
+            if a is not None and not a.nchw and not (a.lid or "").endswith("/om"):
+                put(*self._mask_op(a))
+        for name in HEAT_MAPS:
+            if name in outputs:
+                put(*self._mask_op(outputs[name], HM_FILL))
+        self.ops, self.meta, self.trace = ops, meta, trace
+
     def finish(self):
         """Close the launch list: one tiny launch folds this forward's range words into the
         running (largest, smallest) per-launch maxima the host reads at its next look."""
@@ -1168,6 +1249,8 @@ class Plan:
     """A compiled forward pass for one input shape."""
 
     def __init__(self, builder, outputs):
+        if builder.ragged:
+            builder.add_masks(outputs)
         builder.finish()
         self.b = builder
         self.outputs = outputs  # name -> Act (NCHW)
@@ -1179,7 +1262,26 @@ class Plan:
     def flops(self):
         return self.b.flops
 
-    def run(self, images, events=None, event_after=None, borrow=False, digest=False):
+    def check_rects(self, rects):
+        """Host check of a ragged plan's rectangles: (B, 4) integers (x0, y0, x1, y1) inside the canvas, every
+        edge on a multiple of the coarsest level's stride (an empty rectangle clears its image), and at the
+        canvas origin where the plan was built for that.  Returns them as a (B, 4) int32 array."""
+        import numpy as np
+        b = self.b
+        r = np.ascontiguousarray(np.asarray(rects.cpu() if torch.is_tensor(rects) else rects).astype(np.int64))
+        if r.shape != (b.B, 4):
+            raise ValueError("rects must be (%d, 4): one (x0, y0, x1, y1) per image, got %r" % (b.B, r.shape))
+        if (r < 0).any() or (r[:, 2] > b.W).any() or (r[:, 3] > b.H).any() or (r[:, 0] > r[:, 2]).any() \
+                or (r[:, 1] > r[:, 3]).any():
+            raise ValueError("rects must lie inside the %d x %d canvas" % (b.H, b.W))
+        if (r % b.rect_align).any():
+            raise ValueError("rects must have every edge on a multiple of %d, the network's coarsest stride"
+                             % b.rect_align)
+        if b.origin and (r[:, :2] != 0).any():
+            raise ValueError("this plan was built for rectangles at the canvas origin (origin=True)")
+        return r.astype(np.int32)
+
+    def run(self, images, events=None, event_after=None, borrow=False, digest=False, rects=None):
         """Replay the launch list.  ``events``: optional list that receives one
         torch.cuda.Event per op boundary (len(ops)+1), recorded on the launch stream; with
         ``event_after`` (a set of op indices) events are recorded only at the start and after
@@ -1188,12 +1290,22 @@ class Plan:
         Returns fresh head tensors, like the reference's nn.Module.  ``borrow=True`` returns the
         plan's own persistent head buffers instead (zero-copy): they are OVERWRITTEN by the next
         run of this plan (same B, H, W) -- only for callers that consume them at once, as the
-        detectors do."""
+        detectors do.  ``rects`` (ragged plans): the batch's (B, 4) int32 rectangles, host or device; the
+        first launch then zeroes ``images`` outside them IN PLACE."""
         if not images.is_cuda:
             raise native.NativeError("input batch must be on a HIP device; there is no CPU path")
         native.require_f32(images)
         images = images.contiguous()
         assert tuple(images.shape) == (self.b.B, self.b.input.C, self.b.H, self.b.W), images.shape
+        if (rects is not None) != self.b.ragged:
+            raise native.NativeError("a ragged plan runs with rects, an ordinary plan without")
+        if rects is not None:
+            # into the plan's own table on the launch stream, in front of the first launch (a graph replays
+            # with the same table); a host array has been through ``check_rects``, a device tensor is the
+            # caller's upload of a checked one
+            if not torch.is_tensor(rects):
+                rects = torch.from_numpy(rects)
+            self.b.rects.copy_(rects.reshape(self.b.B, 4), non_blocking=True)
         if self.b._pack_events:
             # weights packed on another stream (or just now): complete before the first launch
             st = torch.cuda.current_stream()
@@ -1396,23 +1508,28 @@ class PlannedModule(torch.nn.Module):
         """logical tensor id -> f32s exponent, or None before the first calibration."""
         return self.__dict__.get("_exps")
 
-    def calibrate(self, x, merge=False):
+    def calibrate(self, x, merge=False, rects=None, origin=True):
         """Measure max |value| of every tensor of the network on the batch ``x`` with the plain
         fp32 kernels (no splits, nothing can saturate) and derive the f32s exponents from it:
         tensor t is then stored as real * 2^-e_t with its largest magnitude in [2^9, 2^10).
         Runs by itself on the first f32s forward, and again when a forward reports a clamped
         value (inputs far outside the calibration batch).  ``merge``: keep the larger of the old
         and the new exponent per tensor.  Costs one fp32-MFMA forward + one pass over the
-        activations; the f32s plans are rebuilt (the packed weights are kept)."""
+        activations; the f32s plans are rebuilt (the packed weights are kept).  ``rects`` / ``origin``: the
+        rectangles of a canvas batch (checked, ``Plan.check_rects``) -- the pass then runs masked, as the
+        forward it calibrates."""
         if not x.is_cuda:
             raise native.NativeError("calibration needs a batch on a HIP device")
         B, C, H, W = x.shape
         lib = native.lib()
         with torch.no_grad():
-            pb = PlanBuilder(x.device, B, H, W, dtype=torch.float32, wcache={}, calibrating=True)
+            pb = PlanBuilder(x.device, B, H, W, dtype=torch.float32, wcache={}, calibrating=True,
+                             ragged=rects is not None, origin=origin)
             outs = self.describe(pb, pb.set_input(C))
             plan = Plan(pb, outs)
-            plan.run(x.contiguous().float(), borrow=True)
+            if rects is not None:
+                rects = plan.check_rects(rects)
+            plan.run(x.contiguous().float(), borrow=True, rects=rects)
             acts = [a for _, a in pb.trace if a is not None and a.lid is not None and not a.nchw]
             words = torch.zeros(len(acts) + 1, device=x.device, dtype=torch.int32)
             st = native.stream_ptr()
@@ -1456,15 +1573,19 @@ class PlannedModule(torch.nn.Module):
         self.__dict__["_plans"] = {}      # plans bake the exponents into their epilogue constants
         return exps
 
-    def plan_for(self, B, H, W, device, deferred=None):
+    def plan_for(self, B, H, W, device, deferred=None, ragged=False, origin=True):
         """The plan of one input shape.  Plans (activations + launch list) are kept in an LRU of
         ``max_plans`` shapes -- --keep_res / multi-scale evaluation sees many (H, W) -- while the
         packed weights live in one per-module cache shared by all of them.  ``deferred``: False = the
         dense plan (every head a map); otherwise the plan the batch entry points of the detectors run,
-        which leaves out the heads of ``defer_heads`` (the same dense plan when none are set)."""
+        which leaves out the heads of ``defer_heads`` (the same dense plan when none are set).  ``ragged``:
+        the plan of a canvas batch (``forward(x, rects=...)``), kept apart from the ordinary plan of the shape
+        and by ``origin``; the LRU, the packed weights and the exponents are the same."""
         cache = self.__dict__.setdefault("_plans", {})
         defer = () if deferred is False else self.deferred_names()
         key = (B, H, W, str(device), self.compute_dtype, self.f32s, self.range_tracking_on, defer)
+        if ragged:
+            key += ("ragged", bool(origin))
         plan = cache.pop(key, None)
         if plan is None:
             native.lib()  # raises if the HIP library is missing
@@ -1472,7 +1593,8 @@ class PlannedModule(torch.nn.Module):
                 pb = PlanBuilder(device, B, H, W, dtype=self.compute_dtype,
                                  wcache=self.__dict__.setdefault("_wcache", {}), split=self.f32s,
                                  exps=self.__dict__.get("_exps"),
-                                 track=None if self.range_tracking_on else False, defer=defer)
+                                 track=None if self.range_tracking_on else False, defer=defer,
+                                 ragged=ragged, origin=origin)
                 x = pb.set_input(3)
                 outs = self.describe(pb, x)
             plan = Plan(pb, outs)
@@ -1540,7 +1662,18 @@ class PlannedModule(torch.nn.Module):
         self.__dict__["_low_cal_at"] = nf
         self.__dict__["_recalibrate"] = "decay"
 
-    def forward(self, x, borrow=False, events=None, event_after=None, check=None, deferred=False):
+    @staticmethod
+    def _canvas_rects(x, rects):
+        """``forward``'s ``rects`` on the host as (B, 4) int64, or None when every rectangle is the canvas."""
+        import numpy as np
+        B, _, H, W = x.shape
+        r = np.asarray(rects.cpu() if torch.is_tensor(rects) else rects).astype(np.int64)
+        if r.shape != (B, 4):
+            raise ValueError("rects must be (%d, 4): one (x0, y0, x1, y1) per image, got %r" % (B, r.shape))
+        return None if (r == np.array([0, 0, W, H])).all() else r
+
+    def forward(self, x, borrow=False, events=None, event_after=None, check=None, deferred=False, rects=None,
+                origin=None, rects_dev=None):
         """[{head: (B,C,H/4,W/4)}] like the reference modules (fresh tensors).  ``deferred=True`` runs the
         deferred-heads plan instead (``defer_heads``): the maps of the remaining heads plus the handle
         under ``"_deferred"`` -- or the dense result when the mode or the network's head form defers
@@ -1548,7 +1681,14 @@ class PlannedModule(torch.nn.Module):
         ``events``: see Plan.run.  ``check``: f32s range check of THIS forward before it returns
         (one stream synchronisation; on a clamped value the module re-calibrates on ``x`` and
         runs again).  Default: on for the fresh-tensor form, off with ``borrow=True`` -- those
-        callers (the detectors) synchronise anyway and call ``range_ok`` there."""
+        callers (the detectors) synchronise anyway and call ``range_ok`` there.
+        ``rects``: a canvas batch -- image b is the rectangle ``rects[b]`` = (x0, y0, x1, y1) of ``x``
+        (network-input pixels, half-open, a HOST (B, 4) integer array; every edge a multiple of the network's
+        coarsest stride) and the head maps inside it are those of the image's own forward; outside it ``hm`` /
+        ``hm_hp`` hold ``HM_FILL`` and the other maps anything.  ``x`` is zeroed outside the rectangles in
+        place.  ``origin``: False builds the plan that also takes rectangles off the canvas origin (default:
+        whether these are); ``rects_dev``: the same table already on the device.  None, or rectangles that
+        all equal the canvas, is the ordinary plan, bit for bit."""
         if self.training:
             raise native.NativeError("centernet_amd implements the inference path only; call .eval()")
         if not x.is_cuda:
@@ -1557,26 +1697,40 @@ class PlannedModule(torch.nn.Module):
                 "CPU restatement under oracle/ is test infrastructure." % x.device)
         B, C, H, W = x.shape
         f32s = self.uses_f32s()
+        cal, rg = {}, {}     # what a canvas batch adds to calibrate and to plan_for
+        if isinstance(rects, CanvasRects):
+            rects, rects_dev, origin = rects
+        if rects is not None:
+            rects = self._canvas_rects(x, rects)
+        if rects is not None:
+            cal = dict(rects=rects, origin=bool((rects[:, :2] == 0).all()) if origin is None else bool(origin))
+            rg = dict(ragged=True, origin=cal["origin"])
         if f32s:
             pending = self.__dict__.pop("_recalibrate", None)
             if self.__dict__.get("_exps") is None:
-                self.calibrate(x)
+                self.calibrate(x, **cal)
             elif pending:
-                self.calibrate(x, merge=True if pending == "merge" else pending)
+                self.calibrate(x, merge=True if pending == "merge" else pending, **cal)
             self.__dict__["_nfwd"] = self.__dict__.get("_nfwd", 0) + 1
         if check is None:
             check = f32s and not borrow
         deferred = bool(deferred)
-        plan = self.plan_for(B, H, W, x.device, deferred)
-        out = plan.run(x, events=events, event_after=event_after, borrow=borrow, digest=bool(check and f32s))
+        plan = self.plan_for(B, H, W, x.device, deferred, **rg)
+        run_rects = None
+        if rects is not None:
+            rects = plan.check_rects(rects)
+            run_rects = rects if rects_dev is None else rects_dev
+        self.__dict__["_ran"] = plan         # (a pipe reads the range words of the plan that ran)
+        out = plan.run(x, events=events, event_after=event_after, borrow=borrow, digest=bool(check and f32s),
+                       rects=run_rects)
         if check and f32s:
             st, bad = plan.range_status()
             if st == "overflow":
-                self.calibrate(x, merge=True)
-                plan = self.plan_for(B, H, W, x.device, deferred)
+                self.calibrate(x, merge=True, **cal)
+                plan = self.plan_for(B, H, W, x.device, deferred, **rg)
                 if events is not None:
                     del events[:]          # the markers of the invalid forward
-                out = plan.run(x, events=events, event_after=event_after, borrow=borrow)
+                out = plan.run(x, events=events, event_after=event_after, borrow=borrow, rects=run_rects)
                 st, bad = plan.range_status()
                 if st == "overflow":
                     raise RangeError("f32s forward still clamps after re-calibration: %r" % (bad[:3],))

@@ -254,8 +254,13 @@ class FramePipe(object):
             self._pre_process(slot, li, stream)
             if li == len(self.levels) - 1 and self.bgr is None:
                 self.ev_pre[slot].record()
-            dets = det._run_scale(lv.batch, self.flip)
-            plan = det.model.plan_for(lv.batch.shape[0], lv.batch.shape[2], lv.batch.shape[3], lv.batch.device)
+            rects = self._rects(slot, li)
+            if rects is None:
+                dets = det._run_scale(lv.batch, self.flip)
+                plan = det.model.plan_for(lv.batch.shape[0], lv.batch.shape[2], lv.batch.shape[3], lv.batch.device)
+            else:
+                dets = det._run_scale(lv.batch, self.flip, rects=rects)
+                plan = det.model.__dict__["_ran"]        # (the ragged plan, or the ordinary one for a full canvas)
             rs = getattr(plan.b, "range_sum", None) if plan.b.range is not None else None
             self.has_digest[slot][li] = rs is not None
             if rs is not None:
@@ -299,9 +304,20 @@ class FramePipe(object):
             torch.cuda.synchronize()
             det.tail_fallbacks += 1
             return self._run_sync(frames, **kw)
+        return self._host_tail(slot, slice(0, n), kw)
+
+    def _rects(self, slot, level):
+        """The canvas rectangles of the batch in ``slot`` at test scale ``level`` (``ImagePipe`` under
+        --keep_res), or None: every image fills the batch tensor."""
+        return None
+
+    def _host_tail(self, slot, sel, kw):
+        """The host tail on the images ``sel`` (a slice) of the raw detections copied out for ``slot``."""
+        det = self.det
         if not self.merge:
-            return det.results_batch(self.dets_host[slot][0].numpy()[:n], self._metas(slot, 0, n), self.scale, **kw)
-        return det._results_merged([(d.numpy()[:n], self._metas(slot, li, n), lv.scale)
+            return det.results_batch(self.dets_host[slot][0].numpy()[sel], self._metas(slot, 0, sel.stop)[sel],
+                                     self.scale, **kw)
+        return det._results_merged([(d.numpy()[sel], self._metas(slot, li, sel.stop)[sel], lv.scale)
                                     for li, (d, lv) in enumerate(zip(self.dets_host[slot], self.levels))], **kw)
 
 
@@ -318,7 +334,8 @@ class ImageTables(object):
 
     def of(self, H, W):
         """What one (H, W) image needs at every test scale: ``rec`` (S, 2) descriptors without their offsets,
-        ``to_source`` (S, 6), ``metas`` [S], ``scaled`` [S] (h, w), ``resize`` [S]."""
+        ``to_source`` (S, 6), ``metas`` [S], ``scaled`` [S] (h, w), ``resize`` [S], ``inp`` [S] (h, w) the
+        network input of the image."""
         e = self._geometry.get((H, W))
         if e is not None:
             return e
@@ -327,7 +344,7 @@ class ImageTables(object):
         S = len(self.scales)
         rec = np.zeros((S, 2), native.IMAGE_DESC)
         e = types.SimpleNamespace(rec=rec, to_source=np.zeros((S, 6), np.float64), metas=[], scaled=[], resize=[],
-                                  nbytes=H * W * 3)
+                                  inp=[], nbytes=H * W * 3)
         for l, scale in enumerate(self.scales):
             g, to_input, meta = self.det._pipe_level(H, W, scale)
             if g.scaled_h <= 0 or g.scaled_w <= 0:
@@ -344,6 +361,7 @@ class ImageTables(object):
             e.metas.append(meta)
             e.scaled.append((g.scaled_h, g.scaled_w))
             e.resize.append((g.scaled_h, g.scaled_w) != (H, W))
+            e.inp.append((g.inp_h, g.inp_w))
         if len(self._geometry) >= self.GEOMETRY_CACHE:
             self._geometry.clear()
         self._geometry[(H, W)] = e
@@ -371,6 +389,55 @@ class ImageTables(object):
             plan.append((True, max(e.scaled[l][0] for e in es), max(e.scaled[l][1] for e in es), int(sz.sum())))
         return int(sizes.sum()), offsets, [[e.metas[l] for e in es] for l in range(S)], plan
 
+    def canvas(self, shapes, pinned=None):
+        """--keep_res, where the network input follows the image: per test scale the canvas (h, w) that holds
+        the inputs of images of ``shapes`` -- the maxima of their own input sizes, or with ``pinned`` =
+        (h, w) (``check_canvas`` has seen it) that canvas, taken through ``input_geometry`` at the scale as
+        the largest image it holds is."""
+        es = [self.of(H, W) for H, W in shapes]
+        if pinned is None:
+            return [(max(e.inp[l][0] for e in es), max(e.inp[l][1] for e in es)) for l in range(len(self.scales))]
+        out = []
+        for scale in self.scales:
+            g = self.det.input_geometry(pinned[0] - 1, pinned[1] - 1, scale)
+            out.append((g.inp_h, g.inp_w))
+        return out
+
+    def check_canvas(self, shapes, canvas):
+        """``run_images(canvas=)``: (h, w), both multiples of pad + 1 and at least the network input of every
+        image of ``shapes`` at scale 1; ``ValueError`` otherwise.  Returns (h, w) as integers."""
+        step = int(self.det.opt.pad) + 1
+        try:
+            h, w = (int(v) for v in canvas)
+        except (TypeError, ValueError):
+            raise ValueError("canvas must be (h, w), got %r" % (canvas,))
+        if h <= 0 or w <= 0 or h % step or w % step or (h, w) != tuple(canvas):
+            raise ValueError("canvas must be positive multiples of pad + 1 = %d, got %r" % (step, tuple(canvas)))
+        for H, W in shapes:
+            g = self.det.input_geometry(H, W, 1.0)
+            if g.inp_h > h or g.inp_w > w:
+                raise ValueError("canvas %d x %d is smaller than the %d x %d network input of a %d x %d image"
+                                 % (h, w, g.inp_h, g.inp_w, H, W))
+        return h, w
+
+    def fill_rects(self, shapes, canvases, flip, rects):
+        """Fill the (S, k * B, 4) int32 rectangle table, k = 2 with ``flip``: image i at the origin of the
+        scale's canvas, (0, 0, inp_w, inp_h); with ``flip`` entries 2i and 2i + 1 -- that rectangle and its
+        mirror image in the canvas, (Wc - inp_w, 0, Wc, inp_h), where ``flip_concat`` puts the mirrored image.
+        Entries past the batch's images stay empty (their slices are cleared)."""
+        rects[...] = 0
+        k = 2 if flip else 1
+        for j, (H, W) in enumerate(shapes):
+            e = self.of(H, W)
+            for l, (hc, wc) in enumerate(canvases):
+                h, w = e.inp[l]
+                if h > hc or w > wc:
+                    raise ValueError("canvas %d x %d does not hold the %d x %d input of a %d x %d image at test "
+                                     "scale %s" % (hc, wc, h, w, H, W, self.scales[l]))
+                rects[l, k * j] = (0, 0, w, h)
+                if flip:
+                    rects[l, k * j + 1] = (wc - w, 0, wc, h)
+
 
 class ImagePipe(FramePipe):
     """``FramePipe`` for batches of B images of ANY sizes (``run_images`` / ``run_images_stream``), in the
@@ -387,19 +454,38 @@ class ImagePipe(FramePipe):
     (``cn_warp_normalize_u8_f32_ragged``; ddd, whose levels never resize: ``cn_warp_table_u8_f32_ragged``),
     then ``FramePipe``'s own steps, the tail reading the slot's maps (``DeviceTail.source_map``).  A task's
     side array (ddd: the images' matrices) rides as under ``FramePipe``.  The host side of the tables is
-    ``ImageTables``."""
+    ``ImageTables``.
 
-    def __init__(self, det, B, scales, flip, depth):
+    ``canvas=True``, the --keep_res form: the network input follows the image, so the images of a
+    batch give inputs of several sizes.  Per batch and test scale they share a CANVAS, the maxima of their
+    input heights and widths (``pinned``: one canvas for every batch, ``run_images(canvas=)``); the warp writes
+    image i's own padded input at the canvas origin of slice i (with flip-test the mirror image of the whole
+    canvas into the next slice, so the mirrored image sits at its right edge), and the network runs a ragged
+    plan (``PlannedModule.forward(x, rects=...)``) whose masks keep every image apart from what surrounds it.
+    ``lv.batch`` is then the tensor of the batch's canvas, out of a small per-level dictionary keyed by
+    canvas; a pinned (S, k * B, 4) int32 rectangle table per slot and its device copy ride with the
+    descriptors; a pipe without a device tail runs the host tail image by image (every image has its own
+    output size)."""
+
+    CANVAS_BATCHES = 4       # batch tensors kept per test scale of a canvas pipe, least recently used first out
+
+    def __init__(self, det, B, scales, flip, depth, canvas=False, pinned=None):
         opt, dev = det.opt, det.opt.device
         self._setup(det, B, scales, flip, depth)
         S, k = len(self.scales), 2 if self.flip else 1
+        self.canvas, self.pinned_canvas = bool(canvas), pinned
         meta = {'out_height': opt.input_h // opt.down_ratio, 'out_width': opt.input_w // opt.down_ratio}
         # lv.meta: what all images share (no 'c' / 's'); lv.scaled: the level's packed resized images
         self.levels = [types.SimpleNamespace(
-            scale=scale, g=None, meta=meta, scaled=None,
-            batch=torch.empty((B * k, 3, opt.input_h, opt.input_w), device=dev, dtype=torch.float32))
+            scale=scale, g=None, meta=None if canvas else meta, scaled=None, batches={},
+            batch=None if canvas else torch.empty((B * k, 3, opt.input_h, opt.input_w), device=dev,
+                                                  dtype=torch.float32))
             for scale in self.scales]
         self.scale, self.batch = self.scales[0], self.levels[0].batch
+        if canvas:
+            self.rects_pinned = [torch.zeros((S, k * B, 4), dtype=torch.int32).pin_memory() for _ in range(depth)]
+            self.rects_dev = [torch.zeros((S, k * B, 4), dtype=torch.int32, device=dev) for _ in range(depth)]
+            self.canvases = [None] * depth       # per slot, per level (h, w)
         self.capacity = [0] * depth
         self.pinned_in, self.np_in, self.dev_in = [None] * depth, [None] * depth, [None] * depth
         self.desc_pinned = [torch.zeros((S * 2 * B * native.IMAGE_DESC.itemsize,), dtype=torch.uint8).pin_memory()
@@ -432,6 +518,9 @@ class ImagePipe(FramePipe):
         if nbytes > self.capacity[slot]:
             self._grow(slot, nbytes)
         self.nbytes[slot] = nbytes
+        if self.canvas:
+            self.canvases[slot] = self.tables.canvas(shapes, self.pinned_canvas)
+            self.tables.fill_rects(shapes, self.canvases[slot], self.flip, self.rects_pinned[slot].numpy())
         for lv, (resize, _, _, scaled_bytes) in zip(self.levels, self.plan[slot]):
             # read and written on the launch stream only: its allocator orders a new buffer behind the old one's use
             if resize and (lv.scaled is None or lv.scaled.numel() < scaled_bytes):
@@ -453,9 +542,41 @@ class ImagePipe(FramePipe):
         if self.used[slot]:
             self.copy_stream.wait_event(self.ev_done[slot])      # the maps' reader is the tail, not the pre-process
         self.to_source_dev[slot].copy_(self.to_source_pinned[slot], non_blocking=True)
+        if self.canvas:                      # (read by the forwards of every level: behind ``ev_done`` too)
+            self.rects_dev[slot].copy_(self.rects_pinned[slot], non_blocking=True)
+
+    def _canvas_batch(self, slot, level):
+        """``lv.batch`` for the canvas of the batch in ``slot``: written and read on the launch stream only."""
+        lv, (h, w) = self.levels[level], self.canvases[slot][level]
+        t = lv.batches.pop((h, w), None)
+        if t is None:
+            while len(lv.batches) >= self.CANVAS_BATCHES:
+                lv.batches.pop(next(iter(lv.batches)))
+            t = torch.empty((self.B * (2 if self.flip else 1), 3, h, w), device=self.det.opt.device,
+                            dtype=torch.float32)
+        lv.batches[(h, w)] = t
+        lv.batch = t
+        if level == 0:
+            self.batch = t
+
+    def _rects(self, slot, level):
+        if not self.canvas:
+            return None
+        from .engine import CanvasRects
+        return CanvasRects(self.rects_pinned[slot][level].numpy(), self.rects_dev[slot][level], not self.flip)
+
+    def _host_tail(self, slot, sel, kw):
+        if not self.canvas:
+            return super(ImagePipe, self)._host_tail(slot, sel, kw)
+        out = []
+        for i in range(sel.start, sel.stop):     # every image has its own output size: a batch of one each
+            out += super(ImagePipe, self)._host_tail(slot, slice(i, i + 1), kw)
+        return out
 
     def _pre_process(self, slot, level, stream):
         lib, B, lv = native.lib(), self.B, self.levels[level]
+        if self.canvas:
+            self._canvas_batch(slot, level)
         item = native.IMAGE_DESC.itemsize
         descs = self.desc_dev[slot].data_ptr() + level * 2 * B * item
         src = self.dev_in[slot]
@@ -471,4 +592,6 @@ class ImagePipe(FramePipe):
         return self.metas[slot][level][:n]
 
     def _run_sync(self, frames, **kw):
+        if self.canvas:
+            return self.det._run_images_sync_keep_res(frames, self.scales, **kw)
         return self.det._run_images_sync(frames, self.scales, **kw)

@@ -190,6 +190,10 @@ def _declare(lib):
     lib.cn_copy_channels_f32.argtypes = [vp, i, vp, i, sz, i, vp]
     lib.cn_upsample2x_add_f32.restype = i
     lib.cn_upsample2x_add_f32.argtypes = [vp, vp, vp, i, i, i, i, vp]
+    lib.cn_mask_rects_f32.restype = i
+    lib.cn_mask_rects_f32.argtypes = [vp, i, i, i, i, i, i, vp, i, vp]
+    lib.cn_mask_rects_nchw_f32.restype = i
+    lib.cn_mask_rects_nchw_f32.argtypes = [vp, i, i, i, i, vp, i, f, vp]
     lib.cn_heads3x3_1x1_f32.restype = i
     lib.cn_heads3x3_1x1_f32.argtypes = [vp, i, i, i, i, i, vp, vp, i, i, ctypes.POINTER(HeadOut), vp]
     lib.cn_warp_normalize_u8_f32.restype = i

@@ -467,6 +467,23 @@ int cn_dw_conv_transpose_f32(const float *x, const float *w_taps, const float *a
  * Root.forward, pose_dla_dcn.py:159). */
 int cn_copy_channels_f32(const float *src, int src_pitch, float *dst, int dst_pitch,
                          size_t npix, int C, void *stream);
+/* Canvas masks (--keep_res batches of mixed input sizes): image b of a batch owns the rectangle
+ * rects_dev[b] of a common canvas, given in network-input pixels, half-open; a tensor at 1 / 2^shift of the
+ * input keeps [y0 >> shift, y1 >> shift) x [x0 >> shift, x1 >> shift) of image b (clipped to H x W) and
+ * everything else of its H x W is overwritten: with zero bytes in the NHWC form -- zero in plain fp32 and
+ * in f32s alike -- and with `fill` in the NCHW form.  Store-only launches, one workgroup per (8 rows, image) -- rows of C x H in the NCHW form.
+ * A rectangle that covers the tensor writes nothing; an empty or inverted one clears the image.  The
+ * rectangles live in DEVICE memory (they travel with the batch's descriptors and survive a graph capture).
+ * cn_mask_rects_f32: channels [c_off, c_off + C) of a (B, H, W, pitch) tensor of 4-byte elements, taken in
+ * whole 32-channel groups (C is rounded up to the next group, cut at the pitch: a tensor narrower than a
+ * group is cleared in whole pixels); pitch, c_off and the cleared width multiples of 4 and the first cleared
+ * element 16-byte aligned, CN_ERR_ALIGN otherwise.  CN_ERR_NULL for a null tensor or table, CN_ERR_SHAPE for
+ * sizes <= 0, c_off + C > pitch, B > 65535 or a shift outside 0 .. 30. */
+typedef struct cn_rect { int32_t x0, y0, x1, y1; } cn_rect;
+int cn_mask_rects_f32(void *t_nhwc, int B, int H, int W, int pitch, int c_off, int C,
+                      const cn_rect *rects_dev, int shift, void *stream);
+int cn_mask_rects_nchw_f32(float *t, int B, int C, int H, int W, const cn_rect *rects_dev,
+                           int shift, float fill, void *stream);
 /* Nearest x2 up-sampling + add of the skip branch (large_hourglass.py:102-109, 163-174). */
 int cn_upsample2x_add_f32(const float *x, const float *add, float *y, int B, int H, int W,
                           int C, void *stream);

@@ -7,7 +7,15 @@ side of a batch (tables + packing into the pinned buffer: ImagePipe._stage) is t
 FramePipe._stage for the one-size frames, and so is the pre-process launch on the device, to say where the
 difference to the ceiling lies.  The first line is
 the box calibration: a register-only fp16 MFMA loop and a 512 MiB copy, what this box delivers at the moment.
-The whole measurement runs under its own time limit (SIGALRM): a hang ends the tool with status 124."""
+The whole measurement runs under its own time limit (SIGALRM): a hang ends the tool with status 124.
+  python tools/bench_images.py --keep_res [--batch 32] [--batches 24] [--out profiles/keep_res_images_bench.txt]
+--keep_res: the same network with the input following the image; run_images_stream batches the mixed sizes on
+a canvas and is measured against the two routes mixed sizes had before it: the loop of
+run(image), and run_frames_stream over hand-made buckets of one size each (which compute no padding).  The exit
+status is 0 when the stream beats the loop and 1 when not; the ratio to the buckets is reported.
+  python tools/bench_images.py --keep_res --steps 20
+the step of one canvas batch on its ragged plan and of the same batch on the ordinary plan of the canvas size,
+back to back -- the run to put under ``rocprofv3 --kernel-trace --stats`` for the share of the mask launches."""
 import argparse
 import contextlib
 import os
@@ -50,6 +58,116 @@ def box_line(dev):
         tf, 2.0 * nbytes * 8 / e0.elapsed_time(e1) / 1e9)
 
 
+KEEP_RES_SIZES = [(480, 640), (640, 480), (427, 640), (640, 427), (375, 500), (640, 640)]      # (rows, columns)
+
+
+def keep_res_detector():
+    with contextlib.redirect_stdout(sys.stderr):
+        opt = opts().init(["ctdet", "--arch", "resdcn_18", "--keep_res"])
+        det = detector_factory[opt.task](opt)
+    synth.fill_state_dict_(det.model, 317)
+    det.model.invalidate_plans()
+    det.model.max_plans = 32         # six bucket shapes, six single-image shapes and the canvas stay planned
+    return det, opt
+
+
+def keep_res_steps(a):
+    """``--keep_res --steps N``: N steps of one canvas batch, ragged plan, then N on the ordinary plan."""
+    det, opt = keep_res_detector()
+    rng = np.random.RandomState(5)
+    batch = [rng.randint(0, 256, KEEP_RES_SIZES[j % len(KEEP_RES_SIZES)] + (3,)).astype(np.uint8) for j in range(a.batch)]
+    pipe = det._canvas_pipe_for(batch, 1, None, "bench_images")
+    pipe.submit(0, batch)
+    pipe.collect(0, batch)
+    x, rects = pipe.levels[0].batch, pipe._rects(0, 0)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for name, kw in (("ragged plan", {"rects": rects}), ("ordinary plan of the canvas", {})):
+        for _ in range(3):
+            det.run_batch(x, **kw)
+        e0.record()
+        for _ in range(a.steps):
+            det.run_batch(x, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        out.append("%s: %.3f ms per step (network + decode, B=%d, canvas %d x %d, %d steps)"
+                   % (name, e0.elapsed_time(e1) / a.steps, a.batch, x.shape[2], x.shape[3], a.steps))
+    plan = det.model.__dict__["_ran"]
+    ragged = [p for k, p in det.model.__dict__["_plans"].items() if "ragged" in k][0]
+    out.append("launches per step: ragged %d (of them %d masks), ordinary %d"
+               % (len(ragged.b.ops), sum(m["kind"] == "mask" for m in ragged.b.meta), len(plan.b.ops)))
+    assert det.range_ok()
+    print("\n".join(out))
+    return 0
+
+
+def keep_res_main(a):
+    det, opt = keep_res_detector()
+    box = box_line(opt.device)
+    rng = np.random.RandomState(5)
+    B, n = a.batch, a.batches
+    pool = [rng.randint(0, 256, KEEP_RES_SIZES[rng.randint(len(KEEP_RES_SIZES))] + (3,)).astype(np.uint8)
+            for _ in range(3 * B)]
+    mixed = [[pool[(i * B + j) % len(pool)] for j in range(B)] for i in range(n)]
+    # the same number of images, sorted by hand into batches of one size each (a size's last batch filled up)
+    per = max(1, n // len(KEEP_RES_SIZES))
+    buckets = []
+    for size in KEEP_RES_SIZES:
+        own = [f for f in pool if f.shape[:2] == size] or [rng.randint(0, 256, size + (3,)).astype(np.uint8)]
+        buckets.append([[own[(i * B + j) % len(own)] for j in range(B)] for i in range(per)])
+
+    seen = set()
+
+    def images_stream():
+        done = sum(len(r) for r in det.run_images_stream(iter(mixed), depth=3))
+        # (the stream's pipe, before the six bucket pipes push it out of the detector's four)
+        seen.update(det._canvas_pipe_for(mixed[0], 3, None, "bench_images").levels[0].batches)
+        return done
+
+    def bucket_streams():
+        return sum(len(r) for bucket in buckets for r in det.run_frames_stream(iter(bucket), depth=3))
+
+    def loop():
+        for b in mixed[:max(1, n // 4)]:
+            for f in b:
+                det.run(f)
+        return max(1, n // 4) * B
+
+    fns = [("loop of run(image)", loop), ("run_images_stream on canvases", images_stream),
+           ("run_frames_stream per size bucket", bucket_streams)]
+    rates = {name: [] for name, _ in fns}
+    for name, fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(a.repeats):
+        for name, fn in fns:
+            t0 = time.perf_counter()
+            images = fn()
+            torch.cuda.synchronize()
+            rates[name].append(images / (time.perf_counter() - t0))
+    signal.alarm(0)
+    canvases = sorted(seen)
+    area = np.mean([((f.shape[0] | opt.pad) + 1) * ((f.shape[1] | opt.pad) + 1) for b in mixed for f in b])
+
+    def line(name):
+        r = rates[name]
+        return "%-36s %8.1f images/s   (min %.1f, max %.1f over %d)" % (name + ":", max(r), min(r), max(r), len(r))
+    lo, im, bu = (rates[name] for name, _ in fns)
+    lines = [box,
+             "ctdet resdcn_18 --keep_res, B=%d, %d batches, %d alternating repeats; %d seeded images of the sizes %s; "
+             "canvases seen: %s; an image's own input is %.0f %% of its canvas on average"
+             % (B, n, a.repeats, len(pool), ", ".join("%dx%d" % (w, h) for h, w in KEEP_RES_SIZES),
+                ", ".join("%d x %d" % c for c in canvases), 100.0 * area / (canvases[-1][0] * canvases[-1][1]))] + \
+        [line(name) for name, _ in fns] + [
+        "run_images_stream / loop: %.1fx (the condition: > 1); run_images_stream / buckets: %.2f (reported; best "
+        "over best)" % (max(im) / max(lo), max(im) / max(bu))]
+    print("\n".join(lines))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0 if max(im) > max(lo) else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -57,6 +175,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=500)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--keep_res", action="store_true")
+    ap.add_argument("--steps", type=int, default=0)
     a = ap.parse_args()
 
     def expired(*_):
@@ -64,6 +184,8 @@ def main():
         os._exit(124)
     signal.signal(signal.SIGALRM, expired)
     signal.alarm(a.timeout)
+    if a.keep_res:
+        return keep_res_steps(a) if a.steps else keep_res_main(a)
 
     with contextlib.redirect_stdout(sys.stderr):
         opt = opts().init(["ctdet", "--arch", "resdcn_18"])
