@@ -1,211 +1,42 @@
-// cn_decode.hip -- heat-map decode for gfx950: sigmoid -> 3x3 peak test ->
-// exact top-K -> gather -> box assembly.
+// cn_decode.hip -- the top-K of a heat-map for gfx950: sigmoid -> 3x3 peak test -> exact top-K -> the rows
+// of the K winners (ctdet boxes, _topk / _topk_channel lists, multi_pose stage-A rows).
 //
-// Reference behaviour being replaced (paths relative to /root/reference/src/lib):
+// Reference behaviour being replaced (src/lib of the reference):
 //   hm.sigmoid_()                      detectors/ctdet.py:31
 //   _nms                               models/decode.py:9-15
 //   _topk_channel / _topk              models/decode.py:92-119
 //   _transpose_and_gather_feat         models/utils.py:22-26
 //   ctdet_decode                       models/decode.py:464-495
 //
-// Design (HBM-bound: the heat-map is read exactly once):
-//   kernel 1  nms_topk_kernel   one workgroup per (image, class, row band).  The
-//             band (+1 halo row each side) is staged in LDS after the sigmoid,
-//             every thread keeps its peak-tested values in registers, and an
-//             exact wave/LDS radix select over a 64-bit key (score, ~index)
-//             leaves the band's K best peaks, sorted, as candidates.
-//   kernel 2  merge_topk_kernel one workgroup per image: the same radix select
-//             over the C*bands*K candidates (== torch's second topk over C*K,
-//             decode.py:112), then each of the K winners gathers wh/reg straight
-//             from the NCHW maps (no permute().contiguous() copy, utils.py:23)
-//             and writes its box.
+// Three forms compute the same K rows, bit for bit (tests/test_gpu_decode.py):
+//   one launch     plane_select_merge_kernel: planes of at most 128 x 128 cells, a workgroup holds one
+//                  (image, class) plane in registers; the image's last plane to arrive selects and emits.
+//   two launches   group_max_kernel + collect_merge_kernel: any plane size; group maxima give an image
+//                  threshold, the planes collect the cells that reach it, the last arriver selects and emits.
+//   per band       nms_topk_kernel per (image, class, row band) leaves the band's K best as candidates,
+//                  merge_topk_kernel selects among them and emits.  With one band per plane the channel
+//                  lists are already final: the merge is skipped (the direct form).
+// The image-level forms rank ALL classes of an image and exist for MODE_CTDET and MODE_TOPK only.
 //
-// Order of equal scores (torch.topk leaves it unspecified): score descending,
-// then class ascending, then spatial index ascending -- the key below makes
-// that a strict total order, so the result is deterministic.
-#include "cn_common.h"
-
-// Decode arithmetic must round exactly like the reference's torch ops (bit-exact parity):
-// no mul+add fusion anywhere in this file (hipcc's default is -ffp-contract=fast-honor-pragmas
-// and HIP's __fmul_rn/__fadd_rn are plain operators).
-#pragma clang fp contract(off)
-// Rounded-once helpers compiled under contract(off): unlike HIP's header-inline __fmul_rn /
-// __fadd_rn their results can never be fused into an FMA after inlining.
-static __device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-static __device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+// Host side: every entry fills a TopkCall (cn_internal.h).  topk_route() is the one place that says which
+// form a call takes, its band geometry and every workspace offset -- the workspace and state-region
+// queries read the same plan -- and topk_run() is the one place that checks, routes and launches.  The
+// select machinery is in cn_select.h; pose matching and the ddd / exct / agnex decoders, which reach the
+// top-K through topk_run() and cn_topk_f32, are in cn_decode_tasks.hip.
+//
+// Order of equal scores (torch.topk leaves it unspecified): score descending, then class ascending, then
+// spatial index ascending -- the 64-bit key makes that a strict total order, so the result is deterministic.
+#include "cn_internal.h"
+#include "cn_select.h"
 
 namespace {
-
-constexpr int NT = 256;      // threads per workgroup (4 waves)
-constexpr int KMAX = 128;    // largest supported K
-constexpr int HBINS = 2048;  // radix-select histogram bins (11-bit digits)
-
-typedef unsigned long long u64;
-
-// Order-preserving float -> uint32 map (larger float -> larger key).
-__device__ __forceinline__ uint32_t f2key(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k)
-{
-    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
-constexpr uint32_t KEY_ZERO = 0x80000000u;  // f2key(+0.0f)
-
-constexpr int MAXW = 16;  // waves of the largest workgroup that uses SelShared (1024 threads)
-
-struct SelShared {
-    uint32_t hist[HBINS];
-    u64 sel[KMAX];
-    uint32_t wsum[MAXW];
-    uint32_t cnt;
-    uint32_t digit, need, bincount;
-    uint32_t ncand;
-    uint32_t pad_[3];
-};
-static_assert(sizeof(SelShared) % 16 == 0, "keep the LDS carve 16-byte aligned");
-
-__device__ __forceinline__ int pass_shift(int p)
-{
-    // 64-bit key split into digits of 11,11,10 | 11,11,10 bits (msb first)
-    return p == 0 ? 53 : p == 1 ? 42 : p == 2 ? 32 : p == 3 ? 21 : p == 4 ? 10 : 0;
-}
-__device__ __forceinline__ uint32_t pass_dmask(int p) { return (p == 2 || p == 5) ? 1023u : 2047u; }
-
-// Exact selection of the `need0` largest 64-bit keys among the elements that
-// `for_each(f)` enumerates (f(key64, is_plain_zero)); keys must be distinct.
-// On return every thread holds (prefix, mask): an element is selected iff
-// (key & mask) >= prefix.  Elements whose score is exactly +0.0 (the ~89 % of a
-// heat-map that the peak test suppressed) are counted per wave instead of one
-// LDS atomic each, otherwise they would serialise on a single histogram bin.
-template <int TB, class ForEach>
-__device__ __forceinline__ void radix_select(ForEach &&for_each, uint32_t need0, SelShared &sh,
-                                             u64 &out_prefix, u64 &out_mask)
-{
-    static_assert(HBINS % TB == 0 && TB / CN_WAVE <= MAXW, "block size");
-    constexpr int BPT = HBINS / TB;  // histogram bins owned by a thread
-    const int tid = threadIdx.x;
-    const int lane = tid & (CN_WAVE - 1);
-    const int wave = tid / CN_WAVE;
-    u64 prefix = 0, mask = 0;
-    uint32_t need = need0;
-    const u64 zkey = (u64)KEY_ZERO << 32;
-#pragma unroll 1
-    for (int pass = 0; pass < 6; ++pass) {
-        const int shift = pass_shift(pass);
-        const uint32_t dmask = pass_dmask(pass);
-        for (int i = tid; i < HBINS; i += TB) sh.hist[i] = 0;
-        __syncthreads();
-        uint32_t zc = 0;
-        for_each([&](u64 k, bool plain_zero) {
-            if ((k & mask) == prefix) {
-                if (plain_zero && pass < 3)
-                    ++zc;
-                else
-                    atomicAdd(&sh.hist[(uint32_t)(k >> shift) & dmask], 1u);
-            }
-        });
-        if (pass < 3) {
-            for (int o = CN_WAVE / 2; o > 0; o >>= 1) zc += __shfl_down(zc, o);
-            if (lane == 0 && zc) atomicAdd(&sh.hist[(uint32_t)(zkey >> shift) & dmask], zc);
-        }
-        __syncthreads();
-        // suffix sums over bins: thread t owns bins [BPT*t, BPT*t + BPT)
-        uint32_t p = 0;
-#pragma unroll
-        for (int j = 0; j < BPT; ++j) p += sh.hist[tid * BPT + j];
-        uint32_t s = p;
-#pragma unroll
-        for (int o = 1; o < CN_WAVE; o <<= 1) {
-            const uint32_t t = __shfl_down(s, o);
-            if (lane + o < CN_WAVE) s += t;
-        }
-        if (lane == 0) sh.wsum[wave] = s;
-        __syncthreads();
-        for (int w = wave + 1; w < TB / CN_WAVE; ++w) s += sh.wsum[w];
-        const uint32_t above = s - p;  // elements in strictly higher bins
-        if (above < need && s >= need) {
-            uint32_t run = above;
-            for (int j = BPT - 1; j >= 0; --j) {
-                const uint32_t h = sh.hist[tid * BPT + j];
-                if (run + h >= need) {
-                    sh.digit = tid * BPT + j;
-                    sh.need = need - run;
-                    sh.bincount = h;
-                    break;
-                }
-                run += h;
-            }
-        }
-        __syncthreads();
-        prefix |= (u64)sh.digit << shift;
-        mask |= (u64)dmask << shift;
-        need = sh.need;
-        if (sh.bincount == need) break;  // the whole bin is taken: done
-    }
-    out_prefix = prefix;
-    out_mask = mask;
-}
-
-// Collect the selected keys into sh.sel[0..KMAX) and sort them descending.  The sort is a
-// 128-element bitonic network run by ONE wave (two keys per lane, cross-lane exchange by
-// shuffles): no workgroup barriers inside the network.
-template <int TB, class ForEach>
-__device__ __forceinline__ void collect_and_sort(ForEach &&for_each, u64 prefix, u64 mask,
-                                                 SelShared &sh)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    if (tid == 0) sh.cnt = 0;
-    for (int i = tid; i < KMAX; i += TB) sh.sel[i] = 0;  // pad keys sort last
-    __syncthreads();
-    for_each([&](u64 k, bool) {
-        if ((k & mask) >= prefix) {
-            const uint32_t pos = atomicAdd(&sh.cnt, 1u);
-            if (pos < (uint32_t)KMAX) sh.sel[pos] = k;
-        }
-    });
-    __syncthreads();
-    if (tid < CN_WAVE) {
-        const int lane = tid;
-        u64 v[2] = {sh.sel[lane], sh.sel[lane + CN_WAVE]};
-        for (int k = 2; k <= KMAX; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                if (j == CN_WAVE) {  // partner = the lane's other slot (only when k == 128)
-                    const u64 hi = v[0] > v[1] ? v[0] : v[1];
-                    const u64 lo = v[0] > v[1] ? v[1] : v[0];
-                    v[0] = hi;
-                    v[1] = lo;
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        const int i = s * CN_WAVE + lane;
-                        const uint32_t olo = __shfl_xor((uint32_t)v[s], j);
-                        const uint32_t ohi = __shfl_xor((uint32_t)(v[s] >> 32), j);
-                        const u64 o = ((u64)ohi << 32) | olo;
-                        const bool desc = (i & k) == 0;
-                        const bool lower = (i & j) == 0;
-                        const bool take_max = (lower == desc);
-                        v[s] = take_max ? (v[s] > o ? v[s] : o) : (v[s] > o ? o : v[s]);
-                    }
-                }
-            }
-        }
-        sh.sel[lane] = v[0];
-        sh.sel[lane + CN_WAVE] = v[1];
-    }
-    __syncthreads();
-}
 
 // (sigmoidf_ref: cn_common.h -- one definition of the logistic for every decode form and the flip average)
 
 constexpr int CAND_CAP = 4096;  // compacted positive peaks per band (uint16 tile offsets)
 
 // ---------------------------------------------------------------------------
-// kernel 1: per (image, class, row-band): sigmoid + 3x3 peak test + top-K
+// The per-band select: per (image, class, row-band): sigmoid + 3x3 peak test + top-K
 // grid (nbands, C, B), block NT, dynamic LDS = SelShared | tile (R+2)*W floats | peak list
 //
 // Fast path: the peak test (four cells per step, horizontal 3-max shared between the three
@@ -216,7 +47,7 @@ constexpr int CAND_CAP = 4096;  // compacted positive peaks per band (uint16 til
 // full scan that re-evaluates the peak test per element, so every input is still exact.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void nms_topk_kernel(const float *__restrict__ heat, int C, int H,
-                                                      int W, int K, int R, int apply_sigmoid,
+                                                      int W, int K, int R, int flags,
                                                       float *__restrict__ cand_score,
                                                       int32_t *__restrict__ cand_idx)
 {
@@ -236,10 +67,10 @@ __global__ __launch_bounds__(NT) void nms_topk_kernel(const float *__restrict__ 
     const float *plane = heat + ((size_t)b * C + c) * (size_t)H * W;
     const float NEG_INF = -__builtin_huge_valf();
     // ablation bits for tools/bench_decode.py (never set through the Python API)
-    const bool dbg_noselect = (apply_sigmoid & 256) != 0;
-    const bool dbg_nonms = (apply_sigmoid & CN_DECODE_NO_PEAK_TEST) != 0;  // plain topk
-    const bool dbg_slow = (apply_sigmoid & 1024) != 0;
-    apply_sigmoid &= 1;
+    const bool dbg_noselect = (flags & 256) != 0;
+    const bool dbg_nonms = (flags & CN_DECODE_NO_PEAK_TEST) != 0;  // plain topk
+    const bool dbg_slow = (flags & 1024) != 0;
+    const int apply_sigmoid = flags & CN_DECODE_SIGMOID;
     if (tid == 0) sh.ncand = 0;
 
     // ---- stage rows r0-1 .. r0+rows (rows+2 rows) into LDS, sigmoid applied once
@@ -911,25 +742,21 @@ __device__ __forceinline__ void plane_collect(const float *__restrict__ heat, in
 }
 
 // ---------------------------------------------------------------------------
-// kernel 2: merge candidate lists of one group into its K best, sorted.
+// The rows of the K winners, and the merge of the per-band form.
 //   CTDET : group = image; N = C*per_class candidates, class = j / per_class;
 //           output = gathered boxes (decode.py:472-493)
 //   !CTDET: group = (image, channel); output = (scores, inds)  (_topk_channel)
 // ---------------------------------------------------------------------------
-enum { MODE_CTDET = 0, MODE_CHANNEL = 1, MODE_POSE = 2, MODE_TOPK = 3 };
-
-constexpr int NTM = 1024;  // the merge runs one workgroup per image: make it a big one
-
 
 // rows 0 .. K-1 of the sorted selection sh.sel -> outputs of group g (see merge_topk_kernel)
 template <int MODE>
-__device__ __forceinline__ void emit_rows(const SelShared &sh, int g, int H, int W, int K, int C,
-                                          const float *__restrict__ wh, const float *__restrict__ reg,
-                                          int cat_spec_wh, float *__restrict__ dets, int det_dim,
-                                          int32_t *__restrict__ inds_out, float *__restrict__ out_scores,
-                                          const float *__restrict__ kps_map, int J,
-                                          int32_t *__restrict__ cls_out)
+__device__ __forceinline__ void emit_rows(const SelShared &sh, int g, int H, int W, int K, int C, const EmitArgs &ea)
 {
+    const float *__restrict__ wh = ea.wh, *__restrict__ reg = ea.reg, *__restrict__ kps_map = ea.kps_map;
+    float *__restrict__ dets = ea.dets, *__restrict__ out_scores = ea.out_scores;
+    int32_t *__restrict__ inds_out = ea.inds_out, *__restrict__ cls_out = ea.cls_out;
+    const int cat_spec_wh = ea.cat_spec_wh, J = ea.J;
+    const int det_dim = 6 + 2 * J;   // a row: box, score, 2J keypoint coordinates (MODE_POSE), class
     constexpr bool CTDET = (MODE != MODE_CHANNEL);
     const int tid = threadIdx.x;
     const int HW = H * W;
@@ -986,10 +813,7 @@ __device__ __forceinline__ void emit_rows(const SelShared &sh, int g, int H, int
 template <int MODE>
 __global__ __launch_bounds__(NTM) void merge_topk_kernel(
     const float *__restrict__ cand_score, const int32_t *__restrict__ cand_idx, int N,
-    int per_class, int H, int W, int K, int C, const float *__restrict__ wh,
-    const float *__restrict__ reg, int cat_spec_wh, float *__restrict__ dets, int det_dim,
-    int32_t *__restrict__ inds_out, float *__restrict__ out_scores,
-    const float *__restrict__ kps_map, int J, int32_t *__restrict__ cls_out)
+    int per_class, int H, int W, int K, int C, const EmitArgs ea)
 {
     constexpr bool CTDET = (MODE != MODE_CHANNEL);  // group = image, class from position
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1012,8 +836,7 @@ __global__ __launch_bounds__(NTM) void merge_topk_kernel(
     };
     radix_select<NTM>(for_each, (uint32_t)K, sh, prefix, mask);
     collect_and_sort<NTM>(for_each, prefix, mask, sh);
-    emit_rows<MODE>(sh, g, H, W, K, C, wh, reg, cat_spec_wh, dets, det_dim, inds_out, out_scores, kps_map, J,
-                    cls_out);
+    emit_rows<MODE>(sh, g, H, W, K, C, ea);
 }
 
 // ---------------------------------------------------------------------------
@@ -1026,15 +849,6 @@ __global__ __launch_bounds__(NTM) void merge_topk_kernel(
 // Degenerate images and saturated plateaus are dealt with plane by plane in plane_collect (every
 // plane hands on at most its K best keys): the last arriver always finds between K and C * K keys.
 // ---------------------------------------------------------------------------
-struct EmitArgs {
-    const float *wh, *reg;
-    int cat_spec_wh;
-    float *dets;
-    int det_dim;
-    int32_t *inds_out;
-    float *out_scores;
-    int32_t *cls_out;
-};
 
 template <int MODE>
 __global__ __launch_bounds__(NT) void collect_merge_kernel(const float *__restrict__ heat, int C, int H,
@@ -1096,8 +910,7 @@ __global__ __launch_bounds__(NT) void collect_merge_kernel(const float *__restri
         radix_select<NT>(for_each, (uint32_t)K, sh, prefix, mask);
         collect_and_sort<NT>(for_each, prefix, mask, sh);
     }
-    emit_rows<MODE>(sh, b, H, W, K, C, ea.wh, ea.reg, ea.cat_spec_wh, ea.dets, ea.det_dim, ea.inds_out,
-                    ea.out_scores, (const float *)nullptr, 0, ea.cls_out);
+    emit_rows<MODE>(sh, b, H, W, K, C, ea);
 }
 
 // ---------------------------------------------------------------------------
@@ -1226,8 +1039,7 @@ __device__ __attribute__((noinline)) void psm_last_arriver(SelShared &sh, int32_
         radix_select<OP_NT>(for_each, (uint32_t)K, sh, prefix, mask);
         collect_and_sort<OP_NT>(for_each, prefix, mask, sh);
     }
-    emit_rows<MODE>(sh, b, H, W, K, C, ea.wh, ea.reg, ea.cat_spec_wh, ea.dets, ea.det_dim, ea.inds_out,
-                    ea.out_scores, (const float *)nullptr, 0, ea.cls_out);
+    emit_rows<MODE>(sh, b, H, W, K, C, ea);
 }
 
 #ifndef CN_PSM_WAVES
@@ -1464,81 +1276,184 @@ __global__ __launch_bounds__(OP_NT, CN_PSM_WAVES) void plane_select_merge_kernel
     }
 }
 
-
-struct BandPlan {
-    int R;       // rows per band
-    int nbands;
-    size_t lds;  // dynamic LDS bytes of kernel 1
-};
-
-// Deterministic function of the shapes only (workspace query == launch).
-// Bands of <= 8192 cells: tile + list + select state stay under ~52 KB, so three
-// workgroups share a CU and their load / peak-test / select phases overlap.
-bool make_band_plan(int B, int C, int H, int W, int K, BandPlan *bp)
+// the launches of a routed call; the image-level kernels exist for the modes that rank all classes of an image
+template <int MODE>
+int topk_launch(const TopkCall &c, const TopkPlan &p)
 {
-    (void)B; (void)C;
-    if (W <= 0 || H <= 0 || W > 4096) return false;
-    int R = 8192 / W;
-    if (R < 1) R = 1;
-    if (R > H) R = H;
-    while (R < H && R * W < K) ++R;  // a band should be able to supply K candidates
-    if ((long)R * W > 16384) return false;
-    bp->R = R;
-    bp->nbands = cn_cdiv(H, R);
-    bp->lds = sizeof(SelShared) + (size_t)(R + 2) * W * sizeof(float) + CAND_CAP * sizeof(uint16_t);
-    return bp->lds <= 160 * 1024;
-}
-
-int launch_nms_topk(const float *heat, int B, int C, int H, int W, int K, int apply_sigmoid,
-                    const BandPlan &bp, float *cand_score, int32_t *cand_idx, hipStream_t st)
-{
-    dim3 grid(bp.nbands, C, B), block(NT);
+    char *ws = (char *)c.workspace;
+    const int B = c.B, C = c.C, H = c.H, W = c.W, K = c.K;
+    if constexpr (MODE == MODE_CTDET || MODE == MODE_TOPK) {
+        if (p.form == TOPK_ONE_LAUNCH || p.form == TOPK_TWO_LAUNCHES) {
+            uint32_t *gpeak = (uint32_t *)(ws + p.gpeak);
+            uint32_t *gall = (uint32_t *)(ws + p.gall);
+            int32_t *counts = (int32_t *)(ws + p.counts);
+            int32_t *done = (int32_t *)(ws + p.done);
+            u64 *keys = (u64 *)(ws + p.keys);
+            dim3 grid((unsigned)(B * C)), block(NT);
+            if (p.form == TOPK_ONE_LAUNCH) {
+                // The image state words (arrival counter, floor) must be zero on entry and are left at zero
+                // by the kernel: a caller that keeps the workspace to itself says so (CN_DECODE_STATE_CLEAN)
+                // after zeroing it once; anyone else pays a small fill.
+                if (p.fill_state) {
+                    if (hipMemsetAsync(ws + p.state_offset, 0, p.state_bytes, c.st) != hipSuccess) return CN_ERR_LAUNCH;
+                }
+                hipLaunchKernelGGL(plane_select_merge_kernel<MODE>, grid, dim3(OP_NT), sizeof(SelShared), c.st,
+                                   c.heat, B, C, H, W, c.flags, K, keys, (int32_t *)(ws + p.pcount), done,
+                                   (uint32_t *)(ws + p.floorv), c.ea);
+                CN_CHECK_LAUNCH();
+                return CN_OK;
+            }
+            hipLaunchKernelGGL(group_max_kernel, grid, block, 0, c.st, c.heat, H, W, p.nrg, p.ncb, c.flags, gpeak,
+                               gall, C, counts, done);
+            CN_CHECK_LAUNCH();
+            hipLaunchKernelGGL(collect_merge_kernel<MODE>, grid, block, sizeof(SelShared), c.st, c.heat, C, H, W,
+                               p.nrg, p.ncb, c.flags, K, gpeak, gall, keys, p.cap, counts, done, c.ea);
+            CN_CHECK_LAUNCH();
+            return CN_OK;
+        }
+    }
+    // per band; with one band per plane the channel lists are final as the select writes them
+    const bool direct = p.form == TOPK_BAND_DIRECT;
+    float *cand_score = direct ? c.ea.out_scores : (float *)(ws + p.cand_score);
+    int32_t *cand_idx = direct ? c.ea.inds_out : (int32_t *)(ws + p.cand_idx);
     CN_SET_MAX_LDS_ONCE(nms_topk_kernel, 160 * 1024);
-    hipLaunchKernelGGL(nms_topk_kernel, grid, block, bp.lds, st, heat, C, H, W, K, bp.R,
-                       apply_sigmoid, cand_score, cand_idx);
+    hipLaunchKernelGGL(nms_topk_kernel, dim3(p.nbands, C, B), dim3(NT), p.lds, c.st, c.heat, C, H, W, K, p.R,
+                       c.flags, cand_score, cand_idx);
+    CN_CHECK_LAUNCH();
+    if (direct) return CN_OK;
+    const int per_class = p.nbands * K;
+    constexpr bool per_channel = MODE == MODE_CHANNEL;   // one group per (image, channel), else per image
+    hipLaunchKernelGGL(merge_topk_kernel<MODE>, dim3(per_channel ? B * C : B), dim3(NTM), sizeof(SelShared), c.st,
+                       cand_score, cand_idx, per_channel ? per_class : C * per_class, per_class, H, W, K, C, c.ea);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
 
 }  // namespace
 
-namespace {
-// image-level (threshold-pruned) top-K: layout of its scratch behind the per-band candidate
-// arrays, and whether a shape takes it (enough groups per image for a meaningful threshold;
-// single-class maps such as the pose centre map keep the per-band select)
-struct ImgPlan {
-    bool use;
-    bool one_pass;                 // planes of <= 128 x 128 cells: plane_select_merge_kernel (ONE launch)
-    int nrg, ncb;                  // 8-row groups per plane, 128-column blocks per row
-    int cap;                       // candidate keys per image: every plane hands on at most its K best
-    size_t gpeak, gall, counts, done, floorv, pcount, keys, total;   // byte offsets in the workspace
-    size_t state_bytes;            // counts | done | floorv: contiguous, zero between calls of the one-launch form
-};
-ImgPlan make_img_plan(int B, int C, int H, int W, int K, const BandPlan &bp)
+// Which form a top-K call takes and where its scratch lives: a deterministic function of the shapes, the mode
+// and the flags (workspace query == launch).
+TopkPlan topk_route(const TopkCall &c)
 {
-    ImgPlan p = {};
-    const size_t n = (size_t)B * C * bp.nbands * K;
-    size_t o = cn_align_up(n * sizeof(float), 256) + cn_align_up(n * sizeof(int32_t), 256);
+    TopkPlan p = {};
+    const int B = c.B, C = c.C, H = c.H, W = c.W, K = c.K;
+    p.rc = CN_ERR_SHAPE;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return p;
+    p.rc = CN_ERR_UNSUPPORTED;
+    // ---- band geometry of the per-band select.  Bands of <= 8192 cells: tile + list + select state stay
+    // under ~52 KB, so three workgroups share a CU and their load / peak-test / select phases overlap.
+    if (W > 4096) return p;
+    int R = 8192 / W;
+    if (R < 1) R = 1;
+    if (R > H) R = H;
+    while (R < H && R * W < K) ++R;  // a band should be able to supply K candidates
+    if ((long)R * W > 16384) return p;
+    p.R = R;
+    p.nbands = cn_cdiv(H, R);
+    p.lds = sizeof(SelShared) + (size_t)(R + 2) * W * sizeof(float) + CAND_CAP * sizeof(uint16_t);
+    if (p.lds > 160 * 1024) return p;
+    p.rc = CN_OK;
+    // ---- workspace: the per-band candidate arrays, the image-level scratch behind them.  One layout for
+    // every mode and flag: what a query answers holds for whatever form the call then takes.
+    const size_t n = (size_t)B * C * p.nbands * K;
+    size_t o = 0;
+    p.cand_score = o; o += cn_align_up(n * sizeof(float), 256);
+    p.cand_idx = o;   o += cn_align_up(n * sizeof(int32_t), 256);
+    p.cand_bytes = o;
     p.nrg = cn_cdiv(H, GROWS);
     p.ncb = cn_cdiv(W, 128);
     // enough groups per image for a meaningful threshold; rows of whole quads
-    p.use = (W & 3) == 0 && (long)C * p.nrg * p.ncb >= 4L * K;
-    p.one_pass = p.use && H <= (OP_NT / 32) * OP_ROWS && W <= 128 && C <= OP_CMAX;
+    const bool use = (W & 3) == 0 && (long)C * p.nrg * p.ncb >= 4L * K;
+    // planes of <= 128 x 128 cells: plane_select_merge_kernel (ONE launch)
+    const bool one_pass = use && H <= (OP_NT / 32) * OP_ROWS && W <= 128 && C <= OP_CMAX;
     const size_t ng = (size_t)B * C * p.nrg * p.ncb;
     p.gpeak = o;  o += cn_align_up(ng * 4, 256);
     p.gall = o;   o += cn_align_up(ng * 4, 256);
     p.counts = o; o += cn_align_up((size_t)B * 4, 256);
     p.done = o;   o += cn_align_up((size_t)B * 4, 256);
     p.floorv = o; o += cn_align_up((size_t)B * 4, 256);
-    p.state_bytes = o - p.counts;
+    const size_t state_bytes = o - p.counts;   // counts | done | floorv: contiguous
     p.pcount = o; o += cn_align_up((size_t)B * C * 4, 256);   // keys in every plane's slot (one-launch form)
-    p.cap = C * (p.one_pass ? OP_PE : K);
+    p.cap = C * (one_pass ? OP_PE : K);        // every plane hands on at most its K best (its slot: OP_PE)
     p.keys = o;   o += cn_align_up((size_t)B * p.cap * 8, 256);
     p.total = o;
+    // ---- the form
+    // the image-level forms rank all classes of an image: single-class maps (the pose centre map) and the
+    // per-channel lists keep the per-band select
+    const bool image_mode = c.mode == MODE_CTDET || c.mode == MODE_TOPK;
+    if (image_mode && use && !(c.flags & CN_DECODE_PER_BAND))   // (the flag: tests / A-B)
+        p.form = (one_pass && !(c.flags & CN_DECODE_TWO_LAUNCHES)) ? TOPK_ONE_LAUNCH : TOPK_TWO_LAUNCHES;
+    else   // one band per plane: the select already leaves the final sorted (B, C, K) channel lists
+        p.form = (c.mode == MODE_CHANNEL && p.nbands == 1) ? TOPK_BAND_DIRECT : TOPK_BAND_MERGE;
+    if (p.form == TOPK_ONE_LAUNCH) {
+        p.state_offset = p.counts;
+        p.state_bytes = state_bytes;
+        p.fill_state = !(c.flags & CN_DECODE_STATE_CLEAN);
+    }
     return p;
 }
 
-}  // namespace
+int topk_checks(const TopkCall &c)
+{
+    if (!c.heat) return CN_ERR_NULL;
+    if (c.B <= 0 || c.C <= 0 || c.H <= 0 || c.W <= 0 || c.K <= 0) return CN_ERR_SHAPE;
+    if ((long)c.K > (long)c.H * c.W) return CN_ERR_SHAPE;  // torch.topk: k out of range
+    if (c.K > KMAX) return CN_ERR_UNSUPPORTED;
+    if ((long)c.C * c.H * c.W >= (1L << 31)) return CN_ERR_UNSUPPORTED;
+    const int rc = topk_route(c).rc;
+    if (rc != CN_OK) return rc;
+    if (((c.W & 3) == 0) && !cn_aligned16(c.heat)) return CN_ERR_ALIGN;
+    return CN_OK;
+}
+
+int topk_run(const TopkCall &c)
+{
+    const int rc = topk_checks(c);
+    if (rc != CN_OK) return rc;
+    const TopkPlan p = topk_route(c);
+    const EmitArgs &ea = c.ea;
+    bool missing = false;   // an output the mode writes
+    switch (c.mode) {
+    case MODE_CTDET: missing = !ea.wh || !ea.dets; break;
+    case MODE_POSE: missing = !ea.wh || !ea.kps_map || !ea.dets; break;
+    case MODE_TOPK: missing = !ea.out_scores || !ea.inds_out || !ea.cls_out; break;
+    case MODE_CHANNEL: missing = !ea.out_scores || !ea.inds_out; break;
+    default: return CN_ERR_UNSUPPORTED;
+    }
+    if (missing) return CN_ERR_NULL;
+    if (p.form != TOPK_BAND_DIRECT) {   // (the direct form touches no workspace)
+        if (!c.workspace) return CN_ERR_NULL;
+        if (c.workspace_bytes < (c.cand_only ? p.cand_bytes : p.total)) return CN_ERR_WORKSPACE;
+    }
+    switch (c.mode) {   // the one place a run-time mode becomes a template argument
+    case MODE_CTDET: return topk_launch<MODE_CTDET>(c, p);
+    case MODE_POSE: return topk_launch<MODE_POSE>(c, p);
+    case MODE_TOPK: return topk_launch<MODE_TOPK>(c, p);
+    default: return topk_launch<MODE_CHANNEL>(c, p);
+    }
+}
+
+// the call of an entry: shapes, flags, mode and where it works; the entry adds its outputs
+static TopkCall topk_call(const float *heat, int B, int C, int H, int W, int K, int flags, int mode,
+                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    TopkCall c = {};
+    c.heat = heat;
+    c.B = B; c.C = C; c.H = H; c.W = W; c.K = K;
+    c.flags = flags;
+    c.mode = mode;
+    c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes;
+    c.st = (hipStream_t)stream;
+    return c;
+}
+
+extern "C" size_t cn_ctdet_decode_workspace_bytes(int B, int C, int H, int W, int K)
+{
+    const TopkPlan p = topk_route(topk_call(nullptr, B, C, H, W, K, 0, MODE_CTDET, nullptr, 0, nullptr));
+    return p.rc == CN_OK ? p.total : 0;
+}
+
 // Where the one-launch image-level decode keeps its per-image state words inside the workspace of
 // cn_ctdet_decode_f32 / cn_topk_f32 (byte offset and size; 0 bytes when the shape takes another form).
 // They are zero between calls: a caller that owns its workspace (CN_DECODE_STATE_CLEAN) can check or
@@ -1546,66 +1461,10 @@ ImgPlan make_img_plan(int B, int C, int H, int W, int K, const BandPlan &bp)
 extern "C" int cn_decode_state_region(int B, int C, int H, int W, int K, size_t *offset, size_t *bytes)
 {
     if (!offset || !bytes) return CN_ERR_NULL;
-    *offset = 0; *bytes = 0;
-    BandPlan bp;
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return CN_ERR_SHAPE;
-    if (!make_band_plan(B, C, H, W, K, &bp)) return CN_ERR_UNSUPPORTED;
-    const ImgPlan ip = make_img_plan(B, C, H, W, K, bp);
-    if (ip.use && ip.one_pass) { *offset = ip.counts; *bytes = ip.state_bytes; }
-    return CN_OK;
-}
-namespace {
-// the image-level decode: TWO launches (group maxima; threshold + candidates + select + outputs)
-template <int MODE>
-int launch_image_topk(const float *heat, int B, int C, int H, int W, int K, int flags, const ImgPlan &ip,
-                      char *ws, const EmitArgs &ea, hipStream_t st)
-{
-    uint32_t *gpeak = (uint32_t *)(ws + ip.gpeak);
-    uint32_t *gall = (uint32_t *)(ws + ip.gall);
-    int32_t *counts = (int32_t *)(ws + ip.counts);
-    int32_t *done = (int32_t *)(ws + ip.done);
-    u64 *keys = (u64 *)(ws + ip.keys);
-    dim3 grid((unsigned)(B * C)), block(NT);
-    if (ip.one_pass && !(flags & CN_DECODE_TWO_LAUNCHES)) {
-        // ONE launch.  The image state words (arrival counter, floor) must be zero on entry and are
-        // left at zero by the kernel: a caller that keeps the workspace to itself says so
-        // (CN_DECODE_STATE_CLEAN) after zeroing it once; anyone else pays a small fill.
-        if (!(flags & CN_DECODE_STATE_CLEAN)) {
-            if (hipMemsetAsync(ws + ip.counts, 0, ip.state_bytes, st) != hipSuccess) return CN_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL(plane_select_merge_kernel<MODE>, grid, dim3(OP_NT), sizeof(SelShared), st, heat, B, C,
-                           H, W, flags, K, keys, (int32_t *)(ws + ip.pcount), done, (uint32_t *)(ws + ip.floorv),
-                           ea);
-        CN_CHECK_LAUNCH();
-        return CN_OK;
-    }
-    hipLaunchKernelGGL(group_max_kernel, grid, block, 0, st, heat, H, W, ip.nrg, ip.ncb, flags, gpeak,
-                       gall, C, counts, done);
-    CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(collect_merge_kernel<MODE>, grid, block, sizeof(SelShared), st, heat, C, H, W,
-                       ip.nrg, ip.ncb, flags, K, gpeak, gall, keys, ip.cap, counts, done, ea);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-}  // namespace
-
-extern "C" size_t cn_ctdet_decode_workspace_bytes(int B, int C, int H, int W, int K)
-{
-    BandPlan bp;
-    if (B <= 0 || C <= 0 || K <= 0 || !make_band_plan(B, C, H, W, K, &bp)) return 0;
-    return make_img_plan(B, C, H, W, K, bp).total;
-}
-
-static int decode_checks(const void *heat, int B, int C, int H, int W, int K, BandPlan *bp)
-{
-    if (!heat) return CN_ERR_NULL;
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return CN_ERR_SHAPE;
-    if ((long)K > (long)H * W) return CN_ERR_SHAPE;  // torch.topk: k out of range
-    if (K > KMAX) return CN_ERR_UNSUPPORTED;
-    if ((long)C * H * W >= (1L << 31)) return CN_ERR_UNSUPPORTED;
-    if (!make_band_plan(B, C, H, W, K, bp)) return CN_ERR_UNSUPPORTED;
-    if (((W & 3) == 0) && !cn_aligned16(heat)) return CN_ERR_ALIGN;
-    return CN_OK;
+    const TopkPlan p = topk_route(topk_call(nullptr, B, C, H, W, K, 0, MODE_CTDET, nullptr, 0, nullptr));
+    *offset = p.state_offset;   // (0, 0 without a plan)
+    *bytes = p.state_bytes;
+    return p.rc;
 }
 
 extern "C" int cn_ctdet_decode_f32(const float *heat, const float *wh, const float *reg, int B,
@@ -1613,242 +1472,38 @@ extern "C" int cn_ctdet_decode_f32(const float *heat, const float *wh, const flo
                                    float *dets, int32_t *inds, void *workspace,
                                    size_t workspace_bytes, void *stream)
 {
-    BandPlan bp;
-    int rc = decode_checks(heat, B, C, H, W, K, &bp);
-    if (rc != CN_OK) return rc;
-    if (!wh || !dets || !workspace) return CN_ERR_NULL;
-    const size_t need = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
-    if (workspace_bytes < need) return CN_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)B * C * bp.nbands * K;
-    float *cand_score = (float *)workspace;
-    int32_t *cand_idx = (int32_t *)((char *)workspace + cn_align_up(n * sizeof(float), 256));
-    const ImgPlan ip = make_img_plan(B, C, H, W, K, bp);
-    if (ip.use && !(apply_sigmoid & 2048)) {   // bit 11: force the per-band select (tests / A-B)
-        const EmitArgs ea = {wh, reg, cat_spec_wh, dets, 6, inds, nullptr, nullptr};
-        return launch_image_topk<MODE_CTDET>(heat, B, C, H, W, K, apply_sigmoid, ip, (char *)workspace, ea, st);
-    }
-    rc = launch_nms_topk(heat, B, C, H, W, K, apply_sigmoid, bp, cand_score, cand_idx, st);
-    if (rc != CN_OK) return rc;
-    hipLaunchKernelGGL(merge_topk_kernel<MODE_CTDET>, dim3(B), dim3(NTM), sizeof(SelShared), st,
-                       cand_score, cand_idx, C * bp.nbands * K, bp.nbands * K, H, W, K, C, wh, reg,
-                       cat_spec_wh, dets, 6, inds, (float *)nullptr, (const float *)nullptr, 0,
-                       (int32_t *)nullptr);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    TopkCall c = topk_call(heat, B, C, H, W, K, apply_sigmoid, MODE_CTDET, workspace, workspace_bytes, stream);
+    c.ea.wh = wh;
+    c.ea.reg = reg;
+    c.ea.cat_spec_wh = cat_spec_wh;
+    c.ea.dets = dets;
+    c.ea.inds_out = inds;
+    return topk_run(c);
+}
+
+extern "C" int cn_topk_f32(const float *heat, int B, int C, int H, int W, int K, int apply_sigmoid,
+                           float *scores, int32_t *inds, int32_t *clses, void *workspace,
+                           size_t workspace_bytes, void *stream)
+{
+    TopkCall c = topk_call(heat, B, C, H, W, K, apply_sigmoid, MODE_TOPK, workspace, workspace_bytes, stream);
+    c.ea.out_scores = scores;
+    c.ea.inds_out = inds;
+    c.ea.cls_out = clses;
+    return topk_run(c);
 }
 
 extern "C" int cn_nms_topk_channel_f32(const float *heat, int B, int C, int H, int W, int K,
                                        int apply_sigmoid, float *scores, int32_t *inds,
                                        void *workspace, size_t workspace_bytes, void *stream)
 {
-    BandPlan bp;
-    int rc = decode_checks(heat, B, C, H, W, K, &bp);
-    if (rc != CN_OK) return rc;
-    if (!scores || !inds) return CN_ERR_NULL;
-    hipStream_t st = (hipStream_t)stream;
-    if (bp.nbands == 1) {
-        // one band per plane: kernel 1 already emits the final sorted (B,C,K) lists
-        return launch_nms_topk(heat, B, C, H, W, K, apply_sigmoid, bp, scores, inds, st);
-    }
-    if (!workspace) return CN_ERR_NULL;
-    const size_t need = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
-    if (workspace_bytes < need) return CN_ERR_WORKSPACE;
-    const size_t n = (size_t)B * C * bp.nbands * K;
-    float *cand_score = (float *)workspace;
-    int32_t *cand_idx = (int32_t *)((char *)workspace + cn_align_up(n * sizeof(float), 256));
-    rc = launch_nms_topk(heat, B, C, H, W, K, apply_sigmoid, bp, cand_score, cand_idx, st);
-    if (rc != CN_OK) return rc;
-    hipLaunchKernelGGL(merge_topk_kernel<MODE_CHANNEL>, dim3(B * C), dim3(NTM), sizeof(SelShared),
-                       st, cand_score, cand_idx, bp.nbands * K, bp.nbands * K, H, W, K, C,
-                       (const float *)nullptr, (const float *)nullptr, 0, (float *)nullptr, 0, inds,
-                       scores, (const float *)nullptr, 0, (int32_t *)nullptr);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    TopkCall c = topk_call(heat, B, C, H, W, K, apply_sigmoid, MODE_CHANNEL, workspace, workspace_bytes, stream);
+    c.ea.out_scores = scores;
+    c.ea.inds_out = inds;
+    return topk_run(c);
 }
-
 
 // ---------------------------------------------------------------------------
-// multi_pose decode (models/decode.py:497-571)
-//   stage A  nms_topk + merge<MODE_POSE>: boxes, scores, regression keypoints
-//   stage B  nms_topk (+ channel merge) on hm_hp: K candidates per joint (_topk_channel)
-//   stage C  pose_match_kernel: nearest candidate per (detection, joint), reject rule, blend
-// Arithmetic is kept in the reference's association (no FMA contraction) so the result
-// is bit-identical to torch on CPU: the argmin and the threshold tests are discontinuous.
-// ---------------------------------------------------------------------------
-namespace {
-
-__global__ __launch_bounds__(KMAX) void pose_match_kernel(
-    const float *__restrict__ hp_scores, const int32_t *__restrict__ hp_inds,
-    const float *__restrict__ hp_offset, float *__restrict__ dets, int J, int K, int H, int W,
-    int det_dim)
-{
-    __shared__ float cs[KMAX], cx[KMAX], cy[KMAX];
-    const int j = blockIdx.x, b = blockIdx.y;
-    const int q = threadIdx.x;
-    const int HW = H * W;
-    const float thresh = 0.1f;
-    if (q < K) {
-        const size_t o = ((size_t)b * J + j) * K + q;
-        float s = hp_scores[o];
-        const int ind = hp_inds[o];
-        const int yi = ind / W, xi = ind - yi * W;
-        float x = (float)xi, y = (float)yi;
-        if (hp_offset) {  // decode.py:534-539
-            x = add_rn(x, hp_offset[((size_t)b * 2 + 0) * HW + ind]);
-            y = add_rn(y, hp_offset[((size_t)b * 2 + 1) * HW + ind]);
-        } else {
-            x = add_rn(x, 0.5f);
-            y = add_rn(y, 0.5f);
-        }
-        const float m = (s > thresh) ? 1.0f : 0.0f;  // decode.py:544-547
-        const float im = __fsub_rn(1.0f, m);
-        cs[q] = add_rn(mul_rn(im, -1.0f), mul_rn(m, s));
-        cy[q] = add_rn(mul_rn(im, -10000.0f), mul_rn(m, y));
-        cx[q] = add_rn(mul_rn(im, -10000.0f), mul_rn(m, x));
-    }
-    __syncthreads();
-    if (q < K) {
-        float *d = dets + ((size_t)b * K + q) * det_dim;
-        const float rx = d[5 + 2 * j], ry = d[5 + 2 * j + 1];
-        float best = 0.f;
-        int bi = -1;
-        for (int c = 0; c < K; ++c) {  // decode.py:550-551, first minimum
-            const float dx = __fsub_rn(rx, cx[c]);
-            const float dy = __fsub_rn(ry, cy[c]);
-            const float dist = __fsqrt_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)));
-            if (bi < 0 || dist < best) {
-                best = dist;
-                bi = c;
-            }
-        }
-        const float sc = cs[bi], kx = cx[bi], ky = cy[bi];
-        const float l = d[0], t = d[1], r = d[2], bt = d[3];
-        const float bh = __fsub_rn(bt, t), bw = __fsub_rn(r, l);
-        const float mx = mul_rn(fmaxf(bh, bw), 0.3f);
-        const bool reject = (kx < l) || (kx > r) || (ky < t) || (ky > bt) || (sc < thresh) ||
-                            (best > mx);  // decode.py:562-565
-        const float m = reject ? 1.0f : 0.0f;
-        const float im = __fsub_rn(1.0f, m);
-        d[5 + 2 * j] = add_rn(mul_rn(im, kx), mul_rn(m, rx));  // decode.py:566
-        d[5 + 2 * j + 1] = add_rn(mul_rn(im, ky), mul_rn(m, ry));
-    }
-}
-
-struct PoseWs {
-    size_t cand_s, cand_i, hp_s, hp_i, total;
-};
-bool pose_ws_plan(int B, int C, int H, int W, int J, int K, PoseWs *p, BandPlan *bp_hm,
-                  BandPlan *bp_hp)
-{
-    if (!make_band_plan(B, C, H, W, K, bp_hm) || !make_band_plan(B, J > 0 ? J : 1, H, W, K, bp_hp))
-        return false;
-    const size_t n_hm = (size_t)B * C * bp_hm->nbands * K;
-    const size_t n_hp = (size_t)B * J * bp_hp->nbands * K;
-    const size_t n = n_hm > n_hp ? n_hm : n_hp;  // candidate buffers are reused by both stages
-    size_t o = 0;
-    p->cand_s = o; o += cn_align_up(n * 4, 256);
-    p->cand_i = o; o += cn_align_up(n * 4, 256);
-    p->hp_s = o;   o += cn_align_up((size_t)B * J * K * 4, 256);
-    p->hp_i = o;   o += cn_align_up((size_t)B * J * K * 4, 256);
-    p->total = o;
-    return true;
-}
-
-// stages B and C on rows that hold stage A (cn_multi_pose_decode_f32 and cn_multi_pose_match_f32 both end here)
-int pose_match_stages(const float *hm_hp, const float *hp_offset, int B, int J, int H, int W, int K,
-                      int apply_sigmoid, const BandPlan &bph, float *dets, float *cand_s, int32_t *cand_i,
-                      float *hp_s, int32_t *hp_i, hipStream_t st)
-{
-    const int D = 4 + 1 + 2 * J + 1;
-    int rc;
-    // stage B: per-joint top-K of the keypoint heat-map
-    if (bph.nbands == 1) {
-        rc = launch_nms_topk(hm_hp, B, J, H, W, K, apply_sigmoid, bph, hp_s, hp_i, st);
-        if (rc != CN_OK) return rc;
-    } else {
-        rc = launch_nms_topk(hm_hp, B, J, H, W, K, apply_sigmoid, bph, cand_s, cand_i, st);
-        if (rc != CN_OK) return rc;
-        hipLaunchKernelGGL(merge_topk_kernel<MODE_CHANNEL>, dim3(B * J), dim3(NTM),
-                           sizeof(SelShared), st, cand_s, cand_i, bph.nbands * K, bph.nbands * K, H,
-                           W, K, J, (const float *)nullptr, (const float *)nullptr, 0,
-                           (float *)nullptr, 0, hp_i, hp_s, (const float *)nullptr, 0,
-                           (int32_t *)nullptr);
-        CN_CHECK_LAUNCH();
-    }
-    // stage C
-    hipLaunchKernelGGL(pose_match_kernel, dim3(J, B), dim3(KMAX), 0, st, hp_s, hp_i, hp_offset,
-                       dets, J, K, H, W, D);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
-}  // namespace
-
-extern "C" size_t cn_multi_pose_decode_workspace_bytes(int B, int C, int H, int W, int J, int K)
-{
-    PoseWs p;
-    BandPlan a, b;
-    if (B <= 0 || C <= 0 || J <= 0 || K <= 0 || !pose_ws_plan(B, C, H, W, J, K, &p, &a, &b)) return 0;
-    return p.total;
-}
-
-extern "C" int cn_multi_pose_decode_f32(const float *heat, const float *wh, const float *kps,
-                                        const float *reg, const float *hm_hp,
-                                        const float *hp_offset, int B, int C, int H, int W, int J,
-                                        int K, int apply_sigmoid, float *dets, void *workspace,
-                                        size_t workspace_bytes, void *stream)
-{
-    BandPlan bp, bph;
-    int rc = decode_checks(heat, B, C, H, W, K, &bp);
-    if (rc != CN_OK) return rc;
-    if (!wh || !kps || !dets || !workspace) return CN_ERR_NULL;
-    if (J <= 0) return CN_ERR_SHAPE;
-    PoseWs p;
-    if (!pose_ws_plan(B, C, H, W, J, K, &p, &bp, &bph)) return CN_ERR_UNSUPPORTED;
-    if (workspace_bytes < p.total) return CN_ERR_WORKSPACE;
-    if (hm_hp && ((W & 3) == 0) && !cn_aligned16(hm_hp)) return CN_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    float *cand_s = (float *)(ws + p.cand_s);
-    int32_t *cand_i = (int32_t *)(ws + p.cand_i);
-    float *hp_s = (float *)(ws + p.hp_s);
-    int32_t *hp_i = (int32_t *)(ws + p.hp_i);
-    const int D = 4 + 1 + 2 * J + 1;
-    // stage A
-    rc = launch_nms_topk(heat, B, C, H, W, K, apply_sigmoid, bp, cand_s, cand_i, st);
-    if (rc != CN_OK) return rc;
-    hipLaunchKernelGGL(merge_topk_kernel<MODE_POSE>, dim3(B), dim3(NTM), sizeof(SelShared), st,
-                       cand_s, cand_i, C * bp.nbands * K, bp.nbands * K, H, W, K, C, wh, reg, 0,
-                       dets, D, (int32_t *)nullptr, (float *)nullptr, kps, J, (int32_t *)nullptr);
-    CN_CHECK_LAUNCH();
-    if (!hm_hp) return CN_OK;
-    return pose_match_stages(hm_hp, hp_offset, B, J, H, W, K, apply_sigmoid, bph, dets, cand_s, cand_i, hp_s, hp_i,
-                             st);
-}
-
-extern "C" int cn_multi_pose_match_f32(const float *hm_hp, const float *hp_offset, int B, int J, int H, int W,
-                                       int K, int flags, float *dets, void *workspace, size_t workspace_bytes,
-                                       void *stream)
-{
-    BandPlan bp, bph;
-    if (J <= 0) return hm_hp ? CN_ERR_SHAPE : CN_ERR_NULL;
-    int rc = decode_checks(hm_hp, B, J, H, W, K, &bph);
-    if (rc != CN_OK) return rc;
-    if (!dets || !workspace) return CN_ERR_NULL;
-    PoseWs p;   // the layout of cn_multi_pose_decode_f32 with a one-class centre map
-    if (!pose_ws_plan(B, 1, H, W, J, K, &p, &bp, &bph)) return CN_ERR_UNSUPPORTED;
-    if (workspace_bytes < p.total) return CN_ERR_WORKSPACE;
-    char *ws = (char *)workspace;
-    return pose_match_stages(hm_hp, hp_offset, B, J, H, W, K, flags & CN_DECODE_SIGMOID, bph, dets,
-                             (float *)(ws + p.cand_s), (int32_t *)(ws + p.cand_i), (float *)(ws + p.hp_s),
-                             (int32_t *)(ws + p.hp_i), (hipStream_t)stream);
-}
-
-
-// ---------------------------------------------------------------------------
-// _topk / _transpose_and_gather_feat / ddd_decode (models/decode.py:103-119,
-// models/utils.py:12-26, models/decode.py:426-462)
+// _transpose_and_gather_feat (models/utils.py:12-26)
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -1868,73 +1523,7 @@ __global__ void gather_feat_kernel(const float *__restrict__ feat, const int32_t
                                              : __builtin_nanf("");
 }
 
-// one thread per (b,k): [xs, ys, score, rot(8), depth, dim(3), (wh(2),) cls]  (decode.py:433-460)
-__global__ void ddd_assemble_kernel(const float *__restrict__ scores, const int32_t *__restrict__ inds,
-                                    const int32_t *__restrict__ clses, const float *__restrict__ rot,
-                                    const float *__restrict__ depth, const float *__restrict__ dim,
-                                    const float *__restrict__ wh, const float *__restrict__ reg,
-                                    float *__restrict__ dets, int B, int K, int H, int W, int raw_depth)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * K) return;
-    const int b = i / K;
-    const int HW = H * W;
-    const int ind = inds[i];
-    const int yi = ind / W, xi = ind - yi * W;
-    float xs = (float)xi, ys = (float)yi;
-    if (reg) {
-        xs = xs + reg[((size_t)b * 2 + 0) * HW + ind];
-        ys = ys + reg[((size_t)b * 2 + 1) * HW + ind];
-    } else {
-        xs = xs + 0.5f;
-        ys = ys + 0.5f;
-    }
-    const int D = wh ? 18 : 16;
-    float *d = dets + (size_t)i * D;
-    d[0] = xs; d[1] = ys; d[2] = scores[i];
-    for (int c = 0; c < 8; ++c) d[3 + c] = rot[((size_t)b * 8 + c) * HW + ind];
-    float dep = depth[(size_t)b * HW + ind];
-    // CN_DECODE_DDD_RAW_DEPTH: the head's raw value; detectors/ddd.py:60 on the K gathered cells only
-    if (raw_depth) dep = 1.0f / (sigmoidf_ref(dep) + 1e-6f) - 1.0f;
-    d[11] = dep;
-    for (int c = 0; c < 3; ++c) d[12 + c] = dim[((size_t)b * 3 + c) * HW + ind];
-    if (wh) {
-        d[15] = wh[((size_t)b * 2 + 0) * HW + ind];
-        d[16] = wh[((size_t)b * 2 + 1) * HW + ind];
-    }
-    d[D - 1] = (float)clses[i];
-}
-
 }  // namespace
-
-extern "C" int cn_topk_f32(const float *heat, int B, int C, int H, int W, int K, int apply_sigmoid,
-                           float *scores, int32_t *inds, int32_t *clses, void *workspace,
-                           size_t workspace_bytes, void *stream)
-{
-    BandPlan bp;
-    int rc = decode_checks(heat, B, C, H, W, K, &bp);
-    if (rc != CN_OK) return rc;
-    if (!scores || !inds || !clses || !workspace) return CN_ERR_NULL;
-    const size_t need = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
-    if (workspace_bytes < need) return CN_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)B * C * bp.nbands * K;
-    float *cand_score = (float *)workspace;
-    int32_t *cand_idx = (int32_t *)((char *)workspace + cn_align_up(n * sizeof(float), 256));
-    const ImgPlan ip = make_img_plan(B, C, H, W, K, bp);
-    if (ip.use && !(apply_sigmoid & 2048)) {
-        const EmitArgs ea = {nullptr, nullptr, 0, nullptr, 0, inds, scores, clses};
-        return launch_image_topk<MODE_TOPK>(heat, B, C, H, W, K, apply_sigmoid, ip, (char *)workspace, ea, st);
-    }
-    rc = launch_nms_topk(heat, B, C, H, W, K, apply_sigmoid, bp, cand_score, cand_idx, st);
-    if (rc != CN_OK) return rc;
-    hipLaunchKernelGGL(merge_topk_kernel<MODE_TOPK>, dim3(B), dim3(NTM), sizeof(SelShared), st,
-                       cand_score, cand_idx, C * bp.nbands * K, bp.nbands * K, H, W, K, C,
-                       (const float *)nullptr, (const float *)nullptr, 0, (float *)nullptr, 0, inds,
-                       scores, (const float *)nullptr, 0, clses);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
 
 extern "C" int cn_gather_feat_f32(const float *feat, const int32_t *inds, float *out, int B, int C,
                                   int H, int W, int K, void *stream)
@@ -1948,417 +1537,3 @@ extern "C" int cn_gather_feat_f32(const float *feat, const int32_t *inds, float 
     return CN_OK;
 }
 
-extern "C" size_t cn_ddd_decode_workspace_bytes(int B, int C, int H, int W, int K)
-{
-    const size_t base = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
-    if (!base) return 0;
-    return base + 3 * cn_align_up((size_t)B * K * 4, 256);
-}
-
-extern "C" int cn_ddd_decode_f32(const float *heat, const float *rot, const float *depth,
-                                 const float *dim, const float *wh, const float *reg, int B, int C,
-                                 int H, int W, int K, int apply_sigmoid, float *dets,
-                                 void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (!rot || !depth || !dim || !dets || !workspace) return CN_ERR_NULL;
-    const size_t base = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
-    if (!base) return CN_ERR_UNSUPPORTED;
-    if (workspace_bytes < cn_ddd_decode_workspace_bytes(B, C, H, W, K)) return CN_ERR_WORKSPACE;
-    const size_t slot = cn_align_up((size_t)B * K * 4, 256);
-    float *scores = (float *)((char *)workspace + base);
-    int32_t *inds = (int32_t *)((char *)workspace + base + slot);
-    int32_t *clses = (int32_t *)((char *)workspace + base + 2 * slot);
-    int rc = cn_topk_f32(heat, B, C, H, W, K, apply_sigmoid & ~CN_DECODE_DDD_RAW_DEPTH, scores, inds, clses,
-                         workspace, base, stream);
-    if (rc != CN_OK) return rc;
-    hipLaunchKernelGGL(ddd_assemble_kernel, dim3(cn_cdiv(B * K, 128)), dim3(128), 0,
-                       (hipStream_t)stream, scores, inds, clses, rot, depth, dim, wh, reg, dets, B, K,
-                       H, W, (apply_sigmoid & CN_DECODE_DDD_RAW_DEPTH) ? 1 : 0);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
-// ---------------------------------------------------------------------------
-// exct_decode (models/decode.py:273-424; aggr_weight > 0: cn_exct_aggregate_f32 in front): ExtremeNet-style grouping of the
-// K best top / left / bottom / right extreme points into boxes.
-//   stage A  cn_topk_f32 x4 (_nms + _topk of the four extreme-point heat-maps)
-//   stage B  exct_score_kernel: the K^4 candidate scores (decode.py:316-366), written once
-//   stage C  exct_select_kernel: exact top-num_dets (radix select + 1024-key bitonic sort in
-//            LDS) and the box / extreme-point assembly (decode.py:372-420)
-// Candidate index = ((t*K + l)*K + b)*K + r, as the reference's view(batch, -1).
-// Tie order (unspecified by torch.topk): score desc, candidate index asc.
-// ---------------------------------------------------------------------------
-namespace {
-
-constexpr int EXCT_MAX_DETS = 1024;
-
-struct ExctLists {  // (B, K) arrays of the four _topk calls, order t, l, b, r
-    const float *score[4];
-    const int32_t *ind[4];
-    const int32_t *cls[4];
-};
-
-__device__ __forceinline__ float exct_score(const ExctLists &L, const float *__restrict__ ct_heat,
-                                            int b, int K, int H, int W, int C, int it, int il,
-                                            int ib, int ir, float scores_thresh, float center_thresh)
-{
-    const int o = b * K;
-    const float ts = L.score[0][o + it], ls = L.score[1][o + il], bs = L.score[2][o + ib],
-                rs = L.score[3][o + ir];
-    const int ti = L.ind[0][o + it], li = L.ind[1][o + il], bi = L.ind[2][o + ib],
-              ri = L.ind[3][o + ir];
-    const int tc = L.cls[0][o + it], lc = L.cls[1][o + il], bc = L.cls[2][o + ib],
-              rc = L.cls[3][o + ir];
-    const float t_y = (float)(ti / W), t_x = (float)(ti % W);
-    const float l_y = (float)(li / W), l_x = (float)(li % W);
-    const float b_y = (float)(bi / W), b_x = (float)(bi % W);
-    const float r_y = (float)(ri / W), r_x = (float)(ri % W);
-    // decode.py:331-336: centre of the box -> centre heat-map of the TOP point's class
-    const int cx = (int)((l_x + r_x + 0.5f) / 2.0f);
-    const int cy = (int)((t_y + b_y + 0.5f) / 2.0f);
-    const float cs = ct_heat[((size_t)b * C + tc) * H * W + (size_t)cy * W + cx];
-    // decode.py:343: (t + l + b + r + 2*ct) / 6, left to right
-    float s = ((((ts + ls) + bs) + rs) + 2.0f * cs) / 6.0f;
-    // decode.py:346-366: one unit off per violated rule, in the reference's order
-    const bool sc_bad = (ts < scores_thresh) || (ls < scores_thresh) || (bs < scores_thresh) ||
-                        (rs < scores_thresh) || (cs < center_thresh);
-    const bool cls_bad = (tc != lc) || (tc != bc) || (tc != rc);
-    const bool top_bad = (t_y > l_y) || (t_y > b_y) || (t_y > r_y);
-    const bool left_bad = (l_x > t_x) || (l_x > b_x) || (l_x > r_x);
-    const bool bottom_bad = (b_y < t_y) || (b_y < l_y) || (b_y < r_y);
-    const bool right_bad = (r_x < t_x) || (r_x < l_x) || (r_x < b_x);
-    s = s - (sc_bad ? 1.0f : 0.0f);
-    s = s - (cls_bad ? 1.0f : 0.0f);
-    s = s - (top_bad ? 1.0f : 0.0f);
-    s = s - (left_bad ? 1.0f : 0.0f);
-    s = s - (bottom_bad ? 1.0f : 0.0f);
-    s = s - (right_bad ? 1.0f : 0.0f);
-    return s;
-}
-
-__global__ void exct_score_kernel(const ExctLists L, const float *__restrict__ ct_heat,
-                                  float *__restrict__ cand, int K, int H, int W, int C,
-                                  float scores_thresh, float center_thresh)
-{
-    const int b = blockIdx.y;
-    const size_t n = (size_t)K * K * K * K;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const int ir = (int)(i % K), ib = (int)((i / K) % K), il = (int)((i / ((size_t)K * K)) % K),
-                  it = (int)(i / ((size_t)K * K * K));
-        cand[(size_t)b * n + i] =
-            exct_score(L, ct_heat, b, K, H, W, C, it, il, ib, ir, scores_thresh, center_thresh);
-    }
-}
-
-struct ExctRegr {
-    const float *r[4];  // t, l, b, r regression maps (B,2,H,W) or all null
-};
-
-// one 1024-thread workgroup per image
-// ``cls_map`` (B, H, W) or null: the class-agnostic form (agnex_ct_decode, decode.py:171-187,262-263) takes a
-// detection's class from the centre map's arg-max at the box centre instead of from the top point's list
-__global__ __launch_bounds__(NTM) void exct_select_kernel(
-    const float *__restrict__ cand, const ExctLists L, const ExctRegr R, float *__restrict__ dets,
-    int K, int H, int W, int num_dets, const int32_t *__restrict__ cls_map)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    SelShared &sh = *reinterpret_cast<SelShared *>(smem);
-    u64 *big = reinterpret_cast<u64 *>(smem + sizeof(SelShared));  // [EXCT_MAX_DETS]
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const uint32_t n = (uint32_t)K * K * K * K;
-    const float *cs = cand + (size_t)b * n;
-
-    auto for_each = [&](auto &&f) {
-        for (uint32_t j = tid; j < n; j += NTM) {
-            const uint32_t kk = f2key(cs[j] + 0.0f);
-            f(((u64)kk << 32) | (u64)(0xFFFFFFFFu - j), false);
-        }
-    };
-    u64 prefix, mask;
-    radix_select<NTM>(for_each, (uint32_t)num_dets, sh, prefix, mask);
-    // collect the selected keys (exactly num_dets of them) and sort all 1024 slots descending
-    __syncthreads();
-    if (tid == 0) sh.cnt = 0;
-    big[tid] = 0;  // pad keys sort last (NTM == EXCT_MAX_DETS)
-    __syncthreads();
-    for_each([&](u64 k, bool) {
-        if ((k & mask) >= prefix) {
-            const uint32_t pos = atomicAdd(&sh.cnt, 1u);
-            if (pos < (uint32_t)EXCT_MAX_DETS) big[pos] = k;
-        }
-    });
-    __syncthreads();
-    for (int k = 2; k <= EXCT_MAX_DETS; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int partner = tid ^ j;
-            if (partner > tid) {
-                const u64 x = big[tid], y = big[partner];
-                const bool desc = (tid & k) == 0;
-                if (desc ? (x < y) : (x > y)) {
-                    big[tid] = y;
-                    big[partner] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid >= num_dets) return;
-    const u64 key = big[tid];
-    const float score = key2f((uint32_t)(key >> 32));
-    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)key;
-    const int ir = (int)(idx % K), ib = (int)((idx / K) % K), il = (int)((idx / (K * K)) % K),
-              it = (int)(idx / (K * K * K));
-    const int o = b * K;
-    const int HW = H * W;
-    const int sel[4] = {it, il, ib, ir};
-    float xs[4], ys[4], gx[4], gy[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int ind = L.ind[e][o + sel[e]];
-        float x = (float)(ind % W), y = (float)(ind / W);
-        gx[e] = x;
-        gy[e] = y;
-        if (R.r[0]) {  // decode.py:372-390 (all four regression maps given)
-            x = x + R.r[e][((size_t)b * 2 + 0) * HW + ind];
-            y = y + R.r[e][((size_t)b * 2 + 1) * HW + ind];
-        } else {      // decode.py:391-399
-            x = x + 0.5f;
-            y = y + 0.5f;
-        }
-        xs[e] = x;
-        ys[e] = y;
-    }
-    float *d = dets + ((size_t)b * num_dets + tid) * 14;
-    d[0] = xs[1]; d[1] = ys[0]; d[2] = xs[3]; d[3] = ys[2];  // bboxes = (l_x, t_y, r_x, b_y)
-    d[4] = score;
-    d[5] = xs[0]; d[6] = ys[0]; d[7] = xs[1]; d[8] = ys[1];
-    d[9] = xs[2]; d[10] = ys[2]; d[11] = xs[3]; d[12] = ys[3];
-    if (cls_map) {   // decode.py:171-172: the box centre on the grid, from the points BEFORE their offsets
-        const int cx = (int)((gx[1] + gx[3] + 0.5f) / 2.0f);
-        const int cy = (int)((gy[0] + gy[2] + 0.5f) / 2.0f);
-        d[13] = (float)cls_map[(size_t)b * HW + (size_t)cy * W + cx];
-    } else {
-        d[13] = (float)L.cls[0][o + it];                      // clses = t_clses
-    }
-}
-
-// agnex_ct_decode's `torch.max(ct_heat, dim=1)` (decode.py:164): per cell the largest value over the classes and
-// the FIRST class that holds it
-__global__ void channel_max_kernel(const float *__restrict__ heat, float *__restrict__ vmax,
-                                   int32_t *__restrict__ imax, int C, int HW, size_t cells)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = i / HW, p = i - b * HW;
-        const float *src = heat + b * (size_t)C * HW + p;
-        float best = src[0];
-        int arg = 0;
-        for (int c = 1; c < C; ++c) {
-            const float v = src[(size_t)c * HW];
-            if (v > best) {
-                best = v;
-                arg = c;
-            }
-        }
-        vmax[i] = best;
-        imax[i] = arg;
-    }
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------
-// Edge aggregation of exct_decode (models/decode.py:17-90, aggr_weight > 0): along a row (_h_aggregate)
-// or a column (_v_aggregate) of every plane, from both ends, a running sum that continues while the
-// values do not fall -- ret[i] = heat[i] + ret[i-1] * (heat[i] >= heat[i-1]) -- minus the value itself;
-// out = (w * first + w * second) + heat in the reference's order of float32 operations.  One thread per
-// line, two sequential passes (the recurrence is serial by definition; the maps are small).
-// ---------------------------------------------------------------------------
-namespace {
-__global__ void exct_aggregate_kernel(const float *__restrict__ heat, float *__restrict__ out, int planes,
-                                      int H, int W, int horizontal, float w)
-{
-    const int nline = horizontal ? H : W, len = horizontal ? W : H;
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)planes * nline) return;
-    const int plane = (int)(t / nline), line = (int)(t - (long)plane * nline);
-    const size_t base = (size_t)plane * H * W + (horizontal ? (size_t)line * W : (size_t)line);
-    const size_t step = horizontal ? 1 : (size_t)W;
-    // first pass (from the start: _left / _top): out holds ret - heat
-    float prev_h = heat[base], prev_r = prev_h;
-    out[base] = add_rn(prev_r, -prev_h);
-    for (int i = 1; i < len; ++i) {
-        const float h = heat[base + i * step];
-        const float r = add_rn(h, mul_rn(prev_r, (h >= prev_h) ? 1.0f : 0.0f));
-        out[base + i * step] = add_rn(r, -h);
-        prev_h = h;
-        prev_r = r;
-    }
-    // second pass (from the end: _right / _bottom) and the combination
-    prev_h = heat[base + (size_t)(len - 1) * step];
-    prev_r = prev_h;
-    {
-        const size_t o = base + (size_t)(len - 1) * step;
-        out[o] = add_rn(add_rn(mul_rn(w, out[o]), mul_rn(w, add_rn(prev_r, -prev_h))), prev_h);
-    }
-    for (int i = len - 2; i >= 0; --i) {
-        const size_t o = base + i * step;
-        const float h = heat[o];
-        const float r = add_rn(h, mul_rn(prev_r, (h >= prev_h) ? 1.0f : 0.0f));
-        out[o] = add_rn(add_rn(mul_rn(w, out[o]), mul_rn(w, add_rn(r, -h))), h);
-        prev_h = h;
-        prev_r = r;
-    }
-}
-}  // namespace
-
-extern "C" int cn_exct_aggregate_f32(const float *heat, float *out, int B, int C, int H, int W,
-                                     int horizontal, float aggr_weight, void *stream)
-{
-    if (!heat || !out) return CN_ERR_NULL;
-    if (heat == out) return CN_ERR_UNSUPPORTED;      // two passes read the input
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return CN_ERR_SHAPE;
-    const long lines = (long)B * C * (horizontal ? H : W);
-    hipLaunchKernelGGL(exct_aggregate_kernel, dim3((unsigned)((lines + 63) / 64)), dim3(64), 0,
-                       (hipStream_t)stream, heat, out, B * C, H, W, horizontal ? 1 : 0, aggr_weight);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
-namespace {
-// decode.py:297-305 for one edge map: heat * (max_pool2d(heat, 3, 1, 1) == heat), then values > 1 set
-// to 1.  (Clamping BEFORE the peak test would turn every plateau of clamped cells into peaks.)
-__global__ void exct_nms_clamp_kernel(const float *__restrict__ heat, float *__restrict__ out, int H, int W,
-                                      size_t total)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W), y = (int)((i / W) % H);
-        const float v = heat[i];
-        float m = v;
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int yy = y + dy, xx = x + dx;
-                if (yy >= 0 && yy < H && xx >= 0 && xx < W) m = fmaxf(m, heat[i + (long)dy * W + dx]);
-            }
-        out[i] = (m == v) ? fminf(v, 1.0f) : 0.0f;
-    }
-}
-}  // namespace
-
-extern "C" size_t cn_exct_decode_workspace_bytes(int B, int C, int H, int W, int K)
-{
-    const size_t base = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
-    if (!base) return 0;
-    const size_t lists = 4 * 3 * cn_align_up((size_t)B * K * 4, 256);
-    const size_t cand = cn_align_up((size_t)B * K * K * K * K * sizeof(float), 256);
-    const size_t map = cn_align_up((size_t)B * C * H * W * sizeof(float), 256);   // CN_EXCT_CLAMP_ONE: one peak-tested, clamped edge map
-    return base + lists + cand + map;
-}
-
-static int exct_decode_impl(const float *t_heat, const float *l_heat, const float *b_heat,
-                            const float *r_heat, const float *ct_heat, const float *t_regr,
-                            const float *l_regr, const float *b_regr, const float *r_regr,
-                            int B, int C, int H, int W, int K, float scores_thresh,
-                            float center_thresh, int num_dets, int apply_sigmoid,
-                            float *dets, void *workspace, size_t workspace_bytes,
-                            void *stream, const int32_t *cls_map)
-{
-    if (!t_heat || !l_heat || !b_heat || !r_heat || !ct_heat || !dets || !workspace) return CN_ERR_NULL;
-    if (num_dets <= 0 || K <= 0) return CN_ERR_SHAPE;
-    if (K > 64 || num_dets > EXCT_MAX_DETS) return CN_ERR_UNSUPPORTED;  // K^4 must fit 32 bits / LDS sort
-    if ((long)num_dets > (long)K * K * K * K) return CN_ERR_SHAPE;      // torch.topk: k out of range
-    if (apply_sigmoid & ~CN_EXCT_CLAMP_ONE) return CN_ERR_UNSUPPORTED;  // the centre map is gathered, not scanned
-    const bool clamp_one = (apply_sigmoid & CN_EXCT_CLAMP_ONE) != 0;
-    const size_t base = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
-    if (!base) return CN_ERR_UNSUPPORTED;
-    if (workspace_bytes < cn_exct_decode_workspace_bytes(B, C, H, W, K)) return CN_ERR_WORKSPACE;
-    const bool all_regr = t_regr && l_regr && b_regr && r_regr;  // decode.py:372-373
-    const size_t slot = cn_align_up((size_t)B * K * 4, 256);
-    char *p = (char *)workspace + base;
-    ExctLists L;
-    const float *heats[4] = {t_heat, l_heat, b_heat, r_heat};
-    for (int e = 0; e < 4; ++e) {
-        float *s = (float *)p; p += slot;
-        int32_t *i = (int32_t *)p; p += slot;
-        int32_t *c = (int32_t *)p; p += slot;
-        int rc;
-        if (clamp_one) {
-            // peak test on the raw map, survivors clamped to 1 (decode.py:297-305), then the plain _topk
-            // over every cell of the result (zeros of the suppressed cells take part, as in the reference)
-            const size_t cells = (size_t)B * C * H * W;
-            float *tmp = (float *)((char *)workspace + base + 4 * 3 * slot +
-                                   cn_align_up((size_t)B * K * K * K * K * sizeof(float), 256));
-            hipLaunchKernelGGL(exct_nms_clamp_kernel, dim3((unsigned)((cells + 255) / 256 < 8192 ? (cells + 255) / 256 : 8192)),
-                               dim3(256), 0, (hipStream_t)stream, heats[e], tmp, H, W, cells);
-            CN_CHECK_LAUNCH();
-            rc = cn_topk_f32(tmp, B, C, H, W, K, CN_DECODE_NO_PEAK_TEST, s, i, c, workspace, base, stream);
-        } else {
-            rc = cn_topk_f32(heats[e], B, C, H, W, K, 0, s, i, c, workspace, base, stream);
-        }
-        if (rc != CN_OK) return rc;
-        L.score[e] = s; L.ind[e] = i; L.cls[e] = c;
-    }
-    float *cand = (float *)p;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)K * K * K * K;
-    dim3 grid((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096), B);
-    hipLaunchKernelGGL(exct_score_kernel, grid, dim3(256), 0, st, L, ct_heat, cand, K, H, W, C,
-                       scores_thresh, center_thresh);
-    CN_CHECK_LAUNCH();
-    ExctRegr R;
-    R.r[0] = all_regr ? t_regr : nullptr; R.r[1] = all_regr ? l_regr : nullptr;
-    R.r[2] = all_regr ? b_regr : nullptr; R.r[3] = all_regr ? r_regr : nullptr;
-    const size_t lds = sizeof(SelShared) + EXCT_MAX_DETS * sizeof(u64);
-    hipLaunchKernelGGL(exct_select_kernel, dim3(B), dim3(NTM), lds, st, cand, L, R, dets, K, H, W,
-                       num_dets, cls_map);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
-}
-
-extern "C" int cn_exct_decode_f32(const float *t_heat, const float *l_heat, const float *b_heat,
-                                  const float *r_heat, const float *ct_heat, const float *t_regr,
-                                  const float *l_regr, const float *b_regr, const float *r_regr,
-                                  int B, int C, int H, int W, int K, float scores_thresh,
-                                  float center_thresh, int num_dets, int apply_sigmoid,
-                                  float *dets, void *workspace, size_t workspace_bytes,
-                                  void *stream)
-{
-    return exct_decode_impl(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr, B, C, H, W, K,
-                            scores_thresh, center_thresh, num_dets, apply_sigmoid, dets, workspace,
-                            workspace_bytes, stream, nullptr);
-}
-
-// agnex_ct_decode (models/decode.py:121-271): the class-agnostic form -- ONE top / left / bottom / right map per
-// image, the centre map over C classes.  The grouping is exct_decode's over single-channel maps (every point is
-// "class 0": the class rule never fires and subtracts an exact 0) against the per-cell maximum of the centre map;
-// a detection's class is that map's arg-max at the box centre.  Workspace: the single-class exct workspace + the
-// (B, H, W) maximum and arg-max planes.
-extern "C" size_t cn_agnex_ct_decode_workspace_bytes(int B, int C, int H, int W, int K)
-{
-    const size_t base = cn_exct_decode_workspace_bytes(B, 1, H, W, K);
-    if (!base || C <= 0) return 0;
-    return base + 2 * cn_align_up((size_t)B * H * W * 4, 256);
-}
-
-extern "C" int cn_agnex_ct_decode_f32(const float *t_heat, const float *l_heat, const float *b_heat,
-                                      const float *r_heat, const float *ct_heat, const float *t_regr,
-                                      const float *l_regr, const float *b_regr, const float *r_regr,
-                                      int B, int C, int H, int W, int K, float scores_thresh,
-                                      float center_thresh, int num_dets, int flags, float *dets,
-                                      void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (!t_heat || !l_heat || !b_heat || !r_heat || !ct_heat || !dets || !workspace) return CN_ERR_NULL;
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return CN_ERR_SHAPE;
-    const size_t base = cn_exct_decode_workspace_bytes(B, 1, H, W, K);
-    if (!base) return CN_ERR_UNSUPPORTED;
-    if (workspace_bytes < cn_agnex_ct_decode_workspace_bytes(B, C, H, W, K)) return CN_ERR_WORKSPACE;
-    const size_t cells = (size_t)B * H * W;
-    float *vmax = (float *)((char *)workspace + base);
-    int32_t *imax = (int32_t *)((char *)workspace + base + cn_align_up(cells * 4, 256));
-    const unsigned grid = (unsigned)((cells + 255) / 256 < 8192 ? (cells + 255) / 256 : 8192);
-    hipLaunchKernelGGL(channel_max_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ct_heat, vmax, imax, C,
-                       H * W, cells);
-    CN_CHECK_LAUNCH();
-    return exct_decode_impl(t_heat, l_heat, b_heat, r_heat, vmax, t_regr, l_regr, b_regr, r_regr, B, 1, H, W, K,
-                            scores_thresh, center_thresh, num_dets, flags, dets, workspace, base, stream, imax);
-}

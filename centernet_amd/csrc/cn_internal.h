@@ -1,5 +1,6 @@
 // cn_internal.h -- prototypes of the functions one .hip file defines and another calls, and the two call
-// descriptions they pass (ConvCall: the convolution family, DcnWinCall: the f32s deformable kernels).  Included
+// descriptions they pass (ConvCall: the convolution family, DcnWinCall: the f32s deformable kernels, TopkCall: the
+// top-K of the decoders).  Included
 // by both sides, so the defining file is compiled against the declaration its callers see.
 #pragma once
 #include "cn_common.h"
@@ -54,6 +55,51 @@ struct DcnWinCall {
 int cn_dcn_window_f32s(const DcnWinCall &c, int min_wgs, int *ksplit_out, hipStream_t st);
 int cn_dcn_team_f32s(const DcnWinCall &c, int nmode, int *ksplit_out, hipStream_t st);
 int cn_dcn_wide_f32s(const DcnWinCall &c, int nb, int *ksplit_out, hipStream_t st);
+
+// ---- cn_decode.hip: the top-K of a heat-map, one call description.  Every entry that ranks a heat-map fills a
+// TopkCall; topk_route() says which form the call takes and where its scratch lives, topk_run() checks, asks
+// the route and launches.  cn_decode_tasks.hip (pose, ddd, exct, agnex) reaches the top-K through these.
+enum { MODE_CTDET = 0, MODE_CHANNEL = 1, MODE_POSE = 2, MODE_TOPK = 3 };   // what the K rows become
+struct EmitArgs {              // outputs of the K rows (emit_rows in cn_decode.hip); unused ones null / 0
+    const float *wh, *reg;
+    int cat_spec_wh;
+    int J;                     // MODE_POSE: joints of kps_map
+    float *dets;               // rows of 6 + 2J floats: box, score, 2J keypoint coordinates, class
+    int32_t *inds_out;
+    float *out_scores;
+    int32_t *cls_out;
+    const float *kps_map;      // MODE_POSE: (B, 2J, H, W)
+};
+struct TopkCall {
+    const float *heat;         // (B, C, H, W)
+    int B, C, H, W, K;
+    int flags;                 // the entry's CN_DECODE_* bits
+    int mode;                  // MODE_*
+    EmitArgs ea;
+    void *workspace;
+    size_t workspace_bytes;
+    bool cand_only;            // the workspace holds the per-band candidate arrays only (the pose stages, which
+                               // never take an image-level form); else it must hold TopkPlan::total
+    hipStream_t st;
+};
+enum { TOPK_ONE_LAUNCH, TOPK_TWO_LAUNCHES, TOPK_BAND_MERGE, TOPK_BAND_DIRECT };
+struct TopkPlan {
+    int rc;                    // CN_OK, or why the shape has no plan (then nothing else is set)
+    int form;                  // TOPK_*
+    int R, nbands;             // per-band select: rows per band, bands per plane
+    size_t lds;                // its dynamic LDS bytes
+    int nrg, ncb;              // image-level forms: 8-row groups per plane, 128-column blocks per row
+    int cap;                   // candidate keys per image
+    // byte offsets in the workspace: the per-band candidate arrays, then the image-level scratch
+    size_t cand_score, cand_idx, cand_bytes;
+    size_t gpeak, gall, counts, done, floorv, pcount, keys;
+    size_t total;              // what cn_ctdet_decode_workspace_bytes answers: the same for every mode and flag
+    size_t state_offset, state_bytes;   // TOPK_ONE_LAUNCH: counts | done | floorv, zero between calls; else 0, 0
+    bool fill_state;           // ... and the call zeroes them itself (no CN_DECODE_STATE_CLEAN)
+};
+TopkPlan topk_route(const TopkCall &c);   // pure host function of the shapes, the mode and the flags
+int topk_checks(const TopkCall &c);       // the shape / pointer checks every top-K entry starts with
+int topk_run(const TopkCall &c);          // topk_checks, the mode's output and workspace checks, route, launch
 
 // ---- cn_dcn_general.hip
 int cn_dcn_general_launch(const float *input, const float *weight, const float *bias,

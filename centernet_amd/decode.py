@@ -1,5 +1,6 @@
 """Heat-map decode entry points (mirror of src/lib/models/decode.py), backed by the
-fused HIP kernels in csrc/cn_decode.hip / cn_pose.hip.
+fused HIP kernels in csrc/cn_decode.hip (the top-K forms and their one route) and
+csrc/cn_decode_tasks.hip (pose matching, ddd, exct, agnex).
 
 Same callables, same argument meaning, tensors in / tensor out:
     ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100)      decode.py:464-495
@@ -27,7 +28,6 @@ def _workspace(nbytes, device):
     return ws
 
 
-_STATE_CLEAN = 4096    # CN_DECODE_STATE_CLEAN: the workspace's image state words are zero (see below)
 _own_ws = {}
 _verify_state = __import__("os").environ.get("CN_DECODE_VERIFY_STATE") == "1"
 
@@ -45,6 +45,28 @@ def _own_workspace(entry, nbytes, device, shape):
         ws = torch.zeros(max(int(nbytes), 256), device=device, dtype=torch.uint8)
         _own_ws[key] = ws
     return ws
+
+
+def _owned_call(entry, cname, lib, shape, flags, device, call):
+    """``call(flags, ws) -> return code`` of the library entry ``cname`` on the owned workspace of ``entry``
+    for this (B, C, H, W, K), with ``DECODE_STATE_CLEAN`` added to ``flags``.  A failed call may have left the
+    image state words dirty: the owned workspaces are dropped, never reused.  ``CN_DECODE_VERIFY_STATE=1``
+    (debug): synchronise and look at the state words the kernel promises to leave at zero
+    (``cn_decode_state_region``)."""
+    ws = _own_workspace(entry, lib.cn_ctdet_decode_workspace_bytes(*shape), device, shape)
+    rc = call(flags | native.DECODE_STATE_CLEAN, ws)
+    if rc:
+        _own_ws.clear()
+    native.check(rc, cname)
+    if _verify_state:
+        import ctypes
+        off, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        native.check(lib.cn_decode_state_region(*shape, ctypes.byref(off), ctypes.byref(nb)),
+                     "cn_decode_state_region")
+        words = ws[off.value:off.value + nb.value].view(torch.int32)
+        if nb.value and int(words.abs().max().item()) != 0:
+            _own_ws.clear()
+            raise native.NativeError("%s left its workspace state words dirty" % cname)
 
 
 def _prep(*ts):
@@ -84,32 +106,18 @@ def ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100, apply_sigmoid=Fal
         raise RuntimeError("selected index k out of range")  # torch.topk's error
     dets = torch.empty((B, K, 6), device=heat.device, dtype=torch.float32)
     inds = torch.empty((B, K), device=heat.device, dtype=torch.int32)
-    nbytes = lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K)
     flags = int(bool(apply_sigmoid)) | int(_debug_flags)
-    if _debug_flags:
-        ws = _workspace(nbytes, heat.device)
+
+    def call(flags, ws):
+        return lib.cn_ctdet_decode_f32(native.ptr(heat), native.ptr(wh), native.ptr(reg), B, C, H, W, K,
+                                       int(bool(cat_spec_wh)), flags,
+                                       native.ptr(dets), native.ptr(inds), native.ptr(ws), ws.numel(),
+                                       native.stream_ptr())
+    if _debug_flags:    # (tests / A-B: a shared workspace, the library fills the state words)
+        ws = _workspace(lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), heat.device)
+        native.check(call(flags, ws), "cn_ctdet_decode_f32")
     else:
-        ws = _own_workspace("ctdet", nbytes, heat.device, (B, C, H, W, K))
-        flags |= _STATE_CLEAN
-    rc = lib.cn_ctdet_decode_f32(native.ptr(heat), native.ptr(wh), native.ptr(reg), B, C, H, W, K,
-                                 int(bool(cat_spec_wh)), flags,
-                                 native.ptr(dets), native.ptr(inds), native.ptr(ws), ws.numel(),
-                                 native.stream_ptr())
-    if rc:
-        # a failed call may have left the image state words of an owned workspace dirty: never reuse it
-        _own_ws.clear()
-    native.check(rc, "cn_ctdet_decode_f32")
-    if _verify_state and not _debug_flags:
-        # debug mode (CN_DECODE_VERIFY_STATE=1): synchronise and look at the state words the kernel
-        # promises to leave at zero (cn_decode_state_region)
-        import ctypes
-        off, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        native.check(lib.cn_decode_state_region(B, C, H, W, K, ctypes.byref(off), ctypes.byref(nb)),
-                     "cn_decode_state_region")
-        words = ws[off.value:off.value + nb.value].view(torch.int32)
-        if nb.value and int(words.abs().max().item()) != 0:
-            _own_ws.clear()
-            raise native.NativeError("cn_ctdet_decode_f32 left its workspace state words dirty")
+        _owned_call("ctdet", "cn_ctdet_decode_f32", lib, (B, C, H, W, K), flags, heat.device, call)
     return (dets, inds.long()) if return_inds else dets
 
 
@@ -142,12 +150,14 @@ def _cells_topk(heat, late, K, apply_sigmoid, maps=()):
         _expect(name, t, B, channels, H, W, dev)
     if K > H * W:
         raise RuntimeError("selected index k out of range")
-    ws = _own_workspace("topk", lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev, (B, C, H, W, K))
     st = native.stream_ptr()
-    scores, inds, clses, rc = _topk_f32(lib, heat, B, C, H, W, K, int(bool(apply_sigmoid)) | _STATE_CLEAN, ws, st)
-    if rc:
-        _own_ws.clear()     # (as in ctdet_decode: the state words of an owned workspace may be dirty)
-    native.check(rc, "cn_topk_f32")
+    out = []
+
+    def call(flags, ws):
+        out[:] = _topk_f32(lib, heat, B, C, H, W, K, flags, ws, st)
+        return out.pop()
+    _owned_call("topk", "cn_topk_f32", lib, (B, C, H, W, K), int(bool(apply_sigmoid)), dev, call)
+    scores, inds, clses = out
     return heat, B, C, H, W, scores, inds, clses, st
 
 
@@ -227,10 +237,6 @@ def multi_pose_decode_at_cells(heat, late, hm_hp=None, hp_offset=None, K=100, ap
     return _cells_result(dets, inds, vals, return_inds, return_vals)
 
 
-_NO_PEAK_TEST = 512   # flag bit of the decode entry points: rank every cell (plain topk)
-_EXCT_CLAMP_ONE = 2   # CN_EXCT_CLAMP_ONE (cn_exct_decode_f32): clamp the peak-tested edge maps to 1
-
-
 def _topk_channel(scores, K=40, apply_sigmoid=False, nms=False):
     """decode.py:92-101: per-channel top-K -> (scores, inds, ys, xs), each (B, C, K).  With
     ``nms=True`` the 3x3 peak test of ``_nms`` is fused in front (how the reference chains
@@ -240,7 +246,7 @@ def _topk_channel(scores, K=40, apply_sigmoid=False, nms=False):
     B, C, H, W = scores.shape
     if K > H * W:
         raise RuntimeError("selected index k out of range")
-    flags = int(bool(apply_sigmoid)) | (0 if nms else _NO_PEAK_TEST)
+    flags = int(bool(apply_sigmoid)) | (0 if nms else native.DECODE_NO_PEAK_TEST)
     s = torch.empty((B, C, K), device=scores.device, dtype=torch.float32)
     i = torch.empty((B, C, K), device=scores.device, dtype=torch.int32)
     nbytes = lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K)
@@ -290,7 +296,7 @@ def _topk(scores, K=40, apply_sigmoid=False, nms=False):
     B, C, H, W = scores.shape
     if K > H * W:
         raise RuntimeError("selected index k out of range")
-    flags = int(bool(apply_sigmoid)) | (0 if nms else _NO_PEAK_TEST)
+    flags = int(bool(apply_sigmoid)) | (0 if nms else native.DECODE_NO_PEAK_TEST)
     ws = _workspace(lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), scores.device)
     s, i, c, rc = _topk_f32(lib, scores, B, C, H, W, K, flags, ws, native.stream_ptr())
     native.check(rc, "cn_topk_f32")
@@ -423,7 +429,7 @@ def exct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr=None, l_regr=Non
                                         native.ptr(r_heat), native.ptr(ct_heat), native.ptr(t_regr),
                                         native.ptr(l_regr), native.ptr(b_regr), native.ptr(r_regr), B, Cc, H,
                                         W, K, scores_thresh, center_thresh, num_dets,
-                                        _EXCT_CLAMP_ONE if aggr_weight > 0 else 0, native.ptr(dets),
+                                        native.EXCT_CLAMP_ONE if aggr_weight > 0 else 0, native.ptr(dets),
                                         native.ptr(ws), ws.numel(), native.stream_ptr())
         native.check(rc, "cn_agnex_ct_decode_f32")
         return dets
@@ -433,7 +439,7 @@ def exct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr=None, l_regr=Non
                                 native.ptr(l_regr), native.ptr(b_regr), native.ptr(r_regr), B, C, H,
                                 W, K, scores_thresh, center_thresh, num_dets,
                                 # aggregated edge maps exceed 1: clamp behind the peak test (decode.py:302-305)
-                                _EXCT_CLAMP_ONE if aggr_weight > 0 else 0, native.ptr(dets),
+                                native.EXCT_CLAMP_ONE if aggr_weight > 0 else 0, native.ptr(dets),
                                 native.ptr(ws), ws.numel(), native.stream_ptr())
     native.check(rc, "cn_exct_decode_f32")
     return dets

@@ -28,8 +28,15 @@ CONV_X_PLAIN, CONV_Y_PLAIN, CONV_R_PLAIN, CONV_STEM_F32S, CONV_STEM_MAXPOOL = 1,
 CONV_STEM_Y_F32S = 32
 MERGE_MAX_ROWS = 2048       # CN_MERGE_MAX_ROWS: S * K rows per image that the merge kernels take
 MERGE_MAX_CLASSES = 1024    # CN_MERGE_MAX_CLASSES
+# flag bits of the decode entries: the #defines of the same names in include/centernet_amd.h
+# (tests/test_decode_route_host.py compares them)
 DECODE_SIGMOID = 1          # CN_DECODE_SIGMOID
+DECODE_NO_PEAK_TEST = 512   # CN_DECODE_NO_PEAK_TEST: rank every cell (plain topk)
+DECODE_PER_BAND = 2048      # CN_DECODE_PER_BAND: force the per-band select (tests / A-B)
+DECODE_STATE_CLEAN = 4096   # CN_DECODE_STATE_CLEAN: the caller owns the workspace, its image state words are zero
+DECODE_TWO_LAUNCHES = 8192  # CN_DECODE_TWO_LAUNCHES: the two-launch image-level form (tests / A-B)
 DECODE_DDD_RAW_DEPTH = 16384    # CN_DECODE_DDD_RAW_DEPTH: cn_ddd_decode_f32 transforms the gathered depths
+EXCT_CLAMP_ONE = 2          # CN_EXCT_CLAMP_ONE (cn_exct_decode_f32): clamp the peak-tested edge maps to 1
 
 # cn_image_desc, one image of a mixed-size batch (cn_warp_normalize_u8_f32_ragged / cn_resize_bilinear_u8_ragged)
 IMAGE_DESC = np.dtype([("offset", np.uint64), ("H", np.int32), ("W", np.int32), ("pitch", np.int32),

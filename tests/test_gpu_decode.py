@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 import torch
 
-from centernet_amd import synth
+from centernet_amd import native, synth
 from oracle import cref
 
 pytestmark = pytest.mark.gpu
@@ -240,7 +240,7 @@ def test_mismatched_inputs_raise_instead_of_reading_out_of_bounds(dev):
 def test_image_level_select_equals_per_band_select(dev, shape):
     """The threshold-pruned image-level top-K (group maxima -> K-th largest as threshold ->
     candidate keys -> exact select) and the per-(class, band) select of round 1 (debug flag
-    2048) give bit-identical detections; both equal the oracle."""
+    DECODE_PER_BAND) give bit-identical detections; both equal the oracle."""
     from centernet_amd.decode import ctdet_decode
     B, C, H, W, K = shape
     heat = synth.heatmap((B, C, H, W), 31 + C)
@@ -248,7 +248,7 @@ def test_image_level_select_equals_per_band_select(dev, shape):
     reg = synth.uniform((B, 2, H, W), 0, 1, 6)
     a, ia = ctdet_decode(_gpu(heat, dev), _gpu(wh, dev), _gpu(reg, dev), K=K, return_inds=True)
     b, ib = ctdet_decode(_gpu(heat, dev), _gpu(wh, dev), _gpu(reg, dev), K=K, return_inds=True,
-                         _debug_flags=2048)
+                         _debug_flags=native.DECODE_PER_BAND)
     assert torch.equal(ia, ib) and torch.equal(a, b)
     ref, ref_inds = cref.ctdet_decode(heat, wh, reg, K=K, return_inds=True)
     assert np.array_equal(ia.cpu().numpy(), ref_inds)
@@ -286,7 +286,7 @@ def test_image_level_select_degenerate_maps(dev):
 def test_one_launch_form_equals_the_other_forms(dev, shape, sig):
     """Planes of <= 128 x 128 cells take the ONE-launch form (plane in registers, lane-maximum
     threshold, image floor, last-arriver select).  It must be bit-identical to the two-launch form
-    (flag 8192) and the per-band select (2048), with the library's own fill of the state words
+    (DECODE_TWO_LAUNCHES) and the per-band select (DECODE_PER_BAND), with the library's own fill of the state words
     (debug-flag calls share a scratch workspace) and without it (the default call owns a zeroed
     workspace, CN_DECODE_STATE_CLEAN); post-sigmoid input also against the oracle."""
     from centernet_amd.decode import ctdet_decode
@@ -299,8 +299,8 @@ def test_one_launch_form_equals_the_other_forms(dev, shape, sig):
     args = (_gpu(heat, dev), _gpu(wh, dev), _gpu(reg, dev))
     a, ia = ctdet_decode(*args, K=K, apply_sigmoid=sig, return_inds=True)                       # one launch, clean state
     f, i_f = ctdet_decode(*args, K=K, apply_sigmoid=sig, return_inds=True, _debug_flags=16384)   # one launch + fill
-    t, it = ctdet_decode(*args, K=K, apply_sigmoid=sig, return_inds=True, _debug_flags=8192)
-    p, ip_ = ctdet_decode(*args, K=K, apply_sigmoid=sig, return_inds=True, _debug_flags=2048)
+    t, it = ctdet_decode(*args, K=K, apply_sigmoid=sig, return_inds=True, _debug_flags=native.DECODE_TWO_LAUNCHES)
+    p, ip_ = ctdet_decode(*args, K=K, apply_sigmoid=sig, return_inds=True, _debug_flags=native.DECODE_PER_BAND)
     for d, i in ((f, i_f), (t, it), (p, ip_)):
         assert torch.equal(ia, i) and torch.equal(a, d)
     if not sig:
@@ -360,3 +360,46 @@ def test_topk_plain_function_takes_the_one_launch_form(dev):
     s, i, c, ys, xs = _topk(_gpu(scores, dev), K=K, nms=False)
     assert np.array_equal(s.cpu().numpy().view(np.uint32), ts.view(np.uint32))
     assert np.array_equal(i.cpu().numpy(), ti) and np.array_equal(c.cpu().numpy(), tc)
+
+
+# the smallest shapes at which each condition of topk_route (csrc/cn_decode.hip) flips
+ROUTE_SHAPES = [(2, 8, 16, 16, 4),      # 16 groups per image >= 4 K: the one-launch form is taken
+                (2, 8, 16, 16, 5),      # 16 < 20: it is not
+                (1, 4, 72, 128, 8),     # two bands per plane: the merge kernel merges
+                (2, 3, 10, 18, 6)]      # W & 3 != 0: per band only
+
+
+@pytest.mark.parametrize("shape", ROUTE_SHAPES)
+def test_topk_forms_agree_through_the_raw_binding(dev, shape):
+    """cn_topk_f32 (MODE_TOPK) with no flag, DECODE_TWO_LAUNCHES and DECODE_PER_BAND: whatever forms the
+    route makes of the three, scores, inds and clses are bit-identical."""
+    from centernet_amd import decode
+    B, C, H, W, K = shape
+    lib = native.lib()
+    heat = _gpu(synth.heatmap((B, C, H, W), 211 + H + K), dev)
+    ws = decode._workspace(lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), dev)
+    outs = []
+    for flags in (0, native.DECODE_TWO_LAUNCHES, native.DECODE_PER_BAND):
+        s, i, c, rc = decode._topk_f32(lib, heat, B, C, H, W, K, flags, ws, native.stream_ptr())
+        assert rc == 0, (flags, rc)
+        torch.cuda.synchronize()
+        outs.append((s.view(torch.int32), i, c))
+    for o in outs[1:]:
+        assert all(torch.equal(x, y) for x, y in zip(outs[0], o))
+    s, i, c = outs[0]
+    assert int(i.min()) >= 0 and int(i.max()) < H * W and int(c.min()) >= 0 and int(c.max()) < C
+
+
+@pytest.mark.parametrize("shape", ROUTE_SHAPES)
+def test_topk_channel_direct_and_merged_vs_torch(dev, shape):
+    """cn_nms_topk_channel_f32 as the plain per-channel top-K against torch.topk: one band per plane (the
+    select's lists are final, no merge) and two bands (merged), both from the route."""
+    from centernet_amd.decode import _topk_channel
+    B, C, H, W, K = shape
+    x = _gpu(synth.normal((B, C, H, W), 1.0, 307 + W), dev)
+    s, i, ys, xs = _topk_channel(x, K=K, nms=False)
+    want = torch.topk(x.view(B, C, -1), K).values
+    assert torch.equal(s.view(torch.int32), want.view(torch.int32))
+    assert torch.equal(torch.gather(x.view(B, C, -1), 2, i).view(torch.int32), want.view(torch.int32))
+    assert all(len(set(r.tolist())) == K for r in i.view(-1, K))     # K different cells per channel
+    assert torch.equal(ys, (i // W).float()) and torch.equal(xs, (i % W).float())

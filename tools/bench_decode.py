@@ -4,6 +4,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from centernet_amd import native
 lib = native.lib()
+SIG, CLEAN = native.DECODE_SIGMOID, native.DECODE_STATE_CLEAN
+TWO, BAND = native.DECODE_TWO_LAUNCHES, native.DECODE_PER_BAND
 dev = torch.device("cuda:0")
 B, C, H, W, K = int(os.environ.get("B", 32)), 80, 128, 128, 100
 g = torch.Generator().manual_seed(0)
@@ -74,7 +76,7 @@ zws = torch.zeros(n, device=dev, dtype=torch.uint8)     # owned + zeroed once: C
 def check_forms():
     """all forms bit-identical on this map before anything is timed"""
     outs = []
-    for flags, w in ((1 | 4096, zws), (1, ws), (1 | 8192, ws), (1 | 2048, ws)):
+    for flags, w in ((SIG | CLEAN, zws), (SIG, ws), (SIG | TWO, ws), (SIG | BAND, ws)):
         rc = lib.cn_ctdet_decode_f32(native.ptr(logits), native.ptr(wh), native.ptr(reg), B, C, H, W, K, 0,
                                      flags, native.ptr(dets), native.ptr(inds), native.ptr(w), n,
                                      native.stream_ptr())
@@ -86,11 +88,11 @@ def check_forms():
 
 
 check_forms()
-for name, flags, w in (("one launch, owned workspace (default product path)", 1 | 4096, zws),
-                       ("one launch + state fill (any caller)", 1, ws),
-                       ("one launch, post-sigmoid map in (reference contract)", 4096 | (1 << 30), zws),
-                       ("two launches (flag 8192; round-4 first form)", 1 | 8192, ws),
-                       ("per-band select of round 1 (flag 2048)", 1 | 2048, ws)):
+for name, flags, w in (("one launch, owned workspace (default product path)", SIG | CLEAN, zws),
+                       ("one launch + state fill (any caller)", SIG, ws),
+                       ("one launch, post-sigmoid map in (reference contract)", CLEAN | (1 << 30), zws),
+                       ("two launches (DECODE_TWO_LAUNCHES; round-4 first form)", SIG | TWO, ws),
+                       ("per-band select of round 1 (DECODE_PER_BAND)", SIG | BAND, ws)):
     ws_cur = w
 
     def run_w(flags, iters=30, w=w):
@@ -123,7 +125,7 @@ if os.environ.get("COLD") == "1":
     big = torch.empty((1 << 30) // 4, device=dev)
     big2 = torch.empty_like(big)
     src = logits.clone()
-    for cname, cflags in (("class-major (default)", 1 | 4096),):
+    for cname, cflags in (("class-major (default)", SIG | CLEAN),):
         times = []
         for it in range(12):
             big2.copy_(big)
