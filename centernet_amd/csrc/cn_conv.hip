@@ -1371,137 +1371,49 @@ extern "C" int cn_conv2d_f32(const cn_conv_desc *d, const float *x, const float 
     return cn_conv2d(d, x, w_packed, scale, shift, residual, y, nullptr, 0, stream);
 }
 
-// Tap-split factor of the deformable kernel: the gather makes every K chunk latency-bound, so a
-// layer needs ~4 workgroups per CU to keep the matrix cores busy; small maps get them by
-// splitting the 9 taps over 3 or 9 workgroups per tile (fp32 partial sums + reduce kernel).
-static int dcn_ksplit(int B, int H, int W, int Cout)
+// ---- the deformable convolution's launches that are bound to igemm_kernel (the entry, the route and the other
+// forms: cn_dcn.hip)
+static IgemmArgs dcn_args(const DcnCall &c)
 {
-    if (cn_knobs.nosplit || cn_knobs.dcn_split == 1) return 1;
-    if (cn_knobs.dcn_split == 3 || cn_knobs.dcn_split == 9) return cn_knobs.dcn_split;
-    const long wgs = (long)cn_cdiv(B * H * W, 64) * cn_cdiv(Cout, Cout > 64 ? 128 : 64);
-    if (wgs >= 1024) return 1;
-    return wgs * 3 >= 600 ? 3 : 9;  // measured (tools/bench_dcn.py): 3 wins from ~2 workgroups/CU
-}
-
-extern "C" size_t cn_dcn_v2_forward_nhwc_workspace_bytes(int B, int Cin, int H, int W, int Cout)
-{
-    if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-    // slabs of the gather form's tap split (3 / 9) or of the window form's K-chunk split (<= 8):
-    // small grids only (either form splits when its plain grid has < 1024 / < 192 workgroups)
-    const int s = dcn_ksplit(B, H, W, Cout);
-    return s > 1 ? (size_t)(s > 8 ? s : 8) * B * H * W * round_up(Cout, 32) * sizeof(float) : 0;
-}
-
-extern "C" int cn_dcn_v2_forward_nhwc_f32(const float *input_nhwc, const float *weight_packed,
-                                          const float *bias, const float *offset_mask_nhwc,
-                                          int om_pitch, const float *scale, const float *shift,
-                                          float *output_nhwc, int B, int Cin, int H, int W,
-                                          int Cout, int mask_sigmoid, int relu, void *workspace,
-                                          size_t workspace_bytes, void *stream)
-{
-    return cn_dcn_v2_forward_nhwc(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale,
-                                  shift, output_nhwc, Cout, B, Cin, H, W, Cout, mask_sigmoid, relu,
-                                  CN_DTYPE_F32, 0, nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weight_packed,
-                                      const float *bias, const float *offset_mask_nhwc,
-                                      int om_pitch, const float *scale, const float *shift,
-                                      void *output_nhwc, int out_pitch, int B, int Cin, int H,
-                                      int W, int Cout, int mask_sigmoid, int relu, int dtype,
-                                      int flags, const cn_f32s_ctl *ctl, void *workspace,
-                                      size_t workspace_bytes, void *stream)
-{
-    if (!input_nhwc || !weight_packed || !offset_mask_nhwc || !output_nhwc) return CN_ERR_NULL;
-    if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || out_pitch < Cout) return CN_ERR_SHAPE;
-    if (om_pitch < 27) return CN_ERR_SHAPE;
-    if ((Cin & 3) != 0) return CN_ERR_UNSUPPORTED;
-    const bool f32s = (dtype == CN_DTYPE_F32S);
-    if (dtype != CN_DTYPE_F32 && !f32s) return CN_ERR_UNSUPPORTED;
-    if (f32s && !(flags & CN_CONV_Y_PLAIN) && (out_pitch & 31)) return CN_ERR_UNSUPPORTED;
-    if (!cn_aligned16(input_nhwc) || !cn_aligned16(weight_packed)) return CN_ERR_ALIGN;
-    if (f32s && !(flags & CN_CONV_Y_PLAIN) && !aligned128(output_nhwc)) return CN_ERR_ALIGN;
-    if ((long)B * H * W * (long)(Cin > out_pitch ? Cin : out_pitch) >= (1L << 30)) return CN_ERR_UNSUPPORTED;  // 32-bit byte offsets
-    // f32s: the LDS-window forms (cn_dcn3.hip team form, cn_dcn2.hip register-sampling form) for every
-    // shape they take and every grid that fills the chip; the gather form below (tap split) serves the rest
-    if (f32s && cn_knobs.dcn_form != 1) {
-        const bool forced = cn_knobs.dcn_form >= 2;
-        const bool ws_ok = workspace && cn_aligned16(workspace) && !cn_knobs.nosplit;
-        int ks = 1;
-        int rc = CN_ERR_UNSUPPORTED;
-        // team form: forced by key 23 = 4 (T mode) / 5 (N mode), or chosen by key 36 for grids that fill the chip
-        const long tiles128 = (long)B * (H / 8) * (W / 16);
-        const bool team_auto = cn_knobs.dcn_form == 0 && tiles128 >= 64 &&
-                               ((cn_knobs.dcn_team == 1 && Cout <= 64) || cn_knobs.dcn_team >= 2);
-        // wide form (cn_dcn4.hip): every sample once per tile for ALL output channels; Cout % 128 == 0
-        const bool wide_auto = cn_knobs.dcn_form == 0 && cn_knobs.dcn_wide && tiles128 >= 64 && (Cout & 127) == 0 && !cn_knobs.dbgskip;
-        DcnWinCall c = {};
-        c.x = input_nhwc; c.w = weight_packed; c.bias = bias; c.om = offset_mask_nhwc; c.om_pitch = om_pitch;
-        c.scale = scale; c.shift = shift; c.y = output_nhwc; c.out_pitch = out_pitch;
-        c.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
-        c.B = B; c.Cin = Cin; c.H = H; c.W = W; c.Cout = Cout; c.mask_sigmoid = mask_sigmoid; c.relu = relu;
-        c.x_mul = (ctl && ctl->x_mul != 0.f) ? ctl->x_mul : 1.f;
-        c.range = ctl ? ctl->range : nullptr;
-        c.dbg = cn_knobs.dbgskip;
-        c.partial = ws_ok ? (float *)workspace : nullptr;
-        c.partial_bytes = ws_ok ? workspace_bytes : 0;
-        hipStream_t st = (hipStream_t)stream;
-        if (cn_knobs.dcn_form == 6 || cn_knobs.dcn_form == 7 || wide_auto)
-            rc = cn_dcn_wide_f32s(c, cn_knobs.dcn_form == 7 ? 4 : 0, &ks, st);
-        if (rc == CN_ERR_UNSUPPORTED && (cn_knobs.dcn_form == 4 || cn_knobs.dcn_form == 5 || team_auto))
-            rc = cn_dcn_team_f32s(c, cn_knobs.dcn_form == 5 ? 2 : ((team_auto && cn_knobs.dcn_team == 3) ? 1 : 0), &ks, st);
-        if (rc == CN_ERR_UNSUPPORTED && cn_knobs.dcn_form < 4)
-            rc = cn_dcn_window_f32s(c, forced ? 1 : 192, &ks, st);
-        if (rc == CN_OK && ks > 1) {
-            // second stage of the K split: fixed-order sum of the slabs + the usual epilogue
-            IgemmArgs r = {};
-            r.bias = bias; r.scale = scale; r.shift = shift; r.residual = nullptr; r.y = output_nhwc;
-            set_ctl(r, ctl);
-            r.B = B; r.H = H; r.W = W; r.Ho = H; r.Wo = W; r.Cout = Cout; r.out_pitch = out_pitch;
-            r.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
-            r.OH = H; r.OW = W; r.oy_mul = 1; r.oy_add = 0; r.ox_mul = 1; r.ox_add = 0;
-            r.relu = relu; r.M = B * H * W; r.cout_pad = round_up(Cout, 32);
-            r.ksplit = ks; r.partial = (float *)workspace;
-            return launch_splitk_reduce(CN_DTYPE_F32S, r, 4096, (hipStream_t)stream);
-        }
-        if (rc != CN_ERR_UNSUPPORTED) return rc;
-    }
     IgemmArgs a = {};
-    a.x = input_nhwc; a.w = weight_packed; a.bias = bias; a.scale = scale; a.shift = shift;
-    a.residual = nullptr; a.y = output_nhwc; a.om = offset_mask_nhwc; a.om_pitch = om_pitch;
-    a.mask_sigmoid = mask_sigmoid;
-    set_ctl(a, ctl);
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Ho = H; a.Wo = W; a.Cout = Cout;
+    a.x = c.x; a.w = c.w; a.bias = c.bias; a.scale = c.scale; a.shift = c.shift;
+    a.residual = nullptr; a.y = c.y; a.om = c.om; a.om_pitch = c.om_pitch;
+    a.mask_sigmoid = c.mask_sigmoid;
+    a.x_mul = c.x_mul; a.res_mul = 1.f; a.range = c.range;
+    a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Ho = c.H; a.Wo = c.W; a.Cout = c.Cout;
     a.KH = 3; a.KW = 3; a.stride = 1; a.pad_h = 1; a.pad_w = 1; a.dil = 1;
-    a.in_pitch = Cin; a.out_pitch = out_pitch;
+    a.in_pitch = c.Cin; a.out_pitch = c.out_pitch;
     a.in_plain = 1;                                   // the gather reads plain fp32 in every mode
-    a.out_plain = (flags & CN_CONV_Y_PLAIN) ? 1 : 0;
-    a.OH = H; a.OW = W; a.oy_mul = 1; a.oy_add = 0; a.ox_mul = 1; a.ox_add = 0;
-    a.relu = relu;
-    a.M = B * H * W;
-    a.cin_pad = round_up(Cin, 32);
-    a.cout_pad = round_up(Cout, 32);
+    a.out_plain = c.out_plain;
+    a.OH = c.H; a.OW = c.W; a.oy_mul = 1; a.oy_add = 0; a.ox_mul = 1; a.ox_add = 0;
+    a.relu = c.relu;
+    a.M = c.B * c.H * c.W;
+    a.cin_pad = round_up(c.Cin, 32);
+    a.cout_pad = round_up(c.Cout, 32);
     a.nchunk = a.cin_pad / 32;
     a.KT = 9 * a.nchunk;
-    a.vec_out = ((Cout & 3) == 0 && (out_pitch & 3) == 0 && cn_aligned16(output_nhwc)) ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream;
-    // tiles as pixel blocks (8 x 8, or 8 x 16 for the 128-pixel tiles of Cout <= 32) when the map
-    // divides into them
-    a.tile2d = (cn_knobs.dcn_tile2d && (W & 7) == 0 && (H % (Cout > 32 ? 8 : 16)) == 0) ? 1 : 0;
-    // tap split (needs the caller's workspace; without one the layer runs unsplit)
     a.ksplit = 1;
-    if (Cout > 32) {
-        const int want = dcn_ksplit(B, H, W, Cout);
-        const size_t need = (size_t)want * a.M * a.cout_pad * sizeof(float);
-        if (want > 1 && workspace && workspace_bytes >= need && cn_aligned16(workspace)) {
-            a.ksplit = want;
-            a.partial = (float *)workspace;
-        }
-    }
-    const int rc = (Cin & 31) ? igemm_dispatch<A_DCN_PAD, false>(dtype, cout_class(Cout), false, a, st)
-                              : igemm_dispatch<A_DCN, false>(dtype, cout_class(Cout), false, a, st);
-    if (rc != CN_OK || a.ksplit == 1) return rc;
-    return launch_splitk_reduce(dtype, a, 4096, st);
+    return a;
+}
+
+int cn_dcn_gather(const DcnCall &c, const DcnPlan &p, hipStream_t st)
+{
+    IgemmArgs a = dcn_args(c);
+    a.vec_out = p.vec_out;
+    a.tile2d = p.tile2d;
+    a.ksplit = p.ksplit;
+    a.partial = p.ksplit > 1 ? (float *)c.workspace : nullptr;
+    return p.form == DCN_GATHER_PAD ? igemm_dispatch<A_DCN_PAD, false>(c.dtype, cout_class(c.Cout), false, a, st)
+                                    : igemm_dispatch<A_DCN, false>(c.dtype, cout_class(c.Cout), false, a, st);
+}
+
+// second stage of a split of any form: fixed-order sum of the `ksplit` slabs in the workspace + the usual epilogue
+int cn_dcn_reduce(const DcnCall &c, int ksplit, hipStream_t st)
+{
+    IgemmArgs a = dcn_args(c);
+    a.ksplit = ksplit;
+    a.partial = (float *)c.workspace;
+    return launch_splitk_reduce(c.dtype, a, 4096, st);
 }
 
 // ---- ConvTranspose2d(kernel 4, stride 2, padding 1, no output padding) -----------------

@@ -19,11 +19,6 @@
 // Epilogue as everywhere: y = relu?((acc + bias) * scale + shift), plain fp32 or f32s, range words.
 #include "cn_dcn_window.h"
 
-// K is split until a launch has this many workgroups (round-4 sweep of 256 / 512 / 1024 and of 64-wide N tiles
-// for Cout > 64, cn_set_tuning keys 34 / 35: within +-5 % on every layer shape, profiles/r04_dcn_split_sweep.txt;
-// the keys were removed in round 5)
-constexpr int DCN2_SPLIT_WGS = 256;
-
 namespace {
 
 // This form keeps an argument struct of its own: with mask_sigmoid where it has always been, every field
@@ -416,27 +411,22 @@ __global__ __launch_bounds__(R_NT, 2) void dcn_reg_kernel(const Dcn2Args a)
 
 }  // namespace
 
-// Shapes this kernel takes (the caller falls back to the global-gather form otherwise): maps of
-// whole 8 x 16 pixel blocks, whole 32-channel chunks, Cout a multiple of 4 and >= 33, and at least
-// `min_wgs` workgroups (the tap-split gather form serves the small grids).
-int cn_dcn_window_f32s(const DcnWinCall &c, int min_wgs, int *ksplit_out, hipStream_t st)
+// Shapes this kernel takes: maps of whole 8 x 16 pixel blocks, whole 32-channel chunks, Cout a multiple of 4
+// and >= 33.
+bool cn_dcn_window_takes(const DcnCall &c)
 {
-    if (ksplit_out) *ksplit_out = 1;
-    if (!dcnw_shape_ok(c) || (c.Cout & 3) || c.Cout <= 32) return CN_ERR_UNSUPPORTED;
-    if (c.H > 32767 || c.W > 32767) return CN_ERR_UNSUPPORTED;                       // 16-bit corner coordinates in a record
-    if ((c.om_pitch & 1) || (((uintptr_t)c.om) & 7u)) return CN_ERR_UNSUPPORTED;     // (offset pairs are 8-byte loads)
-    const int bn = c.Cout > 64 ? 128 : 64;
-    const long wgs = (long)c.B * (c.H / DCNW_TY) * (c.W / DCNW_TX) * cn_cdiv(c.Cout, bn);
-    int ksplit = 1;
-    if (wgs < DCN2_SPLIT_WGS || wgs < min_wgs) {
-        ksplit = dcnw_pick_ksplit(wgs, DCN2_SPLIT_WGS, c);
-        if (wgs * ksplit < 256 && wgs < min_wgs) return CN_ERR_UNSUPPORTED;   // (the tap-split gather form serves these)
-    }
-    const Dcn2Args a = dcnw_fill_args<Dcn2Args>(c, ksplit);
-    if (ksplit_out) *ksplit_out = ksplit;
-    if (bn == 64)
+    if (!dcnw_shape_ok(c) || (c.Cout & 3) || c.Cout <= 32) return false;
+    if (c.H > 32767 || c.W > 32767) return false;                       // 16-bit corner coordinates in a record
+    return !(c.om_pitch & 1) && !(((uintptr_t)c.om) & 7u);              // (offset pairs are 8-byte loads)
+}
+
+int cn_dcn_window_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st)
+{
+    if (p.form != DCN_WINDOW) return CN_ERR_UNSUPPORTED;
+    const Dcn2Args a = dcnw_fill_args<Dcn2Args>(c, p.ksplit);
+    if (p.bn == 64)
         return dcnw_launch<dcn_reg_kernel<64, true, true>, dcn_reg_kernel<64, false, true>,
-                           dcn_reg_kernel<64, false, false>, R_NT, (int)R_LDS>(a, (unsigned)cn_cdiv(c.Cout, bn), st);
+                           dcn_reg_kernel<64, false, false>, R_NT, (int)R_LDS>(a, p.grid_y, st);
     return dcnw_launch<dcn_reg_kernel<128, true, true>, dcn_reg_kernel<128, false, true>,
-                       dcn_reg_kernel<128, false, false>, R_NT, (int)R_LDS>(a, (unsigned)cn_cdiv(c.Cout, bn), st);
+                       dcn_reg_kernel<128, false, false>, R_NT, (int)R_LDS>(a, p.grid_y, st);
 }

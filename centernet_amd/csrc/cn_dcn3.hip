@@ -34,7 +34,6 @@
 // value * mask (:174; here the mask multiplies the four corner weights -- a reassociation of
 // 1-2 ulp in fp32, far below the 2^-22 of the f32s split), bias then accumulate (dcn_v2_cuda.c:61-97).
 #include "cn_dcn_window.h"
-#include "cn_tuning.h"
 
 // probe build, key 9 bit 256: cycle stamps of wave 0 of every 64th workgroup (tile life: start, records, first window, taps, epilogue, end)
 __device__ unsigned long long cn_d3_trace[64 * 8];
@@ -423,26 +422,22 @@ extern "C" int cn_dcn_team_trace(unsigned long long *out)
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(cn_d3_trace), sizeof(unsigned long long) * 64 * 8) == hipSuccess ? CN_OK : CN_ERR_LAUNCH;
 }
 
-// Shapes this kernel takes (the caller falls back to the other forms otherwise): maps of whole
-// 8 x 16 pixel tiles, whole 32-channel chunks, Cout a multiple of 4 and >= 33.  nmode: 1 (2 = even on small grids) = the teams
-// split a 128-channel block (needs Cout % 128 == 0), 0 = they split the steps of a 64-channel block.
-int cn_dcn_team_f32s(const DcnWinCall &c, int nmode, int *ksplit_out, hipStream_t st)
+// Shapes this kernel takes: maps of whole 8 x 16 pixel tiles, whole 32-channel chunks, Cout a multiple of 4 and
+// >= 33.  DCN_TEAM_N: the teams split a 128-channel block (Cout % 128 == 0), DCN_TEAM_T: they split the steps of a
+// 64-channel block.
+bool cn_dcn_team_takes(const DcnCall &c)
 {
-    if (ksplit_out) *ksplit_out = 1;
-    if (!dcnw_shape_ok(c) || !dcnw_far_ok(c) || (c.Cout & 3) || c.Cout <= 32) return CN_ERR_UNSUPPORTED;
-    const long tiles = (long)c.B * (c.H / DCNW_TY) * (c.W / DCNW_TX);
-    if (nmode && (c.Cout & 127)) nmode = 0;
-    // N mode halves the workgroup count: only where two workgroups per CU remain (measured: 256 -> 128 @ 32^2 at
-    // B = 32 has 256 tiles: 0.093 ms in T mode, 0.109 in N mode; 128 -> 128 @ 64^2 and 256 -> 256 @ 32^2: 0.179 /
-    // 0.172 against 0.195 / 0.209)
-    if (nmode == 1 && tiles * (c.Cout / 128) < cn_knobs.dcn_team_wgs) nmode = 0;
-    const unsigned nby = (unsigned)cn_cdiv(c.Cout, nmode ? 128 : 64);
-    DcnWinArgs a = dcnw_fill_args(c, dcnw_pick_ksplit(tiles * nby, cn_knobs.dcn_team_wgs, c));
-    a.stagger = cn_knobs.dcn_team_stagger;
-    if (ksplit_out) *ksplit_out = a.ksplit;
-    if (nmode)
+    return dcnw_shape_ok(c) && dcnw_far_ok(c) && !(c.Cout & 3) && c.Cout > 32;
+}
+
+int cn_dcn_team_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st)
+{
+    if (p.form != DCN_TEAM_T && p.form != DCN_TEAM_N) return CN_ERR_UNSUPPORTED;
+    DcnWinArgs a = dcnw_fill_args(c, p.ksplit);
+    a.stagger = p.stagger;
+    if (p.form == DCN_TEAM_N)
         return dcnw_launch<dcn_team_kernel<true, true, true>, dcn_team_kernel<true, true, false>,
-                           dcn_team_kernel<true, false, false>, T_NT, T_LDS>(a, nby, st);
+                           dcn_team_kernel<true, false, false>, T_NT, T_LDS>(a, p.grid_y, st);
     return dcnw_launch<dcn_team_kernel<false, true, true>, dcn_team_kernel<false, true, false>,
-                       dcn_team_kernel<false, false, false>, T_NT, T_LDS>(a, nby, st);
+                       dcn_team_kernel<false, false, false>, T_NT, T_LDS>(a, p.grid_y, st);
 }

@@ -34,7 +34,6 @@
 // value * mask (:174; the mask multiplies the four corner weights), bias then accumulate
 // (dcn_v2_cuda.c:61-97).
 #include "cn_dcn_window.h"
-#include "cn_tuning.h"
 
 // probe build, key 9 bit 512: cycle stamps of waves 0 and 4 of workgroup 0 over its first 64 steps
 __device__ unsigned long long cn_d4_trace[2 * 64 * 8];
@@ -496,27 +495,24 @@ extern "C" int cn_dcn_wide_trace(unsigned long long *out)
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(cn_d4_trace), sizeof(unsigned long long) * 2 * 64 * 8) == hipSuccess ? CN_OK : CN_ERR_LAUNCH;
 }
 
-// Shapes this kernel takes (the caller falls back to the team form otherwise): maps of whole 8 x 16 pixel
-// tiles, whole 32-channel chunks, Cout a multiple of 128.  nb: 0 = by shape (8 blocks where Cout % 256 == 0,
-// else 4 -- the grid is not looked at: one too small for the chip gets the K split below), 4 / 8 = forced.
-int cn_dcn_wide_f32s(const DcnWinCall &c, int nb, int *ksplit_out, hipStream_t st)
+// Shapes this kernel takes: maps of whole 8 x 16 pixel tiles, whole 32-channel chunks, Cout a multiple of 128
+// (DCN_WIDE8: of 256).
+bool cn_dcn_wide_takes(const DcnCall &c)
 {
-    if (ksplit_out) *ksplit_out = 1;
-    if (!dcnw_shape_ok(c) || !dcnw_far_ok(c) || (c.Cout & 127)) return CN_ERR_UNSUPPORTED;
-    const long tiles = (long)c.B * (c.H / DCNW_TY) * (c.W / DCNW_TX);
-    if (nb != 4 && nb != 8) nb = (c.Cout % 256 == 0) ? 8 : 4;
-    if (nb == 8 && (c.Cout & 255)) nb = 4;
-    const unsigned nby = (unsigned)(c.Cout / (32 * nb));
-    DcnWinArgs a = dcnw_fill_args(c, dcnw_pick_ksplit(tiles * nby, cn_knobs.dcn_wide_wgs, c));
-    // L2 prefetch: pays where the weight stream is long and cold (four-block form on deep K: +5 % cold); costs 1-4 % elsewhere
-    a.prefetch = (cn_knobs.dcn_wide_prefetch && nb == 4 && c.Cin >= 256) ? 1 : 0;
-    if (ksplit_out) *ksplit_out = a.ksplit;
+    return dcnw_shape_ok(c) && dcnw_far_ok(c) && !(c.Cout & 127);
+}
+
+int cn_dcn_wide_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st)
+{
+    if (p.form != DCN_WIDE4 && p.form != DCN_WIDE8) return CN_ERR_UNSUPPORTED;
+    DcnWinArgs a = dcnw_fill_args(c, p.ksplit);
+    a.prefetch = p.prefetch;
     // LDS: shared regions + epilogue constants + ring; the four-block form adds its second window
     constexpr int LDS8 = W_RING + 2 * 8 * 4096, LDS4 = W_RING + 2 * 4 * 4096 + DCNW_WBYTES;
     static_assert(LDS8 <= 163840 && LDS4 <= 163840, "one workgroup per CU");
-    if (nb == 8)
+    if (p.form == DCN_WIDE8)
         return dcnw_launch<dcn_wide_kernel<8, true, true>, dcn_wide_kernel<8, true, false>,
-                           dcn_wide_kernel<8, false, false>, W_NT, LDS8>(a, nby, st);
+                           dcn_wide_kernel<8, false, false>, W_NT, LDS8>(a, p.grid_y, st);
     return dcnw_launch<dcn_wide_kernel<4, true, true>, dcn_wide_kernel<4, true, false>,
-                       dcn_wide_kernel<4, false, false>, W_NT, LDS4>(a, nby, st);
+                       dcn_wide_kernel<4, false, false>, W_NT, LDS4>(a, p.grid_y, st);
 }

@@ -4,7 +4,8 @@
 //     XCD-aware tile order and the tile / window origin (dcnw_tile);
 //   * for the team and the wide form, whose windows are filled by LDS-DMA: the swizzled window layout
 //     (dcnw_enc), the record regions behind the window, the staging pitch, the zero line, the argument struct;
-//   * the host side of an entry point: shape checks, K-split chooser, argument fill, launch ladder.
+//   * the host side of a launcher: shape checks, argument fill, launch ladder (which form runs, its blocks and
+//     its K split are dcn_route's, cn_dcn.hip).
 // A form keeps its step loop, the LDS carve behind the shared regions, its workgroup size and its own checks.
 // The prologue (DMA offsets, offset / mask loads, record formation) and the epilogue tail are still written
 // out in each kernel: lifted into helpers here they changed the instruction stream of every shipped build.
@@ -108,10 +109,10 @@ __device__ __forceinline__ DcnwTile dcnw_tile(int tiles_x, int tiles_y)
     return t;
 }
 
-// ---- host side of an entry point -------------------------------------------------------------------------------
+// ---- host side of a launcher -------------------------------------------------------------------------------------
 // what every window form needs: maps of whole 8 x 16 pixel tiles, whole 32-channel chunks, 16-byte quads in and
 // out, 32-bit byte offsets into x
-inline bool dcnw_shape_ok(const DcnWinCall &c)
+inline bool dcnw_shape_ok(const DcnCall &c)
 {
     if ((c.H & 7) || (c.W & 15) || (c.Cin & 31)) return false;
     if ((c.out_pitch & 3) || !cn_aligned16(c.y) || !cn_aligned16(c.x)) return false;
@@ -120,29 +121,13 @@ inline bool dcnw_shape_ok(const DcnWinCall &c)
 
 // the far path of the records above: 15-bit corner coordinates, 24-bit integer multiplies (pixel index, bytes
 // per pixel)
-inline bool dcnw_far_ok(const DcnWinCall &c)
+inline bool dcnw_far_ok(const DcnCall &c)
 {
     return c.H <= 16383 && c.W <= 16383 && (size_t)c.B * c.H * c.W < ((size_t)1 << 24) && (size_t)c.Cin * 4 < ((size_t)1 << 24);
 }
 
-// Too few tiles for the chip but a deep K (512 -> 256 @ 16^2): split the 32-channel chunks over 2 / 4 / 8
-// workgroups per tile -- raw fp32 partial sums in the caller's workspace, summed in a fixed order by
-// splitk_reduce_kernel (deterministic).  The smallest split that reaches `target` workgroups, else the deepest
-// one that divides the chunks, leaves two per workgroup and fits the workspace.
-inline int dcnw_pick_ksplit(long wgs, int target, const DcnWinCall &c)
-{
-    const int nchunk = c.Cin / 32;
-    const int cout_pad = (c.Cout + 31) / 32 * 32;
-    int ksplit = 1;
-    for (int s2 = 2; s2 <= 8 && c.partial && wgs * ksplit < target; s2 *= 2)
-        if (nchunk % s2 == 0 && nchunk / s2 >= 2 &&
-            (size_t)s2 * c.B * c.H * c.W * cout_pad * sizeof(float) <= c.partial_bytes)
-            ksplit = s2;
-    return ksplit;
-}
-
 template <class Args = DcnWinArgs>
-Args dcnw_fill_args(const DcnWinCall &c, int ksplit)
+Args dcnw_fill_args(const DcnCall &c, int ksplit)
 {
     Args a = {};
     a.x = c.x; a.w = c.w; a.bias = c.bias; a.scale = c.scale; a.shift = c.shift; a.om = c.om; a.y = c.y;
@@ -155,7 +140,7 @@ Args dcnw_fill_args(const DcnWinCall &c, int ksplit)
     a.tiles_y = c.H / DCNW_TY;
     a.x_mul = c.x_mul; a.range = c.range; a.dbg = c.dbg;
     a.ksplit = ksplit;
-    a.partial = ksplit > 1 ? c.partial : nullptr;
+    a.partial = ksplit > 1 ? (float *)c.workspace : nullptr;
     return a;
 }
 

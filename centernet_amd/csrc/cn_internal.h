@@ -1,5 +1,5 @@
 // cn_internal.h -- prototypes of the functions one .hip file defines and another calls, and the two call
-// descriptions they pass (ConvCall: the convolution family, DcnWinCall: the f32s deformable kernels, TopkCall: the
+// descriptions they pass (ConvCall: the convolution family, DcnCall: the deformable convolution, TopkCall: the
 // top-K of the decoders).  Included
 // by both sides, so the defining file is compiled against the declaration its callers see.
 #pragma once
@@ -34,27 +34,51 @@ enum { CN_STEM_NONE = 0, CN_STEM_WINDOW, CN_STEM_PERSIST, CN_STEM_PERSIST_F32S, 
 int cn_stem_form(const ConvCall &c, int persistent);
 int cn_stem_conv_f32(const ConvCall &c, int persistent, hipStream_t st);
 
-// ---- f32s deformable kernels: cn_dcn2.hip (window), cn_dcn3.hip (team), cn_dcn4.hip (wide); what they share is
-// in cn_dcn_window.h.  One call description for all three (cn_conv.hip fills it once)
-struct DcnWinCall {
+// ---- the deformable convolution (NHWC entry): one call description.  cn_dcn.hip fills it once per
+// cn_dcn_v2_forward_nhwc call (after the argument checks); dcn_route() there says which form runs and how it is
+// laid out, and every `takes` predicate and launcher below reads the call and the plan.  The forms: the global
+// gather of the implicit GEMM (cn_conv.hip, every dtype) and the three f32s LDS-window forms (cn_dcn2.hip
+// register-sampling window, cn_dcn3.hip team, cn_dcn4.hip wide; what those share is in cn_dcn_window.h)
+struct DcnCall {
     const float *x;            // (B, H, W, Cin) plain fp32
-    const void *w;             // f32s-packed weights, row form + fragment copy
+    const void *w;             // packed weights of `dtype` (f32s: row form + fragment copy)
     const float *bias, *om;    // om: (B, H, W, om_pitch): 18 offsets + 9 masks per pixel
     int om_pitch;
     const float *scale, *shift;
     void *y;
     int out_pitch, out_plain;
     int B, Cin, H, W, Cout, mask_sigmoid, relu;
-    float x_mul;               // f32s input exponent (a power of two)
-    uint32_t *range;           // range words of the launch, or null
+    int dtype;                 // CN_DTYPE_F32 / CN_DTYPE_F32S
+    float x_mul;               // cn_f32s_ctl resolved: f32s input exponent (a power of two, 1 without a ctl)
+    uint32_t *range;           // ... and the range words of the launch, or null
     int dbg;                   // cn_set_tuning key 9
-    float *partial;            // K-split workspace, or null: no split
-    size_t partial_bytes;
+    void *workspace;           // as the caller gave them; whether they allow a split is the route's to judge
+    size_t workspace_bytes;
 };
-// each returns CN_ERR_UNSUPPORTED for a shape it does not take; *ksplit_out > 1: `partial` holds that many slabs
-int cn_dcn_window_f32s(const DcnWinCall &c, int min_wgs, int *ksplit_out, hipStream_t st);
-int cn_dcn_team_f32s(const DcnWinCall &c, int nmode, int *ksplit_out, hipStream_t st);
-int cn_dcn_wide_f32s(const DcnWinCall &c, int nb, int *ksplit_out, hipStream_t st);
+// the values of cn_dcn_route_info::form (include/centernet_amd.h)
+enum { DCN_GATHER = CN_DCN_GATHER, DCN_GATHER_PAD = CN_DCN_GATHER_PAD, DCN_WINDOW = CN_DCN_WINDOW,
+       DCN_TEAM_T = CN_DCN_TEAM_T, DCN_TEAM_N = CN_DCN_TEAM_N, DCN_WIDE4 = CN_DCN_WIDE4, DCN_WIDE8 = CN_DCN_WIDE8 };
+struct DcnPlan {
+    int form;                  // DCN_*
+    int bn;                    // output channels per block
+    unsigned grid_x, grid_y;   // tiles, blocks of output channels (cdiv(Cout, bn))
+    int ksplit;                // grid.z; > 1: the form writes that many [B*H*W][cout_pad] slabs of raw sums into the
+                               // workspace and cn_dcn_reduce follows
+    int prefetch, stagger;     // wide: L2 prefetch of the weights; team: start delay of the second occupant
+    int tile2d, vec_out;       // gather: tiles are pixel blocks; y allows 16-byte stores
+};
+DcnPlan dcn_route(const DcnCall &c);   // cn_dcn.hip: pure host function of the call and cn_knobs; launches nothing
+// `takes`: the shapes and pointers a window form serves (dcn_route asks in its order of preference).  A launcher
+// runs the plan it is given and nothing else: one that is not its own is a bug, not a fallback
+bool cn_dcn_window_takes(const DcnCall &c);
+bool cn_dcn_team_takes(const DcnCall &c);
+bool cn_dcn_wide_takes(const DcnCall &c);
+int cn_dcn_window_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st);
+int cn_dcn_team_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st);
+int cn_dcn_wide_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st);
+// cn_conv.hip, bound to igemm_kernel: the gather forms, and the second stage of every form's split
+int cn_dcn_gather(const DcnCall &c, const DcnPlan &p, hipStream_t st);
+int cn_dcn_reduce(const DcnCall &c, int ksplit, hipStream_t st);
 
 // ---- cn_decode.hip: the top-K of a heat-map, one call description.  Every entry that ranks a heat-map fills a
 // TopkCall; topk_route() says which form the call takes and where its scratch lives, topk_run() checks, asks

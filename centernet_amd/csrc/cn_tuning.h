@@ -39,10 +39,9 @@ constexpr CnTuningKey CN_TUNING_KEYS[] = {
     {16, &CnTuning::split_min_chunks, 8, 1, 64},  // K chunks per split-K slice, at least
     {17, &CnTuning::split_max, 16, 1, 64},        // split-K slices, at most
     {22, &CnTuning::dcn_tile2d, 1, 0, 1},         // deformable kernel: 1 = 8-wide pixel blocks as tiles, 0 = row segments
-    // f32s deformable kernel: 0 = by shape and grid (wide form per key 41, team form per key 36, else the
-    // register-sampling window form, else the gather form), 1 = global-gather form always, 2 = register-sampling
-    // form (cn_dcn2.hip), 4 / 5 = team form (cn_dcn3.hip) in T / N mode, 6 / 7 = wide form (cn_dcn4.hip; 7: four
-    // blocks per workgroup), each for every shape it takes
+    // f32s deformable kernel: 0 = by shape and grid, in dcn_route's order of preference (cn_dcn.hip), 1 = global-gather
+    // form always, 2 = register-sampling form (cn_dcn2.hip), 4 / 5 = team form (cn_dcn3.hip) in T / N mode, 6 / 7 = wide
+    // form (cn_dcn4.hip; 7: four blocks per workgroup), each for every shape it takes (the gather form for the others)
     {23, &CnTuning::dcn_form, 0, 0, 2, 4, {4, 5, 6, 7}},
     {27, &CnTuning::stem16s, 1, 0, 1},            // f32s form of the stride-1 16-channel stem (DLA base_layer); 0 = fp32 kernel
     // LDS-halo kernel (cn_conv3x3.hip)

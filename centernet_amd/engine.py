@@ -931,19 +931,26 @@ class PlanBuilder:
 
         self._grow_ws(lib.cn_dcn_v2_forward_nhwc_workspace_bytes(x.B, ci, x.H, x.W, co))
 
-        def run():
+        def call(fn, *more):
             wsp = ctypes.c_void_p(self.ws.data_ptr()) if self.ws is not None else None
-            rc = lib.cn_dcn_v2_forward_nhwc(x.ptr(), wpp, bp, om.ptr(), om.pitch, sp, hp,
-                                            out.ptr(), out.pitch, x.B, ci, x.H, x.W, co, msig,
-                                            int(relu), cd, flags, cref, wsp, self.ws_bytes,
-                                            native.stream_ptr())
+            return fn(x.ptr(), wpp, bp, om.ptr(), om.pitch, sp, hp, out.ptr(), out.pitch, x.B, ci, x.H, x.W, co,
+                      msig, int(relu), cd, flags, cref, wsp, self.ws_bytes, native.stream_ptr(), *more)
+
+        def run():
+            rc = call(lib.cn_dcn_v2_forward_nhwc)
             if rc:
                 native.check(rc, "cn_dcn_v2_forward_nhwc")
+
+        def route():
+            """the kernel form, grid and K split the launch gets (cn_dcn_v2_route: host only)"""
+            info = native.DcnRouteInfo()
+            native.check(call(lib.cn_dcn_v2_route, ctypes.byref(info)), "cn_dcn_v2_route")
+            return info
         self.ops.append(run)
         fl = 2 * x.B * x.H * x.W * co * ci * 9
         # SURVEY.md 8(d): activations 4*(Cin + 27 + Cout)*HW per image + weights once per launch
         by = 4 * (x.B * x.H * x.W * (ci + 27 + co) + co * ci * 9 + co)
-        self.meta.append(dict(kind="dcn", flops=fl, bytes=by, samples=x.B * x.H * x.W * 9 * ci))
+        self.meta.append(dict(kind="dcn", flops=fl, bytes=by, samples=x.B * x.H * x.W * 9 * ci, route=route))
         self.trace.append(("dcn", out))
         self.flops += fl
         return out

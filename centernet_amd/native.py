@@ -37,6 +37,10 @@ DECODE_STATE_CLEAN = 4096   # CN_DECODE_STATE_CLEAN: the caller owns the workspa
 DECODE_TWO_LAUNCHES = 8192  # CN_DECODE_TWO_LAUNCHES: the two-launch image-level form (tests / A-B)
 DECODE_DDD_RAW_DEPTH = 16384    # CN_DECODE_DDD_RAW_DEPTH: cn_ddd_decode_f32 transforms the gathered depths
 EXCT_CLAMP_ONE = 2          # CN_EXCT_CLAMP_ONE (cn_exct_decode_f32): clamp the peak-tested edge maps to 1
+# forms and flags of cn_dcn_v2_route: the #defines CN_<name> of the header (tests/test_dcn_route_host.py compares them)
+DCN_GATHER, DCN_GATHER_PAD, DCN_WINDOW, DCN_TEAM_T, DCN_TEAM_N, DCN_WIDE4, DCN_WIDE8 = range(7)
+DCN_FLAG_PREFETCH, DCN_FLAG_STAGGER, DCN_FLAG_TILE2D, DCN_FLAG_VEC_OUT = 1, 2, 4, 8
+DCN_FORM_NAMES = ("gather", "gather_pad", "window", "team_t", "team_n", "wide4", "wide8")
 
 # cn_image_desc, one image of a mixed-size batch (cn_warp_normalize_u8_f32_ragged / cn_resize_bilinear_u8_ragged)
 IMAGE_DESC = np.dtype([("offset", np.uint64), ("H", np.int32), ("W", np.int32), ("pitch", np.int32),
@@ -54,6 +58,11 @@ class F32sCtl(ctypes.Structure):
     """Mirror of ``cn_f32s_ctl``: range control of the f32s kernels (multipliers that carry the
     per-tensor exponents + the device words that receive the largest |value| a launch split)."""
     _fields_ = [("x_mul", ctypes.c_float), ("res_mul", ctypes.c_float), ("range", ctypes.c_void_p)]
+
+
+class DcnRouteInfo(ctypes.Structure):
+    """Mirror of ``cn_dcn_route_info``: the kernel form, grid and K split of a cn_dcn_v2_forward_nhwc call."""
+    _fields_ = [(n, ctypes.c_int) for n in ("form", "grid_x", "grid_y", "ksplit", "flags")]
 
 
 class ConvDesc(ctypes.Structure):
@@ -151,6 +160,8 @@ def _declare(lib):
     lib.cn_maxpool_nhwc_scaled.argtypes = [vp, vp, i, i, i, i, i, i, i, i, f, vp]
     lib.cn_dcn_v2_forward_nhwc.restype = i
     lib.cn_dcn_v2_forward_nhwc.argtypes = [vp, vp, vp, vp, i, vp, vp, vp] + [i] * 10 + [ctl, vp, sz, vp]
+    lib.cn_dcn_v2_route.restype = i
+    lib.cn_dcn_v2_route.argtypes = lib.cn_dcn_v2_forward_nhwc.argtypes + [ctypes.POINTER(DcnRouteInfo)]
     lib.cn_pack_deconv4x4s2_weight.restype = i
     lib.cn_pack_deconv4x4s2_weight.argtypes = [vp, vp, i, i, i, vp]
     lib.cn_conv_transpose4x4s2.restype = i

@@ -115,14 +115,13 @@ const char *cn_arch(void);
  * key 22: gather-form deformable kernel: 1 = a tile is an 8-wide BLOCK of pixels (8 x 8 / 8 x 16) when the
  *         map divides into them (default: the nine taps of a block sample a compact neighbourhood that
  *         stays in L1 / L2), 0 = BM consecutive pixels of a row.
- * key 23: form of the f32s deformable kernel.  0 = by shape and grid (default): the wide form (cn_dcn4.hip,
- *         see key 41) or the team form (cn_dcn3.hip, see key 36) on grids that fill the chip, else the
- *         register-sampling LDS-window form (cn_dcn2.hip: every lane samples its own MFMA operand from a
- *         window of the input in LDS) when the grid has >= 192 workgroups, else the global-gather form.
- *         1 = the global-gather form always.  For every shape the form takes (tests, A/B): 2 = the
- *         register-sampling form, 4 / 5 = the team form in T / N mode, 6 / 7 = the wide form (a workgroup
- *         owns ALL output channels of its tile; 7 = four blocks per workgroup).  3 is refused (the
- *         wave-specialised window form it selected was removed).
+ * key 23: form of the f32s deformable kernel.  0 = by shape and grid (default), in the order of preference of
+ *         dcn_route (csrc/cn_dcn.hip; cn_dcn_v2_route below says what a call gets).  1 = the global-gather
+ *         form always.  For every shape the form takes, the gather form for the others (tests, A/B): 2 = the
+ *         register-sampling form (cn_dcn2.hip: every lane samples its own MFMA operand from a window of the
+ *         input in LDS), 4 / 5 = the team form in T / N mode, 6 / 7 = the wide form (a workgroup owns ALL
+ *         output channels of its tile; 7 = four blocks per workgroup).  3 is refused (the wave-specialised
+ *         window form it selected was removed).
  * key 27: 7x7 / stride 1 stem of <= 16 output channels with CN_CONV_STEM_F32S: 1 = f32s kernel
  *         (default), 0 = the fp32 16x16x4 kernel (then cn_stem_f32s_supported answers 0 for it).
  * LDS-halo kernel (cn_conv3x3.hip):
@@ -266,6 +265,33 @@ int cn_dcn_v2_forward_nhwc_f32(const float *input_nhwc, const float *weight_pack
                                float *output_nhwc, int B, int Cin, int H, int W,
                                int Cout, int mask_sigmoid, int relu, void *workspace,
                                size_t workspace_bytes, void *stream);
+/* Which kernel form and K split a cn_dcn_v2_forward_nhwc call with these arguments gets under the current
+ * tuning keys.  Host only: launches nothing, tests the pointers for null and alignment and never follows them
+ * (stream is ignored).  Returns what the call would return from its argument checks; *info is written only
+ * with CN_OK. */
+#define CN_DCN_GATHER 0      /* global gather on the implicit GEMM */
+#define CN_DCN_GATHER_PAD 1  /* ... for Cin % 32 != 0 */
+#define CN_DCN_WINDOW 2      /* f32s LDS-window forms: register sampling (cn_dcn2.hip) */
+#define CN_DCN_TEAM_T 3      /* team form (cn_dcn3.hip), the teams split the K steps of a 64-channel block */
+#define CN_DCN_TEAM_N 4      /* ... the teams split a 128-channel block */
+#define CN_DCN_WIDE4 5       /* wide form (cn_dcn4.hip), four 32-channel blocks per workgroup */
+#define CN_DCN_WIDE8 6       /* ... eight */
+#define CN_DCN_FLAG_PREFETCH 1  /* wide: L2 prefetch of the weights */
+#define CN_DCN_FLAG_STAGGER 2   /* team: the second occupant of a CU starts late */
+#define CN_DCN_FLAG_TILE2D 4    /* gather: tiles are pixel blocks */
+#define CN_DCN_FLAG_VEC_OUT 8   /* gather: 16-byte stores to y */
+typedef struct cn_dcn_route_info {
+    int form;            /* CN_DCN_* */
+    int grid_x, grid_y;  /* pixel tiles, blocks of output channels */
+    int ksplit;          /* 1, or the slabs of partial sums in the workspace that a reduce launch sums */
+    int flags;           /* CN_DCN_FLAG_* */
+} cn_dcn_route_info;
+int cn_dcn_v2_route(const float *input_nhwc, const void *weight_packed, const float *bias,
+                    const float *offset_mask_nhwc, int om_pitch, const float *scale,
+                    const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
+                    int H, int W, int Cout, int mask_sigmoid, int relu, int dtype, int flags,
+                    const cn_f32s_ctl *ctl, void *workspace, size_t workspace_bytes,
+                    void *stream, cn_dcn_route_info *info);
 
 /* Plain fp32 NHWC <-> f32s NHWC (CN_DTYPE_F32S: fp16 high / low pairs in 128-byte groups of 32
  * channels).  Pitches in channels; f32s pitches are multiples of 32; channels of the last

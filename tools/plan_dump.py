@@ -2,7 +2,7 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from centernet_amd import synth
+from centernet_amd import native, synth
 from centernet_amd.model import create_model
 arch = sys.argv[1] if len(sys.argv) > 1 else "dla_34"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 2
@@ -15,4 +15,8 @@ with torch.no_grad():
     m(synth.images(B, 512, 512, seed=0).to(dev))
 plan = m.plan_for(B, 512, 512, dev)
 for i, ((kind, act), meta) in enumerate(zip(plan.b.trace, plan.b.meta)):
-    print("%3d %-9s -> (%d,%d,%d) pitch %d %s%s" % (i, kind, act.H, act.W, act.C, act.pitch, act.fmt, " nchw" if act.nchw else ""))
+    how = ""
+    if kind == "dcn":   # the form and K split of the deformable launch, from the library's route query
+        r = meta["route"]()
+        how = "  %s grid %d x %d x %d" % (native.DCN_FORM_NAMES[r.form], r.grid_x, r.grid_y, r.ksplit)
+    print("%3d %-9s -> (%d,%d,%d) pitch %d %s%s%s" % (i, kind, act.H, act.W, act.C, act.pitch, act.fmt, " nchw" if act.nchw else "", how))
