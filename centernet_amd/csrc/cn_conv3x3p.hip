@@ -29,7 +29,8 @@
 //
 // Geometry: tile = 8 rows x 16 columns of output pixels (halo 10 x 18 = 180 rows of 128 bytes per
 // 32-channel chunk, double-buffered), BN = 64 output channels, four consumer waves as 2 (pixels)
-// x 2 (channels): a wave owns 64 pixels x 32 channels = two 32x32 accumulators.  The MFMA
+// x 2 (channels): a wave owns 64 pixels x 32 channels = two 32x32 accumulators (the generic forms by default:
+// eight 16x16 accumulators of v_mfma_f32_16x16x32_f16, template S16 -- the chip holds a higher clock on it).  The MFMA
 // operands are swapped (D[channel][pixel]) so that a lane ends up with four CONSECUTIVE output
 // channels of its pixel: the epilogue splits them in place and transposes through a wave-private
 // LDS strip into full 128-byte output rows (coalesced 16-byte stores, no cross-wave barrier).
@@ -89,7 +90,8 @@ struct P3Args {
     uint32_t *range;
     int stagger;
     int knobs;                // A/B switches (cn_set_tuning key 30): 1 = no s_setprio 1 around the consumers' MFMA block
-                              // (unpipelined forms), 2 = the pipelined fragment schedule (template PIPE)
+                              // (unpipelined forms), 2 = the pipelined fragment schedule (template PIPE),
+                              // 4 = the 32x32x16 MFMA shape in the forms whose default is 16x16x32 (template S16)
                               // (with the loaders at priority 3 the raised priority measured 3-5 % faster)
     // instrumented instantiation only (DBG = true; cn_conv3x3p_probe): ablation switches and cycle counters
     int dbg;                  // 1: no MFMAs, 2: no fragment reads (and no MFMAs), 4: no weight DMA, 8: no halo DMA,
@@ -163,12 +165,28 @@ __device__ constexpr int p3_s2_tap(int i)     // weight matrix (ky * 3 + kx) of 
 #define P3_HALO2 1
 #endif
 
+// Swizzle key of a halo row (a pixel's 128 bytes = eight 16-byte slots: four of the high parts, four of the low
+// parts), by halo column.  32x32x16 fragments (a lane group of a ds_read_b128 = pixels of two tile rows, two
+// slots): (column >> 1) & 7.  16x16x32 fragments (lane = pixel of ONE tile row + 16 * slot, four slots): that key
+// leaves the reads at kx = 1 and 2 two-way conflicted; the table below (columns 0 .. 17 in pairs) is conflict-free
+// for kx = 0, 1, 2 -- tests/test_c3p_fragment_map_host.py mirrors both and counts the bank units of every group.
+__host__ __device__ constexpr int p3_halo_key(bool s16, int hx)
+{
+    return s16 ? (int)((0x062654210ull >> (4 * (hx >> 1))) & 7) : ((hx >> 1) & 7);
+}
+
 constexpr int p3_halo_loaders(int ntap, bool s2) { return (P3_HALO2 && (s2 || ntap == 4)) ? 2 : 1; }
 constexpr int p3_threads(int ntap, bool s2) { return 320 + 64 * p3_halo_loaders(ntap, s2); }
 
-template <int RES, bool OUT_PLAIN, bool DBG = false, bool HEADS = false, int NTAP = 9, bool S2 = false, bool PIPE = false>
+// S16: the generic consumers on v_mfma_f32_16x16x32_f16 (eight 16x16 accumulators per wave) instead of
+// v_mfma_f32_32x32x16_f16 (two 32x32): same wave tile, reads and matrix cycles -- see CONSUMERS below.  Appended
+// last: bench.py reads the other arguments by position.
+template <int RES, bool OUT_PLAIN, bool DBG = false, bool HEADS = false, int NTAP = 9, bool S2 = false, bool PIPE = false,
+          bool S16 = false>
 __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const P3Args a, const P3Heads hd)
 {
+    static_assert(!S16 || (!HEADS && !DBG), "16x16x32: the generic consumers only (the heads' hidden accumulators are the B "
+                                            "operand of their 1x1 GEMM in the 32x32 layout)");
     static_assert(!PIPE || !DBG, "pipelined fragment schedule: not in the instrumented instantiation");
     static_assert(!S2 || (NTAP == 9 && RES == 0 && !DBG && !HEADS), "stride 2: nine taps, no residual");
     // residual rows requested this many steps before an item's last step ends (0 .. 3 measured with
@@ -270,7 +288,7 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
             }
         } else {
             // ---- halos: piece k covers halo rows 8k .. 8k+7; lane = (row in piece, 16-byte slot s);
-            // slot s of row r receives source column s ^ key(r), key = (halo column >> 1) & 7
+            // slot s of row r receives source column s ^ key(r), key = p3_halo_key of the halo column
             // (two loader waves: wave 5 + h takes pieces 2 j + h -- one copy of this code per h, so that every
             // piece index stays a compile-time constant)
             auto halo_loader = [&](auto HW) {
@@ -283,7 +301,7 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
                 const int k = j * NHL + hw;
                 const int r = 8 * k + prow;
                 const int hy = r / P_HW, hx = r - hy * P_HW;
-                const int col = ps ^ ((hx >> 1) & 7);
+                const int col = ps ^ p3_halo_key(S16, hx);
                 poff[j] = (S2 ? 2 : 1) * ((hy - 1) * a.Wi + (hx - 1)) * a.in_pitchB + col * 16;
                 pyx[j] = (r < P_HR) ? (hy | (hx << 8)) : -1;
             }
@@ -812,11 +830,28 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
     // 32 wn + l31 of the tile.  They are recomputed per item from an opaque copy of the lane id
     // so that nothing of them is live (or spilled and reloaded behind the output stores) across
     // an epilogue.
+    //
+    // S16 (v_mfma_f32_16x16x32_f16): the wave tile is 2 channel blocks x 4 pixel blocks of 16 x 16, acc[4 cb + pb] =
+    // D[channel 16 cb + 4 (lane >> 4) + 0..3][pixel 16 pb + (lane & 15)] -- again four consecutive channels per
+    // lane.  Pixel block pb = tile row 4 wm + pb (18 halo rows apart: an immediate), weight block cb = rows
+    // 32 wn + 16 cb + (lane & 15) (2 KiB apart).  One ds_read_b128 is a whole K = 32 operand half: lane >> 4
+    // selects the 16-byte slot (channels 8 (lane >> 4) .. + 7) of the row's high or low 64 bytes, so a step is 4
+    // weight + 8 pixel fragments and 24 MFMAs of 16 cycles: reads, matrix cycles and accumulator registers as in
+    // the 32x32 form.  The halo rows carry the swizzle key of this mapping (p3_halo_key).
     int arow, aswz, b0;
     auto lane_consts = [&]() {
         int ln = lane;
         asm volatile("" : "+v"(ln));
         const int l31 = ln & 31, lh = ln >> 5, px = ln & 15;
+        if constexpr (S16) {
+            const int sl = ln >> 4;
+            arow = (4 * wm * P_HW + px) * 128;
+            aswz = 0;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) aswz |= (((sl ^ p3_halo_key(true, px + kx)) & 7) << 4) << (8 * kx);
+            b0 = (32 * wn + px) * 128 + (((sl ^ ((px >> 1) & 7)) & 7) << 4);
+            return;
+        }
         arow = ((4 * wm + (l31 >> 4)) * P_HW + px) * 128;
         aswz = 0;
 #pragma unroll
@@ -825,12 +860,14 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
     };
     lane_consts();
 
-    cn_f32x16 acc[2];
+    typedef typename std::conditional<S16, cn_f32x4, cn_f32x16>::type acc_t;
+    constexpr int NACC = S16 ? 8 : 2, ACC_N = S16 ? 4 : 16;
+    acc_t acc[NACC];
     auto zero_acc = [&]() {
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < NACC; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+            for (int r = 0; r < ACC_N; ++r) acc[i][r] = 0.f;
     };
     zero_acc();
     float rng_out = 0.f;
@@ -854,6 +891,35 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
         int ax = arow + ((aswz >> (8 * kx)) & 0xff) + (DECONV ? tapoff : 0), bx = b0;
         asm volatile("" : "+v"(ax), "+v"(bx));
         const int tapimm = DECONV ? 0 : tapoff;   // (a compile-time immediate in the 9-tap form)
+        if constexpr (S16) {
+            // 16x16x32: whole-K fragments, wh / wl of the two channel blocks, xh / xl of the four pixel blocks
+            p3_f16x8 wh[2], wl[2], xh[4], xl[4];
+            constexpr int prow = P_HW * 128, wblk = 16 * 128;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) wh[cb] = lds128(wb + cb * wblk + bx);
+#pragma unroll
+            for (int pb = 0; pb < 4; ++pb) xl[pb] = lds128(hb + tapimm + pb * prow + (ax ^ 64));
+#pragma unroll
+            for (int pb = 0; pb < 4; ++pb) xh[pb] = lds128(hb + tapimm + pb * prow + ax);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) wl[cb] = lds128(wb + cb * wblk + (bx ^ 64));
+            __builtin_amdgcn_sched_barrier(0);
+            if (!(a.knobs & 1)) __builtin_amdgcn_s_setprio(1);
+            // smallest terms first per tile: w_hi * x_lo, w_lo * x_hi, then w_hi * x_hi (the order of the
+            // pipelined schedule below: pixel blocks 0, 1 of both channel blocks, then 2, 3)
+#pragma unroll
+            for (int term = 0; term < 3; ++term)
+#pragma unroll
+                for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                        for (int pb = 2 * ph; pb < 2 * ph + 2; ++pb)
+                            acc[4 * cb + pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                                term == 1 ? wl[cb] : wh[cb], term == 0 ? xl[pb] : xh[pb], acc[4 * cb + pb], 0, 0, 0);
+            if (!(a.knobs & 1)) __builtin_amdgcn_s_setprio(0);
+            return;
+        } else {
         constexpr int blk1 = 2 * P_HW * 128;   // block 1 of the wave: two tile rows below block 0
         if (DBG && (a.dbg & 64)) {
             // ablation: half of the fragment reads (the low parts re-use the high parts' registers)
@@ -900,6 +966,7 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
                 acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[kh], xf[kh][i], acc[i], 0, 0, 0);
         }
         if (!(a.knobs & 1)) __builtin_amdgcn_s_setprio(0);
+        }
     };
 
     // pixel of the row-layout lane: block i, pass k -> row 8k + (lane >> 3) of the wave's block
@@ -946,9 +1013,8 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
         const int stg = sb + wave * P_STG;
         const int ln = opaque_lane();
         const int rrow = ln >> 3, rcol = ln & 7, l31 = ln & 31, lh = ln >> 5;
-        // scale / shift of the lane's channels 8g + 4 lh .. + 3 of the wave's group: from the wave's
+        // scale / shift of the lane's channels (piece_c0 below) of the wave's group: from the wave's
         // LDS stash (requested at the item's first step, stored two steps later)
-        const int rowb = stg + l31 * P_STG_ROW + 8 * lh;    // + 16 g (+ 64): f32s pieces; plain: 2x
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if constexpr (RES != 0) {
@@ -961,25 +1027,36 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
             }
             // every residual piece of the wave is read before any output piece is written: with
             // different formats on the two sides a lane's output bytes are other lanes' residual bytes
+            // piece g of the lane: four consecutive channels c0 .. c0 + 3 of the wave's group, of strip row srow.
+            // 32x32: row l31 of block i, c0 = 8 g + 4 lh.  16x16x32: the strip takes pixel blocks 2 i, 2 i + 1
+            // (rows 0-15, 16-31: the same 32 pixels in the same rows), piece g = (channel block g >> 1, pixel
+            // block 2 i + (g & 1)): row 16 (g & 1) + (lane & 15), c0 = 16 (g >> 1) + 4 (lane >> 4)
+            auto piece_c0 = [&](int g) { return S16 ? 16 * (g >> 1) + 4 * (ln >> 4) : 8 * g + 4 * lh; };
+            auto piece_row = [&](int g) { return stg + (S16 ? 16 * (g & 1) + (ln & 15) : l31) * P_STG_ROW; };
             cn_f32x4 rr[4];
             if constexpr (RES != 0) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     if constexpr (RES == 2)
-                        rr[g] = *reinterpret_cast<const cn_f32x4 *>(smem + rowb + 8 * lh + 32 * g);
+                        rr[g] = *reinterpret_cast<const cn_f32x4 *>(smem + piece_row(g) + 4 * piece_c0(g));
                     else
-                        rr[g] = cn_join4(*reinterpret_cast<const cn_f16x4v *>(smem + rowb + 16 * g),
-                                         *reinterpret_cast<const cn_f16x4v *>(smem + rowb + 64 + 16 * g));
+                        rr[g] = cn_join4(*reinterpret_cast<const cn_f16x4v *>(smem + piece_row(g) + 2 * piece_c0(g)),
+                                         *reinterpret_cast<const cn_f16x4v *>(smem + piece_row(g) + 64 + 2 * piece_c0(g)));
                 }
                 asm volatile("" ::: "memory");
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const cn_f32x4 sc = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + wave * 256 + (8 * g + 4 * lh) * 4);
-                const cn_f32x4 sh = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + wave * 256 + 128 + (8 * g + 4 * lh) * 4);
+                const cn_f32x4 sc = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + wave * 256 + piece_c0(g) * 4);
+                const cn_f32x4 sh = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + wave * 256 + 128 + piece_c0(g) * 4);
                 cn_f32x4 v;
+                if constexpr (S16) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * g + e] * sc[e] + sh[e];
+                    for (int e = 0; e < 4; ++e) v[e] = acc[4 * (g >> 1) + 2 * i + (g & 1)][e] * sc[e] + sh[e];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = acc[i][4 * g + e] * sc[e] + sh[e];
+                }
                 if constexpr (RES != 0) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaf(rr[g][e], a.res_mul, v[e]);
@@ -987,13 +1064,13 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], relu_floor);
                 if constexpr (OUT_PLAIN) {
-                    *reinterpret_cast<cn_f32x4 *>(smem + rowb + 8 * lh + 32 * g) = v;
+                    *reinterpret_cast<cn_f32x4 *>(smem + piece_row(g) + 4 * piece_c0(g)) = v;
                 } else {
                     cn_rng_upd4(rng_out, v);
                     cn_f16x4v h4, l4;
                     cn_split4(v, h4, l4);
-                    *reinterpret_cast<cn_f16x4v *>(smem + rowb + 16 * g) = h4;
-                    *reinterpret_cast<cn_f16x4v *>(smem + rowb + 64 + 16 * g) = l4;
+                    *reinterpret_cast<cn_f16x4v *>(smem + piece_row(g) + 2 * piece_c0(g)) = h4;
+                    *reinterpret_cast<cn_f16x4v *>(smem + piece_row(g) + 64 + 2 * piece_c0(g)) = l4;
                 }
             }
             // rows back in row layout: 8 lanes = one 128-byte output row
@@ -1052,29 +1129,127 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
         };
         // (same order of the products as the unpipelined step: smallest terms first)
         auto mfma_front = [&](const Frag &F) {
+            if constexpr (!S16) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.wh, F.xl[i], acc[i], 0, 0, 0);
-            if constexpr (P3_SPLIT >= 4) {
+            }
+            if constexpr (!S16 && P3_SPLIT >= 4) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.wl, F.xh[i], acc[i], 0, 0, 0);
             }
-            if constexpr (P3_SPLIT >= 6) {
+            if constexpr (!S16 && P3_SPLIT >= 6) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.wh, F.xh[i], acc[i], 0, 0, 0);
             }
         };
         auto mfma_back = [&](const Frag &F) {
-            if constexpr (P3_SPLIT < 4) {
+            if constexpr (!S16 && P3_SPLIT < 4) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.wl, F.xh[i], acc[i], 0, 0, 0);
             }
-            if constexpr (P3_SPLIT < 6) {
+            if constexpr (!S16 && P3_SPLIT < 6) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.wh, F.xh[i], acc[i], 0, 0, 0);
             }
         };
         auto keep = [&](const Frag &F) {
             asm volatile("" :: "v"(F.wh), "v"(F.wl), "v"(F.xh[0]), "v"(F.xh[1]), "v"(F.xl[0]), "v"(F.xl[1]));
+        };
+        // ---- the same for 16x16x32 (S16).  A K = 32 instruction has no K halves to split a step by: every weight
+        // fragment meets every pixel fragment, so no two blocks of a step have disjoint operands.  What the step
+        // does have is operands that die early.  Per tile the terms run in the unpipelined order -- A = w_hi * x_lo,
+        // B = w_lo * x_hi, C = w_hi * x_hi, eight MFMAs (128 matrix cycles) each, pixel blocks 0, 1 in front of
+        // 2, 3 -- so x_lo is dead behind A, w_lo behind B, and C needs w_hi and x_hi only.  C of step t is
+        // therefore what the wave carries across barrier t + 1 (the 32x32 form carries the back part of a block):
+        //     barrier t + 1
+        //     reads 1 of step t + 1: w_hi (into the OTHER of two w_hi sets: C (t) still holds this one) and x_lo
+        //                            (last used by A (t): B (t) = 128 matrix cycles back)
+        //     C (t)                  (128 matrix cycles over the latency of reads 1)
+        //     A (t + 1), blocks 0, 1
+        //     reads 2: w_lo (last used by B (t): 192 cycles back), x_hi of blocks 0, 1 (last used by the first half
+        //                            of C (t): 128 back)
+        //     A (t + 1), blocks 2, 3
+        //     reads 3: x_hi of blocks 2, 3 (last used by the second half of C (t): 128 back)
+        //     B (t + 1), blocks 0, 1 (64 cycles behind reads 2), then 2, 3 (64 behind reads 3)
+        //     fence, barrier t + 2: every read of step t + 1 is complete
+        // A refill is never closer than 128 matrix cycles (the four 32-cycle MFMAs of the 32x32 form) to its
+        // registers' last use, a read has 64 to 128 cycles of the wave's own MFMAs queued behind it, and no read
+        // crosses a barrier.  The second w_hi set is 8 registers; with an odd number of steps per stage the set a
+        // stage ends on is copied to the one the next begins on (2 fragments per nine steps).
+        p3_f16x8 wh16[2][2], wl16[2], xh16[4], xl16[4];
+        auto tap_addr = [&](auto T, int &ax, int &bx) {
+            constexpr int t = decltype(T)::value;
+            const int ky = S2 ? p3_s2_oy(t) : (DECONV ? t / 2 + par_y : t / 3);
+            const int kx = S2 ? p3_s2_ox(t) : (DECONV ? t % 2 + par_x : t % 3);
+            const int tapoff = (ky * P_HW + kx) * 128;
+            ax = arow + ((aswz >> (8 * kx)) & 0xff) + (DECONV ? tapoff : 0);
+            bx = b0;
+            asm volatile("" : "+v"(ax), "+v"(bx));
+            return DECONV ? 0 : tapoff;
+        };
+        constexpr int prow16 = P_HW * 128, wblk16 = 16 * 128;
+        auto reads1 = [&](auto T, auto P, int hb, int wb) {
+            constexpr int p = decltype(P)::value;
+            int ax, bx;
+            const int imm = tap_addr(T, ax, bx);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) wh16[p][cb] = lds128(wb + cb * wblk16 + bx);
+#pragma unroll
+            for (int pb = 0; pb < 4; ++pb) xl16[pb] = lds128(hb + imm + pb * prow16 + (ax ^ 64));
+        };
+        auto mm16 = [&](auto TERM, auto P, auto PH) {
+            constexpr int term = decltype(TERM)::value, p = decltype(P)::value, ph = decltype(PH)::value;
+            if constexpr (S16) {
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                    for (int pb = 2 * ph; pb < 2 * ph + 2; ++pb)
+                        acc[4 * cb + pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                            term == 1 ? wl16[cb] : wh16[p][cb], term == 0 ? xl16[pb] : xh16[pb], acc[4 * cb + pb], 0, 0, 0);
+            }
+        };
+        auto pstep16 = [&](auto T, auto &HB, auto &WB, bool more, int hb1) {
+            constexpr int t = decltype(T)::value, p = t & 1;
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_setprio(1);
+            mm16(P3_IC(0), P3_IC(p), P3_IC(0));
+            __builtin_amdgcn_sched_barrier(0);
+            int ax, bx;
+            const int imm = tap_addr(T, ax, bx);
+            const int hb = HB(t), wb = WB(t);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) wl16[cb] = lds128(wb + cb * wblk16 + (bx ^ 64));
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) xh16[pb] = lds128(hb + imm + pb * prow16 + ax);
+            __builtin_amdgcn_sched_barrier(0);
+            mm16(P3_IC(0), P3_IC(p), P3_IC(1));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int pb = 2; pb < 4; ++pb) xh16[pb] = lds128(hb + imm + pb * prow16 + ax);
+            __builtin_amdgcn_sched_barrier(0);
+            // (x_lo stays allocated over reads 2 and 3: their registers are not its own)
+            asm volatile("" :: "v"(xl16[0]), "v"(xl16[1]), "v"(xl16[2]), "v"(xl16[3]));
+            mm16(P3_IC(1), P3_IC(p), P3_IC(0));
+            mm16(P3_IC(1), P3_IC(p), P3_IC(1));
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_setprio(0);
+            p3_lds_fence();                  // every fragment of step t has been waited for by B already
+            p3_barrier();                    // barrier t + 1 (t = NTAP - 1: barrier 0 of the next stage)
+            if constexpr (t + 1 < NTAP) {
+                reads1(P3_IC(t + 1), P3_IC(1 - p), HB(t + 1), WB(t + 1));
+            } else {
+                if (more) reads1(P3_IC(0), P3_IC(1 - p), S2 ? 0 : hb1, WB(NTAP));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // (w_lo stays allocated over reads 1)
+            asm volatile("" :: "v"(wl16[0]), "v"(wl16[1]));
+            mm16(P3_IC(2), P3_IC(p), P3_IC(0));
+            mm16(P3_IC(2), P3_IC(p), P3_IC(1));
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (t + 1 == NTAP && p == 0) {      // the next stage begins on set 0
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) wh16[0][cb] = wh16[1][cb];
+            }
         };
         bar();                                   // barrier 0 of stage 0
         int s = 0;                               // stage counter of the workgroup (halo buffer parity)
@@ -1096,7 +1271,8 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
                 ssv = (ln >> 5) ? hv : sv;
             }
             __builtin_amdgcn_sched_barrier(0);
-            load_half(P3_IC(0), P3_IC(0), S2 ? 0 : (s & 1) * P_HBYTES, P_WOFF + (g & 3) * P_WSLOT, F0);
+            if constexpr (S16) reads1(P3_IC(0), P3_IC(0), S2 ? 0 : (s & 1) * P_HBYTES, P_WOFF + (g & 3) * P_WSLOT);
+            else load_half(P3_IC(0), P3_IC(0), S2 ? 0 : (s & 1) * P_HBYTES, P_WOFF + (g & 3) * P_WSLOT, F0);
             __builtin_amdgcn_sched_barrier(0);
             for (c = 0; c < a.nchunk; ++c, ++s) {
                 const int hb0 = (s & 1) * P_HBYTES, hb1 = ((s + 1) & 1) * P_HBYTES;
@@ -1105,6 +1281,10 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
                 const bool more = (c + 1 < a.nchunk);     // another stage of this item follows
                 auto pstep = [&](auto T) {
                     constexpr int t = decltype(T)::value;
+                    if constexpr (S16) {
+                        pstep16(T, HB, WB, more, hb1);
+                        return;
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                     __builtin_amdgcn_s_setprio(1);
                     mfma_front(F0);
@@ -1297,6 +1477,13 @@ static P3Args p3_args(const ConvCall &c, int H, int W, int npar)
     return a;
 }
 
+// MFMA shape of the generic consumers, per form: true = the form runs v_mfma_f32_16x16x32_f16 (template S16) unless
+// cn_set_tuning key 30 has the value 4 set (bit 2, the A/B switch: the 32x32x16 shape).  A form is true only where the 16x16x32
+// form measured faster by wall on the flagship's layers (profiles/c3p_mfma_shape_ab.txt); for a form that is false
+// no 16x16x32 instantiation is built.
+constexpr bool P3_S16_S1 = true, P3_S16_S2 = true, P3_S16_DECONV = true;
+static bool p3_s16(const P3Args &a, bool form_default) { return form_default && !(a.knobs & 4); }
+
 // The persistent grid: a multiple of 8 (one share per XCD), never more than one workgroup per item, and per XCD
 // at most cn_set_tuning key 47 workgroups (default 64: two per CU)
 static dim3 p3_grid(const P3Args &a)
@@ -1310,16 +1497,21 @@ int cn_deconv4x4s2_persist(const ConvCall &c, hipStream_t st)
 {
     const P3Args a = p3_args(c, c.H, c.W, 4);
     const dim3 grid = p3_grid(a), block(p3_threads(4, false));
+#define P3_LAUNCH4_(OP, PIPE, S16)                                                                               \
+    do {                                                                                                         \
+        CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, OP, false, false, 4, false, PIPE, S16>), P_LDS);                  \
+        hipLaunchKernelGGL((conv3x3p_kernel<0, OP, false, false, 4, false, PIPE, S16>), grid, block, P_LDS, st, a, P3Heads{}); \
+    } while (0)
 #define P3_LAUNCH4(OP, PIPE)                                                                                     \
     do {                                                                                                         \
-        CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, OP, false, false, 4, false, PIPE>), P_LDS);                       \
-        hipLaunchKernelGGL((conv3x3p_kernel<0, OP, false, false, 4, false, PIPE>), grid, block, P_LDS, st, a, P3Heads{}); \
+        if (p3_s16(a, P3_S16_DECONV)) P3_LAUNCH4_(OP, PIPE, P3_S16_DECONV); else P3_LAUNCH4_(OP, PIPE, false);   \
     } while (0)
     if (a.knobs & 2) {
         if (c.out_plain) P3_LAUNCH4(true, true); else P3_LAUNCH4(false, true);
     } else {
         if (c.out_plain) P3_LAUNCH4(true, false); else P3_LAUNCH4(false, false);
     }
+#undef P3_LAUNCH4_
 #undef P3_LAUNCH4
     CN_CHECK_LAUNCH();
     return CN_OK;
@@ -1343,10 +1535,14 @@ int cn_conv3x3s2_persist(const ConvCall &c, hipStream_t st)
 {
     const P3Args a = p3_args(c, c.Ho, c.Wo, 1);   // Ho = (H - 1) / 2 + 1: the caller's route checks the geometry
     const dim3 grid = p3_grid(a), block(p3_threads(9, true));
+#define P3_LAUNCHS2_(OP, PIPE, S16)                                                                              \
+    do {                                                                                                         \
+        CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, OP, false, false, 9, true, PIPE, S16>), P_LDS);                   \
+        hipLaunchKernelGGL((conv3x3p_kernel<0, OP, false, false, 9, true, PIPE, S16>), grid, block, P_LDS, st, a, P3Heads{}); \
+    } while (0)
 #define P3_LAUNCHS2(OP, PIPE)                                                                                    \
     do {                                                                                                         \
-        CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, OP, false, false, 9, true, PIPE>), P_LDS);                        \
-        hipLaunchKernelGGL((conv3x3p_kernel<0, OP, false, false, 9, true, PIPE>), grid, block, P_LDS, st, a, P3Heads{}); \
+        if (p3_s16(a, P3_S16_S2)) P3_LAUNCHS2_(OP, PIPE, P3_S16_S2); else P3_LAUNCHS2_(OP, PIPE, false);         \
     } while (0)
     if (a.knobs & 2) {
         if (c.out_plain) P3_LAUNCHS2(true, true); else P3_LAUNCHS2(false, true);
@@ -1354,6 +1550,7 @@ int cn_conv3x3s2_persist(const ConvCall &c, hipStream_t st)
         if (c.out_plain) P3_LAUNCHS2(true, false); else P3_LAUNCHS2(false, false);
     }
 #undef P3_LAUNCHS2
+#undef P3_LAUNCHS2_
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -1397,10 +1594,14 @@ int cn_conv3x3s1_persist(const ConvCall &c, hipStream_t st)
     a.res_plain = c.res_plain;
     a.res_mul = (c.ctl && c.ctl->res_mul != 0.f) ? c.ctl->res_mul : 1.f;
     const dim3 grid = p3_grid(a), block(384);
+#define P3_LAUNCH__(R, OP, PIPE, S16)                                                                            \
+    do {                                                                                                         \
+        CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<R, OP, false, false, 9, false, PIPE, S16>), P_LDS);                  \
+        hipLaunchKernelGGL((conv3x3p_kernel<R, OP, false, false, 9, false, PIPE, S16>), grid, block, P_LDS, st, a, P3Heads{}); \
+    } while (0)
 #define P3_LAUNCH_(R, OP, PIPE)                                                                                  \
     do {                                                                                                         \
-        CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<R, OP, false, false, 9, false, PIPE>), P_LDS);                       \
-        hipLaunchKernelGGL((conv3x3p_kernel<R, OP, false, false, 9, false, PIPE>), grid, block, P_LDS, st, a, P3Heads{}); \
+        if (p3_s16(a, P3_S16_S1)) P3_LAUNCH__(R, OP, PIPE, P3_S16_S1); else P3_LAUNCH__(R, OP, PIPE, false);     \
     } while (0)
 #define P3_LAUNCH(R, OP)                                                    \
     do {                                                                    \
@@ -1427,6 +1628,7 @@ int cn_conv3x3s1_persist(const ConvCall &c, hipStream_t st)
     }
 #undef P3_LAUNCH
 #undef P3_LAUNCH_
+#undef P3_LAUNCH__
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

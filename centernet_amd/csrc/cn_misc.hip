@@ -1,6 +1,7 @@
 // cn_misc.hip -- memory-bound helpers around the hot path: layout conversion at
 // the API edge, max pooling, and the NCHW (reference-layout) entry point of DCNv2.
 #include "cn_internal.h"
+#include <type_traits>
 
 namespace {
 
@@ -1010,6 +1011,107 @@ __global__ __launch_bounds__(64) void calib_clock_kernel(unsigned long long *out
     out[1] = t1 - t0;
 }
 
+// ---- MFMA shape probe (tools/bench_mfma_shape.py): the f32s step of the persistent 3x3 kernel
+// (cn_conv3x3p.hip) with nothing around it, in the 32x32x16 and in the 16x16x32 shape, on operands the
+// caller supplies.  A wave owns 64 pixels x 32 channels of fp32 accumulators (32 registers): two 32x32
+// tiles or 2 (channels) x 4 (pixels) 16x16 tiles.  One step = K 32 of every tile as three products
+// (high * low, low * high, high * high: smallest terms first) = 12 MFMAs of 32 cycles or 24 of 16, on
+// 12 operand fragments of 16 bytes per lane: 4 of the weights (A) and 8 of the pixels (B).
+//   32x32x16: fragment 2 * part + kh of the weights, 4 + 4 * tile + 2 * part + kh of the pixels
+//   16x16x32: fragment 2 * cb + part of the weights, 4 + 2 * pb + part of the pixels
+// (part 0 = high, 1 = low; kh = K half).  Wave w of a workgroup takes bytes 12288 w .. of `operands`,
+// fragment f of lane l at 1024 f + 16 l: the LDS image is that copy, lane-linear, so every
+// ds_read_b128 is conflict-free.  FROM_LDS: all 12 fragments are read again in every step (the
+// kernel's 12 reads per 384 matrix cycles); otherwise once, in front of the loop.  STAMP: lane 0 of
+// every workgroup writes (shader cycles, 100 MHz ticks) of its loop to stamps[2 * workgroup ..].
+constexpr int SHAPE_WAVES = 8;                       // one workgroup per CU: two waves per SIMD
+constexpr int SHAPE_WAVE_BYTES = 12 * 64 * 16;
+constexpr int SHAPE_LDS = SHAPE_WAVES * SHAPE_WAVE_BYTES;        // 96 KiB: no second workgroup on the CU
+
+template <bool S16, bool FROM_LDS, bool STAMP>
+__global__ __launch_bounds__(64 * SHAPE_WAVES) void calib_mfma_shape_kernel(const cn_f16x8v *__restrict__ operands,
+                                                                            float *sink, unsigned long long *stamps,
+                                                                            int iters)
+{
+    extern __shared__ __attribute__((aligned(16))) char shape_smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    cn_f16x8v *img = reinterpret_cast<cn_f16x8v *>(shape_smem + wave * SHAPE_WAVE_BYTES);
+#pragma unroll
+    for (int f = 0; f < 12; ++f) img[f * 64 + lane] = operands[(wave * 12 + f) * 64 + lane];
+    __syncthreads();
+    cn_f16x8v fr[12];
+    auto read_all = [&]() {
+#pragma unroll
+        for (int f = 0; f < 12; ++f) fr[f] = img[f * 64 + lane];
+    };
+    typedef typename std::conditional<S16, cn_f32x4, cn_f32x16>::type acc_t;
+    constexpr int NACC = S16 ? 8 : 2;
+    acc_t acc[NACC];
+#pragma unroll
+    for (int j = 0; j < NACC; ++j)
+#pragma unroll
+        for (int r = 0; r < (S16 ? 4 : 16); ++r) acc[j][r] = 0.f;
+    if (!FROM_LDS) read_all();
+    unsigned long long t0 = 0, c0 = 0;
+    if (STAMP) {
+        t0 = wall_clock64();
+        c0 = clock64();
+#pragma unroll
+        for (int j = 0; j < NACC; ++j) asm volatile("" : "+v"(acc[j]));   // the loop stays behind the stamps
+    }
+    for (int it = 0; it < iters; ++it) {
+        if (FROM_LDS) {
+            asm volatile("" ::: "memory");           // the image may have changed: read it again
+            read_all();
+        }
+        if constexpr (S16) {
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                acc_t *d = acc + 4 * cb;
+#pragma unroll
+                for (int pb = 0; pb < 4; ++pb)
+                    d[pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr[2 * cb], fr[4 + 2 * pb + 1], d[pb], 0, 0, 0);
+#pragma unroll
+                for (int pb = 0; pb < 4; ++pb)
+                    d[pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr[2 * cb + 1], fr[4 + 2 * pb], d[pb], 0, 0, 0);
+#pragma unroll
+                for (int pb = 0; pb < 4; ++pb)
+                    d[pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fr[2 * cb], fr[4 + 2 * pb], d[pb], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int kh = 0; kh < 2; ++kh) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[kh], fr[4 + 4 * i + 2 + kh], acc[i], 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[2 + kh], fr[4 + 4 * i + kh], acc[i], 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[kh], fr[4 + 4 * i + kh], acc[i], 0, 0, 0);
+            }
+        }
+    }
+    if (STAMP) {
+        // (the accumulators are complete before the clocks are read a second time)
+#pragma unroll
+        for (int j = 0; j < NACC; ++j) asm volatile("" : "+v"(acc[j]));
+        const unsigned long long c1 = clock64();
+        const unsigned long long t1 = wall_clock64();
+        if (threadIdx.x == 0) {
+            stamps[2 * blockIdx.x] = c1 - c0;
+            stamps[2 * blockIdx.x + 1] = t1 - t0;
+        }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NACC; ++j)
+#pragma unroll
+        for (int r = 0; r < (S16 ? 4 : 16); ++r) s += acc[j][r];
+    if (s == 12345.678f) sink[0] = s;     // never true: keeps the accumulators live
+}
+
 }  // namespace
 
 extern "C" int cn_calib_clock(unsigned long long *out, int ticks, void *stream)
@@ -1039,6 +1141,39 @@ extern "C" double cn_calib_mfma_f16(float *sink, int iters, void *stream)
     if (hipGetLastError() != hipSuccess) return 0.0;
     // FLOPs of the launch: waves x iters x 16 MFMAs x 2 * 32 * 32 * 16
     return (double)blocks * 4.0 * (double)iters * 16.0 * 32768.0;
+}
+
+extern "C" double cn_calib_mfma_shape(const void *operands, float *sink, unsigned long long *stamps, int shape,
+                                      int from_lds, int iters, void *stream)
+{
+    if (!operands || !sink || iters <= 0 || !cn_aligned16(operands)) return 0.0;
+    if (shape != 16 && shape != 32) return 0.0;
+    const int blocks = 256;                // one workgroup of 8 waves per CU
+    const dim3 grid(blocks), block(64 * SHAPE_WAVES);
+    const cn_f16x8v *ops = (const cn_f16x8v *)operands;
+    hipStream_t st = (hipStream_t)stream;
+#define CN_SHAPE_LAUNCH(S16, L, T)                                                                         \
+    do {                                                                                                   \
+        CN_SET_MAX_LDS_ONCE((calib_mfma_shape_kernel<S16, L, T>), SHAPE_LDS);                              \
+        hipLaunchKernelGGL((calib_mfma_shape_kernel<S16, L, T>), grid, block, SHAPE_LDS, st, ops, sink, stamps, iters); \
+    } while (0)
+#define CN_SHAPE_LAUNCH2(S16, L)                                                                           \
+    do {                                                                                                   \
+        if (stamps) CN_SHAPE_LAUNCH(S16, L, true);                                                         \
+        else CN_SHAPE_LAUNCH(S16, L, false);                                                               \
+    } while (0)
+    if (shape == 16) {
+        if (from_lds) CN_SHAPE_LAUNCH2(true, true);
+        else CN_SHAPE_LAUNCH2(true, false);
+    } else {
+        if (from_lds) CN_SHAPE_LAUNCH2(false, true);
+        else CN_SHAPE_LAUNCH2(false, false);
+    }
+#undef CN_SHAPE_LAUNCH2
+#undef CN_SHAPE_LAUNCH
+    if (hipGetLastError() != hipSuccess) return 0.0;
+    // FLOPs of the launch: waves x iters x 3 products x 2 * 64 pixels * 32 channels * K 32
+    return (double)blocks * SHAPE_WAVES * (double)iters * 3.0 * 2.0 * 64.0 * 32.0 * 32.0;
 }
 
 extern "C" int cn_calib_copy(const void *src, void *dst, size_t bytes, void *stream)

@@ -148,6 +148,8 @@ def _declare(lib):
     lib.cn_flip_average_f32_batch.argtypes = [vp, vp, i, i, i, i, vp, vp, i, i, vp]
     lib.cn_calib_mfma_f16.restype = ctypes.c_double
     lib.cn_calib_mfma_f16.argtypes = [vp, i, vp]
+    lib.cn_calib_mfma_shape.restype = ctypes.c_double
+    lib.cn_calib_mfma_shape.argtypes = [vp, vp, vp, i, i, i, vp]
     lib.cn_calib_copy.restype = i
     lib.cn_calib_copy.argtypes = [vp, vp, sz, vp]
     lib.cn_calib_clock.restype = i

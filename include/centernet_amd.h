@@ -152,7 +152,9 @@ const char *cn_arch(void);
  *         2 ... 7 = also for launches of fewer than 256 work items.
  * key 29: start delay of the second resident workgroup, 0 ... 255 units of 256 cycles (default 0).
  * key 30: A/B switches, a bit set, 0 ... 255 (default 2): bit 0 = no s_setprio(1) around the consumers'
- *         MFMA block, bit 1 = the pipelined schedule.
+ *         MFMA block, bit 1 = the pipelined schedule, bit 2 = v_mfma_f32_32x32x16_f16 in the generic forms
+ *         (3x3 / s1, stride 2, transposed) whose default is v_mfma_f32_16x16x32_f16 (the fused heads run
+ *         32x32x16 whatever the bit says).
  * key 31: 1 = the fused heads with a 64-wide hidden layer run on it (default), 0 = on the LDS-halo kernel.
  * key 32: 1 = ConvTranspose2d(4, 2, 1) runs on it in parity form (default), 0 = on the LDS-halo kernel.
  * key 33: 1 = 3x3 / stride 2 / pad 1 runs on it in parity-plane form (default), 0 = on the implicit GEMM.
@@ -343,6 +345,18 @@ int cn_flip_average_f32_batch(float *x_pairs, float *out, int P, int C, int H, i
  * grid-stride copy of `bytes` (multiple of 16) from src to dst. */
 double cn_calib_mfma_f16(float *sink, int iters, void *stream);
 int cn_calib_copy(const void *src, void *dst, size_t bytes, void *stream);
+/* cn_calib_mfma_shape (tools/bench_mfma_shape.py): the bare f32s step of the persistent 3x3 kernel -- a
+ * wave tile of 64 pixels x 32 channels, K 32 per step as three fp16 products per tile -- as
+ * v_mfma_f32_32x32x16_f16 (shape = 32: two tiles, 12 instructions per step) or v_mfma_f32_16x16x32_f16
+ * (shape = 16: eight tiles, 24 instructions), 256 workgroups x 8 waves = two waves per SIMD.  operands:
+ * CN_CALIB_SHAPE_OPERAND_BYTES of fp16 values the caller chooses (wave w: 12 fragments of 64 lanes x 16
+ * bytes at 12288 w).  from_lds != 0: every step reads its 12 fragments from LDS again (ds_read_b128);
+ * 0: once, in front of the loop.  stamps: NULL, or 2 x 256 words that receive per workgroup the shader
+ * cycles and the 100 MHz ticks of its loop (a build of its own: without stamps no clock is read).
+ * Returns the FLOPs of the launch (0 on error). */
+#define CN_CALIB_SHAPE_OPERAND_BYTES 98304
+double cn_calib_mfma_shape(const void *operands, float *sink, unsigned long long *stamps, int shape,
+                           int from_lds, int iters, void *stream);
 /* cn_calib_latency: ONE lane walks `steps` dependent loads through `chain` (chain[i] = index of the
  * next element; the caller lays the walk out: a buffer beyond the caches for the HBM latency, a small
  * one for L2), then `steps` dependent device-scope atomic additions on *atom.  out[0], out[1]: ticks of

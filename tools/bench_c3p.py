@@ -5,6 +5,8 @@ the resdcn_18 / dla_34 trunk shapes.  GPU box only.
 usage: python tools/bench_c3p.py            # correctness + timing
        QUICK=1 python tools/bench_c3p.py    # correctness only
        STAG=0,8,16 python tools/bench_c3p.py   # also sweep the start delay of the second workgroup (key 29)
+       AB=1 python tools/bench_c3p.py      # only: the flagship's s1 / stride-2 / transposed layers under two values of
+                                           # key 30 (AB_KNOBS=2,6: the default MFMA shape against 32x32x16)
 """
 import ctypes
 import os
@@ -124,6 +126,75 @@ def check(case, nb=None, label=""):
         label, out[0][0], out[2][0], d01, out[0][2], out[2][2], "ok" if ok else "FAIL"))
     return ok
 
+
+def ab_layers():
+    """AB=1: the flagship's (resdcn_18, B = 32, 512 x 512) launches of the generic forms, built by the engine as the
+    network builds them, timed under two values of key 30 (AB_KNOBS, default 2,6: the default MFMA shape against
+    32x32x16) in interleaved rounds after 2 s of back-to-back launches.  Per layer: median and min .. max of both
+    arms; per form: the summed medians."""
+    import time
+    from centernet_amd.engine import Act, PlanBuilder
+    arms = [int(v) for v in os.environ.get("AB_KNOBS", "2,6").split(",")]
+    rounds = int(os.environ.get("ROUNDS", "9"))
+    layers = [("s1", 64, 128, 64, None), ("s1", 64, 128, 64, "f32s"), ("s1", 128, 64, 128, None), ("s1", 128, 64, 128, "f32s"),
+              ("s1", 256, 32, 256, None), ("s1", 256, 32, 256, "f32s"), ("s1", 512, 16, 512, None), ("s1", 512, 16, 512, "f32s"),
+              ("s2", 64, 128, 128, None), ("s2", 128, 64, 256, None), ("s2", 256, 32, 512, None),
+              ("deconv", 256, 16, 256, None), ("deconv", 128, 32, 128, None), ("deconv", 64, 64, 64, None)]
+    g = torch.Generator().manual_seed(7)
+    sums = {}
+    print("== key 30 = %d against %d, B = 32, ms per launch: median (min .. max) over %d interleaved rounds" % (arms[0], arms[1], rounds))
+    for form, ci, hw, co, res in layers:
+        pb = PlanBuilder(dev, 32, hw, hw, split=True)
+        xin = pb.packed(Act(torch.randn((32, hw, hw, ci), generator=g).to(dev), 32, hw, hw, ci))
+        if form == "deconv":
+            w = torch.randn((ci, co, 4, 4), generator=g) * (2.0 / (ci * 4)) ** 0.5
+            pb.conv_transpose4x4s2(xin, w, bn=None, relu=True)
+        else:
+            w = torch.randn((co, ci, 3, 3), generator=g) * (2.0 / (ci * 9)) ** 0.5
+            r = None
+            if res:
+                r = pb.packed(Act(torch.randn((32, hw, hw, co), generator=g).to(dev), 32, hw, hw, co))
+            pb.conv(xin, w, bias=torch.randn(co, generator=g), relu=True, stride=2 if form == "s2" else 1, padding=1, residual=r)
+        for op in pb.ops[:-1]:
+            op()
+        launch = pb.ops[-1]
+
+        def ms(n=10):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(n):
+                launch()
+            e.record()
+            torch.cuda.synchronize()
+            return s.elapsed_time(e) / n
+        t_end = time.time() + float(os.environ.get("WARM_S", "2.0"))
+        while time.time() < t_end:
+            for k in arms:
+                lib.cn_set_tuning(30, k)
+                ms(20)
+        times = {k: [] for k in arms}
+        for _ in range(rounds):
+            for k in arms:
+                lib.cn_set_tuning(30, k)
+                times[k].append(ms())
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        print("%-6s %3d -> %3d @ %3d res %-4s | %s | ratio %.4f" % (
+            form, ci, co, hw, res, " | ".join("key30=%d %.4f (%.4f .. %.4f)" % (k, med[k], min(times[k]), max(times[k])) for k in arms),
+            med[arms[0]] / med[arms[1]]))
+        acc = sums.setdefault(form, {k: [0.0, 0.0] for k in arms})
+        for k in arms:
+            acc[k][0] += med[k]
+            acc[k][1] += max(times[k]) - min(times[k])
+        del pb
+    for form, acc in sums.items():
+        print("%-6s summed medians: %s | ratio %.4f" % (form, " | ".join(
+            "key30=%d %.4f ms (summed spread %.4f)" % (k, acc[k][0], acc[k][1]) for k in arms), acc[arms[0]][0] / acc[arms[1]][0]))
+    lib.cn_reset_tuning()
+
+
+if os.environ.get("AB"):
+    ab_layers()
+    sys.exit(0)
 
 allok = True
 lib.cn_set_tuning(30, int(os.environ.get("CHECK_KNOBS", "0")))     # key 30 for the correctness pass
