@@ -175,18 +175,27 @@ __host__ __device__ constexpr int p3_halo_key(bool s16, int hx)
     return s16 ? (int)((0x062654210ull >> (4 * (hx >> 1))) & 7) : ((hx >> 1) & 7);
 }
 
+// Swizzle key of weight row n of a (tap, chunk) tile.  The fused heads on 16x16x32 (hs16) read the rows of a
+// 16-row block as n = base + (r & 7) + 16 (r >> 3), r = lane & 15 (P3 heads16 below: the hidden channels a lane
+// ends up with are then the K set of a packed 1x1 piece), so the key takes bit 4 of n where the other forms take
+// bit 3: in terms of r it is the same (r >> 1) & 7, and the reads are conflict-free for the same reason.
+__host__ __device__ constexpr int p3_weight_key(bool hs16, int n)
+{
+    return hs16 ? (((n >> 1) & 3) | (((n >> 4) & 1) << 2)) : ((n >> 1) & 7);
+}
+
 constexpr int p3_halo_loaders(int ntap, bool s2) { return (P3_HALO2 && (s2 || ntap == 4)) ? 2 : 1; }
 constexpr int p3_threads(int ntap, bool s2) { return 320 + 64 * p3_halo_loaders(ntap, s2); }
 
-// S16: the generic consumers on v_mfma_f32_16x16x32_f16 (eight 16x16 accumulators per wave) instead of
-// v_mfma_f32_32x32x16_f16 (two 32x32): same wave tile, reads and matrix cycles -- see CONSUMERS below.  Appended
-// last: bench.py reads the other arguments by position.
+// S16: the consumers on v_mfma_f32_16x16x32_f16 (eight 16x16 accumulators per wave) instead of
+// v_mfma_f32_32x32x16_f16 (two 32x32): same wave tile, reads and matrix cycles -- see CONSUMERS below (the generic
+// forms and, in the pipelined schedule, the fused heads).  Appended last: bench.py reads the other arguments by position.
 template <int RES, bool OUT_PLAIN, bool DBG = false, bool HEADS = false, int NTAP = 9, bool S2 = false, bool PIPE = false,
           bool S16 = false>
 __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const P3Args a, const P3Heads hd)
 {
-    static_assert(!S16 || (!HEADS && !DBG), "16x16x32: the generic consumers only (the heads' hidden accumulators are the B "
-                                            "operand of their 1x1 GEMM in the 32x32 layout)");
+    static_assert(!S16 || !DBG, "16x16x32: not in the instrumented instantiation");
+    static_assert(!S16 || !HEADS || PIPE, "16x16x32 heads: the pipelined schedule only");
     static_assert(!PIPE || !DBG, "pipelined fragment schedule: not in the instrumented instantiation");
     static_assert(!S2 || (NTAP == 9 && RES == 0 && !DBG && !HEADS), "stride 2: nine taps, no residual");
     // residual rows requested this many steps before an item's last step ends (0 .. 3 measured with
@@ -230,14 +239,14 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
 #define P3_IC(v) std::integral_constant<int, (v)>{}
         if (wave == 4) {
             // ---- weight tiles: piece p = rows 8p .. 8p+7 of the 64-row tile of (tap, chunk);
-            // slot s of row n receives source column s ^ ((n >> 1) & 7)
+            // slot s of row n receives source column s ^ p3_weight_key(n) (= (n >> 1) & 7 but for the heads on 16x16x32)
             unsigned wofs[8];        // per item: byte offset of the lane's source inside one tap's matrix
             auto set_wofs = [&](int nb) {
 #pragma unroll
                 for (int p = 0; p < 8; ++p) {
                     const int n = 8 * p + prow;
                     const int row = min(nb * 64 + n, a.cout_pad - 1);
-                    wofs[p] = (unsigned)(row * a.cin_padB + ((ps ^ ((n >> 1) & 7)) << 4));
+                    wofs[p] = (unsigned)(row * a.cin_padB + ((ps ^ p3_weight_key(HEADS && S16, n)) << 4));
                 }
             };
             set_wofs(first % a.nblk);
@@ -437,7 +446,304 @@ __global__ __launch_bounds__(p3_threads(NTAP, S2), 4) void conv3x3p_kernel(const
     }
 
 
-    if constexpr (HEADS) {
+    if constexpr (HEADS && S16) {
+        // =============================== CONSUMERS, fused heads, 16x16x32 ===============================
+        // Waves 4 x 1 as in the 32x32 form below: wave w owns tile rows 2 w, 2 w + 1 and all 64 hidden channels of
+        // the item's head, as 4 channel blocks x 2 pixel blocks of 16 x 16: acc[2 cb + pb] = D[row 4 s + e of block
+        // cb][pixel 16 pb + (lane & 15)], s = lane >> 4, e = 0 .. 3.  Pixel block pb = tile row 2 w + pb (18 halo
+        // rows apart: an immediate), halo key p3_halo_key(true, .) as in the generic 16x16x32 consumers.
+        // Which hidden channel a ROW of a block is, is only an LDS address: row r = lane & 15 of block cb = 2 j + u
+        // reads weight row 32 j + 8 u + (r & 7) + 16 (r >> 3), so D row 4 s + e of block 2 j + u is hidden channel
+        //     c = 32 j + 16 (s >> 1) + 4 (s & 1) + e + 8 u.
+        // The eight values (u = 0, 1; e = 0 .. 3) a lane holds of blocks 2 j, 2 j + 1 are then the K = 32 B operand
+        // of step j of the 1x1 GEMM with K order 32 j + 16 (s >> 1) + 8 u + 4 (s & 1) + e -- the K set of the piece
+        // (row >> 5, j, s2 = s >> 1, part, lane = (row & 31) + 32 (s & 1)) of cn_pack_head_w2_f32s, which is read as
+        // the A operand as it is: both shapes take the same packed buffer.  The 1x1 output runs in cdiv(cout, 16)
+        // blocks of 16 rows (80 classes: 5 blocks, the 32x32 form computes 96 rows), out[16 ob + 4 s + e][pixel].
+        // tests/test_c3p_heads_map_host.py mirrors these maps.
+        // (wave index and ReLU floor as scalars: as lane values they are two registers held over the whole walk)
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        // the lane id, recomputed where it is needed (two instructions): held in a register over the whole walk it is
+        // the one register too many (with it the range maximum is spilled and reloaded once per item)
+        auto lane_id = [&]() {
+            int ln;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+            return ln;
+        };
+        int arow, aswz, b0;
+        auto lane_consts = [&]() {
+            const int ln = lane_id();
+            const int px = ln & 15, sl = ln >> 4;
+            arow = (2 * wv * P_HW + px) * 128;
+            aswz = 0;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) aswz |= (((sl ^ p3_halo_key(true, px + kx)) & 7) << 4) << (8 * kx);
+            b0 = ((px & 7) + 16 * (px >> 3)) * 128 + (((sl ^ ((px >> 1) & 7)) & 7) << 4);
+        };
+        lane_consts();
+        cn_f32x4 acc[8];
+        auto zero_acc = [&]() {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
+        };
+        zero_acc();
+        float rng_out = 0.f;
+        auto lds128 = [&](int off) { return *reinterpret_cast<const p3_f16x8 *>(smem + off); };
+        const float relu_floor = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(a.relu ? 0 : (int)0xff800000u));
+        const int HWp = a.H * a.W;
+        // 1x1 A fragments (high | low) of the 16-row output block ob, K step j: two 16-byte pieces of the packed buffer
+        auto load_w2 = [&](p3_f16x8 (&dst)[2], const char *wbase, int ob, int j, int ln) {
+            const int row = 16 * ob + (ln & 15), s = ln >> 4;
+            const int piece = (((row >> 5) * 2 + j) * 2 + (s >> 1)) * 2, l2 = (row & 31) + 32 * (s & 1);
+#pragma unroll
+            for (int part = 0; part < 2; ++part)
+                dst[part] = *reinterpret_cast<const p3_f16x8 *>(wbase + ((piece + part) * 64 + l2) * 16);
+        };
+        // 1x1 fragments of the current output block, K step 0 / 1 (of output block 0: step 0 is requested in the
+        // item's last step, step 1 between the two K steps of the hidden layer -- registers)
+        p3_f16x8 wfa[2], wfb[2];
+        auto epilogue = [&](const P3Item &it) {
+            const int ln = lane_id();
+            const int px = ln & 15, s = ln >> 4;
+            const int head = it.nb;
+            const int cout2 = hd.cout[head];
+            const char *w2 = hd.wf[head];
+            float *y2 = hd.y[head];
+            const int nob = (cout2 + 15) >> 4;
+            // hidden layer -> (high, low) B fragments [K step j][pixel block]
+            p3_f16x8 shi[2][2], slo[2][2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                if (j == 1) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    load_w2(wfb, w2, 0, 1, ln);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                cn_f16x4v hq[2][2], lq[2][2];     // [pixel block][u]
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int n = 32 * j + 8 * u + 16 * (s >> 1) + 4 * (s & 1);
+                    const cn_f32x4 sc = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + n * 4);
+                    const cn_f32x4 sh = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + 256 + n * 4);
+#pragma unroll
+                    for (int pb = 0; pb < 2; ++pb) {
+                        cn_f32x4 t;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) t[e] = fmaxf(acc[2 * (2 * j + u) + pb][e] * sc[e] + sh[e], relu_floor);
+                        cn_rng_upd4(rng_out, t);
+                        cn_split4(t, hq[pb][u], lq[pb][u]);
+                    }
+                }
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb) {
+                    shi[j][pb] = __builtin_shufflevector(hq[pb][0], hq[pb][1], 0, 1, 2, 3, 4, 5, 6, 7);
+                    slo[j][pb] = __builtin_shufflevector(lq[pb][0], lq[pb][1], 0, 1, 2, 3, 4, 5, 6, 7);
+                }
+            }
+            const int oy = it.ty0 + 2 * wv, ox = it.tx0 + px;
+            const bool ok0 = oy < a.H && ox < a.W, ok1 = oy + 1 < a.H && ox < a.W;
+            float *ypix = y2 + (size_t)it.b * cout2 * HWp + oy * a.W + ox;
+#pragma unroll 1
+            for (int ob = 0; ob < nob; ++ob) {
+                cn_f32x4 acc2[2];
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc2[pb][r] = 0.f;
+                __builtin_amdgcn_sched_barrier(0);     // (operand hazard: fragments landed before the first MFMA)
+                // smallest terms first, as in the 32x32 form: w_lo * h_hi, w_hi * h_lo, w_hi * h_hi per K step
+#pragma unroll
+                for (int term = 0; term < 3; ++term)
+#pragma unroll
+                    for (int pb = 0; pb < 2; ++pb)
+                        acc2[pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfa[term == 0 ? 1 : 0], term == 1 ? slo[0][pb] : shi[0][pb],
+                                                                          acc2[pb], 0, 0, 0);
+#pragma unroll
+                for (int term = 0; term < 3; ++term)
+#pragma unroll
+                    for (int pb = 0; pb < 2; ++pb)
+                        acc2[pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfb[term == 0 ? 1 : 0], term == 1 ? slo[1][pb] : shi[1][pb],
+                                                                          acc2[pb], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                // output scale / bias of the lane's four rows from the LDS stash (rows beyond cout hold 1 / 0).
+                // Reading the accumulators closes the MFMA chain -- only then are the fragment registers re-used
+                // for the next block's loads (they land under this block's stores)
+                const int co0 = 16 * ob + 4 * s;
+                const cn_f32x4 os = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + 512 + co0 * 4);
+                const cn_f32x4 bs = *reinterpret_cast<const cn_f32x4 *>(smem + P_SSOFF + 896 + co0 * 4);
+                cn_f32x4 v[2];
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[pb][e] = acc2[pb][e] * os[e] + bs[e];
+                __builtin_amdgcn_sched_barrier(0);
+                if (ob + 1 < nob) {
+                    load_w2(wfa, w2, ob + 1, 0, ln);
+                    load_w2(wfb, w2, ob + 1, 1, ln);
+                }
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int co = co0 + e;
+                        if ((pb ? ok1 : ok0) && co < cout2) ypix[(size_t)co * HWp + pb * a.W] = v[pb][e];
+                    }
+            }
+        };
+
+#define P3_IC(v) std::integral_constant<int, (v)>{}
+        // ---- the pipelined schedule of the generic 16x16x32 consumers (pstep16 below) with the roles the 4 x 2
+        // wave tile gives the operands: four weight fragments meet two pixel fragments.  Terms per tile in the
+        // order A = w_hi * x_lo, B = w_lo * x_hi, C = w_hi * x_hi, eight MFMAs (128 matrix cycles) each, pixel
+        // block 0 in front of 1; C of step t is carried across barrier t + 1:
+        //     barrier t + 1
+        //     reads 1 of step t + 1: w_hi (into the OTHER of two w_hi sets: C (t) still holds this one) and x_lo
+        //                            (last used by A (t): B (t) = 128 matrix cycles back)
+        //     C (t)                  (128 matrix cycles over the latency of reads 1)
+        //     A (t + 1), pixel block 0
+        //     reads 2: w_lo (last used by B (t): 192 cycles back), x_hi of block 0 (last used by the first half of
+        //                            C (t): 128 back)
+        //     A (t + 1), pixel block 1
+        //     reads 3: x_hi of block 1 (last used by the second half of C (t): 128 back)
+        //     B (t + 1), block 0 (64 cycles behind reads 2), then 1 (64 behind reads 3)
+        //     fence, barrier t + 2: every read of step t + 1 is complete
+        // No read crosses a barrier, every read is issued before the first MFMA that could alias it.  The second
+        // w_hi set is 16 registers; a stage of nine steps ends on set 0 with set 1 loaded, which is copied to the
+        // set the next stage begins on (4 fragments per nine steps).  Nothing is carried across an item boundary.
+        p3_f16x8 wh[2][4], wl[4], xh[2], xl[2];
+        int g = 0, sidx = 0;
+        constexpr int prow16 = P_HW * 128;
+        auto wblk = [](int cb) { return (32 * (cb >> 1) + 8 * (cb & 1)) * 128; };
+        auto tap_addr = [&](auto T, int &ax, int &bx) {
+            constexpr int t = decltype(T)::value;
+            constexpr int ky = t / 3, kx = t % 3;
+            ax = arow + ((aswz >> (8 * kx)) & 0xff);
+            bx = b0;
+            asm volatile("" : "+v"(ax), "+v"(bx));
+            return (ky * P_HW + kx) * 128;
+        };
+        auto reads1 = [&](auto T, auto P, int hb, int wb) {
+            constexpr int p = decltype(P)::value;
+            int ax, bx;
+            const int imm = tap_addr(T, ax, bx);
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) wh[p][cb] = lds128(wb + wblk(cb) + bx);
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) xl[pb] = lds128(hb + imm + pb * prow16 + (ax ^ 64));
+        };
+        auto mm = [&](auto TERM, auto P, auto PB) {
+            constexpr int term = decltype(TERM)::value, p = decltype(P)::value, pb = decltype(PB)::value;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb)
+                acc[2 * cb + pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(term == 1 ? wl[cb] : wh[p][cb], term == 0 ? xl[pb] : xh[pb],
+                                                                          acc[2 * cb + pb], 0, 0, 0);
+        };
+        auto pstage = [&](auto LAST, int c, const P3Item &cur) {
+            constexpr bool last = decltype(LAST)::value;
+            const int hb = (sidx & 1) * P_HBYTES, hb1 = ((sidx + 1) & 1) * P_HBYTES;
+            auto WB = [&](int i) { return P_WOFF + ((g + i) & 3) * P_WSLOT; };
+            // per item: scale (prescale factor * exponents) and bias1 of the head's 64 hidden channels and the output
+            // scale / bias of its 1x1 rows, requested at the first step, parked in the LDS stash three steps later.
+            // One array per wave -- 0: scale, 1: bias1, 2: output scale, 3: bias2 -- so a lane holds two values over
+            // those steps, not six; every wave reads all four in its epilogue, six barriers later at the least
+            const bool st_one = (wv & 1) == 0;          // the array's default: 1 (scales) or 0 (biases)
+            float st0 = st_one ? 1.f : 0.f, st1 = st0;
+            if (c == 0) {
+                const int ln = lane_id();
+                if (wv < 2) {
+                    const float *p = wv == 0 ? a.scale : a.shift;
+                    if (p) st0 = p[64 * cur.nb + ln];
+                } else {
+                    const float *p = wv == 2 ? hd.oscale[cur.nb] : hd.bias[cur.nb];
+                    const int cout2 = hd.cout[cur.nb];      // rows that do not exist: 1 / 0
+                    if (p && ln < cout2) st0 = p[ln];
+                    if (p && ln + 64 < cout2) st1 = p[ln + 64];
+                }
+            }
+            auto pstep = [&](auto T) {
+                constexpr int t = decltype(T)::value, p = t & 1;
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_setprio(1);
+                mm(P3_IC(0), P3_IC(p), P3_IC(0));
+                __builtin_amdgcn_sched_barrier(0);
+                int ax, bx;
+                const int imm = tap_addr(T, ax, bx);
+                const int wb = WB(t);
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) wl[cb] = lds128(wb + wblk(cb) + (bx ^ 64));
+                xh[0] = lds128(hb + imm + ax);
+                __builtin_amdgcn_sched_barrier(0);
+                mm(P3_IC(0), P3_IC(p), P3_IC(1));
+                __builtin_amdgcn_sched_barrier(0);
+                xh[1] = lds128(hb + imm + prow16 + ax);
+                if constexpr (last && t == 8) {
+                    // the item's last step: the first 1x1 fragments are requested here -- no reads 1 follow, so they
+                    // can take the idle w_hi set (last used by C (7): A (8) = 128 matrix cycles back); B (8), C (8)
+                    // and the hidden layer's scale / split pass are over their latency
+                    const int ln = lane_id();
+                    load_w2(wfa, hd.wf[cur.nb], 0, 0, ln);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                // (x_lo stays allocated over reads 2 and 3: their registers are not its own)
+                asm volatile("" :: "v"(xl[0]), "v"(xl[1]));
+                mm(P3_IC(1), P3_IC(p), P3_IC(0));
+                mm(P3_IC(1), P3_IC(p), P3_IC(1));
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_setprio(0);
+                p3_lds_fence();                  // every fragment of step t has been waited for by B already
+                p3_barrier();                    // barrier t + 1 (t = 8: barrier 0 of the next stage)
+                if constexpr (t + 1 < 9) reads1(P3_IC(t + 1), P3_IC(1 - p), hb, WB(t + 1));
+                else if constexpr (!last) reads1(P3_IC(0), P3_IC(1 - p), hb1, WB(9));
+                __builtin_amdgcn_sched_barrier(0);
+                // (w_lo stays allocated over reads 1)
+                asm volatile("" :: "v"(wl[0]), "v"(wl[1]), "v"(wl[2]), "v"(wl[3]));
+                mm(P3_IC(2), P3_IC(p), P3_IC(0));
+                mm(P3_IC(2), P3_IC(p), P3_IC(1));
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (t + 1 == 9 && !last) {      // the next stage begins on set 0
+#pragma unroll
+                    for (int cb = 0; cb < 4; ++cb) wh[0][cb] = wh[1][cb];
+                }
+            };
+            pstep(P3_IC(0));
+            pstep(P3_IC(1));
+            pstep(P3_IC(2));
+            if (c == 0) {
+                const int so = P_SSOFF + (wv == 0 ? 0 : wv == 1 ? 256 : wv == 2 ? 512 : 896);
+                const int ln = lane_id();
+                *reinterpret_cast<float *>(smem + so + ln * 4) = st0;
+                if (wv >= 2 && ln < 32) *reinterpret_cast<float *>(smem + so + (64 + ln) * 4) = st1;
+            }
+            pstep(P3_IC(3));
+            pstep(P3_IC(4));
+            pstep(P3_IC(5));
+            pstep(P3_IC(6));
+            pstep(P3_IC(7));
+            pstep(P3_IC(8));
+            g += 9;
+            ++sidx;
+        };
+        p3_barrier();                        // barrier 0 of the first stage
+        for (int k = 0; k < nit; ++k) {
+            const P3Item cur = p3_decode(a, first + k * nx);
+            __builtin_amdgcn_sched_barrier(0);
+            reads1(P3_IC(0), P3_IC(0), (sidx & 1) * P_HBYTES, P_WOFF + (g & 3) * P_WSLOT);
+            __builtin_amdgcn_sched_barrier(0);
+            for (int c = 0; c < a.nchunk - 1; ++c) pstage(std::false_type{}, c, cur);
+            pstage(std::true_type{}, a.nchunk - 1, cur);
+            // (behind barrier 0 of the next item: the stash is rewritten behind its barrier 3 at the earliest,
+            // which no wave passes before every wave has left this epilogue)
+            if (a.nchunk == 1) p3_lds_fence();
+            epilogue(cur);
+            zero_acc();
+            lane_consts();
+        }
+#undef P3_IC
+        if (a.range) cn_rng_commit(a.range, 0, rng_out);
+        return;
+    } else if constexpr (HEADS) {
         // =============================== CONSUMERS, fused heads ===============================
         // Waves 4 x 1: wave w owns pixels 32 w .. 32 w + 31 of the tile (tile rows 2 w, 2 w + 1) and
         // ALL 64 hidden channels of the item's head: acc[j] = D[hidden 32 j ..][pixel], so a lane
@@ -1477,11 +1783,11 @@ static P3Args p3_args(const ConvCall &c, int H, int W, int npar)
     return a;
 }
 
-// MFMA shape of the generic consumers, per form: true = the form runs v_mfma_f32_16x16x32_f16 (template S16) unless
+// MFMA shape of the consumers, per form (the three generic ones and the fused heads): true = the form runs v_mfma_f32_16x16x32_f16 (template S16) unless
 // cn_set_tuning key 30 has the value 4 set (bit 2, the A/B switch: the 32x32x16 shape).  A form is true only where the 16x16x32
-// form measured faster by wall on the flagship's layers (profiles/c3p_mfma_shape_ab.txt); for a form that is false
+// form measured faster by wall on the flagship's layers (profiles/c3p_mfma_shape_ab.txt, c3p_heads_shape_walk_ab.txt); for a form that is false
 // no 16x16x32 instantiation is built.
-constexpr bool P3_S16_S1 = true, P3_S16_S2 = true, P3_S16_DECONV = true;
+constexpr bool P3_S16_S1 = true, P3_S16_S2 = true, P3_S16_DECONV = true, P3_S16_HEADS = true;
 static bool p3_s16(const P3Args &a, bool form_default) { return form_default && !(a.knobs & 4); }
 
 // The persistent grid: a multiple of 8 (one share per XCD), never more than one workgroup per item, and per XCD
@@ -1682,10 +1988,15 @@ int cn_heads3x3p(const void *x, int B, int H, int W, int Cin, int in_pitch, cons
     const dim3 grid = p3_grid(a), block(384);
     // the heads exist in the pipelined schedule only: their unpipelined instantiation kept three barriers
     // reachable with an LDS read in flight (tools/audit_barriers.py) and is no longer built; key 30 bit 1
-    // does not reach this launch
+    // does not reach this launch (bit 2 does: both shapes read the same packed 1x1 buffers)
     a.knobs |= 2;
-    CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, false, false, true, 9, false, true>), P_LDS);
-    hipLaunchKernelGGL((conv3x3p_kernel<0, false, false, true, 9, false, true>), grid, block, P_LDS, st, a, hd);
+#define P3_LAUNCHH(S16)                                                                                          \
+    do {                                                                                                         \
+        CN_SET_MAX_LDS_ONCE((conv3x3p_kernel<0, false, false, true, 9, false, true, S16>), P_LDS);                \
+        hipLaunchKernelGGL((conv3x3p_kernel<0, false, false, true, 9, false, true, S16>), grid, block, P_LDS, st, a, hd); \
+    } while (0)
+    if (p3_s16(a, P3_S16_HEADS)) P3_LAUNCHH(P3_S16_HEADS); else P3_LAUNCHH(false);
+#undef P3_LAUNCHH
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

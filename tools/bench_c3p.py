@@ -5,8 +5,11 @@ the resdcn_18 / dla_34 trunk shapes.  GPU box only.
 usage: python tools/bench_c3p.py            # correctness + timing
        QUICK=1 python tools/bench_c3p.py    # correctness only
        STAG=0,8,16 python tools/bench_c3p.py   # also sweep the start delay of the second workgroup (key 29)
-       AB=1 python tools/bench_c3p.py      # only: the flagship's s1 / stride-2 / transposed layers under two values of
-                                           # key 30 (AB_KNOBS=2,6: the default MFMA shape against 32x32x16)
+       AB=1 python tools/bench_c3p.py      # only: the flagship's s1 / stride-2 / transposed layers and its fused-heads
+                                           # launch under two values of key 30 (AB_KNOBS=2,6: the default MFMA shape
+                                           # against 32x32x16; AB_FORMS=heads: those forms only)
+       CHAIN=1 python tools/bench_c3p.py   # only: layer 1 of the flagship and its stride-2 successor back to back
+                                           # on distinct buffers, under two values of key 30 (CHAIN_KNOBS=2,6)
 """
 import ctypes
 import os
@@ -128,10 +131,11 @@ def check(case, nb=None, label=""):
 
 
 def ab_layers():
-    """AB=1: the flagship's (resdcn_18, B = 32, 512 x 512) launches of the generic forms, built by the engine as the
-    network builds them, timed under two values of key 30 (AB_KNOBS, default 2,6: the default MFMA shape against
-    32x32x16) in interleaved rounds after 2 s of back-to-back launches.  Per layer: median and min .. max of both
-    arms; per form: the summed medians."""
+    """AB=1: the flagship's (resdcn_18, B = 32, 512 x 512) launches of the generic forms and its fused-heads launch
+    (the hm head: 64 hidden channels, 80 outputs, at 128 x 128), built by the engine as the network builds them,
+    timed under two values of key 30 (AB_KNOBS, default 2,6: the default MFMA shape against 32x32x16) in interleaved
+    rounds after 2 s of back-to-back launches.  Per layer: median and min .. max of both arms; per form: the summed
+    medians.  AB_FORMS: a comma-separated subset of s1, s2, deconv, heads."""
     import time
     from centernet_amd.engine import Act, PlanBuilder
     arms = [int(v) for v in os.environ.get("AB_KNOBS", "2,6").split(",")]
@@ -139,7 +143,11 @@ def ab_layers():
     layers = [("s1", 64, 128, 64, None), ("s1", 64, 128, 64, "f32s"), ("s1", 128, 64, 128, None), ("s1", 128, 64, 128, "f32s"),
               ("s1", 256, 32, 256, None), ("s1", 256, 32, 256, "f32s"), ("s1", 512, 16, 512, None), ("s1", 512, 16, 512, "f32s"),
               ("s2", 64, 128, 128, None), ("s2", 128, 64, 256, None), ("s2", 256, 32, 512, None),
-              ("deconv", 256, 16, 256, None), ("deconv", 128, 32, 128, None), ("deconv", 64, 64, 64, None)]
+              ("deconv", 256, 16, 256, None), ("deconv", 128, 32, 128, None), ("deconv", 64, 64, 64, None),
+              ("heads", 64, 128, 80, None)]
+    forms = os.environ.get("AB_FORMS")
+    if forms:
+        layers = [l for l in layers if l[0] in forms.split(",")]
     g = torch.Generator().manual_seed(7)
     sums = {}
     print("== key 30 = %d against %d, B = 32, ms per launch: median (min .. max) over %d interleaved rounds" % (arms[0], arms[1], rounds))
@@ -149,6 +157,12 @@ def ab_layers():
         if form == "deconv":
             w = torch.randn((ci, co, 4, 4), generator=g) * (2.0 / (ci * 4)) ** 0.5
             pb.conv_transpose4x4s2(xin, w, bn=None, relu=True)
+        elif form == "heads":
+            c1, c2 = torch.nn.Conv2d(ci, 64, 3, padding=1), torch.nn.Conv2d(64, co, 1)
+            with torch.no_grad():
+                c1.weight.copy_(torch.randn(c1.weight.shape, generator=g) * (2.0 / (ci * 9)) ** 0.5)
+                c2.weight.copy_(torch.randn(c2.weight.shape, generator=g) * 0.15)
+            pb.heads_from_convs(xin, {"hm": (c1.eval(), c2.eval())})
         else:
             w = torch.randn((co, ci, 3, 3), generator=g) * (2.0 / (ci * 9)) ** 0.5
             r = None
@@ -192,8 +206,86 @@ def ab_layers():
     lib.cn_reset_tuning()
 
 
+def chain_walk():
+    """CHAIN=1: the four layer-1 launches of the flagship wired as in the network (x0 -> a -> b + x0 -> c -> d + b;
+    64 -> 64 @ 128 x 128, B = 32) and the 64 -> 128 / stride-2 launch behind them, on distinct buffers, back to
+    back: 134 MB per map, so what a launch finds in the 256 MiB Infinity Cache is what its producer left there --
+    the state a repeated single launch (AB=1) never sees.  x0 is rewritten by a copy in front of every chain, as
+    the stem writes it in the network.  Two values of key 30 (CHAIN_KNOBS) are timed in interleaved rounds; per
+    chain and per launch: median (min .. max) of both arms, and the rule of profiles/c3p_mfma_shape_ab.txt 2 on
+    the chain (the first arm is kept when its median beats the second's by more than the second's max - min).
+    profiles/c3p_heads_shape_walk_ab.txt: the walk-direction experiment this mode was written for."""
+    import time
+    from centernet_amd.engine import Act, PlanBuilder
+    arms = [int(v) for v in os.environ.get("CHAIN_KNOBS", "2,6").split(",")]
+    rounds = int(os.environ.get("ROUNDS", "9"))
+    reps = int(os.environ.get("CHAIN_REPS", "10"))
+    B, hw = 32, 128
+    g = torch.Generator().manual_seed(11)
+    pb = PlanBuilder(dev, B, hw, hw, split=True)
+
+    def w(co, ci):
+        return torch.randn((co, ci, 3, 3), generator=g) * (2.0 / (ci * 9)) ** 0.5
+    x0 = pb.packed(Act(torch.randn((B, hw, hw, 64), generator=g).to(dev), B, hw, hw, 64))
+    n0 = len(pb.ops)
+    a = pb.conv(x0, w(64, 64), bias=torch.randn(64, generator=g), relu=True, padding=1)
+    b = pb.conv(a, w(64, 64), bias=torch.randn(64, generator=g), relu=True, padding=1, residual=x0)
+    c = pb.conv(b, w(64, 64), bias=torch.randn(64, generator=g), relu=True, padding=1)
+    d = pb.conv(c, w(64, 64), bias=torch.randn(64, generator=g), relu=True, padding=1, residual=b)
+    pb.conv(d, w(128, 64), bias=torch.randn(128, generator=g), relu=True, stride=2, padding=1)
+    for op in pb.ops[:n0]:
+        op()
+    launches = pb.ops[n0:]
+    names = ["s1 x0->a", "s1 a->b +x0", "s1 b->c", "s1 c->d +b", "s2 d->e"]
+    src = x0.t.clone()
+    nl = len(launches)
+
+    def run(n):
+        """n chains: ms per chain and per launch"""
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(nl + 1)] for _ in range(n)]
+        for i in range(n):
+            x0.t.copy_(src)
+            ev[i][0].record()
+            for j, op in enumerate(launches):
+                op()
+                ev[i][j + 1].record()
+        torch.cuda.synchronize()
+        per = [sum(ev[i][j].elapsed_time(ev[i][j + 1]) for i in range(n)) / n for j in range(nl)]
+        return sum(ev[i][0].elapsed_time(ev[i][nl]) for i in range(n)) / n, per
+    t_end = time.time() + float(os.environ.get("WARM_S", "2.0"))
+    while time.time() < t_end:
+        for k in arms:
+            lib.cn_set_tuning(30, k)
+            run(reps)
+    chain = {k: [] for k in arms}
+    per = {k: [[] for _ in range(nl)] for k in arms}
+    for _ in range(rounds):
+        for k in arms:
+            lib.cn_set_tuning(30, k)
+            t, p = run(reps)
+            chain[k].append(t)
+            for j in range(nl):
+                per[k][j].append(p[j])
+
+    def fmt(v):
+        return "%.4f (%.4f .. %.4f)" % (sorted(v)[len(v) // 2], min(v), max(v))
+    print("== key 30 = %s, ms: median (min .. max) over %d interleaved rounds of %d chains" % (arms, rounds, reps))
+    for j in range(nl):
+        print("%-12s | %s" % (names[j], " | ".join("key30=%d %s" % (k, fmt(per[k][j])) for k in arms)))
+    print("%-12s | %s" % ("chain", " | ".join("key30=%d %s" % (k, fmt(chain[k])) for k in arms)))
+    med = {k: sorted(chain[k])[len(chain[k]) // 2] for k in arms}
+    spread = max(chain[arms[1]]) - min(chain[arms[1]])
+    print("chain: key30=%d is %.4f ms %s than key30=%d; spread (max - min) of key30=%d: %.4f ms -> %s" % (
+        arms[0], abs(med[arms[1]] - med[arms[0]]), "faster" if med[arms[0]] < med[arms[1]] else "slower", arms[1],
+        arms[1], spread, "KEEP" if med[arms[1]] - med[arms[0]] > spread else "STOP"))
+    lib.cn_reset_tuning()
+
+
 if os.environ.get("AB"):
     ab_layers()
+    sys.exit(0)
+if os.environ.get("CHAIN"):
+    chain_walk()
     sys.exit(0)
 
 allok = True
