@@ -125,7 +125,6 @@ __global__ __launch_bounds__(NT) void igemm_kernel(const IgemmArgs a)
     // value when it writes the A tile.
     constexpr bool SPLIT = std::is_same<T, cn_f32s>::value;
     constexpr bool DCN = (AMODE == A_DCN || AMODE == A_DCN_PAD);
-    static_assert(!(F16 && DCN), "the deformable kernel is fp32 / f32s only");
     static_assert(!(SPLIT && AMODE == A_STEM), "the stem reads the fp32 image: fp32 kernel");
     static_assert(NBUF == 1 || NBUF == 2, "LDS tile buffers");
     static_assert(WM * WN == NT / CN_WAVE, "4 waves");
@@ -274,7 +273,7 @@ __global__ __launch_bounds__(NT) void igemm_kernel(const IgemmArgs a)
                     // byte offsets of the four corner pixels (fit 32 bits: checked by the host),
                     // so the gather below is `global_load base(SGPR) + offset(VGPR)`
                     const int base = b * H * W;
-                    const int pb4 = a.in_pitch * (int)sizeof(float);
+                    const int pb4 = a.in_pitch * (int)sizeof(T);   // sizeof(cn_f32s) == 4: its input is plain fp32
                     i0 = (base + yl * W + xl) * pb4;
                     i1 = (base + yl * W + xh) * pb4;
                     i2 = (base + yh * W + xl) * pb4;
@@ -382,7 +381,7 @@ __global__ __launch_bounds__(NT) void igemm_kernel(const IgemmArgs a)
             const int c = c0 + EPV * q;
             const char *xb = reinterpret_cast<const char *>(a.x);
             const bool cok = c < a.Cin;  // false only in the padded tail of a Cin % 32 != 0 layer
-            const unsigned cbyte = (unsigned)(cok ? c : 0) * (unsigned)sizeof(float);
+            const unsigned cbyte = (unsigned)(cok ? c : 0) * (unsigned)sizeof(T);
 #pragma unroll
             for (int p = 0; p < PA; ++p) {
                 const int r = p * 32 + lrow;
@@ -418,6 +417,19 @@ __global__ __launch_bounds__(NT) void igemm_kernel(const IgemmArgs a)
                 const float *wt = swt + (tap * BM + r) * 4;
                 const float mk = smk[tap * BM + r];
                 const float w1 = wt[0], w2 = wt[1], w3 = wt[2], w4 = wt[3];
+                if constexpr (F16 && DCN) {
+                    // corners are 8 halves: blend and mask in fp32, ONE rounding to fp16 into the A tile
+                    const cn_f16x8 h0 = __builtin_bit_cast(cn_f16x8, ra[p][0]), h1 = __builtin_bit_cast(cn_f16x8, ra[p][1]);
+                    const cn_f16x8 h2 = __builtin_bit_cast(cn_f16x8, ra[p][2]), h3 = __builtin_bit_cast(cn_f16x8, ra[p][3]);
+                    cn_f16x8 o;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float s = (float)h0[e] * w1 + (float)h1[e] * w2 + (float)h2[e] * w3 + (float)h3[e] * w4;
+                        o[e] = (_Float16)(s * mk);
+                    }
+                    *reinterpret_cast<cn_f16x8 *>(Ad + r * LDT + 4 * q) = o;
+                    continue;
+                }
                 cn_f32x4 v;
                 // (w1*v1 + w2*v2 + w3*v3 + w4*v4) * mask   (dcn_v2_im2col_cuda.cu:43-45,174)
                 v = ra[p][0] * w1 + ra[p][1] * w2 + ra[p][2] * w3 + ra[p][3] * w4;
@@ -685,7 +697,10 @@ __global__ __launch_bounds__(NT) void igemm_kernel(const IgemmArgs a)
                             cn_store4_f32s(a.y, (size_t)offs[it], a.out_pitch, n, v);
                         }
                     } else {
-                        store4_from_f32(reinterpret_cast<T *>(a.y) + (size_t)offs[it] * a.out_pitch + n, v);
+                        if (F16 && a.out_plain)   // fp16 call with CN_CONV_Y_PLAIN: y is plain fp32
+                            store4_from_f32(reinterpret_cast<float *>(a.y) + (size_t)offs[it] * a.out_pitch + n, v);
+                        else
+                            store4_from_f32(reinterpret_cast<T *>(a.y) + (size_t)offs[it] * a.out_pitch + n, v);
                     }
                 }
             } else if (n < a.Cout) {
@@ -711,7 +726,9 @@ __global__ __launch_bounds__(NT) void igemm_kernel(const IgemmArgs a)
                             }
                         } else {
                             if (a.residual) t += (float)reinterpret_cast<const T *>(a.residual)[o];
-                            reinterpret_cast<T *>(a.y)[o] = (T)(a.relu ? fmaxf(t, 0.f) : t);
+                            t = a.relu ? fmaxf(t, 0.f) : t;
+                            if (F16 && a.out_plain) reinterpret_cast<float *>(a.y)[o] = t;
+                            else reinterpret_cast<T *>(a.y)[o] = (T)t;
                         }
                     }
                 }
@@ -779,11 +796,10 @@ int launch_igemm_n(const IgemmArgs &a, hipStream_t st)
     return CN_OK;
 }
 
-// fp16 activations/weights (fp32 accumulate): dense + stem forms only
+// fp16 activations/weights (fp32 accumulate)
 template <int BM, int BN, int WM, int WN, int AMODE, bool OUT_NCHW>
 int launch_igemm_h(const IgemmArgs &a, hipStream_t st)
 {
-    static_assert(AMODE != A_DCN && AMODE != A_DCN_PAD, "fp16 DCN is not built");
     if (!OUT_NCHW && AMODE == A_DENSE && a.stride == 1)
         return launch_igemm_n<_Float16, BM, BN, WM, WN, AMODE, OUT_NCHW, 1>(a, st);
     return launch_igemm_n<_Float16, BM, BN, WM, WN, AMODE, OUT_NCHW, 2>(a, st);
@@ -813,16 +829,14 @@ int launch_igemm(const IgemmArgs &a, hipStream_t st)
     return launch_igemm_n<float, BM, BN, WM, WN, AMODE, OUT_NCHW, 2>(a, st);
 }
 
-// dtype leg of one tile shape.  fp16: dense and stem forms only; f32s: not the stem
+// dtype leg of one tile shape.  f32s: not the stem
 template <int BM, int BN, int WM, int WN, int AMODE, bool OUT_NCHW>
 int launch_igemm_t(int dtype, const IgemmArgs &a, hipStream_t st)
 {
     if constexpr (AMODE != A_STEM) {
         if (dtype == CN_DTYPE_F32S) return launch_igemm_s<BM, BN, WM, WN, AMODE, OUT_NCHW>(a, st);
     }
-    if constexpr (AMODE == A_DENSE || AMODE == A_STEM) {
-        if (dtype == CN_DTYPE_F16) return launch_igemm_h<BM, BN, WM, WN, AMODE, OUT_NCHW>(a, st);
-    }
+    if (dtype == CN_DTYPE_F16) return launch_igemm_h<BM, BN, WM, WN, AMODE, OUT_NCHW>(a, st);
     return launch_igemm<BM, BN, WM, WN, AMODE, OUT_NCHW>(a, st);
 }
 
@@ -981,7 +995,9 @@ __global__ void splitk_reduce_kernel(const IgemmArgs a)
                 float t = (v[e] + bs) * sc + sf;
                 const size_t o = off * a.out_pitch + n + e;
                 if (res) t += (float)res[o];
-                y[o] = (T)(a.relu ? fmaxf(t, 0.f) : t);
+                t = a.relu ? fmaxf(t, 0.f) : t;
+                if (sizeof(T) == 2 && a.out_plain) reinterpret_cast<float *>(a.y)[o] = t;   // fp16 call, CN_CONV_Y_PLAIN
+                else y[o] = (T)t;
             }
         }
     }
@@ -1332,7 +1348,7 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
         if (!c.out_nchw && !c.out_plain && !aligned128(y)) return CN_ERR_ALIGN;
         if (residual && !c.res_plain && !aligned128(residual)) return CN_ERR_ALIGN;
     }
-    const size_t valign = d->dtype == CN_DTYPE_F16 ? 8 : 16;  // 4 output elements per store
+    const size_t valign = (d->dtype == CN_DTYPE_F16 && !c.out_plain) ? 8 : 16;  // 4 output elements per store
     c.vec_out = (!c.out_nchw && (d->out_pitch & 3) == 0 && (((uintptr_t)y) % valign) == 0 &&
                  (!residual || ((((uintptr_t)residual) % valign) == 0 && (c.res_pitch & 3) == 0))) ? 1 : 0;
     const ConvRoute r = conv_route(c, residual != nullptr, scale != nullptr,
@@ -1383,14 +1399,15 @@ static IgemmArgs dcn_args(const DcnCall &c)
     a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Ho = c.H; a.Wo = c.W; a.Cout = c.Cout;
     a.KH = 3; a.KW = 3; a.stride = 1; a.pad_h = 1; a.pad_w = 1; a.dil = 1;
     a.in_pitch = c.Cin; a.out_pitch = c.out_pitch;
-    a.in_plain = 1;                                   // the gather reads plain fp32 in every mode
+    a.in_plain = 1;                                   // the gather reads a plain tensor (fp16 mode: of halves)
     a.out_plain = c.out_plain;
     a.OH = c.H; a.OW = c.W; a.oy_mul = 1; a.oy_add = 0; a.ox_mul = 1; a.ox_add = 0;
     a.relu = c.relu;
     a.M = c.B * c.H * c.W;
-    a.cin_pad = round_up(c.Cin, 32);
+    const int bke = c.dtype == CN_DTYPE_F16 ? 64 : 32;   // channels per K chunk of the packed weight
+    a.cin_pad = round_up(c.Cin, bke);
     a.cout_pad = round_up(c.Cout, 32);
-    a.nchunk = a.cin_pad / 32;
+    a.nchunk = a.cin_pad / bke;
     a.KT = 9 * a.nchunk;
     a.ksplit = 1;
     return a;
@@ -1421,7 +1438,7 @@ int cn_dcn_reduce(const DcnCall &c, int ksplit, hipStream_t st)
 // with ky(0,.) = {3,1}, ky(1,.) = {2,0}: four 2x2 convolutions, one launch (blockIdx.z).
 namespace {
 __global__ void pack_deconv_weight_kernel(const float *__restrict__ w, float *__restrict__ wp,
-                                          int Cin, int Cout, int cout_pad, int cin_pad, int f32s)
+                                          int Cin, int Cout, int cout_pad, int cin_pad, int f32s, int f16)
 {
     const size_t total = (size_t)16 * cout_pad * cin_pad;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -1441,6 +1458,8 @@ __global__ void pack_deconv_weight_kernel(const float *__restrict__ w, float *__
             const size_t g = (i - (size_t)(c & 31)) * 2;
             wh[g + (c & 31)] = hi;
             wh[g + 32 + (c & 31)] = (_Float16)(v - (float)hi);
+        } else if (f16) {   // halves, 64-channel K chunks (cin_pad is the caller's)
+            reinterpret_cast<_Float16 *>(wp)[i] = (_Float16)v;
         } else {
             wp[i] = v;
         }
@@ -1465,13 +1484,17 @@ extern "C" int cn_pack_deconv4x4s2_weight(const float *w_iohw, void *w_packed, i
 {
     if (!w_iohw || !w_packed) return CN_ERR_NULL;
     if (Cin <= 0 || Cout <= 0) return CN_ERR_SHAPE;
-    if (dtype != CN_DTYPE_F32 && dtype != CN_DTYPE_F32S) return CN_ERR_UNSUPPORTED;
-    const size_t total = cn_packed_deconv4x4s2_weight_floats(Cin, Cout);
+    const bool f16 = dtype == CN_DTYPE_F16;
+    if (dtype != CN_DTYPE_F32 && dtype != CN_DTYPE_F32S && !f16) return CN_ERR_UNSUPPORTED;
+    // fp16: 16 * cout_pad * round_up(Cin, 64) halves -- never more bytes than the fp32 form, so a buffer of
+    // cn_packed_deconv4x4s2_weight_floats(Cin, Cout) floats holds every dtype
+    const int cin_pad = round_up(Cin, f16 ? 64 : 32);
+    const size_t total = (size_t)16 * round_up(Cout, 32) * cin_pad;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(pack_deconv_weight_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       w_iohw, (float *)w_packed, Cin, Cout, round_up(Cout, 32), round_up(Cin, 32),
-                       dtype == CN_DTYPE_F32S ? 1 : 0);
+                       w_iohw, (float *)w_packed, Cin, Cout, round_up(Cout, 32), cin_pad,
+                       dtype == CN_DTYPE_F32S ? 1 : 0, f16 ? 1 : 0);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -1492,9 +1515,11 @@ extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, 
 {
     if (!x_nhwc || !w_packed || !y_nhwc) return CN_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return CN_ERR_SHAPE;
-    if ((Cin & 3) || (in_pitch & 3) || in_pitch < Cin || out_pitch < Cout) return CN_ERR_UNSUPPORTED;
-    const bool f32s = (dtype == CN_DTYPE_F32S);
-    if (dtype != CN_DTYPE_F32 && !f32s) return CN_ERR_UNSUPPORTED;
+    const bool f32s = (dtype == CN_DTYPE_F32S), f16 = (dtype == CN_DTYPE_F16);
+    if (dtype != CN_DTYPE_F32 && !f32s && !f16) return CN_ERR_UNSUPPORTED;
+    const int epv = f16 ? 8 : 4;   // elements of a 16-byte input vector
+    if ((Cin % epv) || (in_pitch % epv) || in_pitch < Cin || out_pitch < Cout) return CN_ERR_UNSUPPORTED;
+    if (f16 && (flags & (CN_CONV_X_PLAIN | CN_CONV_Y_PLAIN))) return CN_ERR_UNSUPPORTED;   // half in, half out
     if (f32s && !(flags & CN_CONV_X_PLAIN) && (in_pitch & 31)) return CN_ERR_UNSUPPORTED;
     if (f32s && !(flags & CN_CONV_Y_PLAIN) && (out_pitch & 31)) return CN_ERR_UNSUPPORTED;
     if (!cn_aligned16(x_nhwc) || !cn_aligned16(w_packed)) return CN_ERR_ALIGN;
@@ -1515,7 +1540,8 @@ extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, 
     c.vec_out = ((out_pitch & 3) == 0 && cn_aligned16(y_nhwc)) ? 1 : 0;
     c.ctl = ctl;
     c.ksplit = 1;
-    c.cin_pad = round_up(Cin, 32); c.cout_pad = round_up(Cout, 32); c.nchunk = c.cin_pad / 32;
+    const int bke = f16 ? 64 : 32;
+    c.cin_pad = round_up(Cin, bke); c.cout_pad = round_up(Cout, 32); c.nchunk = c.cin_pad / bke;
     hipStream_t st = (hipStream_t)stream;
     // LDS-halo form (cn_conv3x3.hip) unless disabled (cn_set_tuning key 10) or the tile would be
     // mostly padding (Cout <= 32)

@@ -139,7 +139,7 @@ __device__ __forceinline__ void conv3x3s1_body(const C3Args &a, const C3Heads &h
     constexpr bool SPLIT = std::is_same<T, cn_f32s>::value;
     constexpr bool WREG = (NBUFB == 0);
     static_assert(!WREG || SPLIT, "register-streamed weights are built for f32s");
-    static_assert(!DECONV || (!HEADS && !KSKIP && sizeof(T) == 4), "deconv variant: fp32 / f32s");
+    static_assert(!DECONV || (!HEADS && !KSKIP), "deconv variant: plain epilogue, every K group");
     static_assert(!SPLIT || !KSKIP, "f32s multiplies the zero-padded channels");
     const int par_y = DECONV ? (int)(blockIdx.z >> 1) : 0, par_x = DECONV ? (int)(blockIdx.z & 1) : 0;
     constexpr int NT = WM * WN * 64;  // 4 waves (256 threads) or 8 waves (512 threads)
@@ -1030,7 +1030,10 @@ __device__ __forceinline__ void conv3x3s1_body(const C3Args &a, const C3Heads &h
                         cn_store4_f32s(a.y, (size_t)offs[k], a.out_pitch, n, v);
                     }
                 } else {
-                    c3_store4(reinterpret_cast<T *>(a.y) + (size_t)offs[k] * a.out_pitch + n, v);
+                    if (F16 && a.out_plain)   // fp16 call with CN_CONV_Y_PLAIN: y is plain fp32
+                        c3_store4(reinterpret_cast<float *>(a.y) + (size_t)offs[k] * a.out_pitch + n, v);
+                    else
+                        c3_store4(reinterpret_cast<T *>(a.y) + (size_t)offs[k] * a.out_pitch + n, v);
                 }
             }
         } else if (n < a.Cout) {
@@ -1056,7 +1059,9 @@ __device__ __forceinline__ void conv3x3s1_body(const C3Args &a, const C3Heads &h
                         }
                     } else {
                         if (a.residual) t += (float)reinterpret_cast<const T *>(a.residual)[(size_t)off * a.res_pitch + n + e];
-                        reinterpret_cast<T *>(a.y)[o] = (T)(a.relu ? fmaxf(t, 0.f) : t);
+                        t = a.relu ? fmaxf(t, 0.f) : t;
+                        if (F16 && a.out_plain) reinterpret_cast<float *>(a.y)[o] = t;
+                        else reinterpret_cast<T *>(a.y)[o] = (T)t;
                     }
                 }
             }
@@ -1406,6 +1411,13 @@ int cn_deconv4x4s2_halo(const ConvCall &c, hipStream_t st)
         // (64-wide: the one-tap-ahead schedule keeps three workgroups per CU, 0.092 vs 0.105 ms)
         return wide ? launch_c3<cn_f32s, 32, 64, 2, 2, false, 128, false, true, 2, 1>(a, st)
                     : launch_c3<cn_f32s, 16, 64, 2, 2, false, 128, false, true, 2, 1>(a, st);
+    }
+    if (dtype == CN_DTYPE_F16) {   // the fp32 tile shapes, 64-channel chunks (nobody has tuned these for halves)
+        if (Cout > 64)
+            return wide ? launch_c3<_Float16, 32, 128, 4, 2, false, 128, false, true>(a, st)
+                        : launch_c3<_Float16, 16, 128, 4, 2, false, 128, false, true>(a, st);
+        return wide ? launch_c3<_Float16, 32, 64, 2, 2, false, 128, false, true>(a, st)
+                    : launch_c3<_Float16, 16, 64, 2, 2, false, 128, false, true>(a, st);
     }
     if (Cout > 64)
         return wide ? launch_c3<float, 32, 128, 4, 2, false, 128, false, true>(a, st)

@@ -1,7 +1,7 @@
 // cn_dcn.hip -- the NHWC entry of the modulated deformable convolution (DCNv2): argument checks, the one call
 // description (DcnCall, cn_internal.h), the one route, the switch over its forms, and the two host queries that
 // read the same route.  No kernel lives here: the gather forms are the implicit GEMM's (cn_conv.hip, cn_dcn_gather),
-// the f32s LDS-window forms are cn_dcn2.hip / cn_dcn3.hip / cn_dcn4.hip.
+// the f32s LDS-window forms are cn_dcn2.hip / cn_dcn3.hip / cn_dcn4.hip, the fp16 LDS-window form cn_dcn_h.hip.
 #include "cn_internal.h"
 #include "cn_tuning.h"
 
@@ -94,9 +94,21 @@ DcnPlan dcn_route(const DcnCall &c)
             if (wgs * p.ksplit >= WINDOW_SPLIT_WGS || wgs >= (forced ? 1 : WINDOW_MIN_WGS)) return p;
         }
     }
+    if (c.dtype == CN_DTYPE_F16 && forced != 1 && cn_dcn_half_window_takes(c)) {
+        // fp16 LDS-window form (key 23: 0 = auto, 2 = forced, 1 = gather).  It has no K split: as for the f32s
+        // register-sampling form, grids below WINDOW_MIN_WGS go to the gather form and its tap split unless forced
+        DcnPlan p = {};
+        p.form = DCNH_WINDOW;
+        p.bn = c.Cout > 64 ? 128 : 64;
+        p.grid_x = (unsigned)tiles;
+        p.grid_y = (unsigned)cn_cdiv(c.Cout, p.bn);
+        p.ksplit = 1;
+        if (forced == 2 || tiles * p.grid_y >= WINDOW_MIN_WGS) return p;
+    }
     // the gather form: 64-pixel tiles by 128 / 64 output channels, 128-pixel tiles at <= 32 output channels
     DcnPlan p = {};
-    p.form = (c.Cin & 31) ? DCN_GATHER_PAD : DCN_GATHER;
+    // (_PAD: the last K chunk -- 32 channels, 64 in fp16 mode -- is partial)
+    p.form = (c.Cin & (c.dtype == CN_DTYPE_F16 ? 63 : 31)) ? DCN_GATHER_PAD : DCN_GATHER;
     p.bn = c.Cout > 64 ? 128 : (c.Cout > 32 ? 64 : 32);
     p.grid_x = (unsigned)cn_cdiv(c.B * c.H * c.W, c.Cout > 32 ? 64 : 128);
     p.grid_y = (unsigned)cn_cdiv(c.Cout, p.bn);
@@ -127,18 +139,23 @@ extern "C" size_t cn_dcn_v2_forward_nhwc_workspace_bytes(int B, int Cin, int H, 
     return s > 1 ? (size_t)(s > 8 ? s : 8) * B * H * W * round_up32(Cout) * sizeof(float) : 0;
 }
 
-// the argument checks of the entry and the one place that fills the call description
+// the argument checks of the entries and the one place that fills the call description.  CN_DTYPE_F16 comes from
+// the typed half entries only (cn_dcn_v2_forward_nhwc_f16 / cn_dcn_v2_route_f16, whose x and y are halves): the
+// dtype-generic entries take float pointers and refuse it, as they always have
 static int dcn_fill(DcnCall &c, const float *input_nhwc, const void *weight_packed, const float *bias,
                     const float *offset_mask_nhwc, int om_pitch, const float *scale, const float *shift,
                     void *output_nhwc, int out_pitch, int B, int Cin, int H, int W, int Cout, int mask_sigmoid,
-                    int relu, int dtype, int flags, const cn_f32s_ctl *ctl, void *workspace, size_t workspace_bytes)
+                    int relu, int dtype, int flags, const cn_f32s_ctl *ctl, void *workspace, size_t workspace_bytes,
+                    bool half_entry = false)
 {
     if (!input_nhwc || !weight_packed || !offset_mask_nhwc || !output_nhwc) return CN_ERR_NULL;
     if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || out_pitch < Cout) return CN_ERR_SHAPE;
     if (om_pitch < 27) return CN_ERR_SHAPE;
-    if ((Cin & 3) != 0) return CN_ERR_UNSUPPORTED;
-    const bool f32s = (dtype == CN_DTYPE_F32S);
-    if (dtype != CN_DTYPE_F32 && !f32s) return CN_ERR_UNSUPPORTED;
+    const bool f32s = (dtype == CN_DTYPE_F32S), f16 = (dtype == CN_DTYPE_F16);
+    if (dtype != CN_DTYPE_F32 && !f32s && !(f16 && half_entry)) return CN_ERR_UNSUPPORTED;
+    // every bilinear corner is a 16-byte gather: 4 floats, or 8 halves in fp16 mode (x, w and y are halves there;
+    // offsets / masks, bias, scale and shift stay fp32)
+    if ((Cin & (f16 ? 7 : 3)) != 0) return CN_ERR_UNSUPPORTED;
     if (f32s && !(flags & CN_CONV_Y_PLAIN) && (out_pitch & 31)) return CN_ERR_UNSUPPORTED;
     if (!cn_aligned16(input_nhwc) || !cn_aligned16(weight_packed)) return CN_ERR_ALIGN;
     // f32s tensors are addressed in 128-byte groups of 32 channels
@@ -157,6 +174,9 @@ static int dcn_fill(DcnCall &c, const float *input_nhwc, const void *weight_pack
     return CN_OK;
 }
 
+static void dcn_info(const DcnCall &c, cn_dcn_route_info *info);
+static int dcn_launch(const DcnCall &c, hipStream_t st);
+
 extern "C" int cn_dcn_v2_route(const float *input_nhwc, const void *weight_packed, const float *bias,
                                const float *offset_mask_nhwc, int om_pitch, const float *scale,
                                const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
@@ -172,6 +192,12 @@ extern "C" int cn_dcn_v2_route(const float *input_nhwc, const void *weight_packe
                             out_pitch, B, Cin, H, W, Cout, mask_sigmoid, relu, dtype, flags, nullptr, workspace,
                             workspace_bytes);
     if (rc != CN_OK) return rc;
+    dcn_info(c, info);
+    return CN_OK;
+}
+
+static void dcn_info(const DcnCall &c, cn_dcn_route_info *info)
+{
     const DcnPlan p = dcn_route(c);
     info->form = p.form;
     info->grid_x = (int)p.grid_x;
@@ -179,7 +205,6 @@ extern "C" int cn_dcn_v2_route(const float *input_nhwc, const void *weight_packe
     info->ksplit = p.ksplit;
     info->flags = (p.prefetch ? CN_DCN_FLAG_PREFETCH : 0) | (p.stagger ? CN_DCN_FLAG_STAGGER : 0) |
                   (p.tile2d ? CN_DCN_FLAG_TILE2D : 0) | (p.vec_out ? CN_DCN_FLAG_VEC_OUT : 0);
-    return CN_OK;
 }
 
 extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weight_packed,
@@ -191,15 +216,22 @@ extern "C" int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weigh
                                       size_t workspace_bytes, void *stream)
 {
     DcnCall c;
-    int rc = dcn_fill(c, input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift, output_nhwc,
-                      out_pitch, B, Cin, H, W, Cout, mask_sigmoid, relu, dtype, flags, ctl, workspace, workspace_bytes);
+    const int rc = dcn_fill(c, input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift, output_nhwc,
+                            out_pitch, B, Cin, H, W, Cout, mask_sigmoid, relu, dtype, flags, ctl, workspace, workspace_bytes);
     if (rc != CN_OK) return rc;
+    return dcn_launch(c, (hipStream_t)stream);
+}
+
+// route the call and run its form (and the reduce launch behind a split)
+static int dcn_launch(const DcnCall &c, hipStream_t st)
+{
     const DcnPlan p = dcn_route(c);
-    hipStream_t st = (hipStream_t)stream;
+    int rc;
     switch (p.form) {
     case DCN_WIDE4: case DCN_WIDE8: rc = cn_dcn_wide_f32s(c, p, st); break;
     case DCN_TEAM_T: case DCN_TEAM_N: rc = cn_dcn_team_f32s(c, p, st); break;
     case DCN_WINDOW: rc = cn_dcn_window_f32s(c, p, st); break;
+    case DCNH_WINDOW: rc = cn_dcn_window_f16(c, p, st); break;
     default: rc = cn_dcn_gather(c, p, st); break;
     }
     if (rc != CN_OK || p.ksplit == 1) return rc;
@@ -217,4 +249,37 @@ extern "C" int cn_dcn_v2_forward_nhwc_f32(const float *input_nhwc, const float *
     return cn_dcn_v2_forward_nhwc(input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale,
                                   shift, output_nhwc, Cout, B, Cin, H, W, Cout, mask_sigmoid, relu,
                                   CN_DTYPE_F32, 0, nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---- fp16 compute mode: x, the packed weight (cn_pack_conv_weight(..., CN_DTYPE_F16)) and y are halves; offsets /
+// masks, bias, scale and shift fp32.  The same call description, route and forms as above with dtype = CN_DTYPE_F16.
+extern "C" int cn_dcn_v2_forward_nhwc_f16(const void *input_nhwc, const void *weight_packed, const float *bias,
+                                          const float *offset_mask_nhwc, int om_pitch, const float *scale,
+                                          const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
+                                          int H, int W, int Cout, int mask_sigmoid, int relu, void *workspace,
+                                          size_t workspace_bytes, void *stream)
+{
+    DcnCall c;
+    const int rc = dcn_fill(c, (const float *)input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift,
+                            output_nhwc, out_pitch, B, Cin, H, W, Cout, mask_sigmoid, relu, CN_DTYPE_F16, 0, nullptr,
+                            workspace, workspace_bytes, true);
+    if (rc != CN_OK) return rc;
+    return dcn_launch(c, (hipStream_t)stream);
+}
+
+extern "C" int cn_dcn_v2_route_f16(const void *input_nhwc, const void *weight_packed, const float *bias,
+                                   const float *offset_mask_nhwc, int om_pitch, const float *scale,
+                                   const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
+                                   int H, int W, int Cout, int mask_sigmoid, int relu, void *workspace,
+                                   size_t workspace_bytes, void *stream, cn_dcn_route_info *info)
+{
+    (void)stream;
+    if (!info) return CN_ERR_NULL;
+    DcnCall c;
+    const int rc = dcn_fill(c, (const float *)input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift,
+                            output_nhwc, out_pitch, B, Cin, H, W, Cout, mask_sigmoid, relu, CN_DTYPE_F16, 0, nullptr,
+                            workspace, workspace_bytes, true);
+    if (rc != CN_OK) return rc;
+    dcn_info(c, info);
+    return CN_OK;
 }

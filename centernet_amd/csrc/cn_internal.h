@@ -40,7 +40,7 @@ int cn_stem_conv_f32(const ConvCall &c, int persistent, hipStream_t st);
 // gather of the implicit GEMM (cn_conv.hip, every dtype) and the three f32s LDS-window forms (cn_dcn2.hip
 // register-sampling window, cn_dcn3.hip team, cn_dcn4.hip wide; what those share is in cn_dcn_window.h)
 struct DcnCall {
-    const float *x;            // (B, H, W, Cin) plain fp32
+    const float *x;            // (B, H, W, Cin) plain fp32; CN_DTYPE_F16 (the _f16 entries): the pointer addresses halves
     const void *w;             // packed weights of `dtype` (f32s: row form + fragment copy)
     const float *bias, *om;    // om: (B, H, W, om_pitch): 18 offsets + 9 masks per pixel
     int om_pitch;
@@ -48,7 +48,7 @@ struct DcnCall {
     void *y;
     int out_pitch, out_plain;
     int B, Cin, H, W, Cout, mask_sigmoid, relu;
-    int dtype;                 // CN_DTYPE_F32 / CN_DTYPE_F32S
+    int dtype;                 // CN_DTYPE_F32 / CN_DTYPE_F32S / CN_DTYPE_F16
     float x_mul;               // cn_f32s_ctl resolved: f32s input exponent (a power of two, 1 without a ctl)
     uint32_t *range;           // ... and the range words of the launch, or null
     int dbg;                   // cn_set_tuning key 9
@@ -57,7 +57,8 @@ struct DcnCall {
 };
 // the values of cn_dcn_route_info::form (include/centernet_amd.h)
 enum { DCN_GATHER = CN_DCN_GATHER, DCN_GATHER_PAD = CN_DCN_GATHER_PAD, DCN_WINDOW = CN_DCN_WINDOW,
-       DCN_TEAM_T = CN_DCN_TEAM_T, DCN_TEAM_N = CN_DCN_TEAM_N, DCN_WIDE4 = CN_DCN_WIDE4, DCN_WIDE8 = CN_DCN_WIDE8 };
+       DCN_TEAM_T = CN_DCN_TEAM_T, DCN_TEAM_N = CN_DCN_TEAM_N, DCN_WIDE4 = CN_DCN_WIDE4, DCN_WIDE8 = CN_DCN_WIDE8,
+       DCNH_WINDOW = CN_DCNH_WINDOW };
 struct DcnPlan {
     int form;                  // DCN_*
     int bn;                    // output channels per block
@@ -76,6 +77,9 @@ bool cn_dcn_wide_takes(const DcnCall &c);
 int cn_dcn_window_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st);
 int cn_dcn_team_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st);
 int cn_dcn_wide_f32s(const DcnCall &c, const DcnPlan &p, hipStream_t st);
+// cn_dcn_h.hip: the fp16 LDS-window form (CN_DTYPE_F16 calls only; never split: p.ksplit == 1)
+bool cn_dcn_half_window_takes(const DcnCall &c);
+int cn_dcn_window_f16(const DcnCall &c, const DcnPlan &p, hipStream_t st);
 // cn_conv.hip, bound to igemm_kernel: the gather forms, and the second stage of every form's split
 int cn_dcn_gather(const DcnCall &c, const DcnPlan &p, hipStream_t st);
 int cn_dcn_reduce(const DcnCall &c, int ksplit, hipStream_t st);

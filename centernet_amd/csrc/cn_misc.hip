@@ -125,6 +125,41 @@ __global__ void maxpool_nhwc_f32s_kernel(const void *__restrict__ x, void *__res
     cn_rng_commit(range, 0, rng);
 }
 
+// half NHWC in (pixel pitch in_pitch), half NHWC out (pixel pitch out_pitch), 8 channels (16 bytes) per lane.
+// max of halves is exact, so the compare runs on the halves themselves; -inf padding as above.
+typedef _Float16 mp_f16x8 __attribute__((ext_vector_type(8)));
+__global__ void maxpool_nhwc_f16_kernel(const _Float16 *__restrict__ x, _Float16 *__restrict__ y, int B, int H,
+                                        int W, int C, int in_pitch, int out_pitch, int Ho, int Wo, int k,
+                                        int s, int pad)
+{
+    const int c8n = C >> 3;
+    const size_t total = (size_t)B * Ho * Wo * c8n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const int c8 = (int)(i % c8n);
+        size_t r = i / c8n;
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        const _Float16 ninf = (_Float16)(-__builtin_huge_valf());
+        mp_f16x8 m = {ninf, ninf, ninf, ninf, ninf, ninf, ninf, ninf};
+        for (int dy = 0; dy < k; ++dy) {
+            const int iy = oy * s - pad + dy;
+            if (iy < 0 || iy >= H) continue;
+            for (int dx = 0; dx < k; ++dx) {
+                const int ix = ox * s - pad + dx;
+                if (ix < 0 || ix >= W) continue;
+                const mp_f16x8 v = *reinterpret_cast<const mp_f16x8 *>(
+                    x + (((size_t)b * H + iy) * W + ix) * in_pitch + c8 * 8);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) m[e] = v[e] > m[e] ? v[e] : m[e];
+            }
+        }
+        *reinterpret_cast<mp_f16x8 *>(y + (((size_t)b * Ho + oy) * Wo + ox) * out_pitch + c8 * 8) = m;
+    }
+}
+
 // offset (B,18,HW) + mask (B,9,HW) NCHW -> om (B,HW,32) NHWC
 __global__ void pack_offset_mask_kernel(const float *__restrict__ offset,
                                         const float *__restrict__ mask, float *__restrict__ om,
@@ -335,6 +370,24 @@ extern "C" int cn_maxpool_nhwc_f32s(const void *x, void *y, int B, int H, int W,
     const size_t total = (size_t)B * Ho * Wo * (C >> 2);
     hipLaunchKernelGGL(maxpool_nhwc_f32s_kernel, dim3(blocks_for(total, 256, 65535)), dim3(256), 0,
                        (hipStream_t)stream, x, y, B, H, W, C, in_pitch, out_pitch, Ho, Wo, k, s, pad, mul, range);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_maxpool_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, int in_pitch,
+                                   int out_pitch, int k, int s, int pad, void *stream)
+{
+    if (!x || !y) return CN_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || s <= 0 || pad < 0 || in_pitch < C || out_pitch < C)
+        return CN_ERR_SHAPE;
+    if ((C & 7) || (in_pitch & 7) || (out_pitch & 7)) return CN_ERR_UNSUPPORTED;   // whole 16-byte groups of halves
+    if (!cn_aligned16(x) || !cn_aligned16(y)) return CN_ERR_ALIGN;
+    const int Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
+    if (Ho <= 0 || Wo <= 0) return CN_ERR_SHAPE;
+    const size_t total = (size_t)B * Ho * Wo * (C >> 3);
+    hipLaunchKernelGGL(maxpool_nhwc_f16_kernel, dim3(blocks_for(total, 256, 65535)), dim3(256), 0,
+                       (hipStream_t)stream, (const _Float16 *)x, (_Float16 *)y, B, H, W, C, in_pitch, out_pitch,
+                       Ho, Wo, k, s, pad);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

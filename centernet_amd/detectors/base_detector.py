@@ -61,6 +61,8 @@ class BaseDetector(object):
         self.model = net.to(opt.device).eval()
         if getattr(opt, 'fp32_mfma', False):
             self.model.fp32_mfma()
+        if getattr(opt, 'fp16', False):
+            self.model.half_compute()
         self.opt = opt
         self.mean = np.asarray(opt.mean, np.float32).reshape(1, 1, 3)
         self.std = np.asarray(opt.std, np.float32).reshape(1, 1, 3)

@@ -355,7 +355,8 @@ class PlanBuilder:
             # zero-filled once: the pad channels of the last group are read as K by the next layer
             t = torch.zeros((B, H, W, pitch), device=self.device, dtype=torch.float32)
         else:
-            t = torch.empty((B, H, W, pitch), device=self.device, dtype=self.dtype)
+            t = torch.empty((B, H, W, pitch), device=self.device,
+                            dtype=torch.float16 if fmt == "f16" else torch.float32)
         return Act(t, B, H, W, C, pitch, fmt=fmt, exp=self._exp(lid), lid=lid)
 
     def plain(self, x):
@@ -556,6 +557,8 @@ class PlanBuilder:
             out.lid, out.exp = lid, self._exp(lid)
         if use_s and out.fmt != "f32s":
             flags |= CONV_Y_PLAIN
+        if cd == DTYPE_F16 and not out.nchw and out.fmt == "f32":
+            flags |= CONV_Y_PLAIN       # a half plan's fp32 consumer (the offsets of the deformable kernel)
         assert use_s or stem_s or out.fmt != "f32s"
         res_pitch = 0
         if residual is not None and residual.pitch != out.pitch:
@@ -644,10 +647,10 @@ class PlanBuilder:
         2x2 convolutions in one launch (reference: resnet_dcn.py:228-235)."""
         ci, co, kh, kw = weight.shape
         assert (kh, kw) == (4, 4) and ci == x.C
-        assert self.dtype == torch.float32, "ConvTranspose is built for fp32 only"
         lib = self.lib
         lid = self._lid()
         use_s = self.split
+        half = self.dtype == torch.float16     # halves in, halves out (``out_plain`` only concerns f32s plans)
         scale, shift = fold_bn(None, bn, co, self.device)
         cacheable = isinstance(weight, torch.nn.Parameter)
         key = self._wkey("deconv4x4s2_f32s" if use_s else "deconv4x4s2", [weight])
@@ -662,7 +665,7 @@ class PlanBuilder:
             wp = torch.empty(lib.cn_packed_deconv4x4s2_weight_floats(ci, co), device=self.device,
                              dtype=torch.float32)
             native.check(lib.cn_pack_deconv4x4s2_weight(native.ptr(w), native.ptr(wp), ci, co,
-                                                        DTYPE_F32S if use_s else DTYPE_F32,
+                                                        DTYPE_F32S if use_s else self.cdtype,
                                                         native.stream_ptr()),
                          "cn_pack_deconv4x4s2_weight")
             ev = torch.cuda.Event()
@@ -689,7 +692,7 @@ class PlanBuilder:
             ctl = self._ctl(lid, _pow2(-x.exp) if x.fmt == "f32" else 1.0)
         self.keep += [scale, shift, wp, factor]
         sp, hp, wpp = native.ptr(scale), native.ptr(shift), native.ptr(wp)
-        cd = DTYPE_F32S if use_s else DTYPE_F32
+        cd = DTYPE_F32S if use_s else self.cdtype
         cref = ctypes.byref(ctl) if ctl is not None else None
 
         def run():
@@ -700,7 +703,7 @@ class PlanBuilder:
                 native.check(rc, "cn_conv_transpose4x4s2")
         self.ops.append(run)
         fl = 2 * x.B * (2 * x.H) * (2 * x.W) * co * ci * 4
-        by = 4 * (x.B * x.H * x.W * (ci + 4 * co) + co * ci * 16)
+        by = (2 if half else 4) * (x.B * x.H * x.W * (ci + 4 * co) + co * ci * 16)
         self.meta.append(dict(kind="conv", flops=fl, bytes=by))
         self.trace.append(("deconv", out))
         self.flops += fl
@@ -710,11 +713,22 @@ class PlanBuilder:
         """MaxPool2d.  ``to_s`` / ``out``: an f32s input of whole groups stays f32s -- written into
         ``out`` when given (a channel slice of a concatenation buffer) -- so that its consumers (a
         projection, a Root's concatenation: pose_dla_dcn.py:206-221) read (high, low) pairs."""
-        assert self.dtype == torch.float32, "max-pool is built for fp32 only"
         lid = self._lid(lid)
         lib = self.lib
         from_s = x.fmt == "f32s" and x.C % 32 == 0     # read (high, low) pairs
         Ho, Wo = _out_size(x.H, k, s, pad), _out_size(x.W, k, s, pad)
+        if self.dtype == torch.float16:
+            # half plan: halves in, halves out, always a launch of its own
+            assert x.fmt == "f16" and out is None and not to_s
+            pooled = self._new(x.B, Ho, Wo, x.C, lid=lid)
+
+            def run():
+                rc = lib.cn_maxpool_nhwc_f16(x.ptr(), pooled.ptr(), x.B, x.H, x.W, x.C, x.pitch, pooled.pitch,
+                                             k, s, pad, native.stream_ptr())
+                if rc:
+                    native.check(rc, "cn_maxpool_nhwc_f16")
+            self._emit_simple(run, "maxpool", pooled, 2 * x.B * x.C * (x.H * x.W + Ho * Wo))
+            return pooled
         if from_s and (to_s or (out is not None and out.fmt == "f32s")):
             if out is None:
                 out = self._new(x.B, Ho, Wo, x.C, fmt="f32s", lid=lid)
@@ -893,13 +907,14 @@ class PlanBuilder:
         assert tuple(dcn_mod.kernel_size) == (3, 3) and dcn_mod.stride == 1 and \
             dcn_mod.padding == 1 and dcn_mod.dilation == 1 and dcn_mod.deformable_groups == 1, \
             "only the 3x3/s1/p1/d1/dg1 DCN that CenterNet instantiates is supported"
-        assert self.dtype == torch.float32, "the deformable kernel is fp32 only"
+        half = self.dtype == torch.float16     # halves in, halves out (``out_plain`` only concerns f32s plans)
         lid = self._lid()
         com = dcn_mod.conv_offset_mask
-        # plain fp32 in REAL units (offsets are pixels, the mask a logit): never an f32s tensor
+        # plain fp32 in REAL units (offsets are pixels, the mask a logit): never an f32s tensor, and in a
+        # half plan not halves either (the offset convolution reads the half activation and stores fp32)
         x = self.plain(x)
         if om is None:
-            om = self._new(x.B, x.H, x.W, 27, pitch=32, lid=lid + "/om")
+            om = self._new(x.B, x.H, x.W, 27, pitch=32, fmt="f32", lid=lid + "/om")
             self.conv(x, com.weight, bias=com.bias, stride=1, padding=1, out=om, lid=lid + "/om")
         assert om.fmt == "f32" and om.pitch >= 27 and (om.B, om.H, om.W) == (x.B, x.H, x.W)
         msig = int(bool(mask_sigmoid))
@@ -923,9 +938,9 @@ class PlanBuilder:
             wp = self._pack(dcn_mod.weight)
         self.keep += [bias, scale, shift]
         lib = self.lib
-        assert x.pitch == x.C and x.c_off == 0 and x.fmt == "f32"
+        assert x.pitch == x.C and x.c_off == 0 and x.fmt == ("f16" if half else "f32")
         bp, sp, hp, wpp = native.ptr(bias), native.ptr(scale), native.ptr(shift), native.ptr(wp)
-        cd = DTYPE_F32S if use_s else DTYPE_F32
+        cd = DTYPE_F32S if use_s else self.cdtype
         flags = CONV_Y_PLAIN if (use_s and out_plain) else 0
         cref = ctypes.byref(ctl) if ctl is not None else None
 
@@ -933,23 +948,27 @@ class PlanBuilder:
 
         def call(fn, *more):
             wsp = ctypes.c_void_p(self.ws.data_ptr()) if self.ws is not None else None
+            mode = () if half else (cd, flags, cref)     # the typed half entries take no dtype, flags or ctl
             return fn(x.ptr(), wpp, bp, om.ptr(), om.pitch, sp, hp, out.ptr(), out.pitch, x.B, ci, x.H, x.W, co,
-                      msig, int(relu), cd, flags, cref, wsp, self.ws_bytes, native.stream_ptr(), *more)
+                      msig, int(relu), *mode, wsp, self.ws_bytes, native.stream_ptr(), *more)
 
         def run():
-            rc = call(lib.cn_dcn_v2_forward_nhwc)
+            rc = call(lib.cn_dcn_v2_forward_nhwc_f16 if half else lib.cn_dcn_v2_forward_nhwc)
             if rc:
                 native.check(rc, "cn_dcn_v2_forward_nhwc")
 
         def route():
             """the kernel form, grid and K split the launch gets (cn_dcn_v2_route: host only)"""
             info = native.DcnRouteInfo()
-            native.check(call(lib.cn_dcn_v2_route, ctypes.byref(info)), "cn_dcn_v2_route")
+            native.check(call(lib.cn_dcn_v2_route_f16 if half else lib.cn_dcn_v2_route, ctypes.byref(info)),
+                         "cn_dcn_v2_route")
             return info
         self.ops.append(run)
         fl = 2 * x.B * x.H * x.W * co * ci * 9
         # SURVEY.md 8(d): activations 4*(Cin + 27 + Cout)*HW per image + weights once per launch
         by = 4 * (x.B * x.H * x.W * (ci + 27 + co) + co * ci * 9 + co)
+        if half:    # half activations and weights; offsets / masks and the bias stay fp32
+            by = 2 * (x.B * x.H * x.W * (ci + co) + co * ci * 9) + 4 * (x.B * x.H * x.W * 27 + co)
         self.meta.append(dict(kind="dcn", flops=fl, bytes=by, samples=x.B * x.H * x.W * 9 * ci, route=route))
         self.trace.append(("dcn", out))
         self.flops += fl
@@ -1451,7 +1470,7 @@ class PlannedModule(torch.nn.Module):
     def describe(self, pb, x):  # pragma: no cover - interface
         raise NotImplementedError
 
-    compute_dtype = torch.float32   # set to torch.float16 with .half_compute() (hourglass)
+    compute_dtype = torch.float32   # set to torch.float16 with .half_compute()
     f32s = None                     # None: default (on unless CN_F32S=0); see .fp32_mfma()
 
     def fp32_mfma(self, enable=True):
@@ -1462,8 +1481,11 @@ class PlannedModule(torch.nn.Module):
         return self
 
     def half_compute(self, enable=True):
-        """fp16 activations/weights with fp32 accumulation (BASELINE configs[4]); parameters
-        stay fp32 in the module, only the packed plan copies are fp16."""
+        """fp16 activations/weights with fp32 accumulation; parameters stay fp32 in the module, only the
+        packed plan copies are fp16.  Plans Hourglass (BASELINE configs[4]), ``res_18/34/50/101/152`` and
+        ``resdcn_18/34/50/101/152`` end to end: the deformable layers read half activations with fp32
+        offsets / masks, the heads stay fp32 NCHW and nothing is deferred.  ``dla_34`` (depthwise
+        transposed convolution, tree concatenation) has no half form and fails while its plan is built."""
         self.compute_dtype = torch.float16 if enable else torch.float32
         self.drop_plans()
         return self

@@ -39,8 +39,15 @@ DECODE_DDD_RAW_DEPTH = 16384    # CN_DECODE_DDD_RAW_DEPTH: cn_ddd_decode_f32 tra
 EXCT_CLAMP_ONE = 2          # CN_EXCT_CLAMP_ONE (cn_exct_decode_f32): clamp the peak-tested edge maps to 1
 # forms and flags of cn_dcn_v2_route: the #defines CN_<name> of the header (tests/test_dcn_route_host.py compares them)
 DCN_GATHER, DCN_GATHER_PAD, DCN_WINDOW, DCN_TEAM_T, DCN_TEAM_N, DCN_WIDE4, DCN_WIDE8 = range(7)
+DCNH_WINDOW = 7      # CN_DCNH_WINDOW: the LDS-window form of DTYPE_F16 calls
 DCN_FLAG_PREFETCH, DCN_FLAG_STAGGER, DCN_FLAG_TILE2D, DCN_FLAG_VEC_OUT = 1, 2, 4, 8
 DCN_FORM_NAMES = ("gather", "gather_pad", "window", "team_t", "team_n", "wide4", "wide8")
+
+
+def dcn_form_name(form):
+    """Readable name of cn_dcn_route_info.form, the fp16 forms included."""
+    return "window_f16" if form == DCNH_WINDOW else DCN_FORM_NAMES[form]
+
 
 # cn_image_desc, one image of a mixed-size batch (cn_warp_normalize_u8_f32_ragged / cn_resize_bilinear_u8_ragged)
 IMAGE_DESC = np.dtype([("offset", np.uint64), ("H", np.int32), ("W", np.int32), ("pitch", np.int32),
@@ -158,12 +165,18 @@ def _declare(lib):
     lib.cn_calib_latency.argtypes = [vp, ctypes.c_uint32, i, vp, vp, vp]
     lib.cn_maxpool_nhwc_f32s.restype = i
     lib.cn_maxpool_nhwc_f32s.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, f, vp, vp]
+    lib.cn_maxpool_nhwc_f16.restype = i
+    lib.cn_maxpool_nhwc_f16.argtypes = [vp, vp, i, i, i, i, i, i, i, i, i, vp]
     lib.cn_maxpool_nhwc_scaled.restype = i
     lib.cn_maxpool_nhwc_scaled.argtypes = [vp, vp, i, i, i, i, i, i, i, i, f, vp]
     lib.cn_dcn_v2_forward_nhwc.restype = i
     lib.cn_dcn_v2_forward_nhwc.argtypes = [vp, vp, vp, vp, i, vp, vp, vp] + [i] * 10 + [ctl, vp, sz, vp]
     lib.cn_dcn_v2_route.restype = i
     lib.cn_dcn_v2_route.argtypes = lib.cn_dcn_v2_forward_nhwc.argtypes + [ctypes.POINTER(DcnRouteInfo)]
+    lib.cn_dcn_v2_forward_nhwc_f16.restype = i
+    lib.cn_dcn_v2_forward_nhwc_f16.argtypes = [vp, vp, vp, vp, i, vp, vp, vp] + [i] * 8 + [vp, sz, vp]
+    lib.cn_dcn_v2_route_f16.restype = i
+    lib.cn_dcn_v2_route_f16.argtypes = lib.cn_dcn_v2_forward_nhwc_f16.argtypes + [ctypes.POINTER(DcnRouteInfo)]
     lib.cn_pack_deconv4x4s2_weight.restype = i
     lib.cn_pack_deconv4x4s2_weight.argtypes = [vp, vp, i, i, i, vp]
     lib.cn_conv_transpose4x4s2.restype = i

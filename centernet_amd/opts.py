@@ -40,6 +40,9 @@ _FLAGS = [
     # new: compute on the plain fp32 matrix instruction instead of f32s (three fp16 MFMAs per
     # product on range-controlled fp16 pairs) -- the A/B reference mode
     ("--fp32_mfma", dict(action="store_true")),
+    # new: fp16 activations and weights with fp32 accumulation (PlannedModule.half_compute): hourglass,
+    # res_N and resdcn_N; not together with --fp32_mfma
+    ("--fp16", dict(action="store_true")),
     ("--shift", dict(type=float, default=0.1)), ("--scale", dict(type=float, default=0.4)),
     ("--rotate", dict(type=float, default=0)), ("--flip", dict(type=float, default=0.5)),
     ("--no_color_aug", dict(action="store_true")), ("--aug_rot", dict(type=float, default=0)),
@@ -97,6 +100,8 @@ class opts(object):
         argv = _sys.argv[1:] if args == '' else list(args)
         if opt.task == 'exdet' and not any(a == '--K' or str(a).startswith('--K=') for a in argv):
             opt.K = 40
+        if opt.fp16 and opt.fp32_mfma:
+            self.parser.error("--fp16 and --fp32_mfma both choose the compute mode: give one of them")
         opt.gpus_str = opt.gpus
         opt.gpus = [int(g) for g in opt.gpus.split(',')]
         opt.gpus = [i for i in range(len(opt.gpus))] if opt.gpus[0] >= 0 else [-1]

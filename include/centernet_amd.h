@@ -41,9 +41,11 @@ typedef enum cn_status {
 #define CN_LAYOUT_NCHW 0
 #define CN_LAYOUT_NHWC 1
 
-/* Element type of activations / packed weights.  fp32 is the parity path; fp16 (fp32
- * accumulate, v_mfma_f32_32x32x16_f16) exists for BASELINE configs[4] (Hourglass-104 fp16),
- * a surface the reference does not have. */
+/* Element type of activations / packed weights.  fp32 is the parity path; fp16 (half activations and
+ * weights, fp32 accumulate on v_mfma_f32_32x32x16_f16, fp32 epilogue) is a compute mode the reference
+ * does not have: it runs Hourglass-104 (BASELINE configs[4]) and the ResNet nets (res_N, resdcn_N) --
+ * every convolution form, the deformable convolution (gather forms), ConvTranspose 4x4/s2 and the
+ * max-pool take it.  Offsets / masks of the deformable convolution, bias, scale and shift stay fp32. */
 #define CN_DTYPE_F32 0
 #define CN_DTYPE_F16 1
 /* fp32 values stored as fp16 (high, low) pairs, 32-channel groups of 128 bytes; computed
@@ -251,10 +253,12 @@ int cn_dcn_v2_forward_f32(const float *input, const float *weight, const float *
  * too small workspace the layer runs unsplit (same result up to fp32 summation order).
  */
 size_t cn_dcn_v2_forward_nhwc_workspace_bytes(int B, int Cin, int H, int W, int Cout);
-/* dtype-generic form: the input stays a PLAIN fp32 NHWC tensor in every mode (one 16-byte gather
- * per bilinear corner); dtype = CN_DTYPE_F32S takes an f32s-packed weight, contracts on the
+/* dtype-generic form: the input stays a PLAIN fp32 NHWC tensor in the fp32 and f32s modes (one 16-byte
+ * gather per bilinear corner); dtype = CN_DTYPE_F32S takes an f32s-packed weight, contracts on the
  * fp16 matrix instruction (the blended sample is split as it enters the LDS A tile) and writes
- * y as f32s (pitch % 32 == 0) or, with CN_CONV_Y_PLAIN, as plain fp32. */
+ * y as f32s (pitch % 32 == 0) or, with CN_CONV_Y_PLAIN, as plain fp32.
+ * dtype = CN_DTYPE_F16 is refused here (CN_ERR_UNSUPPORTED, as it always was: these pointers address
+ * floats): half tensors go through cn_dcn_v2_forward_nhwc_f16 / cn_dcn_v2_route_f16 below. */
 int cn_dcn_v2_forward_nhwc(const float *input_nhwc, const void *weight_packed, const float *bias,
                            const float *offset_mask_nhwc, int om_pitch, const float *scale,
                            const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
@@ -272,12 +276,14 @@ int cn_dcn_v2_forward_nhwc_f32(const float *input_nhwc, const float *weight_pack
  * (stream is ignored).  Returns what the call would return from its argument checks; *info is written only
  * with CN_OK. */
 #define CN_DCN_GATHER 0      /* global gather on the implicit GEMM */
-#define CN_DCN_GATHER_PAD 1  /* ... for Cin % 32 != 0 */
+#define CN_DCN_GATHER_PAD 1  /* ... for Cin % 32 != 0 (CN_DTYPE_F16: Cin % 64 != 0) */
 #define CN_DCN_WINDOW 2      /* f32s LDS-window forms: register sampling (cn_dcn2.hip) */
 #define CN_DCN_TEAM_T 3      /* team form (cn_dcn3.hip), the teams split the K steps of a 64-channel block */
 #define CN_DCN_TEAM_N 4      /* ... the teams split a 128-channel block */
 #define CN_DCN_WIDE4 5       /* wide form (cn_dcn4.hip), four 32-channel blocks per workgroup */
 #define CN_DCN_WIDE8 6       /* ... eight */
+/* the form of CN_DTYPE_F16 calls only, numbered behind the forms above */
+#define CN_DCNH_WINDOW 7     /* fp16 LDS-window form: register sampling of halves (cn_dcn_h.hip) */
 #define CN_DCN_FLAG_PREFETCH 1  /* wide: L2 prefetch of the weights */
 #define CN_DCN_FLAG_STAGGER 2   /* team: the second occupant of a CU starts late */
 #define CN_DCN_FLAG_TILE2D 4    /* gather: tiles are pixel blocks */
@@ -294,6 +300,26 @@ int cn_dcn_v2_route(const float *input_nhwc, const void *weight_packed, const fl
                     int H, int W, int Cout, int mask_sigmoid, int relu, int dtype, int flags,
                     const cn_f32s_ctl *ctl, void *workspace, size_t workspace_bytes,
                     void *stream, cn_dcn_route_info *info);
+
+/* fp16 compute mode of the deformable convolution: input_nhwc is a HALF NHWC tensor (B, H, W, Cin) with
+ * Cin % 8 == 0 (a bilinear corner is a 16-byte gather of 8 halves, else CN_ERR_UNSUPPORTED), the weight is
+ * cn_pack_conv_weight(..., CN_DTYPE_F16)'s (64-channel K chunks), y a half NHWC tensor at out_pitch.
+ * offset_mask_nhwc (pitch >= 27, real units), bias, scale and shift stay fp32; mask_sigmoid, relu, the
+ * epilogue order, the alignment checks and the workspace (cn_dcn_v2_forward_nhwc_workspace_bytes: fp32 slabs of
+ * the gather form's tap split) are those of cn_dcn_v2_forward_nhwc.  The four corners are read as halves,
+ * blended and multiplied by the mask in fp32, rounded ONCE to fp16 into the matrix operand, accumulated in
+ * fp32; the epilogue is fp32 with one rounding at the store.  cn_dcn_v2_route_f16 is the host query of the
+ * same call (forms CN_DCN_GATHER, CN_DCN_GATHER_PAD, CN_DCNH_WINDOW). */
+int cn_dcn_v2_forward_nhwc_f16(const void *input_nhwc, const void *weight_packed, const float *bias,
+                               const float *offset_mask_nhwc, int om_pitch, const float *scale,
+                               const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
+                               int H, int W, int Cout, int mask_sigmoid, int relu, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int cn_dcn_v2_route_f16(const void *input_nhwc, const void *weight_packed, const float *bias,
+                        const float *offset_mask_nhwc, int om_pitch, const float *scale,
+                        const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
+                        int H, int W, int Cout, int mask_sigmoid, int relu, void *workspace,
+                        size_t workspace_bytes, void *stream, cn_dcn_route_info *info);
 
 /* Plain fp32 NHWC <-> f32s NHWC (CN_DTYPE_F32S: fp16 high / low pairs in 128-byte groups of 32
  * channels).  Pitches in channels; f32s pitches are multiples of 32; channels of the last
@@ -404,8 +430,11 @@ typedef struct cn_conv_desc {
 } cn_conv_desc;
 /* 1 when cn_conv2d honours d->res_pitch != d->out_pitch for this descriptor (host-only) */
 int cn_conv2d_res_pitch_supported(const cn_conv_desc *d);
-/* dtype = CN_DTYPE_F32S only: x (and the residual) / y are plain fp32 NHWC tensors; the kernel
- * converts while staging / storing (e.g. the offset maps the deformable kernel reads). */
+/* dtype = CN_DTYPE_F32S: x (and the residual) / y are plain fp32 NHWC tensors; the kernel
+ * converts while staging / storing (e.g. the offset maps the deformable kernel reads).
+ * dtype = CN_DTYPE_F16 takes CN_CONV_Y_PLAIN alone: y is a plain fp32 NHWC tensor (out_pitch in floats,
+ * the epilogue stores fp32 without rounding to half) -- the offset / mask convolution of a half plan.
+ * x, w and the residual stay halves. */
 #define CN_CONV_X_PLAIN 1
 #define CN_CONV_Y_PLAIN 2
 #define CN_CONV_R_PLAIN 4
@@ -463,7 +492,10 @@ int cn_conv2d(const cn_conv_desc *desc, const void *x, const void *w_packed, con
  * x (B,H,W,in_pitch) NHWC -> y (B,2H,2W,out_pitch) NHWC.
  * ------------------------------------------------------------------------ */
 size_t cn_packed_deconv4x4s2_weight_floats(int Cin, int Cout);
-/* dtype-generic forms (CN_DTYPE_F32 / CN_DTYPE_F32S; `flags`: CN_CONV_X_PLAIN / CN_CONV_Y_PLAIN) */
+/* dtype-generic forms (CN_DTYPE_F32 / CN_DTYPE_F32S; `flags`: CN_CONV_X_PLAIN / CN_CONV_Y_PLAIN).
+ * CN_DTYPE_F16: half NHWC in and out (Cin % 8 == 0, in_pitch % 8 == 0, flags 0), fp32 scale / shift; the
+ * packed weight is [parity 4][tap 4][Cout_pad32][Cin_pad64] halves and fits a buffer of
+ * cn_packed_deconv4x4s2_weight_floats() floats like every other dtype's. */
 int cn_pack_deconv4x4s2_weight(const float *w_iohw, void *w_packed, int Cin, int Cout, int dtype,
                                void *stream);
 int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, const float *scale,
@@ -495,6 +527,11 @@ int cn_maxpool_nhwc_scaled(const void *x_nhwc, float *y_nhwc, int B, int H, int 
  * side 0 receives max |y| */
 int cn_maxpool_nhwc_f32s(const void *x, void *y, int B, int H, int W, int C, int in_pitch, int out_pitch,
                          int k, int s, int pad, float mul, uint32_t *range, void *stream);
+
+/* half NHWC in (pixel pitch in_pitch), half NHWC out (pixel pitch out_pitch): general k / s / pad with -inf
+ * padding as above; C, in_pitch and out_pitch multiples of 8 (16 bytes of halves per lane) */
+int cn_maxpool_nhwc_f16(const void *x, void *y, int B, int H, int W, int C, int in_pitch, int out_pitch,
+                        int k, int s, int pad, void *stream);
 
 /* Depthwise ConvTranspose2d(C, C, kernel 2f, stride f, padding f/2, groups=C, bias=False)
  * -- the up-sampling of IDAUp (pose_dla_dcn.py:370-373) -- fused with the element-wise

@@ -18,5 +18,5 @@ for i, ((kind, act), meta) in enumerate(zip(plan.b.trace, plan.b.meta)):
     how = ""
     if kind == "dcn":   # the form and K split of the deformable launch, from the library's route query
         r = meta["route"]()
-        how = "  %s grid %d x %d x %d" % (native.DCN_FORM_NAMES[r.form], r.grid_x, r.grid_y, r.ksplit)
+        how = "  %s grid %d x %d x %d" % (native.dcn_form_name(r.form), r.grid_x, r.grid_y, r.ksplit)
     print("%3d %-9s -> (%d,%d,%d) pitch %d %s%s%s" % (i, kind, act.H, act.W, act.C, act.pitch, act.fmt, " nchw" if act.nchw else "", how))
