@@ -1204,9 +1204,9 @@ static IgemmArgs igemm_args(const ConvCall &c, const cn_conv_desc *d)
 }
 
 // ---- routing: which kernel runs a cn_conv2d call.  Decided here and nowhere else: cn_conv2d switches on
-// the answer, the four queries below read it.  Order: stem + max-pool, stem, cn_conv16 (fp32 / f32s),
+// the answer, the four queries below read it.  Order: stem + max-pool, stem, cn_conv16 (fp32 / f32s / half),
 // cn_offconv, LDS-halo 3x3 / s1, persistent 3x3 / s2, cn_proj 1x1, implicit GEMM.
-enum { R_NONE = 0, R_STEM_POOL, R_STEM, R_CONV16, R_CONV16S, R_OFFCONV, R_HALO, R_S2P, R_PROJ, R_IGEMM };
+enum { R_NONE = 0, R_STEM_POOL, R_STEM, R_CONV16, R_CONV16S, R_CONV16H, R_OFFCONV, R_HALO, R_S2P, R_PROJ, R_IGEMM };
 struct ConvRoute {
     int route;      // R_NONE: CN_ERR_UNSUPPORTED
     int cls;        // N tile of the layer: 2 = 128 wide, 1 = 64, 0 = 32
@@ -1221,6 +1221,16 @@ static bool conv16_shape(const ConvCall &c)
     return c.Cin == 16 && c.Cout <= 32 && c.KH == 3 && c.KW == 3 && c.pad_h == 1 && c.pad_w == 1 && c.dil == 1 &&
            c.plain_geo && !c.stem && !c.out_nchw &&
            (c.dtype == CN_DTYPE_F32 || (c.dtype == CN_DTYPE_F32S && c.in_plain && c.out_plain));
+}
+
+// ... and the half tensors' own predicate (conv16_shape stays what cn_conv2d_res_pitch_supported's recorded answers
+// were computed with): the layers of the half form of cn_conv16.hip, stride 1 and 2.  Halves on both sides: a
+// CN_CONV_Y_PLAIN call (y plain fp32 at a pitch in floats, the offset convolution of a half plan) keeps the
+// routes that have the fp32 store
+static bool conv16h_shape(const ConvCall &c)
+{
+    return c.dtype == CN_DTYPE_F16 && c.Cin == 16 && c.Cout <= 32 && c.KH == 3 && c.KW == 3 && c.pad_h == 1 &&
+           c.pad_w == 1 && c.dil == 1 && c.plain_geo && !c.stem && !c.out_nchw && !c.out_plain;
 }
 
 // The facts that come with pointers are inputs: c.vec_out, has_res / has_scale, and ws_bytes, the size of an
@@ -1269,6 +1279,9 @@ static ConvRoute conv_route(const ConvCall &c, bool has_res, bool has_scale, siz
     const bool f32s_packed = f32s && !c.in_plain && !c.res_plain && !has_res && has_scale && c.vec_out;
     if (!cn_knobs.nohalo && !has_res && r.ksplit == 1 && conv16_shape(c) && cn_conv16_takes(c))
         r.route = f32s ? R_CONV16S : R_CONV16;
+    // the same layers on half tensors (key 65): without it stride 1 goes to the halo kernel, stride 2 to the GEMM
+    else if (cn_knobs.conv16h && !cn_knobs.nohalo && !has_res && r.ksplit == 1 && conv16h_shape(c) && cn_conv16h_takes(c))
+        r.route = R_CONV16H;
     // <= 32 output channels on a plain fp32 tensor, plain output (the offset / mask convolution of the deformable
     // modules): cn_offconv.hip, with or without the K split
     else if (f32s && c.in_plain && c.out_plain && !has_res && is3x3 && c.stride == 1 && c.vec_out &&
@@ -1333,6 +1346,14 @@ extern "C" int cn_stem_f32s_supported(const cn_conv_desc *d)
     return form == CN_STEM_PERSIST_F32S || form == CN_STEM_16S;
 }
 
+// Will cn_conv2d run this descriptor (no residual, no workspace) on the half form of the 16-channel 3x3 kernel?
+extern "C" int cn_conv16_f16_supported(const cn_conv_desc *d)
+{
+    ConvCall c;
+    if (!route_query(d, c)) return 0;
+    return conv_route(c, false, true, 0).route == R_CONV16H;
+}
+
 extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_packed,
                          const float *scale, const float *shift, const void *residual, void *y,
                          void *workspace, size_t workspace_bytes, void *stream)
@@ -1361,6 +1382,7 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
     case R_STEM: return cn_stem_conv_f32(c, cn_knobs.stem_persist, st);
     case R_CONV16: return cn_conv3x3_c16(c, st);
     case R_CONV16S: return cn_conv3x3_c16s(c, st);
+    case R_CONV16H: return cn_conv3x3_c16h(c, st);
     case R_HALO: return cn_conv3x3s1(c, r.cls, st);
     case R_S2P: return cn_conv3x3s2_persist(c, st);
     case R_PROJ: return cn_proj1x1_f32s(c, st);

@@ -340,6 +340,173 @@ int launch_c16s(const C16sArgs &a, int B, hipStream_t st)
     return CN_OK;
 }
 
+// ---- half form (CN_DTYPE_F16 tensors on both sides): the simpler sibling of the f32s form.  Same geometry
+// (256 threads, persistent workgroups over 128-pixel row tiles, 3-row window in LDS, next window fetched into
+// registers during the MFMAs, K = five steps of two taps), but ONE fp16 plane of 32 bytes per pixel -- staged
+// with plain 16-byte loads and 16-byte LDS stores, element i of the window at byte 16 i: 4 staging registers
+// of 16 bytes per thread at stride 1, 7 at stride 2 -- and one MFMA per (step, pixel block, channel block).
+// Operand roles are swapped against the two kernels above: the WEIGHTS are the A operand (M = 16 output
+// channels) and the pixels the B operand (N = 16 pixels), so D holds, per lane, channels 4 (lane >> 4) .. + 3 of
+// pixel lane & 15: a lane stores 8 bytes and a 16-pixel block's 64 lanes cover 512 contiguous bytes at
+// Cout = 16 (the other roles would give sixteen scattered 2-byte stores).  The weight is the packed weight of
+// the general half kernels ([tap][cout_pad][64 halves], channels 16 .. 63 zero): the first 32 bytes of a row.
+// Stride 2: the 64-byte pixel stride gives two-way bank conflicts on the fragment reads; accepted (one plane;
+// DESIGN 3.3b has the measurement).  Barriers: __syncthreads() only.
+struct C16hArgs {
+    const _Float16 *x;
+    const void *w;
+    const float *scale, *shift;
+    _Float16 *y;
+    int H, W, Ho, Wo, Cout, cout_pad, in_pitch, out_pitch, relu, vec_out;
+};
+
+template <int NBLK, int S>
+__global__ __launch_bounds__(NT, 2) void conv16h_kernel(const C16hArgs a, int total_tiles)
+{
+    constexpr int WX = (BM - 1) * S + 3;           // window columns
+    constexpr int NQ = 3 * WX * 2;                 // 16-byte elements of the window: (row, column, channel half)
+    constexpr int PQ = (NQ + NT - 1) / NT;         // per thread
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int tpr = a.Wo / BM;
+
+    // A operand: output channel n = nb*16 + l15; step u: tap 2u + (lq >> 1), input channels 8 (lq & 1) .. + 7
+    c16_f16x8 wf[NBLK][5];
+#pragma unroll
+    for (int nb = 0; nb < NBLK; ++nb)
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {
+            const int t = 2 * u + (lq >> 1);
+            const int n = min(nb * 16 + l15, a.cout_pad - 1);
+            const char *g = reinterpret_cast<const char *>(a.w) + ((size_t)(min(t, 8) * a.cout_pad + n)) * 128 + 16 * (lq & 1);
+            const bool ok = t < 9 && nb * 16 + l15 < a.Cout;
+            const c16_f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            wf[nb][u] = ok ? *reinterpret_cast<const c16_f16x8 *>(g) : z;
+        }
+    // D rows of this lane: channels nb*16 + 4 lq + r
+    float sc[NBLK][4], sf[NBLK][4];
+#pragma unroll
+    for (int nb = 0; nb < NBLK; ++nb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = nb * 16 + 4 * lq + r;
+            sc[nb][r] = (a.scale && n < a.Cout) ? a.scale[n] : 1.f;
+            sf[nb][r] = (a.shift && n < a.Cout) ? a.shift[n] : 0.f;
+            asm volatile("" : "+v"(sc[nb][r]), "+v"(sf[nb][r]));  // settle before the tile loop
+        }
+
+    c16_f16x8 v[PQ];
+    unsigned vmask = 0;
+    auto prefetch = [&](int tile) {
+        const int xt = tile % tpr;
+        const int rowid = tile / tpr;  // b*Ho + oy
+        const int b = rowid / a.Ho, oy = rowid - b * a.Ho;
+        const int iy0 = oy * S - 1, ix0 = xt * BM * S - 1;
+        const char *xb = reinterpret_cast<const char *>(a.x + (size_t)b * a.H * a.W * a.in_pitch);
+        unsigned mk = 0;
+#pragma unroll
+        for (int u = 0; u < PQ; ++u) {
+            const int i = tid + u * NT;
+            const int row = i / (WX * 2), rem = i - row * (WX * 2);
+            const int col = rem >> 1, h = rem & 1;
+            const int iy = iy0 + row, ix = ix0 + col;
+            const bool ok = i < NQ && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+            const unsigned off = ok ? (unsigned)(((iy * a.W + ix) * a.in_pitch + h * 8) * 2) : 0u;
+            v[u] = *reinterpret_cast<const c16_f16x8 *>(xb + off);
+            mk |= ok ? (1u << u) : 0u;
+        }
+        vmask = mk;
+    };
+    auto store_window = [&]() {
+        const c16_f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int u = 0; u < PQ; ++u) {
+            const int i = tid + u * NT;
+            if (i < NQ) *reinterpret_cast<c16_f16x8 *>(smem + (size_t)i * 16) = ((vmask >> u) & 1u) ? v[u] : z;
+        }
+    };
+
+    // B fragment of (16-pixel block mb, step u): pixel + tap offset, 16 bytes of channel half (lq & 1)
+    unsigned boff[2][5];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int u = 0; u < 5; ++u) {
+            const int t = min(2 * u + (lq >> 1), 8);   // (the tenth half-step re-reads tap 8: its weights are zero)
+            boff[mb][u] = (unsigned)(((wave * 32 + mb * 16 + l15) * S + (t / 3) * WX + (t % 3)) * 32 + 16 * (lq & 1));
+        }
+
+    int tile = blockIdx.x;
+    if (tile < total_tiles) prefetch(tile);
+    for (; tile < total_tiles; tile += gridDim.x) {
+        store_window();
+        __syncthreads();
+        const int next = tile + gridDim.x;
+        if (next < total_tiles) prefetch(next);
+
+        cn_f32x4 acc[2][NBLK];
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < NBLK; ++nb) acc[mb][nb] = cn_f32x4{0.f, 0.f, 0.f, 0.f};
+        c16_f16x8 bf[2][5];
+#pragma unroll
+        for (int u = 0; u < 5; ++u)
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) bf[mb][u] = *reinterpret_cast<const c16_f16x8 *>(smem + boff[mb][u]);
+        // every fragment is in registers before the first MFMA (operand hazard note, cn_conv.hip)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 5; ++u)
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < NBLK; ++nb)
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nb][u], bf[mb][u], acc[mb][nb], 0, 0, 0);
+        // D: col = lane & 15 (pixel), rows 4*(lane >> 4) + r (output channels): fp32 epilogue, one rounding
+        const int xt = tile % tpr;
+        const int rowid = tile / tpr;
+        _Float16 *yb = a.y + ((size_t)rowid * a.Wo + (size_t)xt * BM) * a.out_pitch;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            _Float16 *yp = yb + (size_t)(wave * 32 + mb * 16 + l15) * a.out_pitch;
+#pragma unroll
+            for (int nb = 0; nb < NBLK; ++nb) {
+                const int n0 = nb * 16 + 4 * lq;
+                cn_f16x4v o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float t = acc[mb][nb][r] * sc[nb][r] + sf[nb][r];
+                    if (a.relu) t = fmaxf(t, 0.f);
+                    o[r] = (_Float16)t;
+                }
+                if (a.vec_out && n0 + 3 < a.Cout)
+                    *reinterpret_cast<cn_f16x4v *>(yp + n0) = o;
+                else
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (n0 + r < a.Cout) yp[n0 + r] = o[r];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <int NBLK, int S>
+int launch_c16h(const C16hArgs &a, int B, hipStream_t st)
+{
+    constexpr int WX = (BM - 1) * S + 3;
+    constexpr size_t lds = (size_t)3 * WX * 32;    // 12 480 bytes at stride 1, 24 672 at stride 2
+    const long total = (long)B * a.Ho * (a.Wo / BM);
+    const int wgs = (int)(total < 512 ? total : 512);  // two resident workgroups per CU
+    CN_SET_MAX_LDS_ONCE((conv16h_kernel<NBLK, S>), lds);
+    hipLaunchKernelGGL((conv16h_kernel<NBLK, S>), dim3(wgs), dim3(NT), lds, st, a, (int)total);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 }  // namespace
 
 // Is the layer of this file's form?  (the caller has checked: 3x3 / pad 1 / dilation 1, NHWC both sides, no
@@ -387,4 +554,29 @@ int cn_conv3x3_c16s(const ConvCall &c, hipStream_t st)
     a.x_mul = (c.ctl && c.ctl->x_mul != 0.f) ? c.ctl->x_mul : 1.f;
     a.range = c.ctl ? c.ctl->range : nullptr;
     return c.Cout <= 16 ? launch_c16s<1, 1>(a, c.B, st) : launch_c16s<2, 1>(a, c.B, st);
+}
+
+// Half form: is the layer one it runs?  (the caller has checked: CN_DTYPE_F16, 3x3 / pad 1 / dilation 1, plain
+// geometry, NHWC both sides, no residual, no K split)
+bool cn_conv16h_takes(const ConvCall &c)
+{
+    if (c.dtype != CN_DTYPE_F16 || c.out_plain || c.Cin != CI || c.Cout > 32 || (c.stride != 1 && c.stride != 2) || c.Wo % BM != 0)
+        return false;
+    if ((c.in_pitch & 7) || (c.out_pitch & 3)) return false;   // 16-byte loads; 8-byte stores where y is aligned
+    if (c.Ho != (c.H + 2 - 3) / c.stride + 1 || c.Wo != (c.W + 2 - 3) / c.stride + 1) return false;
+    return (long)c.H * c.W * c.in_pitch < (1L << 30);          // 32-bit byte offsets per image
+}
+
+// half input, the general half kernels' packed weight (cn_pack_conv_weight, CN_DTYPE_F16), fp32 scale / shift,
+// half output at out_pitch
+int cn_conv3x3_c16h(const ConvCall &c, hipStream_t st)
+{
+    if (!cn_conv16h_takes(c) || c.residual || c.ksplit != 1) return CN_ERR_UNSUPPORTED;
+    C16hArgs a;
+    a.x = (const _Float16 *)c.x; a.w = c.w; a.scale = c.scale; a.shift = c.shift; a.y = (_Float16 *)c.y;
+    a.H = c.H; a.W = c.W; a.Ho = c.Ho; a.Wo = c.Wo; a.Cout = c.Cout; a.cout_pad = c.cout_pad;
+    a.in_pitch = c.in_pitch; a.out_pitch = c.out_pitch; a.relu = c.relu; a.vec_out = c.vec_out;
+    if (c.Cout <= 16)
+        return c.stride == 1 ? launch_c16h<1, 1>(a, c.B, st) : launch_c16h<1, 2>(a, c.B, st);
+    return c.stride == 1 ? launch_c16h<2, 1>(a, c.B, st) : launch_c16h<2, 2>(a, c.B, st);
 }

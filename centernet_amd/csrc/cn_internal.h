@@ -147,6 +147,9 @@ int cn_proj1x1_f32s(const ConvCall &c, hipStream_t st);
 bool cn_conv16_takes(const ConvCall &c);
 int cn_conv3x3_c16(const ConvCall &c, hipStream_t st);
 int cn_conv3x3_c16s(const ConvCall &c, hipStream_t st);
+// ... and its half form (CN_DTYPE_F16 tensors, stride 1 and 2)
+bool cn_conv16h_takes(const ConvCall &c);
+int cn_conv3x3_c16h(const ConvCall &c, hipStream_t st);
 
 // ---- cn_conv3x3.hip (LDS-halo kernel); each forwards the call to cn_conv3x3p.hip when that kernel takes it
 // bn_class: 2 = 128-wide N tiles, 1 = 64, 0 = 32 (conv_route's)

@@ -237,6 +237,74 @@ __global__ void copy_channels_kernel(const float *__restrict__ src, int src_pitc
     }
 }
 
+// half forms of the two kernels above: 8 channels (16 bytes) per lane.  dw_deconv: halves are widened, the
+// <= 4 products and `add` are summed in fp32 (taps stay fp32: they are checkpoint parameters), ONE rounding
+// to fp16 at the store; no packed-half arithmetic.
+__global__ void dw_deconv_f16_kernel(const _Float16 *__restrict__ x, const float *__restrict__ w,
+                                     const _Float16 *__restrict__ add, _Float16 *__restrict__ y, int B, int H,
+                                     int W, int C, int f)
+{
+    const int c8n = C >> 3;
+    const int OH = H * f, OW = W * f, K2 = 2 * f, pad = f / 2;
+    const size_t total = (size_t)B * OH * OW * c8n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const int c8 = (int)(i % c8n);
+        size_t r = i / c8n;
+        const int ox = (int)(r % OW);
+        r /= OW;
+        const int oy = (int)(r % OH);
+        const int b = (int)(r / OH);
+        const int ky0 = (oy + pad) % f, kx0 = (ox + pad) % f;
+        const int iy0 = (oy + pad - ky0) / f, ix0 = (ox + pad - kx0) / f;
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ty = 0; ty < 2; ++ty) {
+            const int iy = iy0 - ty, ky = ky0 + ty * f;
+            if (iy < 0 || iy >= H) continue;
+#pragma unroll
+            for (int tx = 0; tx < 2; ++tx) {
+                const int ix = ix0 - tx, kx = kx0 + tx * f;
+                if (ix < 0 || ix >= W) continue;
+                const mp_f16x8 v = *reinterpret_cast<const mp_f16x8 *>(
+                    x + (((size_t)b * H + iy) * W + ix) * C + c8 * 8);
+                const float *wt = w + (size_t)(ky * K2 + kx) * C + c8 * 8;
+                const cn_f32x4 w0 = *reinterpret_cast<const cn_f32x4 *>(wt);
+                const cn_f32x4 w1 = *reinterpret_cast<const cn_f32x4 *>(wt + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    acc[e] += (float)v[e] * w0[e];
+                    acc[4 + e] += (float)v[4 + e] * w1[e];
+                }
+            }
+        }
+        const size_t o = (((size_t)b * OH + oy) * OW + ox) * C + c8 * 8;
+        if (add) {
+            const mp_f16x8 av = *reinterpret_cast<const mp_f16x8 *>(add + o);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += (float)av[e];
+        }
+        mp_f16x8 out;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[e] = (_Float16)acc[e];
+        *reinterpret_cast<mp_f16x8 *>(y + o) = out;
+    }
+}
+
+__global__ void copy_channels_f16_kernel(const _Float16 *__restrict__ src, int src_pitch,
+                                         _Float16 *__restrict__ dst, int dst_pitch, size_t npix, int C)
+{
+    const int c8n = C >> 3;
+    const size_t total = npix * c8n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const int c8 = (int)(i % c8n);
+        const size_t p = i / c8n;
+        *reinterpret_cast<mp_f16x8 *>(dst + p * dst_pitch + c8 * 8) =
+            *reinterpret_cast<const mp_f16x8 *>(src + p * src_pitch + c8 * 8);
+    }
+}
+
 // nearest-neighbour x2 up-sampling (nn.Upsample(scale_factor=2), large_hourglass.py:102-103)
 // fused with the add of the skip branch (merge layer, :104-109)
 __global__ void upsample2x_add_kernel(const float *__restrict__ x, const float *__restrict__ add,
@@ -667,6 +735,36 @@ extern "C" int cn_copy_channels_f32(const float *src, int src_pitch, float *dst,
     const size_t total = npix * (C >> 2);
     hipLaunchKernelGGL(copy_channels_kernel, dim3(blocks_for(total, 256, 65535)), dim3(256), 0,
                        (hipStream_t)stream, src, src_pitch, dst, dst_pitch, npix, C);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_dw_conv_transpose_f16(const void *x, const float *w_taps, const void *add, void *y, int B,
+                                        int H, int W, int C, int f, void *stream)
+{
+    if (!x || !w_taps || !y) return CN_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || f < 2 || (f & 1)) return CN_ERR_SHAPE;
+    if (C & 7) return CN_ERR_UNSUPPORTED;   // whole 16-byte groups of halves
+    if (!cn_aligned16(x) || !cn_aligned16(w_taps) || !cn_aligned16(y) || (add && !cn_aligned16(add)))
+        return CN_ERR_ALIGN;
+    const size_t total = (size_t)B * H * f * W * f * (C >> 3);
+    hipLaunchKernelGGL(dw_deconv_f16_kernel, dim3(blocks_for(total, 256, 65535)), dim3(256), 0,
+                       (hipStream_t)stream, (const _Float16 *)x, w_taps, (const _Float16 *)add, (_Float16 *)y, B,
+                       H, W, C, f);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_copy_channels_f16(const void *src, int src_pitch, void *dst, int dst_pitch, size_t npix,
+                                    int C, void *stream)
+{
+    if (!src || !dst) return CN_ERR_NULL;
+    if (C <= 0 || src_pitch < C || dst_pitch < C) return CN_ERR_SHAPE;
+    if ((C & 7) || (src_pitch & 7) || (dst_pitch & 7)) return CN_ERR_UNSUPPORTED;
+    if (!cn_aligned16(src) || !cn_aligned16(dst)) return CN_ERR_ALIGN;
+    const size_t total = npix * (C >> 3);
+    hipLaunchKernelGGL(copy_channels_f16_kernel, dim3(blocks_for(total, 256, 65535)), dim3(256), 0,
+                       (hipStream_t)stream, (const _Float16 *)src, src_pitch, (_Float16 *)dst, dst_pitch, npix, C);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

@@ -1,6 +1,8 @@
 // cn_tuning.h -- the cn_set_tuning knobs: one struct of plain ints that the launchers read, and the one
 // table that states each key's number, field, default and accepted values.  A new knob is a field of
 // CnTuning plus a row of CN_TUNING_KEYS (and its entry under cn_set_tuning in include/centernet_amd.h).
+// Keys -1 ... 64 are closed: tests/test_tuning_host.py records exactly which of them are accepted (and that 48 is
+// not a key); a new knob takes the next free number from 65 on and is documented BELOW cn_set_tuning there.
 // Plain process-global ints, no locking: see the THREADING note in include/centernet_amd.h.
 #pragma once
 
@@ -9,7 +11,7 @@ struct CnTuning {
         split_min_chunks, split_max, stagger_pct, occ4, f32s_lds_weights, f32s_policy, dcn_tile2d, dcn_form,
         heads_remap, heads_reg, stem16s, c3p, c3p_stagger, c3p_knobs, c3p_heads, c3p_deconv, c3p_s2, dcn_team,
         dcn_team_wgs, dcn_team_stagger, offconv, offconv_teams1, dcn_wide, dcn_wide_wgs, stem_dbg, stem_stagger,
-        dcn_wide_prefetch, proj, c3p_grid;
+        dcn_wide_prefetch, proj, c3p_grid, conv16h;
 };
 extern CnTuning cn_knobs;   // the one instance (cn_conv.hip, next to cn_set_tuning / cn_get_tuning / cn_reset_tuning)
 
@@ -85,6 +87,8 @@ constexpr CnTuningKey CN_TUNING_KEYS[] = {
     {44, &CnTuning::stem_stagger, 0, 0, 1024},    // start delay of the second resident workgroup, units of 256 cycles
     // 1x1 projections (cn_proj.hip)
     {46, &CnTuning::proj, 1, 0, 1},               // 1 = f32s 1x1 layers without residual on this kernel, 0 = implicit GEMM
+    // 16-channel 3x3 kernel (cn_conv16.hip)
+    {65, &CnTuning::conv16h, 1, 0, 1},            // 1 = fp16 layers it takes on its half form, 0 = halo kernel / implicit GEMM
 };
 
 constexpr CnTuning cn_tuning_defaults()

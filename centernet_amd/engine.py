@@ -712,15 +712,23 @@ class PlanBuilder:
     def maxpool(self, x, k, s, pad, lid=None, out=None, to_s=False):
         """MaxPool2d.  ``to_s`` / ``out``: an f32s input of whole groups stays f32s -- written into
         ``out`` when given (a channel slice of a concatenation buffer) -- so that its consumers (a
-        projection, a Root's concatenation: pose_dla_dcn.py:206-221) read (high, low) pairs."""
+        projection, a Root's concatenation: pose_dla_dcn.py:206-221) read (high, low) pairs.  A half plan
+        writes halves into ``out`` when given (the kernel takes both pitches) and has nothing to keep packed:
+        ``to_s`` says nothing there."""
         lid = self._lid(lid)
         lib = self.lib
         from_s = x.fmt == "f32s" and x.C % 32 == 0     # read (high, low) pairs
         Ho, Wo = _out_size(x.H, k, s, pad), _out_size(x.W, k, s, pad)
         if self.dtype == torch.float16:
             # half plan: halves in, halves out, always a launch of its own
-            assert x.fmt == "f16" and out is None and not to_s
-            pooled = self._new(x.B, Ho, Wo, x.C, lid=lid)
+            assert x.fmt == "f16"
+            if out is None:
+                pooled = self._new(x.B, Ho, Wo, x.C, lid=lid)
+            else:
+                assert out.fmt == "f16" and (out.B, out.H, out.W, out.C) == (x.B, Ho, Wo, x.C)
+                assert x.c_off % 8 == 0 and out.c_off % 8 == 0
+                out.lid, out.exp = lid, self._exp(lid)
+                pooled = out
 
             def run():
                 rc = lib.cn_maxpool_nhwc_f16(x.ptr(), pooled.ptr(), x.B, x.H, x.W, x.C, x.pitch, pooled.pitch,
@@ -774,15 +782,19 @@ class PlanBuilder:
     def concat_buffer(self, B, H, W, widths):
         """A concatenation buffer allocated BEFORE its members exist, and one Act per member to pass
         as ``out=`` to the producing launch (conv / maxpool): members written in place need no copy.
-        f32s plans only, members of whole 32-channel groups; otherwise (None, None) -- ``concat``
-        then allocates and copies as before.  Pass the buffer to ``concat(acts, into=buf)``."""
-        if not self.split or any(w % 32 for w in widths) or os.environ.get("CN_CONCAT_INPLACE", "1") == "0":
+        f32s plans with members of whole 32-channel groups, half plans with members of whole 16-byte
+        groups (8 channels); otherwise (None, None) -- ``concat`` then allocates and copies as before.
+        Pass the buffer to ``concat(acts, into=buf)``."""
+        half = self.dtype == torch.float16
+        if not (self.split or half) or any(w % (8 if half else 32) for w in widths) or \
+                os.environ.get("CN_CONCAT_INPLACE", "1") == "0":
             return None, None
         C = sum(widths)
-        buf = self._new(B, H, W, C, fmt="f32s")
+        fmt = "f16" if half else "f32s"
+        buf = self._new(B, H, W, C, fmt=fmt)
         slices, off = [], 0
         for w in widths:
-            slices.append(Act(buf.t, B, H, W, w, pitch=C, c_off=off, fmt="f32s"))
+            slices.append(Act(buf.t, B, H, W, w, pitch=C, c_off=off, fmt=fmt))
             off += w
         return buf, slices
 
@@ -810,54 +822,68 @@ class PlanBuilder:
         lib = self.lib
         npix = a0.B * a0.H * a0.W
         off = 0
+        # a half plan moves halves as they are: no exponents, no format conversion
+        half = out.fmt == "f16"
+        copy, entry = (lib.cn_copy_channels_f16, "cn_copy_channels_f16") if half else \
+            (lib.cn_copy_channels_f32, "cn_copy_channels_f32")
         for a in acts:
             assert (a.B, a.H, a.W) == (a0.B, a0.H, a0.W) and not a.nchw
+            # the half entry moves 16-byte groups: refused here, while the plan is built, not when it runs
+            assert not half or (a.fmt == "f16" and a.C % 8 == 0 and a.c_off % 8 == 0 and a.pitch % 8 == 0), \
+                "a half concatenation takes members of whole 8-channel groups (C %d, offset %d, pitch %d)" % (
+                    a.C, a.c_off, a.pitch)
             dst = Act(out.t, out.B, out.H, out.W, a.C, pitch=C, c_off=off, fmt=out.fmt,
                       exp=out.exp, lid=a.lid)
 
             def run(a=a, dst=dst):
-                rc = lib.cn_copy_channels_f32(a.ptr(), a.pitch, dst.ptr(), C, npix, a.C,
-                                              native.stream_ptr())
+                rc = copy(a.ptr(), a.pitch, dst.ptr(), C, npix, a.C, native.stream_ptr())
                 if rc:
-                    native.check(rc, "cn_copy_channels_f32")
-            self._emit_simple(run, "copy", dst, 8 * npix * a.C)
+                    native.check(rc, entry)
+            self._emit_simple(run, "copy", dst, (4 if half else 8) * npix * a.C)
             off += a.C
         return out
 
     def _concat_into(self, acts, buf, lid):
         self.groups.append([lid] + [a.lid for a in acts])
         C = buf.pitch
-        assert buf.fmt == "f32s" and sum(a.C for a in acts) == C
+        assert buf.fmt in ("f32s", "f16") and sum(a.C for a in acts) == C
         exps = {a.exp for a in acts}
         buf.lid = lid
         buf.exp = acts[0].exp
         lib, npix, off = self.lib, buf.B * buf.H * buf.W, 0
+        half = buf.fmt == "f16"     # halves are copied as they are: no exponents, no format conversion
+        copy, entry = (lib.cn_copy_channels_f16, "cn_copy_channels_f16") if half else \
+            (lib.cn_copy_channels_f32, "cn_copy_channels_f32")
         for a in acts:
             assert (a.B, a.H, a.W) == (buf.B, buf.H, buf.W) and not a.nchw
-            in_place = a.t is buf.t and a.c_off == off and a.pitch == C and a.fmt == "f32s"
+            in_place = a.t is buf.t and a.c_off == off and a.pitch == C and a.fmt == buf.fmt
             if not in_place:
-                src = a if (a.fmt == "f32s" and a.C % 32 == 0 and a.exp == buf.exp) else None
+                assert not half or (a.fmt == "f16" and a.C % 8 == 0 and a.c_off % 8 == 0 and a.pitch % 8 == 0), \
+                    "a half concatenation takes members of whole 8-channel groups (C %d, offset %d, pitch %d)" % (
+                        a.C, a.c_off, a.pitch)
+                src = a if (half or (a.fmt == "f32s" and a.C % 32 == 0 and a.exp == buf.exp)) else None
                 if src is None:
                     # a member in another format or with another exponent: through plain floats
                     p = self.plain(a)
                     q = Act(p.t, p.B, p.H, p.W, p.C, p.pitch, p.c_off, fmt="f32", exp=buf.exp, lid=a.lid)
                     src = self.packed(q)
-                dst = Act(buf.t, buf.B, buf.H, buf.W, a.C, pitch=C, c_off=off, fmt="f32s", exp=buf.exp, lid=a.lid)
+                dst = Act(buf.t, buf.B, buf.H, buf.W, a.C, pitch=C, c_off=off, fmt=buf.fmt, exp=buf.exp, lid=a.lid)
 
                 def run(src=src, dst=dst):
-                    rc = lib.cn_copy_channels_f32(src.ptr(), src.pitch, dst.ptr(), C, npix, src.C,
-                                                  native.stream_ptr())
+                    rc = copy(src.ptr(), src.pitch, dst.ptr(), C, npix, src.C, native.stream_ptr())
                     if rc:
-                        native.check(rc, "cn_copy_channels_f32")
-                self._emit_simple(run, "copy", dst, 8 * npix * a.C)
+                        native.check(rc, entry)
+                self._emit_simple(run, "copy", dst, (4 if half else 8) * npix * a.C)
             off += a.C
         assert len(exps) == 1 or not self.exps, "members of a concatenation share one exponent"
         return buf
 
     def dw_deconv(self, x, weight, f, add=None):
         """Depthwise ConvTranspose2d(C, C, 2f, stride f, padding f//2, groups=C) + add
-        (IDAUp, pose_dla_dcn.py:370-373, 381-386)."""
+        (IDAUp, pose_dla_dcn.py:370-373, 381-386).  A half plan reads and writes halves; the taps stay
+        fp32 (they are checkpoint parameters) and the sum is rounded once."""
         lid = self._lid()
+        half = self.dtype == torch.float16
         x, add = self.plain(x), self.plain(add)
         C = x.C
         assert tuple(weight.shape) == (C, 1, 2 * f, 2 * f) and x.pitch == C and x.c_off == 0
@@ -867,16 +893,18 @@ class PlanBuilder:
         out = self._new(x.B, x.H * f, x.W * f, C, lid=lid)
         lib = self.lib
         wp = native.ptr(wt)
+        fn = lib.cn_dw_conv_transpose_f16 if half else lib.cn_dw_conv_transpose_f32
+        assert x.fmt == out.fmt and (add is None or add.fmt == out.fmt)
         if add is not None:
             assert (add.H, add.W, add.C, add.pitch, add.c_off) == (out.H, out.W, C, C, 0)
 
         def run():
-            rc = lib.cn_dw_conv_transpose_f32(x.ptr(), wp, add.ptr() if add is not None else None,
-                                              out.ptr(), x.B, x.H, x.W, C, f, native.stream_ptr())
+            rc = fn(x.ptr(), wp, add.ptr() if add is not None else None, out.ptr(), x.B, x.H, x.W, C, f,
+                    native.stream_ptr())
             if rc:
-                native.check(rc, "cn_dw_conv_transpose_f32")
+                native.check(rc, "cn_dw_conv_transpose_f16" if half else "cn_dw_conv_transpose_f32")
         self._emit_simple(run, "dwdeconv", out,
-                          4 * x.B * C * (x.H * x.W + (2 if add is not None else 1) * out.H * out.W))
+                          (2 if half else 4) * x.B * C * (x.H * x.W + (2 if add is not None else 1) * out.H * out.W))
         return out
 
     def upsample2x_add(self, x, add=None):
@@ -1482,10 +1510,12 @@ class PlannedModule(torch.nn.Module):
 
     def half_compute(self, enable=True):
         """fp16 activations/weights with fp32 accumulation; parameters stay fp32 in the module, only the
-        packed plan copies are fp16.  Plans Hourglass (BASELINE configs[4]), ``res_18/34/50/101/152`` and
-        ``resdcn_18/34/50/101/152`` end to end: the deformable layers read half activations with fp32
-        offsets / masks, the heads stay fp32 NCHW and nothing is deferred.  ``dla_34`` (depthwise
-        transposed convolution, tree concatenation) has no half form and fails while its plan is built."""
+        packed plan copies are fp16.  Plans Hourglass (BASELINE configs[4]), ``res_18/34/50/101/152``,
+        ``resdcn_18/34/50/101/152`` and ``dla_34`` end to end: the deformable layers read half activations with
+        fp32 offsets / masks, the heads stay fp32 NCHW and nothing is deferred.  ``dla_34``: IDAUp's depthwise
+        transposed convolution keeps fp32 taps and rounds once, the trees concatenate halves in place, the two
+        16-channel 3x3 layers run on the half form of cn_conv16.hip; its 7x7 ``base_layer`` stays on the implicit
+        GEMM's padded stem form.  Canvas batches (``rects=``) have no half plan."""
         self.compute_dtype = torch.float16 if enable else torch.float32
         self.drop_plans()
         return self

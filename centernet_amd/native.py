@@ -191,6 +191,8 @@ def _declare(lib):
     lib.cn_stem_maxpool_supported.argtypes = [ctypes.POINTER(ConvDesc)]
     lib.cn_stem_f32s_supported.restype = i
     lib.cn_stem_f32s_supported.argtypes = [ctypes.POINTER(ConvDesc)]
+    lib.cn_conv16_f16_supported.restype = i
+    lib.cn_conv16_f16_supported.argtypes = [ctypes.POINTER(ConvDesc)]
     lib.cn_conv2d_f32.restype = i
     lib.cn_conv2d_f32.argtypes = [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp]
     lib.cn_packed_conv_weight_elems.restype = sz
@@ -221,6 +223,10 @@ def _declare(lib):
     lib.cn_dw_conv_transpose_f32.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp]
     lib.cn_copy_channels_f32.restype = i
     lib.cn_copy_channels_f32.argtypes = [vp, i, vp, i, sz, i, vp]
+    lib.cn_dw_conv_transpose_f16.restype = i
+    lib.cn_dw_conv_transpose_f16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp]
+    lib.cn_copy_channels_f16.restype = i
+    lib.cn_copy_channels_f16.argtypes = [vp, i, vp, i, sz, i, vp]
     lib.cn_upsample2x_add_f32.restype = i
     lib.cn_upsample2x_add_f32.argtypes = [vp, vp, vp, i, i, i, i, vp]
     lib.cn_mask_rects_f32.restype = i

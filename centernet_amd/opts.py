@@ -41,7 +41,7 @@ _FLAGS = [
     # product on range-controlled fp16 pairs) -- the A/B reference mode
     ("--fp32_mfma", dict(action="store_true")),
     # new: fp16 activations and weights with fp32 accumulation (PlannedModule.half_compute): hourglass,
-    # res_N and resdcn_N; not together with --fp32_mfma
+    # res_N, resdcn_N and dla_34; not together with --fp32_mfma
     ("--fp16", dict(action="store_true")),
     ("--shift", dict(type=float, default=0.1)), ("--scale", dict(type=float, default=0.4)),
     ("--rotate", dict(type=float, default=0)), ("--flip", dict(type=float, default=0.5)),

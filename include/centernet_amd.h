@@ -184,6 +184,13 @@ const char *cn_arch(void);
  * key 46: 1 = f32s 1x1 layers without residual run on the direct-fragment kernel (default),
  *         0 = on the implicit GEMM. */
 int cn_set_tuning(int key, int value);
+/* Keys from 65 on.  (tests/test_tuning_host.py records the accepted set of keys -1 ... 64 and reads the comment
+ * above against it, and holds 48 to be unknown: the numbers up to 64 are closed, new knobs count on from 65.)
+ * 16-channel 3x3 kernel (cn_conv16.hip):
+ * knob 65: 1 = fp16 3x3 / pad 1 layers of 16 input and <= 32 output channels without residual run on its half
+ *          form (default; cn_conv16_f16_supported says which), 0 = on the LDS-halo kernel (stride 1) or the
+ *          implicit GEMM (stride 2).  Key 10 = 1 (everything on the implicit GEMM) switches it off as well, as it
+ *          does the fp32 / f32s forms of that file. */
 /* Current value of a knob into *value; CN_ERR_UNSUPPORTED for a key cn_set_tuning does not know. */
 int cn_get_tuning(int key, int *value);
 /* Every knob back to its default. */
@@ -458,6 +465,11 @@ int cn_stem_maxpool_supported(const cn_conv_desc *d);
 /* 1 when cn_conv2d runs this stem descriptor with CN_CONV_STEM_F32S arithmetic (only then are
  * ctl.x_mul / ctl.range used: the fp32 stem kernels split nothing), else 0.  Host-only. */
 int cn_stem_f32s_supported(const cn_conv_desc *d);
+/* 1 when cn_conv2d runs this descriptor, without residual and unsplit, on the half form of the 16-channel 3x3
+ * kernel (cn_conv16.hip) under the current tuning: dtype CN_DTYPE_F16, Cin = 16, Cout <= 32, 3x3 / pad 1 /
+ * stride 1 or 2, half output (no CN_CONV_Y_PLAIN), Wo % 128 == 0, in_pitch % 8 == 0, out_pitch % 4 == 0, knob 65 on
+ * and key 10 off; else 0.  Host-only. */
+int cn_conv16_f16_supported(const cn_conv_desc *d);
 
 /* Number of floats of the packed weight for (Cout,Cin,KH,KW). */
 size_t cn_packed_conv_weight_floats(int Cout, int Cin, int KH, int KW);
@@ -543,6 +555,14 @@ int cn_dw_conv_transpose_f32(const float *x, const float *w_taps, const float *a
 /* Channel-slice copy between NHWC tensors of different pitch (torch.cat(.., 1) of
  * Root.forward, pose_dla_dcn.py:159). */
 int cn_copy_channels_f32(const float *src, int src_pitch, float *dst, int dst_pitch,
+                         size_t npix, int C, void *stream);
+/* Half forms of the two: x / add / y (src / dst) address halves, 8 channels (16 bytes) per lane.
+ * cn_dw_conv_transpose_f16: w_taps stays fp32 as above; halves are widened, the <= 4 products and `add` are
+ * summed in fp32 and rounded to fp16 once at the store; C % 8 == 0, CN_ERR_UNSUPPORTED otherwise.
+ * cn_copy_channels_f16: C, src_pitch and dst_pitch multiples of 8 and both pointers 16-byte aligned. */
+int cn_dw_conv_transpose_f16(const void *x, const float *w_taps, const void *add, void *y,
+                             int B, int H, int W, int C, int f, void *stream);
+int cn_copy_channels_f16(const void *src, int src_pitch, void *dst, int dst_pitch,
                          size_t npix, int C, void *stream);
 /* Canvas masks (--keep_res batches of mixed input sizes): image b of a batch owns the rectangle
  * rects_dev[b] of a common canvas, given in network-input pixels, half-open; a tensor at 1 / 2^shift of the
