@@ -82,6 +82,8 @@ struct IgemmArgs {
     int tile2d;                          // deformable kernel: tile rows are an 8-wide pixel BLOCK of one image
     float x_mul, res_mul;                // f32s range control (cn_f32s_ctl)
     uint32_t *range;                     // f32s: [0] max |stored output|, [1] max |split input|
+    const cn_rect *rects;                // fp16 deformable kernel, canvas batches: the images' own origins (DcnCall), or null
+    int rect_shift;
 };
 
 __device__ __forceinline__ float sigmoidf_dev(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -253,12 +255,22 @@ __global__ __launch_bounds__(NT) void igemm_kernel(const IgemmArgs a)
                 // modulation factor it is multiplied with anyway
                 if constexpr (SPLIT) mk *= a.x_mul;
                 const int ki = tap / 3, kj = tap - ki * 3;
-                const float h_im = (float)(oy - 1 + ki) + off_h;
-                const float w_im = (float)(ox - 1 + kj) + off_w;
+                // canvas batches in fp16 mode: the position relative to the image's own origin (y0, x0), so that the
+                // fractions round as in the image's own forward; (0, 0) otherwise -- the arithmetic it always was
+                int y0 = 0, x0 = 0;
+                if constexpr (sizeof(T) == 2) {
+                    if (a.rects) {
+                        const cn_rect rc = a.rects[b];
+                        y0 = min(max(rc.y0 >> a.rect_shift, 0), a.H);
+                        x0 = min(max(rc.x0 >> a.rect_shift, 0), a.W);
+                    }
+                }
+                const float h_im = (float)(oy - y0 - 1 + ki) + off_h;
+                const float w_im = (float)(ox - x0 - 1 + kj) + off_w;
                 const int H = a.H, W = a.W;
-                if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
+                if (h_im > -1.f - (float)y0 && w_im > -1.f - (float)x0 && h_im < (float)(H - y0) && w_im < (float)(W - x0)) {
                     const float hf = floorf(h_im), wf = floorf(w_im);
-                    const int h_low = (int)hf, w_low = (int)wf;
+                    const int h_low = (int)hf + y0, w_low = (int)wf + x0;
                     const int h_high = h_low + 1, w_high = w_low + 1;
                     const float lh = h_im - hf, lw = w_im - wf;
                     const float hh = 1.f - lh, hw = 1.f - lw;
@@ -1418,6 +1430,7 @@ static IgemmArgs dcn_args(const DcnCall &c)
     a.residual = nullptr; a.y = c.y; a.om = c.om; a.om_pitch = c.om_pitch;
     a.mask_sigmoid = c.mask_sigmoid;
     a.x_mul = c.x_mul; a.res_mul = 1.f; a.range = c.range;
+    a.rects = c.rects; a.rect_shift = c.rect_shift;
     a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Ho = c.H; a.Wo = c.W; a.Cout = c.Cout;
     a.KH = 3; a.KW = 3; a.stride = 1; a.pad_h = 1; a.pad_w = 1; a.dil = 1;
     a.in_pitch = c.Cin; a.out_pitch = c.out_pitch;

@@ -267,6 +267,28 @@ extern "C" int cn_dcn_v2_forward_nhwc_f16(const void *input_nhwc, const void *we
     return dcn_launch(c, (hipStream_t)stream);
 }
 
+// Canvas batches: image b owns the rectangle rects_dev[b] >> shift of the (H, W) tensor, and its
+// sampling positions are formed relative to that rectangle's origin, then moved back by whole pixels -- the
+// fractions, and with them every rounding, are those of the image's own forward wherever the rectangle lies.
+// The same route and forms; a null table is cn_dcn_v2_forward_nhwc_f16.
+extern "C" int cn_dcn_v2_forward_nhwc_f16_rects(const void *input_nhwc, const void *weight_packed, const float *bias,
+                                                const float *offset_mask_nhwc, int om_pitch, const float *scale,
+                                                const float *shift, void *output_nhwc, int out_pitch, int B,
+                                                int Cin, int H, int W, int Cout, int mask_sigmoid, int relu,
+                                                void *workspace, size_t workspace_bytes,
+                                                const cn_rect *rects_dev, int rect_shift, void *stream)
+{
+    if (rect_shift < 0 || rect_shift > 30) return CN_ERR_SHAPE;
+    DcnCall c;
+    const int rc = dcn_fill(c, (const float *)input_nhwc, weight_packed, bias, offset_mask_nhwc, om_pitch, scale, shift,
+                            output_nhwc, out_pitch, B, Cin, H, W, Cout, mask_sigmoid, relu, CN_DTYPE_F16, 0, nullptr,
+                            workspace, workspace_bytes, true);
+    if (rc != CN_OK) return rc;
+    c.rects = rects_dev;
+    c.rect_shift = rect_shift;
+    return dcn_launch(c, (hipStream_t)stream);
+}
+
 extern "C" int cn_dcn_v2_route_f16(const void *input_nhwc, const void *weight_packed, const float *bias,
                                    const float *offset_mask_nhwc, int om_pitch, const float *scale,
                                    const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,

@@ -29,6 +29,8 @@ struct DcnHArgs {
     _Float16 *y;
     int B, H, W, Cin, Cout, om_pitch, mask_sigmoid, relu;
     int cout_pad, nchunk, tiles_x, tiles_y, out_pitch;
+    const cn_rect *rects;      // canvas batches: the images' own origins (DcnCall), or null
+    int rect_shift;
 };
 
 __device__ __forceinline__ float dh_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }   // the gather form's
@@ -121,6 +123,14 @@ __global__ __launch_bounds__(H_NT, 2) void dcn_half_kernel(const DcnHArgs a)
             mkv[p] = om[18 + tap];
         }
         fill_load(0);
+        // canvas batches: positions relative to the image's own origin (y0, x0), so that the fractions round as in
+        // the image's own forward; (0, 0) otherwise -- the arithmetic it always was
+        int y0 = 0, x0 = 0;
+        if (a.rects) {
+            const cn_rect rc = a.rects[b];
+            y0 = min(max(rc.y0 >> a.rect_shift, 0), a.H);
+            x0 = min(max(rc.x0 >> a.rect_shift, 0), a.W);
+        }
 #pragma unroll
         for (int p = 0; p < NR; ++p) {
             const int i = p * H_NT + tid;
@@ -129,12 +139,13 @@ __global__ __launch_bounds__(H_NT, 2) void dcn_half_kernel(const DcnHArgs a)
             float mk = mkv[p];
             if (a.mask_sigmoid) mk = dh_sigmoid(mk);    // dcn_v2.py:67
             const int ki = tap / 3, kj = tap - ki * 3;
-            const float h_im = (float)(oy - 1 + ki) + off_h[p];
-            const float w_im = (float)(ox - 1 + kj) + off_w[p];
+            const float h_im = (float)(oy - y0 - 1 + ki) + off_h[p];
+            const float w_im = (float)(ox - x0 - 1 + kj) + off_w[p];
             cn_i32x4 rec = {0, 0, 0, 0};
-            if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {   // :165
+            if (h_im > -1.f - (float)y0 && w_im > -1.f - (float)x0 && h_im < (float)(H - y0) &&
+                w_im < (float)(W - x0)) {   // :165
                 const float hf = floorf(h_im), wf = floorf(w_im);
-                const int yl = (int)hf, xl = (int)wf;
+                const int yl = (int)hf + y0, xl = (int)wf + x0;
                 rec[0] = __float_as_int(h_im - hf);
                 rec[1] = __float_as_int(w_im - wf);
                 rec[2] = __float_as_int(mk);
@@ -338,5 +349,6 @@ int cn_dcn_window_f16(const DcnCall &c, const DcnPlan &p, hipStream_t st)
     a.nchunk = c.Cin / 64;
     a.tiles_x = c.W / DCNW_TX; a.tiles_y = c.H / DCNW_TY;
     a.out_pitch = c.out_pitch;
+    a.rects = c.rects; a.rect_shift = c.rect_shift;
     return p.bn == 64 ? dcn_half_launch<64>(a, p.grid_y, st) : dcn_half_launch<128>(a, p.grid_y, st);
 }

@@ -54,6 +54,10 @@ struct DcnCall {
     int dbg;                   // cn_set_tuning key 9
     void *workspace;           // as the caller gave them; whether they allow a split is the route's to judge
     size_t workspace_bytes;
+    // canvas batches (cn_dcn_v2_forward_nhwc_f16_rects): image b's own origin is (rects[b].x0, rects[b].y0) >> rect_shift
+    // and a sampling position is formed relative to it, as the image's own forward forms it; null: the tensor's origin
+    const cn_rect *rects;
+    int rect_shift;
 };
 // the values of cn_dcn_route_info::form (include/centernet_amd.h)
 enum { DCN_GATHER = CN_DCN_GATHER, DCN_GATHER_PAD = CN_DCN_GATHER_PAD, DCN_WINDOW = CN_DCN_WINDOW,

@@ -1000,10 +1000,13 @@ __device__ inline mask_span mask_kept(const cn_rect *__restrict__ rects, int b, 
     return k;
 }
 
-// t: the first masked channel of pixel (0, 0, 0); a pixel is `pitch` floats, q4 16-byte units of it are cleared
-__global__ __launch_bounds__(256) void mask_rects_nhwc_kernel(float *__restrict__ t, int H, int W, int pitch,
+// t: the first masked channel of pixel (0, 0, 0); a pixel is `pitch` elements of type T (float, or uint16_t for
+// halves), q4 16-byte units of it are cleared (all-zero bytes are +0.0 in both)
+template <typename T>
+__global__ __launch_bounds__(256) void mask_rects_nhwc_kernel(T *__restrict__ t, int H, int W, int pitch,
                                                               int q4, const cn_rect *__restrict__ rects, int shift)
 {
+    constexpr int PER = 16 / (int)sizeof(T);           // elements of one 16-byte store
     const int b = blockIdx.y;
     const mask_span k = mask_kept(rects, b, shift, H, W);
     if (k.x0 == 0 && k.x1 == W && k.y0 == 0 && k.y1 == H) return;
@@ -1014,11 +1017,11 @@ __global__ __launch_bounds__(256) void mask_rects_nhwc_kernel(float *__restrict_
         const int left = inside ? k.x0 : W;            // columns [0, left) and [right, W) are cleared
         const int right = inside ? k.x1 : W;
         const int n = (left + (W - right)) * q4;
-        float *row = t + ((size_t)b * H + y) * (size_t)W * pitch;
+        T *row = t + ((size_t)b * H + y) * (size_t)W * pitch;
         for (int i = threadIdx.x; i < n; i += blockDim.x) {
             const int px = i / q4, q = i - px * q4;
             const int x = px < left ? px : px - left + right;
-            *reinterpret_cast<cn_f32x4 *>(row + (size_t)x * pitch + q * 4) = zero;
+            *reinterpret_cast<cn_f32x4 *>(row + (size_t)x * pitch + q * PER) = zero;
         }
     }
 }
@@ -1059,8 +1062,28 @@ extern "C" int cn_mask_rects_f32(void *t_nhwc, int B, int H, int W, int pitch, i
     float *t = (float *)t_nhwc + c_off;
     if (!cn_aligned16(t)) return CN_ERR_ALIGN;
     dim3 grid(cn_cdiv(H, MASK_ROWS), B);
-    hipLaunchKernelGGL(mask_rects_nhwc_kernel, grid, dim3(256), 0, (hipStream_t)stream, t, H, W, pitch, width >> 2,
-                       rects_dev, shift);
+    hipLaunchKernelGGL(mask_rects_nhwc_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, t, H, W, pitch,
+                       width >> 2, rects_dev, shift);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_mask_rects_f16(void *t_nhwc, int B, int H, int W, int pitch, int c_off, int C,
+                                 const cn_rect *rects_dev, int shift, void *stream)
+{
+    if (!t_nhwc || !rects_dev) return CN_ERR_NULL;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || pitch <= 0 || c_off < 0 || c_off + C > pitch || B > 65535)
+        return CN_ERR_SHAPE;
+    if (shift < 0 || shift > 30) return CN_ERR_SHAPE;
+    // whole 8-channel groups (16 bytes), cut at the pitch -- NOT the 32-channel groups of the fp32 entry: a half
+    // plan concatenates in place with members of 16 and 32 channels side by side in one buffer
+    const int width = min(cn_cdiv(C, 8) * 8, pitch - c_off);
+    if ((pitch & 7) || (c_off & 7) || (width & 7)) return CN_ERR_ALIGN;
+    uint16_t *t = (uint16_t *)t_nhwc + c_off;
+    if (!cn_aligned16(t)) return CN_ERR_ALIGN;
+    dim3 grid(cn_cdiv(H, MASK_ROWS), B);
+    hipLaunchKernelGGL(mask_rects_nhwc_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, t, H, W, pitch,
+                       width >> 3, rects_dev, shift);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

@@ -256,8 +256,6 @@ class PlanBuilder:
         self.ragged, self.origin = bool(ragged), bool(origin)
         self.rects, self.rect_align = None, 1
         if self.ragged:
-            if dtype != torch.float32:
-                raise native.NativeError("canvas batches (rects=) are built for the fp32 compute modes only")
             self.rects = torch.zeros((B, 4), device=device, dtype=torch.int32)
         # heads that are NOT launched densely (PlannedModule.defer_heads): ``heads_from_convs`` leaves
         # them out of the fused launch and puts a DeferredHeads handle into ``self.deferred``
@@ -980,8 +978,18 @@ class PlanBuilder:
             return fn(x.ptr(), wpp, bp, om.ptr(), om.pitch, sp, hp, out.ptr(), out.pitch, x.B, ci, x.H, x.W, co,
                       msig, int(relu), *mode, wsp, self.ws_bytes, native.stream_ptr(), *more)
 
+        # a half canvas plan: sampling positions relative to every image's own rectangle, so that an image off the
+        # canvas origin (flip-test's mirror image) rounds as its own forward does (cn_dcn_v2_forward_nhwc_f16_rects)
+        at = (ctypes.c_void_p(self.rects.data_ptr()), self._mask_shift(x)) if (half and self.ragged) else None
+
         def run():
-            rc = call(lib.cn_dcn_v2_forward_nhwc_f16 if half else lib.cn_dcn_v2_forward_nhwc)
+            if at is not None:
+                wsp = ctypes.c_void_p(self.ws.data_ptr()) if self.ws is not None else None
+                rc = lib.cn_dcn_v2_forward_nhwc_f16_rects(x.ptr(), wpp, bp, om.ptr(), om.pitch, sp, hp, out.ptr(),
+                                                          out.pitch, x.B, ci, x.H, x.W, co, msig, int(relu), wsp,
+                                                          self.ws_bytes, at[0], at[1], native.stream_ptr())
+            else:
+                rc = call(lib.cn_dcn_v2_forward_nhwc_f16 if half else lib.cn_dcn_v2_forward_nhwc)
             if rc:
                 native.check(rc, "cn_dcn_v2_forward_nhwc")
 
@@ -1221,8 +1229,10 @@ class PlanBuilder:
         return shift
 
     def _mask_op(self, a, fill=None):
-        """The mask launch of activation ``a``: ``cn_mask_rects_f32`` on its channel groups, or for an NCHW
-        tensor ``cn_mask_rects_nchw_f32`` with ``fill`` (the network input is bound at run time)."""
+        """The mask launch of activation ``a``: ``cn_mask_rects_f32`` on its 32-channel groups (plain fp32 and
+        f32s), ``cn_mask_rects_f16`` on the 8-channel groups of a half activation -- picked by the element type of
+        the tensor, not by the plan's mode -- or for an NCHW tensor ``cn_mask_rects_nchw_f32`` with ``fill`` (the
+        network input is bound at run time)."""
         lib, rects, shift = self.lib, ctypes.c_void_p(self.rects.data_ptr()), self._mask_shift(a)
         if a.nchw:
             is_input, fill = a is self.input, float(fill)
@@ -1235,13 +1245,17 @@ class PlanBuilder:
                     native.check(rc, "cn_mask_rects_nchw_f32")
             return run, 4 * a.B * a.C * a.H * a.W
         base = ctypes.c_void_p(a.t.data_ptr())
+        half = a.t.dtype == torch.float16
+        assert half == (a.fmt == "f16") and (half or a.t.dtype == torch.float32), (a.fmt, a.t.dtype)
+        assert tuple(a.t.shape) == (a.B, a.H, a.W, a.pitch) and a.t.is_contiguous(), (tuple(a.t.shape), a.pitch)
+        mask, entry = (lib.cn_mask_rects_f16, "cn_mask_rects_f16") if half else \
+            (lib.cn_mask_rects_f32, "cn_mask_rects_f32")
 
         def run():
-            rc = lib.cn_mask_rects_f32(base, a.B, a.H, a.W, a.pitch, a.c_off, a.C, rects, shift,
-                                       native.stream_ptr())
+            rc = mask(base, a.B, a.H, a.W, a.pitch, a.c_off, a.C, rects, shift, native.stream_ptr())
             if rc:
-                native.check(rc, "cn_mask_rects_f32")
-        return run, 4 * a.B * a.H * a.W * a.C
+                native.check(rc, entry)
+        return run, (2 if half else 4) * a.B * a.H * a.W * a.C
 
     def add_masks(self, outputs):
         """Ragged plans: the launch list with its masks -- one on the network input, one behind every op on the
@@ -1515,7 +1529,12 @@ class PlannedModule(torch.nn.Module):
         fp32 offsets / masks, the heads stay fp32 NCHW and nothing is deferred.  ``dla_34``: IDAUp's depthwise
         transposed convolution keeps fp32 taps and rounds once, the trees concatenate halves in place, the two
         16-channel 3x3 layers run on the half form of cn_conv16.hip; its 7x7 ``base_layer`` stays on the implicit
-        GEMM's padded stem form.  Canvas batches (``rects=``) have no half plan."""
+        GEMM's padded stem form.  Canvas batches (``rects=``, the mixed-size --keep_res
+        batches of ``run_images``) have a half plan for every one of these families: the launch list with
+        ``cn_mask_rects_f16`` behind every op that wrote a half activation, in whole 8-channel groups so that the
+        members of an in-place concatenation stay apart, and the deformable layers on
+        ``cn_dcn_v2_forward_nhwc_f16_rects``, which samples relative to every image's own rectangle so that an image
+        off the canvas origin rounds as its own forward does."""
         self.compute_dtype = torch.float16 if enable else torch.float32
         self.drop_plans()
         return self

@@ -175,6 +175,8 @@ def _declare(lib):
     lib.cn_dcn_v2_route.argtypes = lib.cn_dcn_v2_forward_nhwc.argtypes + [ctypes.POINTER(DcnRouteInfo)]
     lib.cn_dcn_v2_forward_nhwc_f16.restype = i
     lib.cn_dcn_v2_forward_nhwc_f16.argtypes = [vp, vp, vp, vp, i, vp, vp, vp] + [i] * 8 + [vp, sz, vp]
+    lib.cn_dcn_v2_forward_nhwc_f16_rects.restype = i
+    lib.cn_dcn_v2_forward_nhwc_f16_rects.argtypes = [vp, vp, vp, vp, i, vp, vp, vp] + [i] * 8 + [vp, sz, vp, i, vp]
     lib.cn_dcn_v2_route_f16.restype = i
     lib.cn_dcn_v2_route_f16.argtypes = lib.cn_dcn_v2_forward_nhwc_f16.argtypes + [ctypes.POINTER(DcnRouteInfo)]
     lib.cn_pack_deconv4x4s2_weight.restype = i
@@ -231,6 +233,8 @@ def _declare(lib):
     lib.cn_upsample2x_add_f32.argtypes = [vp, vp, vp, i, i, i, i, vp]
     lib.cn_mask_rects_f32.restype = i
     lib.cn_mask_rects_f32.argtypes = [vp, i, i, i, i, i, i, vp, i, vp]
+    lib.cn_mask_rects_f16.restype = i
+    lib.cn_mask_rects_f16.argtypes = [vp, i, i, i, i, i, i, vp, i, vp]
     lib.cn_mask_rects_nchw_f32.restype = i
     lib.cn_mask_rects_nchw_f32.argtypes = [vp, i, i, i, i, vp, i, f, vp]
     lib.cn_heads3x3_1x1_f32.restype = i

@@ -581,6 +581,27 @@ int cn_mask_rects_f32(void *t_nhwc, int B, int H, int W, int pitch, int c_off, i
                       const cn_rect *rects_dev, int shift, void *stream);
 int cn_mask_rects_nchw_f32(float *t, int B, int C, int H, int W, const cn_rect *rects_dev,
                            int shift, float fill, void *stream);
+/* cn_mask_rects_f16: the same rectangle rule on a (B, H, W, pitch) tensor of 2-byte elements (halves; +0.0 is
+ * written); pitch, c_off and C count halves.  Channels [c_off, c_off + C) are taken in whole 8-CHANNEL groups
+ * (16 bytes; C is rounded up to the next group, cut at the pitch) -- not the 32-channel groups of the fp32
+ * entry: a half plan concatenates in place with members of 16 and 32 channels side by side in one buffer, and
+ * a wider rounding would clear the neighbouring member.  pitch, c_off and the cleared width multiples of 8 and
+ * the first cleared element 16-byte aligned, CN_ERR_ALIGN otherwise; CN_ERR_NULL / CN_ERR_SHAPE as above. */
+int cn_mask_rects_f16(void *t_nhwc, int B, int H, int W, int pitch, int c_off, int C,
+                      const cn_rect *rects_dev, int shift, void *stream);
+/* cn_dcn_v2_forward_nhwc_f16 on a canvas batch: the same arguments, checks, route and forms, plus the batch's
+ * rectangle table and the level of the tensor (rect_shift 0 .. 30, CN_ERR_SHAPE otherwise).  Image b's sampling
+ * positions are formed relative to its rectangle's origin (rects_dev[b].x0 >> rect_shift, .y0 >> rect_shift,
+ * clipped to the tensor) and moved back by whole pixels, so the bilinear fractions -- and every rounding behind
+ * them -- are those of the image's own forward wherever its rectangle lies on the canvas.  What lies outside
+ * the rectangle must be zero (cn_mask_rects_f16): it stands in for the samples the image's own forward drops.
+ * A null table is cn_dcn_v2_forward_nhwc_f16, bit for bit. */
+int cn_dcn_v2_forward_nhwc_f16_rects(const void *input_nhwc, const void *weight_packed, const float *bias,
+                                     const float *offset_mask_nhwc, int om_pitch, const float *scale,
+                                     const float *shift, void *output_nhwc, int out_pitch, int B, int Cin,
+                                     int H, int W, int Cout, int mask_sigmoid, int relu, void *workspace,
+                                     size_t workspace_bytes, const cn_rect *rects_dev, int rect_shift,
+                                     void *stream);
 /* Nearest x2 up-sampling + add of the skip branch (large_hourglass.py:102-109, 163-174). */
 int cn_upsample2x_add_f32(const float *x, const float *add, float *y, int B, int H, int W,
                           int C, void *stream);
