@@ -30,10 +30,22 @@
 //              with ballots; orig[] records which row now sits where, and the decayed scores are written
 //              afterwards, at the positions their rows occupy.  tests/test_tta_host.py holds this form
 //              equal to cn_soft_nms_f32 on seeded arrays before any GPU run.
-#include "cn_common.h"
+//
+// The tile merge of run_tiles (cn_ctdet_tiles_merge_f32; post_process.ctdet_tiles_results is its host
+// restatement) is the same merge with tiles in the place of scales, for frames whose rows no longer fit one
+// workgroup's LDS: three launches, the class-grouped rows of a frame in global memory between them.
+//   tiles_group_kernel  one workgroup per frame: the core filter (a row survives when its centre lies in its
+//                       tile's core), a class histogram per wave, the scan to the class bounds and a stable
+//                       scatter -- exdet_post_kernel's counting sort with (tile, row) in the place of rows;
+//   tiles_nms_kernel    one wave per (frame, class): the segment into NmsLds at o = 0, soft_nms_segment, back;
+//   tiles_cut_kernel    one workgroup per frame: the max_per_frame-th largest score by cn_select.h's
+//                       radix_select over distinct (score, position) keys, then the ordered compaction.
+// What bounds a frame is the longest class segment (CN_MERGE_MAX_ROWS, the LDS of one soft-NMS), not its rows.
+#include "cn_select.h"
 
 // hipcc defaults to -ffp-contract=fast-honor-pragmas: the float64 point map and the float32 chains below are
-// the host's operations one by one only without FMA contraction, anywhere in this file.
+// the host's operations one by one only without FMA contraction, anywhere in this file (cn_select.h sets the
+// same pragma for the files that include it; it is repeated here because this file depends on it by itself).
 #pragma clang fp contract(off)
 
 namespace {
@@ -646,6 +658,224 @@ __global__ __launch_bounds__(MG_THREADS) void exdet_post_kernel(const float *__r
     // rows behind the last bound: zeros, so that the array is a function of the input
     for (int e = total * 5 + t; e < R * 5; e += MG_THREADS) out[e] = 0.f;
 }
+// ------------------------------------------------------------------------------------------------
+// run_tiles: the tile merge (see the head of the file)
+// ------------------------------------------------------------------------------------------------
+// Row e = t * K + r of frame b (row r of tile t as cn_ctdet_post_process_f32 left it) -> its class when it is a
+// row of a class (r in front of the tile's last bound) and its centre lies in the tile's core, else -1.
+// cx = (x1 + x2) * 0.5f, lo <= cx < hi in float32: the host's comparison; a NaN centre fails it.
+__device__ __forceinline__ int tile_row_class(const float *__restrict__ rows, const int32_t *__restrict__ bounds,
+                                              const float *__restrict__ cores, int b, int T, int K, int nc, int e)
+{
+    const int t = e / K, r = e - t * K;
+    const int32_t *bd = bounds + ((size_t)b * T + t) * ((size_t)nc + 1);
+    if (r >= bd[nc]) return -1;
+    const float *s = rows + (((size_t)b * T + t) * K + r) * 5;
+    const float cx = (s[0] + s[2]) * 0.5f, cy = (s[1] + s[3]) * 0.5f;
+    const float *co = cores + (size_t)t * 4;
+    if (!(cx >= co[0] && cx < co[2] && cy >= co[1] && cy < co[3])) return -1;
+    int lo = 0, hi = nc;                 // the last c with bd[c] <= r
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (bd[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Launch 1.  grouped (B, T * K, 5): per class the survivors of all tiles in tile order, each tile's rows in
+// their order (the np.concatenate of the host); segs (B, nc + 1): the class bounds in it.  Every wave owns a
+// contiguous quarter of the frame's T * K rows in whole steps of 64, as in exdet_post_kernel; the class of a
+// row is computed again in step 3 instead of being kept (T * K int16 would not fit next to the histograms).
+// A frame with a class segment above MG_ROWS is not merged: status[b] = 1, its out_bounds zero.
+struct TilesGroupLds {
+    int hist[MG_WAVES][MG_CLASSES + 1];
+    int red[MG_WAVES];
+    int over;
+};
+__global__ __launch_bounds__(MG_THREADS) void tiles_group_kernel(const float *__restrict__ rows,
+                                                                 const int32_t *__restrict__ bounds, int T, int K,
+                                                                 int nc, const float *__restrict__ cores,
+                                                                 float *__restrict__ grouped,
+                                                                 int32_t *__restrict__ segs,
+                                                                 int32_t *__restrict__ out_bounds,
+                                                                 int32_t *__restrict__ status)
+{
+    __shared__ TilesGroupLds L;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & (CN_WAVE - 1), w = t / CN_WAVE;
+    const int R = T * K;
+    const int per = (R + MG_THREADS - 1) / MG_THREADS * CN_WAVE;
+    const int w0 = min(w * per, R), w1 = min(w0 + per, R);
+    for (int c = t; c < MG_WAVES * (MG_CLASSES + 1); c += MG_THREADS) (&L.hist[0][0])[c] = 0;
+    if (t == 0) L.over = 0;
+    __syncthreads();
+    // 1. the survivors' class histograms (LDS atomics: counts only)
+    for (int e = w0 + lane; e < w1; e += CN_WAVE) {
+        const int c = tile_row_class(rows, bounds, cores, b, T, K, nc, e);
+        if (c >= 0) atomicAdd(&L.hist[w][c], 1);
+    }
+    __syncthreads();
+    // 2. class bounds: exclusive scan of the class totals, a chunk of classes per thread; hist[w][c] becomes
+    //    the position of wave w's first row of class c
+    const int cper = (nc + MG_THREADS) / MG_THREADS, c0 = min(t * cper, nc), c1 = min(c0 + cper, nc);
+    int n = 0;
+    for (int c = c0; c < c1; ++c)
+        for (int k = 0; k < MG_WAVES; ++k) n += L.hist[k][c];
+    int total, run = block_exclusive_scan(n, L.red, total);
+    int32_t *sg = segs + (size_t)b * (nc + 1);
+    bool over = false;
+    for (int c = c0; c < c1; ++c) {
+        const int first = run;
+        sg[c] = run;
+        for (int k = 0; k < MG_WAVES; ++k) {
+            const int h = L.hist[k][c];
+            L.hist[k][c] = run;
+            run += h;
+        }
+        over |= run - first > MG_ROWS;
+    }
+    if (t == 0) sg[nc] = total;
+    if (over) L.over = 1;                // (every writer writes 1)
+    __syncthreads();
+    if (L.over) {                        // the same word for every thread: the whole workgroup leaves
+        if (t == 0) status[b] = 1;
+        for (int c = t; c <= nc; c += MG_THREADS) out_bounds[(size_t)b * (nc + 1) + c] = 0;
+        return;
+    }
+    if (t == 0) status[b] = 0;
+    // 3. positions by ballot, wave by wave in input order (hist[w][.] is wave w's alone from here on)
+    int *cur = L.hist[w];
+    float *out = grouped + (size_t)b * R * 5;
+    for (int base = w0; base < w1; base += CN_WAVE) {
+        const int e = base + lane;
+        const int c = e < w1 ? tile_row_class(rows, bounds, cores, b, T, K, nc, e) : -1;
+        int pos = -1;
+        unsigned long long todo = __ballot(c >= 0);
+        while (todo) {                                          // wave-uniform: one class of the step per turn
+            const int leader = __builtin_ctzll(todo);
+            const int cl = __shfl(c, leader);
+            const unsigned long long m = __ballot(c == cl);
+            if (c == cl) pos = cur[cl] + __popcll(m & ((1ull << lane) - 1ull));
+            wave_sync();
+            if (lane == leader) cur[cl] += __popcll(m);
+            wave_sync();
+            todo &= ~m;
+        }
+        if (pos < 0 || pos >= R) continue;
+        const int tl = e / K;
+        const float *s = rows + (((size_t)b * T + tl) * K + (e - tl * K)) * 5;
+        float *o = out + (size_t)pos * 5;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) o[k] = s[k];
+    }
+}
+
+// Launch 2.  One wave per (frame, class): a segment of two rows or more goes through soft_nms_segment in LDS
+// and back, in place.  Segments of different workgroups do not overlap.
+__global__ __launch_bounds__(CN_WAVE) void tiles_nms_kernel(float *__restrict__ grouped,
+                                                            const int32_t *__restrict__ segs,
+                                                            const int32_t *__restrict__ status, int R, int nc)
+{
+    __shared__ NmsLds L;
+    const int b = blockIdx.x / nc, c = blockIdx.x - b * nc, lane = threadIdx.x;
+    if (status[b]) return;
+    const int32_t *sg = segs + (size_t)b * (nc + 1);
+    const int o = sg[c], n = sg[c + 1] - o;
+    if (n <= 1 || n > MG_ROWS || o < 0 || o + n > R) return;
+    float *g = grouped + ((size_t)b * R + o) * 5;
+    for (int p = lane; p < n; p += CN_WAVE) {
+        const float *s = g + (size_t)p * 5;
+        L.box[0][p] = s[0];
+        L.box[1][p] = s[1];
+        L.box[2][p] = s[2];
+        L.box[3][p] = s[3];
+        L.sc[p] = s[4];
+    }
+    wave_sync();
+    soft_nms_segment<false>(L, 0, n, lane, nullptr);
+    wave_sync();
+    for (int p = lane; p < n; p += CN_WAVE) {
+        float *d = g + (size_t)p * 5;
+        d[0] = L.box[0][p];
+        d[1] = L.box[1][p];
+        d[2] = L.box[2][p];
+        d[3] = L.box[3][p];
+        d[4] = L.sc[p];
+    }
+}
+
+// Launch 3.  thresh = the max_per_frame-th largest score, duplicates counted: radix_select takes the
+// max_per_frame largest of the DISTINCT keys (score key, ~position), and the smallest score among them is that
+// score.  Then score >= thresh in array order, a contiguous chunk of rows per thread; the thread that passes a
+// class bound on its way writes the bound's new value.
+struct TilesCutLds {
+    SelShared sel;
+    int seg[MG_CLASSES + 1];
+    int red[MG_WAVES];
+    uint32_t low[MG_WAVES];
+};
+__global__ __launch_bounds__(MG_THREADS) void tiles_cut_kernel(const float *__restrict__ grouped,
+                                                               const int32_t *__restrict__ segs,
+                                                               const int32_t *__restrict__ status, int R, int nc,
+                                                               int max_per_frame, float *__restrict__ out_rows,
+                                                               int32_t *__restrict__ out_bounds)
+{
+    __shared__ TilesCutLds L;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & (CN_WAVE - 1), w = t / CN_WAVE;
+    if (status[b]) return;
+    for (int c = t; c <= nc; c += MG_THREADS) L.seg[c] = segs[(size_t)b * (nc + 1) + c];
+    __syncthreads();
+    const int total = min(max(L.seg[nc], 0), R);
+    const float *g = grouped + (size_t)b * R * 5;
+    const bool cut = total > max_per_frame;
+    float thresh = 0.f;
+    if (cut) {                           // (the same for every thread)
+        auto for_each = [&](auto &&f) {
+            for (int r = t; r < total; r += MG_THREADS) {
+                const uint32_t k = f2key(g[(size_t)r * 5 + 4]);
+                f(((u64)k << 32) | (uint32_t)~(uint32_t)r, k == KEY_ZERO);
+            }
+        };
+        u64 prefix, mask;
+        radix_select<MG_THREADS>(for_each, (uint32_t)max_per_frame, L.sel, prefix, mask);
+        uint32_t low = 0xffffffffu;
+        for_each([&](u64 k, bool) {
+            if ((k & mask) >= prefix) low = min(low, (uint32_t)(k >> 32));
+        });
+        for (int o = CN_WAVE / 2; o > 0; o >>= 1) low = min(low, (uint32_t)__shfl_xor((int)low, o));
+        if (lane == 0) L.low[w] = low;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MG_WAVES; ++k) low = min(low, L.low[k]);
+        thresh = key2f(low);
+    }
+    const int per = (total + MG_THREADS - 1) / MG_THREADS, r0 = min(t * per, total), r1 = min(r0 + per, total);
+    int n = 0, kept;
+    for (int r = r0; r < r1; ++r) n += (!cut || g[(size_t)r * 5 + 4] >= thresh) ? 1 : 0;
+    int run = block_exclusive_scan(n, L.red, kept);
+    int cnext = 0;                       // the first class bound at or behind r0
+    {
+        int lo = -1, hi = nc + 1;        // seg[] ascends: the first c with seg[c] >= r0
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (L.seg[mid] >= r0) hi = mid; else lo = mid;
+        }
+        cnext = hi;
+    }
+    float *ob = out_rows + (size_t)b * R * 5;
+    int32_t *obd = out_bounds + (size_t)b * (nc + 1);
+    for (int r = r0; r < r1; ++r) {
+        while (cnext <= nc && L.seg[cnext] == r) obd[cnext++] = run;
+        const float *s = g + (size_t)r * 5;
+        if (!cut || s[4] >= thresh) {
+            float *d = ob + (size_t)run * 5;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) d[k] = s[k];
+            ++run;
+        }
+    }
+    for (int c = t; c <= nc; c += MG_THREADS)
+        if (L.seg[c] >= total) obd[c] = kept;
+}
 }  // namespace
 
 extern "C" int cn_ctdet_post_process_f32(const float *dets, int B, int K, int num_classes,
@@ -736,6 +966,42 @@ extern "C" int cn_exdet_merge_f32(const float *rows, const int32_t *bounds, int 
     if ((long long)S * R > (1 << 24)) return CN_ERR_SHAPE;        // (S * R is an int inside the kernel)
     hipLaunchKernelGGL(class_merge_kernel<true>, dim3(B), dim3(MG_THREADS), 0, (hipStream_t)stream, rows, bounds, S,
                        B, R, num_classes, 1, max_per_image, out_rows, out_bounds, status);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+static size_t tiles_grouped_bytes(int B, int T, int K) { return cn_align_up((size_t)B * T * K * 5 * sizeof(float), 16); }
+
+extern "C" size_t cn_ctdet_tiles_merge_workspace_bytes(int B, int T, int K, int num_classes)
+{
+    if (B <= 0 || T <= 0 || K <= 0 || num_classes <= 0) return 0;
+    return tiles_grouped_bytes(B, T, K) + cn_align_up((size_t)B * (num_classes + 1) * sizeof(int32_t), 16);
+}
+
+extern "C" int cn_ctdet_tiles_merge_f32(const float *rows, const int32_t *bounds, int B, int T, int K,
+                                        int num_classes, const float *cores_dev, int apply_nms, int max_per_frame,
+                                        float *out_rows, int32_t *out_bounds, int32_t *status, void *workspace,
+                                        size_t workspace_bytes, void *stream)
+{
+    if (!rows || !bounds || !cores_dev || !out_rows || !out_bounds || !status || !workspace) return CN_ERR_NULL;
+    if (B <= 0 || T <= 0 || K <= 0 || num_classes <= 0 || max_per_frame <= 0) return CN_ERR_SHAPE;
+    if (K > PP_KMAX || (long long)T * K > CN_TILES_MAX_ROWS || num_classes > CN_MERGE_MAX_CLASSES) return CN_ERR_SHAPE;
+    if ((long long)B * num_classes > 0x7fffffffLL) return CN_ERR_SHAPE;      // (the grid of the soft-NMS launch)
+    if (workspace_bytes < cn_ctdet_tiles_merge_workspace_bytes(B, T, K, num_classes)) return CN_ERR_WORKSPACE;
+    if (!cn_aligned16(workspace)) return CN_ERR_ALIGN;
+    float *grouped = reinterpret_cast<float *>(workspace);
+    int32_t *segs = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + tiles_grouped_bytes(B, T, K));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(tiles_group_kernel, dim3(B), dim3(MG_THREADS), 0, st, rows, bounds, T, K, num_classes,
+                       cores_dev, grouped, segs, out_bounds, status);
+    CN_CHECK_LAUNCH();
+    if (T > 1 || apply_nms) {
+        hipLaunchKernelGGL(tiles_nms_kernel, dim3((unsigned)B * num_classes), dim3(CN_WAVE), 0, st, grouped, segs,
+                           status, T * K, num_classes);
+        CN_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(tiles_cut_kernel, dim3(B), dim3(MG_THREADS), 0, st, grouped, segs, status, T * K,
+                       num_classes, max_per_frame, out_rows, out_bounds);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

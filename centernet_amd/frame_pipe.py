@@ -1,5 +1,6 @@
 """The frame pipe of ``run_frames`` / ``run_frames_stream`` (``FramePipe``), its form for batches of images of
-mixed sizes (``ImagePipe`` with ``ImageTables``: ``run_images`` / ``run_images_stream``) and the base class of a
+mixed sizes (``ImagePipe`` with ``ImageTables``: ``run_images`` / ``run_images_stream``), its form for frames cut
+into overlapping tiles (``TilePipe``: ctdet's ``run_tiles`` / ``run_tiles_stream``) and the base class of a
 task's device tail (``DeviceTail``): what runs behind the decode of every test scale, on the launch stream, so
 that the host only slices pinned rows.  The task classes (``detectors/*.py``) supply a ``DeviceTail``
 subclass each -- the admission test, the kernel calls and the result shape -- through one hook,
@@ -595,3 +596,82 @@ class ImagePipe(FramePipe):
         if self.canvas:
             return self.det._run_images_sync_keep_res(frames, self.scales, **kw)
         return self.det._run_images_sync(frames, self.scales, **kw)
+
+
+class TilePipe(FramePipe):
+    """``FramePipe`` for frames much larger than the network input (``run_tiles`` / ``run_tiles_stream``, ctdet,
+    DESIGN.md 3.6b): the B frames of (H, W) are cut into T overlapping (input_h, input_w) tiles each at native
+    resolution (``tiles.tile_grid``), tile t of frame b is image b * T + t of the TILE BATCH, and the pipe's
+    levels are the chunks of ``C = min(tile_batch, B * T)`` tiles of that batch, not test scales: every chunk
+    runs the ONE plan of batch C, a short last chunk padded to C in a batch tensor of its own whose surplus
+    slices are zero from the start and whose surplus rows nobody reads.  Static on the device: one
+    ``cn_image_desc`` per tile, all of a frame's pointing into that frame with the tile's own matrix, so a
+    chunk's pre-process is one ``cn_warp_normalize_u8_f32_ragged`` launch on its slice of the table; the
+    (B * T, 6) output grid -> frame maps; the (T, 4) cores.  The tail (``TilesTail``) post-processes each chunk
+    into its slice of the (B * T, K, 5) rows and merges the frames' tiles behind the last chunk
+    (``cn_ctdet_tiles_merge_f32``).  Range digests, staging, the copy stream, NV12 and both hand-back routes
+    are ``FramePipe``'s; the synchronous path is ``det._run_tiles_sync``."""
+
+    def __init__(self, det, B, H, W, overlap, margin, tile_batch, max_per_frame, depth, pixel_format='bgr'):
+        from .tiles import tile_grid, tile_maps
+        opt, dev = det.opt, det.opt.device
+        if not (0 < H <= 32767 and 0 < W <= 32767):
+            raise ValueError("run_tiles needs frames of 1 .. 32767 rows and columns, got %d x %d" % (H, W))
+        th, tw = int(opt.input_h), int(opt.input_w)
+        self.grid = grid = tile_grid(H, W, th, tw, overlap, margin)
+        self.overlap, self.margin, self.tile_batch = overlap, margin, int(tile_batch)
+        self.max_per_frame = int(max_per_frame)
+        self.T, self.N = grid.T, B * grid.T
+        self.C = C = min(self.tile_batch, self.N)
+        chunks = [(lo, min(lo + C, self.N)) for lo in range(0, self.N, C)]
+        self._setup(det, B, (1.0,) * len(chunks), False, depth)      # one digest per level, i.e. per chunk
+        self.H, self.W, self.pixel_format = H, W, pixel_format
+        self.frame_shape = (H * 3 // 2, W) if pixel_format == 'nv12' else (H, W, 3)
+        metas, dst_to_src, to_source = tile_maps(grid, opt.down_ratio)
+        self.tile_metas = metas * B                                  # image b * T + t
+        desc = np.zeros((self.N,), native.IMAGE_DESC)
+        for b in range(B):
+            d = desc[b * grid.T:(b + 1) * grid.T]
+            d['offset'], d['H'], d['W'], d['pitch'] = b * H * W * 3, H, W, 3 * W
+            d['dst_to_src'] = dst_to_src
+        self.desc_dev = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(dev)
+        # (not per slot as ``ImagePipe``'s: the maps of a tile pipe never change; the tail addresses its chunk)
+        self.to_source_dev = torch.from_numpy(np.ascontiguousarray(np.tile(to_source, (B, 1)))).to(dev)
+        self.cores_dev = torch.from_numpy(np.ascontiguousarray(grid.cores)).to(dev)
+        shared = torch.empty((C, 3, th, tw), device=dev, dtype=torch.float32)
+        self.levels = []
+        for lo, hi in chunks:
+            short = hi - lo < C
+            self.levels.append(types.SimpleNamespace(
+                scale=1.0, g=None, meta=None, lo=lo, hi=hi, n=hi - lo,
+                batch=torch.zeros((C, 3, th, tw), device=dev, dtype=torch.float32) if short else shared))
+        self.scale, self.batch = 1.0, self.levels[0].batch
+        self.pinned_in = [torch.empty((B,) + self.frame_shape, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        self.np_in = [t.numpy() for t in self.pinned_in]
+        self.dev_in = [torch.empty((B,) + self.frame_shape, dtype=torch.uint8, device=dev) for _ in range(depth)]
+        if pixel_format == 'nv12':
+            self.bgr = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        self._setup_tail()
+
+    def _setup_tail(self):
+        self.tail = self.det._tiles_tail(self)
+        self.dets_host = None if self.tail is not None else [[None] * len(self.levels) for _ in range(self.depth)]
+
+    def _pre_process(self, slot, level, stream):
+        """On the launch stream: the tiles of chunk ``level`` out of the uploaded frames, one launch."""
+        lv = self.levels[level]
+        src = self.dev_in[slot] if self.bgr is None else self.bgr
+        descs = ctypes.c_void_p(self.desc_dev.data_ptr() + lv.lo * native.IMAGE_DESC.itemsize)
+        native.check(native.lib().cn_warp_normalize_u8_f32_ragged(
+            native.ptr(src), descs, lv.n, int(lv.batch.shape[2]), int(lv.batch.shape[3]), self.mean, self.std, 0,
+            native.ptr(lv.batch), stream), "cn_warp_normalize_u8_f32_ragged")
+
+    def _run_sync(self, frames, **kw):
+        if self.pixel_format == 'nv12':
+            frames = [nv12_to_bgr(f) for f in frames]
+        return self.det._run_tiles_sync(frames, self.overlap, self.margin, self.tile_batch, self.max_per_frame)
+
+    def _host_tail(self, slot, sel, kw):
+        """A pipe without a device tail: the host tile merge on the raw detections copied out per chunk."""
+        dets = np.concatenate([d.numpy()[:lv.n] for d, lv in zip(self.dets_host[slot], self.levels)], axis=0)
+        return self.det._tiles_host_tail(dets, self.grid, self.B, self.max_per_frame)

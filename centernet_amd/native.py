@@ -28,6 +28,7 @@ CONV_X_PLAIN, CONV_Y_PLAIN, CONV_R_PLAIN, CONV_STEM_F32S, CONV_STEM_MAXPOOL = 1,
 CONV_STEM_Y_F32S = 32
 MERGE_MAX_ROWS = 2048       # CN_MERGE_MAX_ROWS: S * K rows per image that the merge kernels take
 MERGE_MAX_CLASSES = 1024    # CN_MERGE_MAX_CLASSES
+TILES_MAX_ROWS = 65536      # CN_TILES_MAX_ROWS: T * K rows per frame that cn_ctdet_tiles_merge_f32 takes
 # flag bits of the decode entries: the #defines of the same names in include/centernet_amd.h
 # (tests/test_decode_route_host.py compares them)
 DECODE_SIGMOID = 1          # CN_DECODE_SIGMOID
@@ -262,6 +263,10 @@ def _declare(lib):
     lib.cn_ctdet_post_process_f32.argtypes = [vp, i, i, i, vp, i, ctypes.c_float, vp, vp, vp]
     lib.cn_ctdet_merge_f32.restype = i
     lib.cn_ctdet_merge_f32.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp]
+    lib.cn_ctdet_tiles_merge_workspace_bytes.restype = sz
+    lib.cn_ctdet_tiles_merge_workspace_bytes.argtypes = [i, i, i, i]
+    lib.cn_ctdet_tiles_merge_f32.restype = i
+    lib.cn_ctdet_tiles_merge_f32.argtypes = [vp, vp, i, i, i, i, vp, i, i, vp, vp, vp, vp, sz, vp]
     lib.cn_exdet_post_process_f32.restype = i
     lib.cn_exdet_post_process_f32.argtypes = [vp, i, i, i, i, vp, i, ctypes.c_float, vp, vp, vp]
     lib.cn_exdet_merge_f32.restype = i

@@ -177,6 +177,50 @@ def ctdet_results_batch(dets, metas, num_classes, scale=1, max_per_image=100):
     return out
 
 
+def ctdet_merge(detections, num_classes, nms, max_per_image):
+    """``CtdetDetector.merge_outputs`` as a function (detectors/ctdet.py; reference ctdet.py:58-73):
+    ``detections`` = [{class: (n, 5) float32}] of one image in merge order (test scales, or the tiles of
+    ``run_tiles``), ``nms`` = the reference's ``len(self.scales) > 1 or self.opt.nms``.  Per class the
+    concatenation, soft-NMS when ``nms`` (in place: the whole array is kept), then the ``max_per_image`` best
+    over all classes by score threshold -- ``>=``, so ties may exceed the cap."""
+    classes = range(1, num_classes + 1)
+    if len(detections) == 1 and not nms:
+        results = {c: detections[0][c] for c in classes}     # nothing to merge, nothing edited
+    else:
+        results = {c: np.concatenate([d[c] for d in detections], axis=0).astype(np.float32)
+                   for c in classes}
+    if nms:
+        from .soft_nms import soft_nms
+        for c in classes:
+            soft_nms(results[c], Nt=0.5, method=2)
+    scores = np.hstack([results[c][:, 4] for c in classes])
+    if len(scores) > max_per_image:
+        kth = len(scores) - max_per_image
+        thresh = np.partition(scores, kth)[kth]
+        for c in classes:
+            results[c] = results[c][results[c][:, 4] >= thresh]
+    return results
+
+
+def ctdet_tiles_results(per_tile, cores, num_classes, nms, max_per_frame):
+    """The tile merge of ``run_tiles`` for one frame -- the specification ``cn_ctdet_tiles_merge_f32`` restates
+    on the device.  ``per_tile``: [T] ``post_process`` results {class: (n, 5) float32} in FRAME pixels, in tile
+    order; ``cores`` (T, 4) float32 (``tiles.tile_grid``).  A row of tile t survives when its centre lies in
+    the tile's core (``tiles.in_core``: float32, lower edges closed, upper edges open); the survivors go through
+    ``ctdet_merge`` with the tiles in the place of test scales: soft-NMS when ``T > 1 or nms``, then the
+    ``max_per_frame`` cut with ties kept."""
+    from .tiles import in_core
+    T = len(per_tile)
+    kept = []
+    for tile, core in zip(per_tile, cores):
+        one = {}
+        for c in range(1, num_classes + 1):
+            rows = np.asarray(tile[c], np.float32).reshape(-1, 5)
+            one[c] = rows[in_core(rows, core)]
+        kept.append(one)
+    return ctdet_merge(kept, num_classes, T > 1 or bool(nms), max_per_frame)
+
+
 def ddd_norm_table(mean, std):
     """(3, 256) float32: ``(level / 255 - mean[c]) / std[c]`` with the ddd class's float32 chain
     (detectors/ddd.py:45-46) for every uint8 level -- what ``DddDetector.pre_process`` indexes on the

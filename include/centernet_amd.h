@@ -722,6 +722,31 @@ int cn_ctdet_post_process_f32(const float *dets, int B, int K, int num_classes, 
 #define CN_MERGE_MAX_CLASSES 1024
 int cn_ctdet_merge_f32(const float *rows, const int32_t *bounds, int S, int B, int K, int num_classes,
                        int apply_nms, int max_per_image, float *out_rows, int32_t *out_bounds, void *stream);
+/* The tile merge of run_tiles (post_process.ctdet_tiles_results on the device, bit for bit): the ctdet merge with
+ * the T overlapping tiles of a frame in the place of test scales, for frames with more rows than one workgroup
+ * holds.  rows (B*T, K, 5) / bounds (B*T, num_classes + 1): cn_ctdet_post_process_f32's output of tile t of
+ * frame b in image b*T + t, rows in FRAME pixels.  cores_dev (T, 4) float32 on the device: [x_lo, y_lo, x_hi,
+ * y_hi] of tile t's core with the margin applied, -inf / +inf at the frame's edges.  Per frame:
+ *   a row of tile t survives when its centre cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f (float32) has
+ *   x_lo <= cx < x_hi and y_lo <= cy < y_hi; per class the survivors of all tiles in tile order, each tile's
+ *   rows in their order; when T > 1 or apply_nms, Gaussian soft-NMS of every class as cn_ctdet_merge_f32 runs
+ *   it (the whole in-place array kept); then, when the frame has more than max_per_frame rows, the rows whose
+ *   score is >= the max_per_frame-th largest score (duplicates counted, ties kept), in order.
+ * out_rows (B, T*K, 5) / out_bounds (B, num_classes + 1): the format of cn_ctdet_merge_f32.  status (B) int32.
+ * Three launches at most (group, soft-NMS per (frame, class), cut), no host synchronisation, no floating-point
+ * atomics: the result is a function of the input.  The class-grouped rows lie in the workspace between the
+ * launches (cn_ctdet_tiles_merge_workspace_bytes; 16-byte aligned, CN_ERR_ALIGN otherwise; CN_ERR_NULL without
+ * one, CN_ERR_WORKSPACE for a short one).  Limits: K <= 128, T*K <= CN_TILES_MAX_ROWS, num_classes <=
+ * CN_MERGE_MAX_CLASSES, CN_ERR_SHAPE above.  What bounds a frame is one class: a frame in which a class segment
+ * has more than CN_MERGE_MAX_ROWS survivors (the LDS of one soft-NMS) is not merged -- status[b] != 0, its
+ * bounds all zero, its rows undefined; every other frame has status[b] == 0 and its result (the convention of
+ * cn_exdet_merge_f32). */
+#define CN_TILES_MAX_ROWS 65536
+size_t cn_ctdet_tiles_merge_workspace_bytes(int B, int T, int K, int num_classes);
+int cn_ctdet_tiles_merge_f32(const float *rows, const int32_t *bounds, int B, int T, int K, int num_classes,
+                             const float *cores_dev, int apply_nms, int max_per_frame, float *out_rows,
+                             int32_t *out_bounds, int32_t *status, void *workspace, size_t workspace_bytes,
+                             void *stream);
 /* exdet task, the device tail of its frame pipe (detectors/exdet.py:51-81; reference exdet.py:86-123).
  * cn_exdet_post_process_f32: ExdetDetector.post_process, the `score > 0` filter and the per-class selection of
  * merge_outputs for one test scale of a batch.  dets (B, R, 14): the raw rows of cn_exct_decode_f32 /
