@@ -2,7 +2,9 @@
 heat-map + box size + 17 joint offsets, optional joint heat-maps / sub-pixel offsets, decoded
 by the fused ``cn_multi_pose_decode_f32`` kernels (``run_batch``: top-K on ``hm``, the ``wh`` / ``hps`` /
 ``reg`` heads at the K cells only, ``cn_multi_pose_heads_at_cells_f32``, then the joint match on the dense
-``hm_hp`` / ``hp_offset``, ``cn_multi_pose_match_f32``)."""
+``hm_hp`` / ``hp_offset``, ``cn_multi_pose_match_f32``).  New surface: ``run_batch``, ``run_frames`` and ``run_tiles``
+(frames much larger than the network input, tiled and merged on the device)."""
+import math
 import time
 
 import numpy as np
@@ -11,9 +13,10 @@ import torch
 from .. import native
 from ..decode import multi_pose_decode, multi_pose_decode_at_cells
 from ..frame_pipe import DeviceTail
-from ..post_process import multi_pose_post_process
+from ..post_process import multi_pose_post_process, multi_pose_tiles_results
 from ..utils import flip_average, flip_average_batch
 from .base_detector import BaseDetector
+from .tiles_mixin import TilesMixin
 
 ROW = 39  # [x1, y1, x2, y2, score, 17 x (x, y)]
 
@@ -30,7 +33,7 @@ def deferred_pose_heads(opt):
     return ('wh', 'hps')
 
 
-class MultiPoseDetector(BaseDetector):
+class MultiPoseDetector(TilesMixin, BaseDetector):
     def __init__(self, opt):
         super(MultiPoseDetector, self).__init__(opt)
         self.flip_idx = opt.flip_idx
@@ -156,6 +159,111 @@ class MultiPoseDetector(BaseDetector):
             from ..soft_nms import soft_nms_39
             soft_nms_39(people, Nt=0.5, method=2)
         return {1: people if arrays else people.tolist()}
+
+
+    # ------------------------------------------------------------------ run_tiles: large frames, tiled
+    @staticmethod
+    def _tiles_min_score(min_score):
+        """``min_score`` of ``run_tiles``: None, or a finite number -> None / float."""
+        if min_score is None:
+            return None
+        if isinstance(min_score, (bool, str, bytes)) or not isinstance(min_score, (int, float, np.integer, np.floating)) \
+                or not math.isfinite(min_score):
+            raise ValueError("run_tiles: min_score must be a finite number or None, got %r" % (min_score,))
+        return float(min_score)
+
+    def _tiles_tail(self, pipe):
+        return PoseTilesTail(pipe) if PoseTilesTail.admits(pipe) else None
+
+    def _tiles_host_tail(self, dets, grid, B, max_per_frame, min_score=None, arrays=False):
+        """Host tail of ``run_tiles``: (B * T, K, 40) host raw detections of the tile batch -> per frame ``{1:
+        rows}`` in frame pixels: ``_post_batch`` with the tile metas, then ``post_process.multi_pose_tiles_results``
+        (core filter, ``min_score``, ``merge_outputs``' soft-NMS with tiles for scales, the ``max_per_frame`` cut)."""
+        from ..tiles import tile_maps
+        metas = tile_maps(grid, self.opt.down_ratio)[0]
+        posts = self._post_batch(np.asarray(dets), metas * B, 1.0)
+        out = []
+        for b in range(B):
+            rows = multi_pose_tiles_results([p[1] for p in posts[b * grid.T:(b + 1) * grid.T]], grid.cores,
+                                            self.opt.nms, max_per_frame, min_score)[1]
+            out.append({1: rows if arrays else rows.tolist()})
+        return out
+
+    def run_tiles(self, frames, overlap=None, margin=None, tile_batch=32, max_per_frame=None, pixel_format='bgr',
+                  arrays=False, *, min_score=None):
+        """``CtdetDetector.run_tiles`` for people in large frames: a list of (H, W, 3) uint8 BGR frames of one
+        size -> per frame ``{1: rows}`` in frame pixels, rows [x1, y1, x2, y2, score, 17 x (x, y)] as nested
+        lists, or with ``arrays=True`` one (n, 39) float32 array (the ``run_frames`` convention).  Tiling,
+        ``overlap``, ``margin``, ``tile_batch``, ``pixel_format`` and the refusals are the ctdet entry's.  The merge
+        (``cn_multi_pose_tiles_merge_f32``; ``post_process.multi_pose_tiles_results`` is its specification): a
+        tile keeps the people whose box centre lies in its core and, with ``min_score`` (keyword only: a finite
+        number, ``ValueError`` otherwise), whose score is at least that; when the frame has more than one tile
+        or with ``--nms``, Gaussian soft-NMS over the frame as ``merge_outputs`` runs it over test scales; then
+        the ``max_per_frame`` (default ``max_per_image``) best rows, ties included.  A frame with more than
+        ``native.POSE_TILES_MAX_ROWS`` survivors sends its batch through the host tail (``tail_fallbacks``):
+        ``min_score`` is what keeps a 4K frame's candidates below that.  With one tile per frame and
+        ``max_per_frame >= K`` the result is ``run_frames``', bit for bit."""
+        args = self._tiles_args(overlap, margin, tile_batch, max_per_frame)
+        return self._tiles_run(frames, args, pixel_format, arrays, min_score=self._tiles_min_score(min_score))
+
+    def run_tiles_stream(self, batches, depth=3, overlap=None, margin=None, tile_batch=32, max_per_frame=None,
+                         pixel_format='bgr', arrays=False, *, min_score=None):
+        """``run_tiles`` over an iterable of batches (lists of frames, all batches of one length and frame
+        size), pipelined as ``run_frames_stream``.  Yields the per-frame results batch by batch, in order."""
+        args = self._tiles_args(overlap, margin, tile_batch, max_per_frame)
+        yield from self._tiles_stream(batches, depth, args, pixel_format, arrays,
+                                      min_score=self._tiles_min_score(min_score))
+
+
+class PoseTilesTail(DeviceTail):
+    """The multi_pose tail of ``TilePipe``: per chunk cn_multi_pose_post_process_f32 with one inverse map per tile
+    into the chunk's slice of the (B * T, K, 39) tile rows; behind the last chunk cn_multi_pose_tiles_merge_f32:
+    final 39-column rows in frame pixels, their count and one status word per frame."""
+
+    @classmethod
+    def admits(cls, pipe):
+        """Not with more detections per tile or rows per frame than the kernels take."""
+        K = pipe.det.opt.K
+        return K <= 128 and pipe.T * K <= native.TILES_MAX_ROWS
+
+    def __init__(self, pipe):
+        super(PoseTilesTail, self).__init__(pipe)    # (``pipe.to_source_dev`` is set: no per-level maps)
+        K, B, T = self.det.opt.K, pipe.B, pipe.T
+        self.output('rows', (B, T * K, ROW), torch.float32)
+        self.output('counts', (B,), torch.int32)
+        self.output('status', (B,), torch.int32)
+        self.tile_rows = torch.empty((B * T, K, ROW), device=self.device, dtype=torch.float32)
+        self.ws_bytes = int(native.lib().cn_multi_pose_tiles_merge_workspace_bytes(B, T, K))
+        self.ws = torch.empty((max(self.ws_bytes, 16),), device=self.device, dtype=torch.uint8)
+        min_score = pipe.options.get('min_score')
+        self.min_score = float('nan') if min_score is None else float(min_score)     # (NaN: no score test)
+
+    def run(self, slot, level, dets):
+        """Chunk ``level``: the raw detections of its tiles -> frame pixels, into its slice."""
+        pipe, lv = self.pipe, self.pipe.levels[level]
+        dets = dets.contiguous()
+        native.check(native.lib().cn_multi_pose_post_process_f32(
+            native.ptr(dets), lv.n, self.det.opt.K, native.ptr(pipe.to_source_dev[lv.lo:]), 1, 1.0,
+            native.ptr(self.tile_rows[lv.lo:]), native.stream_ptr()), "cn_multi_pose_post_process_f32")
+
+    def finish(self, slot):
+        pipe, opt = self.pipe, self.det.opt
+        native.check(native.lib().cn_multi_pose_tiles_merge_f32(
+            native.ptr(self.tile_rows), pipe.B, pipe.T, opt.K, native.ptr(pipe.cores_dev), int(bool(opt.nms)),
+            pipe.max_per_frame, self.min_score, native.ptr(self.out['rows']), native.ptr(self.out['counts']),
+            native.ptr(self.out['status']), native.ptr(self.ws), self.ws_bytes, native.stream_ptr()),
+            "cn_multi_pose_tiles_merge_f32")
+        super(PoseTilesTail, self).finish(slot)
+
+    def results(self, slot, n):
+        """Per frame ``{1: rows}``, or None when a frame's status is set: more survivors than the merge holds,
+        the batch goes back to the host tail.  Only the counted rows leave the pinned buffer."""
+        if self.host('status', slot).numpy().any():
+            return None
+        rows, counts = self.host('rows', slot).numpy(), self.host('counts', slot).numpy().tolist()
+        if self.arrays:
+            return [{1: rows[i, :counts[i]].copy()} for i in range(n)]
+        return [{1: rows[i, :counts[i]].tolist()} for i in range(n)]
 
 
 class MultiPoseTail(DeviceTail):

@@ -599,8 +599,8 @@ class ImagePipe(FramePipe):
 
 
 class TilePipe(FramePipe):
-    """``FramePipe`` for frames much larger than the network input (``run_tiles`` / ``run_tiles_stream``, ctdet,
-    DESIGN.md 3.6b): the B frames of (H, W) are cut into T overlapping (input_h, input_w) tiles each at native
+    """``FramePipe`` for frames much larger than the network input (``run_tiles`` / ``run_tiles_stream``, ctdet and
+    multi_pose): the B frames of (H, W) are cut into T overlapping (input_h, input_w) tiles each at native
     resolution (``tiles.tile_grid``), tile t of frame b is image b * T + t of the TILE BATCH, and the pipe's
     levels are the chunks of ``C = min(tile_batch, B * T)`` tiles of that batch, not test scales: every chunk
     runs the ONE plan of batch C, a short last chunk padded to C in a batch tensor of its own whose surplus
@@ -609,11 +609,15 @@ class TilePipe(FramePipe):
     chunk's pre-process is one ``cn_warp_normalize_u8_f32_ragged`` launch on its slice of the table; the
     (B * T, 6) output grid -> frame maps; the (T, 4) cores.  The tail (``TilesTail``) post-processes each chunk
     into its slice of the (B * T, K, 5) rows and merges the frames' tiles behind the last chunk
-    (``cn_ctdet_tiles_merge_f32``).  Range digests, staging, the copy stream, NV12 and both hand-back routes
-    are ``FramePipe``'s; the synchronous path is ``det._run_tiles_sync``."""
+    (``cn_ctdet_tiles_merge_f32``); multi_pose: ``PoseTilesTail``, 39-column rows, ``cn_multi_pose_tiles_merge_f32``.
+    The pipe is task-neutral: it calls ``det._tiles_tail``, ``det._tiles_host_tail`` and ``det._run_tiles_sync`` and
+    hands them ``options``, the task's arguments beyond ``max_per_frame``.  Range digests, staging, the copy stream,
+    NV12 and both hand-back routes are ``FramePipe``'s; the synchronous path is ``det._run_tiles_sync``."""
 
-    def __init__(self, det, B, H, W, overlap, margin, tile_batch, max_per_frame, depth, pixel_format='bgr'):
+    def __init__(self, det, B, H, W, overlap, margin, tile_batch, max_per_frame, depth, pixel_format='bgr',
+                 options=None):
         from .tiles import tile_grid, tile_maps
+        self.options = dict(options or {})       # the task's own, beyond max_per_frame (multi_pose: min_score)
         opt, dev = det.opt, det.opt.device
         if not (0 < H <= 32767 and 0 < W <= 32767):
             raise ValueError("run_tiles needs frames of 1 .. 32767 rows and columns, got %d x %d" % (H, W))
@@ -669,9 +673,10 @@ class TilePipe(FramePipe):
     def _run_sync(self, frames, **kw):
         if self.pixel_format == 'nv12':
             frames = [nv12_to_bgr(f) for f in frames]
-        return self.det._run_tiles_sync(frames, self.overlap, self.margin, self.tile_batch, self.max_per_frame)
+        return self.det._run_tiles_sync(frames, self.overlap, self.margin, self.tile_batch, self.max_per_frame,
+                                        **dict(self.options, **kw))
 
     def _host_tail(self, slot, sel, kw):
         """A pipe without a device tail: the host tile merge on the raw detections copied out per chunk."""
         dets = np.concatenate([d.numpy()[:lv.n] for d, lv in zip(self.dets_host[slot], self.levels)], axis=0)
-        return self.det._tiles_host_tail(dets, self.grid, self.B, self.max_per_frame)
+        return self.det._tiles_host_tail(dets, self.grid, self.B, self.max_per_frame, **dict(self.options, **kw))

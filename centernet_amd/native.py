@@ -29,6 +29,8 @@ CONV_STEM_Y_F32S = 32
 MERGE_MAX_ROWS = 2048       # CN_MERGE_MAX_ROWS: S * K rows per image that the merge kernels take
 MERGE_MAX_CLASSES = 1024    # CN_MERGE_MAX_CLASSES
 TILES_MAX_ROWS = 65536      # CN_TILES_MAX_ROWS: T * K rows per frame that cn_ctdet_tiles_merge_f32 takes
+POSE_TILES_MAX_ROWS = 5120  # CN_POSE_TILES_MAX_ROWS: survivors per frame that cn_multi_pose_tiles_merge_f32 holds
+POSE_TILES_ONE_WAVE_ROWS = 256   # CN_POSE_TILES_ONE_WAVE_ROWS: up to there its soft-NMS runs on one wave
 # flag bits of the decode entries: the #defines of the same names in include/centernet_amd.h
 # (tests/test_decode_route_host.py compares them)
 DECODE_SIGMOID = 1          # CN_DECODE_SIGMOID
@@ -275,6 +277,10 @@ def _declare(lib):
     lib.cn_multi_pose_post_process_f32.argtypes = [vp, i, i, vp, i, ctypes.c_float, vp, vp]
     lib.cn_multi_pose_merge_f32.restype = i
     lib.cn_multi_pose_merge_f32.argtypes = [vp, i, i, i, i, vp, vp]
+    lib.cn_multi_pose_tiles_merge_workspace_bytes.restype = sz
+    lib.cn_multi_pose_tiles_merge_workspace_bytes.argtypes = [i, i, i]
+    lib.cn_multi_pose_tiles_merge_f32.restype = i
+    lib.cn_multi_pose_tiles_merge_f32.argtypes = [vp, i, i, i, vp, i, i, ctypes.c_float, vp, vp, vp, vp, sz, vp]
     lib.cn_resize_bilinear_u8.restype = i
     lib.cn_resize_bilinear_u8.argtypes = [vp, i, i, i, i, i, vp, vp]
     lib.cn_warp_affine_u8_host.restype = i

@@ -221,6 +221,42 @@ def ctdet_tiles_results(per_tile, cores, num_classes, nms, max_per_frame):
     return ctdet_merge(kept, num_classes, T > 1 or bool(nms), max_per_frame)
 
 
+def multi_pose_tiles_results(per_tile, cores, nms, max_per_frame, min_score=None):
+    """The tile merge of multi_pose ``run_tiles`` for one frame -- the specification
+    ``cn_multi_pose_tiles_merge_f32`` restates on the device, the host tail and the hand-back route.
+    ``per_tile``: [T] (n, 39) float32 rows [x1, y1, x2, y2, score, 17 x (x, y)] in FRAME pixels, in tile order
+    (``MultiPoseDetector._post_batch`` with the tile's meta); ``cores`` (T, 4) float32 (``tiles.tile_grid``).
+    (a) a row of tile t survives when its box centre lies in the tile's core (``tiles.in_core``: float32, lower
+    edges closed, upper edges open) and, with a ``min_score``, ``score >= float32(min_score)`` -- a NaN score
+    fails; ``None``: no score test; (b) the survivors of all tiles in tile order, each tile's in their order;
+    (c) when ``T > 1 or nms``: ``soft_nms_39(rows, Nt=0.5, method=2)`` in place with the WHOLE array kept, what
+    ``MultiPoseDetector.merge_outputs`` does with test scales; (d) when more than ``max_per_frame`` rows are
+    left, the rows with score >= the ``max_per_frame``-th largest score: duplicates counted, ties kept, order
+    kept (ctdet's cut).  -> ``{1: (n, 39) float32}``.
+    Rows past the kept count of the soft-NMS are stale copies (the box and score they last held, the joints the
+    exchanges left there) and can pass the cut: inherited from ``merge_outputs`` on purpose, it keeps one tile
+    per frame equal to ``run_frames``."""
+    from .tiles import in_core
+    T = len(per_tile)
+    kept = []
+    for tile, core in zip(per_tile, cores):
+        rows = np.asarray(tile, np.float32).reshape(-1, 39)
+        keep = in_core(rows[:, :5], core)
+        if min_score is not None:
+            with np.errstate(invalid='ignore'):
+                keep &= rows[:, 4] >= np.float32(min_score)
+        kept.append(rows[keep])
+    rows = np.ascontiguousarray(np.concatenate(kept, axis=0), np.float32) if T else np.zeros((0, 39), np.float32)
+    if (T > 1 or nms) and len(rows) > 1:                # (soft-NMS does nothing to fewer than two rows)
+        from .soft_nms import soft_nms_39
+        soft_nms_39(rows, Nt=0.5, method=2)
+    if len(rows) > max_per_frame:
+        kth = len(rows) - max_per_frame
+        thresh = np.partition(rows[:, 4], kth)[kth]
+        rows = rows[rows[:, 4] >= thresh]
+    return {1: rows}
+
+
 def ddd_norm_table(mean, std):
     """(3, 256) float32: ``(level / 255 - mean[c]) / std[c]`` with the ddd class's float32 chain
     (detectors/ddd.py:45-46) for every uint8 level -- what ``DddDetector.pre_process`` indexes on the

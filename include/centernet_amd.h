@@ -791,6 +791,35 @@ int cn_multi_pose_post_process_f32(const float *dets, int B, int K, const double
  * Row cap: S*K <= CN_MERGE_MAX_ROWS, CN_ERR_SHAPE above. */
 int cn_multi_pose_merge_f32(const float *rows, int S, int B, int K, int apply_nms, float *out_rows,
                             void *stream);
+/* The tile merge of multi_pose run_tiles (post_process.multi_pose_tiles_results on the device, bit for bit).
+ * rows (B*T, K, 39): cn_multi_pose_post_process_f32's output of tile t of frame b in image b*T + t, rows in FRAME
+ * pixels.  cores_dev (T, 4) float32 on the device, as for cn_ctdet_tiles_merge_f32.  Per frame:
+ *   a row of tile t survives when its box centre cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f (float32) has
+ *   x_lo <= cx < x_hi and y_lo <= cy < y_hi and, unless min_score is NaN, score >= min_score (a NaN score fails);
+ *   the survivors of all tiles in tile order, each tile's rows in their order; when T > 1 or apply_nms, Gaussian
+ *   soft-NMS (sigma 0.5, threshold 0.001) with the arithmetic and the row moves of cn_soft_nms_f32 at stride 39,
+ *   as cn_multi_pose_merge_f32 runs it -- the WHOLE in-place array is kept, rows past the kept count included
+ *   (they can pass the cut: MultiPoseDetector.merge_outputs keeps them too, and one tile per frame thereby
+ *   equals run_frames); then, when more than max_per_frame rows are left, the rows whose score is >= the
+ *   max_per_frame-th largest score (duplicates counted, ties kept), in order.
+ * out_rows (B, T*K, 39): the first out_counts[b] rows of frame b are its result, the rest is not written.
+ * out_counts (B), status (B): int32.  ONE launch, one workgroup of sixteen waves per frame that shares the argmax
+ * and the decay of every soft-NMS step when the frame has more than CN_POSE_TILES_ONE_WAVE_ROWS survivors (up to
+ * there one wave runs the same steps without barriers, which is faster: profiles/run_tiles_pose.txt); no host
+ * synchronisation, no floating-point atomics: the result is a function of the input.  The survivors live in dynamic LDS: per row 4 x 4 bytes of box, 4 of score, 4 of
+ * decayed score, 2 of source row index, 2 of start-of-step position and one discard bit = 28.125 bytes,
+ * CN_POSE_TILES_MAX_ROWS x 28.125 = 144000 bytes next to 9.6 KB of select histogram and reduction words, of the
+ * 160 KB of a gfx950 workgroup.  A frame with more survivors is not merged: status[b] = 1, out_counts[b] = 0;
+ * every other frame has status[b] = 0 and its result.  The workspace is unused by this form (16 bytes are
+ * asked for) and checked as the ctdet entry checks it: CN_ERR_NULL without one, CN_ERR_WORKSPACE for a short
+ * one, CN_ERR_ALIGN off 16 bytes.  Limits: K <= 128, T >= 1, T*K <= CN_TILES_MAX_ROWS, CN_ERR_SHAPE otherwise.  A
+ * refused call launches nothing. */
+#define CN_POSE_TILES_MAX_ROWS 5120
+#define CN_POSE_TILES_ONE_WAVE_ROWS 256
+size_t cn_multi_pose_tiles_merge_workspace_bytes(int B, int T, int K);
+int cn_multi_pose_tiles_merge_f32(const float *rows, int B, int T, int K, const float *cores_dev, int apply_nms,
+                                  int max_per_frame, float min_score, float *out_rows, int32_t *out_counts,
+                                  int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 int cn_resize_bilinear_u8(const uint8_t *image_hwc, int H, int W, int pitch_bytes, int out_h,
                           int out_w, uint8_t *out_hwc, void *stream);
 

@@ -1,5 +1,5 @@
 """run_tiles on large frames against run_frames on the same tiles, and the tile merge against its host restatement.
-python tools/bench_tiles.py [--frames 8] [--batches 24] [--K 100,32] [--out FILE]
+python tools/bench_tiles.py [--task ctdet|multi_pose] [--frames 8] [--batches 24] [--K 100,32] [--out FILE]
 ctdet resdcn_18 with seeded weights, 512 x 512 tiles at overlap 128 of 2160 x 3840 frames (10 x 6 = 60 tiles a frame),
 once per value of --K (detections per tile):
   (a) run_tiles_stream, batches of --frames frames, tile_batch 32: frames/s and tiles/s, and how many batches the
@@ -9,6 +9,15 @@ once per value of --K (detections per tile):
       60-tile frame and of the whole batch, against post_process.ctdet_tiles_results on the same rows -- the rows
       as the stream left them, and the same rows with the classes dealt evenly (seeded weights on noise put most
       rows into one class, which at K = 100 is above the cap of a class segment).
+--task multi_pose: dla_34 with seeded weights on the same frames, once per value of --K and of --min_score:
+  (a) run_tiles_stream as above: frames/s, tiles/s and the batches handed back (a frame with more survivors than
+      CN_POSE_TILES_MAX_ROWS);
+  (c) cn_multi_pose_tiles_merge_f32 (one launch) between two device events on the rows of one frame and of the whole
+      batch, against post_process.multi_pose_tiles_results on the same rows;
+  (d) once: the workgroup-wide soft-NMS against the one-wave form it stands next to -- cn_multi_pose_tiles_merge_f32
+      and cn_multi_pose_merge_f32 on the same seeded rows (infinite cores, no cut: both load, run soft-NMS and gather
+      the same rows), segment lengths 64 ... 2048, the two calls alternating in one process (up to
+      CN_POSE_TILES_ONE_WAVE_ROWS the new kernel runs its steps on one wave too: the crossover of the two forms).
 Every window ends in a device synchronise; the box calibration (cn_calib_copy, 512 MiB) is taken in the same process."""
 import argparse
 import contextlib
@@ -21,7 +30,7 @@ import numpy as np
 import torch
 
 from centernet_amd import native, synth, tiles
-from centernet_amd.post_process import ctdet_tiles_results
+from centernet_amd.post_process import ctdet_tiles_results, multi_pose_tiles_results
 
 H, W, TILE, OVERLAP = 2160, 3840, 512, 128
 
@@ -59,8 +68,12 @@ def main():
     ap.add_argument("--batches", type=int, default=24, help="run_tiles batches per timed window")
     ap.add_argument("--K", default="100,32", help="detections per tile, one measurement per value")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--task", default="ctdet", choices=("ctdet", "multi_pose"))
+    ap.add_argument("--min_score", default="none,0.1", help="multi_pose: score thresholds, one measurement per value")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_tiles needs a HIP device"
+    if a.task == "multi_pose":
+        return main_pose(a)
     from centernet_amd.detectors.detector_factory import detector_factory
     from centernet_amd.opts import opts
     with contextlib.redirect_stdout(sys.stderr):
@@ -165,6 +178,175 @@ def measure(det, a, frames, grid, lines):
     for nb in sorted({1, B}):
         merge_times(det, pipe, grid, rows, bounds, nb, "rows as run", lines)
         merge_times(det, pipe, grid, rows, even, nb, "the same rows, classes dealt evenly", lines)
+
+
+# ------------------------------------------------------------------------------------------------
+# --task multi_pose
+# ------------------------------------------------------------------------------------------------
+def pose_rows(rng, n, clusters):
+    """(n, 39) seeded rows: ``clusters`` > 0: boxes in that many dense clusters (the rows of tests/test_gpu_pose_tiles.py:
+    most of them are discarded, few steps); 0: boxes spread over a 4K frame (few overlaps: as many steps as rows)"""
+    if clusters:
+        c = rng.uniform(0, 600, (clusters, 2))[rng.randint(0, clusters, n)] + rng.normal(0, 3.0, (n, 2))
+    else:
+        c = rng.uniform(0, 1, (n, 2)) * (W, H)
+    wh = rng.uniform(8, 50, (n, 2))
+    rows = np.empty((n, 39), np.float32)
+    rows[:, 0:2], rows[:, 2:4] = c - wh / 2, c + wh / 2
+    rows[:, 4] = rng.randint(1, 400, n) / np.float32(400)
+    rows[:, 5:] = rng.uniform(-50, 700, (n, 34))
+    return rows
+
+
+def nms_forms(lines, rounds=15, reps=20):
+    """(d): both kernels on the same rows, alternating; per call the median over the rounds and their spread"""
+    lib = native.lib()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    lines.append("(d) soft-NMS forms, B = 2 frames of n rows (T = n / K tiles of K = min(n, 128)), infinite cores, no "
+                 "cut; us per call, median of %d alternating rounds of %d calls (min .. max): "
+                 "wg = cn_multi_pose_tiles_merge_f32 (16 waves), wave = cn_multi_pose_merge_f32 (1 wave)" % (rounds, reps))
+    for clusters in (12, 0):
+        for n in (64, 128, 256, 384, 512, 1024, 2048):
+            B, K = 2, min(n, 128)
+            T = n // K
+            rows = pose_rows(np.random.RandomState(56 if (clusters, n) == (12, 2048) else 1000 + n), B * n, clusters)
+            rows = rows.reshape(B * T, K, 39)
+            host = rows[:T].reshape(n, 39).copy()
+            kept = lib.cn_soft_nms_f32(host.ctypes.data, n, 39, 0.5, 0.5, 0.001, 2)
+            tiles_in = torch.from_numpy(rows).cuda()
+            scales_in = torch.from_numpy(np.ascontiguousarray(rows.reshape(B, T, K, 39).transpose(1, 0, 2, 3))).cuda()
+            cores = torch.from_numpy(np.tile(np.array([-np.inf, -np.inf, np.inf, np.inf], np.float32), (T, 1))).cuda()
+            out_a, out_b = torch.empty((B, n, 39), device="cuda"), torch.empty((B, n, 39), device="cuda")
+            counts, status = torch.empty((B,), dtype=torch.int32, device="cuda"), torch.empty((B,), dtype=torch.int32, device="cuda")
+            ws = torch.empty((16,), dtype=torch.uint8, device="cuda")
+
+            def wg():
+                native.check(lib.cn_multi_pose_tiles_merge_f32(
+                    native.ptr(tiles_in), B, T, K, native.ptr(cores), 1, n, float("nan"), native.ptr(out_a),
+                    native.ptr(counts), native.ptr(status), native.ptr(ws), 16, native.stream_ptr()), "tiles merge")
+
+            def wave():
+                native.check(lib.cn_multi_pose_merge_f32(native.ptr(scales_in), T, B, K, 1, native.ptr(out_b),
+                                                         native.stream_ptr()), "scale merge")
+
+            def timed(f):
+                e0.record()
+                for _ in range(reps):
+                    f()
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / reps * 1e3
+            timed(wg), timed(wave)
+            assert torch.equal(out_a.view(torch.int32), out_b.view(torch.int32))      # the same bits
+            ta, tb = [], []
+            for _ in range(rounds):
+                ta.append(timed(wg))
+                tb.append(timed(wave))
+            lines.append("    %-9s n = %4d (%4d steps in frame 0): wg %8.1f (%.1f .. %.1f)   wave %8.1f (%.1f .. %.1f)   "
+                         "wave / wg %.2f" % ("clustered" if clusters else "spread", n, min(kept, n), np.median(ta), min(ta),
+                                             max(ta), np.median(tb), min(tb), max(tb), np.median(tb) / np.median(ta)))
+
+
+def pose_merge_times(det, pipe, grid, rows, nb, min_score, lines):
+    """(c) for the first ``nb`` frames of the host ``rows`` (B * T, K, 39): the launch between two device events
+    against the host specification on the same rows"""
+    lib, tail, T, K = native.lib(), pipe.tail, grid.T, det.opt.K
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    r = torch.from_numpy(rows).cuda()
+    out_rows = torch.empty((nb, T * K, 39), device="cuda")
+    counts = torch.empty((nb,), dtype=torch.int32, device="cuda")
+    status = torch.empty((nb,), dtype=torch.int32, device="cuda")
+
+    def run(reps):
+        e0.record()
+        for _ in range(reps):
+            native.check(lib.cn_multi_pose_tiles_merge_f32(
+                native.ptr(r), nb, T, K, native.ptr(pipe.cores_dev), int(bool(det.opt.nms)), pipe.max_per_frame,
+                tail.min_score, native.ptr(out_rows), native.ptr(counts), native.ptr(status), native.ptr(tail.ws),
+                tail.ws_bytes, native.stream_ptr()), "pose tiles merge")
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+    run(3)
+    dev_ms = min(run(20) for _ in range(3))
+    reps = 3
+    survivors = []
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        for b in range(nb):
+            host = multi_pose_tiles_results(list(rows[b * T:(b + 1) * T]), grid.cores, det.opt.nms, pipe.max_per_frame,
+                                            min_score)
+    host_ms = (time.perf_counter() - t0) / reps * 1e3
+    from centernet_amd.tiles import in_core
+    for b in range(nb):
+        n = 0
+        for t in range(T):
+            keep = in_core(rows[b * T + t][:, :5], grid.cores[t])
+            if min_score is not None:
+                keep &= rows[b * T + t][:, 4] >= np.float32(min_score)
+            n += int(keep.sum())
+        survivors.append(n)
+    lines.append("(c) %d frame(s) x %d tiles x K %d, min_score %s: survivors a frame %d .. %d, frames with status set %d: "
+                 "cn_multi_pose_tiles_merge_f32 %.1f us for its 1 launch; multi_pose_tiles_results on the same rows "
+                 "%.2f ms (%d rows kept in the last frame)"
+                 % (nb, T, K, min_score, min(survivors), max(survivors), int((status != 0).sum()), dev_ms * 1e3, host_ms,
+                    len(host[1])))
+
+
+class Echo(list):
+    """the report's lines, each shown on stderr as it is measured (the whole report is printed at the end)"""
+    def append(self, line):
+        print(line, file=sys.stderr, flush=True)
+        list.append(self, line)
+
+
+def main_pose(a):
+    from centernet_amd.detectors.detector_factory import detector_factory
+    from centernet_amd.opts import opts
+    with contextlib.redirect_stdout(sys.stderr):
+        opt = opts().init(["multi_pose", "--arch", "dla_34"])
+        det = detector_factory[opt.task](opt)
+    synth.fill_state_dict_(det.model, 317)
+    det.model.invalidate_plans()
+    lines = Echo(["box calibration: 512 MiB copy %.2f TB/s (read + write)" % calibration()])
+    nms_forms(lines)
+    B = a.frames
+    rng = np.random.RandomState(5)
+    frames = [rng.randint(0, 256, (H, W, 3)).astype(np.uint8) for _ in range(B)]
+    grid = tiles.tile_grid(H, W, TILE, TILE, OVERLAP)
+    for K in [int(v) for v in a.K.split(",")]:
+        det.opt.K = K
+        for pipe in det.__dict__.pop("_pipes", {}).values():     # (their tails are sized by K)
+            pipe.pool.shutdown(wait=False)
+        for ms in a.min_score.split(","):
+            min_score = None if ms.lower() == "none" else float(ms)
+            det.tail_fallbacks = 0
+            lines.append("multi_pose dla_34: frames %d x %d, tiles %d x %d at overlap %d: %d x %d = %d tiles a frame, %d "
+                         "frames a batch, K = %d, min_score %s, survivor cap %d"
+                         % (H, W, TILE, TILE, OVERLAP, grid.nx, grid.ny, grid.T, B, K, min_score,
+                            native.POSE_TILES_MAX_ROWS))
+
+            def tile_stream(n):
+                return det.run_tiles_stream((frames for _ in range(n)), depth=3, overlap=OVERLAP, tile_batch=32,
+                                            arrays=True, min_score=min_score)
+            list(tile_stream(3))
+            det.tail_fallbacks = 0
+            rates = windows(tile_stream, a.batches, B)
+            fps = float(np.median(rates))
+            lines.append("(a) run_tiles_stream(B=%d, tile_batch=32, depth=3, arrays=True), %d batches a window: frames/s %s, "
+                         "median %.1f = %.0f tiles/s; tail_fallbacks %d of %d batches"
+                         % (B, a.batches, " ".join("%.1f" % r for r in rates), fps, fps * grid.T, det.tail_fallbacks,
+                            3 * a.batches))
+            pipe = det._tile_pipe_for(frames, 3, *det._tiles_args(OVERLAP, None, 32, None), 'bgr', min_score=min_score)
+            rows = pipe.tail.tile_rows.cpu().numpy()
+            for nb in sorted({1, B}):
+                pose_merge_times(det, pipe, grid, rows, nb, min_score, lines)
+    print("\n".join(lines))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
 
 
 if __name__ == "__main__":
