@@ -41,6 +41,8 @@
 //   tiles_cut_kernel    one workgroup per frame: the max_per_frame-th largest score by cn_select.h's
 //                       radix_select over distinct (score, position) keys, then the ordered compaction.
 // What bounds a frame is the longest class segment (CN_MERGE_MAX_ROWS, the LDS of one soft-NMS), not its rows.
+// cn_ctdet_tiles_merge_gated_f32 (a tile pyramid; post_process.ctdet_pyramid_results) is the same
+// three launches with a size gate per tile next to the core in the filter; the old entry passes a null gate table.
 #include "cn_select.h"
 
 // hipcc defaults to -ffp-contract=fast-honor-pragmas: the float64 point map and the float32 chains below are
@@ -664,8 +666,11 @@ __global__ __launch_bounds__(MG_THREADS) void exdet_post_kernel(const float *__r
 // Row e = t * K + r of frame b (row r of tile t as cn_ctdet_post_process_f32 left it) -> its class when it is a
 // row of a class (r in front of the tile's last bound) and its centre lies in the tile's core, else -1.
 // cx = (x1 + x2) * 0.5f, lo <= cx < hi in float32: the host's comparison; a NaN centre fails it.
+// gates (T, 2) [lo, hi) or null (cn_ctdet_tiles_merge_gated_f32; uniform over the launch): with w = x2 - x1 and
+// h = y2 - y1 a NaN in either drops the row, otherwise s = max(w, h) must have lo <= s < hi as well.
 __device__ __forceinline__ int tile_row_class(const float *__restrict__ rows, const int32_t *__restrict__ bounds,
-                                              const float *__restrict__ cores, int b, int T, int K, int nc, int e)
+                                              const float *__restrict__ cores, const float *__restrict__ gates,
+                                              int b, int T, int K, int nc, int e)
 {
     const int t = e / K, r = e - t * K;
     const int32_t *bd = bounds + ((size_t)b * T + t) * ((size_t)nc + 1);
@@ -674,6 +679,12 @@ __device__ __forceinline__ int tile_row_class(const float *__restrict__ rows, co
     const float cx = (s[0] + s[2]) * 0.5f, cy = (s[1] + s[3]) * 0.5f;
     const float *co = cores + (size_t)t * 4;
     if (!(cx >= co[0] && cx < co[2] && cy >= co[1] && cy < co[3])) return -1;
+    if (gates) {
+        const float w = s[2] - s[0], h = s[3] - s[1];
+        if (w != w || h != h) return -1;
+        const float sz = w > h ? w : h;      // (no NaN left: a plain maximum)
+        if (!(sz >= gates[2 * t] && sz < gates[2 * t + 1])) return -1;
+    }
     int lo = 0, hi = nc;                 // the last c with bd[c] <= r
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -695,6 +706,7 @@ struct TilesGroupLds {
 __global__ __launch_bounds__(MG_THREADS) void tiles_group_kernel(const float *__restrict__ rows,
                                                                  const int32_t *__restrict__ bounds, int T, int K,
                                                                  int nc, const float *__restrict__ cores,
+                                                                 const float *__restrict__ gates,
                                                                  float *__restrict__ grouped,
                                                                  int32_t *__restrict__ segs,
                                                                  int32_t *__restrict__ out_bounds,
@@ -710,7 +722,7 @@ __global__ __launch_bounds__(MG_THREADS) void tiles_group_kernel(const float *__
     __syncthreads();
     // 1. the survivors' class histograms (LDS atomics: counts only)
     for (int e = w0 + lane; e < w1; e += CN_WAVE) {
-        const int c = tile_row_class(rows, bounds, cores, b, T, K, nc, e);
+        const int c = tile_row_class(rows, bounds, cores, gates, b, T, K, nc, e);
         if (c >= 0) atomicAdd(&L.hist[w][c], 1);
     }
     __syncthreads();
@@ -747,7 +759,7 @@ __global__ __launch_bounds__(MG_THREADS) void tiles_group_kernel(const float *__
     float *out = grouped + (size_t)b * R * 5;
     for (int base = w0; base < w1; base += CN_WAVE) {
         const int e = base + lane;
-        const int c = e < w1 ? tile_row_class(rows, bounds, cores, b, T, K, nc, e) : -1;
+        const int c = e < w1 ? tile_row_class(rows, bounds, cores, gates, b, T, K, nc, e) : -1;
         int pos = -1;
         unsigned long long todo = __ballot(c >= 0);
         while (todo) {                                          // wave-uniform: one class of the step per turn
@@ -978,12 +990,12 @@ extern "C" size_t cn_ctdet_tiles_merge_workspace_bytes(int B, int T, int K, int 
     return tiles_grouped_bytes(B, T, K) + cn_align_up((size_t)B * (num_classes + 1) * sizeof(int32_t), 16);
 }
 
-extern "C" int cn_ctdet_tiles_merge_f32(const float *rows, const int32_t *bounds, int B, int T, int K,
-                                        int num_classes, const float *cores_dev, int apply_nms, int max_per_frame,
-                                        float *out_rows, int32_t *out_bounds, int32_t *status, void *workspace,
-                                        size_t workspace_bytes, void *stream)
+// the old entry (gates_dev null) and the gated one: the same three launches
+static int tiles_merge(const float *rows, const int32_t *bounds, int B, int T, int K, int num_classes,
+                       const float *cores_dev, const float *gates_dev, int apply_nms, int max_per_frame,
+                       float *out_rows, int32_t *out_bounds, int32_t *status, void *workspace,
+                       size_t workspace_bytes, void *stream)
 {
-    if (!rows || !bounds || !cores_dev || !out_rows || !out_bounds || !status || !workspace) return CN_ERR_NULL;
     if (B <= 0 || T <= 0 || K <= 0 || num_classes <= 0 || max_per_frame <= 0) return CN_ERR_SHAPE;
     if (K > PP_KMAX || (long long)T * K > CN_TILES_MAX_ROWS || num_classes > CN_MERGE_MAX_CLASSES) return CN_ERR_SHAPE;
     if ((long long)B * num_classes > 0x7fffffffLL) return CN_ERR_SHAPE;      // (the grid of the soft-NMS launch)
@@ -993,7 +1005,7 @@ extern "C" int cn_ctdet_tiles_merge_f32(const float *rows, const int32_t *bounds
     int32_t *segs = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + tiles_grouped_bytes(B, T, K));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(tiles_group_kernel, dim3(B), dim3(MG_THREADS), 0, st, rows, bounds, T, K, num_classes,
-                       cores_dev, grouped, segs, out_bounds, status);
+                       cores_dev, gates_dev, grouped, segs, out_bounds, status);
     CN_CHECK_LAUNCH();
     if (T > 1 || apply_nms) {
         hipLaunchKernelGGL(tiles_nms_kernel, dim3((unsigned)B * num_classes), dim3(CN_WAVE), 0, st, grouped, segs,
@@ -1004,4 +1016,30 @@ extern "C" int cn_ctdet_tiles_merge_f32(const float *rows, const int32_t *bounds
                        num_classes, max_per_frame, out_rows, out_bounds);
     CN_CHECK_LAUNCH();
     return CN_OK;
+}
+
+extern "C" int cn_ctdet_tiles_merge_f32(const float *rows, const int32_t *bounds, int B, int T, int K,
+                                        int num_classes, const float *cores_dev, int apply_nms, int max_per_frame,
+                                        float *out_rows, int32_t *out_bounds, int32_t *status, void *workspace,
+                                        size_t workspace_bytes, void *stream)
+{
+    if (!rows || !bounds || !cores_dev || !out_rows || !out_bounds || !status || !workspace) return CN_ERR_NULL;
+    return tiles_merge(rows, bounds, B, T, K, num_classes, cores_dev, nullptr, apply_nms, max_per_frame, out_rows,
+                       out_bounds, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t cn_ctdet_tiles_merge_gated_workspace_bytes(int B, int T, int K, int num_classes)
+{
+    return cn_ctdet_tiles_merge_workspace_bytes(B, T, K, num_classes);
+}
+
+extern "C" int cn_ctdet_tiles_merge_gated_f32(const float *rows, const int32_t *bounds, int B, int T, int K,
+                                              int num_classes, const float *cores_dev, const float *gates_dev,
+                                              int apply_nms, int max_per_frame, float *out_rows, int32_t *out_bounds,
+                                              int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!rows || !bounds || !cores_dev || !gates_dev || !out_rows || !out_bounds || !status || !workspace)
+        return CN_ERR_NULL;
+    return tiles_merge(rows, bounds, B, T, K, num_classes, cores_dev, gates_dev, apply_nms, max_per_frame, out_rows,
+                       out_bounds, status, workspace, workspace_bytes, stream);
 }

@@ -11,7 +11,7 @@ import torch
 from .. import native
 from ..decode import ctdet_decode, ctdet_decode_at_cells
 from ..frame_pipe import DeviceTail
-from ..post_process import ctdet_merge, ctdet_results_batch, ctdet_tiles_results
+from ..post_process import ctdet_merge, ctdet_pyramid_results, ctdet_results_batch, ctdet_tiles_results
 from ..utils import flip_average, flip_average_batch
 from .base_detector import BaseDetector
 from .tiles_mixin import TilesMixin
@@ -118,15 +118,45 @@ class CtdetDetector(TilesMixin, BaseDetector):
     def _tiles_tail(self, pipe):
         return TilesTail(pipe) if TilesTail.admits(pipe) else None
 
-    def _tiles_host_tail(self, dets, grid, B, max_per_frame):
+    def _tiles_host_tail(self, dets, grid, B, max_per_frame, levels=None, size_gate=None, gate_slack=0.25):
         """Host tail of ``run_tiles``: (B * T, K, 6) host raw detections of the tile batch -> per frame
         ``{class: (n, 5) float32}`` in frame pixels: ``post_process`` of every tile with the tile's meta, then
-        ``post_process.ctdet_tiles_results`` (core filter, ``merge_outputs``' steps with tiles for scales)."""
+        ``post_process.ctdet_tiles_results`` (core filter, ``merge_outputs``' steps with tiles for scales).  With
+        ``levels`` ``grid`` is the ``tiles.pyramid_grid`` of these options: its metas carry the output grid ->
+        frame map of their level, and the merge is ``post_process.ctdet_pyramid_results`` (the size gate)."""
         from ..tiles import tile_maps
+        if levels is not None:
+            posts = self._post_batch(np.asarray(dets), grid.metas * B, 1.0)
+            return [ctdet_pyramid_results(posts[b * grid.T:(b + 1) * grid.T], grid.cores, grid.gates,
+                                          self.opt.num_classes, self.opt.nms, max_per_frame) for b in range(B)]
         metas = tile_maps(grid, self.opt.down_ratio)[0]
         posts = self._post_batch(np.asarray(dets), metas * B, 1.0)
         return [ctdet_tiles_results(posts[b * grid.T:(b + 1) * grid.T], grid.cores, self.opt.num_classes,
                                     self.opt.nms, max_per_frame) for b in range(B)]
+
+    def run_tiles(self, frames, overlap=None, margin=None, tile_batch=32, max_per_frame=None, pixel_format='bgr',
+                  levels=None, size_gate=None, gate_slack=0.25):
+        """``TilesMixin.run_tiles``, and with ``levels`` a tile PYRAMID for objects larger than
+        the overlap, which no native-resolution tile sees whole: ``levels`` is a strictly increasing tuple of
+        integers in [0, 3]; level l is the frame box-filtered by 2**l (``cn_tile_box_normalize_u8_f32``, straight
+        from the frame) and tiled like the frame itself, ``overlap`` and ``margin`` in that level's pixels
+        (``tiles.pyramid_grid``).  Every level answers for the object sizes it sees whole: with s = max(w, h) of
+        a box in frame pixels and g = ``size_gate`` (pixels of a tile, by default min(overlap)), the boundary
+        between consecutive listed levels a < b is g * 2**a; level a keeps s below boundary * (1 + gate_slack),
+        level b from boundary * (1 - gate_slack) on, and the soft-NMS of the merge
+        (``cn_ctdet_tiles_merge_gated_f32``) removes what both bands report.  The defaults are definitions from
+        the geometry, not tuned values.  ``levels=None``: no pyramid, exactly the call without the keyword;
+        ``levels=(0,)`` gives the same results through the pyramid's kernels.  More than 65536 rows per frame
+        (tiles x K) and bad ``levels`` / ``size_gate`` / ``gate_slack`` raise ``ValueError``."""
+        args = self._tiles_args(overlap, margin, tile_batch, max_per_frame)
+        return self._tiles_run(frames, args, pixel_format, **self._pyramid_options(args, levels, size_gate, gate_slack))
+
+    def run_tiles_stream(self, batches, depth=3, overlap=None, margin=None, tile_batch=32, max_per_frame=None,
+                         pixel_format='bgr', levels=None, size_gate=None, gate_slack=0.25):
+        """``run_tiles`` over an iterable of batches, pipelined (``TilesMixin.run_tiles_stream``)."""
+        args = self._tiles_args(overlap, margin, tile_batch, max_per_frame)
+        yield from self._tiles_stream(batches, depth, args, pixel_format,
+                                      **self._pyramid_options(args, levels, size_gate, gate_slack))
 
 
 class TilesTail(DeviceTail):
@@ -162,6 +192,13 @@ class TilesTail(DeviceTail):
 
     def finish(self, slot):
         pipe, opt = self.pipe, self.det.opt
+        if pipe.gates_dev is not None:       # a tile pyramid: the size gate of every tile's level in the filter
+            native.check(native.lib().cn_ctdet_tiles_merge_gated_f32(
+                native.ptr(self.tile_rows), native.ptr(self.tile_bounds), pipe.B, pipe.T, opt.K, opt.num_classes,
+                native.ptr(pipe.cores_dev), native.ptr(pipe.gates_dev), int(bool(opt.nms)), pipe.max_per_frame,
+                native.ptr(self.out['rows']), native.ptr(self.out['bounds']), native.ptr(self.out['status']),
+                native.ptr(self.ws), self.ws_bytes, native.stream_ptr()), "cn_ctdet_tiles_merge_gated_f32")
+            return super(TilesTail, self).finish(slot)
         native.check(native.lib().cn_ctdet_tiles_merge_f32(
             native.ptr(self.tile_rows), native.ptr(self.tile_bounds), pipe.B, pipe.T, opt.K, opt.num_classes,
             native.ptr(pipe.cores_dev), int(bool(opt.nms)), pipe.max_per_frame, native.ptr(self.out['rows']),

@@ -1,4 +1,4 @@
-"""``run_tiles`` / ``run_tiles_stream`` (DESIGN.md 3.6b, 3.6c): frames much larger than the network input, cut into
+"""``run_tiles`` / ``run_tiles_stream`` (DESIGN.md 3.6b, 3.6c, 3.6d): frames much larger than the network input, cut into
 overlapping input-sized tiles at native resolution and merged per frame on the device.  What is the same for
 every task that tiles -- the argument checks, the pipe cache, the synchronous comparison path and the two public
 loops -- lives here; a task adds ``_tiles_tail(pipe)`` (its ``DeviceTail`` of ``TilePipe``, or None) and
@@ -52,6 +52,30 @@ class TilesMixin(object):
             raise ValueError("run_tiles: margin must be >= 0, got %r" % (margin,))
         return (int(oy), int(ox)), (float(my), float(mx)), int(tile_batch), int(max_per_frame)
 
+    def _pyramid_options(self, args, levels, size_gate, gate_slack):
+        """The pyramid arguments of ctdet's ``run_tiles`` (no device needed) -> the pipe's ``options``: nothing
+        without ``levels`` (today's path, today's pipe key), else the three with their defaults filled in."""
+        if levels is None:
+            return {}
+        from ..tiles import check_levels, level_gates
+        levels = check_levels(levels)
+        if size_gate is None:      # (as tiles.pyramid_grid: one level has no boundary, also at overlap 0)
+            size_gate = max(min(args[0]), 1) if len(levels) == 1 else min(args[0])
+        level_gates(levels, size_gate, gate_slack)          # (the checks; ValueError)
+        return dict(levels=levels, size_gate=float(size_gate), gate_slack=float(gate_slack))
+
+    def _tiles_grid(self, H, W, overlap, margin, options):
+        """``tile_grid`` of the frame, or with ``levels`` among the options its ``pyramid_grid`` (with maps);
+        there ``T * K`` above the merge's row cap is refused, before any device work."""
+        from ..tiles import check_pyramid_rows, pyramid_grid, tile_grid
+        th, tw = int(self.opt.input_h), int(self.opt.input_w)
+        if options.get('levels') is None:
+            return tile_grid(H, W, th, tw, overlap, margin)
+        grid = pyramid_grid(H, W, th, tw, overlap, margin, options['levels'], options.get('size_gate'),
+                            options.get('gate_slack', 0.25), down_ratio=self.opt.down_ratio)
+        check_pyramid_rows(grid.T, int(self.opt.K), native.TILES_MAX_ROWS)
+        return grid
+
     def _tiles_frames(self, frames, pixel_format):
         if torch.is_tensor(frames):
             raise ValueError("run_tiles takes host frames (a list of uint8 arrays)")
@@ -66,6 +90,8 @@ class TilesMixin(object):
                depth, pixel_format) + tuple(sorted(options.items()))
         pipes = self.__dict__.setdefault("_pipes", {})
         if key not in pipes:
+            if options.get('levels') is not None:
+                self._tiles_grid(H, W, overlap, margin, options)     # (its refusals, before the pipe is built)
             if len(pipes) >= 4:
                 pipes.pop(next(iter(pipes))).pool.shutdown(wait=False)
             pipes[key] = TilePipe(self, B, H, W, overlap, margin, tile_batch, max_per_frame, depth, pixel_format,
@@ -76,13 +102,22 @@ class TilesMixin(object):
         """One batch of BGR frames, synchronously: every tile through the single-image warp
         (``cn_warp_normalize_u8_f32`` with the tile's matrix on its frame: ``pre_process_device`` for a tile),
         the chunks of ``tile_batch`` tiles of ``TilePipe`` -- a short last chunk in a zeroed batch of the full
-        size -- through ``_forward_checked``, host tail (``options``: the task's).  The comparison path of the
-        tile pipe and its re-run path."""
-        from ..tiles import tile_grid, tile_maps
+        size -- through ``_forward_checked``, host tail (``options``: the task's).  With ``levels`` among the
+        options the tiles are ``tiles.pyramid_grid``'s and every tile goes through a single-tile
+        ``cn_tile_box_normalize_u8_f32`` launch instead.  The comparison path of the tile pipe and its re-run
+        path."""
+        from ..tiles import tile_maps
         B, H, W = self._frames_geometry(frames)
         th, tw, dev = int(self.opt.input_h), int(self.opt.input_w), self.opt.device
-        grid = tile_grid(H, W, th, tw, overlap, margin)
-        dst_to_src = tile_maps(grid, self.opt.down_ratio)[1]
+        grid = self._tiles_grid(H, W, overlap, margin, options)
+        pyramid = options.get('levels') is not None
+        if pyramid:      # one cn_tile_box_desc per tile of a frame; the frame's offset is added per launch
+            desc = np.zeros((grid.T,), native.TILE_BOX_DESC)
+            desc['H'], desc['W'], desc['pitch'], desc['level'] = H, W, 3 * W, grid.level
+            desc['y0'], desc['x0'] = [o[0] for o in grid.origins], [o[1] for o in grid.origins]
+            desc_dev = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(dev)
+        else:
+            dst_to_src = tile_maps(grid, self.opt.down_ratio)[1]
         uploaded = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(dev)
         mean = (ctypes.c_float * 3)(*[float(v) for v in self.mean.reshape(-1)])
         std = (ctypes.c_float * 3)(*[float(v) for v in self.std.reshape(-1)])
@@ -94,6 +129,11 @@ class TilesMixin(object):
             batch = torch.zeros((C, 3, th, tw), device=dev, dtype=torch.float32)
             for j in range(n):
                 b, t = divmod(lo + j, grid.T)
+                if pyramid:
+                    native.check(native.lib().cn_tile_box_normalize_u8_f32(
+                        native.ptr(uploaded[b]), ctypes.c_void_p(desc_dev.data_ptr() + t * desc.itemsize), 1, th, tw,
+                        mean, std, native.ptr(batch[j:j + 1]), native.stream_ptr()), "cn_tile_box_normalize_u8_f32")
+                    continue
                 native.check(native.lib().cn_warp_normalize_u8_f32(
                     native.ptr(uploaded[b]), H, W, W * 3, (ctypes.c_double * 6)(*dst_to_src[t]), th, tw, mean, std,
                     0, native.ptr(batch[j:j + 1]), native.stream_ptr()), "cn_warp_normalize_u8_f32")

@@ -606,7 +606,9 @@ class TilePipe(FramePipe):
     runs the ONE plan of batch C, a short last chunk padded to C in a batch tensor of its own whose surplus
     slices are zero from the start and whose surplus rows nobody reads.  Static on the device: one
     ``cn_image_desc`` per tile, all of a frame's pointing into that frame with the tile's own matrix, so a
-    chunk's pre-process is one ``cn_warp_normalize_u8_f32_ragged`` launch on its slice of the table; the
+    chunk's pre-process is one ``cn_warp_normalize_u8_f32_ragged`` launch on its slice of the table (with ctdet's
+    ``levels`` the table is ``tiles.pyramid_grid``'s: ``cn_tile_box_desc``, ``cn_tile_box_normalize_u8_f32``, and a
+    (T, 2) gate table beside the cores for ``cn_ctdet_tiles_merge_gated_f32``: DESIGN.md 3.6d); the
     (B * T, 6) output grid -> frame maps; the (T, 4) cores.  The tail (``TilesTail``) post-processes each chunk
     into its slice of the (B * T, K, 5) rows and merges the frames' tiles behind the last chunk
     (``cn_ctdet_tiles_merge_f32``); multi_pose: ``PoseTilesTail``, 39-column rows, ``cn_multi_pose_tiles_merge_f32``.
@@ -616,13 +618,15 @@ class TilePipe(FramePipe):
 
     def __init__(self, det, B, H, W, overlap, margin, tile_batch, max_per_frame, depth, pixel_format='bgr',
                  options=None):
-        from .tiles import tile_grid, tile_maps
-        self.options = dict(options or {})       # the task's own, beyond max_per_frame (multi_pose: min_score)
+        from .tiles import tile_maps
+        # the task's own, beyond max_per_frame (multi_pose: min_score; ctdet: levels, size_gate, gate_slack)
+        self.options = dict(options or {})
+        self.pyramid = self.options.get('levels')          # the listed levels of a tile pyramid, or None
         opt, dev = det.opt, det.opt.device
         if not (0 < H <= 32767 and 0 < W <= 32767):
             raise ValueError("run_tiles needs frames of 1 .. 32767 rows and columns, got %d x %d" % (H, W))
         th, tw = int(opt.input_h), int(opt.input_w)
-        self.grid = grid = tile_grid(H, W, th, tw, overlap, margin)
+        self.grid = grid = det._tiles_grid(H, W, overlap, margin, self.options)
         self.overlap, self.margin, self.tile_batch = overlap, margin, int(tile_batch)
         self.max_per_frame = int(max_per_frame)
         self.T, self.N = grid.T, B * grid.T
@@ -631,13 +635,23 @@ class TilePipe(FramePipe):
         self._setup(det, B, (1.0,) * len(chunks), False, depth)      # one digest per level, i.e. per chunk
         self.H, self.W, self.pixel_format = H, W, pixel_format
         self.frame_shape = (H * 3 // 2, W) if pixel_format == 'nv12' else (H, W, 3)
-        metas, dst_to_src, to_source = tile_maps(grid, opt.down_ratio)
+        self.gates_dev = None
+        if self.pyramid is None:
+            metas, dst_to_src, to_source = tile_maps(grid, opt.down_ratio)
+            desc = np.zeros((self.N,), native.IMAGE_DESC)
+        else:            # cn_tile_box_desc per tile (its level and origin), one size gate per tile
+            metas, to_source = grid.metas, grid.to_source
+            desc = np.zeros((self.N,), native.TILE_BOX_DESC)
+            self.gates_dev = torch.from_numpy(np.ascontiguousarray(grid.gates)).to(dev)
         self.tile_metas = metas * B                                  # image b * T + t
-        desc = np.zeros((self.N,), native.IMAGE_DESC)
         for b in range(B):
             d = desc[b * grid.T:(b + 1) * grid.T]
             d['offset'], d['H'], d['W'], d['pitch'] = b * H * W * 3, H, W, 3 * W
-            d['dst_to_src'] = dst_to_src
+            if self.pyramid is None:
+                d['dst_to_src'] = dst_to_src
+            else:
+                d['level'] = grid.level
+                d['y0'], d['x0'] = [o[0] for o in grid.origins], [o[1] for o in grid.origins]
         self.desc_dev = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(dev)
         # (not per slot as ``ImagePipe``'s: the maps of a tile pipe never change; the tail addresses its chunk)
         self.to_source_dev = torch.from_numpy(np.ascontiguousarray(np.tile(to_source, (B, 1)))).to(dev)
@@ -665,6 +679,12 @@ class TilePipe(FramePipe):
         """On the launch stream: the tiles of chunk ``level`` out of the uploaded frames, one launch."""
         lv = self.levels[level]
         src = self.dev_in[slot] if self.bgr is None else self.bgr
+        if self.pyramid is not None:     # (a chunk may span levels: the level is the tile's)
+            descs = ctypes.c_void_p(self.desc_dev.data_ptr() + lv.lo * native.TILE_BOX_DESC.itemsize)
+            native.check(native.lib().cn_tile_box_normalize_u8_f32(
+                native.ptr(src), descs, lv.n, int(lv.batch.shape[2]), int(lv.batch.shape[3]), self.mean, self.std,
+                native.ptr(lv.batch), stream), "cn_tile_box_normalize_u8_f32")
+            return
         descs = ctypes.c_void_p(self.desc_dev.data_ptr() + lv.lo * native.IMAGE_DESC.itemsize)
         native.check(native.lib().cn_warp_normalize_u8_f32_ragged(
             native.ptr(src), descs, lv.n, int(lv.batch.shape[2]), int(lv.batch.shape[3]), self.mean, self.std, 0,

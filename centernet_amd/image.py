@@ -162,6 +162,33 @@ def resize_bilinear(img, dsize):
     return out
 
 
+def tile_box_normalize(frame, level, y0, x0, th, tw, mean, std):
+    """The pre-process of one tile of a tile pyramid -- the specification ``cn_tile_box_normalize_u8_f32``
+    restates on the device, bit for bit.  ``frame``: (H, W, 3) uint8; the tile is the (th, tw) window at
+    (y0, x0) of level ``level`` (0..3), the frame box-filtered by f = 1 << level straight from the frame:
+    ``v = (sum of the f x f source bytes + (f * f >> 1)) >> (2 * level)``, source positions outside the frame
+    contribute 0 and the divisor stays f * f; then ``((v / 255. - mean) / std)`` in float64, rounded once to
+    float32 (``mean`` / ``std``: 3 float32 values) -> (3, th, tw) float32."""
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError("tile_box_normalize needs an (H, W, 3) uint8 frame")
+    if int(level) != level or not 0 <= level <= 3:
+        raise ValueError("level must be an integer in [0, 3], got %r" % (level,))
+    level, f = int(level), 1 << int(level)
+    H, W = frame.shape[:2]
+    Y, X = int(y0) * f, int(x0) * f                  # the window's origin in frame pixels
+    src = np.zeros((th * f, tw * f, 3), np.int32)
+    ys, xs = max(Y, 0), max(X, 0)
+    ye, xe = min(Y + th * f, H), min(X + tw * f, W)
+    if ye > ys and xe > xs:
+        src[ys - Y:ye - Y, xs - X:xe - X] = frame[ys:ye, xs:xe]
+    v = (src.reshape(th, f, tw, f, 3).sum(axis=(1, 3)) + (f * f >> 1)) >> (2 * level)
+    mean = np.asarray(mean, np.float32).reshape(1, 1, 3)
+    std = np.asarray(std, np.float32).reshape(1, 1, 3)
+    out = ((v / 255. - mean) / std).astype(np.float32)
+    return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+
 PIXEL_FORMATS = ("bgr", "nv12")
 
 

@@ -56,6 +56,10 @@ def dcn_form_name(form):
 IMAGE_DESC = np.dtype([("offset", np.uint64), ("H", np.int32), ("W", np.int32), ("pitch", np.int32),
                        ("reserved", np.int32), ("dst_to_src", np.float64, (6,)), ("scale", np.float64, (2,))])
 assert IMAGE_DESC.itemsize == 88
+# cn_tile_box_desc, one tile of a tile pyramid (cn_tile_box_normalize_u8_f32)
+TILE_BOX_DESC = np.dtype([("offset", np.uint64), ("H", np.int32), ("W", np.int32), ("pitch", np.int32),
+                          ("level", np.int32), ("y0", np.int32), ("x0", np.int32)])
+assert TILE_BOX_DESC.itemsize == 32
 
 _lib = None
 
@@ -269,6 +273,13 @@ def _declare(lib):
     lib.cn_ctdet_tiles_merge_workspace_bytes.argtypes = [i, i, i, i]
     lib.cn_ctdet_tiles_merge_f32.restype = i
     lib.cn_ctdet_tiles_merge_f32.argtypes = [vp, vp, i, i, i, i, vp, i, i, vp, vp, vp, vp, sz, vp]
+    lib.cn_ctdet_tiles_merge_gated_workspace_bytes.restype = sz
+    lib.cn_ctdet_tiles_merge_gated_workspace_bytes.argtypes = [i, i, i, i]
+    lib.cn_ctdet_tiles_merge_gated_f32.restype = i
+    lib.cn_ctdet_tiles_merge_gated_f32.argtypes = [vp, vp, i, i, i, i, vp, vp, i, i, vp, vp, vp, vp, sz, vp]
+    lib.cn_tile_box_normalize_u8_f32.restype = i
+    lib.cn_tile_box_normalize_u8_f32.argtypes = [vp, vp, i, i, i, ctypes.POINTER(ctypes.c_float),
+                                                 ctypes.POINTER(ctypes.c_float), vp, vp]
     lib.cn_exdet_post_process_f32.restype = i
     lib.cn_exdet_post_process_f32.argtypes = [vp, i, i, i, i, vp, i, ctypes.c_float, vp, vp, vp]
     lib.cn_exdet_merge_f32.restype = i

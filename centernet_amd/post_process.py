@@ -17,16 +17,23 @@ def _inverse_maps(metas):
     """The frames grouped by geometry: [(indices of the frames, their (2, 3) float64 output grid -> source
     map)], one entry per distinct (centre, extent, output grid) in order of first appearance -- every frame of a
     video shares one.  ``get_affine_transform`` reads centre and extent as float32, so their float32 bytes
-    decide the map."""
+    decide the map.  A meta that carries its map (``'to_source'``, (2, 3) float64: a tile of a pyramid level,
+    ``tiles.pyramid_maps``) is grouped by that map's bytes and keeps it."""
     from .image import get_affine_transform
     groups = {}
     for i, m in enumerate(metas):
-        key = (np.asarray(m['c'], np.float32).tobytes(), np.asarray(m['s'], np.float32).tobytes(),
-               int(m['out_width']), int(m['out_height']))
+        if 'to_source' in m:
+            key = np.asarray(m['to_source'], np.float64).tobytes()
+        else:
+            key = (np.asarray(m['c'], np.float32).tobytes(), np.asarray(m['s'], np.float32).tobytes(),
+                   int(m['out_width']), int(m['out_height']))
         groups.setdefault(key, []).append(i)
-    return [(idx, get_affine_transform(metas[idx[0]]['c'], metas[idx[0]]['s'], 0,
-                                       (metas[idx[0]]['out_width'], metas[idx[0]]['out_height']), inv=1))
-            for idx in groups.values()]
+
+    def inverse(m):
+        if 'to_source' in m:
+            return np.asarray(m['to_source'], np.float64).reshape(2, 3)
+        return get_affine_transform(m['c'], m['s'], 0, (m['out_width'], m['out_height']), inv=1)
+    return [(idx, inverse(metas[idx[0]])) for idx in groups.values()]
 
 
 def _split_by_class(rows, classes, num_classes):
@@ -217,6 +224,25 @@ def ctdet_tiles_results(per_tile, cores, num_classes, nms, max_per_frame):
         for c in range(1, num_classes + 1):
             rows = np.asarray(tile[c], np.float32).reshape(-1, 5)
             one[c] = rows[in_core(rows, core)]
+        kept.append(one)
+    return ctdet_merge(kept, num_classes, T > 1 or bool(nms), max_per_frame)
+
+
+def ctdet_pyramid_results(per_tile, cores, gates, num_classes, nms, max_per_frame):
+    """The merge of a tile pyramid for one frame -- the specification ``cn_ctdet_tiles_merge_gated_f32``
+    restates on the device: ``ctdet_tiles_results`` with the size gate in the filter.  ``per_tile``, ``cores``:
+    as there, all tiles of all levels in ``tiles.pyramid_grid`` order; ``gates`` (T, 2) float32 [lo, hi) in
+    frame pixels.  A row of tile t survives when its centre lies in the tile's core AND its size lies in the
+    tile's gate (``tiles.in_gate``: w = x2 - x1, h = y2 - y1 in float32, a NaN in either fails, else
+    lo <= max(w, h) < hi); then ``ctdet_merge`` with ``T > 1 or nms``."""
+    from .tiles import in_core, in_gate
+    T = len(per_tile)
+    kept = []
+    for tile, core, gate in zip(per_tile, cores, gates):
+        one = {}
+        for c in range(1, num_classes + 1):
+            rows = np.asarray(tile[c], np.float32).reshape(-1, 5)
+            one[c] = rows[in_core(rows, core) & in_gate(rows, gate)]
         kept.append(one)
     return ctdet_merge(kept, num_classes, T > 1 or bool(nms), max_per_frame)
 

@@ -93,6 +93,120 @@ def tile_maps(grid, down_ratio):
     return metas, dst_to_src, to_source
 
 
+def check_levels(levels):
+    """``levels`` of a tile pyramid as a tuple of ints, or ``ValueError``."""
+    try:
+        lv = tuple(levels)
+    except TypeError:
+        lv = None
+    if not lv or any(isinstance(l, bool) or not isinstance(l, (int, np.integer)) or not 0 <= l <= 3 for l in lv) \
+            or any(b <= a for a, b in zip(lv, lv[1:])):
+        raise ValueError("levels must be a non-empty, strictly increasing tuple of integers in [0, 3], got %r"
+                         % (levels,))
+    return tuple(int(l) for l in lv)
+
+
+def level_gates(levels, size_gate, gate_slack=0.25):
+    """(len(levels), 2) float32 [lo, hi) of the object sizes each listed level answers for, in frame pixels.
+    ``size_gate`` = g, in pixels of a tile: the largest object some tile of a level is sure to see whole.  For
+    consecutive listed levels a < b the boundary is ``g * 2**a``; level a keeps sizes below ``boundary * (1 +
+    gate_slack)``, level b from ``boundary * (1 - gate_slack)`` on -- the bands overlap, and the soft-NMS of the
+    merge removes what both report.  The first level's lo is -inf, the last one's hi +inf.  Formed in float64,
+    rounded once to float32."""
+    levels = check_levels(levels)
+    g, slack = float(size_gate), float(gate_slack)
+    if not g > 0 or not np.isfinite(g):
+        raise ValueError("size_gate must be > 0, got %r" % (size_gate,))
+    if not 0 <= slack < 1:
+        raise ValueError("gate_slack must lie in [0, 1), got %r" % (gate_slack,))
+    out = np.empty((len(levels), 2), np.float64)
+    out[0, 0], out[-1, 1] = -np.inf, np.inf
+    for i, a in enumerate(levels[:-1]):
+        beta = g * 2.0 ** a
+        out[i, 1] = beta * (1.0 + slack)
+        out[i + 1, 0] = beta * (1.0 - slack)
+    return out.astype(np.float32)
+
+
+def pyramid_grid(H, W, th, tw, overlap, margin=None, levels=(0,), size_gate=None, gate_slack=0.25,
+                 down_ratio=None):
+    """The tiles of a tile PYRAMID over an (H, W) frame: level l of ``levels`` (non-empty, strictly increasing,
+    integers in [0, 3]) is the frame box-filtered by f = 2**l, an image of ceil(H / f) x ceil(W / f), tiled by
+    ``tile_grid(Hl, Wl, th, tw, overlap, margin)`` -- overlap and margin in that level's pixels; a level image
+    smaller than a tile is one tile padded with zeros.  Tile order: all tiles of the first listed level in
+    ``tile_grid`` order, then the next level's.  Level pixel v -> frame pixel u (integer = pixel centre):
+    ``u = v * f + (f - 1) / 2``.
+    -> ``tile_grid``'s kind of namespace: ``H, W, th, tw, T``; ``levels``; per level ``grids`` (its
+    ``tile_grid``), ``level_lo`` (its first tile) and ``level_T`` (its tile count); per tile ``level``, ``origins``
+    [(y0, x0)] in LEVEL pixels, ``cores`` (T, 4) float32 in FRAME pixels (the level grid's float32 bounds mapped
+    in float64, rounded once; +-inf stay), ``gates`` (T, 2) float32 [lo, hi) in frame pixels (``level_gates`` of
+    ``size_gate``, by default min(overlap_y, overlap_x); the level's band repeated for its tiles).  With a
+    ``down_ratio`` also ``metas`` and ``to_source`` (``pyramid_maps``).  ``ValueError`` for anything else.
+    ``levels=(0,)`` is ``tile_grid`` / ``tile_maps`` bit for bit, with the gate (-inf, +inf)."""
+    levels = check_levels(levels)
+    oy, ox = _pair(overlap)
+    if size_gate is None and len(levels) == 1:
+        size_gate = max(min(oy, ox), 1)      # (one level has no boundary: also at overlap 0)
+    band = level_gates(levels, min(oy, ox) if size_gate is None else size_gate, gate_slack)
+    grids, level_lo, level_T, level, origins, cores, gates = [], [], [], [], [], [], []
+    for i, l in enumerate(levels):
+        f = 1 << l
+        g = tile_grid(-(-int(H) // f), -(-int(W) // f), th, tw, overlap, margin)
+        grids.append(g)
+        level_lo.append(len(origins))
+        level_T.append(g.T)
+        level += [l] * g.T
+        origins += g.origins
+        cores.append(g.cores if f == 1 else
+                     (g.cores.astype(np.float64) * f + (f - 1) / 2.0).astype(np.float32))
+        gates.append(np.repeat(band[i:i + 1], g.T, axis=0))
+    out = types.SimpleNamespace(H=int(H), W=int(W), th=int(th), tw=int(tw), T=len(origins), levels=levels,
+                                grids=grids, level_lo=level_lo, level_T=level_T, level=level, origins=origins,
+                                cores=np.ascontiguousarray(np.concatenate(cores, axis=0)),
+                                gates=np.ascontiguousarray(np.concatenate(gates, axis=0)), bands=band)
+    if down_ratio is not None:
+        out.metas, out.to_source = pyramid_maps(out, down_ratio)
+    return out
+
+
+def pyramid_maps(grid, down_ratio):
+    """Per tile of a ``pyramid_grid``: ([T] metas, (T, 6) float64 output grid -> FRAME maps).  The map is
+    ``tile_maps``' output grid -> level image map of the tile composed in float64 with the level map: both rows
+    times f, translation ``t * f + (f - 1) / 2``; a meta is the tile's ``tile_meta`` in level pixels plus that map
+    as ``'to_source'`` (2, 3), which the host post-process then takes instead of deriving one."""
+    metas, maps = [], []
+    for l, g in zip(grid.levels, grid.grids):
+        f = 1 << l
+        ms, _, to_level = tile_maps(g, down_ratio)
+        if f > 1:
+            to_level = to_level * float(f)
+            to_level[:, 2] += (f - 1) / 2.0
+            to_level[:, 5] += (f - 1) / 2.0
+        maps.append(to_level)
+        metas += [dict(m, to_source=to_level[t].reshape(2, 3)) for t, m in enumerate(ms)]
+    return metas, np.ascontiguousarray(np.concatenate(maps, axis=0))
+
+
+def check_pyramid_rows(T, K, max_rows=65536):
+    """``ValueError`` when the T tiles of a pyramid with K detections each are more rows per frame than the
+    gated merge takes (``CN_TILES_MAX_ROWS``): fewer levels, larger tiles or a smaller K."""
+    if int(T) * int(K) > int(max_rows):
+        raise ValueError("run_tiles: %d tiles of K = %d detections are %d rows per frame, above the merge's %d"
+                         % (T, K, int(T) * int(K), max_rows))
+
+
+def in_gate(rows, gate):
+    """The rows [x1, y1, x2, y2, ...] (float32) whose size lies in ``gate`` = [lo, hi): a boolean mask.  With
+    w = x2 - x1 and h = y2 - y1 in float32 a NaN in either fails; otherwise s = max(w, h), lo <= s < hi."""
+    rows = np.asarray(rows, np.float32).reshape(-1, 5) if np.size(rows) else np.zeros((0, 5), np.float32)
+    lo, hi = (np.float32(v) for v in gate)
+    with np.errstate(invalid='ignore'):
+        w, h = rows[:, 2] - rows[:, 0], rows[:, 3] - rows[:, 1]
+        ok = ~(np.isnan(w) | np.isnan(h))
+        s = np.where(w > h, w, h)
+        return ok & (s >= lo) & (s < hi)
+
+
 def in_core(rows, core):
     """The rows [x1, y1, x2, y2, ...] (float32) whose centre lies in ``core`` = [x_lo, y_lo, x_hi, y_hi]:
     a boolean mask; centre and comparisons in float32, lower edges closed, upper edges open."""

@@ -700,6 +700,27 @@ int cn_warp_normalize_u8_f32_ragged(const uint8_t *packed, const cn_image_desc *
 int cn_resize_bilinear_u8_ragged(const uint8_t *packed_in, const cn_image_desc *in_descs_dev, uint8_t *packed_out,
                                  const cn_image_desc *out_descs_dev, int N, int max_out_h, int max_out_w,
                                  void *stream);
+/* The pre-process of a tile pyramid (run_tiles with levels; image.tile_box_normalize is its host restatement):
+ * tile n is a (out_h, out_w) window at origin (y0, x0) of LEVEL `level` of its frame, the frame box-filtered by
+ * f = 1 << level, computed straight from the frame -- no level image is stored, and the rounding happens once:
+ *   v[c] = (sum over dy, dx in [0, f) of src[(y0 + y) * f + dy, (x0 + x) * f + dx, c] + (f * f >> 1)) >> (2 * level)
+ *   out[n, c, y, x] = float32(((double)v[c] / 255.0 - mean[c]) / std[c])
+ * Source positions outside [0, H) x [0, W) contribute 0 and the divisor stays f * f (a zero border, as the
+ * warp's).  Level 0 is the pixel itself: cn_warp_normalize_u8_f32_ragged at the tile's translation, bit for bit;
+ * level 1 on an even-sized frame: cn_resize_bilinear_u8 at exactly half size, then that warp, bit for bit.
+ * One descriptor per tile in DEVICE memory, 32 bytes, 8-byte aligned.  output dense (N, 3, out_h, out_w).
+ * mean3 / std3: HOST floats.  The descriptors are only known on the device: the caller validates them before
+ * the upload (H, W in 1..32767, pitch >= 3 * W, level in 0..3, y0 / x0 in -32768..32767, the frame inside the
+ * buffer; any offset and pitch, no alignment needed); a tile with H <= 0, W <= 0 or a level outside 0..3 is
+ * skipped, its output untouched.  CN_ERR_NULL / CN_ERR_SHAPE as cn_warp_normalize_u8_f32_ragged returns them. */
+typedef struct cn_tile_box_desc {
+    uint64_t offset;       /* bytes from the start of the packed buffer to the tile's frame */
+    int32_t H, W, pitch;   /* the frame: rows, columns, row pitch in bytes (>= 3 * W) */
+    int32_t level;         /* 0..3: the frame box-filtered by 1 << level */
+    int32_t y0, x0;        /* the tile's origin in level pixels */
+} cn_tile_box_desc;
+int cn_tile_box_normalize_u8_f32(const uint8_t *packed, const cn_tile_box_desc *descs_dev, int N, int out_h,
+                                 int out_w, const float *mean3, const float *std3, float *out_nchw, void *stream);
 /* ctdet_post_process + the per-class split (utils/post_process.py:83-100, utils/image.py:19-24,63-66,
  * detectors/ctdet.py:47-56) on the device.  dets (B, K, 6) raw detections in output-grid units (K <= 128);
  * to_source_2x3: the float64 inverse map of get_affine_transform(c, s, 0, out_size, inv=1) -- one for
@@ -747,6 +768,19 @@ int cn_ctdet_tiles_merge_f32(const float *rows, const int32_t *bounds, int B, in
                              const float *cores_dev, int apply_nms, int max_per_frame, float *out_rows,
                              int32_t *out_bounds, int32_t *status, void *workspace, size_t workspace_bytes,
                              void *stream);
+/* The merge of a tile pyramid (post_process.ctdet_pyramid_results on the device, bit for bit):
+ * cn_ctdet_tiles_merge_f32 with a size gate per tile.  gates_dev (T, 2) float32 on the device: [lo, hi) of tile
+ * t in frame pixels (tiles.pyramid_grid: one band per pyramid level, -inf / +inf at the ends).  With w = x2 - x1
+ * and h = y2 - y1 in float32, a row with a NaN in w or h is dropped; otherwise s = max(w, h), and the row
+ * survives when lo <= s < hi AND its centre lies in the tile's core.  Everything else -- the three launches, the
+ * workspace (cn_ctdet_tiles_merge_gated_workspace_bytes, the same size), the limits, status and the return
+ * codes -- is cn_ctdet_tiles_merge_f32's; CN_ERR_NULL without a gate table.  With every gate (-inf, +inf) and no
+ * NaN size the result is cn_ctdet_tiles_merge_f32's. */
+size_t cn_ctdet_tiles_merge_gated_workspace_bytes(int B, int T, int K, int num_classes);
+int cn_ctdet_tiles_merge_gated_f32(const float *rows, const int32_t *bounds, int B, int T, int K, int num_classes,
+                                   const float *cores_dev, const float *gates_dev, int apply_nms,
+                                   int max_per_frame, float *out_rows, int32_t *out_bounds, int32_t *status,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 /* exdet task, the device tail of its frame pipe (detectors/exdet.py:51-81; reference exdet.py:86-123).
  * cn_exdet_post_process_f32: ExdetDetector.post_process, the `score > 0` filter and the per-class selection of
  * merge_outputs for one test scale of a batch.  dets (B, R, 14): the raw rows of cn_exct_decode_f32 /

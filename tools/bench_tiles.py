@@ -18,6 +18,12 @@ once per value of --K (detections per tile):
       and cn_multi_pose_merge_f32 on the same seeded rows (infinite cores, no cut: both load, run soft-NMS and gather
       the same rows), segment lengths 64 ... 2048, the two calls alternating in one process (up to
       CN_POSE_TILES_ONE_WAVE_ROWS the new kernel runs its steps on one wave too: the crossover of the two forms).
+--levels 0,1,2 (ctdet): the tile pyramid instead, once per value of --K:
+  (p1) run_tiles_stream without levels and with them on the same frames, windows alternating in one process: frames/s,
+       tiles/s, the tile counts per level and the batches handed back;
+  (p2) cn_tile_box_normalize_u8_f32 alone per level -- all tiles of that level of two frames in one launch, between two
+       device events -- with the bytes it must read and write per second, next to cn_warp_normalize_u8_f32_ragged on the
+       same level-0 tiles.
 Every window ends in a device synchronise; the box calibration (cn_calib_copy, 512 MiB) is taken in the same process."""
 import argparse
 import contextlib
@@ -70,6 +76,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--task", default="ctdet", choices=("ctdet", "multi_pose"))
     ap.add_argument("--min_score", default="none,0.1", help="multi_pose: score thresholds, one measurement per value")
+    ap.add_argument("--levels", default=None, help="ctdet: pyramid levels, e.g. 0,1,2: measure the tile pyramid instead")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_tiles needs a HIP device"
     if a.task == "multi_pose":
@@ -91,7 +98,10 @@ def main():
         det.tail_fallbacks = 0
         for pipe in det.__dict__.pop("_pipes", {}).values():     # (their tails are sized by K)
             pipe.pool.shutdown(wait=False)
-        measure(det, a, frames, grid, lines)
+        if a.levels:
+            measure_pyramid(det, a, frames, tuple(int(v) for v in a.levels.split(",")), lines)
+        else:
+            measure(det, a, frames, grid, lines)
     print("\n".join(lines))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -178,6 +188,95 @@ def measure(det, a, frames, grid, lines):
     for nb in sorted({1, B}):
         merge_times(det, pipe, grid, rows, bounds, nb, "rows as run", lines)
         merge_times(det, pipe, grid, rows, even, nb, "the same rows, classes dealt evenly", lines)
+
+
+# ------------------------------------------------------------------------------------------------
+# --levels: the tile pyramid
+# ------------------------------------------------------------------------------------------------
+def measure_pyramid(det, a, frames, levels, lines):
+    B, K = a.frames, det.opt.K
+    pyr = tiles.pyramid_grid(H, W, TILE, TILE, OVERLAP, None, levels, None, 0.25, down_ratio=det.opt.down_ratio)
+    T0 = tiles.tile_grid(H, W, TILE, TILE, OVERLAP).T
+    lines.append("frames %d x %d, tiles %d x %d at overlap %d, %d frames a batch, K = %d; levels %s: %s = %d tiles a frame "
+                 "(%d without levels), gates %s"
+                 % (H, W, TILE, TILE, OVERLAP, B, K, levels, " + ".join(str(n) for n in pyr.level_T), pyr.T, T0,
+                    pyr.bands.tolist()))
+
+    # (p1) the two streams, windows alternating
+    def stream(lv):
+        return lambda n: det.run_tiles_stream((frames for _ in range(n)), depth=3, overlap=OVERLAP, tile_batch=32,
+                                              levels=lv)
+    rates, back = {None: [], levels: []}, {None: 0, levels: 0}
+    for lv in (None, levels):
+        list(stream(lv)(3))
+    for _ in range(3):
+        for lv in (None, levels):
+            det.tail_fallbacks = 0
+            rates[lv] += windows(stream(lv), a.batches, B, n=1)
+            back[lv] += det.tail_fallbacks
+    for lv, T in ((None, T0), (levels, pyr.T)):
+        fps = float(np.median(rates[lv]))
+        lines.append("(p1) run_tiles_stream(B=%d, tile_batch=32, depth=3, levels=%s), %d batches a window, alternating: "
+                     "frames/s %s, median %.1f = %.0f tiles/s; tail_fallbacks %d of %d batches"
+                     % (B, lv, a.batches, " ".join("%.1f" % r for r in rates[lv]), fps, fps * T, back[lv], 3 * a.batches))
+    lines.append("(p1) frames/s with levels / without: %.3f; tiles with / without: %.3f"
+                 % (np.median(rates[levels]) / np.median(rates[None]), pyr.T / float(T0)))
+
+    # (p2) the box kernel alone per level, and the ragged warp on the level-0 tiles of the same two frames
+    lib, nb = native.lib(), min(B, 2)
+    src = torch.from_numpy(np.ascontiguousarray(np.stack(frames[:nb]))).cuda()
+    pipe = det._tile_pipe_for(frames, 3, *det._tiles_args(OVERLAP, None, 32, None), 'bgr')
+    mean, std = pipe.mean, pipe.std                      # (the detector's, as the C arrays the entries take)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(f, reps=10):
+        f()
+        ts = []
+        for _ in range(5):
+            e0.record()
+            for _ in range(reps):
+                f()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / reps * 1e3)
+        return float(np.median(ts)), min(ts), max(ts)
+    for l in (0, 1, 2, 3):
+        g = tiles.tile_grid(-(-H // (1 << l)), -(-W // (1 << l)), TILE, TILE, OVERLAP)
+        n = nb * g.T
+        desc = np.zeros((n,), native.TILE_BOX_DESC)
+        for b in range(nb):
+            d = desc[b * g.T:(b + 1) * g.T]
+            d['offset'], d['H'], d['W'], d['pitch'], d['level'] = b * H * W * 3, H, W, 3 * W, l
+            d['y0'], d['x0'] = [o[0] for o in g.origins], [o[1] for o in g.origins]
+        dd = torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).cuda()
+        out = torch.empty((n, 3, TILE, TILE), device="cuda")
+
+        def box():
+            native.check(lib.cn_tile_box_normalize_u8_f32(native.ptr(src), native.ptr(dd), n, TILE, TILE, mean, std,
+                                                          native.ptr(out), native.stream_ptr()), "box")
+        us, lo, hi = timed(box)
+        nbytes = n * TILE * TILE * (3 * 4 ** l + 12)       # (tiles inside the frame; border tiles read less)
+        lines.append("(p2) level %d: %d tiles (%d frames x %d): cn_tile_box_normalize_u8_f32 %.1f us (%.1f .. %.1f), "
+                     "%.1f MB to read + write = %.2f TB/s" % (l, n, nb, g.T, us, lo, hi, nbytes / 1e6, nbytes / us / 1e6))
+        if l == 0:
+            idesc = np.zeros((n,), native.IMAGE_DESC)
+            m = tiles.tile_maps(g, det.opt.down_ratio)[1]
+            for b in range(nb):
+                d = idesc[b * g.T:(b + 1) * g.T]
+                d['offset'], d['H'], d['W'], d['pitch'], d['dst_to_src'] = b * H * W * 3, H, W, 3 * W, m
+            idd = torch.from_numpy(idesc.view(np.uint8).reshape(-1).copy()).cuda()
+            ref = torch.empty_like(out)
+
+            def warp():
+                native.check(lib.cn_warp_normalize_u8_f32_ragged(native.ptr(src), native.ptr(idd), n, TILE, TILE, mean,
+                                                                 std, 0, native.ptr(ref), native.stream_ptr()), "warp")
+            us, lo, hi = timed(warp)
+            box()
+            torch.cuda.synchronize()
+            lines.append("(p2) level 0, the same tiles: cn_warp_normalize_u8_f32_ragged %.1f us (%.1f .. %.1f) = %.2f TB/s; "
+                         "outputs bit-identical: %s"
+                         % (us, lo, hi, nbytes / us / 1e6, torch.equal(out.view(torch.int32), ref.view(torch.int32))))
+        del out
 
 
 # ------------------------------------------------------------------------------------------------
