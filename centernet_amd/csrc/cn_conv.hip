@@ -1138,7 +1138,9 @@ static bool plain_geometry(const cn_conv_desc *d)
 }
 
 // The descriptor checks of cn_conv2d and its queries, then every field of the call that needs no pointer
-static int conv_fill(const cn_conv_desc *d, ConvCall &c)
+// with_map = false (cn_stem_maxpool_supported only): OH .. ox_add are not read -- that question comes before
+// there is an output map, and the pooled map the flag stands for is not the scatter's
+static int conv_fill(const cn_conv_desc *d, ConvCall &c, bool with_map = true)
 {
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 ||
         d->KW <= 0 || d->stride <= 0 || d->dil <= 0 || d->Ho <= 0 || d->Wo <= 0)
@@ -1147,6 +1149,11 @@ static int conv_fill(const cn_conv_desc *d, ConvCall &c)
     const int ho = (d->H + 2 * d->pad_h - (d->dil * (d->KH - 1) + 1)) / d->stride + 1;
     const int wo = (d->W + 2 * d->pad_w - (d->dil * (d->KW - 1) + 1)) / d->stride + 1;
     if (d->oy_mul == 1 && d->ox_mul == 1 && (ho != d->Ho || wo != d->Wo)) return CN_ERR_SHAPE;
+    // the output scatter stays inside the (B, OH, OW) map (long: a large factor must not wrap into range)
+    if (with_map &&
+        (d->OH <= 0 || d->OW <= 0 || d->oy_mul < 1 || d->ox_mul < 1 || d->oy_add < 0 || d->ox_add < 0 ||
+        (long)(d->Ho - 1) * d->oy_mul + d->oy_add >= d->OH || (long)(d->Wo - 1) * d->ox_mul + d->ox_add >= d->OW))
+        return CN_ERR_SHAPE;
     if ((long)d->B * d->H * d->W * (long)(d->in_layout == CN_LAYOUT_NHWC ? d->in_pitch : d->Cin) >=
         (1L << 31))
         return CN_ERR_UNSUPPORTED;
@@ -1245,6 +1252,10 @@ static bool conv16h_shape(const ConvCall &c)
            c.pad_w == 1 && c.dil == 1 && c.plain_geo && !c.stem && !c.out_nchw && !c.out_plain;
 }
 
+// the tile igemm_dispatch's ladder runs a dense or stem call of class `cls` on: pixels, channels
+static int igemm_bm(int cls, bool bm64) { return (cls == 2 && bm64) ? 64 : 128; }
+static int igemm_bn(int cls) { return cls == 2 ? 128 : (cls == 1 ? 64 : 32); }
+
 // The facts that come with pointers are inputs: c.vec_out, has_res / has_scale, and ws_bytes, the size of an
 // aligned workspace (0 = none).  Nothing here reads c.x .. c.y, c.ksplit or c.partial.
 static ConvRoute conv_route(const ConvCall &c, bool has_res, bool has_scale, size_t ws_bytes)
@@ -1282,10 +1293,11 @@ static ConvRoute conv_route(const ConvCall &c, bool has_res, bool has_scale, siz
     // ... unless the 128-pixel grid is exactly one round of two workgroups per CU (512): then the
     // 64-pixel grid (1024 at three per CU = 1.33 rounds) loses (128->256/s2@32^2: 0.210 -> 0.183 ms)
     r.bm64 = (r.cls == 2) && (cn_knobs.bm ? (cn_knobs.bm == 64) : (wgs128 < 1024 && wgs128 != 512));
-    // split-K for under-filled grids (needs the caller's workspace; skipped without it)
-    if (!cn_knobs.nosplit)
-        r.want = plan_ksplit(M, c.Cout, c.KH * c.KW * c.nchunk, r.bm64 ? 64 : 128,
-                             r.cls == 2 ? 128 : (r.cls == 1 ? 64 : 32));
+    // split-K for under-filled grids (needs the caller's workspace; skipped without it).  Plain geometry only: the
+    // first stage stores a partial row at the output pixel's index and the second reads row m of the conv grid, which
+    // are the same number only when the scatter is the identity onto a (B, Ho, Wo) map
+    if (!cn_knobs.nosplit && c.plain_geo)
+        r.want = plan_ksplit(M, c.Cout, c.KH * c.KW * c.nchunk, igemm_bm(r.cls, r.bm64), igemm_bn(r.cls));
     if (r.want > 1 && ws_bytes >= (size_t)r.want * M * c.cout_pad * sizeof(float)) r.ksplit = r.want;
     const bool is3x3 = c.KH == 3 && c.KW == 3 && c.pad_h == 1 && c.pad_w == 1 && c.dil == 1 && c.plain_geo;
     const bool f32s_packed = f32s && !c.in_plain && !c.res_plain && !has_res && has_scale && c.vec_out;
@@ -1341,7 +1353,7 @@ extern "C" size_t cn_conv2d_workspace_bytes(const cn_conv_desc *d)
 extern "C" int cn_stem_maxpool_supported(const cn_conv_desc *d)
 {
     ConvCall c;
-    if (!route_query(d, c)) return 0;
+    if (!d || conv_fill(d, c, false) != CN_OK) return 0;
     c.stem_f32s = c.stem_pool = 1;   // the question: would these flags be accepted
     return conv_route(c, false, true, 0).route == R_STEM_POOL;
 }
@@ -1366,13 +1378,13 @@ extern "C" int cn_conv16_f16_supported(const cn_conv_desc *d)
     return conv_route(c, false, true, 0).route == R_CONV16H;
 }
 
-extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_packed,
-                         const float *scale, const float *shift, const void *residual, void *y,
-                         void *workspace, size_t workspace_bytes, void *stream)
+// The pointer checks of cn_conv2d, the call description and its route: what cn_conv2d and cn_conv2d_route share
+static int conv_prepare(const cn_conv_desc *d, const void *x, const void *w_packed, const float *scale,
+                        const float *shift, const void *residual, void *y, void *workspace,
+                        size_t workspace_bytes, ConvCall &c, ConvRoute &r)
 {
     if (!d || !x || !w_packed || !y) return CN_ERR_NULL;
     if (!cn_aligned16(x) || !cn_aligned16(w_packed)) return CN_ERR_ALIGN;
-    ConvCall c;
     int rc = conv_fill(d, c);
     if (rc != CN_OK) return rc;
     c.x = x; c.w = w_packed; c.scale = scale; c.shift = shift; c.residual = residual; c.y = y;
@@ -1384,33 +1396,90 @@ extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_pac
     const size_t valign = (d->dtype == CN_DTYPE_F16 && !c.out_plain) ? 8 : 16;  // 4 output elements per store
     c.vec_out = (!c.out_nchw && (d->out_pitch & 3) == 0 && (((uintptr_t)y) % valign) == 0 &&
                  (!residual || ((((uintptr_t)residual) % valign) == 0 && (c.res_pitch & 3) == 0))) ? 1 : 0;
-    const ConvRoute r = conv_route(c, residual != nullptr, scale != nullptr,
-                                   (workspace && cn_aligned16(workspace)) ? workspace_bytes : 0);
+    r = conv_route(c, residual != nullptr, scale != nullptr,
+                   (workspace && cn_aligned16(workspace)) ? workspace_bytes : 0);
     c.ksplit = r.ksplit;
     c.partial = r.ksplit > 1 ? (float *)workspace : nullptr;
-    hipStream_t st = (hipStream_t)stream;
+    return CN_OK;
+}
+
+// Run the routed call -- or, for cn_conv2d_route (c.describe set), walk the same switch and let the routed file say
+// which of its forms it would launch; the files with one form have nothing to add to the route
+static int conv_run(const ConvCall &c, const ConvRoute &r, const cn_conv_desc *d, hipStream_t st)
+{
+    const bool ask = c.describe != nullptr;
+    int rc;
     switch (r.route) {
     case R_STEM_POOL: return cn_stem_pool_f32s(c, st);
     case R_STEM: return cn_stem_conv_f32(c, cn_knobs.stem_persist, st);
-    case R_CONV16: return cn_conv3x3_c16(c, st);
-    case R_CONV16S: return cn_conv3x3_c16s(c, st);
-    case R_CONV16H: return cn_conv3x3_c16h(c, st);
+    case R_CONV16: return ask ? CN_OK : cn_conv3x3_c16(c, st);
+    case R_CONV16S: return ask ? CN_OK : cn_conv3x3_c16s(c, st);
+    case R_CONV16H: return ask ? CN_OK : cn_conv3x3_c16h(c, st);
     case R_HALO: return cn_conv3x3s1(c, r.cls, st);
-    case R_S2P: return cn_conv3x3s2_persist(c, st);
-    case R_PROJ: return cn_proj1x1_f32s(c, st);
+    case R_S2P: return ask ? CN_OK : cn_conv3x3s2_persist(c, st);
+    case R_PROJ: return ask ? CN_OK : cn_proj1x1_f32s(c, st);
     case R_OFFCONV:   // its K split ends in the implicit GEMM's second stage
         rc = cn_offconv_f32s(c, st);
-        if (rc != CN_OK || c.ksplit == 1) return rc;
+        if (rc != CN_OK || c.ksplit == 1 || ask) return rc;
         return launch_splitk_reduce(c.dtype, igemm_args(c, d), 8192, st);
     case R_IGEMM: break;
     default: return CN_ERR_UNSUPPORTED;
     }
+    // the class and pixel tile each of the three dispatches below hands igemm_dispatch
+    const int cls = c.stem ? cout_class(c.Cout) : r.cls;
+    const bool bm64 = !c.out_nchw && !c.stem && r.bm64;
+    if (ask) {
+        c.describe->m_tile = igemm_bm(cls, bm64);
+        c.describe->n_tile = igemm_bn(cls);
+        return CN_OK;
+    }
     const IgemmArgs a = igemm_args(c, d);
-    if (c.out_nchw) return igemm_dispatch<A_DENSE, true>(c.dtype, r.cls, false, a, st);
-    if (c.stem) return igemm_dispatch<A_STEM, false>(c.dtype, cout_class(c.Cout), false, a, st);
-    rc = igemm_dispatch<A_DENSE, false>(c.dtype, r.cls, r.bm64, a, st);
+    if (c.out_nchw) return igemm_dispatch<A_DENSE, true>(c.dtype, cls, bm64, a, st);
+    if (c.stem) return igemm_dispatch<A_STEM, false>(c.dtype, cls, bm64, a, st);
+    rc = igemm_dispatch<A_DENSE, false>(c.dtype, cls, bm64, a, st);
     if (rc != CN_OK || c.ksplit == 1) return rc;
     return launch_splitk_reduce(c.dtype, a, 8192, st);
+}
+
+extern "C" int cn_conv2d(const cn_conv_desc *d, const void *x, const void *w_packed,
+                         const float *scale, const float *shift, const void *residual, void *y,
+                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    ConvCall c;
+    ConvRoute r;
+    const int rc = conv_prepare(d, x, w_packed, scale, shift, residual, y, workspace, workspace_bytes, c, r);
+    if (rc != CN_OK) return rc;
+    return conv_run(c, r, d, (hipStream_t)stream);
+}
+
+// Host-only: the checks, the route and the routed file's own word on its form; no pointer is read, nothing launched
+extern "C" int cn_conv2d_route(const cn_conv_desc *d, const void *x, const void *w_packed,
+                               const float *scale, const float *shift, const void *residual, void *y,
+                               void *workspace, size_t workspace_bytes, void *stream,
+                               cn_conv_route_info *info)
+{
+    (void)stream;
+    if (!info) return CN_ERR_NULL;
+    *info = {};
+    ConvCall c;
+    ConvRoute r;
+    int rc = conv_prepare(d, x, w_packed, scale, shift, residual, y, workspace, workspace_bytes, c, r);
+    if (rc != CN_OK) return rc;
+    ConvForm f = {};
+    c.describe = &f;
+    rc = conv_run(c, r, d, nullptr);
+    static_assert(R_NONE == CN_ROUTE_NONE && R_STEM_POOL == CN_ROUTE_STEM_POOL && R_STEM == CN_ROUTE_STEM &&
+                      R_CONV16 == CN_ROUTE_CONV16 && R_CONV16S == CN_ROUTE_CONV16S && R_CONV16H == CN_ROUTE_CONV16H &&
+                      R_OFFCONV == CN_ROUTE_OFFCONV && R_HALO == CN_ROUTE_HALO && R_S2P == CN_ROUTE_S2P &&
+                      R_PROJ == CN_ROUTE_PROJ && R_IGEMM == CN_ROUTE_IGEMM,
+                  "the public CN_ROUTE_* are the R_* values");
+    info->route = r.route;
+    if (rc != CN_OK) return rc;
+    info->n_tile = f.n_tile; info->m_tile = f.m_tile;
+    info->ksplit = r.ksplit; info->want = r.want;
+    info->variant = f.variant;
+    info->grid_x = f.grid_x; info->grid_y = f.grid_y;
+    return CN_OK;
 }
 
 extern "C" int cn_conv2d_f32(const cn_conv_desc *d, const float *x, const float *w_packed,

@@ -75,6 +75,12 @@ struct C3Args {
     uint32_t *range;             // f32s: [0] max |stored output| / hidden tile, [1] max |split plain input|
 };
 
+// The host's view of a launch: the kernel's arguments (the kernels take the C3Args slice) and the record a
+// cn_conv2d_route query wants filled in place of the launch (cn_internal.h; null: launch)
+struct C3Launch : C3Args {
+    ConvForm *describe;
+};
+
 // Fused detection heads (HEADS = true): blockIdx.y selects the head; its 64 hidden channels
 // never leave the workgroup.
 constexpr int MAX_HEADS = 8;
@@ -1103,16 +1109,20 @@ inline bool c3_occ4_pays(long wgs)
 }
 
 template <typename T, int TW, bool DECONV = false>
-int launch_c3_occ4(const C3Args &a, hipStream_t st)
+int launch_c3_occ4(const C3Launch &a, hipStream_t st)
 {
     constexpr int TH = 128 / TW;
     constexpr size_t lds = c3_union_floats<TW, 64, 2, false, 128, 1>() * 4 + 128 * 4;
-    CN_SET_MAX_LDS_ONCE((conv3x3s1_occ4_kernel<T, TW, DECONV>), lds);
     C3Args b = a;
     b.tiles_x = cn_cdiv(a.W, TW);
     b.tiles_y = cn_cdiv(a.H, TH);
     b.stagger = 0;
     dim3 grid((unsigned)(a.B * b.tiles_x * b.tiles_y), cn_cdiv(a.Cout, 64), DECONV ? 4 : 1);
+    if (a.describe) {
+        *a.describe = {CN_C3_TILE | CN_C3_OCC4 | (TW == 32 ? CN_C3_TW32 : 0), 64, 128, (int)grid.x, (int)grid.y};
+        return CN_OK;
+    }
+    CN_SET_MAX_LDS_ONCE((conv3x3s1_occ4_kernel<T, TW, DECONV>), lds);
     const C3Heads none = {};
     hipLaunchKernelGGL((conv3x3s1_occ4_kernel<T, TW, DECONV>), grid, dim3(256), lds, st, b, none);
     CN_CHECK_LAUNCH();
@@ -1121,12 +1131,11 @@ int launch_c3_occ4(const C3Args &a, hipStream_t st)
 
 template <typename T, int TW, int BN, int WM, int WN, bool HEADS = false, int BM = 128,
           bool KSKIP = false, bool DECONV = false, int NBUFB = 2, int PDQ = CN_F32S_PREFETCH_TAPS>
-int launch_c3(const C3Args &a, hipStream_t st, const C3Heads *hd = nullptr)
+int launch_c3(const C3Launch &a, hipStream_t st, const C3Heads *hd = nullptr)
 {
     constexpr int TH = BM / TW;
     constexpr size_t lds = c3_union_floats<TW, BN, WM, HEADS, BM, NBUFB>() * 4 + BM * 4 +
                            c3_table_floats<BN, WM, HEADS>() * 4;
-    CN_SET_MAX_LDS_ONCE((conv3x3s1_kernel<T, TW, BN, WM, WN, HEADS, BM, KSKIP, DECONV, NBUFB, PDQ>), lds);
     C3Args b = a;
     b.tiles_x = cn_cdiv(a.W, TW);
     b.tiles_y = cn_cdiv(a.H, TH);
@@ -1157,6 +1166,15 @@ int launch_c3(const C3Args &a, hipStream_t st, const C3Heads *hd = nullptr)
             b.stagger = 0;
         }
     }
+    if (a.describe) {
+        constexpr bool f32s = std::is_same<T, cn_f32s>::value;
+        *a.describe = {CN_C3_TILE | (TW == 32 ? CN_C3_TW32 : 0) | (WM * WN == 8 ? CN_C3_WAVES8 : 0) |
+                           (KSKIP ? CN_C3_KSKIP : 0) | ((f32s && NBUFB == 0) ? CN_C3_WREG : 0) |
+                           ((f32s && NBUFB != 0) ? (PDQ << 12) : 0),
+                       BN, BM, (int)grid.x, (int)grid.y};
+        return CN_OK;
+    }
+    CN_SET_MAX_LDS_ONCE((conv3x3s1_kernel<T, TW, BN, WM, WN, HEADS, BM, KSKIP, DECONV, NBUFB, PDQ>), lds);
     const C3Heads none = {};
     hipLaunchKernelGGL((conv3x3s1_kernel<T, TW, BN, WM, WN, HEADS, BM, KSKIP, DECONV, NBUFB, PDQ>), grid,
                        dim3(WM * WN * 64), lds,
@@ -1179,7 +1197,7 @@ int launch_c3(const C3Args &a, hipStream_t st, const C3Heads *hd = nullptr)
 // 256->256@32^2 0.144 -> 0.126, 512->512@16^2 0.142 -> 0.115); eight waves of 32 x 64 lose
 // (0.183 / 0.173 / 0.126), and for 64- / 32-wide tiles the LDS form is as fast or faster
 // (64->64@128^2 0.175 vs 0.173, 128->27@64^2 0.068 vs 0.057), so those keep it.
-static int c3_dispatch_f32s_wreg(C3Args &a, hipStream_t st)
+static int c3_dispatch_f32s_wreg(C3Launch &a, hipStream_t st)
 {
     const bool wide = a.W >= 32;
     return wide ? launch_c3<cn_f32s, 32, 128, 2, 2, false, 128, false, false, 0>(a, st)
@@ -1187,7 +1205,7 @@ static int c3_dispatch_f32s_wreg(C3Args &a, hipStream_t st)
 }
 
 template <typename T>
-static int c3_dispatch(C3Args &a, int bn_class, hipStream_t st)
+static int c3_dispatch(C3Launch &a, int bn_class, hipStream_t st)
 {
     // 4 x 32 tiles keep an MFMA block on one halo row; key 21 bit 2 (A/B): 8 x 16 tiles everywhere
     const bool wide = a.W >= 32 && !(std::is_same<T, cn_f32s>::value && (cn_knobs.f32s_policy & 4));
@@ -1293,7 +1311,7 @@ static void c3_fill(C3Args &a, const ConvCall &c)
 // (fp16 tensors: fp32 accumulate, scale / shift fp32)
 int cn_conv3x3s1(const ConvCall &c, int bn_class, hipStream_t st)
 {
-    C3Args a = {};
+    C3Launch a = {};
     c3_fill(a, c);
     a.bm256 = cn_knobs.bm256;
     a.waves8 = cn_knobs.waves8;
@@ -1303,8 +1321,14 @@ int cn_conv3x3s1(const ConvCall &c, int bn_class, hipStream_t st)
     a.ncb = a.cout_pad / 32;
     a.wfrag_off = (size_t)9 * a.cout_pad * a.cin_pad * 4;   // behind the row-ordered copy
     // f32s tensors on both sides: the persistent loader / consumer kernel (cn_conv3x3p.hip)
-    if (c.dtype == CN_DTYPE_F32S && !a.dbg && c.vec_out && c.scale && cn_conv3x3p_takes(c))
+    if (c.dtype == CN_DTYPE_F32S && !a.dbg && c.vec_out && c.scale && cn_conv3x3p_takes(c)) {
+        if (c.describe) {
+            c.describe->variant = CN_C3_PERSIST;
+            return CN_OK;
+        }
         return cn_conv3x3s1_persist(c, st);
+    }
+    a.describe = c.describe;
     if (c.dtype == CN_DTYPE_F32S) return c3_dispatch<cn_f32s>(a, bn_class, st);
     return c.dtype == CN_DTYPE_F16 ? c3_dispatch<_Float16>(a, bn_class, st) : c3_dispatch<float>(a, bn_class, st);
 }
@@ -1355,7 +1379,7 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
     // (cn_conv3x3p.hip, hidden layer in registers)
     if (f32s && cn_heads3x3p_takes(B, H, W, in_pitch, head_conv, n_heads, heads, (flags & CN_CONV_X_PLAIN) != 0))
         return cn_heads3x3p(x, B, H, W, Cin, in_pitch, w1_packed, scale1, bias1, n_heads, heads, ctl, st);
-    C3Args a = {};
+    C3Launch a = {};
     c3_set_ctl(a, ctl);
     a.x = x; a.w = w1_packed; a.scale = scale1; a.shift = bias1; a.residual = nullptr; a.y = nullptr;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = n_heads * head_conv; a.in_pitch = in_pitch;
@@ -1398,7 +1422,7 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
 // w_packed: cn_pack_deconv4x4s2_weight_f32 layout [parity 4][tap 4][cout_pad][cin_pad].
 int cn_deconv4x4s2_halo(const ConvCall &c, hipStream_t st)
 {
-    C3Args a = {};
+    C3Launch a = {};
     c3_fill(a, c);
     const int B = c.B, H = c.H, W = c.W, Cout = c.Cout, dtype = c.dtype;
     const bool wide = W >= 32;

@@ -8,6 +8,10 @@
 // ---- the convolution family: one call description.  cn_conv.hip fills it once per cn_conv2d /
 // cn_conv_transpose4x4s2 call (after the descriptor checks); conv_route() there and every launcher and `takes`
 // predicate below read it.  An extra argument only for what is not a fact of the call (tile class, tuning key).
+// "Describe, don't launch": what cn_conv2d_route hands a routed file.  A launcher that finds one in its call fills it
+// at the point where it would launch -- from the same template arguments and grid -- and returns without touching the
+// device; cn_conv2d never sets one.  variant: the CN_C3_* bits, a CN_STEM_* form or the teams of cn_offconv
+struct ConvForm { int variant, n_tile, m_tile, grid_x, grid_y; };
 struct ConvCall {
     const void *x, *w;                    // tensors of `dtype` (the stem: fp32 NCHW image and fp32 weights)
     const float *scale, *shift;
@@ -24,13 +28,13 @@ struct ConvCall {
     int ksplit;                           // K slices of this launch (1 = no split)
     float *partial;                       // split-K workspace when ksplit > 1
     int cin_pad, cout_pad, nchunk;        // packed weight: K per tap (stem: of all taps), rows per tap, K chunks
+    ConvForm *describe;                   // cn_conv2d_route only (above); null: launch
 };
 
 // ---- cn_stem.hip
 int cn_stem_pool_rows(const ConvCall &c);   // pooled rows per strip of the stem + max-pool kernel, 0 = not taken
 int cn_stem_pool_f32s(const ConvCall &c, hipStream_t st);
-// the kernel cn_stem_conv_f32 runs for the call; persistent: cn_set_tuning key 12
-enum { CN_STEM_NONE = 0, CN_STEM_WINDOW, CN_STEM_PERSIST, CN_STEM_PERSIST_F32S, CN_STEM_16S };
+// the kernel cn_stem_conv_f32 runs for the call: CN_STEM_* of include/centernet_amd.h; persistent: cn_set_tuning key 12
 int cn_stem_form(const ConvCall &c, int persistent);
 int cn_stem_conv_f32(const ConvCall &c, int persistent, hipStream_t st);
 

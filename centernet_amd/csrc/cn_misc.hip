@@ -337,7 +337,7 @@ inline int blocks_for(size_t total, int per_block, int cap)
 
 }  // namespace
 
-extern "C" int cn_version(void) { return 311; }  // 0.3.11: cn_get_tuning, cn_reset_tuning
+extern "C" int cn_version(void) { return 312; }  // 0.3.12: cn_conv2d_route; cn_conv2d checks the output scatter
 
 extern "C" const char *cn_arch(void) { return "gfx950"; }
 

@@ -248,7 +248,12 @@ int cn_offconv_f32s(const ConvCall &c, hipStream_t st)
     a.partial = c.ksplit > 1 ? c.partial : nullptr;
     dim3 grid((unsigned)(c.B * a.tiles_x * a.tiles_y), 1, (unsigned)c.ksplit);
     // four-wave workgroups from three tiles per CU up (four of them fit a CU), else eight waves in two teams
-    if ((long)grid.x * c.ksplit >= cn_knobs.offconv_teams1) {
+    const bool one_team = (long)grid.x * c.ksplit >= cn_knobs.offconv_teams1;
+    if (c.describe) {
+        *c.describe = {one_team ? 1 : 2, 0, 0, (int)grid.x, (int)grid.y};
+        return CN_OK;
+    }
+    if (one_team) {
         CN_SET_MAX_LDS_ONCE(offconv_kernel<1>, O_HBYTES);
         hipLaunchKernelGGL(offconv_kernel<1>, grid, dim3(256), O_HBYTES, st, a);
     } else {

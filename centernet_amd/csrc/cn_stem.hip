@@ -38,6 +38,19 @@ struct StemArgs {
     int dbg;          // stem + max-pool kernel, probe instantiation (cn_set_tuning key 43): 1 = no MFMAs, 2 = no window
                       // stores, 4 = no image loads, 8 = no pooling / output stores, 16 = no barriers
 };
+// The host's view of a launch: the kernel's arguments (the kernels take the StemArgs slice), and the record a
+// cn_conv2d_route query wants filled in place of the launch (cn_internal.h; null: launch) with the form it is of
+struct StemLaunch : StemArgs {
+    ConvForm *describe;
+    int form;
+};
+// true: the launcher was asked to describe, not to launch
+inline bool stem_describe(const StemLaunch &a, unsigned gx, unsigned gy)
+{
+    if (!a.describe) return false;
+    *a.describe = {a.form, 0, 0, (int)gx, (int)gy};
+    return true;
+}
 
 template <int BN>
 __global__ __launch_bounds__(NT) void stem_conv_f32_kernel(const StemArgs a)
@@ -974,14 +987,15 @@ int launch_stem_pool_f32s(const StemArgs &a0, int B, int R, hipStream_t st)
 }
 
 template <int BN>
-int launch_stem_persist_f32s(const StemArgs &a, int B, hipStream_t st)
+int launch_stem_persist_f32s(const StemLaunch &a, int B, hipStream_t st)
 {
     constexpr size_t lds = (size_t)2 * CM_PLANE + (size_t)2 * BN * SLDW * 2;
     const long total = (long)B * a.tiles_per_image;
     const int wgs = (int)(total < 512 ? total : 512);  // two resident workgroups per CU
     dim3 grid(wgs, cn_cdiv(a.Cout, BN));
+    if (stem_describe(a, grid.x, grid.y)) return CN_OK;
     CN_SET_MAX_LDS_ONCE((stem_persist_f32s_kernel<BN>), lds);
-    hipLaunchKernelGGL((stem_persist_f32s_kernel<BN>), grid, dim3(NT), lds, st, a, (int)total);
+    hipLaunchKernelGGL((stem_persist_f32s_kernel<BN>), grid, dim3(NT), lds, st, (const StemArgs &)a, (int)total);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -1188,26 +1202,28 @@ __global__ __launch_bounds__(NT, 2) void stem16s_kernel(const StemArgs a, int to
     if (a.range) cn_rng_commit(a.range, 1, rng_in);
 }
 
-int launch_stem16s(const StemArgs &a, int B, hipStream_t st)
+int launch_stem16s(const StemLaunch &a, int B, hipStream_t st)
 {
     constexpr size_t lds = (size_t)4 * S16_COPY;
     const long total = (long)B * a.tiles_per_image;
     const int wgs = (int)(total < 512 ? total : 512);  // two resident workgroups per CU
-    hipLaunchKernelGGL(stem16s_kernel, dim3(wgs), dim3(NT), lds, st, a, (int)total);
+    if (stem_describe(a, wgs, 1)) return CN_OK;
+    hipLaunchKernelGGL(stem16s_kernel, dim3(wgs), dim3(NT), lds, st, (const StemArgs &)a, (int)total);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
 
 template <int BN, int S>
-int launch_stem_persist(const StemArgs &a, int B, hipStream_t st)
+int launch_stem_persist(const StemLaunch &a, int B, hipStream_t st)
 {
     constexpr int WXP = ((BM - 1) * S + PKW) | 1;
     constexpr size_t lds = (size_t)((((PROWS + 1) * WXP + 3) & ~3) + NT + (BN == 16 ? 0 : BN * PLDW)) * 4;
     const long total = (long)B * a.tiles_per_image;
     const int wgs = (int)(total < 512 ? total : 512);  // two resident workgroups per CU
     dim3 grid(wgs, cn_cdiv(a.Cout, BN));
+    if (stem_describe(a, grid.x, grid.y)) return CN_OK;
     CN_SET_MAX_LDS_ONCE((stem_persist_f32_kernel<BN, S>), lds);
-    hipLaunchKernelGGL((stem_persist_f32_kernel<BN, S>), grid, dim3(NT), lds, st, a, (int)total);
+    hipLaunchKernelGGL((stem_persist_f32_kernel<BN, S>), grid, dim3(NT), lds, st, (const StemArgs &)a, (int)total);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -1229,9 +1245,10 @@ int cn_stem_pool_rows(const ConvCall &c)
 }
 
 // use_ctl = false: the fp32 window kernel, which splits nothing
-static StemArgs stem_args(const ConvCall &c, bool use_ctl, int tiles_per_image)
+static StemLaunch stem_args(const ConvCall &c, bool use_ctl, int tiles_per_image, int form)
 {
-    StemArgs a = {};
+    StemLaunch a = {};
+    a.describe = c.describe; a.form = form;
     a.x_mul = (use_ctl && c.ctl && c.ctl->x_mul != 0.f) ? c.ctl->x_mul : 1.f;
     a.range = (use_ctl && c.ctl) ? c.ctl->range : nullptr;
     a.x = (const float *)c.x; a.w = (const float *)c.w; a.scale = c.scale; a.shift = c.shift; a.y = (float *)c.y;
@@ -1247,7 +1264,8 @@ int cn_stem_pool_f32s(const ConvCall &c, hipStream_t st)
     const int R = cn_stem_pool_rows(c);
     if (!R) return CN_ERR_UNSUPPORTED;
     if (c.stem_y_f32s && ((c.out_pitch & 31) || (((uintptr_t)c.y) & 127u))) return CN_ERR_ALIGN;
-    StemArgs a = stem_args(c, true, c.Ho * (c.Wo / BM));
+    if (c.describe) return CN_OK;   // one form: the route says it all
+    StemArgs a = stem_args(c, true, c.Ho * (c.Wo / BM), 0);
     a.y_f32s = c.stem_y_f32s;
     switch (c.Wo / BM) {
     case 1: return launch_stem_pool_f32s<1>(a, c.B, R, st);
@@ -1296,7 +1314,7 @@ int cn_stem_conv_f32(const ConvCall &c, int persistent, hipStream_t st)
     const int B = c.B, Cout = c.Cout, stride = c.stride;
     if (form == CN_STEM_NONE) return CN_ERR_UNSUPPORTED;
     if (form != CN_STEM_WINDOW) {
-        const StemArgs a = stem_args(c, true, c.Ho * (c.Wo / BM));
+        const StemLaunch a = stem_args(c, true, c.Ho * (c.Wo / BM), form);
         if (form == CN_STEM_PERSIST_F32S)
             return Cout > 32 ? launch_stem_persist_f32s<64>(a, B, st)
                              : launch_stem_persist_f32s<32>(a, B, st);
@@ -1310,17 +1328,18 @@ int cn_stem_conv_f32(const ConvCall &c, int persistent, hipStream_t st)
         return stride == 2 ? launch_stem_persist<32, 2>(a, B, st)
                            : launch_stem_persist<32, 1>(a, B, st);
     }
-    const StemArgs a = stem_args(c, false, cn_cdiv(c.Ho * c.Wo, BM));
+    const StemLaunch a = stem_args(c, false, cn_cdiv(c.Ho * c.Wo, BM), form);
     const int KP = c.cin_pad;
     const int bn = Cout > 32 ? 64 : 32;
     const size_t lds = (size_t)WIN_MAX * 4 + (size_t)bn * (KP + 4) * 4 + (size_t)KP * 4 + BM * 4;
     dim3 grid(a.tiles_per_image, cn_cdiv(Cout, bn), B);
+    if (stem_describe(a, grid.x, grid.y)) return CN_OK;
     if (bn == 64) {
         CN_SET_MAX_LDS_ONCE(stem_conv_f32_kernel<64>, 160 * 1024);
-        hipLaunchKernelGGL(stem_conv_f32_kernel<64>, grid, dim3(NT), lds, st, a);
+        hipLaunchKernelGGL(stem_conv_f32_kernel<64>, grid, dim3(NT), lds, st, (const StemArgs &)a);
     } else {
         CN_SET_MAX_LDS_ONCE(stem_conv_f32_kernel<32>, 160 * 1024);
-        hipLaunchKernelGGL(stem_conv_f32_kernel<32>, grid, dim3(NT), lds, st, a);
+        hipLaunchKernelGGL(stem_conv_f32_kernel<32>, grid, dim3(NT), lds, st, (const StemArgs &)a);
     }
     CN_CHECK_LAUNCH();
     return CN_OK;

@@ -636,7 +636,17 @@ class PlanBuilder:
                                native.stream_ptr())
             if rc:
                 native.check(rc, "cn_conv2d")
+
+        def route():
+            """the kernel, its form, tile and K split the launch gets (cn_conv2d_route: host only)"""
+            xp = ctypes.c_void_p(self.input.t.data_ptr()) if is_input else x.ptr()
+            wsp = ctypes.c_void_p(self.ws.data_ptr()) if self.ws is not None else None
+            info = native.ConvRouteInfo()
+            native.check(lib.cn_conv2d_route(dref, xp, wpp, sp, hp, rp, op, wsp, self.ws_bytes,
+                                             native.stream_ptr(), ctypes.byref(info)), "cn_conv2d_route")
+            return info
         self.ops.append(run)
+        meta = dict(meta, route=route)
         self.meta.append(meta)
         self.trace.append((meta["kind"], out))
 

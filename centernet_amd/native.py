@@ -45,6 +45,25 @@ DCN_GATHER, DCN_GATHER_PAD, DCN_WINDOW, DCN_TEAM_T, DCN_TEAM_N, DCN_WIDE4, DCN_W
 DCNH_WINDOW = 7      # CN_DCNH_WINDOW: the LDS-window form of DTYPE_F16 calls
 DCN_FLAG_PREFETCH, DCN_FLAG_STAGGER, DCN_FLAG_TILE2D, DCN_FLAG_VEC_OUT = 1, 2, 4, 8
 DCN_FORM_NAMES = ("gather", "gather_pad", "window", "team_t", "team_n", "wide4", "wide8")
+# routes and variants of cn_conv2d_route: the #defines CN_<name> of the header (tests/test_conv_route_cases_host.py
+# compares them)
+(ROUTE_NONE, ROUTE_STEM_POOL, ROUTE_STEM, ROUTE_CONV16, ROUTE_CONV16S, ROUTE_CONV16H, ROUTE_OFFCONV, ROUTE_HALO,
+ ROUTE_S2P, ROUTE_PROJ, ROUTE_IGEMM) = range(11)
+CONV_ROUTE_NAMES = ("none", "stem_pool", "stem", "conv16", "conv16s", "conv16h", "offconv", "halo", "s2p", "proj",
+                    "igemm")
+STEM_NONE, STEM_WINDOW, STEM_PERSIST, STEM_PERSIST_F32S, STEM_16S = range(5)
+C3_PERSIST, C3_TILE = 1, 2
+C3_TW32, C3_WAVES8, C3_OCC4, C3_KSKIP, C3_WREG = 0x10, 0x20, 0x40, 0x80, 0x100
+
+
+def c3_prefetch(variant):
+    """CN_C3_PREFETCH: taps of weight prefetch of an f32s tile kernel with an LDS weight tile."""
+    return (variant >> 12) & 3
+
+
+def conv_route_name(route):
+    """Readable name of cn_conv_route_info.route."""
+    return CONV_ROUTE_NAMES[route]
 
 
 def dcn_form_name(form):
@@ -77,6 +96,12 @@ class F32sCtl(ctypes.Structure):
 class DcnRouteInfo(ctypes.Structure):
     """Mirror of ``cn_dcn_route_info``: the kernel form, grid and K split of a cn_dcn_v2_forward_nhwc call."""
     _fields_ = [(n, ctypes.c_int) for n in ("form", "grid_x", "grid_y", "ksplit", "flags")]
+
+
+class ConvRouteInfo(ctypes.Structure):
+    """Mirror of ``cn_conv_route_info``: the kernel, its form, tile and K split of a cn_conv2d call."""
+    _fields_ = [(n, ctypes.c_int) for n in ("route", "n_tile", "m_tile", "ksplit", "want", "variant", "grid_x",
+                                            "grid_y")]
 
 
 class ConvDesc(ctypes.Structure):
@@ -214,6 +239,8 @@ def _declare(lib):
     lib.cn_conv2d_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
     lib.cn_conv2d.restype = i
     lib.cn_conv2d.argtypes = [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.cn_conv2d_route.restype = i
+    lib.cn_conv2d_route.argtypes = lib.cn_conv2d.argtypes + [ctypes.POINTER(ConvRouteInfo)]
     lib.cn_upsample2x_add_f16.restype = i
     lib.cn_upsample2x_add_f16.argtypes = [vp, vp, vp, i, i, i, i, vp]
     lib.cn_packed_deconv4x4s2_weight_floats.restype = sz

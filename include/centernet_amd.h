@@ -495,6 +495,52 @@ size_t cn_conv2d_workspace_bytes(const cn_conv_desc *desc);
 int cn_conv2d(const cn_conv_desc *desc, const void *x, const void *w_packed, const float *scale,
               const float *shift, const void *residual, void *y, void *workspace,
               size_t workspace_bytes, void *stream);
+/* The output scatter must fit the map: oy_mul, ox_mul >= 1, oy_add, ox_add >= 0, (Ho-1)*oy_mul + oy_add < OH and
+ * (Wo-1)*ox_mul + ox_add < OW, CN_ERR_SHAPE otherwise (nothing is launched; the queries answer 0).  A call whose
+ * scatter is not the identity onto a (B, Ho, Wo) map runs on the implicit GEMM and is never K-split. */
+
+/* Which kernel a cn_conv2d call runs and in which form: the arguments of cn_conv2d, the status cn_conv2d's host
+ * checks would return (CN_ERR_UNSUPPORTED where no kernel takes the call), and *info.  Host-only: of the pointers
+ * only null-ness and alignment count, none is dereferenced, nothing is launched.  The answer depends on the
+ * cn_set_tuning keys as the call does.  On a status other than CN_OK *info is zero except route. */
+#define CN_ROUTE_NONE 0
+#define CN_ROUTE_STEM_POOL 1  /* stem + max-pool (CN_CONV_STEM_MAXPOOL) */
+#define CN_ROUTE_STEM 2       /* LDS-window / persistent stem kernels; variant: CN_STEM_* */
+#define CN_ROUTE_CONV16 3     /* 16-channel 3x3, fp32 */
+#define CN_ROUTE_CONV16S 4    /* ... f32s arithmetic on plain tensors */
+#define CN_ROUTE_CONV16H 5    /* ... half tensors */
+#define CN_ROUTE_OFFCONV 6    /* offset / mask convolution; variant: teams per workgroup (1 or 2) */
+#define CN_ROUTE_HALO 7       /* 3x3 / stride 1: variant CN_C3_PERSIST, or CN_C3_TILE with the CN_C3_* bits */
+#define CN_ROUTE_S2P 8        /* persistent 3x3 / stride 2 */
+#define CN_ROUTE_PROJ 9       /* 1x1 projection */
+#define CN_ROUTE_IGEMM 10     /* implicit GEMM: m_tile pixels x n_tile channels, ksplit K slices */
+/* variant of CN_ROUTE_STEM (0 on every other route but those named above) */
+#define CN_STEM_NONE 0
+#define CN_STEM_WINDOW 1
+#define CN_STEM_PERSIST 2
+#define CN_STEM_PERSIST_F32S 3
+#define CN_STEM_16S 4
+/* variant of CN_ROUTE_HALO: the persistent loader / consumer kernel, or the LDS-halo tile kernel with its form:
+ * m_tile pixels (128 or 256) in rows of 16 or 32, n_tile channels, 4 or 8 waves */
+#define CN_C3_PERSIST 1
+#define CN_C3_TILE 2
+#define CN_C3_TW32 0x10       /* tile rows of 32 pixels (else 16) */
+#define CN_C3_WAVES8 0x20     /* eight waves per workgroup (else four) */
+#define CN_C3_OCC4 0x40       /* the four-workgroups-per-CU form */
+#define CN_C3_KSKIP 0x80      /* fp32: the empty K groups of the last chunk are skipped */
+#define CN_C3_WREG 0x100      /* f32s: weights streamed into registers, no LDS weight tile */
+#define CN_C3_PREFETCH(v) (((v) >> 12) & 3)   /* f32s, LDS weight tile: taps of weight prefetch (1..3) */
+typedef struct cn_conv_route_info {
+    int route;            /* CN_ROUTE_* */
+    int n_tile, m_tile;   /* channels / pixels per workgroup tile: CN_ROUTE_HALO tile kernel and CN_ROUTE_IGEMM, else 0 */
+    int ksplit;           /* K slices the call runs with (1: no split) */
+    int want;             /* ... and those the layer wants: cn_conv2d_workspace_bytes = want * B*Ho*Wo * cout_pad32 * 4, 0 for want 1 */
+    int variant;
+    int grid_x, grid_y;   /* workgroups of the launch: CN_ROUTE_STEM, CN_ROUTE_OFFCONV, CN_ROUTE_HALO tile kernel; else 0 */
+} cn_conv_route_info;
+int cn_conv2d_route(const cn_conv_desc *d, const void *x, const void *w_packed, const float *scale,
+                    const float *shift, const void *residual, void *y, void *workspace,
+                    size_t workspace_bytes, void *stream, cn_conv_route_info *info);
 
 /* ------------------------------------------------------------------------
  * ConvTranspose2d(kernel 4, stride 2, padding 1, bias=False) + BN(eval) + ReLU.

@@ -37,6 +37,16 @@ def _run(pb):
     torch.cuda.synchronize()
 
 
+def _route(pb, i=0):
+    """what cn_conv2d_route says of the plan's i-th convolution, under the keys set now (host only)"""
+    return [m for m in pb.meta if m["kind"] == "conv"][i]["route"]()
+
+
+def _route_name(pb, i=0):
+    from centernet_amd import native
+    return native.conv_route_name(_route(pb, i).route)
+
+
 def _bn(C, seed):
     bn = torch.nn.BatchNorm2d(C)
     synth.fill_state_dict_(bn, seed)
@@ -72,39 +82,85 @@ def _bn(C, seed):
 ])
 @pytest.mark.parametrize("split", [True, False], ids=["f32s", "fp32mfma"])
 def test_conv_bn_relu_residual(dev, cfg, split):
-    _conv_case(dev, cfg, split)
+    from centernet_amd import native
+    says = unforced = None
+    if cfg[1] == 16 and cfg[3] % 128 == 0:
+        # the 16-channel cases run on cn_conv16.hip (an f32s plan: its f32s form at stride 1, and at stride 2 the
+        # fp32 form, which the plan builder asks for by dtype), and with key 10 = 1 they would not
+        want = "conv16s" if (split and cfg[6] == 1) else "conv16"
+        says = lambda r: native.conv_route_name(r.route) == want
+        unforced = ({10: 1}, lambda r: native.conv_route_name(r.route) == "igemm")
+    _conv_case(dev, cfg, split, says=says, unforced=unforced)
 
 
 def test_conv_256_pixel_tiles(dev):
     """Opt-in 8 x 32 tiles of the LDS-halo kernel (cn_set_tuning key 14)."""
     from centernet_amd import native
+    tile = lambda m: (lambda r: native.conv_route_name(r.route) == "halo" and r.variant & native.C3_TILE and
+                      (r.n_tile, r.m_tile) == (64, m))
     with native.tuning({14: 1}):
-        _conv_case(dev, (16, 64, 128, 128, 64, 3, 1, 1, False, True, True, True))
-        _conv_case(dev, (17, 48, 100, 132, 64, 3, 1, 1, True, False, True, False))
+        _conv_case(dev, (16, 64, 128, 128, 64, 3, 1, 1, False, True, True, True), says=tile(256),
+                   unforced=({14: 0}, tile(128)))
+        _conv_case(dev, (17, 48, 100, 132, 64, 3, 1, 1, True, False, True, False), says=tile(256),
+                   unforced=({14: 0}, tile(128)))
 
 
 def test_conv_four_workgroups_per_cu_variant(dev):
-    """64-wide halo tiles at four workgroups per CU (single-buffered weights; key 19)."""
+    """64-wide halo tiles at four workgroups per CU (single-buffered weights; key 19).  Key 5 = 1: with the
+    plan's workspace both layers (KT >= 16 on few tiles) would split K and run on the implicit GEMM in both arms,
+    as cn_conv2d_route showed they did."""
     from centernet_amd import native
+
+    def form(occ4):
+        return lambda r: (native.conv_route_name(r.route) == "halo" and r.variant & native.C3_TILE and
+                          r.n_tile == 64 and bool(r.variant & native.C3_OCC4) == occ4)
     for v in (1, 2):
-        with native.tuning({19: v}):
-            _conv_case(dev, (4, 64, 64, 64, 64, 3, 1, 1, False, True, True, True))
-            _conv_case(dev, (3, 96, 19, 27, 40, 3, 1, 1, True, False, True, False))
+        with native.tuning({19: v, 5: 1}):
+            other = ({19: 3 - v}, form(v == 2))
+            _conv_case(dev, (4, 64, 64, 64, 64, 3, 1, 1, False, True, True, True), says=form(v == 1), unforced=other)
+            _conv_case(dev, (3, 96, 19, 27, 40, 3, 1, 1, True, False, True, False), says=form(v == 1),
+                       unforced=other)
 
 
 def test_conv_8_wave_tiles(dev):
-    """Both workgroup shapes of the 128-wide LDS-halo tiles (key 15: 8 waves default, 4 waves)."""
+    """Both workgroup shapes of the 128-wide LDS-halo tiles (key 15: 8 waves default, 4 waves).  cn_conv2d_route
+    showed that the first two layers never reached them: with the plan's workspace they split K (implicit GEMM in
+    both arms), and unsplit (key 5 = 1) the kernel gives them 64-wide tiles (fewer than 512 workgroups and Cout %
+    64 == 0; 130 channels: a 128-wide tile would waste a 64-wide one).  They stay, on the halo kernel; the two
+    layers of 200 channels are the ones on 128-wide tiles."""
     from centernet_amd import native
+
+    def form(n_tile, waves8):
+        return lambda r: (native.conv_route_name(r.route) == "halo" and r.variant & native.C3_TILE and
+                          r.n_tile == n_tile and bool(r.variant & native.C3_WAVES8) == waves8)
     for v in (1, 0):
-        with native.tuning({15: v}):
-            _conv_case(dev, (2, 256, 32, 32, 256, 3, 1, 1, False, True, True, True))
-            _conv_case(dev, (3, 160, 19, 27, 130, 3, 1, 1, True, False, True, False))
+        with native.tuning({15: v, 5: 1}):
+            _conv_case(dev, (2, 256, 32, 32, 256, 3, 1, 1, False, True, True, True), says=form(64, False))
+            _conv_case(dev, (3, 160, 19, 27, 130, 3, 1, 1, True, False, True, False), says=form(64, False))
+            other = ({15: 1 - v}, form(128, v == 0))
+            _conv_case(dev, (4, 64, 19, 27, 200, 3, 1, 1, True, False, True, False), says=form(128, v == 1),
+                       unforced=other)
+            _conv_case(dev, (2, 96, 12, 36, 200, 3, 1, 1, False, True, True, True), says=form(128, v == 1),
+                       unforced=other)
 
 
-def _conv_case(dev, cfg, split=False):
+def _conv_case(dev, cfg, split=False, says=None, unforced=None):
     """``split``: f32s (three fp16 MFMAs per product) or the plain fp32 matrix instruction;
-    the knob tests below exercise the fp32-MFMA tile variants."""
+    the knob tests below exercise the fp32-MFMA tile variants.  ``says``: what cn_conv2d_route must say of the
+    layer under the keys set now (a predicate on the route info); ``unforced`` = (keys, predicate): ... and
+    under these other keys"""
+    from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
+
+    def which_kernel(pb):
+        r = _route(pb)
+        if says is not None:
+            assert says(r), (native.conv_route_name(r.route), hex(r.variant), r.n_tile, r.m_tile, r.ksplit)
+        if unforced is not None:
+            with native.tuning(unforced[0]):
+                r = _route(pb)
+                assert unforced[1](r), (unforced[0], native.conv_route_name(r.route), hex(r.variant), r.n_tile,
+                                        r.m_tile, r.ksplit)
     B, Cin, H, W, Cout, k, s, p, use_bias, use_bn, relu, use_res = cfg
     x = torch.from_numpy(synth.normal((B, Cin, H, W), 1.0, 1))
     w = torch.from_numpy(synth.normal((Cout, Cin, k, k), (2.0 / (Cin * k * k)) ** 0.5, 2))
@@ -127,6 +183,7 @@ def _conv_case(dev, cfg, split=False):
         not PlanBuilder._narrow_form(k, k, p, 1, False, Cin, Cout)
     assert y.fmt == ("f32s" if want_s else "f32")
     y = pb.plain(y)
+    which_kernel(pb)
     _run(pb)
     _check(y.t[..., :Cout].permute(0, 3, 1, 2).cpu(), ref.detach())
     if split:
@@ -137,6 +194,7 @@ def _conv_case(dev, cfg, split=False):
         y = pb.conv(xs, w, bias=bias, bn=bn, relu=relu, residual=rs, stride=s, padding=p,
                     out_plain=True)
         assert y.fmt == "f32"
+        which_kernel(pb)
         _run(pb)
         _check(y.t[..., :Cout].permute(0, 3, 1, 2).cpu(), ref.detach())
 
@@ -224,7 +282,7 @@ def test_stem_kernels_vs_torch(dev, cfg):
     (cn_set_tuning key 12) against torch CPU conv + BN + ReLU."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
-    B, H, W, Cout, stride, _ = cfg
+    B, H, W, Cout, stride, eligible = cfg
     x = synth.images(B, H, W, 7)
     w = torch.from_numpy(synth.normal((Cout, 3, 7, 7), (2.0 / 147) ** 0.5, 2))
     bn = _bn(Cout, 4)
@@ -235,6 +293,12 @@ def test_stem_kernels_vs_torch(dev, cfg):
             xin = pb.set_input(3)
             y = pb.conv(xin, w, bn=bn, relu=True, stride=stride, padding=3)
             pb.input.t = x.to(dev)
+            # key 12 = 1 and whole 128-pixel rows: a persistent form; else the one-tile-per-workgroup kernel
+            r = _route(pb)
+            assert native.conv_route_name(r.route) == "stem"
+            persistent = (native.STEM_PERSIST, native.STEM_PERSIST_F32S, native.STEM_16S)
+            assert (r.variant in persistent) if (variant == 1 and eligible) else (r.variant == native.STEM_WINDOW), \
+                (variant, r.variant)
             _run(pb)
             _check(y.t.permute(0, 3, 1, 2).cpu(), ref)
 
@@ -356,6 +420,7 @@ def test_conv3x3_stride2_on_the_persistent_kernel(dev, cfg):
                     y = pb.conv(pb.packed(_nhwc_act(x, dev)), w, bn=bn, relu=True, stride=2, padding=1,
                                 out_plain=out_plain)
                     assert y.fmt == ("f32" if out_plain else "f32s") and (y.H, y.W) == tuple(ref.shape[2:])
+                    assert _route_name(pb) == ("s2p" if key33 else "igemm")
                     _run(pb)
                     got[key33] = y.to_float().clone()
                     if key33 == 1:
@@ -719,11 +784,23 @@ def test_f32s_halo_weight_forms(dev, lds_weights):
     (default) and the per-tap LDS weight tile (cn_set_tuning key 20) -- odd channel counts,
     several chunks, narrow and wide maps, residual."""
     from centernet_amd import native
-    with native.tuning({20: lds_weights}):
-        _conv_case(dev, (2, 256, 32, 32, 256, 3, 1, 1, False, True, True, True), split=True)
-        _conv_case(dev, (3, 160, 19, 27, 130, 3, 1, 1, True, False, True, False), split=True)
-        _conv_case(dev, (20, 96, 12, 20, 200, 3, 1, 1, True, True, False, False), split=True)
-        _conv_case(dev, (16, 64, 64, 64, 192, 3, 1, 1, True, False, True, False), split=True)
+
+    def form(n_tile, wreg):
+        return lambda r: (native.conv_route_name(r.route) == "halo" and r.variant & native.C3_TILE and
+                          r.n_tile == n_tile and bool(r.variant & native.C3_WREG) == wreg)
+    # cn_conv2d_route showed that under key 20 alone no layer below reached either form: three split K with the
+    # plan's workspace (implicit GEMM) and the fourth has enough tiles for the persistent kernel.  Keys 5 = 1 and
+    # 28 = 0 keep them on the tile kernel, where three of the four get 64-wide tiles (see test_conv_8_wave_tiles);
+    # the 200-channel layers are the ones on 128-wide tiles, the second on a wide map with a residual
+    with native.tuning({20: lds_weights, 5: 1, 28: 0}):
+        _conv_case(dev, (2, 256, 32, 32, 256, 3, 1, 1, False, True, True, True), split=True, says=form(64, False))
+        _conv_case(dev, (3, 160, 19, 27, 130, 3, 1, 1, True, False, True, False), split=True, says=form(64, False))
+        other = ({20: 1 - lds_weights}, form(128, lds_weights == 1))
+        _conv_case(dev, (20, 96, 12, 20, 200, 3, 1, 1, True, True, False, False), split=True,
+                   says=form(128, lds_weights == 0), unforced=other)
+        _conv_case(dev, (16, 64, 64, 64, 192, 3, 1, 1, True, False, True, False), split=True, says=form(64, False))
+        _conv_case(dev, (2, 64, 12, 36, 200, 3, 1, 1, False, True, True, True), split=True,
+                   says=form(128, lds_weights == 0), unforced=other)
 
 
 @pytest.mark.parametrize("scale", [1.0, 1e-4, 3e3])
@@ -752,6 +829,7 @@ def test_offset_conv_kernel(dev, cfg, scale):
             om = pb._new(B, H, W, Cout, pitch=32, lid="om")
             y = pb.conv(xa, w, bias=bias, relu=relu, stride=1, padding=1, out=om, lid="om")
             assert y.fmt == "f32"
+            assert (_route_name(pb) == "offconv") == bool(key39), (key39, _route_name(pb))
             _run(pb)
         got = y.t[..., :Cout].permute(0, 3, 1, 2).double().cpu()
         err = ((got - ref).abs() / (scale + ref.abs())).max()
@@ -796,6 +874,7 @@ def test_projection_1x1_kernel(dev, cfg):
                 xs = pb.packed(_nhwc_act(x, dev))
                 y = pb.conv(xs, w, bias=bias, bn=bn, relu=relu, stride=s, padding=0, out_plain=out_plain)
                 assert y.fmt == ("f32" if out_plain else "f32s")
+                assert _route_name(pb) == ("proj" if key46 else "igemm")
                 yp = pb.plain(y)
                 _run(pb)
                 got[key46, out_plain] = yp.t[..., :Cout].permute(0, 3, 1, 2).cpu().double()
@@ -860,9 +939,17 @@ def test_residual_slice_pitch_contract(dev, Cin, W, mode):
         supported = lib.cn_conv2d_res_pitch_supported(ctypes.byref(d))
         need = lib.cn_conv2d_workspace_bytes(ctypes.byref(d))
         ws = torch.empty(max(need, 16) // 4, device=dev, dtype=torch.float32)
-        rc = lib.cn_conv2d(ctypes.byref(d), native.ptr(xd), native.ptr(wp), native.ptr(k), native.ptr(sh),
-                           ctypes.c_void_p(rd.data_ptr() + 4 * R0), native.ptr(y),
-                           native.ptr(ws) if need else None, need, native.stream_ptr())
+        args = (ctypes.byref(d), native.ptr(xd), native.ptr(wp), native.ptr(k), native.ptr(sh),
+                ctypes.c_void_p(rd.data_ptr() + 4 * R0), native.ptr(y), native.ptr(ws) if need else None, need,
+                native.stream_ptr())
+        info = native.ConvRouteInfo()
+        assert lib.cn_conv2d_route(*args, ctypes.byref(info)) == (native.CN_OK if Cin == 32 else -2)
+        if Cin == 32:     # the kernel the mode names, and it alone takes the residual's pitch
+            assert native.conv_route_name(info.route) == "halo"
+            assert info.variant == native.C3_PERSIST if mode == "f32s_c3p" else info.variant & native.C3_TILE
+        else:
+            assert native.conv_route_name(info.route) == "none"
+        rc = lib.cn_conv2d(*args)
         torch.cuda.synchronize()
     print("Cin %d W %d %s: supported %d, workspace %d bytes, rc %d" % (Cin, W, mode, supported, need, rc))
     if Cin == 32:
