@@ -1612,10 +1612,10 @@ extern "C" int cn_conv_transpose4x4s2_f32(const float *x_nhwc, const float *w_pa
                                   in_pitch, out_pitch, relu, CN_DTYPE_F32, 0, nullptr, stream);
 }
 
-extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, const float *scale,
-                                      const float *shift, void *y_nhwc, int B, int H, int W,
-                                      int Cin, int Cout, int in_pitch, int out_pitch, int relu,
-                                      int dtype, int flags, const cn_f32s_ctl *ctl, void *stream)
+// The checks of cn_conv_transpose4x4s2 and its call description: what the call and cn_conv_transpose4x4s2_route share
+static int deconv_prepare(const void *x_nhwc, const void *w_packed, const float *scale, const float *shift,
+                          void *y_nhwc, int B, int H, int W, int Cin, int Cout, int in_pitch, int out_pitch,
+                          int relu, int dtype, int flags, const cn_f32s_ctl *ctl, ConvCall &c)
 {
     if (!x_nhwc || !w_packed || !y_nhwc) return CN_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return CN_ERR_SHAPE;
@@ -1633,7 +1633,7 @@ extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, 
     if ((long)B * H * W * 4 * (long)out_pitch >= (1L << 31) || (long)B * H * W * (long)in_pitch >= (1L << 31))
         return CN_ERR_UNSUPPORTED;
     // the four parity classes as 2x2 convolutions over the input map (Ho x Wo = H x W)
-    ConvCall c = {};
+    c = {};
     c.x = x_nhwc; c.w = w_packed; c.scale = scale; c.shift = shift; c.y = y_nhwc;
     c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Ho = H; c.Wo = W; c.Cout = Cout;
     c.KH = 2; c.KW = 2; c.stride = 1; c.pad_h = 1; c.pad_w = 1; c.dil = 1;
@@ -1646,15 +1646,71 @@ extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, 
     c.ksplit = 1;
     const int bke = f16 ? 64 : 32;
     c.cin_pad = round_up(Cin, bke); c.cout_pad = round_up(Cout, 32); c.nchunk = c.cin_pad / bke;
-    hipStream_t st = (hipStream_t)stream;
+    return CN_OK;
+}
+
+// Run the described call -- or, for cn_conv_transpose4x4s2_route (c.describe set), walk the same ladder and let the
+// launcher say what it would launch.  *route: the CN_ROUTE_* taken
+static int deconv_run(const ConvCall &c, hipStream_t st, int *route)
+{
     // LDS-halo form (cn_conv3x3.hip) unless disabled (cn_set_tuning key 10) or the tile would be
     // mostly padding (Cout <= 32)
-    if (!cn_knobs.nohalo && Cout > 32 && c.vec_out) return cn_deconv4x4s2_halo(c, st);
+    if (!cn_knobs.nohalo && c.Cout > 32 && c.vec_out) {
+        *route = R_HALO;
+        return cn_deconv4x4s2_halo(c, st);
+    }
+    *route = R_IGEMM;
+    const int cls = cout_class(c.Cout);
+    if (c.describe) {   // the implicit GEMM in parity form: the dense NHWC tiles of the class, one grid layer per parity
+        c.describe->m_tile = igemm_bm(cls, false);
+        c.describe->n_tile = igemm_bn(cls);
+        return CN_OK;
+    }
     IgemmArgs a = igemm_args(c, nullptr);
-    a.OH = 2 * H; a.OW = 2 * W; a.oy_mul = 2; a.ox_mul = 2;
+    a.OH = 2 * c.H; a.OW = 2 * c.W; a.oy_mul = 2; a.ox_mul = 2;
     a.zparity = 1;   // blockIdx.z = parity class
     a.w_zstride = 4 * a.cout_pad * a.cin_pad;
-    return igemm_dispatch<A_DENSE, false>(dtype, cout_class(Cout), false, a, st);
+    return igemm_dispatch<A_DENSE, false>(c.dtype, cls, false, a, st);
+}
+
+extern "C" int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, const float *scale,
+                                      const float *shift, void *y_nhwc, int B, int H, int W,
+                                      int Cin, int Cout, int in_pitch, int out_pitch, int relu,
+                                      int dtype, int flags, const cn_f32s_ctl *ctl, void *stream)
+{
+    ConvCall c;
+    int route;
+    const int rc = deconv_prepare(x_nhwc, w_packed, scale, shift, y_nhwc, B, H, W, Cin, Cout, in_pitch, out_pitch,
+                                  relu, dtype, flags, ctl, c);
+    if (rc != CN_OK) return rc;
+    return deconv_run(c, (hipStream_t)stream, &route);
+}
+
+// Host-only: the checks, the ladder and the launcher's own word on its form; no pointer is read, nothing launched
+extern "C" int cn_conv_transpose4x4s2_route(const void *x_nhwc, const void *w_packed, const float *scale,
+                                            const float *shift, void *y_nhwc, int B, int H, int W,
+                                            int Cin, int Cout, int in_pitch, int out_pitch, int relu,
+                                            int dtype, int flags, const cn_f32s_ctl *ctl, void *stream,
+                                            cn_conv_route_info *info)
+{
+    (void)stream;
+    if (!info) return CN_ERR_NULL;
+    *info = {};
+    ConvCall c;
+    int rc = deconv_prepare(x_nhwc, w_packed, scale, shift, y_nhwc, B, H, W, Cin, Cout, in_pitch, out_pitch,
+                            relu, dtype, flags, ctl, c);
+    if (rc != CN_OK) return rc;
+    ConvForm f = {};
+    c.describe = &f;
+    int route = R_NONE;
+    rc = deconv_run(c, nullptr, &route);
+    info->route = route;
+    if (rc != CN_OK) return rc;
+    info->n_tile = f.n_tile; info->m_tile = f.m_tile;
+    info->ksplit = 1; info->want = 1;
+    info->variant = f.variant;
+    info->grid_x = f.grid_x; info->grid_y = f.grid_y;
+    return CN_OK;
 }
 
 // ---- cn_set_tuning / cn_get_tuning / cn_reset_tuning: lookups in CN_TUNING_KEYS (cn_tuning.h)

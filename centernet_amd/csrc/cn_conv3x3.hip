@@ -1170,7 +1170,7 @@ int launch_c3(const C3Launch &a, hipStream_t st, const C3Heads *hd = nullptr)
         constexpr bool f32s = std::is_same<T, cn_f32s>::value;
         *a.describe = {CN_C3_TILE | (TW == 32 ? CN_C3_TW32 : 0) | (WM * WN == 8 ? CN_C3_WAVES8 : 0) |
                            (KSKIP ? CN_C3_KSKIP : 0) | ((f32s && NBUFB == 0) ? CN_C3_WREG : 0) |
-                           ((f32s && NBUFB != 0) ? (PDQ << 12) : 0),
+                           ((f32s && NBUFB != 0) ? (PDQ << 12) : 0) | ((HEADS && WN == 1) ? CN_C3_HREG : 0),
                        BN, BM, (int)grid.x, (int)grid.y};
         return CN_OK;
     }
@@ -1344,15 +1344,10 @@ extern "C" int cn_heads3x3_1x1_f32(const float *x, int B, int H, int W, int Cin,
                            heads, CN_DTYPE_F32, 0, nullptr, stream);
 }
 
-// dtype-generic form: CN_DTYPE_F32S takes f32s activations (or plain ones with CN_CONV_X_PLAIN)
-// and an f32s-packed 3x3 weight with its per-row prescale factors in `scale1`; the hidden tile
-// and the 1x1 weights are split inside the kernel, outputs stay fp32 NCHW.
-extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int in_pitch,
-                               const void *w1_packed, const float *scale1, const float *bias1,
-                               int head_conv, int n_heads, const cn_head_out *heads, int dtype,
-                               int flags, const cn_f32s_ctl *ctl, void *stream)
+// The checks of cn_heads3x3_1x1 and the heads' table: what the call and cn_heads3x3_1x1_route share
+static int heads_prepare(const void *x, int B, int H, int W, int Cin, int in_pitch, const void *w1_packed,
+                         int head_conv, int n_heads, const cn_head_out *heads, int dtype, int flags, C3Heads &hd)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (!x || !w1_packed || !heads) return CN_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || n_heads <= 0) return CN_ERR_SHAPE;
     // hidden width: 64-channel slices handled one after the other inside the workgroup
@@ -1363,7 +1358,7 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
     if ((in_pitch & 3) || !cn_aligned16(x) || !cn_aligned16(w1_packed)) return CN_ERR_ALIGN;
     if (f32s && !(flags & CN_CONV_X_PLAIN) && (in_pitch & 31)) return CN_ERR_UNSUPPORTED;
     if (f32s && !(flags & CN_CONV_X_PLAIN) && (((uintptr_t)x) & 127u)) return CN_ERR_ALIGN;  // 128-byte groups
-    C3Heads hd = {};
+    hd = {};
     for (int h = 0; h < n_heads; ++h) {
         if (!heads[h].w || !heads[h].y) return CN_ERR_NULL;
         if (heads[h].cout <= 0) return CN_ERR_SHAPE;
@@ -1375,11 +1370,27 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
         if (head_conv > HEAD_CONV && heads[h].cout > W2_ROWS) return CN_ERR_UNSUPPORTED;
     }
     hd.slices = head_conv / HEAD_CONV;
+    return CN_OK;
+}
+
+// Run the checked call -- or, for cn_heads3x3_1x1_route (describe set), walk the same ladder and let the launcher say
+// what it would launch
+static int heads_run(const void *x, int B, int H, int W, int Cin, int in_pitch, const void *w1_packed,
+                     const float *scale1, const float *bias1, int head_conv, int n_heads, const cn_head_out *heads,
+                     int dtype, int flags, const cn_f32s_ctl *ctl, C3Heads &hd, ConvForm *describe, hipStream_t st)
+{
+    const bool f32s = (dtype == CN_DTYPE_F32S);
     // f32s feature map, one 64-wide hidden layer per head: the persistent loader / consumer kernel
     // (cn_conv3x3p.hip, hidden layer in registers)
-    if (f32s && cn_heads3x3p_takes(B, H, W, in_pitch, head_conv, n_heads, heads, (flags & CN_CONV_X_PLAIN) != 0))
+    if (f32s && cn_heads3x3p_takes(B, H, W, in_pitch, head_conv, n_heads, heads, (flags & CN_CONV_X_PLAIN) != 0)) {
+        if (describe) {
+            describe->variant = CN_C3_PERSIST;
+            return CN_OK;
+        }
         return cn_heads3x3p(x, B, H, W, Cin, in_pitch, w1_packed, scale1, bias1, n_heads, heads, ctl, st);
+    }
     C3Launch a = {};
+    a.describe = describe;
     c3_set_ctl(a, ctl);
     a.x = x; a.w = w1_packed; a.scale = scale1; a.shift = bias1; a.residual = nullptr; a.y = nullptr;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = n_heads * head_conv; a.in_pitch = in_pitch;
@@ -1417,6 +1428,46 @@ extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int 
                      : launch_c3<float, 16, 64, 2, 2, true>(a, st, &hd);
 }
 
+// dtype-generic form: CN_DTYPE_F32S takes f32s activations (or plain ones with CN_CONV_X_PLAIN)
+// and an f32s-packed 3x3 weight with its per-row prescale factors in `scale1`; the hidden tile
+// and the 1x1 weights are split inside the kernel, outputs stay fp32 NCHW.
+extern "C" int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int in_pitch,
+                               const void *w1_packed, const float *scale1, const float *bias1,
+                               int head_conv, int n_heads, const cn_head_out *heads, int dtype,
+                               int flags, const cn_f32s_ctl *ctl, void *stream)
+{
+    C3Heads hd;
+    const int rc = heads_prepare(x, B, H, W, Cin, in_pitch, w1_packed, head_conv, n_heads, heads, dtype, flags, hd);
+    if (rc != CN_OK) return rc;
+    return heads_run(x, B, H, W, Cin, in_pitch, w1_packed, scale1, bias1, head_conv, n_heads, heads, dtype, flags,
+                     ctl, hd, nullptr, (hipStream_t)stream);
+}
+
+// Host-only: the checks, the ladder and the launcher's own word on its form.  Of the pointers (those of heads[]
+// included) only null-ness and alignment count; heads[] itself is read, as the call's checks read it
+extern "C" int cn_heads3x3_1x1_route(const void *x, int B, int H, int W, int Cin, int in_pitch,
+                                     const void *w1_packed, const float *scale1, const float *bias1,
+                                     int head_conv, int n_heads, const cn_head_out *heads, int dtype,
+                                     int flags, const cn_f32s_ctl *ctl, void *stream, cn_conv_route_info *info)
+{
+    (void)stream;
+    if (!info) return CN_ERR_NULL;
+    *info = {};
+    C3Heads hd;
+    int rc = heads_prepare(x, B, H, W, Cin, in_pitch, w1_packed, head_conv, n_heads, heads, dtype, flags, hd);
+    if (rc != CN_OK) return rc;
+    ConvForm f = {};
+    rc = heads_run(x, B, H, W, Cin, in_pitch, w1_packed, scale1, bias1, head_conv, n_heads, heads, dtype, flags,
+                   ctl, hd, &f, nullptr);
+    if (rc != CN_OK) return rc;
+    info->route = CN_ROUTE_HALO;
+    info->n_tile = f.n_tile; info->m_tile = f.m_tile;
+    info->ksplit = 1; info->want = 1;
+    info->variant = f.variant;
+    info->grid_x = f.grid_x; info->grid_y = f.grid_y;
+    return CN_OK;
+}
+
 // ConvTranspose2d(kernel 4, stride 2, padding 1) through the LDS-halo kernel: the four output
 // parities are 2x2 convolutions over the 3x3 neighbourhood the halo already holds.
 // w_packed: cn_pack_deconv4x4s2_weight_f32 layout [parity 4][tap 4][cout_pad][cin_pad].
@@ -1426,8 +1477,14 @@ int cn_deconv4x4s2_halo(const ConvCall &c, hipStream_t st)
     c3_fill(a, c);
     const int B = c.B, H = c.H, W = c.W, Cout = c.Cout, dtype = c.dtype;
     const bool wide = W >= 32;
-    if (dtype == CN_DTYPE_F32S && c.vec_out && c.scale && cn_deconv4x4s2p_takes(c))
+    if (dtype == CN_DTYPE_F32S && c.vec_out && c.scale && cn_deconv4x4s2p_takes(c)) {
+        if (c.describe) {
+            c.describe->variant = CN_C3_PERSIST;
+            return CN_OK;
+        }
         return cn_deconv4x4s2_persist(c, st);
+    }
+    a.describe = c.describe;
     if (dtype == CN_DTYPE_F32S) {
         if (Cout > 64)
             return wide ? launch_c3<cn_f32s, 32, 128, 4, 2, false, 128, false, true>(a, st)

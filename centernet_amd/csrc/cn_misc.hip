@@ -337,7 +337,7 @@ inline int blocks_for(size_t total, int per_block, int cap)
 
 }  // namespace
 
-extern "C" int cn_version(void) { return 312; }  // 0.3.12: cn_conv2d_route; cn_conv2d checks the output scatter
+extern "C" int cn_version(void) { return 313; }  // 0.3.13: cn_conv_transpose4x4s2_route, cn_heads3x3_1x1_route
 
 extern "C" const char *cn_arch(void) { return "gfx950"; }
 

@@ -709,10 +709,19 @@ class PlanBuilder:
                                             native.stream_ptr())
             if rc:
                 native.check(rc, "cn_conv_transpose4x4s2")
+
+        def route():
+            """the kernel and its form the launch gets (cn_conv_transpose4x4s2_route: host only)"""
+            info = native.ConvRouteInfo()
+            native.check(lib.cn_conv_transpose4x4s2_route(x.ptr(), wpp, sp, hp, out.ptr(), x.B, x.H, x.W, ci, co,
+                                                          x.pitch, out.pitch, int(relu), cd, flags, cref,
+                                                          native.stream_ptr(), ctypes.byref(info)),
+                         "cn_conv_transpose4x4s2_route")
+            return info
         self.ops.append(run)
         fl = 2 * x.B * (2 * x.H) * (2 * x.W) * co * ci * 4
         by = (2 if half else 4) * (x.B * x.H * x.W * (ci + 4 * co) + co * ci * 16)
-        self.meta.append(dict(kind="conv", flops=fl, bytes=by))
+        self.meta.append(dict(kind="conv", flops=fl, bytes=by, route=route))
         self.trace.append(("deconv", out))
         self.flops += fl
         return out
@@ -1223,8 +1232,16 @@ class PlanBuilder:
                                      arr, cd, flags, cref, native.stream_ptr())
             if rc:
                 native.check(rc, "cn_heads3x3_1x1")
+
+        def route():
+            """the kernel and its form the launch gets (cn_heads3x3_1x1_route: host only)"""
+            info = native.ConvRouteInfo()
+            native.check(lib.cn_heads3x3_1x1_route(x.ptr(), x.B, x.H, x.W, ci, x.pitch, wpp, s1p, b1p, hc, nh,
+                                                   arr, cd, flags, cref, native.stream_ptr(), ctypes.byref(info)),
+                         "cn_heads3x3_1x1_route")
+            return info
         self.ops.append(run)
-        self.meta.append(dict(kind="conv", flops=fl, bytes=by))
+        self.meta.append(dict(kind="conv", flops=fl, bytes=by, route=route))
         self.trace.append(("heads", outs[names[0]]))
         self.flops += fl
         return outs

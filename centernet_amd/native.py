@@ -53,7 +53,7 @@ CONV_ROUTE_NAMES = ("none", "stem_pool", "stem", "conv16", "conv16s", "conv16h",
                     "igemm")
 STEM_NONE, STEM_WINDOW, STEM_PERSIST, STEM_PERSIST_F32S, STEM_16S = range(5)
 C3_PERSIST, C3_TILE = 1, 2
-C3_TW32, C3_WAVES8, C3_OCC4, C3_KSKIP, C3_WREG = 0x10, 0x20, 0x40, 0x80, 0x100
+C3_TW32, C3_WAVES8, C3_OCC4, C3_KSKIP, C3_WREG, C3_HREG = 0x10, 0x20, 0x40, 0x80, 0x100, 0x200
 
 
 def c3_prefetch(variant):
@@ -217,6 +217,10 @@ def _declare(lib):
     lib.cn_conv_transpose4x4s2.argtypes = [vp, vp, vp, vp, vp] + [i] * 10 + [ctl, vp]
     lib.cn_heads3x3_1x1.restype = i
     lib.cn_heads3x3_1x1.argtypes = [vp, i, i, i, i, i, vp, vp, vp, i, i, vp, i, i, ctl, vp]
+    lib.cn_conv_transpose4x4s2_route.restype = i
+    lib.cn_conv_transpose4x4s2_route.argtypes = lib.cn_conv_transpose4x4s2.argtypes + [ctypes.POINTER(ConvRouteInfo)]
+    lib.cn_heads3x3_1x1_route.restype = i
+    lib.cn_heads3x3_1x1_route.argtypes = lib.cn_heads3x3_1x1.argtypes + [ctypes.POINTER(ConvRouteInfo)]
     lib.cn_packed_conv_weight_floats.restype = sz
     lib.cn_packed_conv_weight_floats.argtypes = [i] * 4
     lib.cn_pack_conv_weight_f32.restype = i

@@ -530,6 +530,7 @@ int cn_conv2d(const cn_conv_desc *desc, const void *x, const void *w_packed, con
 #define CN_C3_KSKIP 0x80      /* fp32: the empty K groups of the last chunk are skipped */
 #define CN_C3_WREG 0x100      /* f32s: weights streamed into registers, no LDS weight tile */
 #define CN_C3_PREFETCH(v) (((v) >> 12) & 3)   /* f32s, LDS weight tile: taps of weight prefetch (1..3) */
+#define CN_C3_HREG 0x200      /* cn_heads3x3_1x1_route, f32s: the hidden layer stays in registers (4 x 1 waves), not in LDS (2 x 2) */
 typedef struct cn_conv_route_info {
     int route;            /* CN_ROUTE_* */
     int n_tile, m_tile;   /* channels / pixels per workgroup tile: CN_ROUTE_HALO tile kernel and CN_ROUTE_IGEMM, else 0 */
@@ -560,6 +561,14 @@ int cn_conv_transpose4x4s2(const void *x_nhwc, const void *w_packed, const float
                            const float *shift, void *y_nhwc, int B, int H, int W, int Cin, int Cout,
                            int in_pitch, int out_pitch, int relu, int dtype, int flags,
                            const cn_f32s_ctl *ctl, void *stream);
+/* Which kernel a cn_conv_transpose4x4s2 call runs: its arguments, its status, and *info as cn_conv2d_route fills it.
+ * CN_ROUTE_HALO with variant CN_C3_PERSIST or CN_C3_TILE | bits (n_tile 64 / 128, grid), or CN_ROUTE_IGEMM (the
+ * implicit GEMM in parity form: Cout <= 32, an out_pitch that is no multiple of 4 or a y off 16 bytes, key 10) with
+ * m_tile and n_tile.  ksplit = want = 1.  Host-only: no pointer is dereferenced, nothing is launched. */
+int cn_conv_transpose4x4s2_route(const void *x_nhwc, const void *w_packed, const float *scale,
+                                 const float *shift, void *y_nhwc, int B, int H, int W, int Cin, int Cout,
+                                 int in_pitch, int out_pitch, int relu, int dtype, int flags,
+                                 const cn_f32s_ctl *ctl, void *stream, cn_conv_route_info *info);
 int cn_pack_deconv4x4s2_weight_f32(const float *w_iohw, float *w_packed, int Cin, int Cout,
                                    void *stream);
 int cn_conv_transpose4x4s2_f32(const float *x_nhwc, const float *w_packed, const float *scale,
@@ -691,6 +700,15 @@ int cn_heads3x3_1x1(const void *x, int B, int H, int W, int Cin, int in_pitch,
                     const void *w1_packed, const float *scale1, const float *bias1, int head_conv,
                     int n_heads, const cn_head_out *heads, int dtype, int flags,
                     const cn_f32s_ctl *ctl, void *stream);
+/* Which kernel a cn_heads3x3_1x1 call runs: its arguments, its status, and *info as cn_conv2d_route fills it.
+ * Always CN_ROUTE_HALO: variant CN_C3_PERSIST, or CN_C3_TILE | bits (CN_C3_HREG: the register form) with n_tile the
+ * width of a hidden slice (64 or 128), m_tile 128 and the grid that is launched -- grid_y == 1 with more than one
+ * head where cn_set_tuning key 24 folded the heads into grid_x.  ksplit = want = 1.  Host-only: heads[] is read as
+ * the call's checks read it, of every pointer only null-ness and alignment count, nothing is launched. */
+int cn_heads3x3_1x1_route(const void *x, int B, int H, int W, int Cin, int in_pitch,
+                          const void *w1_packed, const float *scale1, const float *bias1, int head_conv,
+                          int n_heads, const cn_head_out *heads, int dtype, int flags,
+                          const cn_f32s_ctl *ctl, void *stream, cn_conv_route_info *info);
 
 /* ------------------------------------------------------------------------
  * Pre-process on the device: BaseDetector.pre_process

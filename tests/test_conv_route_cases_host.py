@@ -36,7 +36,7 @@ def test_constants_are_the_headers():
     defs = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define CN_(\w+) (0x[0-9a-fA-F]+|\d+)\b", header)}
     names = [n for n in defs if n.startswith(("ROUTE_", "STEM_", "C3_")) and n not in ("STEM_F32S", "STEM_MAXPOOL",
                                                                                        "STEM_Y_F32S")]
-    assert len(names) == 11 + 5 + 7, sorted(names)
+    assert len(names) == 11 + 5 + 8, sorted(names)      # (8: CN_C3_HREG, the fused heads' register form)
     for n in names:
         assert getattr(native, n) == defs[n], n
     assert [native.conv_route_name(defs["ROUTE_" + n.upper()]) for n in native.CONV_ROUTE_NAMES] == \

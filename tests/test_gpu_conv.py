@@ -47,6 +47,17 @@ def _route_name(pb, i=0):
     return native.conv_route_name(_route(pb, i).route)
 
 
+def _halo_form(pb, i=0):
+    """"persist" / "tile" where the plan's i-th convolution, transposed convolution or fused-heads launch runs on
+    the persistent or the one-tile-per-workgroup form of the LDS-halo kernels, else the route's name"""
+    from centernet_amd import native
+    r = _route(pb, i)
+    if r.route != native.ROUTE_HALO:
+        return native.conv_route_name(r.route)
+    assert r.variant == native.C3_PERSIST or r.variant & native.C3_TILE
+    return "persist" if r.variant == native.C3_PERSIST else "tile"
+
+
 def _bn(C, seed):
     bn = torch.nn.BatchNorm2d(C)
     synth.fill_state_dict_(bn, seed)
@@ -331,13 +342,14 @@ def test_stem16_f32s_and_fp32_forms(dev):
 @pytest.mark.parametrize("cfg", [(2, 64, 16, 16, 64), (1, 256, 16, 16, 256), (1, 128, 9, 7, 64),
                                  (2, 128, 37, 45, 96), (1, 64, 8, 40, 24)])
 def test_conv_transpose_4x4_s2(dev, cfg, halo, split):
-    """Both forms: LDS-halo parity kernel (default) and the generic implicit GEMM (key 10)."""
+    """Both forms: LDS-halo parity kernel (default) and the generic implicit GEMM (key 10).  Cout = 24: the halo
+    kernel is entered for Cout > 32 only, so BOTH arms of that case are the implicit GEMM in parity form."""
     from centernet_amd import native
     with native.tuning({10: 0 if halo else 1}):
-        _deconv_case(dev, cfg, split)
+        _deconv_case(dev, cfg, split, says="tile" if (halo and cfg[4] > 32) else "igemm")
 
 
-def _deconv_case(dev, cfg, split=False):
+def _deconv_case(dev, cfg, split=False, says=None):
     from centernet_amd.engine import PlanBuilder
     B, Cin, H, W, Cout = cfg
     x = torch.from_numpy(synth.normal((B, Cin, H, W), 1.0, 1))
@@ -346,25 +358,29 @@ def _deconv_case(dev, cfg, split=False):
     ref = F.relu(bn(F.conv_transpose2d(x, w, None, 2, 1, 0))).detach()
     pb = PlanBuilder(dev, B, H, W, split=split)
     y = pb.plain(pb.conv_transpose4x4s2(_nhwc_act(x, dev), w, bn=bn, relu=True))
+    assert says is None or _halo_form(pb) == says
     _run(pb)
     _check(y.t[..., :Cout].permute(0, 3, 1, 2).cpu(), ref)
     if split:    # f32s input, plain output (the producer of a deformable layer's input)
         pb = PlanBuilder(dev, B, H, W, split=True)
         y = pb.conv_transpose4x4s2(pb.packed(_nhwc_act(x, dev)), w, bn=bn, relu=True, out_plain=True)
         assert y.fmt == "f32"
+        assert says is None or _halo_form(pb) == says
         _run(pb)
         _check(y.t[..., :Cout].permute(0, 3, 1, 2).cpu(), ref)
 
 
 @pytest.mark.parametrize("cfg", [(2, 64, 16, 16, 64), (1, 256, 16, 16, 256), (1, 128, 9, 7, 64),
-                                 (2, 128, 37, 45, 96), (1, 96, 8, 40, 32), (32, 128, 64, 64, 64)])
+                                 (2, 128, 37, 45, 96), (1, 96, 8, 40, 64), (32, 128, 64, 64, 64)])
 def test_conv_transpose_4x4_s2_on_the_persistent_kernel(dev, cfg):
     """ConvTranspose2d(4, 2, 1) in parity form on the persistent loader / consumer kernel
     (cn_conv3x3p.hip, NTAP = 4: item = (tile, parity, output block), four taps per stage): f32s input,
     f32s and plain output, edge tiles, a half-empty output block (96 channels), Cin = 96 -- against
     torch.conv_transpose2d on the CPU and the one-tile-per-workgroup kernel (key 32 = 0); run-to-run
     bit equality.  key 28 = 2 forces the kernel onto shapes with few items; the last case is
-    resdcn_18's second up-sampling layer at the benchmark batch, on the library's own routing."""
+    resdcn_18's second up-sampling layer at the benchmark batch, on the library's own routing.
+    Every case has Cout > 32 (below that the call never reaches either kernel), and each arm is held to the
+    kernel it is named after by the plan's route()."""
     from centernet_amd import native
     from centernet_amd.engine import PlanBuilder
     B, Cin, H, W, Cout = cfg
@@ -381,6 +397,7 @@ def test_conv_transpose_4x4_s2_on_the_persistent_kernel(dev, cfg):
                     pb = PlanBuilder(dev, B, H, W, split=True)
                     y = pb.conv_transpose4x4s2(pb.packed(_nhwc_act(x, dev)), w, bn=bn, relu=True, out_plain=out_plain)
                     assert y.fmt == ("f32" if out_plain else "f32s")
+                    assert _halo_form(pb) == ("persist" if key32 else "tile")
                     _run(pb)
                     got[key32] = y.to_float().clone()
                     if key32 == 1:
@@ -472,6 +489,8 @@ def test_persistent_kernel_pipelined_schedule_is_bit_identical(dev, form):
                             r = pb.packed(res) if form == "conv_res" else pb.plain(res)
                         ts = [pb.conv(xin, w, bn=_bn(Cout, 3), relu=True, stride=2 if form == "s2" else 1, padding=1,
                                       residual=r, out_plain=(form == "conv_plain_res")).t]
+                    if form in ("deconv", "heads"):     # (heads: built in the pipelined schedule only, key 30 bit 1
+                        assert _halo_form(pb) == "persist"   # does not reach them: both arms run the same kernel)
                     reps = 6 if B == 32 else 2
                     for rep in range(reps):
                         for t in ts:
@@ -686,6 +705,7 @@ def test_fused_heads_on_the_persistent_kernel(dev, forced):
                     pb = PlanBuilder(dev, B, H, W, split=True)
                     outs = pb.heads_from_convs(pb.packed(_nhwc_act(x, dev)), pairs)
                     assert len(pb.ops) == 2, "convert + one fused launch"
+                    assert _halo_form(pb) == ("persist" if key31 else "tile")
                     _run(pb)
                     got[key31] = {n: outs[n].t.clone() for n in heads}
                     if key31 == 1:      # run-to-run bit equality of the persistent kernel
@@ -726,6 +746,11 @@ def test_fused_heads_hidden_layer_forms(dev, form):
                 pairs[name] = (c1, c2)
             pb = PlanBuilder(dev, B, H, W, split=True)
             outs = pb.heads_from_convs(pb.packed(_nhwc_act(x, dev)), pairs)
+            # the form this key runs at this hidden width (every map here has W >= 32, every head <= 96 outputs)
+            r = _route(pb)
+            in_regs = form != 0 and (hidden > 64 or form == 3)
+            assert _halo_form(pb) == "tile" and bool(r.variant & native.C3_HREG) == in_regs
+            assert r.n_tile == (128 if (in_regs and form == 2 and hidden % 128 == 0) else 64)
             _run(pb)
             for name in heads:
                 _check(outs[name].t.cpu(), ref[name])

@@ -30,10 +30,10 @@ from centernet_amd import native, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_route_cases as cc   # noqa: E402
-from dcn_cases import SENT, TOL   # noqa: E402
+from dcn_cases import TOL   # noqa: E402
+from route_buffers import Buf as _Buf, pack_f32s as _pack_f32s, unpack_f32s as _unpack_f32s   # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SENT16 = 0x7E5A            # a half NaN no kernel produces
 POOLED = native.CONV_STEM_MAXPOOL
 
 
@@ -87,45 +87,6 @@ def _reference(c):
     mask = torch.zeros((OH, OW), dtype=torch.bool)
     mask[ys, xs] = True
     return ref, mask, float((out["ref32"].double() - out["ref"]).abs().max())
-
-
-# ---- f32s tensors: 32 channels = 32 fp16 high parts, then 32 fp16 low parts (csrc/cn_common.h) ---------------------
-def _pack_f32s(t):
-    g = t.reshape(-1, t.shape[-1] // 32, 32)
-    hi = g.half()
-    lo = (g - hi.float()).half()
-    return torch.cat([hi, lo], -1).contiguous().view(torch.float32).reshape(t.shape)
-
-
-def _unpack_f32s(t):
-    g = t.reshape(-1, t.shape[-1] // 32, 32).contiguous().view(torch.float16)
-    return (g[..., :32].float() + g[..., 32:].float()).reshape(t.shape)
-
-
-class _Buf:
-    """`n` elements of 2 or 4 bytes between two guards, all sentinel; the body 256-byte aligned"""
-
-    def __init__(self, dev, n, esize, guard):
-        self.esize, self.n = esize, n
-        self.g = (guard + 127) // 128 * 128
-        self.sent = SENT16 if esize == 2 else SENT
-        self.t = torch.empty(self.g + n + self.g, device=dev, dtype=torch.int16 if esize == 2 else torch.int32)
-        self.t.fill_(self.sent)
-        self.body = self.t[self.g:self.g + n]
-        assert self.body.data_ptr() % 256 == 0
-
-    def ptr(self, off=0):
-        return self.body.data_ptr() + off * self.esize
-
-    def is_sentinel(self, t):
-        return t == self.sent
-
-    def guards_untouched(self):
-        return bool(self.is_sentinel(self.t[:self.g]).all()) and bool(self.is_sentinel(self.t[self.g + self.n:]).all())
-
-    def values(self, fmt):
-        """the body as floats: "f16" halves, "f32" floats (f32s tensors: still packed)"""
-        return self.body.view(torch.float16 if fmt == "f16" else torch.float32)
 
 
 class _Call:

@@ -130,7 +130,7 @@ def test_symbols_are_exported_declared_and_bound():
         assert re.search(r"\bint\s+%s\s*\(" % name, header), name
         fn = getattr(lib, name)
         assert fn.restype is ctypes.c_int and len(fn.argtypes) == nargs, name
-    assert lib.cn_version() == 312
+    assert lib.cn_version() == 313
 
 
 def test_argument_checks_run_without_a_device():

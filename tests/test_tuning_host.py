@@ -53,7 +53,7 @@ def _get(lib, key):
 
 def test_version():
     from centernet_amd import native
-    assert native.lib().cn_version() == 312
+    assert native.lib().cn_version() == 313
 
 
 def test_accepted_pairs_are_exactly_the_recorded_ones(lib):
