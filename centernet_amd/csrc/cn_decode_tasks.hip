@@ -260,6 +260,7 @@ extern "C" int cn_ddd_decode_f32(const float *heat, const float *rot, const floa
 //   stage B  exct_score_kernel: the K^4 candidate scores (decode.py:316-366), written once
 //   stage C  exct_select_kernel: exact top-num_dets (radix select + 1024-key bitonic sort in
 //            LDS) and the box / extreme-point assembly (decode.py:372-420)
+//   cn_exct_decode_stream_f32: stages B and C without the K^4 array (the exct_stream_* kernels below), K <= 128
 // Candidate index = ((t*K + l)*K + b)*K + r, as the reference's view(batch, -1).
 // Tie order (unspecified by torch.topk): score desc, candidate index asc.
 // ---------------------------------------------------------------------------
@@ -330,9 +331,52 @@ struct ExctRegr {
     const float *r[4];  // t, l, b, r regression maps (B,2,H,W) or all null
 };
 
-// one 1024-thread workgroup per image
-// ``cls_map`` (B, H, W) or null: the class-agnostic form (agnex_ct_decode, decode.py:171-187,262-263) takes a
+// Row `row` of image b from its 64-bit key (decode.py:372-420): the box, the score, the four extreme points and the
+// class.  ``cls_map`` (B, H, W) or null: the class-agnostic form (agnex_ct_decode, decode.py:171-187,262-263) takes a
 // detection's class from the centre map's arg-max at the box centre instead of from the top point's list
+__device__ __forceinline__ void exct_write_row(u64 key, const ExctLists &L, const ExctRegr &R, float *__restrict__ dets,
+                                               int b, int row, int K, int H, int W, int num_dets,
+                                               const int32_t *__restrict__ cls_map)
+{
+    const float score = key2f((uint32_t)(key >> 32));
+    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)key;
+    const int ir = (int)(idx % K), ib = (int)((idx / K) % K), il = (int)((idx / (K * K)) % K),
+              it = (int)(idx / (K * K * K));
+    const int o = b * K;
+    const int HW = H * W;
+    const int sel[4] = {it, il, ib, ir};
+    float xs[4], ys[4], gx[4], gy[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int ind = L.ind[e][o + sel[e]];
+        float x = (float)(ind % W), y = (float)(ind / W);
+        gx[e] = x;
+        gy[e] = y;
+        if (R.r[0]) {  // decode.py:372-390 (all four regression maps given)
+            x = x + R.r[e][((size_t)b * 2 + 0) * HW + ind];
+            y = y + R.r[e][((size_t)b * 2 + 1) * HW + ind];
+        } else {      // decode.py:391-399
+            x = x + 0.5f;
+            y = y + 0.5f;
+        }
+        xs[e] = x;
+        ys[e] = y;
+    }
+    float *d = dets + ((size_t)b * num_dets + row) * 14;
+    d[0] = xs[1]; d[1] = ys[0]; d[2] = xs[3]; d[3] = ys[2];  // bboxes = (l_x, t_y, r_x, b_y)
+    d[4] = score;
+    d[5] = xs[0]; d[6] = ys[0]; d[7] = xs[1]; d[8] = ys[1];
+    d[9] = xs[2]; d[10] = ys[2]; d[11] = xs[3]; d[12] = ys[3];
+    if (cls_map) {   // decode.py:171-172: the box centre on the grid, from the points BEFORE their offsets
+        const int cx = (int)((gx[1] + gx[3] + 0.5f) / 2.0f);
+        const int cy = (int)((gy[0] + gy[2] + 0.5f) / 2.0f);
+        d[13] = (float)cls_map[(size_t)b * HW + (size_t)cy * W + cx];
+    } else {
+        d[13] = (float)L.cls[0][o + it];                      // clses = t_clses
+    }
+}
+
+// one 1024-thread workgroup per image; ``cls_map`` as in exct_write_row
 __global__ __launch_bounds__(NTM) void exct_select_kernel(
     const float *__restrict__ cand, const ExctLists L, const ExctRegr R, float *__restrict__ dets,
     int K, int H, int W, int num_dets, const int32_t *__restrict__ cls_map)
@@ -379,43 +423,144 @@ __global__ __launch_bounds__(NTM) void exct_select_kernel(
         }
     }
     if (tid >= num_dets) return;
-    const u64 key = big[tid];
-    const float score = key2f((uint32_t)(key >> 32));
-    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)key;
-    const int ir = (int)(idx % K), ib = (int)((idx / K) % K), il = (int)((idx / (K * K)) % K),
-              it = (int)(idx / (K * K * K));
-    const int o = b * K;
-    const int HW = H * W;
-    const int sel[4] = {it, il, ib, ir};
-    float xs[4], ys[4], gx[4], gy[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int ind = L.ind[e][o + sel[e]];
-        float x = (float)(ind % W), y = (float)(ind / W);
-        gx[e] = x;
-        gy[e] = y;
-        if (R.r[0]) {  // decode.py:372-390 (all four regression maps given)
-            x = x + R.r[e][((size_t)b * 2 + 0) * HW + ind];
-            y = y + R.r[e][((size_t)b * 2 + 1) * HW + ind];
-        } else {      // decode.py:391-399
-            x = x + 0.5f;
-            y = y + 0.5f;
+    exct_write_row(big[tid], L, R, dets, b, tid, K, H, W, num_dets, cls_map);
+}
+
+// ---- the streaming form of stages B and C (cn_exct_decode_stream_f32): no K^4 array.  The radix select of
+// cn_select.h spread over the chip, one launch per step, the candidates scored again wherever they are read:
+//   count(p)  grid (K*K, B): workgroup (t, l) scores its K*K candidates, bins digit p of the keys that match
+//             the prefix found so far in LDS and adds its non-empty bins to the image's histogram of pass p
+//   pick(p)   grid B: pick_bin() on that histogram -> prefix, mask and need of the image's state; `done` once
+//             everything at or above the boundary bin fits the image's key list
+//   collect   grid (K*K, B): appends every key with (key & mask) >= prefix to the list through a cursor
+//   rows      grid B: sorts the list in LDS (full 64-bit keys, so the cursor's order does not matter), writes
+//             the first num_dets rows
+// count and pick of an image that is `done` return at once, so the launch sequence is the same for every input.
+// No workgroup waits on another: the steps are ordered by the stream.  DESIGN.md 3.4a.
+constexpr int EXCT_LIST = 2 * EXCT_MAX_DETS;   // key slots of an image's list (the rows kernel sorts all of them)
+constexpr int EXCT_PASSES = 6;                 // digits of the 64-bit key (pass_shift)
+static_assert(CN_EXCT_STREAM_MAX_K <= KMAX && (long)CN_EXCT_STREAM_MAX_K * CN_EXCT_STREAM_MAX_K * CN_EXCT_STREAM_MAX_K *
+                      CN_EXCT_STREAM_MAX_K <= (1L << 28), "candidate indices are 32-bit, the lists come from cn_topk_f32");
+
+struct ExctStreamState {    // per image; zeroed by the call (need == 0: not started)
+    u64 prefix, mask;
+    uint32_t need, done, count, pad_;
+};
+
+struct ExctStream {         // the select state in the workspace, each array per image
+    uint32_t *hist;         // [B][EXCT_PASSES][HBINS], zeroed by the call
+    ExctStreamState *state; // [B]
+    u64 *list;              // [B][EXCT_LIST]
+};
+
+__device__ __forceinline__ u64 exct_key(float score, uint32_t idx)
+{
+    return ((u64)f2key(score + 0.0f) << 32) | (u64)(0xFFFFFFFFu - idx);
+}
+
+__global__ __launch_bounds__(NT) void exct_stream_count_kernel(
+    const ExctLists L, const float *__restrict__ ct_heat, const ExctStream S, int K, int H, int W, int C,
+    float scores_thresh, float center_thresh, int num_dets, int pass)
+{
+    __shared__ uint32_t hist[HBINS];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const ExctStreamState st = S.state[b];
+    if (st.done) return;                                    // (uniform: the whole workgroup leaves)
+    for (int i = tid; i < HBINS; i += NT) hist[i] = 0;
+    __syncthreads();
+    const int shift = pass_shift(pass);
+    const uint32_t dmask = pass_dmask(pass);
+    const int it = blockIdx.x / K, il = blockIdx.x % K;
+    const uint32_t first = blockIdx.x * (uint32_t)(K * K);   // index of candidate (t, l, 0, 0)
+    // neighbouring candidates mostly share their leading digits: a thread adds a run of equal digits at once
+    uint32_t cur = 0, run = 0;
+    for (int j = tid; j < K * K; j += NT) {
+        const u64 key = exct_key(exct_score(L, ct_heat, b, K, H, W, C, it, il, j / K, j % K, scores_thresh,
+                                            center_thresh), first + j);
+        if ((key & st.mask) != st.prefix) continue;
+        const uint32_t d = (uint32_t)(key >> shift) & dmask;
+        if (run && d != cur) {
+            atomicAdd(&hist[cur], run);
+            run = 0;
         }
-        xs[e] = x;
-        ys[e] = y;
+        cur = d;
+        ++run;
     }
-    float *d = dets + ((size_t)b * num_dets + tid) * 14;
-    d[0] = xs[1]; d[1] = ys[0]; d[2] = xs[3]; d[3] = ys[2];  // bboxes = (l_x, t_y, r_x, b_y)
-    d[4] = score;
-    d[5] = xs[0]; d[6] = ys[0]; d[7] = xs[1]; d[8] = ys[1];
-    d[9] = xs[2]; d[10] = ys[2]; d[11] = xs[3]; d[12] = ys[3];
-    if (cls_map) {   // decode.py:171-172: the box centre on the grid, from the points BEFORE their offsets
-        const int cx = (int)((gx[1] + gx[3] + 0.5f) / 2.0f);
-        const int cy = (int)((gy[0] + gy[2] + 0.5f) / 2.0f);
-        d[13] = (float)cls_map[(size_t)b * HW + (size_t)cy * W + cx];
-    } else {
-        d[13] = (float)L.cls[0][o + it];                      // clses = t_clses
+    if (run) atomicAdd(&hist[cur], run);
+    __syncthreads();
+    uint32_t *gh = S.hist + ((size_t)b * EXCT_PASSES + pass) * HBINS;
+    for (int i = tid; i < HBINS; i += NT)
+        if (hist[i]) atomicAdd(&gh[i], hist[i]);            // integer sums: the order of arrival does not matter
+}
+
+__global__ __launch_bounds__(NT) void exct_stream_pick_kernel(const ExctStream S, int num_dets, int pass)
+{
+    __shared__ SelShared sh;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    ExctStreamState &st = S.state[b];
+    if (st.done) return;
+    const uint32_t need = pass == 0 ? (uint32_t)num_dets : st.need;
+    const uint32_t *gh = S.hist + ((size_t)b * EXCT_PASSES + pass) * HBINS;
+    for (int i = tid; i < HBINS; i += NT) sh.hist[i] = gh[i];
+    __syncthreads();
+    pick_bin<NT>(sh, need);
+    if (tid == 0) {
+        st.prefix |= (u64)sh.digit << pass_shift(pass);
+        st.mask |= (u64)pass_dmask(pass) << pass_shift(pass);
+        st.need = sh.need;
+        // keys above the boundary bin: num_dets - need; with the bin itself they must fit the list.  The last
+        // pass always ends here: keys are distinct, so its boundary bin holds one key
+        st.done = ((uint32_t)num_dets - sh.need) + sh.bincount <= (uint32_t)EXCT_LIST;
     }
+}
+
+__global__ __launch_bounds__(NT) void exct_stream_collect_kernel(
+    const ExctLists L, const float *__restrict__ ct_heat, const ExctStream S, int K, int H, int W, int C,
+    float scores_thresh, float center_thresh)
+{
+    const int tid = threadIdx.x, b = blockIdx.y;
+    const ExctStreamState st = S.state[b];
+    const int it = blockIdx.x / K, il = blockIdx.x % K;
+    const uint32_t first = blockIdx.x * (uint32_t)(K * K);
+    for (int j = tid; j < K * K; j += NT) {
+        const u64 key = exct_key(exct_score(L, ct_heat, b, K, H, W, C, it, il, j / K, j % K, scores_thresh,
+                                            center_thresh), first + j);
+        if ((key & st.mask) >= st.prefix) {
+            const uint32_t pos = atomicAdd(&S.state[b].count, 1u);
+            if (pos < (uint32_t)EXCT_LIST) S.list[(size_t)b * EXCT_LIST + pos] = key;
+        }
+    }
+}
+
+// one 1024-thread workgroup per image, two list slots per thread
+__global__ __launch_bounds__(NTM) void exct_stream_rows_kernel(
+    const ExctStream S, const ExctLists L, const ExctRegr R, float *__restrict__ dets, int K, int H, int W,
+    int num_dets, const int32_t *__restrict__ cls_map)
+{
+    __shared__ u64 big[EXCT_LIST];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const uint32_t n = min(S.state[b].count, (uint32_t)EXCT_LIST);
+    for (int i = tid; i < EXCT_LIST; i += NTM)
+        big[i] = (uint32_t)i < n ? S.list[(size_t)b * EXCT_LIST + i] : 0;   // pad keys sort last
+    __syncthreads();
+    for (int k = 2; k <= EXCT_LIST; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < EXCT_LIST; i += NTM) {
+                const int partner = i ^ j;
+                if (partner > i) {
+                    const u64 x = big[i], y = big[partner];
+                    const bool desc = (i & k) == 0;
+                    if (desc ? (x < y) : (x > y)) {
+                        big[i] = y;
+                        big[partner] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid >= num_dets) return;
+    exct_write_row(big[tid], L, R, dets, b, tid, K, H, W, num_dets, cls_map);
 }
 
 // agnex_ct_decode's `torch.max(ct_heat, dim=1)` (decode.py:164): per cell the largest value over the classes and
@@ -530,23 +675,56 @@ extern "C" size_t cn_exct_decode_workspace_bytes(int B, int C, int H, int W, int
     return base + lists + cand + map;
 }
 
+// The streaming form's workspace: the top-K workspace, the twelve lists, the one clamped map and the select state --
+// per image EXCT_PASSES histograms, the state words and EXCT_LIST keys (under 1 MiB); no K^4 array.
+static size_t exct_stream_state_bytes(int B)
+{
+    return cn_align_up((size_t)B * EXCT_PASSES * HBINS * sizeof(uint32_t), 256) +
+           cn_align_up((size_t)B * sizeof(ExctStreamState), 256) + cn_align_up((size_t)B * EXCT_LIST * sizeof(u64), 256);
+}
+
+extern "C" size_t cn_exct_decode_stream_workspace_bytes(int B, int C, int H, int W, int K)
+{
+    const size_t base = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
+    if (!base || K > CN_EXCT_STREAM_MAX_K) return 0;
+    const size_t lists = 4 * 3 * cn_align_up((size_t)B * K * 4, 256);
+    const size_t map = cn_align_up((size_t)B * C * H * W * sizeof(float), 256);
+    return base + lists + map + exct_stream_state_bytes(B);
+}
+
+// The argument checks of both forms, in the stored form's order; `streaming` only moves the K limit.
+static int exct_check_args(const float *t_heat, const float *l_heat, const float *b_heat, const float *r_heat,
+                           const float *ct_heat, int K, int num_dets, int flags, const float *dets,
+                           const void *workspace, bool streaming)
+{
+    if (!t_heat || !l_heat || !b_heat || !r_heat || !ct_heat || !dets || !workspace) return CN_ERR_NULL;
+    if (num_dets <= 0 || K <= 0) return CN_ERR_SHAPE;
+    // stored: K^4 floats in memory; streaming: K^4 <= 2^28 candidate indices.  Both: the LDS sort
+    if (K > (streaming ? CN_EXCT_STREAM_MAX_K : CN_EXCT_STORED_MAX_K) || num_dets > EXCT_MAX_DETS) return CN_ERR_UNSUPPORTED;
+    if ((long)num_dets > (long)K * K * K * K) return CN_ERR_SHAPE;      // torch.topk: k out of range
+    if (flags & ~CN_EXCT_CLAMP_ONE) return CN_ERR_UNSUPPORTED;  // the centre map is gathered, not scanned
+    return CN_OK;
+}
+
 static int exct_decode_impl(const float *t_heat, const float *l_heat, const float *b_heat,
                             const float *r_heat, const float *ct_heat, const float *t_regr,
                             const float *l_regr, const float *b_regr, const float *r_regr,
                             int B, int C, int H, int W, int K, float scores_thresh,
                             float center_thresh, int num_dets, int flags,
                             float *dets, void *workspace, size_t workspace_bytes,
-                            void *stream, const int32_t *cls_map)
+                            void *stream, const int32_t *cls_map, bool streaming)
 {
-    if (!t_heat || !l_heat || !b_heat || !r_heat || !ct_heat || !dets || !workspace) return CN_ERR_NULL;
-    if (num_dets <= 0 || K <= 0) return CN_ERR_SHAPE;
-    if (K > 64 || num_dets > EXCT_MAX_DETS) return CN_ERR_UNSUPPORTED;  // K^4 must fit 32 bits / LDS sort
-    if ((long)num_dets > (long)K * K * K * K) return CN_ERR_SHAPE;      // torch.topk: k out of range
-    if (flags & ~CN_EXCT_CLAMP_ONE) return CN_ERR_UNSUPPORTED;  // the centre map is gathered, not scanned
+    const int bad = exct_check_args(t_heat, l_heat, b_heat, r_heat, ct_heat, K, num_dets, flags, dets, workspace,
+                                    streaming);
+    if (bad != CN_OK) return bad;
     const bool clamp_one = (flags & CN_EXCT_CLAMP_ONE) != 0;
     const size_t base = cn_ctdet_decode_workspace_bytes(B, C, H, W, K);
     if (!base) return CN_ERR_UNSUPPORTED;
-    if (workspace_bytes < cn_exct_decode_workspace_bytes(B, C, H, W, K)) return CN_ERR_WORKSPACE;
+    if (workspace_bytes < (streaming ? cn_exct_decode_stream_workspace_bytes(B, C, H, W, K)
+                                     : cn_exct_decode_workspace_bytes(B, C, H, W, K)))
+        return CN_ERR_WORKSPACE;
+    // behind the lists: the stored form's K^4 scores, then the clamped map; the streaming form has the map there
+    const size_t cand_bytes = streaming ? 0 : cn_align_up((size_t)B * K * K * K * K * sizeof(float), 256);
     const bool all_regr = t_regr && l_regr && b_regr && r_regr;  // decode.py:372-373
     const size_t slot = cn_align_up((size_t)B * K * 4, 256);
     char *p = (char *)workspace + base;
@@ -561,8 +739,7 @@ static int exct_decode_impl(const float *t_heat, const float *l_heat, const floa
             // peak test on the raw map, survivors clamped to 1 (decode.py:297-305), then the plain _topk
             // over every cell of the result (zeros of the suppressed cells take part, as in the reference)
             const size_t cells = (size_t)B * C * H * W;
-            float *tmp = (float *)((char *)workspace + base + 4 * 3 * slot +
-                                   cn_align_up((size_t)B * K * K * K * K * sizeof(float), 256));
+            float *tmp = (float *)((char *)workspace + base + 4 * 3 * slot + cand_bytes);
             hipLaunchKernelGGL(exct_nms_clamp_kernel, dim3((unsigned)((cells + 255) / 256 < 8192 ? (cells + 255) / 256 : 8192)),
                                dim3(256), 0, (hipStream_t)stream, heats[e], tmp, H, W, cells);
             CN_CHECK_LAUNCH();
@@ -573,16 +750,41 @@ static int exct_decode_impl(const float *t_heat, const float *l_heat, const floa
         if (rc != CN_OK) return rc;
         L.score[e] = s; L.ind[e] = i; L.cls[e] = c;
     }
-    float *cand = (float *)p;
     hipStream_t st = (hipStream_t)stream;
+    ExctRegr R;
+    R.r[0] = all_regr ? t_regr : nullptr; R.r[1] = all_regr ? l_regr : nullptr;
+    R.r[2] = all_regr ? b_regr : nullptr; R.r[3] = all_regr ? r_regr : nullptr;
+    if (streaming) {
+        char *q = p + cn_align_up((size_t)B * C * H * W * sizeof(float), 256);   // behind the clamped map
+        ExctStream S;
+        S.hist = (uint32_t *)q;
+        q += cn_align_up((size_t)B * EXCT_PASSES * HBINS * sizeof(uint32_t), 256);
+        S.state = (ExctStreamState *)q;
+        q += cn_align_up((size_t)B * sizeof(ExctStreamState), 256);
+        S.list = (u64 *)q;
+        if (hipMemsetAsync(S.hist, 0, (size_t)((char *)S.list - (char *)S.hist), st) != hipSuccess) return CN_ERR_LAUNCH;
+        const dim3 slabs((unsigned)(K * K), (unsigned)B);
+        for (int pass = 0; pass < EXCT_PASSES; ++pass) {
+            hipLaunchKernelGGL(exct_stream_count_kernel, slabs, dim3(NT), 0, st, L, ct_heat, S, K, H, W, C,
+                               scores_thresh, center_thresh, num_dets, pass);
+            CN_CHECK_LAUNCH();
+            hipLaunchKernelGGL(exct_stream_pick_kernel, dim3(B), dim3(NT), 0, st, S, num_dets, pass);
+            CN_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(exct_stream_collect_kernel, slabs, dim3(NT), 0, st, L, ct_heat, S, K, H, W, C,
+                           scores_thresh, center_thresh);
+        CN_CHECK_LAUNCH();
+        hipLaunchKernelGGL(exct_stream_rows_kernel, dim3(B), dim3(NTM), 0, st, S, L, R, dets, K, H, W, num_dets,
+                           cls_map);
+        CN_CHECK_LAUNCH();
+        return CN_OK;
+    }
+    float *cand = (float *)p;
     const size_t n = (size_t)K * K * K * K;
     dim3 grid((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096), B);
     hipLaunchKernelGGL(exct_score_kernel, grid, dim3(256), 0, st, L, ct_heat, cand, K, H, W, C,
                        scores_thresh, center_thresh);
     CN_CHECK_LAUNCH();
-    ExctRegr R;
-    R.r[0] = all_regr ? t_regr : nullptr; R.r[1] = all_regr ? l_regr : nullptr;
-    R.r[2] = all_regr ? b_regr : nullptr; R.r[3] = all_regr ? r_regr : nullptr;
     const size_t lds = sizeof(SelShared) + EXCT_MAX_DETS * sizeof(u64);
     hipLaunchKernelGGL(exct_select_kernel, dim3(B), dim3(NTM), lds, st, cand, L, R, dets, K, H, W,
                        num_dets, cls_map);
@@ -600,7 +802,20 @@ extern "C" int cn_exct_decode_f32(const float *t_heat, const float *l_heat, cons
 {
     return exct_decode_impl(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr, B, C, H, W, K,
                             scores_thresh, center_thresh, num_dets, apply_sigmoid, dets, workspace,
-                            workspace_bytes, stream, nullptr);
+                            workspace_bytes, stream, nullptr, false);
+}
+
+extern "C" int cn_exct_decode_stream_f32(const float *t_heat, const float *l_heat, const float *b_heat,
+                                         const float *r_heat, const float *ct_heat, const float *t_regr,
+                                         const float *l_regr, const float *b_regr, const float *r_regr,
+                                         int B, int C, int H, int W, int K, float scores_thresh,
+                                         float center_thresh, int num_dets, int apply_sigmoid,
+                                         float *dets, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    return exct_decode_impl(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr, B, C, H, W, K,
+                            scores_thresh, center_thresh, num_dets, apply_sigmoid, dets, workspace,
+                            workspace_bytes, stream, nullptr, true);
 }
 
 // agnex_ct_decode (models/decode.py:121-271): the class-agnostic form -- ONE top / left / bottom / right map per
@@ -615,18 +830,31 @@ extern "C" size_t cn_agnex_ct_decode_workspace_bytes(int B, int C, int H, int W,
     return base + 2 * cn_align_up((size_t)B * H * W * 4, 256);
 }
 
-extern "C" int cn_agnex_ct_decode_f32(const float *t_heat, const float *l_heat, const float *b_heat,
-                                      const float *r_heat, const float *ct_heat, const float *t_regr,
-                                      const float *l_regr, const float *b_regr, const float *r_regr,
-                                      int B, int C, int H, int W, int K, float scores_thresh,
-                                      float center_thresh, int num_dets, int flags, float *dets,
-                                      void *workspace, size_t workspace_bytes, void *stream)
+extern "C" size_t cn_agnex_ct_decode_stream_workspace_bytes(int B, int C, int H, int W, int K)
+{
+    const size_t base = cn_exct_decode_stream_workspace_bytes(B, 1, H, W, K);
+    if (!base || C <= 0) return 0;
+    return base + 2 * cn_align_up((size_t)B * H * W * 4, 256);
+}
+
+static int agnex_ct_decode_impl(const float *t_heat, const float *l_heat, const float *b_heat,
+                                const float *r_heat, const float *ct_heat, const float *t_regr,
+                                const float *l_regr, const float *b_regr, const float *r_regr,
+                                int B, int C, int H, int W, int K, float scores_thresh,
+                                float center_thresh, int num_dets, int flags, float *dets,
+                                void *workspace, size_t workspace_bytes, void *stream, bool streaming)
 {
     if (!t_heat || !l_heat || !b_heat || !r_heat || !ct_heat || !dets || !workspace) return CN_ERR_NULL;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return CN_ERR_SHAPE;
-    const size_t base = cn_exct_decode_workspace_bytes(B, 1, H, W, K);
+    if (streaming) {    // every refusal before the first launch (the stored form keeps its order of checks)
+        const int bad = exct_check_args(t_heat, l_heat, b_heat, r_heat, ct_heat, K, num_dets, flags, dets, workspace,
+                                        true);
+        if (bad != CN_OK) return bad;
+    }
+    const size_t base = streaming ? cn_exct_decode_stream_workspace_bytes(B, 1, H, W, K)
+                                  : cn_exct_decode_workspace_bytes(B, 1, H, W, K);
     if (!base) return CN_ERR_UNSUPPORTED;
-    if (workspace_bytes < cn_agnex_ct_decode_workspace_bytes(B, C, H, W, K)) return CN_ERR_WORKSPACE;
+    if (workspace_bytes < base + 2 * cn_align_up((size_t)B * H * W * 4, 256)) return CN_ERR_WORKSPACE;
     const size_t cells = (size_t)B * H * W;
     float *vmax = (float *)((char *)workspace + base);
     int32_t *imax = (int32_t *)((char *)workspace + base + cn_align_up(cells * 4, 256));
@@ -635,5 +863,30 @@ extern "C" int cn_agnex_ct_decode_f32(const float *t_heat, const float *l_heat, 
                        H * W, cells);
     CN_CHECK_LAUNCH();
     return exct_decode_impl(t_heat, l_heat, b_heat, r_heat, vmax, t_regr, l_regr, b_regr, r_regr, B, 1, H, W, K,
-                            scores_thresh, center_thresh, num_dets, flags, dets, workspace, base, stream, imax);
+                            scores_thresh, center_thresh, num_dets, flags, dets, workspace, base, stream, imax,
+                            streaming);
+}
+
+extern "C" int cn_agnex_ct_decode_f32(const float *t_heat, const float *l_heat, const float *b_heat,
+                                      const float *r_heat, const float *ct_heat, const float *t_regr,
+                                      const float *l_regr, const float *b_regr, const float *r_regr,
+                                      int B, int C, int H, int W, int K, float scores_thresh,
+                                      float center_thresh, int num_dets, int flags, float *dets,
+                                      void *workspace, size_t workspace_bytes, void *stream)
+{
+    return agnex_ct_decode_impl(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr, B, C, H, W,
+                                K, scores_thresh, center_thresh, num_dets, flags, dets, workspace, workspace_bytes,
+                                stream, false);
+}
+
+extern "C" int cn_agnex_ct_decode_stream_f32(const float *t_heat, const float *l_heat, const float *b_heat,
+                                             const float *r_heat, const float *ct_heat, const float *t_regr,
+                                             const float *l_regr, const float *b_regr, const float *r_regr,
+                                             int B, int C, int H, int W, int K, float scores_thresh,
+                                             float center_thresh, int num_dets, int flags, float *dets,
+                                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    return agnex_ct_decode_impl(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr, B, C, H, W,
+                                K, scores_thresh, center_thresh, num_dets, flags, dets, workspace, workspace_bytes,
+                                stream, true);
 }

@@ -56,6 +56,47 @@ __device__ __forceinline__ int pass_shift(int p)
 }
 __device__ __forceinline__ uint32_t pass_dmask(int p) { return (p == 2 || p == 5) ? 1023u : 2047u; }
 
+// The bin of sh.hist that holds the `need`-th largest element, counted from the top bin down: on return (behind
+// a barrier) sh.digit is that bin, sh.need what is still needed from inside it and sh.bincount its population.
+// Called by all TB threads with sh.hist complete and a barrier behind its last update.
+template <int TB>
+__device__ __forceinline__ void pick_bin(SelShared &sh, uint32_t need)
+{
+    static_assert(HBINS % TB == 0 && TB / CN_WAVE <= MAXW, "block size");
+    constexpr int BPT = HBINS / TB;  // histogram bins owned by a thread
+    const int tid = threadIdx.x;
+    const int lane = tid & (CN_WAVE - 1);
+    const int wave = tid / CN_WAVE;
+    // suffix sums over bins: thread t owns bins [BPT*t, BPT*t + BPT)
+    uint32_t p = 0;
+#pragma unroll
+    for (int j = 0; j < BPT; ++j) p += sh.hist[tid * BPT + j];
+    uint32_t s = p;
+#pragma unroll
+    for (int o = 1; o < CN_WAVE; o <<= 1) {
+        const uint32_t t = __shfl_down(s, o);
+        if (lane + o < CN_WAVE) s += t;
+    }
+    if (lane == 0) sh.wsum[wave] = s;
+    __syncthreads();
+    for (int w = wave + 1; w < TB / CN_WAVE; ++w) s += sh.wsum[w];
+    const uint32_t above = s - p;  // elements in strictly higher bins
+    if (above < need && s >= need) {
+        uint32_t run = above;
+        for (int j = BPT - 1; j >= 0; --j) {
+            const uint32_t h = sh.hist[tid * BPT + j];
+            if (run + h >= need) {
+                sh.digit = tid * BPT + j;
+                sh.need = need - run;
+                sh.bincount = h;
+                break;
+            }
+            run += h;
+        }
+    }
+    __syncthreads();
+}
+
 // Exact selection of the `need0` largest 64-bit keys among the elements that
 // `for_each(f)` enumerates (f(key64, is_plain_zero)); keys must be distinct.
 // On return every thread holds (prefix, mask): an element is selected iff
@@ -67,10 +108,8 @@ __device__ __forceinline__ void radix_select(ForEach &&for_each, uint32_t need0,
                                              u64 &out_prefix, u64 &out_mask)
 {
     static_assert(HBINS % TB == 0 && TB / CN_WAVE <= MAXW, "block size");
-    constexpr int BPT = HBINS / TB;  // histogram bins owned by a thread
     const int tid = threadIdx.x;
     const int lane = tid & (CN_WAVE - 1);
-    const int wave = tid / CN_WAVE;
     u64 prefix = 0, mask = 0;
     uint32_t need = need0;
     const u64 zkey = (u64)KEY_ZERO << 32;
@@ -94,34 +133,7 @@ __device__ __forceinline__ void radix_select(ForEach &&for_each, uint32_t need0,
             if (lane == 0 && zc) atomicAdd(&sh.hist[(uint32_t)(zkey >> shift) & dmask], zc);
         }
         __syncthreads();
-        // suffix sums over bins: thread t owns bins [BPT*t, BPT*t + BPT)
-        uint32_t p = 0;
-#pragma unroll
-        for (int j = 0; j < BPT; ++j) p += sh.hist[tid * BPT + j];
-        uint32_t s = p;
-#pragma unroll
-        for (int o = 1; o < CN_WAVE; o <<= 1) {
-            const uint32_t t = __shfl_down(s, o);
-            if (lane + o < CN_WAVE) s += t;
-        }
-        if (lane == 0) sh.wsum[wave] = s;
-        __syncthreads();
-        for (int w = wave + 1; w < TB / CN_WAVE; ++w) s += sh.wsum[w];
-        const uint32_t above = s - p;  // elements in strictly higher bins
-        if (above < need && s >= need) {
-            uint32_t run = above;
-            for (int j = BPT - 1; j >= 0; --j) {
-                const uint32_t h = sh.hist[tid * BPT + j];
-                if (run + h >= need) {
-                    sh.digit = tid * BPT + j;
-                    sh.need = need - run;
-                    sh.bincount = h;
-                    break;
-                }
-                run += h;
-            }
-        }
-        __syncthreads();
+        pick_bin<TB>(sh, need);
         prefix |= (u64)sh.digit << shift;
         mask |= (u64)dmask << shift;
         need = sh.need;

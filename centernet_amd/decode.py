@@ -377,21 +377,32 @@ def ddd_decode_at_cells(heat, late, K=40, apply_sigmoid=False, raw_depth=False, 
 
 def agnex_ct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr=None, l_regr=None, b_regr=None,
                     r_regr=None, K=40, scores_thresh=0.1, center_thresh=0.1, aggr_weight=0.0,
-                    num_dets=1000):
+                    num_dets=1000, stream=None):
     """decode.py:121-271 -> (B, num_dets, 14): the class-agnostic ``exct_decode`` -- single-channel edge
     maps, the centre map over the classes; groupings are scored against the centre map's per-cell maximum
-    and take its arg-max at the box centre as their class (``cn_agnex_ct_decode_f32``)."""
+    and take its arg-max at the box centre as their class (``cn_agnex_ct_decode_f32``; ``stream`` as in
+    ``exct_decode``: ``cn_agnex_ct_decode_stream_f32``)."""
     return exct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr, K=K,
                        scores_thresh=scores_thresh, center_thresh=center_thresh, aggr_weight=aggr_weight,
-                       num_dets=num_dets, _agnostic=True)
+                       num_dets=num_dets, stream=stream, _agnostic=True)
 
 
 def exct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr=None, l_regr=None, b_regr=None,
                 r_regr=None, K=40, scores_thresh=0.1, center_thresh=0.1, aggr_weight=0.0,
-                num_dets=1000, _agnostic=False):
+                num_dets=1000, stream=None, _agnostic=False):
     """decode.py:273-424 -> (B, num_dets, 14).  Heat-maps post-sigmoid (values <= 1).
     ``aggr_weight > 0``: the edge aggregation of decode.py:17-90,136-140 runs in front
-    (``cn_exct_aggregate_f32``: rows of t / b, columns of l / r)."""
+    (``cn_exct_aggregate_f32``: rows of t / b, columns of l / r).
+    ``stream``: which form groups the K^4 candidates -- False the stored one (``cn_exct_decode_f32``: every
+    score written to memory, K <= 64), True the streaming one (``cn_exct_decode_stream_f32``: scores recomputed
+    while selecting, K <= 128), None the stored one up to K = 64 and the streaming one above.  Same rows, bit
+    for bit, wherever both run."""
+    if K > native.EXCT_STREAM_MAX_K:
+        raise RuntimeError("exct_decode takes K <= %d (K^4 candidate indices), got K = %d"
+                           % (native.EXCT_STREAM_MAX_K, K))
+    if stream is None:
+        stream = K > native.EXCT_STORED_MAX_K
+    form = "_stream" if stream else ""
     t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr = _prep(
         t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr, l_regr, b_regr, r_regr)
     lib = native.lib()
@@ -422,24 +433,15 @@ def exct_decode(t_heat, l_heat, b_heat, r_heat, ct_heat, t_regr=None, l_regr=Non
     if K > H * W or num_dets > K ** 4:
         raise RuntimeError("selected index k out of range")
     dets = torch.empty((B, num_dets, 14), device=t_heat.device, dtype=torch.float32)
-    if _agnostic:
-        Cc = int(ct_heat.shape[1])
-        ws = _workspace(lib.cn_agnex_ct_decode_workspace_bytes(B, Cc, H, W, K), t_heat.device)
-        rc = lib.cn_agnex_ct_decode_f32(native.ptr(t_heat), native.ptr(l_heat), native.ptr(b_heat),
-                                        native.ptr(r_heat), native.ptr(ct_heat), native.ptr(t_regr),
-                                        native.ptr(l_regr), native.ptr(b_regr), native.ptr(r_regr), B, Cc, H,
-                                        W, K, scores_thresh, center_thresh, num_dets,
-                                        native.EXCT_CLAMP_ONE if aggr_weight > 0 else 0, native.ptr(dets),
-                                        native.ptr(ws), ws.numel(), native.stream_ptr())
-        native.check(rc, "cn_agnex_ct_decode_f32")
-        return dets
-    ws = _workspace(lib.cn_exct_decode_workspace_bytes(B, C, H, W, K), t_heat.device)
-    rc = lib.cn_exct_decode_f32(native.ptr(t_heat), native.ptr(l_heat), native.ptr(b_heat),
-                                native.ptr(r_heat), native.ptr(ct_heat), native.ptr(t_regr),
-                                native.ptr(l_regr), native.ptr(b_regr), native.ptr(r_regr), B, C, H,
-                                W, K, scores_thresh, center_thresh, num_dets,
-                                # aggregated edge maps exceed 1: clamp behind the peak test (decode.py:302-305)
-                                native.EXCT_CLAMP_ONE if aggr_weight > 0 else 0, native.ptr(dets),
-                                native.ptr(ws), ws.numel(), native.stream_ptr())
-    native.check(rc, "cn_exct_decode_f32")
+    # aggregated edge maps exceed 1: clamp behind the peak test (decode.py:302-305)
+    flags = native.EXCT_CLAMP_ONE if aggr_weight > 0 else 0
+    name = ("cn_agnex_ct_decode" if _agnostic else "cn_exct_decode") + form
+    Cc = int(ct_heat.shape[1])              # (== C unless class-agnostic)
+    ws = _workspace(getattr(lib, name + "_workspace_bytes")(B, Cc, H, W, K), t_heat.device)
+    rc = getattr(lib, name + "_f32")(native.ptr(t_heat), native.ptr(l_heat), native.ptr(b_heat),
+                                     native.ptr(r_heat), native.ptr(ct_heat), native.ptr(t_regr),
+                                     native.ptr(l_regr), native.ptr(b_regr), native.ptr(r_regr), B, Cc, H, W, K,
+                                     scores_thresh, center_thresh, num_dets, flags, native.ptr(dets),
+                                     native.ptr(ws), ws.numel(), native.stream_ptr())
+    native.check(rc, name + "_f32")
     return dets

@@ -1,7 +1,8 @@
 """exdet task -- ExtremeNet-style detection (public behaviour of src/lib/detectors/exdet.py:23-118):
 four extreme-point heat-maps + a centre map per class on the HIP network, grouped into boxes by
 ``cn_exct_decode_f32`` (K^4 candidate scoring with the edge aggregation of --aggr_weight in front);
---agnostic_ex: one extreme-point map per edge for all classes, ``cn_agnex_ct_decode_f32``.
+--agnostic_ex: one extreme-point map per edge for all classes, ``cn_agnex_ct_decode_f32``;
+--ex_stream: the ``_stream_f32`` forms of both, which keep no K^4 array and take the reference's --K 100.
 
 Two things the reference's class does are kept as they are, because they ARE its results:
 * ``post_process`` reads the decode's rows as TWO images -- the frame and its mirror image -- and
@@ -14,6 +15,7 @@ One thing differs: the reference's ``merge_outputs`` calls ``soft_nms`` without 
 (exdet.py:110 -- a NameError as shipped); here it is the library's (external/nms.pyx:77-170).
 New surface: ``run_batch`` (device-resident batches) and ``run_frames`` / ``run_frames_stream`` with the
 task's tail on the device (``cn_exdet_post_process_f32`` + ``cn_exdet_merge_f32``)."""
+import functools
 import time
 
 import numpy as np
@@ -33,12 +35,20 @@ EDGE_OFFSETS = ('reg_t', 'reg_l', 'reg_b', 'reg_r')
 
 class ExdetDetector(BaseDetector):
     def __init__(self, opt):
-        if opt.K > 64:
-            # the reference would score K^4 = 10^8 groupings per image at the --K default of 100; the
+        self.ex_stream = bool(getattr(opt, 'ex_stream', False))
+        if self.ex_stream:
+            if opt.K > native.EXCT_STREAM_MAX_K:
+                raise ValueError("the exdet task with --ex_stream needs --K <= %d (K^4 candidate indices)"
+                                 % native.EXCT_STREAM_MAX_K)
+        elif opt.K > native.EXCT_STORED_MAX_K:
+            # the reference would score K^4 = 10^8 groupings per image at the --K default of 100; the stored
             # kernel takes K <= 64 (cn_exct_decode_f32), ExtremeNet's own setting is 40
-            raise ValueError("the exdet task needs --K <= 64 (K^4 candidate groupings per image); use --K 40")
+            raise ValueError("the exdet task needs --K <= 64 (K^4 candidate groupings per image); use --K 40, "
+                             "or --ex_stream for --K up to %d" % native.EXCT_STREAM_MAX_K)
         super(ExdetDetector, self).__init__(opt)
-        self.decode = agnex_ct_decode if opt.agnostic_ex else exct_decode      # exdet.py:26
+        decode = agnex_ct_decode if opt.agnostic_ex else exct_decode           # exdet.py:26
+        # --ex_stream: the streaming grouping at every K; without it the decode's own choice (the stored form here)
+        self.decode = functools.partial(decode, stream=True) if self.ex_stream else decode
 
     def process(self, images, return_time=False):
         """exdet.py:28-55: the five maps post-sigmoid (in place, as there), then ``exct_decode`` with

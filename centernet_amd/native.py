@@ -39,6 +39,8 @@ DECODE_PER_BAND = 2048      # CN_DECODE_PER_BAND: force the per-band select (tes
 DECODE_STATE_CLEAN = 4096   # CN_DECODE_STATE_CLEAN: the caller owns the workspace, its image state words are zero
 DECODE_TWO_LAUNCHES = 8192  # CN_DECODE_TWO_LAUNCHES: the two-launch image-level form (tests / A-B)
 DECODE_DDD_RAW_DEPTH = 16384    # CN_DECODE_DDD_RAW_DEPTH: cn_ddd_decode_f32 transforms the gathered depths
+EXCT_STORED_MAX_K = 64      # cn_exct_decode_f32 / cn_agnex_ct_decode_f32: K^4 scores in memory
+EXCT_STREAM_MAX_K = 128     # cn_exct_decode_stream_f32 / cn_agnex_ct_decode_stream_f32
 EXCT_CLAMP_ONE = 2          # CN_EXCT_CLAMP_ONE (cn_exct_decode_f32): clamp the peak-tested edge maps to 1
 # forms and flags of cn_dcn_v2_route: the #defines CN_<name> of the header (tests/test_dcn_route_host.py compares them)
 DCN_GATHER, DCN_GATHER_PAD, DCN_WINDOW, DCN_TEAM_T, DCN_TEAM_N, DCN_WIDE4, DCN_WIDE8 = range(7)
@@ -380,6 +382,11 @@ def _declare(lib):
     lib.cn_agnex_ct_decode_f32.restype = i
     lib.cn_agnex_ct_decode_f32.argtypes = [vp] * 9 + [i] * 5 + [ctypes.c_float, ctypes.c_float, i, i,
                                                             vp, vp, sz, vp]
+    for name in ("cn_exct_decode_stream", "cn_agnex_ct_decode_stream"):    # the forms without the K^4 array
+        getattr(lib, name + "_workspace_bytes").restype = sz
+        getattr(lib, name + "_workspace_bytes").argtypes = [i] * 5
+        getattr(lib, name + "_f32").restype = i
+        getattr(lib, name + "_f32").argtypes = lib.cn_exct_decode_f32.argtypes
     lib.cn_multi_pose_decode_workspace_bytes.restype = sz
     lib.cn_multi_pose_decode_workspace_bytes.argtypes = [i] * 6
     lib.cn_multi_pose_decode_f32.restype = i

@@ -6,7 +6,7 @@ lines parse, but only the inference-relevant ones are consumed by this package:
 task, --arch, --head_conv, --down_ratio, --input_res/_h/_w, --load_model, --gpus, --K,
 --flip_test, --test_scales, --nms, --keep_res/--fix_res, --cat_spec_wh, --not_reg_offset,
 --not_hm_hp, --not_reg_hp_offset, --debug, --vis_thresh; for the ddd task --not_reg_bbox and
---peak_thresh, for exdet --scores_thresh, --center_thresh, --aggr_weight, --agnostic_ex.
+--peak_thresh, for exdet --scores_thresh, --center_thresh, --aggr_weight, --agnostic_ex, --ex_stream.
 """
 import argparse
 import os
@@ -43,6 +43,9 @@ _FLAGS = [
     # new: fp16 activations and weights with fp32 accumulation (PlannedModule.half_compute): hourglass,
     # res_N, resdcn_N and dla_34; not together with --fp32_mfma
     ("--fp16", dict(action="store_true")),
+    # new: exdet groups its K^4 candidates with the streaming kernels (cn_exct_decode_stream_f32: scores recomputed
+    # while selecting, K <= 128) -- --K then keeps the reference's default of 100; inert for the other tasks
+    ("--ex_stream", dict(action="store_true", help="exdet: streaming K^4 grouping, --K up to 128 (default 100)")),
     ("--shift", dict(type=float, default=0.1)), ("--scale", dict(type=float, default=0.4)),
     ("--rotate", dict(type=float, default=0)), ("--flip", dict(type=float, default=0.5)),
     ("--no_color_aug", dict(action="store_true")), ("--aug_rot", dict(type=float, default=0)),
@@ -94,11 +97,12 @@ class opts(object):
     def parse(self, args=''):
         # opts.py:227-282
         opt = self.parser.parse_args() if args == '' else self.parser.parse_args(args)
-        # exdet scores K^4 groupings per image; the kernel takes K <= 64 and ExtremeNet's own setting is 40.  A
-        # command line that does not pass --K (the reference default of 100) runs at 40 instead of failing.
+        # exdet scores K^4 groupings per image; the stored kernel takes K <= 64 and ExtremeNet's own setting is 40.
+        # A command line that does not pass --K (the reference default of 100) runs at 40 instead of failing --
+        # unless --ex_stream chooses the streaming kernels, which take the reference's default.
         import sys as _sys
         argv = _sys.argv[1:] if args == '' else list(args)
-        if opt.task == 'exdet' and not any(a == '--K' or str(a).startswith('--K=') for a in argv):
+        if opt.task == 'exdet' and not opt.ex_stream and not any(a == '--K' or str(a).startswith('--K=') for a in argv):
             opt.K = 40
         if opt.fp16 and opt.fp32_mfma:
             self.parser.error("--fp16 and --fp32_mfma both choose the compute mode: give one of them")

@@ -1195,6 +1195,34 @@ int cn_agnex_ct_decode_f32(const float *t_heat, const float *l_heat, const float
                            int H, int W, int K, float scores_thresh, float center_thresh, int num_dets,
                            int flags, float *dets, void *workspace, size_t workspace_bytes,
                            void *stream);
+/* The streaming forms of the two decodes above: same arguments, same rows bit for bit (same scores, same tie
+ * order: score descending, candidate index ascending), for 1 <= K <= 128 (K^4 <= 2^28 candidate indices) and
+ * num_dets <= 1024 -- the reference's --K default of 100 included.  The K^4 candidate scores are never stored:
+ * the exact top num_dets is a radix select over the 64-bit (score, ~index) keys whose every step scores the
+ * candidates again from the four top-K lists (per key digit a count launch over (t, l) slabs and a
+ * one-workgroup-per-image pick launch, then a collect launch and a sort + row launch; a fixed launch sequence,
+ * steps an image no longer needs return at once).  Workspace: the top-K workspace, the twelve lists, the one
+ * clamped map of CN_EXCT_CLAMP_ONE and under 1 MiB of select state per image, which the call zeroes itself.
+ * No host synchronisation; capturable in a graph.  Refusals as the stored forms': CN_ERR_NULL, CN_ERR_SHAPE
+ * (num_dets <= 0, K <= 0, num_dets > K^4), CN_ERR_UNSUPPORTED (K > 128, num_dets > 1024, other flags),
+ * CN_ERR_WORKSPACE -- all before anything is launched.  CN_EXCT_STORED_MAX_K / CN_EXCT_STREAM_MAX_K: the largest K
+ * of the stored and of the streaming forms. */
+#define CN_EXCT_STORED_MAX_K 64
+#define CN_EXCT_STREAM_MAX_K 128
+size_t cn_exct_decode_stream_workspace_bytes(int B, int C, int H, int W, int K);
+int cn_exct_decode_stream_f32(const float *t_heat, const float *l_heat, const float *b_heat,
+                              const float *r_heat, const float *ct_heat, const float *t_regr,
+                              const float *l_regr, const float *b_regr, const float *r_regr, int B, int C,
+                              int H, int W, int K, float scores_thresh, float center_thresh, int num_dets,
+                              int apply_sigmoid, float *dets, void *workspace, size_t workspace_bytes,
+                              void *stream);
+size_t cn_agnex_ct_decode_stream_workspace_bytes(int B, int C, int H, int W, int K);
+int cn_agnex_ct_decode_stream_f32(const float *t_heat, const float *l_heat, const float *b_heat,
+                                  const float *r_heat, const float *ct_heat, const float *t_regr,
+                                  const float *l_regr, const float *b_regr, const float *r_regr, int B, int C,
+                                  int H, int W, int K, float scores_thresh, float center_thresh, int num_dets,
+                                  int flags, float *dets, void *workspace, size_t workspace_bytes,
+                                  void *stream);
 
 /* ------------------------------------------------------------------------
  * multi_pose decode.
