@@ -1,5 +1,6 @@
 """Heat-map decode entry points (mirror of src/lib/models/decode.py), backed by the
-fused HIP kernels in csrc/cn_decode.hip (the top-K forms and their one route) and
+fused HIP kernels in csrc/cn_decode.hip (the top-K forms and their one route),
+csrc/cn_decode_large.hip (``ctdet_decode`` and ``_topk`` with 128 < K <= 1024) and
 csrc/cn_decode_tasks.hip (pose matching, ddd, exct, agnex).
 
 Same callables, same argument meaning, tensors in / tensor out:
@@ -93,6 +94,15 @@ def _expect(name, t, B, C, H, W, device):
         raise RuntimeError("%s is on %s, the heat-map on %s" % (name, t.device, device))
 
 
+def _large_k(K):
+    """Which image-level top-K a call with this K (already known to fit the map) takes: False = the forms of
+    ``cn_ctdet_decode_f32`` / ``cn_topk_f32`` (K <= 128, exactly as ever), True = the large-K form of
+    csrc/cn_decode_large.hip (128 < K <= 1024); more raises."""
+    if K > native.DECODE_LARGE_MAX_K:
+        raise RuntimeError("the image-level top-K takes K <= %d, got K = %d" % (native.DECODE_LARGE_MAX_K, K))
+    return K > native.DECODE_MAX_K
+
+
 def ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100, apply_sigmoid=False,
                  return_inds=False, _debug_flags=0):
     heat, wh, reg = _prep(heat, wh, reg)
@@ -104,16 +114,22 @@ def ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100, apply_sigmoid=Fal
     _expect("reg", reg, B, 2, H, W, heat.device)
     if K > H * W:
         raise RuntimeError("selected index k out of range")  # torch.topk's error
+    large = _large_k(K)
     dets = torch.empty((B, K, 6), device=heat.device, dtype=torch.float32)
     inds = torch.empty((B, K), device=heat.device, dtype=torch.int32)
     flags = int(bool(apply_sigmoid)) | int(_debug_flags)
 
     def call(flags, ws):
-        return lib.cn_ctdet_decode_f32(native.ptr(heat), native.ptr(wh), native.ptr(reg), B, C, H, W, K,
-                                       int(bool(cat_spec_wh)), flags,
-                                       native.ptr(dets), native.ptr(inds), native.ptr(ws), ws.numel(),
-                                       native.stream_ptr())
-    if _debug_flags:    # (tests / A-B: a shared workspace, the library fills the state words)
+        entry = lib.cn_ctdet_decode_large_f32 if large else lib.cn_ctdet_decode_f32
+        return entry(native.ptr(heat), native.ptr(wh), native.ptr(reg), B, C, H, W, K,
+                     int(bool(cat_spec_wh)), flags,
+                     native.ptr(dets), native.ptr(inds), native.ptr(ws), ws.numel(),
+                     native.stream_ptr())
+    if large:           # (no state words to keep clean, but the candidate keys cross its two launches: per stream)
+        ws = _own_workspace("ctdet_large", lib.cn_ctdet_decode_large_workspace_bytes(B, C, H, W, K), heat.device,
+                            (B, C, H, W, K))
+        native.check(call(flags, ws), "cn_ctdet_decode_large_f32")
+    elif _debug_flags:  # (tests / A-B: a shared workspace, the library fills the state words)
         ws = _workspace(lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), heat.device)
         native.check(call(flags, ws), "cn_ctdet_decode_f32")
     else:
@@ -121,13 +137,15 @@ def ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100, apply_sigmoid=Fal
     return (dets, inds.long()) if return_inds else dets
 
 
-def _topk_f32(lib, heat, B, C, H, W, K, flags, ws, stream):
-    """``cn_topk_f32`` into fresh (B, K) buffers -> (scores, inds, clses, return code)."""
+def _topk_f32(lib, heat, B, C, H, W, K, flags, ws, stream, large=False):
+    """``cn_topk_f32`` (``large``: ``cn_topk_large_f32``) into fresh (B, K) buffers -> (scores, inds, clses,
+    return code)."""
     scores = torch.empty((B, K), device=heat.device, dtype=torch.float32)
     inds = torch.empty((B, K), device=heat.device, dtype=torch.int32)
     clses = torch.empty((B, K), device=heat.device, dtype=torch.int32)
-    rc = lib.cn_topk_f32(native.ptr(heat), B, C, H, W, K, flags, native.ptr(scores), native.ptr(inds),
-                         native.ptr(clses), native.ptr(ws), ws.numel(), stream)
+    entry = lib.cn_topk_large_f32 if large else lib.cn_topk_f32
+    rc = entry(native.ptr(heat), B, C, H, W, K, flags, native.ptr(scores), native.ptr(inds),
+               native.ptr(clses), native.ptr(ws), ws.numel(), stream)
     return scores, inds, clses, rc
 
 
@@ -297,9 +315,14 @@ def _topk(scores, K=40, apply_sigmoid=False, nms=False):
     if K > H * W:
         raise RuntimeError("selected index k out of range")
     flags = int(bool(apply_sigmoid)) | (0 if nms else native.DECODE_NO_PEAK_TEST)
-    ws = _workspace(lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), scores.device)
-    s, i, c, rc = _topk_f32(lib, scores, B, C, H, W, K, flags, ws, native.stream_ptr())
-    native.check(rc, "cn_topk_f32")
+    large = _large_k(K)
+    if large:           # (the candidate keys cross the form's two launches: a workspace per stream)
+        ws = _own_workspace("topk_large", lib.cn_ctdet_decode_large_workspace_bytes(B, C, H, W, K), scores.device,
+                            (B, C, H, W, K))
+    else:
+        ws = _workspace(lib.cn_ctdet_decode_workspace_bytes(B, C, H, W, K), scores.device)
+    s, i, c, rc = _topk_f32(lib, scores, B, C, H, W, K, flags, ws, native.stream_ptr(), large)
+    native.check(rc, "cn_topk_large_f32" if large else "cn_topk_f32")
     i = i.long()
     return s, i, c.int(), (i // W).float(), (i % W).float()
 

@@ -68,7 +68,9 @@ class BaseDetector(object):
         self.std = np.asarray(opt.std, np.float32).reshape(1, 1, 3)
         self.scales = opt.test_scales
         self.num_classes = opt.num_classes
-        self.max_per_image = 100
+        self.max_per_image = int(getattr(opt, 'max_per_image', 100))     # (--max_per_image; the reference: 100)
+        if self.max_per_image < 1:
+            raise ValueError("--max_per_image must be at least 1, got %d" % self.max_per_image)
         self.pause = True
         self.tail_fallbacks = 0      # batches of the frame pipe that its device tail handed back to the host
         self.model.defer_heads(self._deferred_heads())

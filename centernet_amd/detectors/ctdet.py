@@ -30,6 +30,13 @@ def deferred_ctdet_heads(opt):
 
 
 class CtdetDetector(TilesMixin, BaseDetector):
+    def __init__(self, opt):
+        # K <= 128: the one-launch top-K, the heads at the K cells, the device tails.  128 < K <= 1024: the large-K
+        # top-K (csrc/cn_decode_large.hip) on the dense wh / reg maps, host tails.  More is nobody's path.
+        if opt.K > native.DECODE_LARGE_MAX_K:
+            raise ValueError("the ctdet task needs --K <= %d, got %d" % (native.DECODE_LARGE_MAX_K, opt.K))
+        super(CtdetDetector, self).__init__(opt)
+
     def _deferred_heads(self):
         return deferred_ctdet_heads(self.opt)
 

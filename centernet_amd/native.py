@@ -39,6 +39,8 @@ DECODE_PER_BAND = 2048      # CN_DECODE_PER_BAND: force the per-band select (tes
 DECODE_STATE_CLEAN = 4096   # CN_DECODE_STATE_CLEAN: the caller owns the workspace, its image state words are zero
 DECODE_TWO_LAUNCHES = 8192  # CN_DECODE_TWO_LAUNCHES: the two-launch image-level form (tests / A-B)
 DECODE_DDD_RAW_DEPTH = 16384    # CN_DECODE_DDD_RAW_DEPTH: cn_ddd_decode_f32 transforms the gathered depths
+DECODE_MAX_K = 128          # CN_DECODE_MAX_K: where cn_ctdet_decode_f32 / cn_topk_f32 stop
+DECODE_LARGE_MAX_K = 1024   # CN_DECODE_LARGE_MAX_K: cn_ctdet_decode_large_f32 / cn_topk_large_f32
 EXCT_STORED_MAX_K = 64      # cn_exct_decode_f32 / cn_agnex_ct_decode_f32: K^4 scores in memory
 EXCT_STREAM_MAX_K = 128     # cn_exct_decode_stream_f32 / cn_agnex_ct_decode_stream_f32
 EXCT_CLAMP_ONE = 2          # CN_EXCT_CLAMP_ONE (cn_exct_decode_f32): clamp the peak-tested edge maps to 1
@@ -353,6 +355,12 @@ def _declare(lib):
     lib.cn_nms_topk_channel_f32.argtypes = [vp] + [i] * 6 + [vp, vp, vp, sz, vp]
     lib.cn_topk_f32.restype = i
     lib.cn_topk_f32.argtypes = [vp] + [i] * 6 + [vp, vp, vp, vp, sz, vp]
+    lib.cn_ctdet_decode_large_workspace_bytes.restype = sz
+    lib.cn_ctdet_decode_large_workspace_bytes.argtypes = [i] * 5
+    lib.cn_ctdet_decode_large_f32.restype = i
+    lib.cn_ctdet_decode_large_f32.argtypes = lib.cn_ctdet_decode_f32.argtypes
+    lib.cn_topk_large_f32.restype = i
+    lib.cn_topk_large_f32.argtypes = lib.cn_topk_f32.argtypes
     lib.cn_pack_cell_heads_w1.restype = i
     lib.cn_pack_cell_heads_w1.argtypes = [vp, vp, i, i, vp]
     lib.cn_ctdet_heads_at_cells_f32.restype = i

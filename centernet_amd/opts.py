@@ -7,6 +7,7 @@ task, --arch, --head_conv, --down_ratio, --input_res/_h/_w, --load_model, --gpus
 --flip_test, --test_scales, --nms, --keep_res/--fix_res, --cat_spec_wh, --not_reg_offset,
 --not_hm_hp, --not_reg_hp_offset, --debug, --vis_thresh; for the ddd task --not_reg_bbox and
 --peak_thresh, for exdet --scores_thresh, --center_thresh, --aggr_weight, --agnostic_ex, --ex_stream.
+New here: --host_pre_process, --fp32_mfma, --fp16, --ex_stream, --max_per_image.
 """
 import argparse
 import os
@@ -46,6 +47,9 @@ _FLAGS = [
     # new: exdet groups its K^4 candidates with the streaming kernels (cn_exct_decode_stream_f32: scores recomputed
     # while selecting, K <= 128) -- --K then keeps the reference's default of 100; inert for the other tasks
     ("--ex_stream", dict(action="store_true", help="exdet: streaming K^4 grouping, --K up to 128 (default 100)")),
+    # new: the detections a detector keeps per image (BaseDetector.max_per_image, a constant 100 in the reference);
+    # raise it together with --K to get the rows of a large top-K back
+    ("--max_per_image", dict(type=int, default=100, help="detections kept per image (default 100)")),
     ("--shift", dict(type=float, default=0.1)), ("--scale", dict(type=float, default=0.4)),
     ("--rotate", dict(type=float, default=0)), ("--flip", dict(type=float, default=0.5)),
     ("--no_color_aug", dict(action="store_true")), ("--aug_rot", dict(type=float, default=0)),

@@ -1060,6 +1060,30 @@ int cn_topk_f32(const float *heat, int B, int C, int H, int W, int K, int apply_
                 float *scores, int32_t *inds, int32_t *clses, void *workspace,
                 size_t workspace_bytes, void *stream);
 
+/* The large-K forms of cn_ctdet_decode_f32 and cn_topk_f32 (cn_decode_large.hip): the same arguments, flags,
+ * outputs and tie order, exact for 1 <= K <= CN_DECODE_LARGE_MAX_K (and K <= H*W), and the same rows bit for bit
+ * where both take the call.  Two launches -- an exact select per (image, class, row band), then one workgroup per
+ * image that selects among the bands' candidates, sorts and writes the rows -- with no state in the workspace:
+ * nothing to zero, CN_DECODE_STATE_CLEAN is accepted and ignored, and the result does not depend on the order
+ * in which workgroups run.  The workspace carries the candidates from the first launch to the second: calls that
+ * may overlap (two streams) need a workspace each.  They allocate nothing and never wait for the device.  Meant for K > 128: below
+ * that the entries above are faster.  Workspace: cn_ctdet_decode_large_workspace_bytes for both entries (0 where
+ * the call would be refused for its shape or K).  Checks, in this order and before anything is launched: heat NULL
+ * -> CN_ERR_NULL; B, K <= 0 or K > H*W -> CN_ERR_SHAPE; K > CN_DECODE_LARGE_MAX_K, W > 4096, C*H*W >= 2^31, or B or
+ * C > 65535 (they are grid dimensions) -> CN_ERR_UNSUPPORTED; heat not 16-byte aligned with W % 4 == 0 -> CN_ERR_ALIGN; an output or the workspace NULL
+ * -> CN_ERR_NULL; workspace not 16-byte aligned -> CN_ERR_ALIGN; workspace too small -> CN_ERR_WORKSPACE. */
+#define CN_DECODE_LARGE_MAX_K 1024
+/* ... and where cn_ctdet_decode_f32 / cn_topk_f32 stop, for a caller that routes between the two: */
+#define CN_DECODE_MAX_K 128
+size_t cn_ctdet_decode_large_workspace_bytes(int B, int C, int H, int W, int K);
+int cn_ctdet_decode_large_f32(const float *heat, const float *wh, const float *reg,
+                              int B, int C, int H, int W, int K, int cat_spec_wh,
+                              int apply_sigmoid, float *dets, int32_t *inds,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int cn_topk_large_f32(const float *heat, int B, int C, int H, int W, int K, int apply_sigmoid,
+                      float *scores, int32_t *inds, int32_t *clses, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* The gather-only ctdet heads at the decoded centres (cn_heads_at.hip).  ctdet_decode reads `wh` and `reg`
  * only at the K winning cells of an image (decode.py:472-486), so a caller that does not need the dense
  * maps runs the fused heads for `hm` alone, cn_topk_f32 on it (with the logistic and the peak test:

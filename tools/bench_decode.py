@@ -38,6 +38,69 @@ def heat_map(kind):
     return x.to(dev)
 
 
+def large_k(out_path):
+    """LARGE_K=1: the large-K form (cn_ctdet_decode_large_f32) at K = 128, 256, 512 and 1024 beside the one-launch form
+    at K = 128, on the three map kinds, in one run; logits in, the logistic fused; median (minimum) of 5 rounds of
+    20 calls between two events.  Writes ``out_path`` (OUT=..., by default profiles/decode_large_k.txt) and ends."""
+    lines = ["ctdet decode on (%d, %d, %d, %d) logits, the logistic fused: the large-K form (two launches, "
+             "cn_ctdet_decode_large_f32) beside the one-launch form (cn_ctdet_decode_f32, owned workspace); "
+             "median (minimum) of 5 rounds of 20 calls, events" % (B, C, H, W),
+             "device: %s, %s, %d CUs" % (torch.cuda.get_device_name(0),
+                                         getattr(torch.cuda.get_device_properties(0), "gcnArchName", "?"),
+                                         torch.cuda.get_device_properties(0).multi_processor_count)]
+
+    def timed(call, rounds=5, iters=20):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(rounds):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(iters):
+                call()
+            e.record()
+            torch.cuda.synchronize()
+            ms.append(s.elapsed_time(e) / iters)
+        ms.sort()
+        return ms[len(ms) // 2], ms[0]
+
+    for kind in ("iid", "net", "floor"):
+        x = heat_map(kind).contiguous()
+        rows = {}
+        for form, k in (("one launch", 128), ("large", 128), ("large", 256), ("large", 512), ("large", 1024)):
+            large = form == "large"
+            query = lib.cn_ctdet_decode_large_workspace_bytes if large else lib.cn_ctdet_decode_workspace_bytes
+            entry = lib.cn_ctdet_decode_large_f32 if large else lib.cn_ctdet_decode_f32
+            nb = query(B, C, H, W, k)
+            w = torch.zeros(nb, device=dev, dtype=torch.uint8)
+            d = torch.empty((B, k, 6), device=dev)
+            i = torch.empty((B, k), device=dev, dtype=torch.int32)
+
+            def call():
+                rc = entry(native.ptr(x), native.ptr(wh), native.ptr(reg), B, C, H, W, k, 0, SIG | CLEAN,
+                           native.ptr(d), native.ptr(i), native.ptr(w), nb, native.stream_ptr())
+                assert rc == 0, rc
+            med, low = timed(call)
+            rows[(form, k)] = d.clone()
+            lines.append("%-5s  %-10s  K = %4d   %8.3f ms (%8.3f)   workspace %6.1f MB" % (
+                kind, form, k, med, low, nb / 1e6))
+        same = torch.equal(rows[("one launch", 128)], rows[("large", 128)]) and all(
+            torch.equal(rows[("large", k)][:, :128], rows[("large", 128)]) for k in (256, 512, 1024))
+        lines.append("%-5s  K = 128 rows of both forms, and the first 128 rows at every K, are the same bits: %s" % (
+            kind, same))
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(text)
+
+
+if os.environ.get("LARGE_K") == "1":
+    large_k(os.environ.get("OUT", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                "profiles", "decode_large_k.txt")))
+    sys.exit(0)
+
 KIND = os.environ.get("HEAT", "iid")
 logits = heat_map(KIND).contiguous()
 # the reference-contract entry: ctdet_decode(heat) takes POST-sigmoid maps (models/decode.py:464).  (Round 4's
